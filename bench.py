@@ -17,7 +17,11 @@ schedule, packed weights) are in HBM before the timed region starts.
                    GLOBAL env batch of 48 is sharded contiguously, 48/N items per rank; value = inner iterations over
                    the global 48-image batch per second.
 
-Prints ONE JSON line on rank 0 (fields: see the contract in the task statement) including
+Prints ONE JSON line on rank 0: metric, value, unit, higher_is_better, dtype, ms_per_step (and the workload's config).
+A plain run does only that: set-up, --warmup episodes, the --steps timed episodes, the line.
+  --dump-outputs DIR  after the timed steps, rank 0 writes what its last timed step computed as DIR/<name>.npy (float32,
+                      under 64 MB; see dump_outputs).  Inputs come from fixed seeds: the same arguments give the same inputs.
+  --full              also runs the legs below after the timed region (each can still be left out by its --no-* option):
   roofline     MFMA roofline of the dominant kernel of the DEFAULT convolution family (conv_mode 0: fp32 arithmetic like the
                reference's, conv3x3_wino8_f32_kernel), measured with HIP events around whole production forwards;
   cpu_baseline the CPU oracle timed on the host cores on a bounded sample of the same workload (N=1 only);
@@ -79,7 +83,14 @@ def main():
                     help="pnpx_ctx_set_option on the denoiser context (A/B experiments, e.g. fuse_up=0)")
     ap.add_argument("--selftest-cpu", action="store_true",
                     help="launch / collective plumbing only: gloo + a CPU stub solver, NOT a measurement (tests/)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the roofline (with package power sampled over the timed region), "
+                         "batch table, fast mode and CPU baseline legs; off by default")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last timed step computed as DIR/<name>.npy (float32)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         raise SystemExit(self_launch(args.gpus))      # one rank per GPU; rank 0 of the child job prints the JSON line
@@ -133,7 +144,7 @@ def main():
     torch.cuda.synchronize()
     D.barrier()
     torch.cuda.synchronize()
-    sampler = PowerSampler() if rank == 0 else None          # host thread reading the SMU telemetry, no GPU work
+    sampler = PowerSampler() if rank == 0 and args.full else None   # host thread reading the SMU telemetry, no GPU work
     t0 = time.perf_counter()
     for _ in range(args.steps):
         rewards = episode()
@@ -146,6 +157,8 @@ def main():
     iters = N_POLICY_STEPS * ACTION_PACK * args.steps
     value = (1 if strong else world) * iters / elapsed      # iterations over a 48-image batch per second, whole job
     den.context(dev).status()                                # half-split range guard: raises if any call overflowed
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, env, rewards)
     final_psnr_gain = float(torch.stack(rewards).sum(0).mean().item())
 
     out = {
@@ -179,7 +192,7 @@ def main():
     if share_gpu:
         out["NOT_A_MEASUREMENT"] = f"PNPX_BENCH_SHARE_GPU: {world} ranks time-share device 0 over gloo (plumbing test)"
 
-    if rank == 0 and not args.no_roofline:
+    if rank == 0 and args.full and not args.no_roofline:
         # on the images and noise levels the episode ended with (real operand statistics: the package is power-capped
         # and MFMA power follows operand bit activity)
         out["roofline"] = roofline(den, dev, env.state["output"].detach().clone(), actions[-1]["sigma_d"][:, -1].contiguous())
@@ -188,15 +201,15 @@ def main():
             # the same peak at the clock the power cap actually allowed during the timed region (nominal 2400 MHz)
             peak_at_clk = out["roofline"]["peak"] * power["gfx_clk_mhz_avg"] / 2400.0
             out["roofline"]["frac_of_peak_at_measured_clock"] = out["roofline"]["achieved"] / peak_at_clk
-    if rank == 0 and world == 1 and not args.no_batch_table:
+    if rank == 0 and world == 1 and args.full and not args.no_batch_table:
         out["batch_table"] = batch_table(solver, dev, H, W, args.ratio)
-    if rank == 0 and world == 1 and not args.no_fast_mode and den.context(dev).get_option("conv_mode") == 0:
+    if rank == 0 and world == 1 and args.full and not args.no_fast_mode and den.context(dev).get_option("conv_mode") == 0:
         out["fast_mode"] = fast_mode(params, data, actions, dev, B, H, W, args.steps, args.warmup, den,
                                      None if args.no_batch_table else args.ratio)
         # the same metric in the opt-in half-split mode, surfaced beside `value` (NOT the headline: narrower than fp32)
         out["value_fast_mode"] = out["fast_mode"]["value"]
         out["ms_per_step_fast_mode"] = out["fast_mode"]["ms_per_step"]
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         out["cpu_baseline"], out["parity_rel_l2_vs_cpu"] = cpu_baseline(params, solver, dev, args, value)
         out["speedup_vs_cpu"] = out["value"] / out["cpu_baseline"]["value"]
     if rank == 0:
@@ -223,6 +236,31 @@ def make_episode(env, data, actions, exchange):
         return rewards
 
     return episode
+
+
+DUMP_BYTES = 60 * 10**6        # array data of one dump: below 64 MB with the .npy headers, in either unit
+
+
+def dump_outputs(path, env, rewards):
+    """--dump-outputs: what the last timed episode handed its caller, as float32 DIR/<name>.npy, DUMP_BYTES at most in all:
+      rewards       [6, n_global, 1]      the PSNR reward of every env step (as exchanged, every rank's items)
+      output        [B, 1, H, W]          the reconstructed images after the last env step (this rank's items)
+      solver_state  [b, 3, H, W, 2]       the ADMM variables x | z | u after the last env step (complex as the last axis)
+    Written in this order; an array that does not fit in what is left of the budget keeps a fixed, seeded sample of its
+    items (axis 0, in ascending order; at the default 48 x 256^2: all 48 images and 30 of the 48 solver states)."""
+    os.makedirs(path, exist_ok=True)
+    arrays = (("rewards", torch.stack(rewards)), ("output", env.state["output"]), ("solver_state", env.state["solver"]))
+    left = DUMP_BYTES
+    for name, a in arrays:
+        a = a.detach().float()
+        per_item = a[0].numel() * 4
+        n = min(a.shape[0], left // per_item)
+        if n < a.shape[0]:
+            keep = np.sort(np.random.RandomState(0).choice(a.shape[0], n, replace=False))
+            a = a[torch.from_numpy(keep).to(a.device)]
+        a = a.cpu().numpy()
+        np.save(os.path.join(path, name + ".npy"), a)
+        left -= a.nbytes
 
 
 def free_port():

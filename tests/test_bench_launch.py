@@ -61,3 +61,13 @@ def test_bench_self_launches_eight_ranks_strong_uneven():
     assert eight["collectives_per_env_step"] == 1.0
     one = _run("--gpus", "1", "--batch", "36")
     assert abs(one["reward_sum"] - eight["reward_sum"]) < 1e-4 * abs(one["reward_sum"])
+
+
+def test_bench_options_full_and_dump_outputs():
+    """The secondary legs sit behind --full and the outputs can be dumped; a zero-step run (no ms_per_step) is refused."""
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], capture_output=True, text=True, timeout=300,
+                       cwd=ROOT)
+    assert r.returncode == 0 and "--full" in r.stdout and "--dump-outputs" in r.stdout
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "0"], capture_output=True, text=True,
+                       timeout=300, cwd=ROOT)
+    assert r.returncode == 2 and "--steps" in r.stderr

@@ -13,7 +13,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def test_bench_n1_roofline_fits_in_the_step():
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--no-cpu-baseline",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--full", "--no-cpu-baseline",
            "--no-batch-table"]
     r = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
@@ -39,3 +39,41 @@ def test_bench_n1_roofline_fits_in_the_step():
     fr = d["fast_mode"]["roofline"]
     assert fr["executed_mfma_flops_per_forward"] == 3 * fr["flops_per_forward"]
     assert 30 * fr["flops_per_forward"] / (d["fast_mode"]["ms_per_step"] * 1e-3) / 1e12 <= fr["peak"]
+
+
+def _plain_run(dump, steps, warmup):
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", str(steps), "--warmup", str(warmup),
+           "--dump-outputs", str(dump)]
+    r = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, r.stdout[-2000:]
+    return json.loads(lines[0])
+
+
+def test_bench_plain_run_is_lean_and_dumps_its_outputs(tmp_path):
+    """Without --full the line carries the headline fields and none of the secondary legs; --dump-outputs writes what the
+    last timed episode computed, and since every episode starts from the same seeded inputs, that does not depend on how many
+    episodes ran before it."""
+    import numpy as np
+    d = _plain_run(tmp_path / "a", steps=2, warmup=1)
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in d, k
+    assert d["steps"] == 2 and d["warmup"] == 1 and d["unit"] == "iters/s" and d["higher_is_better"] is True
+    assert d["dtype"].startswith("f32 (")
+    assert abs(d["value"] - 30 / (d["ms_per_step"] * 1e-3)) < 1e-6 * d["value"]
+    assert not {"roofline", "batch_table", "fast_mode", "cpu_baseline"} & set(d)
+    a = {p.stem: np.load(p) for p in (tmp_path / "a").glob("*.npy")}
+    assert set(a) == {"rewards", "output", "solver_state"}
+    assert a["rewards"].shape == (6, 48, 1) and a["output"].shape == (48, 1, 256, 256)
+    assert a["solver_state"].shape[1:] == (3, 256, 256, 2) and 0 < a["solver_state"].shape[0] <= 48
+    assert sum(v.nbytes for v in a.values()) < 64e6
+    for v in a.values():
+        assert v.dtype == np.float32 and np.isfinite(v).all()
+    # the rewards are the ones the line's PSNR gain was computed from
+    assert abs(float(a["rewards"].sum(0).mean()) - d["psnr_gain_db_random_init_denoiser"]) < 1e-4
+    _plain_run(tmp_path / "b", steps=1, warmup=0)
+    b = {p.stem: np.load(p) for p in (tmp_path / "b").glob("*.npy")}
+    for k, v in a.items():
+        assert b[k].shape == v.shape
+        assert np.linalg.norm(b[k] - v) <= 1e-6 * np.linalg.norm(v), k

@@ -8,7 +8,7 @@ O=$GRAFT_REPO_ROOT/gpurun_out/prof_r6
 mkdir -p $O
 WHAT=${1:-all}
 R="rocprofv3 --kernel-trace"
-BOPT="--steps 2 --warmup 1 --no-cpu-baseline --no-batch-table --no-fast-mode"
+BOPT="--steps 2 --warmup 1 --full --no-cpu-baseline --no-batch-table --no-fast-mode"
 if [ $WHAT = conv ] || [ $WHAT = all ]; then
   # the headline leg (default family: fp32 Winograd, two launch chains) ...
   $R --stats -d $O/bench -o bench -- python bench.py $BOPT > $O/bench.log 2>&1
