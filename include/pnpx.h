@@ -329,6 +329,15 @@ int pnpx_csmri_redadmm_backward(pnpx_ctx* ctx, const float* y0, const uint8_t* m
                                 const float* grad_vars_out, float* grad_vars_in, float* grad_sigma_d, float* grad_mu,
                                 float* grad_lamda, float* work, int B, int H, int W, int T, unsigned long long ticket,
                                 void* stream);
+/* AMPSolver_CSMRI.forward (tasks/csmri/solver.py:211-250), inference only.  vars [B,2,H,W,2] = cat(x,z); sigma_d [B,T]
+ * (row stride param_stride); probe [T,B,1,H,W] = the reference's torch.randn_like(r) draw of each iteration (:237).
+ * The reference calls two undefined names; this entry runs its loop with them supplied: self.prox_fun (:238) is
+ * self.prox_mapping (the context's denoiser), and transforms.complex_norm(z) (:230) is, per item, the square root of the
+ * sum of z^2 over its [1,H,W,2] entries.  eps = max(r) / 1000 + 1e-8 is taken over all B items of the call.  Both
+ * denoiser evaluations of an iteration run as one denoiser call over 2B items; eps stays on the device (capturable). */
+int pnpx_csmri_amp(pnpx_ctx* ctx, const float* vars_in, float* vars_out, const float* y0, const uint8_t* mask,
+                   const float* sigma_d, const float* probe, int param_stride, int B, int H, int W, int T,
+                   void* stream);
 /* IADMMSolver_PR.forward (tasks/pr/solver.py:37-76).
  * vars [B,3,H,W,2]; y0 [B,S,H,W]; mask [B,S,H,W,2]. */
 int pnpx_pr_iadmm(pnpx_ctx* ctx, const float* vars_in, float* vars_out, const float* y0,

@@ -74,6 +74,7 @@ _SIGNATURES = {
     "pnpx_csmri_hqs_backward": (C.c_int, [c_void_p, _P, _P, _P, _P, C.c_int, _P, _P, _P, _P, _P, _P] + [C.c_int] * 4 +
                                 [C.c_ulonglong, c_void_p]),
     "pnpx_csmri_hqs": (C.c_int, [c_void_p, _P, _P, _P, _P, _P, _P] + [C.c_int] * 5 + [c_void_p]),
+    "pnpx_csmri_amp": (C.c_int, [c_void_p, _P, _P, _P, _P, _P, _P] + [C.c_int] * 5 + [c_void_p]),
     "pnpx_csmri_pg_train": (C.c_int, [c_void_p, _P, _P, _P, _P, _P, _P] + [C.c_int] * 5 +
                             [_P, C.POINTER(C.c_ulonglong), c_void_p]),
     "pnpx_csmri_pg_backward": (C.c_int, [c_void_p, _P, _P, _P, _P, C.c_int, _P, _P, _P, _P, _P, _P] + [C.c_int] * 4 +

@@ -1098,3 +1098,238 @@ extern "C" int pnpx_csmri_redadmm_backward(pnpx_ctx* ctx, const float* y0, const
     return PNPX_OK;
   });
 }
+
+// ------------------------------------------------------------------------------------------------ AMP (inference only)
+// AMPSolver_CSMRI.forward (tasks/csmri/solver.py:211-250) with its two undefined names supplied: prox_fun = prox_mapping
+// and complex_norm(z)[b] = sqrt(sum of z[b]^2 over its [1,H,W,2] entries).  Per iteration, with the state (x, z):
+//   r = Re(x + F^-1 z);  s = ||z|| / sqrt(HW) * sigma_d[:, i];  x' = D(r, s);  eps = max(r) / 1000 + 1e-8 (over the batch)
+//   div = sum(delta_i * (D(r + eps delta_i, s) - x')) / eps;  z' = (mask ? y0 - F x' : 0) + (z * div) / M
+// Both denoiser evaluations are ONE call over 2B items (d = [r ; r + eps delta_i], sigma = [s ; s]): the same convolution
+// plan, the same K-split class for both halves, so D(r + eps delta) - D(r) is a difference of the same arithmetic.
+// Kernel sequence of an iteration: max partials of r -> probe finish (eps, sigmas, second half) -> denoiser (2B) ->
+// forward row pass of r2c(x') (load functor also emits delta * (x'' - x')) -> per-item sums -> column pass (forward FFT,
+// k-space update of z, inverse FFT; its |z'|^2 terms give the next norm) -> inverse row pass (store functor emits r).
+// eps stays on the device: no host read, no synchronisation inside the loop.
+namespace pnpx {
+namespace {
+
+constexpr int AMP_SLAB = 1024;   // max-partial workgroups (the finish kernel reduces the slab in a fixed order)
+
+struct AmpScratch {
+  float2* k;     // [B,H,W] complex row / column pass intermediate
+  float* d;      // [2B,HW] denoiser input: r, then r + eps * delta
+  float* xr;     // [2B,HW] denoiser output: x', then x''
+  float* c;      // [B,HW] per-pixel terms of the divergence, then of ||z'||^2
+  float* slab;   // [AMP_SLAB] max partials of r
+  float *zn2, *div, *M, *sig, *eps;   // [B], [B], [B], [2B], [1]
+};
+
+int get_amp_scratch(pnpx_ctx* ctx, int B, int H, int W, AmpScratch* S) {
+  const size_t n = (size_t)H * W * B;
+  void* p;
+  PNPX_TRY(ctx_scratch(ctx, n * 28 + sizeof(float) * (AMP_SLAB + 5 * (size_t)B + 64), &p));
+  S->k = static_cast<float2*>(p);
+  S->d = reinterpret_cast<float*>(S->k + n);
+  S->xr = S->d + 2 * n;
+  S->c = S->xr + 2 * n;
+  S->slab = S->c + n;
+  S->zn2 = S->slab + AMP_SLAB;
+  S->div = S->zn2 + B;
+  S->M = S->div + B;
+  S->sig = S->M + B;
+  S->eps = S->sig + 2 * B;
+  return PNPX_OK;
+}
+
+// M[b] = number of sampled k-space points of item b (integer count, exact)
+__global__ void __launch_bounds__(256) mask_count_kernel(const uint8_t* __restrict__ mask, float* __restrict__ M, int HW) {
+  __shared__ int sh[256];
+  const uint8_t* p = mask + (size_t)blockIdx.x * HW;
+  int a = 0;
+  for (int i = threadIdx.x; i < HW; i += 256) a += p[i] ? 1 : 0;
+  sh[threadIdx.x] = a;
+  __syncthreads();
+  for (int st = 128; st > 0; st >>= 1) {
+    if ((int)threadIdx.x < st) sh[threadIdx.x] += sh[threadIdx.x + st];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) M[blockIdx.x] = (float)sh[0];
+}
+// c = |z|^2 per pixel of a complex slot
+__global__ void sqnorm_kernel(const float2* __restrict__ z, size_t istride, float* __restrict__ c, int HW, int B) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= (size_t)HW * B) return;
+  const size_t b = i / HW, r = i - b * HW;
+  const float2 v = z[b * istride + r];
+  c[i] = addr(mulr(v.x, v.x), mulr(v.y, v.y));
+}
+// slab[blockIdx.x] = max over a grid-strided share of r (max is exact: the result does not depend on the order)
+__global__ void __launch_bounds__(256) max_partial_kernel(const float* __restrict__ r, size_t n, float* __restrict__ slab) {
+  __shared__ float sh[256];
+  float a = -INFINITY;
+  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) a = fmaxf(a, r[i]);
+  sh[threadIdx.x] = a;
+  __syncthreads();
+  for (int st = 128; st > 0; st >>= 1) {
+    if ((int)threadIdx.x < st) sh[threadIdx.x] = fmaxf(sh[threadIdx.x], sh[threadIdx.x + st]);
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) slab[blockIdx.x] = sh[0];
+}
+// Probe finish: every workgroup reduces the slab to eps = max(r) / 1000 + 1e-8 (tasks/csmri/solver.py:236) and writes its
+// share of the second half d[n + i] = r[i] + delta[i] * eps (:238); workgroup 0 also stores eps and the 2B noise levels
+// sig[b] = sig[B + b] = (sqrt(||z_b||^2) / sqrt(N)) * sigma_d[b, i] (:230-231).
+__global__ void __launch_bounds__(256) amp_probe_kernel(float* __restrict__ d, const float* __restrict__ delta, size_t n,
+                                                        const float* __restrict__ slab, int nslab,
+                                                        const float* __restrict__ zn2, const float* __restrict__ sd,
+                                                        int stride, int B, int HW, float* __restrict__ sig,
+                                                        float* __restrict__ eps_out) {
+  __shared__ float sh[256];
+  float a = -INFINITY;
+  for (int j = threadIdx.x; j < nslab; j += 256) a = fmaxf(a, slab[j]);
+  sh[threadIdx.x] = a;
+  __syncthreads();
+  for (int st = 128; st > 0; st >>= 1) {
+    if ((int)threadIdx.x < st) sh[threadIdx.x] = fmaxf(sh[threadIdx.x], sh[threadIdx.x + st]);
+    __syncthreads();
+  }
+  const float eps = addr(divr(sh[0], 1000.f), 1e-8f);
+  if (blockIdx.x == 0) {
+    if (threadIdx.x == 0) eps_out[0] = eps;
+    const float sqn = __fsqrt_rn((float)HW);
+    for (int b = threadIdx.x; b < B; b += 256) {
+      const float s = mulr(divr(__fsqrt_rn(zn2[b]), sqn), sd[(size_t)b * stride]);
+      sig[b] = s;
+      sig[B + b] = s;
+    }
+  }
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) d[n + i] = addr(d[i], mulr(delta[i], eps));
+}
+
+struct StoreAmpR {   // r = Re(x + F^-1 z) -> first half of the denoiser input (x: the input state's slot, or the last x')
+  const float2* xc;  // x slot of the input state (first iteration) ...
+  size_t istride;
+  const float* xr;   // ... or the previous prox output [B,HW]
+  float* d;
+  int W, HW;
+  __device__ void operator()(int b, int y, int x, float2 v) const {
+    const size_t o = (size_t)b * HW + (size_t)y * W + x;
+    const float xv = xc ? xc[(size_t)b * istride + (size_t)y * W + x].x : xr[o];
+    d[o] = addr(xv, v.x);
+  }
+};
+struct LoadAmpX {    // r2c(x') into the forward row pass; emits delta * (x'' - x') and, on the last iteration, x = r2c(x')
+  const float* xr;   // [2B,HW]: x' then x''
+  const float* delta;
+  float* c;
+  Slot xo;
+  size_t n;
+  int write_x;
+  __device__ float2 operator()(int b, int y, int x) const {
+    const size_t o = (size_t)b * xo.HW + (size_t)y * xo.W + x;
+    const float x1 = xr[o];
+    c[o] = mulr(delta[o], subr(xr[n + o], x1));
+    if (write_x) xo.at(b, y, x) = make_float2(x1, 0.f);
+    return make_float2(x1, 0.f);
+  }
+};
+// z' = temp + o with temp = y0 - k, temp[~mask] = 0 and o = z * div / M, div = sum / eps   (tasks/csmri/solver.py:239-246).
+// Reads the old z and writes z' at the same pixel (the output slot may be the input slot); emits |z'|^2 per pixel.
+struct MidAmp {
+  const float2* y0;
+  const uint8_t* mask;
+  CSlot zi;
+  Slot zo;
+  const float *dsum, *eps, *M;
+  float* c;
+  __device__ float2 operator()(int b, int ky, int kx, float2 k) const {
+    const size_t o = (size_t)b * zo.HW + (size_t)ky * zo.W + kx;
+    const float dv = divr(dsum[b], eps[0]), m = M[b];
+    const float2 zz = zi.at(b, ky, kx);
+    float2 t = make_float2(0.f, 0.f);
+    if (mask[o]) {
+      const float2 y = y0[o];
+      t = make_float2(subr(y.x, k.x), subr(y.y, k.y));
+    }
+    const float2 zn = make_float2(addr(t.x, divr(mulr(zz.x, dv), m)), addr(t.y, divr(mulr(zz.y, dv), m)));
+    zo.at(b, ky, kx) = zn;
+    c[o] = addr(mulr(zn.x, zn.x), mulr(zn.y, zn.y));
+    return zn;
+  }
+};
+struct StoreAmpK {   // the last iteration: the same update as the store of a forward column pass (no inverse transform)
+  MidAmp m;
+  __device__ void operator()(int b, int y, int x, float2 k) const { (void)m(b, y, x, k); }
+};
+
+static int amp_forward(pnpx_ctx* ctx, const float* vars_in, float* vars_out, const float* y0, const uint8_t* mask,
+                       const float* sigma_d, const float* probe, int param_stride, int B, int H, int W, int T,
+                       hipStream_t s) {
+  PNPX_TRY(check_common(vars_in, vars_out, y0, mask, sigma_d, B, H, W, T, param_stride));
+  if (!probe && T > 0) {
+    set_error("csmri_amp: probe is null");
+    return PNPX_ERR_ARG;
+  }
+  const int HW = H * W;
+  const size_t is = 2 * (size_t)HW, n = (size_t)B * HW;
+  FftPlan2D P;
+  PNPX_TRY(make_fft_plan(ctx, B, H, W, true, &P));
+  if (T == 0) {
+    PNPX_HIP(hipMemcpyAsync(vars_out, vars_in, sizeof(float2) * is * B, hipMemcpyDeviceToDevice, s));
+    return PNPX_OK;
+  }
+  AmpScratch S;
+  PNPX_TRY(get_amp_scratch(ctx, B, H, W, &S));
+  const float2* vin = reinterpret_cast<const float2*>(vars_in);
+  float2* vout = reinterpret_cast<float2*>(vars_out);
+  const float2* y0c = reinterpret_cast<const float2*>(y0);
+  const int nslab = (int)std::min<size_t>(AMP_SLAB, (n + 4095) / 4096);
+  StoreC kst{S.k, H, W};
+  LoadC kld{S.k, H, W};
+  Slot xo{vout, is, W, HW}, zo{vout + HW, is, W, HW};
+  // M, ||z0||^2 and r of the first iteration (inverse transform of z0 in the order of pnpx_fft2: rows, then columns)
+  hipLaunchKernelGGL(mask_count_kernel, dim3(B), dim3(256), 0, s, mask, S.M, HW);
+  PNPX_LAUNCH_CHECK();
+  hipLaunchKernelGGL(sqnorm_kernel, g1(n), dim3(256), 0, s, vin + HW, is, S.c, HW, B);
+  PNPX_LAUNCH_CHECK();
+  hipLaunchKernelGGL(item_sum_kernel, dim3(B), dim3(256), 0, s, S.c, S.zn2, HW);
+  PNPX_LAUNCH_CHECK();
+  PNPX_TRY((launch_rows<true>(P, LoadSlot{CSlot{vin + HW, is, W, HW}}, kst, s)));
+  PNPX_TRY((launch_cols<true, false>(P, kld, MidNone(), StoreAmpR{vin, is, nullptr, S.d, W, HW}, s)));
+  for (int i = 0; i < T; ++i) {
+    const float* dl = probe + (size_t)i * n;
+    hipLaunchKernelGGL(max_partial_kernel, dim3(nslab), dim3(256), 0, s, S.d, n, S.slab);
+    PNPX_LAUNCH_CHECK();
+    hipLaunchKernelGGL(amp_probe_kernel, g1(n), dim3(256), 0, s, S.d, dl, n, S.slab, nslab, S.zn2, sigma_d + i,
+                       param_stride, B, HW, S.sig, S.eps);
+    PNPX_LAUNCH_CHECK();
+    PNPX_TRY(unet_denoise(ctx, S.d, S.sig, 1, S.xr, nullptr, 2 * B, H, W, s, nullptr));
+    PNPX_TRY((launch_rows<false>(P, LoadAmpX{S.xr, dl, S.c, xo, n, i == T - 1}, kst, s)));
+    hipLaunchKernelGGL(item_sum_kernel, dim3(B), dim3(256), 0, s, S.c, S.div, HW);
+    PNPX_LAUNCH_CHECK();
+    const MidAmp mid{y0c, mask, CSlot{(i == 0 ? vin : vout) + HW, is, W, HW}, zo, S.div, S.eps, S.M, S.c};
+    if (i == T - 1) {
+      PNPX_TRY((launch_cols<false, false>(P, kld, MidNone(), StoreAmpK{mid}, s)));
+      break;
+    }
+    PNPX_TRY((launch_cols<false, true>(P, kld, mid, kst, s)));
+    hipLaunchKernelGGL(item_sum_kernel, dim3(B), dim3(256), 0, s, S.c, S.zn2, HW);
+    PNPX_LAUNCH_CHECK();
+    PNPX_TRY((launch_rows<true>(P, kld, StoreAmpR{nullptr, 0, S.xr, S.d, W, HW}, s)));
+  }
+  return PNPX_OK;
+}
+
+}  // namespace
+}  // namespace pnpx
+
+extern "C" int pnpx_csmri_amp(pnpx_ctx* ctx, const float* vars_in, float* vars_out, const float* y0,
+                              const uint8_t* mask, const float* sigma_d, const float* probe, int param_stride, int B,
+                              int H, int W, int T, void* stream) {
+  LOCK_CTX(ctx);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  return pnpx::guarded(ctx, s, [&]() -> int {
+    return amp_forward(ctx, vars_in, vars_out, y0, mask, sigma_d, probe, param_stride, B, H, W, T, s);
+  });
+}

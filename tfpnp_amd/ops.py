@@ -540,6 +540,33 @@ def csmri_hqs(ctx, variables, y0, mask, sigma_d, mu, iter_num=None):
     return _csmri_common("pnpx_csmri_hqs", 2, ctx, variables, y0, mask, (sigma_d, mu), iter_num)
 
 
+def csmri_amp(ctx, variables, y0, mask, sigma_d, probe, iter_num=None):
+    """pnpx_csmri_amp: AMPSolver_CSMRI.forward (tasks/csmri/solver.py:211-250, prox_fun = prox_mapping, complex_norm = the
+    per-item L2 norm).  variables [B,2,H,W,2]; sigma_d [B,T]; probe [>= iter_num, B, 1, H, W] = the Monte-Carlo probe
+    delta of each iteration (the reference's torch.randn_like(r))."""
+    v = _vars(variables, 2, True)
+    B, _, H, W, _ = v.shape
+    ps, T = _params(B, sigma_d)
+    if iter_num is not None:
+        if iter_num > T:
+            raise PnpxError(f"iter_num {iter_num} exceeds the {T} hyper-parameter columns provided")
+        T = iter_num
+    d = _f32(probe, "probe")
+    if d.dim() != 5 or d.shape[0] < T or tuple(d.shape[1:]) != (B, 1, H, W):
+        raise PnpxError(f"probe must be [{T}, {B}, 1, {H}, {W}], got {tuple(d.shape)}")
+    y0 = _f32(y0, "y0")
+    m = _mask_u8(mask)
+    if y0.numel() != B * H * W * 2 or m.numel() != B * H * W:
+        raise PnpxError("y0/mask do not match the state's [B,H,W]")
+    out = torch.empty_like(v)
+    if B == 0:
+        return out
+    with torch.cuda.device(v.device):
+        check(_lib.lib().pnpx_csmri_amp(ctx.handle, _p(v), _p(out), _p(y0), _p(m), _p(ps[0]), _p(d), ps[0].shape[1], B, H,
+                                        W, T, _stream(v)))
+    return out
+
+
 def csmri_pg(ctx, variables, y0, mask, sigma_d, tau, iter_num=None):
     return _csmri_common("pnpx_csmri_pg", 1, ctx, variables, y0, mask, (sigma_d, tau), iter_num)
 

@@ -124,7 +124,7 @@ class REDADMMSolver(PnPSolver):
 
 
 class AMPSolver(PnPSolver):
-    """base.py:212-232 -- (x, z) = (0, y0).  State packing only: the reference's AMPSolver_CSMRI.forward calls an
-    undefined self.prox_fun (tasks/csmri/solver.py:238) and cannot run, so no AMP loop exists here either."""
+    """base.py:212-232 -- (x, z) = (0, y0); hyper-parameter sigma_d.  The loop is tfpnp_amd/tasks/csmri.py
+    AMPSolver_CSMRI (the reference's, with its two undefined names supplied)."""
     init_vars = ('zero', 'y0')
     hyper_keys = ('sigma_d',)

@@ -382,6 +382,15 @@ def csmri_hqs(variables: Tensor, y0: Tensor, mask: Tensor, sigma_d: Tensor, mu: 
 csmri_hqs.register_fake(_same)
 
 
+@_lib_def("pnpx::csmri_amp", mutates_args=(), device_types="cuda")
+def csmri_amp(variables: Tensor, y0: Tensor, mask: Tensor, sigma_d: Tensor, probe: Tensor, iter_num: int, ctx: int) -> Tensor:
+    """AMPSolver_CSMRI.forward (tasks/csmri/solver.py:211-250, prox_fun = prox_mapping), probe [T,B,1,H,W] given."""
+    return ops.csmri_amp(_ctx(ctx, variables), variables, y0, mask, sigma_d, probe, _it(iter_num))
+
+
+csmri_amp.register_fake(_same)
+
+
 @_lib_def("pnpx::csmri_pg", mutates_args=(), device_types="cuda")
 def csmri_pg(variables: Tensor, y0: Tensor, mask: Tensor, sigma_d: Tensor, tau: Tensor, iter_num: int, ctx: int) -> Tensor:
     """PGSolver_CSMRI.forward (tasks/csmri/solver.py:96-120)."""
@@ -461,5 +470,5 @@ def call(name, *args):
 ALL_OPS = ("unet_denoise", "unet_denoise_preclamp", "unet_denoise_backward", "unet_denoise_train",
            "unet_denoise_backward_ticket", "policy_forward", "fft2", "cdp_forward",
            "cdp_backward", "spi_inverse", "psnr", "radon_forward", "radon_backprojection", "csmri_admm", "csmri_admm_train",
-           "csmri_admm_backward", "csmri_hqs",
+           "csmri_admm_backward", "csmri_hqs", "csmri_amp",
            "csmri_pg", "csmri_apg", "csmri_redadmm", "pr_iadmm", "spi_admm", "ct_iadmm", "ct_pg")
