@@ -353,6 +353,26 @@ int pnpx_pr_iadmm_backward(pnpx_ctx* ctx, const float* y0, const float* mask, co
                            const float* tau, int param_stride, const float* saved, const float* grad_vars_out,
                            float* grad_vars_in, float* grad_sigma_d, float* grad_mu, float* grad_tau, float* work,
                            int B, int S, int H, int W, int T, unsigned long long ticket, void* stream);
+/* PGSolver_PR.forward: proximal gradient on the PR data term.  The reference's own loop (tasks/pr/solver.py:79-112) was pasted
+ * from CS-MRI and raises on any PR input; this entry runs it with the gradient step IADMMSolver_PR.forward computes (:61-68):
+ *   Ax = cdp_forward(x, mask);  r = (|Ax| - y0) / |Ax| * Ax  (no epsilon);  z = x - tau_i * cdp_backward(r, mask);
+ *   x  = real2complex(prox_mapping(complex2real(z), sigma_d_i))
+ * vars [B,1,H,W,2]; y0 [B,S,H,W]; mask [B,S,H,W,2]; sigma_d, tau [B,T] (row stride param_stride).  vars_in may carry an
+ * imaginary part (the first iteration reads it); the imaginary part of vars_out is +0.  T = 0 copies the state. */
+int pnpx_pr_pg(pnpx_ctx* ctx, const float* vars_in, float* vars_out, const float* y0, const float* mask,
+               const float* sigma_d, const float* tau, int param_stride, int B, int S, int H, int W, int T,
+               void* stream);
+/* Training path of PGSolver_PR.forward (same contract): `saved` = (2*S + 2)*T*B*H*W floats (the S k-space images before the
+ * residual as complex, then the denoiser inputs, then Re of the data-term gradient); grads wrt (x, sigma_d, tau), each
+ * hyper-parameter gradient [T][B]; work = 3*B*H*W floats.  The imaginary part of grad_vars_out is not read (the output's
+ * imaginary part is a constant).  ticket as in pnpx_csmri_admm_train. */
+int pnpx_pr_pg_train(pnpx_ctx* ctx, const float* vars_in, float* vars_out, const float* y0, const float* mask,
+                     const float* sigma_d, const float* tau, int param_stride, int B, int S, int H, int W, int T,
+                     float* saved, unsigned long long* ticket, void* stream);
+int pnpx_pr_pg_backward(pnpx_ctx* ctx, const float* y0, const float* mask, const float* sigma_d, const float* tau,
+                        int param_stride, const float* saved, const float* grad_vars_out, float* grad_vars_in,
+                        float* grad_sigma_d, float* grad_tau, float* work, int B, int S, int H, int W, int T,
+                        unsigned long long ticket, void* stream);
 /* ADMMSolver_SPI.forward (tasks/spi/solver.py:17-52).
  * vars [B,3,H,W] real; x0 [B,1,H,W]; Kmap [B,1,H,W] (K/10 broadcast, only [b,0,0,0] is read). */
 int pnpx_spi_admm(pnpx_ctx* ctx, const float* vars_in, float* vars_out, const float* x0,

@@ -95,6 +95,11 @@ _SIGNATURES = {
     "pnpx_pr_iadmm_backward": (C.c_int, [c_void_p, _P, _P, _P, _P, _P, C.c_int, _P, _P, _P, _P, _P, _P, _P] + [C.c_int] * 5 +
                                [C.c_ulonglong, c_void_p]),
     "pnpx_pr_iadmm": (C.c_int, [c_void_p, _P, _P, _P, _P, _P, _P, _P] + [C.c_int] * 6 + [c_void_p]),
+    "pnpx_pr_pg_train": (C.c_int, [c_void_p, _P, _P, _P, _P, _P, _P] + [C.c_int] * 6 +
+                         [_P, C.POINTER(C.c_ulonglong), c_void_p]),
+    "pnpx_pr_pg_backward": (C.c_int, [c_void_p, _P, _P, _P, _P, C.c_int, _P, _P, _P, _P, _P, _P] + [C.c_int] * 5 +
+                            [C.c_ulonglong, c_void_p]),
+    "pnpx_pr_pg": (C.c_int, [c_void_p, _P, _P, _P, _P, _P, _P] + [C.c_int] * 6 + [c_void_p]),
     "pnpx_spi_admm_train": (C.c_int, [c_void_p, _P, _P, _P, _P, _P, _P] + [C.c_int] * 5 +
                             [_P, C.POINTER(C.c_ulonglong), c_void_p]),
     "pnpx_spi_admm_backward": (C.c_int, [c_void_p, _P, _P, _P, _P, C.c_int, _P, _P, _P, _P, _P, _P] + [C.c_int] * 4 +

@@ -240,6 +240,94 @@ __global__ void real_of_diff_kernel(const float2* __restrict__ a, const float2* 
   d[i] = subr(a[b * istride + r].x, c[b * istride + r].x);
 }
 
+// ---- PGSolver_PR (pnpx_pr_pg / _train / _backward): x' = r2c(D(Re(x - tau g(x)))), g = cdp_backward((|Ax| - y0) / |Ax| Ax)
+// Only Re z reaches the denoiser and x is real from the second iteration on, so the loop keeps no complex state: x lives in the
+// denoiser's output plane [B][HW] and the data step is one float per pixel in, one out.
+struct LoadCdpReal {  // complex_mul((x[b], 0), mask[b,s]) from a real plane: the products LoadCdp forms with a zero imaginary part
+  const float* x;      // [B][HW]
+  const float2* mask;  // [B,S,H,W]
+  int S, W, HW;
+  __device__ float2 operator()(int img, int y, int xx) const {
+    const int b = img / S;
+    const size_t r = (size_t)y * W + xx;
+    const float a = x[(size_t)b * HW + r];
+    const float2 m = mask[(size_t)img * HW + r];
+    return make_float2(mulr(a, m.x), mulr(a, m.y));
+  }
+};
+// d = Re x - tau * Re g for one pixel from the summed real part; Re x is element `xes * (b HW + r)` of `x` (xes = 2: the real parts
+// of an interleaved complex state, 1: a real plane).  `gsave` (training forward) keeps Re g.
+__device__ __forceinline__ void pr_pg_step_px(float acc, int S, const float* x, int xes, float* d, float* gsave, float t, size_t i) {
+  const float g = divr(acc, (float)S);
+  d[i] = subr(x[i * xes], mulr(t, g));
+  if (gsave) gsave[i] = g;
+}
+// Accumulator of the grouped inverse row pass (fft_lds.h fft256_rows_group_kernel) for the PG step: the REAL part of
+// conj(mask_s) I_s summed over the S masks in the order and with the operations of cdp_adjoint_px (one float of state per pixel,
+// PrUpdateAcc carries two), then the gradient step.  Per pixel: reads Re x and the S masks, writes d.  Bit-identical to an inverse
+// row pass + pr_pg_step_kernel.
+struct PrPgStepAcc {
+  const float2* mask;  // [B*S][HW]
+  const float* x;      // Re x, element stride xes
+  int xes;
+  float* d;            // [B][HW]
+  float* gsave;        // [B][HW] or NULL
+  const float* tau;
+  int stride, S, W, HW;
+  typedef float State;
+  typedef float2 Pre;
+  __device__ float init() const { return 0.f; }
+  __device__ float2 fetch(int img, int y, int xx) const { return mask[(size_t)img * HW + (size_t)y * W + xx]; }
+  __device__ void add(float& acc, float2 m, float2 a) const {
+    const float my = -m.y;
+    acc = addr(acc, subr(mulr(a.x, m.x), mulr(a.y, my)));
+  }
+  __device__ void finish(float acc, int b, int y, int xx) const {
+    pr_pg_step_px(acc, S, x, xes, d, gsave, tau[(size_t)b * stride], (size_t)b * HW + (size_t)y * W + xx);
+  }
+};
+// the same step after a plain inverse row pass (sizes without the grouped 256-point pass): I = the S image-space fields
+__global__ void pr_pg_step_kernel(const float2* __restrict__ I, const float2* __restrict__ mask, const float* x, int xes,
+                                  float* __restrict__ d, float* __restrict__ gsave, const float* __restrict__ tau, int stride,
+                                  int S, int HW, int B) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= (size_t)HW * B) return;
+  const int b = (int)(i / HW);
+  const size_t r = i - (size_t)b * HW;
+  float acc = 0.f;
+  for (int s = 0; s < S; ++s) {
+    const size_t o = ((size_t)b * S + s) * HW + r;
+    const float2 a = I[o], m = mask[o];
+    const float my = -m.y;
+    acc = addr(acc, subr(mulr(a.x, m.x), mulr(a.y, my)));
+  }
+  pr_pg_step_px(acc, S, x, xes, d, gsave, tau[(size_t)b * stride], i);
+}
+// x = (D(d), 0): the state leaves the loop as a complex image once per call
+__global__ void real_to_complex_kernel(const float* __restrict__ xr, float2* __restrict__ out, size_t n) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) out[i] = make_float2(xr[i], 0.f);
+}
+__global__ void complex_real_part_kernel(const float2* __restrict__ in, float* __restrict__ out, size_t n) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) out[i] = in[i].x;
+}
+// Backward of one PG iteration after the denoiser's VJP gd and the data step's adjoint I' (per (item, s), image domain),
+// J = mean_s conj(mask_s) I'_s:  d/d tau = -<gd, Re g>;  cotangent of x = (gd, 0) - tau J.  An inner iteration's x is real (its
+// imaginary part is the constant 0): only the real part travels on, in `gx`; the first iteration's goes to `gvars` whole.
+__global__ void pr_pg_adjoint_kernel(const float2* __restrict__ I, const float2* __restrict__ mask, const float* __restrict__ gd,
+                                     const float* __restrict__ gsave, const float* __restrict__ tau, int stride, int S, int HW,
+                                     int B, float* __restrict__ gx, float2* __restrict__ gvars, float* __restrict__ c_tau) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= (size_t)HW * B) return;
+  const int b = (int)(i / HW);
+  const float2 J = cdp_adjoint_px(I, mask, b, S, HW, i - (size_t)b * HW);
+  const float t = tau[(size_t)b * stride], e = gd[i];
+  c_tau[i] = -(e * gsave[i]);
+  if (gvars) gvars[i] = make_float2(e - t * J.x, -(t * J.y));
+  else gx[i] = e - t * J.x;
+}
+
 // =================================================================================== SPI
 // spi_inverse for one pixel                                                transforms.py:404-439
 __device__ __forceinline__ float spi_inverse_px(float zt, float K1, float K, float mu) {
@@ -900,6 +988,147 @@ int pnpx_pr_iadmm_backward(pnpx_ctx* ctx, const float* y0, const float* mask, co
       PNPX_TRY(unet_denoise_backward_ticket(ctx, sv_d + (size_t)i * n, sigma_d + i, param_stride, gxr, gd,
                                             grad_sigma_d + (size_t)i * B, B, H, W, s, ticket ? ticket + i : 0));
       hipLaunchKernelGGL(pr_adjoint_finish_kernel, g1(n), dim3(256), 0, s, gd, g, is, HW, B);
+      PNPX_LAUNCH_CHECK();
+    }
+    return PNPX_OK;
+  });
+}
+
+// PGSolver_PR.forward; `saved` != NULL (training path): per iteration w = F(mask_s x) before the residual [T][S n][2] (first: the
+// complex part stays 8-byte aligned for any n), the denoiser input d_i [T][n] and Re g [T][n]  (n = B*H*W); activations parked
+// (ticket + i).
+static int pr_pg_forward(pnpx_ctx* ctx, const float* vars_in, float* vars_out, const float* y0, const float* mask,
+                         const float* sigma_d, const float* tau, int param_stride, int B, int S, int H, int W, int T,
+                         float* saved, unsigned long long* ticket_out, hipStream_t s) {
+  REQUIRE(vars_in && vars_out && y0 && mask && sigma_d && tau && B > 0 && S > 0 && H > 0 && W > 0 && T >= 0 && param_stride >= T,
+          "pnpx_pr_pg: bad argument");
+  if (ticket_out) *ticket_out = 0;
+  const int HW = H * W;
+  const size_t n = (size_t)HW * B;
+  if (T == 0) {
+    PNPX_HIP(hipMemcpyAsync(vars_out, vars_in, sizeof(float2) * n, hipMemcpyDeviceToDevice, s));
+    return PNPX_OK;
+  }
+  void* p;
+  PNPX_TRY(ctx_scratch(ctx, n * S * sizeof(float2) + 2 * n * sizeof(float) + 4096, &p));
+  Carver cv{static_cast<char*>(p)};
+  float2* k = cv.take<float2>(n * S);
+  float* dscr = cv.take<float>(n);
+  float* xr = cv.take<float>(n);
+  FftPlan2D P;
+  PNPX_TRY(make_fft_plan(ctx, B * S, H, W, false, &P));
+  StoreC kst{k, H, W};
+  LoadC kld{k, H, W};
+  const float2* mk = reinterpret_cast<const float2*>(mask);
+  float2* sv_w = reinterpret_cast<float2*>(saved);
+  float* sv_d = saved ? saved + (size_t)T * n * 2 * S : nullptr;
+  float* sv_g = saved ? sv_d + (size_t)T * n : nullptr;
+  for (int i = 0; i < T; ++i) {
+    // x of iteration i: the complex input state on the first pass (its imaginary part enters Re z through the masks), the
+    // previous denoiser output (a real plane) later
+    if (i == 0) {
+      PNPX_TRY((launch_rows<false>(P, LoadCdp{reinterpret_cast<const float2*>(vars_in), (size_t)HW, mk, S, W, HW}, kst, s)));
+    } else {
+      PNPX_TRY((launch_rows<false>(P, LoadCdpReal{xr, mk, S, W, HW}, kst, s)));
+    }
+    if (saved) {
+      PNPX_TRY((launch_cols<false, true>(P, kld, MidPrResidualSave{y0, sv_w + (size_t)i * n * S, W, HW}, kst, s)));
+    } else {
+      PNPX_TRY((launch_cols<false, true>(P, kld, MidPrResidual{y0, W, HW}, kst, s)));
+    }
+    const float* xre = (i == 0) ? vars_in : xr;
+    const int xes = (i == 0) ? 2 : 1;
+    float* d = saved ? sv_d + (size_t)i * n : dscr;
+    float* gs = saved ? sv_g + (size_t)i * n : nullptr;
+    if (P.fast256_rows) {
+      // inverse row pass + real part of the coded-diffraction adjoint + gradient step in one kernel
+      PNPX_TRY((launch_rows_group<true>(P, B, S, kld, PrPgStepAcc{mk, xre, xes, d, gs, tau + i, param_stride, S, W, HW}, s)));
+    } else {
+      PNPX_TRY((launch_rows<true>(P, kld, kst, s)));
+      hipLaunchKernelGGL(pr_pg_step_kernel, g1(n), dim3(256), 0, s, k, mk, xre, xes, d, gs, tau + i, param_stride, S, HW, B);
+      PNPX_LAUNCH_CHECK();
+    }
+    if (saved) {
+      unsigned long long tk = 0;
+      PNPX_TRY(unet_denoise_train(ctx, d, sigma_d + i, param_stride, xr, B, H, W, s, &tk));
+      if (i == 0 && ticket_out) *ticket_out = tk;
+    } else {
+      PNPX_TRY(unet_denoise(ctx, d, sigma_d + i, param_stride, xr, nullptr, B, H, W, s, nullptr));
+    }
+  }
+  // the last denoiser output becomes the state (imaginary part +0)
+  hipLaunchKernelGGL(real_to_complex_kernel, g1(n), dim3(256), 0, s, xr, reinterpret_cast<float2*>(vars_out), n);
+  PNPX_LAUNCH_CHECK();
+  return PNPX_OK;
+}
+
+int pnpx_pr_pg(pnpx_ctx* ctx, const float* vars_in, float* vars_out, const float* y0, const float* mask, const float* sigma_d,
+               const float* tau, int param_stride, int B, int S, int H, int W, int T, void* stream) {
+  LOCK_CTX(ctx);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  return pnpx::guarded(ctx, s, [&]() -> int {
+    return pr_pg_forward(ctx, vars_in, vars_out, y0, mask, sigma_d, tau, param_stride, B, S, H, W, T, nullptr, nullptr, s);
+  });
+}
+
+int pnpx_pr_pg_train(pnpx_ctx* ctx, const float* vars_in, float* vars_out, const float* y0, const float* mask,
+                     const float* sigma_d, const float* tau, int param_stride, int B, int S, int H, int W, int T, float* saved,
+                     unsigned long long* ticket, void* stream) {
+  LOCK_CTX(ctx);
+  REQUIRE((saved || T == 0) && ticket, "pnpx_pr_pg_train: saved / ticket is null");
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  return pnpx::guarded(ctx, s, [&]() -> int {
+    return pr_pg_forward(ctx, vars_in, vars_out, y0, mask, sigma_d, tau, param_stride, B, S, H, W, T, saved, ticket, s);
+  });
+}
+
+// VJP of the T-iteration PR PG map wrt (x, sigma_d, tau), iterations walked in reverse:
+//   forward i:   w_s = F(mask_s x);  g = mean_s conj(mask_s) F^-1((|w_s| - y0_s) / |w_s| w_s);  d = Re(x - tau g);  x' = r2c(D(d, sigma_i))
+//   backward i:  gd = D^T Re(gx');  d/d tau = -<gd, Re g>;  e = (gd, 0);  I'_s = F^-1 J_s^T F(mask_s e) with the saved w_s;
+//                gx = e - tau mean_s conj(mask_s) I'_s  (pr_pg_adjoint_kernel)
+// The imaginary part of grad_vars_out is never read: the output's imaginary part is a constant.
+int pnpx_pr_pg_backward(pnpx_ctx* ctx, const float* y0, const float* mask, const float* sigma_d, const float* tau,
+                        int param_stride, const float* saved, const float* grad_vars_out, float* grad_vars_in,
+                        float* grad_sigma_d, float* grad_tau, float* work, int B, int S, int H, int W, int T,
+                        unsigned long long ticket, void* stream) {
+  LOCK_CTX(ctx);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  return pnpx::guarded(ctx, s, [&]() -> int {
+    REQUIRE(y0 && mask && sigma_d && tau && grad_vars_out && grad_vars_in && B > 0 && S > 0 && H > 0 && W > 0 && T >= 0 &&
+                param_stride >= T && (T == 0 || (saved && grad_sigma_d && grad_tau && work)),
+            "pnpx_pr_pg_backward: bad argument");
+    const int HW = H * W;
+    const size_t n = (size_t)HW * B;
+    if (T == 0) {
+      PNPX_HIP(hipMemcpyAsync(grad_vars_in, grad_vars_out, sizeof(float2) * n, hipMemcpyDeviceToDevice, s));
+      return PNPX_OK;
+    }
+    FftPlan2D P;
+    PNPX_TRY(make_fft_plan(ctx, B * S, H, W, false, &P));
+    const float2* mk = reinterpret_cast<const float2*>(mask);
+    float *gx = work, *gd = work + n, *c_tau = work + 2 * n;
+    const float2* sv_w = reinterpret_cast<const float2*>(saved);
+    const float* sv_d = saved + (size_t)T * n * 2 * S;
+    const float* sv_g = sv_d + (size_t)T * n;
+    hipLaunchKernelGGL(complex_real_part_kernel, g1(n), dim3(256), 0, s, reinterpret_cast<const float2*>(grad_vars_out), gx, n);
+    PNPX_LAUNCH_CHECK();
+    for (int i = T - 1; i >= 0; --i) {
+      PNPX_TRY(unet_denoise_backward_ticket(ctx, sv_d + (size_t)i * n, sigma_d + i, param_stride, gx, gd,
+                                            grad_sigma_d + (size_t)i * B, B, H, W, s, ticket ? ticket + i : 0));
+      // the context's scratch is shared with the denoiser's VJP above, which may also GROW (= re-allocate) it: the k-space
+      // buffer is carved anew every iteration and nothing in it has to survive that call
+      void* p;
+      PNPX_TRY(ctx_scratch(ctx, n * S * sizeof(float2) + 4096, &p));
+      float2* k = static_cast<float2*>(p);
+      StoreC kst{k, H, W};
+      LoadC kld{k, H, W};
+      PNPX_TRY((launch_rows<false>(P, LoadCdpReal{gd, mk, S, W, HW}, kst, s)));
+      PNPX_TRY((launch_cols<false, true>(P, kld, MidPrResidualAdjoint{y0, sv_w + (size_t)i * n * S, W, HW}, kst, s)));
+      PNPX_TRY((launch_rows<true>(P, kld, kst, s)));
+      hipLaunchKernelGGL(pr_pg_adjoint_kernel, g1(n), dim3(256), 0, s, k, mk, gd, sv_g + (size_t)i * n, tau + i, param_stride, S,
+                         HW, B, gx, i == 0 ? reinterpret_cast<float2*>(grad_vars_in) : nullptr, c_tau);
+      PNPX_LAUNCH_CHECK();
+      hipLaunchKernelGGL(pr_item_sum_kernel, dim3(B), dim3(256), 0, s, c_tau, grad_tau + (size_t)i * B, HW);
       PNPX_LAUNCH_CHECK();
     }
     return PNPX_OK;

@@ -647,6 +647,64 @@ def pr_iadmm_backward(ctx, y0, mask, sigma_d, mu, tau, saved, grad_out, iter_num
     return gin, g0.t().contiguous(), g1.t().contiguous(), g2.t().contiguous()
 
 
+def _pr_pg_args(variables, y0, mask):
+    v = _vars(variables, 1, True)
+    B, _, H, W, _ = v.shape
+    y0, mask = _f32(y0, "y0"), _f32(mask, "mask")
+    S = mask.shape[1] if mask.dim() == 5 else 0
+    if tuple(mask.shape) != (B, S, H, W, 2) or tuple(y0.shape) != (B, S, H, W):
+        raise PnpxError("pr_pg: y0 must be [B,S,H,W] and mask [B,S,H,W,2]")
+    return v, y0, mask, B, S, H, W
+
+
+def pr_pg(ctx, variables, y0, mask, sigma_d, tau, iter_num=None):
+    """pnpx_pr_pg: PGSolver_PR.forward, x [B,1,H,W,2] -> next x (imaginary part 0)."""
+    v, y0, mask, B, S, H, W = _pr_pg_args(variables, y0, mask)
+    ps, T = _train_T(B, (sigma_d, tau), iter_num)
+    out = torch.empty_like(v)
+    if B == 0:
+        return out
+    with torch.cuda.device(v.device):
+        check(_lib.lib().pnpx_pr_pg(ctx.handle, _p(v), _p(out), _p(y0), _p(mask), *[_p(p) for p in ps], ps[0].shape[1],
+                                    B, S, H, W, T, _stream(v)))
+    return out
+
+
+def pr_pg_train(ctx, variables, y0, mask, sigma_d, tau, iter_num=None):
+    """pnpx_pr_pg_train: PGSolver_PR.forward for autograd -> (next x [B,1,H,W,2], saved [(2S+2)*T*B*H*W], ticket)."""
+    v, y0, mask, B, S, H, W = _pr_pg_args(variables, y0, mask)
+    ps, T = _train_T(B, (sigma_d, tau), iter_num)
+    out = torch.empty_like(v)
+    saved = torch.empty((2 * S + 2) * T * B * H * W, dtype=torch.float32, device=v.device)
+    if B == 0:
+        return out, saved, 0
+    ticket = C.c_ulonglong(0)
+    with torch.cuda.device(v.device):
+        check(_lib.lib().pnpx_pr_pg_train(ctx.handle, _p(v), _p(out), _p(y0), _p(mask), *[_p(p) for p in ps],
+                                          ps[0].shape[1], B, S, H, W, T, _p(saved), C.byref(ticket), _stream(v)))
+    return out, saved, int(ticket.value)
+
+
+def pr_pg_backward(ctx, y0, mask, sigma_d, tau, saved, grad_out, iter_num=None, ticket=0):
+    """pnpx_pr_pg_backward -> (grad x [B,1,H,W,2], grad sigma_d, grad tau, each [B,T])."""
+    g, y0, mask, B, S, H, W = _pr_pg_args(grad_out, y0, mask)
+    ps, T = _params(B, sigma_d, tau)
+    T = T if iter_num is None else iter_num
+    if saved.numel() != (2 * S + 2) * T * B * H * W:
+        raise PnpxError("saved does not belong to a forward of this shape / iteration count")
+    gin = torch.empty_like(g)
+    gs = _hyper_grads(T, B, 2, g.device)
+    if B and T:
+        work = torch.empty(3 * B * H * W, dtype=torch.float32, device=g.device)
+        with torch.cuda.device(g.device):
+            check(_lib.lib().pnpx_pr_pg_backward(ctx.handle, _p(y0), _p(mask), *[_p(p) for p in ps], ps[0].shape[1],
+                                                 _p(saved), _p(g), _p(gin), *[_p(x) for x in gs], _p(work), B, S, H, W, T,
+                                                 int(ticket), _stream(g)))
+    elif B:
+        gin.copy_(g)
+    return (gin, *[x.t().contiguous() for x in gs])
+
+
 def spi_admm(ctx, variables, x0, Kmap, sigma_d, mu, iter_num=None):
     v = _vars(variables, 3, False)
     B, _, H, W = v.shape

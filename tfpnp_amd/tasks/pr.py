@@ -36,14 +36,29 @@ class IADMMSolver_PR(PRMixin, IADMMSolver):
         return T.call("pr_iadmm", variables, y0, mask, sigma_d, mu, tau, -1 if iter_num is None else iter_num, self._ctx(variables).cid)
 
 class PGSolver_PR(PRMixin, PGSolver):
-    """tasks/pr/solver.py:79-112: the reference applies `~mask` to the float CDP mask and the CS-MRI fft2 to PR
-    data (:102-103), which raises on any input; it is not runnable there, so no native loop exists."""
+    """tasks/pr/solver.py:79-112, proximal gradient on the PR data term.
+
+    The reference's gradient step (:102-103) was pasted from CS-MRI -- `fft2(x) - y0` and `temp[~mask, :] = 0` on the float
+    coded-diffraction mask -- and raises on any PR input; it stays broken there.  Here those two lines are replaced by the
+    gradient of the PR data term as the same file computes it in IADMMSolver_PR.forward (:61-68):
+
+        Ax = cdp_forward(x, mask);  r = (|Ax| - y0) / |Ax| * Ax;  z = x - tau_i * cdp_backward(r, mask)
+        x  = real2complex(prox_mapping(complex2real(z), sigma_d_i))
+
+    The substitution is pinned by executed reference code: one reference IADMMSolver_PR.forward call with iter_num = 1, state
+    cat(x, x, 0) and mu = 0 returns exactly this z in its second slot, and tests/golden/pr_pg_B2_64x64.npz is that call chained
+    with the reference's denoiser prox (tools/make_pr_pg_golden.py).  All iterations run in one native call (pnpx_pr_pg)."""
 
     def reset(self, data):
         return real2complex(data['x0'].clone().detach())
 
     def forward(self, inputs, parameters, iter_num=None):
-        raise NotImplementedError('PGSolver_PR.forward is broken in the reference (tasks/pr/solver.py:102-103)')
+        variables, (y0, mask) = inputs
+        sigma_d, tau = parameters
+        if A.needs_grad(variables, sigma_d, tau):          # training path: native forward + fused native VJP (tasks.hip)
+            return T.call("pr_pg_train", variables, y0, mask, sigma_d, tau, -1 if iter_num is None else iter_num,
+                          self._ctx(variables).cid)[0]
+        return T.call("pr_pg", variables, y0, mask, sigma_d, tau, -1 if iter_num is None else iter_num, self._ctx(variables).cid)
 
 
 _solver_map = {'iadmm': IADMMSolver_PR, 'pg': PGSolver_PR}

@@ -349,6 +349,9 @@ csmri_redadmm_train, csmri_redadmm_backward = _solver_train_ops(
 pr_iadmm_train, pr_iadmm_backward = _solver_train_ops(
     "pr_iadmm", _MRI_AUX, ("sigma_d", "mu", "tau"), ops.pr_iadmm_train, ops.pr_iadmm_backward,
     lambda aux: 2 * aux[1].shape[1] + 5)        # mask [B,S,H,W,2]: S k-space images per iteration
+pr_pg_train, pr_pg_backward = _solver_train_ops(
+    "pr_pg", _MRI_AUX, ("sigma_d", "tau"), ops.pr_pg_train, ops.pr_pg_backward,
+    lambda aux: 2 * aux[1].shape[1] + 2)        # S k-space images, the denoiser input and Re g per iteration
 spi_admm_train, spi_admm_backward = _solver_train_ops(
     "spi_admm", [("x0", "Tensor"), ("Kmap", "Tensor")], ("sigma_d", "mu"), ops.spi_admm_train, ops.spi_admm_backward, 2)
 ct_iadmm_train, ct_iadmm_backward = _solver_train_ops(
@@ -430,6 +433,15 @@ def pr_iadmm(variables: Tensor, y0: Tensor, mask: Tensor, sigma_d: Tensor, mu: T
 pr_iadmm.register_fake(_same)
 
 
+@_lib_def("pnpx::pr_pg", mutates_args=(), device_types="cuda")
+def pr_pg(variables: Tensor, y0: Tensor, mask: Tensor, sigma_d: Tensor, tau: Tensor, iter_num: int, ctx: int) -> Tensor:
+    """PGSolver_PR.forward: the loop of tasks/pr/solver.py:79-112 with the PR gradient step of :61-68 (include/pnpx.h)."""
+    return ops.pr_pg(_ctx(ctx, variables), variables, y0, mask, sigma_d, tau, _it(iter_num))
+
+
+pr_pg.register_fake(_same)
+
+
 @_lib_def("pnpx::spi_admm", mutates_args=(), device_types="cuda")
 def spi_admm(variables: Tensor, x0: Tensor, Kmap: Tensor, sigma_d: Tensor, mu: Tensor, iter_num: int, ctx: int) -> Tensor:
     """ADMMSolver_SPI.forward (tasks/spi/solver.py:17-52)."""
@@ -471,4 +483,4 @@ ALL_OPS = ("unet_denoise", "unet_denoise_preclamp", "unet_denoise_backward", "un
            "unet_denoise_backward_ticket", "policy_forward", "fft2", "cdp_forward",
            "cdp_backward", "spi_inverse", "psnr", "radon_forward", "radon_backprojection", "csmri_admm", "csmri_admm_train",
            "csmri_admm_backward", "csmri_hqs", "csmri_amp",
-           "csmri_pg", "csmri_apg", "csmri_redadmm", "pr_iadmm", "spi_admm", "ct_iadmm", "ct_pg")
+           "csmri_pg", "csmri_apg", "csmri_redadmm", "pr_iadmm", "spi_admm", "ct_iadmm", "ct_pg", "pr_pg")
