@@ -6,8 +6,9 @@ term of the actor loss is  -(gamma * V(ob2) + reward)  with (ob2, reward) = env.
 tfpnp_amd ships the native, eval-mode ResNet actors for rollouts and evaluation, not a trainer; what it does provide is
 that differentiable one-step model on the native kernels (fused ADMM forward + VJP, csrc/csmri.hip).  Any nn.Module that
 maps the policy observation to the action dict can therefore be trained against it with ordinary PyTorch optimisers --
-this file is that bridge in its smallest form (reward term only, a small CNN actor, Adam), and
-tests/test_gpu_train_bridge.py runs it.
+this file is that bridge in its smallest form (reward term only by default, a small CNN actor, Adam), and
+tests/test_gpu_train_bridge.py runs it.  With `critic=` (a tfpnp_amd.trainer.mddpg.critic.ResNet_wobn; frozen weights) the
+value term discount * V(get_eval_ob(ob2)) is added, differentiated natively into the actions.
 
 usage (GPU box):  python examples/train_bridge.py [steps] [B] [H]
 """
@@ -42,7 +43,7 @@ class TinyActor(nn.Module):
                            idx_stop=torch.zeros(policy_ob.shape[0], dtype=torch.int64, device=policy_ob.device))
 
 
-def train(steps=12, B=4, H=64, action_pack=3, lr=3e-2, seed=0, log=print):
+def train(steps=12, B=4, H=64, action_pack=3, lr=3e-2, seed=0, log=print, critic=None, discount=0.99, after_backward=None):
     dev = torch.device("cuda:0")
     torch.manual_seed(seed)
     den = UNetDenoiser2D(state_dict=synth.make_unet_params(0))
@@ -55,10 +56,14 @@ def train(steps=12, B=4, H=64, action_pack=3, lr=3e-2, seed=0, log=print):
     history = []
     for it in range(steps):
         action = actor(policy_ob)
-        _, reward = env.forward(ob, action)            # native forward; backward() below runs the native VJP
+        ob2, reward = env.forward(ob, action)          # native forward; backward() below runs the native VJP
         loss = -reward.mean()
+        if critic is not None:                         # DDPG value term (trainer.py:180-192), critic frozen
+            loss = loss - discount * critic(env.get_eval_ob(ob2)).mean()
         opt.zero_grad()
         loss.backward()
+        if after_backward is not None:                 # (it, actor): a look at the gradients before the step
+            after_backward(it, actor)
         opt.step()
         history.append(float(reward.detach().mean()))
         log(f"step {it:2d}  mean delta-PSNR reward {history[-1]:+.4f} dB   sigma_d[0] "

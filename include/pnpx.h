@@ -193,6 +193,31 @@ int pnpx_policy_load(pnpx_ctx* ctx, const float* params_host, size_t n_params, i
 int pnpx_policy_forward(pnpx_ctx* ctx, const float* ob, float* probs, float* det, int B, int H, int W,
                         void* stream);
 
+/* ---- value network / critic (tfpnp/trainer/mddpg/critic.py) --------------------------------------- */
+/* ResNet_wobn(num_inputs, 18, 1) (critic.py:95-131; the trainer never builds another one, trainer/mddpg/critic.py:95 via
+ * tasks/<task>/main.py): 3x3 stride-2 stem, four stages of two BasicBlocks (critic.py:37-60) each entered with stride 2 and a 1x1
+ * stride-2 shortcut, adaptive_avg_pool2d(1), Linear(512, 1).  Convolutions are weight-normalised with bias
+ * (weight = weight_g * weight_v / ||weight_v||, norm per output channel; critic.py:7-8); activations are TReLU
+ * (relu(x - alpha) + alpha, one scalar alpha each; critic.py:11-19).  Weights are FROZEN between loads: weight-norm is folded on the
+ * host at load and only the gradient with respect to the observation is computed.  One critic per context.
+ * params_host: the fp32 content of state_dict() in registration order (82 tensors),
+ *   conv1.{bias, weight_g, weight_v},
+ *   for L in layer1..layer4:  L.0.{conv1.*, conv2.*, shortcut.0.*, relu_1.alpha, relu_2.alpha},
+ *                             L.1.{conv1.*, conv2.*, relu_1.alpha, relu_2.alpha},
+ *   fc.{weight, bias}, relu_1.alpha
+ * where conv.* = bias, weight_g [cout,1,1,1], weight_v [cout,cin,k,k].  num_inputs = channels of the evaluation observation
+ * (env.get_eval_ob, tfpnp/env/base.py; 1..64).  pnpx_critic_num_params returns 0 for a num_inputs outside that range. */
+size_t pnpx_critic_num_params(int num_inputs);
+int pnpx_critic_load(pnpx_ctx* ctx, const float* params_host, size_t n_params, int num_inputs);
+/* ob [B,num_inputs,H,W] (device, contiguous; H, W positive multiples of 32) -> value [B] (critic.py:121-131).
+ * PNPX_ERR_NO_WEIGHTS before a load.  A row's value does not depend on the batch it arrives in. */
+int pnpx_critic_forward(pnpx_ctx* ctx, const float* ob, float* value, int B, int H, int W, void* stream);
+/* Vector-Jacobian product of pnpx_critic_forward with respect to ob: grad_ob [B,num_inputs,H,W] = grad_value[b] * dV_b / d ob_b
+ * (what autograd returns for V_next in trainer/mddpg/trainer.py:180-192).  The forward is re-computed internally; nothing is
+ * kept between calls.  Exactly linear in grad_value (a zero entry gives a zero row). */
+int pnpx_critic_backward(pnpx_ctx* ctx, const float* ob, const float* grad_value, float* grad_ob, int B, int H, int W,
+                         void* stream);
+
 /* ---- transforms (tfpnp/utils/transforms.py) ------------------------------------------------------ */
 /* fft2 / ifft2 (transforms.py:68-103): centered (ifftshift -> FFT -> fftshift), orthonormal, over the
  * last two image dims of [n_img, H, W, 2].  centered=0 gives the plain torch.fft(x, 2, normalized=True)
@@ -236,6 +261,15 @@ int pnpx_live_compact(pnpx_ctx* ctx, const int64_t* idx_left, const int64_t* idx
 int pnpx_policy_ob_pack(pnpx_ctx* ctx, int n_entries, const void* const* src_host, const int* kind_host,
                         const int* channels_host, const int64_t* idx, int n_rows, int H, int W, float* out,
                         void* stream);
+
+/* Adjoint of pnpx_policy_ob_pack for dense rows (what autograd computes through get_policy_ob / get_eval_ob when the observation
+ * feeds the critic, tfpnp/env/base.py:193-206 + trainer/mddpg/trainer.py:180-192): grad_out [n_rows, sum(channels), H, W] ->
+ * per entry t the tensor dst_host[t] with the shape of the entry's source,
+ *   kind 0: the same channels;  kind 1: real part = gradient, imaginary part = 0;  kind 2: re / im interleaved back;
+ *   kind 3 (bool / uint8 sources have no gradient): nothing is written, dst_host[t] may be NULL.
+ * kind_host / channels_host as given to the pack.  One launch. */
+int pnpx_policy_ob_unpack(pnpx_ctx* ctx, int n_entries, void* const* dst_host, const int* kind_host,
+                          const int* channels_host, int n_rows, int H, int W, const float* grad_out, void* stream);
 
 /* ---- solver loops: T inner iterations per call ---------------------------------------------------- */
 /* Hyper-parameter arrays are [B, param_stride] row-major (the policy's [B, action_pack] tensors,

@@ -50,6 +50,10 @@ _SIGNATURES = {
     "pnpx_policy_num_params": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
     "pnpx_policy_load": (C.c_int, [c_void_p, c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_int]),
     "pnpx_policy_forward": (C.c_int, [c_void_p, _P, _P, _P, C.c_int, C.c_int, C.c_int, c_void_p]),
+    "pnpx_critic_num_params": (C.c_size_t, [C.c_int]),
+    "pnpx_critic_load": (C.c_int, [c_void_p, c_void_p, C.c_size_t, C.c_int]),
+    "pnpx_critic_forward": (C.c_int, [c_void_p, _P, _P, C.c_int, C.c_int, C.c_int, c_void_p]),
+    "pnpx_critic_backward": (C.c_int, [c_void_p, _P, _P, _P, C.c_int, C.c_int, C.c_int, c_void_p]),
     "pnpx_unet_profile": (C.c_int, [c_void_p, _P, _P, _P, C.c_int, C.c_int, C.c_int, c_void_p, C.c_int,
                                     c_float_p, C.POINTER(C.c_double), C.POINTER(C.c_char_p), C.POINTER(C.c_int)]),
     "pnpx_fft2": (C.c_int, [c_void_p, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_void_p]),
@@ -64,6 +68,8 @@ _SIGNATURES = {
     "pnpx_live_compact": (C.c_int, [c_void_p, _P, _P, C.c_int, _P, C.POINTER(C.c_int), c_void_p]),
     "pnpx_policy_ob_pack": (C.c_int, [c_void_p, C.c_int, C.POINTER(c_void_p), C.POINTER(C.c_int), C.POINTER(C.c_int), _P,
                                       C.c_int, C.c_int, C.c_int, _P, c_void_p]),
+    "pnpx_policy_ob_unpack": (C.c_int, [c_void_p, C.c_int, C.POINTER(c_void_p), C.POINTER(C.c_int), C.POINTER(C.c_int),
+                                        C.c_int, C.c_int, C.c_int, _P, c_void_p]),
     "pnpx_csmri_admm": (C.c_int, [c_void_p, _P, _P, _P, _P, _P, _P] + [C.c_int] * 5 + [c_void_p]),
     "pnpx_csmri_admm_train": (C.c_int, [c_void_p, _P, _P, _P, _P, _P, _P] + [C.c_int] * 5 +
                               [_P, C.POINTER(C.c_ulonglong), c_void_p]),

@@ -160,6 +160,7 @@ int pnpx_ctx_destroy(pnpx_ctx* ctx) {
   for (pnpx::UNetArena* a : {&ctx->arena, &ctx->arena_grad})
     if (a->buf.p) (void)hipFree(a->buf.p);
   policy_free(ctx);
+  pnpx::critic_free(ctx);
   pnpx::drunet_free(ctx);
   pnpx::train_cache_free(ctx);
   if (ctx->scratch.p) (void)hipFree(ctx->scratch.p);
@@ -191,6 +192,34 @@ int pnpx_policy_forward(pnpx_ctx* ctx, const float* ob, float* probs, float* det
     return PNPX_ERR_ARG;
   }
   return policy_forward(ctx, ob, probs, det, B, H, W, static_cast<hipStream_t>(stream));
+}
+
+size_t pnpx_critic_num_params(int num_inputs) {
+  return (num_inputs >= 1 && num_inputs <= 64) ? critic_num_params(num_inputs) : 0;
+}
+
+int pnpx_critic_load(pnpx_ctx* ctx, const float* params_host, size_t n_params, int num_inputs) {
+  LOCK_CTX(ctx);
+  return critic_load(ctx, params_host, n_params, num_inputs);
+}
+
+int pnpx_critic_forward(pnpx_ctx* ctx, const float* ob, float* value, int B, int H, int W, void* stream) {
+  LOCK_CTX(ctx);
+  if (!ob || !value) {
+    set_error("pnpx_critic_forward: null pointer");
+    return PNPX_ERR_ARG;
+  }
+  return critic_forward(ctx, ob, value, B, H, W, static_cast<hipStream_t>(stream));
+}
+
+int pnpx_critic_backward(pnpx_ctx* ctx, const float* ob, const float* grad_value, float* grad_ob, int B, int H, int W,
+                         void* stream) {
+  LOCK_CTX(ctx);
+  if (!ob || !grad_value || !grad_ob) {
+    set_error("pnpx_critic_backward: null pointer");
+    return PNPX_ERR_ARG;
+  }
+  return critic_backward(ctx, ob, grad_value, grad_ob, B, H, W, static_cast<hipStream_t>(stream));
 }
 
 int pnpx_ctx_reserve(pnpx_ctx* ctx, int B, int H, int W) {
@@ -371,7 +400,7 @@ size_t pnpx_ctx_bytes(const pnpx_ctx* ctx) {
   size_t n = ctx->weights.bytes + ctx->arena.buf.bytes + ctx->arena_grad.buf.bytes + ctx->scratch.bytes +
              ctx->drunet.weights.bytes + ctx->drunet.arena.bytes + ctx->drunet.arena_grad.bytes + ctx->drunet.f32_weights.bytes +
              ctx->drunet.f32_arena.bytes + ctx->drunet.f32_weights_bwd.bytes + ctx->drunet.f32_arena_grad.bytes +
-             ctx->policy.weights.bytes + ctx->policy.arena.bytes;
+             ctx->policy.weights.bytes + ctx->policy.arena.bytes + ctx->critic.weights.bytes + ctx->critic.arena.bytes;
   for (const auto& sl : ctx->train_ring) n += sl.arena.buf.bytes + sl.pre.bytes;
   return n;
 }

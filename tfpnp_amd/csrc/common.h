@@ -111,6 +111,22 @@ struct PolicyNet {
   int capB = 0, capH = 0, capW = 0;
 };
 
+// Value network (critic.hip): ResNet_wobn(num_inputs, 18, 1), weight-norm folded at load, frozen.  Layer index: 0 = stem,
+// 1 + 5 * stage + {0 entry conv1 (stride 2), 1 shortcut (1x1 stride 2), 2 conv2, 3 block-1 conv1, 4 block-1 conv2}.
+struct CriticNet {
+  bool loaded = false;
+  int num_inputs = 0, cin_pad = 0;
+  ConvLayerHsDev fwd[21], bwd[21];   // forward packings and their adjoints (transposed, tap-mirrored)
+  const float* bias[21] = {};
+  float alpha[21] = {};              // TReLU threshold behind the layer (shortcuts: unused)
+  const float* fc_w = nullptr;       // [512]
+  const float* fc_b = nullptr;       // [1]
+  const float* zero = nullptr;       // [1024] zeros: bias operand of the adjoint launches
+  float fc_wmax = 0.f;               // max |fc_w|: the backward pass scales its gradients to O(1)
+  DeviceBuf weights, arena;          // arena: every forward activation + the gradient tensors, zero borders
+  int capB = 0, capH = 0, capW = 0;
+};
+
 // number of independent launch chains for a B-image denoiser forward (unet.hip; option "chains", 0 = automatic)
 int launch_chains(const pnpx_ctx* ctx, int B, int H, int W);
 // a launch-chain fan-out failed half way: drain the side streams before the error is returned, so that nothing queued on them
@@ -235,6 +251,8 @@ struct pnpx_ctx {
   bool train_alloc_failed = false;                 // stop retrying after an out-of-memory until the option is set again
   // --- policy actor
   pnpx::PolicyNet policy;
+  // --- value network (critic)
+  pnpx::CriticNet critic;
   // --- DRUNet denoiser (when loaded it IS the context's denoiser: every prox call of every solver runs it)
   pnpx::DruNet drunet;
   // --- solver scratch (complex fields etc.), grown on demand
@@ -356,6 +374,13 @@ size_t policy_num_params(int num_inputs, int n_det, int spi_head);
 int policy_load(pnpx_ctx* ctx, const float* params, size_t n, int num_inputs, int n_det, int spi_head);
 int policy_forward(pnpx_ctx* ctx, const float* ob, float* probs, float* det, int B, int H, int W, hipStream_t s);
 void policy_free(pnpx_ctx* ctx);
+
+// Value network (critic.hip)
+size_t critic_num_params(int num_inputs);
+int critic_load(pnpx_ctx* ctx, const float* params, size_t n, int num_inputs);
+int critic_forward(pnpx_ctx* ctx, const float* ob, float* value, int B, int H, int W, hipStream_t s);
+int critic_backward(pnpx_ctx* ctx, const float* ob, const float* grad_value, float* grad_ob, int B, int H, int W, hipStream_t s);
+void critic_free(pnpx_ctx* ctx);
 
 // FFT building blocks (fft.hip)
 int fft2(pnpx_ctx* ctx, const float* in, float* out, int n_img, int H, int W, bool inverse, bool centered,

@@ -71,6 +71,9 @@ struct ConvHsArgs {
   const float* first_zero;     // a zero word in device memory (window elements outside the image)
   int first_sigma_stride;
   float first_slope;
+  // critic epilogues only (EPI_TRELU / EPI_DTHR; no other instance reads these)
+  float alpha;                 // TReLU threshold
+  int res_G;                   // EPI_DTHR: channel groups per image of the tensor behind `res` (<= the output's)
 };
 
 int conv_hs_mt(int cout);
@@ -110,6 +113,12 @@ struct ConvHsFuse {       // optional fused work
   // r5: number of independent launch chains the caller runs side by side (unet.hip launch_chains): this launch shares the 256 CUs with
   // share - 1 launches of the same shape, and the launch table picks the tile height for 256 / share workgroups (same bits either way)
   int share = 1;
+  // critic (critic.hip): 1 = TReLU epilogue max(conv + bias [+ res], alpha); 2 = its input-gradient epilogue
+  // (conv [+ res]) * (dmask > alpha), dmask / res optional, res_groups = groups per image of `res` (0 = as the output).
+  // Tap masks: 0x1FF and 0x01B (forward), 0x1FF and 0x1B0 (gradient).
+  int critic_epi = 0;
+  float alpha = 0.f;
+  int res_groups = 0;
 };
 // true when launch_conv_hs will honour ConvHsFuse::first_x for this layer / geometry (else the caller runs conv_first)
 bool conv_hs_can_fold_first(const ConvLayerHs& L, int G0, int B, int H, int W, const ConvHsFuse& fuse);

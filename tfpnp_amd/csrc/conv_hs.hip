@@ -165,6 +165,8 @@ int launch_conv_hs(const ConvLayerHs& L, const char* in0, int G0, const char* in
   a.first_x = a.first_sigma = a.first_w = a.first_b = a.first_zero = nullptr;
   a.first_sigma_stride = 0;
   a.first_slope = 0.f;
+  a.alpha = fuse.alpha;
+  a.res_G = fuse.res_groups > 0 ? fuse.res_groups : L.cout / 8;
   if (fuse.ups_h) {   // fused bilinear x2 of the second source: one instance, picked here
     if (!conv_hs_can_fuse_upsample(L, G0, G1, H, W) || fuse.ups_h * 2 != H || fuse.ups_w * 2 != W || !in1 || fuse.pool_out ||
         fuse.outc_w || fuse.dmask || fuse.res) {
@@ -205,6 +207,14 @@ int launch_conv_hs(const ConvLayerHs& L, const char* in0, int G0, const char* in
       mt_run = 32;
       a.nct = L.cout / 32;
     }
+  }
+  if (fuse.critic_epi) {
+    if (a.outc_w || a.pool_out || fuse.ups_h || fuse.first_x || G1 != 0 || (fuse.critic_epi == 1 && a.dmask) || a.res_G > L.cout / 8 ||
+        !std::isfinite(fuse.alpha)) {
+      set_error("conv_hs: the critic epilogues take one source, a finite threshold and no other fused work");
+      return PNPX_ERR_SHAPE;
+    }
+    return fuse.critic_epi == 1 ? launch_conv_hs_trelu(a, mt_run, fuse.taps, B, s) : launch_conv_hs_dthr(a, mt_run, fuse.taps, B, s);
   }
   if (fuse.taps != 0x1FF) {
     if (a.dmask || a.res || a.outc_w || a.pool_out || fuse.ups_h || fuse.first_x || G1 != 0) {

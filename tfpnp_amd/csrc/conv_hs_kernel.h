@@ -32,8 +32,13 @@ enum HsEpi {
   EPI_ACT = 0,    // out = act(conv + bias) [+ fused 2x2 max-pool output]
   EPI_OUTC = 1,   // network tail: clamp(x + outc(act(conv + bias)) + b) written as an fp32 image (MT == 32)
   EPI_DMASK = 2,  // input-gradient convolution: out = conv * (saved activation > 0 ? 1 : slope)
-  EPI_RES = 3     // out = act(conv + bias + res)
+  EPI_RES = 3,    // out = act(conv + bias + res)
+  // critic (ResNet_wobn, critic.hip): TReLU layers.  These two are the only epilogues that read ConvHsArgs::alpha / res_G.
+  EPI_TRELU = 4,  // out = max(conv + bias [+ res], alpha)
+  EPI_DTHR = 5    // input-gradient convolution: out = (conv [+ res]) * (saved activation > alpha ? 1 : 0)
 };
+// input-gradient epilogues: no bias, rectifier mask fetched from a saved forward activation
+constexpr bool hs_epi_grad(int epi) { return epi == EPI_DMASK || epi == EPI_DTHR; }
 
 #ifndef HS_DMA_TAPS
 #define HS_DMA_TAPS 9
@@ -152,7 +157,7 @@ template <int MT, int NBW, int MBW, int NW, int EPI, int UPS = 0, int WREG = 0, 
 // eight-wave ones -- with the 512-register budget of one wave per SIMD the compiler keeps the accumulators in VGPRs across the
 // loop and copies them to AGPRs and back around every step's MFMAs: 64 v_accvgpr moves per step.  Occupancy is set by LDS.)
 __global__ __launch_bounds__((NW + HS_UPS_WAVES * UPS) * 64,
-                             (NW == 4 && !UPS && !WREG && (MT / 32) * NBW <= (EPI == EPI_DMASK ? 2 : 4)) ? 2 : (NW + HS_UPS_WAVES * UPS) / 4) void conv_hs_kernel(ConvHsArgs a) {
+                             (NW == 4 && !UPS && !WREG && (MT / 32) * NBW <= (hs_epi_grad(EPI) ? 2 : 4)) ? 2 : (NW + HS_UPS_WAVES * UPS) / 4) void conv_hs_kernel(ConvHsArgs a) {
   using G = HsGeom<MT, NBW, MBW, NW, WREG, TAPS>;
   static_assert(TAPS == 0x1FF || (!WREG && !UPS), "sparse-tap layers: generic instances only");
   static_assert(!(WREG && UPS) && (!WREG || MT == 32), "WREG: 32-cout single-source layers only");
@@ -183,7 +188,7 @@ __global__ __launch_bounds__((NW + HS_UPS_WAVES * UPS) * 64,
 
   // the layer's bias vector, pre-scaled by HS_ASCALE, stays in LDS for the life of the workgroup (a global load in
   // the epilogue would make the compiler drain the in-flight LDS-DMA queue in front of it)
-  if constexpr (EPI != EPI_DMASK) {
+  if constexpr (!hs_epi_grad(EPI)) {
     float* lbias = reinterpret_cast<float*>(lds + G::BIAS_OFF);
     for (int i = tid; i < a.nct * MT; i += NT) lbias[i] = a.bias[i] * HS_ASCALE;
     __syncthreads();
@@ -433,6 +438,9 @@ __global__ __launch_bounds__((NW + HS_UPS_WAVES * UPS) * 64,
   // Fetched at the FIRST step of a tile, ahead of that step's DMA issue, so that they land under the tile's main loop: issued in
   // the epilogue they cost a full exposed load latency per tile (r3: +190 us on a 110 us launch of the 32 -> 32 layers).
   [[maybe_unused]] uint2 mk[EPI == EPI_DMASK ? G::MTB : 1][EPI == EPI_DMASK ? NBW : 1][4];
+  // EPI_DTHR: both halves of the saved activation (the threshold alpha is in general not zero: the sign of hi does not decide)
+  [[maybe_unused]] h4 mth[EPI == EPI_DTHR ? G::MTB : 1][EPI == EPI_DTHR ? NBW : 1][4];
+  [[maybe_unused]] h4 mtl[EPI == EPI_DTHR ? G::MTB : 1][EPI == EPI_DTHR ? NBW : 1][4];
   [[maybe_unused]] auto fetch_masks = [&](const Tile& T) {
     const size_t img_rec = (size_t)T.b * Gout * HpWp;
 #pragma unroll
@@ -441,10 +449,22 @@ __global__ __launch_bounds__((NW + HS_UPS_WAVES * UPS) * 64,
       for (int n = 0; n < NBW; ++n) {
         const int y = min(T.y0 + (wave * NBW + n) * G::MBH + py, a.H - 1), x = min(T.x0 + px, a.W - 1);
         const size_t rec = img_rec + (size_t)(y + 1) * a.Wp + (x + 1);
+        if constexpr (EPI == EPI_DTHR) {
 #pragma unroll
-        for (int q = 0; q < 4; ++q)
-          mk[m][n][q] = a.dmask ? *reinterpret_cast<const uint2*>(a.dmask + (rec + (size_t)(T.ct * (MT / 8) + m * 4 + 2 * kg + (q >> 1)) * HpWp) * 32 + 8 * (q & 1))
-                                : make_uint2(0x3c003c00u, 0x3c003c00u);
+          for (int q = 0; q < 4; ++q) {
+            mth[m][n][q] = mtl[m][n][q] = (h4){0, 0, 0, 0};
+            if (a.dmask) {
+              const char* mp = a.dmask + (rec + (size_t)(T.ct * (MT / 8) + m * 4 + 2 * kg + (q >> 1)) * HpWp) * 32 + 8 * (q & 1);
+              mth[m][n][q] = *reinterpret_cast<const h4*>(mp);
+              mtl[m][n][q] = *reinterpret_cast<const h4*>(mp + 16);
+            }
+          }
+        } else {
+#pragma unroll
+          for (int q = 0; q < 4; ++q)
+            mk[m][n][q] = a.dmask ? *reinterpret_cast<const uint2*>(a.dmask + (rec + (size_t)(T.ct * (MT / 8) + m * 4 + 2 * kg + (q >> 1)) * HpWp) * 32 + 8 * (q & 1))
+                                  : make_uint2(0x3c003c00u, 0x3c003c00u);
+        }
       }
   };
 
@@ -462,7 +482,7 @@ __global__ __launch_bounds__((NW + HS_UPS_WAVES * UPS) * 64,
 #pragma unroll
     for (int m = 0; m < G::MTB; ++m) {
       float bias[16];
-      if constexpr (EPI != EPI_DMASK) {
+      if constexpr (!hs_epi_grad(EPI)) {
         const char* lb = lds + G::BIAS_OFF + (T.ct * MT + m * 32 + 16 * kg) * 4;
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
@@ -487,6 +507,56 @@ __global__ __launch_bounds__((NW + HS_UPS_WAVES * UPS) * 64,
               const bool pos = (hh[j] & 0x8000u) == 0 && (hh[j] & 0x7fffu) != 0;
               const float t = acc[m][n][q * 4 + j] * c16;
               v[n][q * 4 + j] = pos ? t : t * a.slope;
+            }
+          }
+        }
+      } else if constexpr (EPI == EPI_DTHR) {
+        // critic input gradient: (conv [+ res]) where the saved TReLU output lies above its threshold.  A clipped output was stored
+        // as split(16 alpha), so it reads back as exactly the same split of the threshold: compare reconstructed values.
+        const float a16 = a.alpha * HS_ASCALE;
+        const _Float16 a_hi = (_Float16)a16;
+        const float thr = (float)a_hi + (float)(_Float16)(a16 - (float)a_hi);
+        const bool masked = a.dmask != nullptr;
+#pragma unroll
+        for (int n = 0; n < NBW; ++n) {
+          const int y = min(T.y0 + (wave * NBW + n) * G::MBH + py, a.H - 1), x = min(T.x0 + px, a.W - 1);
+          const size_t pix = (size_t)(y + 1) * a.Wp + (x + 1);
+#pragma unroll
+          for (int q = 0; q < 4; ++q) {
+            h4 rh = {0, 0, 0, 0}, rl = {0, 0, 0, 0};
+            const int grp = T.ct * (MT / 8) + m * 4 + 2 * kg + (q >> 1);
+            if (a.res && grp < a.res_G) {   // res: HS8 tensor of res_G (<= Gout) groups per image, added to the first res_G groups
+              const char* rp = a.res + (((size_t)T.b * a.res_G + grp) * HpWp + pix) * 32 + 8 * (q & 1);
+              rh = *reinterpret_cast<const h4*>(rp);
+              rl = *reinterpret_cast<const h4*>(rp + 16);
+            }
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+              const bool pos = !masked || ((float)mth[m][n][q][j] + (float)mtl[m][n][q][j]) > thr;
+              const float t = acc[m][n][q * 4 + j] * c16 + ((float)rh[j] + (float)rl[j]);
+              v[n][q * 4 + j] = pos ? t : 0.f;
+            }
+          }
+        }
+      } else if constexpr (EPI == EPI_TRELU) {
+        // critic forward: TReLU(t) = relu(t - alpha) + alpha = max(t, alpha); res is an HS8 tensor laid out like the output
+        const float a16 = a.alpha * HS_ASCALE;
+#pragma unroll
+        for (int n = 0; n < NBW; ++n) {
+          const int y = min(T.y0 + (wave * NBW + n) * G::MBH + py, a.H - 1), x = min(T.x0 + px, a.W - 1);
+          const size_t rec = img_rec + (size_t)(y + 1) * a.Wp + (x + 1);
+#pragma unroll
+          for (int q = 0; q < 4; ++q) {
+            h4 rh = {0, 0, 0, 0}, rl = {0, 0, 0, 0};
+            if (a.res) {
+              const char* rp = a.res + (rec + (size_t)(T.ct * (MT / 8) + m * 4 + 2 * kg + (q >> 1)) * HpWp) * 32 + 8 * (q & 1);
+              rh = *reinterpret_cast<const h4*>(rp);
+              rl = *reinterpret_cast<const h4*>(rp + 16);
+            }
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+              const float t = __builtin_fmaf(acc[m][n][q * 4 + j], c16, bias[q * 4 + j]) + ((float)rh[j] + (float)rl[j]);
+              v[n][q * 4 + j] = __builtin_fmaxf(t, a16);
             }
           }
         }
@@ -838,7 +908,7 @@ __global__ __launch_bounds__((NW + HS_UPS_WAVES * UPS) * 64,
       continue;
     }
     next_halo_by_dma = !(has_next && chunk_is_up(nchk));
-    if constexpr (EPI == EPI_DMASK) {
+    if constexpr (hs_epi_grad(EPI)) {
       if (ch == 0) fetch_masks(cur);
     }
     if (!has_next) {
@@ -1043,5 +1113,7 @@ static int launch_hs_mt(const ConvHsArgs& a, int B, hipStream_t s) {
 int launch_conv_hs_dmask(const ConvHsArgs& a, int mt, int B, hipStream_t s);   // conv_hs_bwd.hip
 int launch_conv_hs_res(const ConvHsArgs& a, int mt, int B, hipStream_t s);     // conv_hs_res.hip
 int launch_conv_hs_taps(const ConvHsArgs& a, int mt, int taps, int B, hipStream_t s);   // conv_hs_taps.hip (EPI_ACT)
+int launch_conv_hs_trelu(const ConvHsArgs& a, int mt, int taps, int B, hipStream_t s);  // conv_hs_trelu.hip (EPI_TRELU)
+int launch_conv_hs_dthr(const ConvHsArgs& a, int mt, int taps, int B, hipStream_t s);   // conv_hs_dthr.hip (EPI_DTHR)
 
 }  // namespace pnpx

@@ -1,0 +1,640 @@
+// Value network (critic) forward and input gradient -- frozen weights.
+//
+// Replaces ResNet_wobn(num_inputs, 18, 1).forward (tfpnp/trainer/mddpg/critic.py:95-131) and the autograd pass through it
+// with respect to its INPUT, which is how the actor loss uses it (trainer/mddpg/trainer.py:180-192: V_next = critic(eval_ob2)
+// is differentiated into the actions; the critic's own weight gradients from that loss are discarded, :206):
+//     x = TReLU(conv3x3(num_inputs, 64, stride 2)(ob))                       critic.py:102,122
+//     4 stages of 2 BasicBlocks (critic.py:37-60), each stage entered with stride 2 and a 1x1 stride-2 shortcut
+//     V = fc(adaptive_avg_pool2d(x, 1))                                      critic.py:128-130
+// Convolutions are weight-normalised with bias (w = g * v / ||v||, norm per output channel: folded on the host at load);
+// TReLU(t) = relu(t - alpha) + alpha = max(t, alpha) with one scalar alpha per activation (critic.py:11-19).
+//
+// The topology is the actor's (policy.hip), so the forward runs on the same half-split launches: the stem and the stage
+// entries as 2x2-window convolutions (tap mask 0x01B) over HS8 space-to-depth tensors, the shortcut as the 1x1 instance
+// (linear epilogue), the stride-1 convolutions with the residual operand -- with the TReLU epilogue (conv_hs_trelu.hip).
+// alpha cannot be folded into the bias: `+ alpha` behind the rectifier would leak into the zero border of the next layer.
+//
+// Backward (dV/d ob times grad_value): the forward is re-computed (every activation stays in the arena; nothing is kept
+// between calls), then the adjoint chain runs on the input-gradient epilogue (conv_hs_dthr.hip):
+//     out = (W^T g [+ res]) * (saved activation > alpha)
+// where the mask is the one of the layer BELOW (the tensor the forward layer read), so every tensor of the chain is the
+// gradient with respect to a pre-activation and each block costs two launches; the sum of a block's two branches is the
+// residual operand.  A stride-2 entry is a stride-1 2x2-window convolution on the space-to-depth grid, so its adjoint is the
+// mirrored window (0x1B0) on the same grid, masked by the saved space-to-depth tensor, followed by depth-to-space; the
+// shortcut's adjoint (1x1, existing linear instance) is its residual operand on the phase-(0,0) channel groups.
+// Gradients are carried as HS8 tensors of  s * dV/d(.)  with s a power of two that brings the head's largest entry into [1, 2);
+// grad_value[b] / s is applied by the last kernel in fp32, so the result is exactly linear in grad_value.
+#include <cmath>
+#include <cstring>
+
+#include "common.h"
+#include "conv_hs.h"
+#include "hs_rec.h"
+#include "hs_relayout.h"
+
+namespace pnpx {
+namespace {
+
+inline dim3 g1(size_t n) { return dim3((unsigned)((n + 255) / 256)); }
+inline int stage_planes(int n) { return 64 << n; }   // n = 0..3
+
+// what a stored TReLU output equal to its threshold reads back as (the hi/lo split of 16 * alpha, conv_hs_kernel.h)
+inline float hs_roundtrip16(float alpha) {
+  const float a16 = alpha * HS_ASCALE;
+  const _Float16 hi = (_Float16)a16;
+  return (float)hi + (float)(_Float16)(a16 - (float)hi);
+}
+
+// observation [B][C][H][W] fp32 -> HS8 space-to-depth tensor [B][4*Cp/8][H/2+2][W/2+2] (phase-major channel groups;
+// channels >= C are zero)
+__global__ __launch_bounds__(256) void critic_pack_ob_kernel(const float* __restrict__ ob, HsRec* __restrict__ out, int C, int Cp,
+                                                             int H, int W, size_t n) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const int W2 = W >> 1, H2 = H >> 1, Gp = Cp >> 3;
+  const int x2 = (int)(i % W2);
+  size_t t = i / W2;
+  const int y2 = (int)(t % H2);
+  t /= H2;
+  const int g = (int)(t % Gp);
+  t /= Gp;
+  const int ph = (int)(t % 4);
+  const size_t b = t / 4;
+  const int y = 2 * y2 + (ph >> 1), x = 2 * x2 + (ph & 1);
+  float v[8];
+#pragma unroll
+  for (int k = 0; k < 8; ++k) {
+    const int c = g * 8 + k;
+    v[k] = c < C ? ob[((b * C + c) * H + y) * (size_t)W + x] * HS_ASCALE : 0.f;
+  }
+  out[((b * 4 * Gp + (size_t)ph * Gp + g) * (H2 + 2) + (y2 + 1)) * (size_t)(W2 + 2) + (x2 + 1)] = hs_pack(v);
+}
+
+// global average pool over HS8 [B][64 groups][h+2][w+2] + Linear(512, 1).  One workgroup per observation; fixed summation
+// order (a result does not depend on the batch it arrives in).
+__global__ __launch_bounds__(256) void critic_pool_fc_kernel(const HsRec* __restrict__ feat, int h, int w,
+                                                             const float* __restrict__ fc_w, const float* __restrict__ fc_b,
+                                                             float* __restrict__ value) {
+  __shared__ float part[256];
+  const int b = blockIdx.x, tid = threadIdx.x;
+  const float inv = 1.f / ((float)(h * w) * HS_ASCALE);
+  float acc = 0.f;
+  for (int c = tid; c < 512; c += 256) {
+    const HsRec* p = feat + ((size_t)b * 64 + (c >> 3)) * (h + 2) * (w + 2);
+    float s = 0.f;
+    for (int y = 0; y < h; ++y)
+      for (int x = 0; x < w; ++x) {
+        const HsRec& r = p[(y + 1) * (w + 2) + x + 1];
+        s += (float)r.hi[c & 7] + (float)r.lo[c & 7];
+      }
+    acc = fmaf(s * inv, fc_w[c], acc);
+  }
+  part[tid] = acc;
+  __syncthreads();
+  for (int st = 128; st > 0; st >>= 1) {
+    if (tid < st) part[tid] += part[tid + st];
+    __syncthreads();
+  }
+  if (tid == 0) value[b] = part[0] + fc_b[0];
+}
+
+// head of the backward pass: g[b][c][y][x] = gsc * fc_w[c] where the last TReLU output lies above its threshold
+// (gsc = s * HS_ASCALE / (h * w): pool and fc are linear)
+__global__ __launch_bounds__(256) void critic_head_grad_kernel(const HsRec* __restrict__ feat, HsRec* __restrict__ g,
+                                                               const float* __restrict__ fc_w, float thr, float gsc, int h,
+                                                               int w, size_t n) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const int x = (int)(i % w);
+  size_t t = i / w;
+  const int y = (int)(t % h);
+  t /= h;   // t = b * 64 + group
+  const int grp = (int)(t % 64);
+  const size_t rec = (t * (h + 2) + (y + 1)) * (size_t)(w + 2) + (x + 1);
+  const HsRec r = feat[rec];
+  float v[8];
+#pragma unroll
+  for (int k = 0; k < 8; ++k) v[k] = ((float)r.hi[k] + (float)r.lo[k]) > thr ? fc_w[grp * 8 + k] * gsc : 0.f;
+  g[rec] = hs_pack(v);
+}
+
+// tail of the backward pass: HS8 space-to-depth gradient [B][4*Cp/8][H/2+2][W/2+2] -> grad_ob [B][C][H][W] fp32, times
+// grad_value[b] * inv (inv = 1 / (s * HS_ASCALE), a power of two)
+__global__ __launch_bounds__(256) void critic_ob_grad_kernel(const HsRec* __restrict__ g, const float* __restrict__ grad_value,
+                                                             float* __restrict__ grad_ob, int C, int Cp, int H, int W,
+                                                             float inv, size_t n) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const int x = (int)(i % W);
+  size_t t = i / W;
+  const int y = (int)(t % H);
+  t /= H;
+  const int c = (int)(t % C);
+  const size_t b = t / C;
+  const int Gp = Cp >> 3, ph = (y & 1) * 2 + (x & 1);
+  const HsRec& r = g[((b * 4 * Gp + (size_t)ph * Gp + (c >> 3)) * ((H >> 1) + 2) + (y >> 1) + 1) * (size_t)((W >> 1) + 2) + (x >> 1) + 1];
+  grad_ob[i] = ((float)r.hi[c & 7] + (float)r.lo[c & 7]) * (grad_value[b] * inv);
+}
+
+// ------------------------------------------------------------------------------------------- parameter layout
+struct Reader {
+  const float* p;
+  const float* take(size_t n) {
+    const float* r = p;
+    p += n;
+    return r;
+  }
+};
+struct WnConv {   // registration order of a weight-normalised Conv2d: bias, weight_g, weight_v
+  const float *b, *g, *v;
+};
+// Dense "effective" weights of one launch: E[cout][K][9] (+ bias[cout])
+struct Eff {
+  int cout, K;
+  std::vector<float> w, bias;
+  Eff(int cout_, int K_) : cout(cout_), K(K_), w((size_t)cout_ * K_ * 9, 0.f), bias(cout_, 0.f) {}
+  float& at(int co, int k, int tap) { return w[((size_t)co * K + k) * 9 + tap]; }
+  float at(int co, int k, int tap) const { return w[((size_t)co * K + k) * 9 + tap]; }
+};
+// weight = weight_g * weight_v / ||weight_v||, norm over everything but the output channel (torch.nn.utils.weight_norm, dim 0)
+std::vector<float> wn_fold(const WnConv& c, int cout, size_t fan) {
+  std::vector<float> w((size_t)cout * fan);
+  for (int co = 0; co < cout; ++co) {
+    double ss = 0.0;
+    for (size_t i = 0; i < fan; ++i) ss += (double)c.v[co * fan + i] * c.v[co * fan + i];
+    const double sc = (double)c.g[co] / std::sqrt(ss);
+    for (size_t i = 0; i < fan; ++i) w[co * fan + i] = (float)(c.v[co * fan + i] * sc);
+  }
+  return w;
+}
+void put_conv_s1(Eff& E, const WnConv& c, int cout, int cin) {
+  const std::vector<float> w = wn_fold(c, cout, (size_t)cin * 9);
+  for (int co = 0; co < cout; ++co) {
+    E.bias[co] = c.b[co];
+    for (int ci = 0; ci < cin; ++ci)
+      for (int t = 0; t < 9; ++t) E.at(co, ci, t) = w[((size_t)co * cin + ci) * 9 + t];
+  }
+}
+// 3x3 stride-2 conv over a space-to-depth input with Cp channels per phase (policy.hip::put_conv_s2): input row
+// 2*yo + (dy - 1) is phase 0 / same half-res row for dy = 1, phase 1 / previous row for dy = 0, phase 1 / same row for dy = 2
+void put_conv_s2(Eff& E, const WnConv& c, int cout, int cin, int Cp) {
+  const std::vector<float> w = wn_fold(c, cout, (size_t)cin * 9);
+  for (int co = 0; co < cout; ++co) {
+    E.bias[co] = c.b[co];
+    for (int ci = 0; ci < cin; ++ci)
+      for (int dy = 0; dy < 3; ++dy)
+        for (int dx = 0; dx < 3; ++dx) {
+          const int py = (dy == 1) ? 0 : 1, ty = (dy == 0) ? 0 : 1;
+          const int px = (dx == 1) ? 0 : 1, tx = (dx == 0) ? 0 : 1;
+          E.at(co, (py * 2 + px) * Cp + ci, ty * 3 + tx) = w[((size_t)co * cin + ci) * 9 + dy * 3 + dx];
+        }
+  }
+}
+// 1x1 stride-2 conv = centre tap over the phase-(0,0) channels
+void put_shortcut(Eff& E, const WnConv& c, int cout, int cin) {
+  const std::vector<float> w = wn_fold(c, cout, (size_t)cin);
+  for (int co = 0; co < cout; ++co) {
+    E.bias[co] = c.b[co];
+    for (int ci = 0; ci < cin; ++ci) E.at(co, ci, 4) = w[(size_t)co * cin + ci];
+  }
+}
+// adjoint with respect to the input: channels transposed, taps mirrored (tap t -> 8 - t), no bias
+Eff adjoint(const Eff& E) {
+  Eff A(E.K, E.cout);
+  for (int co = 0; co < E.cout; ++co)
+    for (int k = 0; k < E.K; ++k)
+      for (int t = 0; t < 9; ++t) A.at(k, co, 8 - t) = E.at(co, k, t);
+  return A;
+}
+
+struct HostBlob {
+  std::vector<float> f;
+  void align() { f.resize((f.size() + 255) & ~(size_t)255, 0.f); }
+  size_t add(const float* p, size_t n) {
+    align();
+    const size_t off = f.size();
+    f.insert(f.end(), p, p + n);
+    return off;
+  }
+};
+struct Packed {
+  size_t w = 0, b = 0;
+  float scale = 1.f;
+  int cin = 0, cout = 0, mt = 0;
+};
+Packed pack_layer(HostBlob& H, const Eff& E, int tapmask, bool with_bias) {
+  Packed P;
+  int nt = 0;
+  for (int t = 0; t < 9; ++t) nt += (tapmask >> t) & 1;
+  H.align();
+  P.w = H.f.size();
+  const size_t n16 = (size_t)E.cout * E.K * nt * 2;
+  H.f.resize(H.f.size() + (n16 + 1) / 2, 0.f);
+  P.mt = (E.cout % 64 == 0) ? 64 : 32;
+  P.scale = pack_conv_weights_hs_taps(E.w.data(), E.cout, E.K, P.mt, tapmask, reinterpret_cast<uint16_t*>(H.f.data() + P.w));
+  if (with_bias) P.b = H.add(E.bias.data(), E.bias.size());
+  P.cin = E.K;
+  P.cout = E.cout;
+  return P;
+}
+
+constexpr int NL = 21;
+inline int fwd_taps(int li) { return li == 0 ? 0x01B : ((li - 1) % 5 == 0 ? 0x01B : ((li - 1) % 5 == 1 ? 0x010 : 0x1FF)); }
+inline int bwd_taps(int li) { return li == 0 ? 0x1B0 : ((li - 1) % 5 == 0 ? 0x1B0 : ((li - 1) % 5 == 1 ? 0x010 : 0x1FF)); }
+
+// ------------------------------------------------------------------------------------------- activation plan
+struct CAct {
+  size_t off = 0;   // floats; an HS8 tensor [C/8][H+2][W+2] of 32-byte records takes C*(H+2)*(W+2) floats per image
+  int C = 0, H = 0, W = 0;
+};
+struct CriticPlan {
+  // forward (all kept: the backward pass reads them as masks)
+  CAct ob_s, stem_o, stem_s;                  // space-to-depth observation; stem output (64, H/2); its space-to-depth copy
+  CAct t1[4], sc[4], o0[4], t2[4], o1[4];
+  CAct o1s[3];                                // space-to-depth copy of o1 (next stage's entry)
+  // gradients with respect to pre-activations, scaled (header comment)
+  CAct gA[4], gB[4], gM[4];                   // planes x h x w: of o1, of o0, of t1 / t2
+  CAct gR[4], gS[4];                          // shortcut adjoint (in_planes x h x w), entry adjoint (4*in_planes x h x w)
+  CAct g_stem, g_ob;                          // of the stem output (64, H/2); of the space-to-depth observation
+  size_t total = 0;
+};
+CriticPlan make_plan(int capB, int cin_pad, int H, int W) {
+  CriticPlan P;
+  size_t off = 0;
+  auto add = [&](CAct& d, int C, int h, int w) {
+    d.off = off;
+    d.C = C;
+    d.H = h;
+    d.W = w;
+    off += (size_t)C * (h + 2) * (w + 2) * capB;
+    off = (off + 63) & ~(size_t)63;
+  };
+  add(P.ob_s, 4 * cin_pad, H / 2, W / 2);
+  add(P.stem_o, 64, H / 2, W / 2);
+  add(P.stem_s, 4 * 64, H / 4, W / 4);
+  add(P.g_stem, 64, H / 2, W / 2);
+  add(P.g_ob, 4 * cin_pad, H / 2, W / 2);
+  int in_planes = 64;
+  for (int n = 0; n < 4; ++n) {
+    const int p = stage_planes(n), h = H >> (n + 2), w = W >> (n + 2);
+    add(P.t1[n], p, h, w);
+    add(P.sc[n], p, h, w);
+    add(P.o0[n], p, h, w);
+    add(P.t2[n], p, h, w);
+    add(P.o1[n], p, h, w);
+    if (n < 3) add(P.o1s[n], 4 * p, h / 2, w / 2);
+    add(P.gA[n], p, h, w);
+    add(P.gB[n], p, h, w);
+    add(P.gM[n], p, h, w);
+    add(P.gR[n], in_planes, h, w);
+    add(P.gS[n], 4 * in_planes, h, w);
+    in_planes = p;
+  }
+  P.total = off + (1u << 18);   // slack: overhanging tiles read past their tensor
+  return P;
+}
+
+int check_call(const CriticNet& N, const char* who, int B, int H, int W) {
+  if (!N.loaded) {
+    set_error("%s called before pnpx_critic_load", who);
+    return PNPX_ERR_NO_WEIGHTS;
+  }
+  if (B <= 0 || H < 32 || W < 32 || (H % 32) || (W % 32)) {
+    set_error("%s: need B > 0 and H, W positive multiples of 32 (got %d x %d x %d)", who, B, H, W);
+    return PNPX_ERR_SHAPE;
+  }
+  return PNPX_OK;
+}
+
+// arena for B observations of H x W (grows to the largest batch seen at one size; zero borders written once)
+int reserve(CriticNet& N, int B, int H, int W) {
+  if (B <= N.capB && H == N.capH && W == N.capW) return PNPX_OK;
+  const bool same = (H == N.capH && W == N.capW);
+  const int nb = same ? (B > N.capB ? B : N.capB) : B;
+  const CriticPlan P = make_plan(nb, N.cin_pad, H, W);
+  PNPX_HIP(hipDeviceSynchronize());
+  if (N.arena.bytes < P.total * sizeof(float)) {
+    if (N.arena.p) PNPX_HIP(hipFree(N.arena.p));
+    N.arena = DeviceBuf();
+    N.capB = N.capH = N.capW = 0;
+    void* p = nullptr;
+    hipError_t e = hipMalloc(&p, P.total * sizeof(float));
+    if (e != hipSuccess) {
+      set_error("critic arena allocation of %zu bytes failed: %s", P.total * sizeof(float), hipGetErrorString(e));
+      return PNPX_ERR_ALLOC;
+    }
+    N.arena.p = p;
+    N.arena.bytes = P.total * sizeof(float);
+  }
+  PNPX_HIP(hipMemset(N.arena.p, 0, P.total * sizeof(float)));
+  PNPX_HIP(hipDeviceSynchronize());
+  N.capB = nb;
+  N.capH = H;
+  N.capW = W;
+  return PNPX_OK;
+}
+
+struct Launch {   // one convolution launch of either pass
+  const ConvLayerHsDev* D = nullptr;
+  const float* bias = nullptr;
+  int taps = 0x1FF;
+  int epi = 0;            // ConvHsFuse::critic_epi (0: the plain linear instance)
+  float alpha = 0.f;
+  const CAct* res = nullptr;
+  const CAct* mask = nullptr;
+};
+int run_conv(pnpx_ctx* ctx, float* A, const Launch& L, const CAct& in, const CAct& out, int B, int h, int w, hipStream_t s) {
+  ConvLayerHs Lh;
+  Lh.cin = L.D->cin;
+  Lh.cout = L.D->cout;
+  Lh.cin_pad = L.D->cin_pad;
+  Lh.mt = L.D->mt;
+  Lh.w = L.D->w;
+  Lh.b = L.bias;
+  Lh.inv_scale = L.D->inv_scale;
+  ConvHsFuse f;
+  f.slope = 1.f;           // (read by the plain instance only: linear)
+  f.taps = L.taps;
+  f.wreg = 0;
+  f.in0_groups = in.C / 8;
+  f.critic_epi = L.epi;
+  f.alpha = L.alpha;
+  f.res = L.res ? reinterpret_cast<const char*>(A + L.res->off) : nullptr;
+  f.res_groups = L.res ? L.res->C / 8 : 0;
+  f.dmask = L.mask ? reinterpret_cast<const char*>(A + L.mask->off) : nullptr;
+  f.range_flag = ctx->opt_range_guard ? ctx->range_flag_dev : nullptr;
+  if (L.D->cout != out.C || L.D->cin_pad > in.C || (L.mask && L.mask->C != out.C) || (L.res && L.res->C > out.C)) {
+    set_error("critic: internal launch geometry mismatch (%d -> %d channels over %d -> %d)", L.D->cin_pad, L.D->cout, in.C, out.C);
+    return PNPX_ERR_SHAPE;
+  }
+  return launch_conv_hs(Lh, reinterpret_cast<const char*>(A + in.off), L.D->cin_pad / 8, nullptr, 0,
+                        reinterpret_cast<char*>(A + out.off), B, h, w, f, s);
+}
+
+// forward over B observations; every activation stays in the arena
+int run_forward(pnpx_ctx* ctx, const CriticPlan& P, const float* ob, int B, int H, int W, hipStream_t s) {
+  CriticNet& N = ctx->critic;
+  float* A = static_cast<float*>(N.arena.p);
+  auto rec = [&](const CAct& d) { return reinterpret_cast<HsRec*>(A + d.off); };
+  auto u4 = [&](const CAct& d) { return reinterpret_cast<uint4*>(A + d.off); };
+  auto trelu = [&](int li, const CAct& in, const CAct& out, const CAct* res, int h, int w) -> int {
+    Launch L;
+    L.D = &N.fwd[li];
+    L.bias = N.bias[li];
+    L.taps = fwd_taps(li);
+    L.epi = 1;
+    L.alpha = N.alpha[li];
+    L.res = res;
+    return run_conv(ctx, A, L, in, out, B, h, w, s);
+  };
+  const size_t n = (size_t)B * 4 * (N.cin_pad / 8) * (H / 2) * (W / 2);
+  hipLaunchKernelGGL(critic_pack_ob_kernel, g1(n), dim3(256), 0, s, ob, rec(P.ob_s), N.num_inputs, N.cin_pad, H, W, n);
+  PNPX_LAUNCH_CHECK();
+  PNPX_TRY(trelu(0, P.ob_s, P.stem_o, nullptr, H / 2, W / 2));
+  const size_t n2 = (size_t)B * 4 * 8 * (H / 4) * (W / 4) * 2;
+  hipLaunchKernelGGL(hs_s2d_kernel, g1(n2), dim3(256), 0, s, u4(P.stem_o), u4(P.stem_s), 8, H / 2, W / 2, n2);
+  PNPX_LAUNCH_CHECK();
+  for (int st = 0; st < 4; ++st) {
+    const int h = H >> (st + 2), w = W >> (st + 2), l0 = 1 + 5 * st;
+    const CAct& s2in = st == 0 ? P.stem_s : P.o1s[st - 1];
+    PNPX_TRY(trelu(l0 + 0, s2in, P.t1[st], nullptr, h, w));
+    {   // shortcut: 1x1 over the phase-(0,0) channels, bias, no activation (the actor's instance)
+      Launch L;
+      L.D = &N.fwd[l0 + 1];
+      L.bias = N.bias[l0 + 1];
+      L.taps = 0x010;
+      PNPX_TRY(run_conv(ctx, A, L, s2in, P.sc[st], B, h, w, s));
+    }
+    PNPX_TRY(trelu(l0 + 2, P.t1[st], P.o0[st], &P.sc[st], h, w));
+    PNPX_TRY(trelu(l0 + 3, P.o0[st], P.t2[st], nullptr, h, w));
+    PNPX_TRY(trelu(l0 + 4, P.t2[st], P.o1[st], &P.o0[st], h, w));
+    if (st < 3) {
+      const int G = P.o1[st].C / 8;
+      const size_t n3 = (size_t)B * 4 * G * (h / 2) * (w / 2) * 2;
+      hipLaunchKernelGGL(hs_s2d_kernel, g1(n3), dim3(256), 0, s, u4(P.o1[st]), u4(P.o1s[st]), G, h, w, n3);
+      PNPX_LAUNCH_CHECK();
+    }
+  }
+  return PNPX_OK;
+}
+
+}  // namespace
+
+size_t critic_num_params(int num_inputs) {
+  size_t n = 2 * 64 + (size_t)64 * num_inputs * 9;
+  int in_planes = 64;
+  for (int s = 0; s < 4; ++s) {
+    const size_t p = stage_planes(s);
+    n += (2 * p + p * in_planes * 9) + (2 * p + p * p * 9) + (2 * p + p * in_planes) + 2;   // block 0
+    n += 2 * (2 * p + p * p * 9) + 2;                                                       // block 1
+    in_planes = (int)p;
+  }
+  return n + 512 + 1 + 1;   // fc.weight, fc.bias, relu_1.alpha
+}
+
+void critic_free(pnpx_ctx* ctx) {
+  CriticNet& N = ctx->critic;
+  if (N.weights.p) (void)hipFree(N.weights.p);
+  if (N.arena.p) (void)hipFree(N.arena.p);
+  N = CriticNet();
+}
+
+int critic_load(pnpx_ctx* ctx, const float* params, size_t n, int num_inputs) {
+  if (!params || num_inputs < 1 || num_inputs > 64 || n != critic_num_params(num_inputs)) {
+    set_error("pnpx_critic_load: expected %zu parameters for %d inputs (1..64), got %zu",
+              (num_inputs >= 1 && num_inputs <= 64) ? critic_num_params(num_inputs) : (size_t)0, num_inputs, n);
+    return PNPX_ERR_ARG;
+  }
+  PNPX_HIP(hipDeviceSynchronize());
+  critic_free(ctx);
+  CriticNet& N = ctx->critic;
+  N.num_inputs = num_inputs;
+  N.cin_pad = (num_inputs + 7) / 8 * 8;
+  Reader R{params};
+  auto take_wn = [&](int cout, size_t fan) {
+    WnConv c;
+    c.b = R.take(cout);
+    c.g = R.take(cout);
+    c.v = R.take((size_t)cout * fan);
+    return c;
+  };
+  HostBlob H;
+  Packed pf[NL], pb[NL];
+  float alpha[NL] = {};
+  auto finish = [&](int li, const Eff& E) {
+    pf[li] = pack_layer(H, E, fwd_taps(li), true);
+    pb[li] = pack_layer(H, adjoint(E), bwd_taps(li), false);
+  };
+  {
+    const WnConv c = take_wn(64, (size_t)num_inputs * 9);
+    Eff E(64, 4 * N.cin_pad);
+    put_conv_s2(E, c, 64, num_inputs, N.cin_pad);
+    finish(0, E);
+  }
+  int in_planes = 64;
+  for (int s = 0; s < 4; ++s) {
+    const int p = stage_planes(s), l0 = 1 + 5 * s;
+    // block 0: conv1 (stride 2), conv2, shortcut.0, relu_1.alpha, relu_2.alpha -- registration order
+    const WnConv c1 = take_wn(p, (size_t)in_planes * 9);
+    const WnConv c2 = take_wn(p, (size_t)p * 9);
+    const WnConv cs = take_wn(p, (size_t)in_planes);
+    alpha[l0 + 0] = *R.take(1);
+    alpha[l0 + 2] = *R.take(1);
+    {
+      Eff E(p, 4 * in_planes);
+      put_conv_s2(E, c1, p, in_planes, in_planes);
+      finish(l0 + 0, E);
+    }
+    {
+      Eff E(p, in_planes);
+      put_shortcut(E, cs, p, in_planes);
+      finish(l0 + 1, E);
+    }
+    {
+      Eff E(p, p);
+      put_conv_s1(E, c2, p, p);
+      finish(l0 + 2, E);
+    }
+    // block 1: conv1, conv2, relu_1.alpha, relu_2.alpha
+    const WnConv d1 = take_wn(p, (size_t)p * 9);
+    const WnConv d2 = take_wn(p, (size_t)p * 9);
+    alpha[l0 + 3] = *R.take(1);
+    alpha[l0 + 4] = *R.take(1);
+    {
+      Eff E(p, p);
+      put_conv_s1(E, d1, p, p);
+      finish(l0 + 3, E);
+    }
+    {
+      Eff E(p, p);
+      put_conv_s1(E, d2, p, p);
+      finish(l0 + 4, E);
+    }
+    in_planes = p;
+  }
+  const float* fcw = R.take(512);
+  const size_t o_fcw = H.add(fcw, 512);
+  const size_t o_fcb = H.add(R.take(1), 1);
+  alpha[0] = *R.take(1);
+  float wmax = 0.f;
+  for (int i = 0; i < 512; ++i) wmax = std::fmax(wmax, std::fabs(fcw[i]));
+  for (int i = 0; i < NL; ++i)
+    if (!std::isfinite(alpha[i])) {
+      set_error("pnpx_critic_load: TReLU threshold %d is not finite", i);
+      critic_free(ctx);
+      return PNPX_ERR_ARG;
+    }
+  H.align();
+  const size_t o_zero = H.f.size();
+  H.f.resize(H.f.size() + 1024, 0.f);
+  H.f.resize(H.f.size() + 8192, 0.f);   // DMA over-read slack
+  void* d = nullptr;
+  hipError_t e = hipMalloc(&d, H.f.size() * sizeof(float));
+  if (e != hipSuccess) {
+    set_error("critic weight allocation of %zu bytes failed: %s", H.f.size() * sizeof(float), hipGetErrorString(e));
+    return PNPX_ERR_ALLOC;
+  }
+  N.weights.p = d;
+  N.weights.bytes = H.f.size() * sizeof(float);
+  PNPX_HIP(hipMemcpy(d, H.f.data(), N.weights.bytes, hipMemcpyHostToDevice));
+  const float* base = static_cast<const float*>(d);
+  auto dev = [&](ConvLayerHsDev& D, const Packed& P) {
+    D.cin = D.cin_pad = P.cin;
+    D.cout = P.cout;
+    D.mt = P.mt;
+    D.w = const_cast<char*>(reinterpret_cast<const char*>(base + P.w));
+    D.inv_scale = 1.0f / (P.scale * HS_ASCALE);
+  };
+  for (int i = 0; i < NL; ++i) {
+    dev(N.fwd[i], pf[i]);
+    dev(N.bwd[i], pb[i]);
+    N.bias[i] = base + pf[i].b;
+    N.alpha[i] = alpha[i];
+  }
+  N.fc_w = base + o_fcw;
+  N.fc_b = base + o_fcb;
+  N.zero = base + o_zero;
+  N.fc_wmax = wmax;
+  N.loaded = true;
+  return PNPX_OK;
+}
+
+int critic_forward(pnpx_ctx* ctx, const float* ob, float* value, int B, int H, int W, hipStream_t s) {
+  CriticNet& N = ctx->critic;
+  PNPX_TRY(check_call(N, "critic forward", B, H, W));
+  PNPX_TRY(reserve(N, B, H, W));
+  const CriticPlan P = make_plan(N.capB, N.cin_pad, H, W);
+  PNPX_TRY(run_forward(ctx, P, ob, B, H, W, s));
+  const float* A = static_cast<const float*>(N.arena.p);
+  hipLaunchKernelGGL(critic_pool_fc_kernel, dim3(B), dim3(256), 0, s, reinterpret_cast<const HsRec*>(A + P.o1[3].off), H / 32, W / 32,
+                     N.fc_w, N.fc_b, value);
+  PNPX_LAUNCH_CHECK();
+  return PNPX_OK;
+}
+
+int critic_backward(pnpx_ctx* ctx, const float* ob, const float* grad_value, float* grad_ob, int B, int H, int W, hipStream_t s) {
+  CriticNet& N = ctx->critic;
+  PNPX_TRY(check_call(N, "critic backward", B, H, W));
+  PNPX_TRY(reserve(N, B, H, W));
+  const CriticPlan P = make_plan(N.capB, N.cin_pad, H, W);
+  PNPX_TRY(run_forward(ctx, P, ob, B, H, W, s));   // re-computation: every activation is now in the arena
+  float* A = static_cast<float*>(N.arena.p);
+  auto rec = [&](const CAct& d) { return reinterpret_cast<HsRec*>(A + d.off); };
+  auto u4 = [&](const CAct& d) { return reinterpret_cast<uint4*>(A + d.off); };
+  // (W^T g [+ res]) masked by the saved activation `mask` against the threshold of layer `mask_li`
+  auto grad = [&](int li, const CAct& in, const CAct& out, const CAct* res, const CAct* mask, int mask_li, int h, int w) -> int {
+    Launch L;
+    L.D = &N.bwd[li];
+    L.bias = N.zero;
+    L.taps = bwd_taps(li);
+    L.epi = 2;
+    L.alpha = mask ? N.alpha[mask_li] : 0.f;
+    L.res = res;
+    L.mask = mask;
+    return run_conv(ctx, A, L, in, out, B, h, w, s);
+  };
+  // gradient scale: a power of two that brings the head's largest entry max|fc_w| / (h w) into [1, 2)
+  const int hl = H / 32, wl = W / 32;
+  float gs = 1.f;
+  if (N.fc_wmax > 0.f) {
+    int e = 0;
+    std::frexp(N.fc_wmax / (float)(hl * wl), &e);
+    gs = std::ldexp(1.0f, 1 - e);
+  }
+  {
+    const size_t n = (size_t)B * 64 * hl * wl;
+    hipLaunchKernelGGL(critic_head_grad_kernel, g1(n), dim3(256), 0, s, rec(P.o1[3]), rec(P.gA[3]), N.fc_w, hs_roundtrip16(N.alpha[20]),
+                       gs * HS_ASCALE / (float)(hl * wl), hl, wl, n);
+    PNPX_LAUNCH_CHECK();
+  }
+  for (int st = 3; st >= 0; --st) {
+    const int h = H >> (st + 2), w = W >> (st + 2), l0 = 1 + 5 * st;
+    // block 1: o1 = TReLU(conv2(t2) + o0), t2 = TReLU(conv1(o0))
+    PNPX_TRY(grad(l0 + 4, P.gA[st], P.gM[st], nullptr, &P.t2[st], l0 + 3, h, w));
+    PNPX_TRY(grad(l0 + 3, P.gM[st], P.gB[st], &P.gA[st], &P.o0[st], l0 + 2, h, w));
+    // block 0: o0 = TReLU(conv2(t1) + shortcut(x)), t1 = TReLU(conv1(x)), x = space-to-depth input
+    PNPX_TRY(grad(l0 + 2, P.gB[st], P.gM[st], nullptr, &P.t1[st], l0 + 0, h, w));
+    {   // shortcut adjoint: 1x1, linear (the existing sparse-tap instance), to the phase-(0,0) channel groups
+      Launch L;
+      L.D = &N.bwd[l0 + 1];
+      L.bias = N.zero;
+      L.taps = 0x010;
+      PNPX_TRY(run_conv(ctx, A, L, P.gB[st], P.gR[st], B, h, w, s));
+    }
+    const CAct& x = st == 0 ? P.stem_s : P.o1s[st - 1];
+    PNPX_TRY(grad(l0 + 0, P.gM[st], P.gS[st], &P.gR[st], &x, st == 0 ? 0 : l0 - 1, h, w));
+    const CAct& below = st == 0 ? P.g_stem : P.gA[st - 1];
+    const int G = below.C / 8;
+    const size_t n = (size_t)B * G * (2 * h) * (2 * w) * 2;
+    hipLaunchKernelGGL(hs_d2s_kernel, g1(n), dim3(256), 0, s, u4(P.gS[st]), u4(below), G, h, w, n);
+    PNPX_LAUNCH_CHECK();
+  }
+  PNPX_TRY(grad(0, P.g_stem, P.g_ob, nullptr, nullptr, 0, H / 2, W / 2));   // stem adjoint: linear
+  const size_t n = (size_t)B * N.num_inputs * H * W;
+  hipLaunchKernelGGL(critic_ob_grad_kernel, g1(n), dim3(256), 0, s, rec(P.g_ob), grad_value, grad_ob, N.num_inputs, N.cin_pad, H, W,
+                     1.0f / (gs * HS_ASCALE), n);
+  PNPX_LAUNCH_CHECK();
+  return PNPX_OK;
+}
+
+}  // namespace pnpx

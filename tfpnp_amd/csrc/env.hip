@@ -116,6 +116,45 @@ __global__ __launch_bounds__(256) void policy_ob_pack_kernel(PackArgs a) {
   }
 }
 
+// adjoint of policy_ob_pack_kernel for dense rows: one thread per 4 consecutive pixels of one channel of grad_out
+struct UnpackArgs {
+  void* dst[ENV_MAX_T];
+  int kind[ENV_MAX_T];
+  int c[ENV_MAX_T];
+  int ch0[ENV_MAX_T];
+  int n_t, C_out, HW;
+  const float* g;           // [n_rows, C_out, H, W]
+};
+__global__ __launch_bounds__(256) void policy_ob_unpack_kernel(UnpackArgs a) {
+  const size_t row = blockIdx.z;
+  const int co = blockIdx.y;
+  const int q = blockIdx.x * blockDim.x + threadIdx.x;
+  if (q * 4 >= a.HW) return;
+  int t = 0;
+#pragma unroll
+  for (int k = 1; k < ENV_MAX_T; ++k)
+    if (k < a.n_t && co >= a.ch0[k]) t = k;
+  const int kind = a.kind[t];
+  if (kind == 3) return;
+  const int cl = co - a.ch0[t];
+  const int p0 = q * 4;
+  const int np = min(4, a.HW - p0);
+  const float* g = a.g + (row * a.C_out + co) * (size_t)a.HW + p0;
+  if (kind == 0) {
+    float* d = static_cast<float*>(a.dst[t]) + (row * a.c[t] + cl) * (size_t)a.HW + p0;
+    for (int j = 0; j < np; ++j) d[j] = g[j];
+  } else if (kind == 1) {
+    float* d = static_cast<float*>(a.dst[t]) + ((row * a.c[t] + cl) * (size_t)a.HW + p0) * 2;
+    for (int j = 0; j < np; ++j) {
+      d[2 * j] = g[j];
+      d[2 * j + 1] = 0.f;
+    }
+  } else {
+    float* d = static_cast<float*>(a.dst[t]) + ((row * a.c[t] + (cl >> 1)) * (size_t)a.HW + p0) * 2 + (cl & 1);
+    for (int j = 0; j < np; ++j) d[2 * j] = g[j];
+  }
+}
+
 }  // namespace pnpx
 
 using namespace pnpx;
@@ -254,6 +293,39 @@ int pnpx_policy_ob_pack(pnpx_ctx* ctx, int n_entries, const void* const* src_hos
   a.out = out;
   const int quads = (a.HW + 3) / 4;
   hipLaunchKernelGGL(policy_ob_pack_kernel, dim3((quads + 255) / 256, co, n_rows), dim3(256), 0,
+                     static_cast<hipStream_t>(stream), a);
+  PNPX_LAUNCH_CHECK();
+  return PNPX_OK;
+}
+
+int pnpx_policy_ob_unpack(pnpx_ctx* ctx, int n_entries, void* const* dst_host, const int* kind_host,
+                          const int* channels_host, int n_rows, int H, int W, const float* grad_out, void* stream) {
+  LOCK_CTX(ctx);
+  if (n_entries <= 0 || n_entries > ENV_MAX_T || !dst_host || !kind_host || !channels_host || n_rows < 0 || H <= 0 ||
+      W <= 0 || (n_rows > 0 && !grad_out)) {
+    set_error("pnpx_policy_ob_unpack: bad arguments (at most %d entries)", ENV_MAX_T);
+    return PNPX_ERR_ARG;
+  }
+  if (n_rows == 0) return PNPX_OK;
+  UnpackArgs a{};
+  int co = 0;
+  for (int t = 0; t < n_entries; ++t) {
+    if (kind_host[t] < 0 || kind_host[t] > 3 || channels_host[t] <= 0 || (kind_host[t] != 3 && !dst_host[t])) {
+      set_error("pnpx_policy_ob_unpack: bad entry %d", t);
+      return PNPX_ERR_ARG;
+    }
+    a.dst[t] = dst_host[t];
+    a.kind[t] = kind_host[t];
+    a.c[t] = channels_host[t];
+    a.ch0[t] = co;
+    co += channels_host[t] * (kind_host[t] == 2 ? 2 : 1);
+  }
+  a.n_t = n_entries;
+  a.C_out = co;
+  a.HW = H * W;
+  a.g = grad_out;
+  const int quads = (a.HW + 3) / 4;
+  hipLaunchKernelGGL(policy_ob_unpack_kernel, dim3((quads + 255) / 256, co, n_rows), dim3(256), 0,
                      static_cast<hipStream_t>(stream), a);
   PNPX_LAUNCH_CHECK();
   return PNPX_OK;

@@ -96,6 +96,12 @@ class PnPEnv:
     def get_policy_ob(self, ob):
         parts = [(ob[key], kind) for key, kind in self.policy_layout]
         if parts and parts[0][0].is_cuda:
+            if torch.is_grad_enabled() and any(v.is_floating_point() and v.requires_grad for v, _ in parts):
+                # training path (the critic's value is differentiated into the actions through ob.variables,
+                # tfpnp/trainer/mddpg/trainer.py:180-192): the same launch behind an op whose backward is its adjoint
+                from .. import torch_ops as T
+                kinds = {'raw': 0, 'real': 1, 'channel': 2}
+                return T.call("policy_ob_pack_diff", [v for v, _ in parts], [kinds[k] for _, k in parts])
             return ops.policy_ob_pack(parts)          # one launch: views + channel concat fused
         views = {'real': transforms.complex2real, 'channel': transforms.complex2channel, 'raw': lambda v: v}
         return torch.cat([views[kind](v) for v, kind in parts], 1)

@@ -19,6 +19,28 @@ _ctx_ids = itertools.count(1)
 _ctx_by_id = weakref.WeakValueDictionary()
 
 
+def critic_flat_params(state_dict, num_inputs):
+    """The flat fp32 parameter vector pnpx_critic_load takes (synth.critic_param_specs order) from a critic state_dict.
+    Weight-norm entries are accepted under the reference's names (`*.weight_g` / `*.weight_v`) and under the names current
+    PyTorch saves the same module with (`*.parametrizations.weight.original0` / `original1`); a missing key or a wrong shape
+    raises PnpxError naming it."""
+    from .synth import critic_param_specs
+    alt = {"weight_g": "parametrizations.weight.original0", "weight_v": "parametrizations.weight.original1"}
+    chunks = []
+    for key, shape in critic_param_specs(num_inputs):
+        v = state_dict.get(key)
+        if v is None:
+            stem, _, leaf = key.rpartition(".")
+            v = state_dict.get(f"{stem}.{alt[leaf]}") if leaf in alt else None
+        if v is None:
+            raise PnpxError(f"critic state_dict is missing '{key}'")
+        v = v.detach().cpu().numpy() if isinstance(v, torch.Tensor) else np.asarray(v)
+        if tuple(v.shape) != tuple(shape):
+            raise PnpxError(f"'{key}' has shape {tuple(v.shape)}, expected {tuple(shape)}")
+        chunks.append(np.ascontiguousarray(v, dtype=np.float32).reshape(-1))
+    return np.concatenate(chunks)
+
+
 def context_by_id(cid):
     """The live Context with integer handle `cid` (how contexts travel through torch.ops.pnpx.* schemas)."""
     try:
@@ -41,6 +63,7 @@ class Context:
         self._has_weights = False
         self.is_drunet = False
         self._policy = None
+        self._critic = None
         self.cid = next(_ctx_ids)          # integer handle for the dispatcher-registered ops (torch_ops.py)
         _ctx_by_id[self.cid] = self
 
@@ -100,6 +123,13 @@ class Context:
         check(_lib.lib().pnpx_policy_load(self.handle, flat.ctypes.data_as(C.c_void_p), flat.size, int(num_inputs),
                                           int(n_det), int(bool(spi_head))))
         self._policy = (int(num_inputs), int(n_det))
+
+    def load_critic(self, state_dict, num_inputs):
+        """state_dict of the reference's ResNet_wobn(num_inputs, 18, 1) (tfpnp/trainer/mddpg/critic.py) -> native critic
+        (key spellings: critic_flat_params).  The weights are frozen until the next load."""
+        flat = critic_flat_params(state_dict, num_inputs)
+        check(_lib.lib().pnpx_critic_load(self.handle, flat.ctypes.data_as(C.c_void_p), flat.size, int(num_inputs)))
+        self._critic = int(num_inputs)
 
     def set_option(self, key, value):
         """e.g. set_option('conv_mode', 1) selects the fast half-split f16 MFMA convolutions (default 0 = fp32 arithmetic)."""
@@ -275,6 +305,38 @@ def policy_forward(ctx, ob):
     with torch.cuda.device(ob.device):
         check(_lib.lib().pnpx_policy_forward(ctx.handle, _p(ob), _p(probs), _p(det), B, H, W, _stream(ob)))
     return probs, det
+
+
+def _critic_ob(ctx, ob, who):
+    ob = _f32(ob, "ob")
+    if ob.dim() != 4 or getattr(ctx, "_critic", None) is None or ob.shape[1] != ctx._critic:
+        raise PnpxError(f"{who}: no critic loaded or observation has the wrong channel count")
+    return ob
+
+
+def critic_forward(ctx, ob):
+    """ob [B,C,H,W] -> V [B,1] of the loaded critic (tfpnp/trainer/mddpg/critic.py:121-131)."""
+    ob = _critic_ob(ctx, ob, "critic_forward")
+    B, _, H, W = ob.shape
+    value = torch.empty((B, 1), device=ob.device, dtype=torch.float32)
+    if B:
+        with torch.cuda.device(ob.device):
+            check(_lib.lib().pnpx_critic_forward(ctx.handle, _p(ob), _p(value), B, H, W, _stream(ob)))
+    return value
+
+
+def critic_backward(ctx, ob, grad_value):
+    """grad_ob [B,C,H,W] = grad_value[b] * dV_b / d ob_b (weights frozen; the forward is re-computed natively)."""
+    ob = _critic_ob(ctx, ob, "critic_backward")
+    grad_value = _f32(grad_value, "grad_value").reshape(-1)
+    B, _, H, W = ob.shape
+    if grad_value.numel() != B:
+        raise PnpxError(f"critic_backward: grad_value must have {B} entries, got {grad_value.numel()}")
+    grad_ob = torch.empty_like(ob)
+    if B:
+        with torch.cuda.device(ob.device):
+            check(_lib.lib().pnpx_critic_backward(ctx.handle, _p(ob), _p(grad_value), _p(grad_ob), B, H, W, _stream(ob)))
+    return grad_ob
 
 
 def unet_profile(ctx, x, sigma):
@@ -1038,3 +1100,27 @@ def policy_ob_pack(entries, idx=None, n_rows=None):
         check(_lib.lib().pnpx_policy_ob_pack(ctx.handle, n, S, K, CH, _p(idx) if idx is not None else None, rows, H, W,
                                              _p(out), _stream(out)))
     return out
+
+
+def policy_ob_unpack(grad_out, kinds, channels):
+    """Adjoint of policy_ob_pack for dense rows: grad_out [B, sum(channels), H, W] -> one gradient per entry with the
+    entry's shape ([B,c,H,W] for kind 0, [B,c,H,W,2] for kinds 1 / 2: imaginary part zero for 'real'); None for kind 3
+    (bool / uint8 entries).  kinds / channels: the pack's integer kinds (0 raw, 1 real, 2 channel, 3 u8) and source channels."""
+    g = _f32(grad_out, "grad_out")
+    kinds, channels = [int(k) for k in kinds], [int(c) for c in channels]
+    n = len(kinds)
+    if g.dim() != 4 or n == 0 or n != len(channels) or any(k not in (0, 1, 2, 3) for k in kinds) or \
+            g.shape[1] != sum(c * (2 if k == 2 else 1) for c, k in zip(channels, kinds)):
+        raise PnpxError("policy_ob_unpack: grad_out does not match the entry layout")
+    B, _, H, W = g.shape
+    outs = [None if k == 3 else torch.empty((B, c, H, W) + ((2,) if k else ()), dtype=torch.float32, device=g.device)
+            for k, c in zip(kinds, channels)]
+    if B == 0:
+        return outs
+    D = (C.c_void_p * n)(*[o.data_ptr() if o is not None else None for o in outs])
+    K = (C.c_int * n)(*kinds)
+    CH = (C.c_int * n)(*channels)
+    ctx = default_context(g.device)
+    with torch.cuda.device(g.device):
+        check(_lib.lib().pnpx_policy_ob_unpack(ctx.handle, n, D, K, CH, B, H, W, _p(g), _stream(g)))
+    return outs

@@ -194,6 +194,53 @@ def make_policy_params(num_inputs, n_det, spi_head=False, seed=0):
     return out
 
 
+# --------------------------------------------------------------------------- critic parameters
+def critic_param_specs(num_inputs):
+    """(key, shape) of ResNet_wobn(num_inputs, 18, 1).state_dict() in registration order (tfpnp/trainer/mddpg/critic.py:
+    95-131; 82 entries).  A weight-normalised convolution registers bias, weight_g [cout,1,1,1], weight_v (critic.py:7-8);
+    every TReLU one scalar alpha (critic.py:11-19)."""
+    specs = []
+
+    def wn(prefix, cout, cin, k):
+        specs.append((f"{prefix}.bias", (cout,)))
+        specs.append((f"{prefix}.weight_g", (cout, 1, 1, 1)))
+        specs.append((f"{prefix}.weight_v", (cout, cin, k, k)))
+
+    wn("conv1", 64, num_inputs, 3)
+    in_planes = 64
+    for li, planes in enumerate((64, 128, 256, 512), start=1):
+        for blk in range(2):
+            pre = f"layer{li}.{blk}"
+            wn(f"{pre}.conv1", planes, in_planes if blk == 0 else planes, 3)
+            wn(f"{pre}.conv2", planes, planes, 3)
+            if blk == 0:
+                wn(f"{pre}.shortcut.0", planes, in_planes, 1)
+            specs.append((f"{pre}.relu_1.alpha", (1,)))
+            specs.append((f"{pre}.relu_2.alpha", (1,)))
+        in_planes = planes
+    specs += [("fc.weight", (1, 512)), ("fc.bias", (1,)), ("relu_1.alpha", (1,))]
+    return specs
+
+
+def make_critic_params(num_inputs, seed=0):
+    """Synthetic critic weights (no trained critic ships with the reference): He-normal weight_v, weight_g ~ sqrt(2) *
+    U(0.5, 1.5) (the folded weight has He scale times U(0.5, 1.5)), biases and TReLU thresholds ~ N(0, 0.1^2) -- alpha is
+    non-zero and of either sign, so TReLU is distinguishable from ReLU --, fc.weight ~ N(0, 1/512)."""
+    rs = np.random.RandomState(seed)
+    out = {}
+    for key, shape in critic_param_specs(num_inputs):
+        if key.endswith("weight_v"):
+            fan_in = shape[1] * shape[2] * shape[3]
+            out[key] = (rs.standard_normal(shape) * math.sqrt(2.0 / fan_in)).astype(np.float32)
+        elif key.endswith("weight_g"):
+            out[key] = (math.sqrt(2.0) * rs.uniform(0.5, 1.5, shape)).astype(np.float32)
+        elif key == "fc.weight":
+            out[key] = (rs.standard_normal(shape) * math.sqrt(1.0 / 512)).astype(np.float32)
+        else:
+            out[key] = (rs.standard_normal(shape) * 0.1).astype(np.float32)
+    return out
+
+
 # --------------------------------------------------------------------------- images
 def phantom(H, W, seed):
     """Smooth ellipse phantom in [0,1], float32 [H,W]."""

@@ -10,7 +10,7 @@ A native context (packed denoiser weights + workspaces) cannot travel through an
 integer handle `ctx` (tfpnp_amd.ops.Context.cid; 0 = the weight-less default context of the tensors' device).
 `iter_num = -1` means "all columns of the hyper-parameter tensors" (the reference's iter_num=None).
 """
-from typing import Tuple
+from typing import List, Sequence, Tuple
 
 import torch
 from torch import Tensor
@@ -470,6 +470,93 @@ def ct_pg(variables: Tensor, y0: Tensor, n_view: int, opnorm: float, sigma_d: Te
 
 ct_pg.register_fake(_same)
 
+# ------------------------------------------------------------------------------------------------- value network
+@_lib_def("pnpx::critic_value", mutates_args=(), device_types="cuda")
+def critic_value(ob: Tensor, ctx: int) -> Tensor:
+    """ResNet_wobn(num_inputs, 18, 1).forward (tfpnp/trainer/mddpg/critic.py:121-131): ob [B,C,H,W] -> V [B,1]."""
+    return ops.critic_forward(ops.context_by_id(ctx), ob)
+
+
+@critic_value.register_fake
+def _(ob, ctx):
+    return torch.empty((ob.shape[0], 1), dtype=ob.dtype, device=ob.device)
+
+
+@_lib_def("pnpx::critic_backward", mutates_args=(), device_types="cuda")
+def critic_backward(ob: Tensor, grad_value: Tensor, ctx: int) -> Tensor:
+    """VJP of critic_value wrt ob (frozen weights; the forward is re-computed inside)."""
+    return ops.critic_backward(ops.context_by_id(ctx), ob, grad_value)
+
+
+@critic_backward.register_fake
+def _(ob, grad_value, ctx):
+    return torch.empty_like(ob, memory_format=torch.contiguous_format)
+
+
+def _critic_setup(ctx, inputs, output):
+    ob, cid = inputs
+    ctx.save_for_backward(ob)
+    _pin(ctx, cid, ob)
+
+
+def _critic_bwd(ctx, g):
+    (ob,) = ctx.saved_tensors
+    return torch.ops.pnpx.critic_backward(ob, g.contiguous(), ctx.cid), None
+
+
+critic_value.register_autograd(_critic_bwd, setup_context=_critic_setup)
+
+
+# ------------------------------------------------------------------------------------------------- observation pack
+def _pack_kind(t, kind):
+    """integer kind of a pack entry (ops._PACK_KINDS): bool / uint8 'raw' entries are kind 3"""
+    return 3 if kind == 0 and t.dtype in (torch.bool, torch.uint8) else kind
+
+
+@_lib_def("pnpx::policy_ob_pack_diff", mutates_args=(), device_types="cuda")
+def policy_ob_pack_diff(entries: Sequence[Tensor], kinds: Sequence[int]) -> Tensor:
+    """get_policy_ob / get_eval_ob (tasks/*/env.py) with an autograd formula: entries in channel order, kinds[i] = 0 raw
+    [B,c,H,W] (fp32, or bool / uint8 without gradient), 1 complex2real, 2 complex2channel of [B,c,H,W,2] -> [B,C,H,W]."""
+    names = {0: "raw", 1: "real", 2: "channel"}
+    return ops.policy_ob_pack([(t, names[k]) for t, k in zip(entries, kinds)])
+
+
+@policy_ob_pack_diff.register_fake
+def _(entries, kinds):
+    t0 = entries[0]
+    C_out = sum(t.shape[1] * (2 if k == 2 else 1) for t, k in zip(entries, kinds))
+    return torch.empty((t0.shape[0], C_out, t0.shape[2], t0.shape[3]), dtype=torch.float32, device=t0.device)
+
+
+@_lib_def("pnpx::policy_ob_unpack", mutates_args=(), device_types="cuda")
+def policy_ob_unpack(grad_out: Tensor, kinds: Sequence[int], channels: Sequence[int]) -> List[Tensor]:
+    """Adjoint of policy_ob_pack_diff (pnpx_policy_ob_unpack): one gradient per entry; kind-3 entries (bool / uint8) get an
+    empty placeholder."""
+    outs = ops.policy_ob_unpack(grad_out, kinds, channels)
+    return [o if o is not None else grad_out.new_empty((0,)) for o in outs]
+
+
+@policy_ob_unpack.register_fake
+def _(grad_out, kinds, channels):
+    B, _, H, W = grad_out.shape
+    return [grad_out.new_empty((0,)) if k == 3 else grad_out.new_empty((B, c, H, W) + ((2,) if k else ()))
+            for k, c in zip(kinds, channels)]
+
+
+def _pack_setup(ctx, inputs, output):
+    entries, kinds = inputs
+    ctx.kinds = [_pack_kind(t, k) for t, k in zip(entries, kinds)]
+    ctx.channels = [t.shape[1] for t in entries]
+
+
+def _pack_bwd(ctx, g):
+    grads = torch.ops.pnpx.policy_ob_unpack(g.contiguous(), ctx.kinds, ctx.channels)
+    return [None if k == 3 else gi for k, gi in zip(ctx.kinds, grads)], None
+
+
+policy_ob_pack_diff.register_autograd(_pack_bwd, setup_context=_pack_setup)
+
+
 def call(name, *args):
     """torch.ops.pnpx.<name>(*args) with the package's error contract: tensors that are not on a ROCm device raise
     PnpxError (there is no CPU kernel to dispatch to) instead of the dispatcher's NotImplementedError."""
@@ -483,4 +570,5 @@ ALL_OPS = ("unet_denoise", "unet_denoise_preclamp", "unet_denoise_backward", "un
            "unet_denoise_backward_ticket", "policy_forward", "fft2", "cdp_forward",
            "cdp_backward", "spi_inverse", "psnr", "radon_forward", "radon_backprojection", "csmri_admm", "csmri_admm_train",
            "csmri_admm_backward", "csmri_hqs", "csmri_amp",
-           "csmri_pg", "csmri_apg", "csmri_redadmm", "pr_iadmm", "spi_admm", "ct_iadmm", "ct_pg", "pr_pg")
+           "csmri_pg", "csmri_apg", "csmri_redadmm", "pr_iadmm", "spi_admm", "ct_iadmm", "ct_pg", "pr_pg",
+           "critic_value", "critic_backward", "policy_ob_pack_diff", "policy_ob_unpack")
