@@ -341,19 +341,22 @@ def test_round3_execution_options_are_bit_identical(unet_params):
                     assert torch.equal(pre, ref), (B, H, W, wreg, chains)
         ctx.set_option("wreg", defaults["wreg"])
         ctx.set_option("chains", defaults["chains"])
-        d = synth.make_csmri_batch(9, 256, 256, ratio=4, seed=17)      # 9 images: one full XCD group + a plain-mapped image
         g = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev())
         a = synth.make_actions(9)[0]
         sol = ADMMSolver_CSMRI(den)
-        v0 = sol.reset({"x0": g(d["x0"])})
-        ref = None
-        for aff in (1, 0):
-            for tile in (0, 512, 2048, 4096):
-                ctx.set_option("fft_affine", aff)
-                ctx.set_option("fft_tile", tile)
-                out = sol((v0, (g(d["y0"]), g(d["mask"]))), (g(a["sigma_d"]), g(a["mu"])))
-                ref = out.clone() if ref is None else ref
-                assert torch.equal(out, ref), (aff, tile)
+        # 9 images: one full XCD group + a plain-mapped image.  256 x 256: both passes on the register-radix-16 kernels, which ignore
+        # the tile size; 128 x 160: generic passes, whose tile geometry fft_tile moves (6 / 3 / 12 / 25 rows, 8 / 4 / 16 / 32 columns)
+        for (H, W) in [(256, 256), (128, 160)]:
+            d = synth.make_csmri_batch(9, H, W, ratio=4, seed=17)
+            v0 = sol.reset({"x0": g(d["x0"])})
+            ref = None
+            for aff in (1, 0):
+                for tile in (0, 512, 2048, 4096):
+                    ctx.set_option("fft_affine", aff)
+                    ctx.set_option("fft_tile", tile)
+                    out = sol((v0, (g(d["y0"]), g(d["mask"]))), (g(a["sigma_d"]), g(a["mu"])))
+                    ref = out.clone() if ref is None else ref
+                    assert torch.equal(out, ref), (H, W, aff, tile)
     finally:
         for k, v in defaults.items():
             ctx.set_option(k, v)

@@ -195,6 +195,7 @@ struct pnpx_ctx {
   int opt_fft_tile = 0;            // complex points per FFT workgroup tile (0 = FFT_TILE_POINTS)
   int opt_fft_fast = 1;            // N = 256 lines on the register-radix-16 FFT kernels (fft_lds.h fft256_*)
   int opt_fft_affine = 1;          // XCD-affine block -> image mapping of the FFT passes (fft_lds.h)
+  int lds_block_limit = 0;         // the device's per-block LDS limit in bytes (queried by the first FFT plan; 0 = not yet)
   int opt_chains = 0;              // denoiser forward as n independent launch chains over slices of the batch (0 = auto)
   std::vector<hipStream_t> side_streams;
   // fork / join events of the launch chains: a ROTATING pool.  An event must not be re-recorded while a hipStreamWaitEvent on

@@ -81,6 +81,19 @@ int make_fft_plan(pnpx_ctx* ctx, int n_img, int H, int W, bool centered, FftPlan
   if (lc < 1) lc = 1;
   if (lc > W) lc = W;
   if (lc > 64) lc = 64;
+  // Option fft_tile goes up to 8192 points, i.e. up to 160 KiB for the two LDS copies of a tile of short lines, and these kernels do not
+  // opt in to more dynamic LDS than a workgroup gets by default: keep a tile within the device's per-block limit (never below 64 KiB, what
+  // every CDNA part has; one line of FFT_MAX_N points needs 32 KiB).  Tile geometry is scheduling only: results do not move, and the
+  // default tile (at most 32 KiB) is never clamped.
+  if (!ctx->lds_block_limit) {
+    int v = 0;
+    if (hipDeviceGetAttribute(&v, hipDeviceAttributeMaxSharedMemoryPerBlock, ctx->device) != hipSuccess) v = 0;
+    ctx->lds_block_limit = v < FFT_LDS_FLOOR ? FFT_LDS_FLOOR : v;
+  }
+  const int max_lr = (int)((size_t)ctx->lds_block_limit / (sizeof(float2) * 2 * (size_t)(W + 1)));
+  const int max_lc = (int)((size_t)ctx->lds_block_limit / (sizeof(float2) * 2 * (size_t)(H + 1)));
+  if (lr > max_lr) lr = max_lr;
+  if (lc > max_lc) lc = max_lc;
   PNPX_TRY(make_pass(ctx, n_img, H, W, W, centered, lr, &P->rows));
   PNPX_TRY(make_pass(ctx, n_img, H, W, H, centered, lc, &P->cols));
   // XCD-affine image mapping (fft_lds.h): every pass of a chain keeps an image on one XCD, so the k-space round trips

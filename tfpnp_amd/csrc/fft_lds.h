@@ -24,6 +24,7 @@ namespace pnpx {
 constexpr int FFT_THREADS = 256;
 constexpr int FFT_TILE_POINTS = 1024;   // complex points per workgroup tile (r3 sweep at 48 x 256^2: 512 / 1024 / 2048 / 4096 -> 124 / 109 / 140 / 210 us per ADMM iteration for the three passes)
 constexpr int FFT_MAX_N = 2048;   // one line (+ ping-pong copy) must fit LDS
+constexpr int FFT_LDS_FLOOR = 64 * 1024;   // dynamic LDS a workgroup may always ask for; make_fft_plan clamps its tiles to the device's limit
 
 __device__ __forceinline__ float2 cmul(float2 a, float2 b) {
   return make_float2(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x);

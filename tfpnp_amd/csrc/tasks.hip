@@ -654,6 +654,22 @@ static void launch_radon_forward(const float* img, size_t istride, const float* 
   hipLaunchKernelGGL(radon_forward_kernel, dim3((unsigned)(8 * (((size_t)B + 7) / 8) * bpi)), dim3(256), 0, s, pad, padT, sub, sino, cs,
                      R, V, det, B);
 }
+// The backprojection kernels promise the oracle's fp32 operations in the oracle's order (oracle/pnp_oracle.py:radon_backprojection).
+// __fmul_rn / __fadd_rn are plain `*` / `+` to the compiler, which contracts them into FMAs under the default -ffp-contract: a detector
+// position that is one ulp off then weighs a steep sinogram edge differently (4.6e-6 of the image maximum at R = 97).  These variants
+// switch contraction off where the operation is formed, so a product and a sum built from them stay two rounded operations.
+__device__ __forceinline__ float mulx(float a, float b) {
+#pragma clang fp contract(off)
+  return a * b;
+}
+__device__ __forceinline__ float addx(float a, float b) {
+#pragma clang fp contract(off)
+  return a + b;
+}
+__device__ __forceinline__ float subx(float a, float b) {
+#pragma clang fp contract(off)
+  return a - b;
+}
 // Pixel-driven backprojection: one thread per pixel, linear interpolation along the detector.
 __global__ void radon_backproject_kernel(const float* __restrict__ sino, float* __restrict__ img,
                                          const float2* __restrict__ cs, int R, int V, int det, int B, float scale) {
@@ -662,16 +678,16 @@ __global__ void radon_backproject_kernel(const float* __restrict__ sino, float* 
   const int x = (int)(i % R), y = (int)((i / R) % R);
   const int b = (int)(i / ((size_t)R * R));
   const float off = (float)R / 2.f - 0.5f, half = (float)det / 2.f - 0.5f;
-  const float xs = subr((float)x, off), ys = subr((float)y, off);
+  const float xs = subx((float)x, off), ys = subx((float)y, off);
   float acc = 0.f;
   for (int v = 0; v < V; ++v) {
-    const float sp = addr(addr(mulr(xs, cs[v].x), mulr(ys, cs[v].y)), half);
+    const float sp = addx(addx(mulx(xs, cs[v].x), mulx(ys, cs[v].y)), half);
     const float f0 = floorf(sp);
     const int s0 = (int)f0;
-    const float f = subr(sp, f0);
+    const float f = subx(sp, f0);
     const float* row = sino + ((size_t)b * V + v) * det;
-    if (s0 >= 0 && s0 < det) acc = addr(acc, mulr(row[s0], subr(1.f, f)));
-    if (s0 + 1 >= 0 && s0 + 1 < det) acc = addr(acc, mulr(row[s0 + 1], f));
+    if (s0 >= 0 && s0 < det) acc = addx(acc, mulx(row[s0], subx(1.f, f)));
+    if (s0 + 1 >= 0 && s0 + 1 < det) acc = addx(acc, mulx(row[s0 + 1], f));
   }
   img[i] = scale == 1.f ? acc : divr(acc, scale);
 }
@@ -701,25 +717,25 @@ __global__ __launch_bounds__(256) void radon_backproject_lds_kernel(const float*
   __syncthreads();
   const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
   const int x = x0 + tx;
-  const float xs = subr((float)min(x, R - 1), off);     // (pixels past the image edge compute inside the window, are not stored)
+  const float xs = subx((float)min(x, R - 1), off);     // (pixels past the image edge compute inside the window, are not stored)
   float ys[4], acc[4];
 #pragma unroll
   for (int j = 0; j < 4; ++j) {
-    ys[j] = subr((float)min(y0 + ty + 8 * j, R - 1), off);
+    ys[j] = subx((float)min(y0 + ty + 8 * j, R - 1), off);
     acc[j] = 0.f;
   }
   for (int v = 0; v < V; ++v) {
     const float2 t = cs[v];
     const float* row = rb_lds + v * RBP_WIN - base[v];
-    const float xc = mulr(xs, t.x);
+    const float xc = mulx(xs, t.x);
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
-      const float sp = addr(addr(xc, mulr(ys[j], t.y)), half);
+      const float sp = addx(addx(xc, mulx(ys[j], t.y)), half);
       const float f0 = floorf(sp);
       const int s0 = (int)f0;
-      const float f = subr(sp, f0);
-      acc[j] = addr(acc[j], mulr(row[s0], subr(1.f, f)));
-      acc[j] = addr(acc[j], mulr(row[s0 + 1], f));
+      const float f = subx(sp, f0);
+      acc[j] = addx(acc[j], mulx(row[s0], subx(1.f, f)));
+      acc[j] = addx(acc[j], mulx(row[s0 + 1], f));
     }
   }
   if (x < R) {
