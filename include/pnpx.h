@@ -198,8 +198,10 @@ int pnpx_policy_forward(pnpx_ctx* ctx, const float* ob, float* probs, float* det
  * tasks/<task>/main.py): 3x3 stride-2 stem, four stages of two BasicBlocks (critic.py:37-60) each entered with stride 2 and a 1x1
  * stride-2 shortcut, adaptive_avg_pool2d(1), Linear(512, 1).  Convolutions are weight-normalised with bias
  * (weight = weight_g * weight_v / ||weight_v||, norm per output channel; critic.py:7-8); activations are TReLU
- * (relu(x - alpha) + alpha, one scalar alpha each; critic.py:11-19).  Weights are FROZEN between loads: weight-norm is folded on the
- * host at load and only the gradient with respect to the observation is computed.  One critic per context.
+ * (relu(x - alpha) + alpha, one scalar alpha each; critic.py:11-19).  Only the gradient with respect to the observation is
+ * computed; there are no weight gradients.  The weights are LIVE: the context keeps the raw parameter vector on the device, and
+ * pnpx_critic_load_device / pnpx_critic_soft_update (below) replace or move it and re-derive the packed weights on the device.
+ * pnpx_critic_load folds weight-norm and packs on the host (once per checkpoint).  One critic per context.
  * params_host: the fp32 content of state_dict() in registration order (82 tensors),
  *   conv1.{bias, weight_g, weight_v},
  *   for L in layer1..layer4:  L.0.{conv1.*, conv2.*, shortcut.0.*, relu_1.alpha, relu_2.alpha},
@@ -209,6 +211,25 @@ int pnpx_policy_forward(pnpx_ctx* ctx, const float* ob, float* probs, float* det
  * (env.get_eval_ob, tfpnp/env/base.py; 1..64).  pnpx_critic_num_params returns 0 for a num_inputs outside that range. */
 size_t pnpx_critic_num_params(int num_inputs);
 int pnpx_critic_load(pnpx_ctx* ctx, const float* params_host, size_t n_params, int num_inputs);
+/* The same load from a parameter vector in DEVICE memory (same order, same length): weight-norm fold, per-convolution scale and
+ * both packings run as a handful of kernels on `stream` and produce the weight bytes pnpx_critic_load produces.  The first
+ * load (or one with another num_inputs) allocates; every later call with the same num_inputs refreshes in place: no allocation,
+ * no device-wide synchronisation, the activation workspace is kept.  Each call ends with one small stream-ordered read-back and
+ * a synchronisation of `stream` (the launches take the weight scales and TReLU thresholds by value); a threshold that is not
+ * finite returns PNPX_ERR_ARG and leaves the context without a critic, as pnpx_critic_load does.  Not capturable into a graph.
+ * Must be issued on the stream the critic's other calls use: that stream alone orders the refresh behind earlier evaluations
+ * and ahead of later ones.  params_dev may be dropped once the call returns. */
+int pnpx_critic_load_device(pnpx_ctx* ctx, const float* params_dev, size_t n_params, int num_inputs, void* stream);
+/* utils/misc.py:81-85 soft_update with this critic as the target: params[i] = params[i] * one_minus_tau + src[i] * tau, the two
+ * products and the sum each rounded to fp32 (what `target * (1.0 - tau) + source * tau` computes on fp32 tensors; pass
+ * (float)(1.0 - tau) and (float)tau, computed in double), followed by the device-side refresh of pnpx_critic_load_device with
+ * its stream rules and its read-back.  src_params_dev: n_params floats on the device in pnpx_critic_load's order.  Works on a
+ * critic loaded by either entry; PNPX_ERR_NO_WEIGHTS before a load. */
+int pnpx_critic_soft_update(pnpx_ctx* ctx, const float* src_params_dev, size_t n_params, float one_minus_tau, float tau,
+                            void* stream);
+/* Copies the live parameter vector (n_params floats, pnpx_critic_load's order) to dst_dev, ordered on `stream`.
+ * PNPX_ERR_NO_WEIGHTS before a load. */
+int pnpx_critic_params(pnpx_ctx* ctx, float* dst_dev, size_t n_params, void* stream);
 /* ob [B,num_inputs,H,W] (device, contiguous; H, W positive multiples of 32) -> value [B] (critic.py:121-131).
  * PNPX_ERR_NO_WEIGHTS before a load.  A row's value does not depend on the batch it arrives in. */
 int pnpx_critic_forward(pnpx_ctx* ctx, const float* ob, float* value, int B, int H, int W, void* stream);

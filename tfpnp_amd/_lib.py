@@ -52,6 +52,9 @@ _SIGNATURES = {
     "pnpx_policy_forward": (C.c_int, [c_void_p, _P, _P, _P, C.c_int, C.c_int, C.c_int, c_void_p]),
     "pnpx_critic_num_params": (C.c_size_t, [C.c_int]),
     "pnpx_critic_load": (C.c_int, [c_void_p, c_void_p, C.c_size_t, C.c_int]),
+    "pnpx_critic_load_device": (C.c_int, [c_void_p, _P, C.c_size_t, C.c_int, c_void_p]),
+    "pnpx_critic_soft_update": (C.c_int, [c_void_p, _P, C.c_size_t, C.c_float, C.c_float, c_void_p]),
+    "pnpx_critic_params": (C.c_int, [c_void_p, _P, C.c_size_t, c_void_p]),
     "pnpx_critic_forward": (C.c_int, [c_void_p, _P, _P, C.c_int, C.c_int, C.c_int, c_void_p]),
     "pnpx_critic_backward": (C.c_int, [c_void_p, _P, _P, _P, C.c_int, C.c_int, C.c_int, c_void_p]),
     "pnpx_unet_profile": (C.c_int, [c_void_p, _P, _P, _P, C.c_int, C.c_int, C.c_int, c_void_p, C.c_int,

@@ -203,6 +203,22 @@ int pnpx_critic_load(pnpx_ctx* ctx, const float* params_host, size_t n_params, i
   return critic_load(ctx, params_host, n_params, num_inputs);
 }
 
+int pnpx_critic_load_device(pnpx_ctx* ctx, const float* params_dev, size_t n_params, int num_inputs, void* stream) {
+  LOCK_CTX(ctx);
+  return critic_load_device(ctx, params_dev, n_params, num_inputs, static_cast<hipStream_t>(stream));
+}
+
+int pnpx_critic_soft_update(pnpx_ctx* ctx, const float* src_params_dev, size_t n_params, float one_minus_tau, float tau,
+                            void* stream) {
+  LOCK_CTX(ctx);
+  return critic_soft_update(ctx, src_params_dev, n_params, one_minus_tau, tau, static_cast<hipStream_t>(stream));
+}
+
+int pnpx_critic_params(pnpx_ctx* ctx, float* dst_dev, size_t n_params, void* stream) {
+  LOCK_CTX(ctx);
+  return critic_params(ctx, dst_dev, n_params, static_cast<hipStream_t>(stream));
+}
+
 int pnpx_critic_forward(pnpx_ctx* ctx, const float* ob, float* value, int B, int H, int W, void* stream) {
   LOCK_CTX(ctx);
   if (!ob || !value) {
@@ -400,7 +416,8 @@ size_t pnpx_ctx_bytes(const pnpx_ctx* ctx) {
   size_t n = ctx->weights.bytes + ctx->arena.buf.bytes + ctx->arena_grad.buf.bytes + ctx->scratch.bytes +
              ctx->drunet.weights.bytes + ctx->drunet.arena.bytes + ctx->drunet.arena_grad.bytes + ctx->drunet.f32_weights.bytes +
              ctx->drunet.f32_arena.bytes + ctx->drunet.f32_weights_bwd.bytes + ctx->drunet.f32_arena_grad.bytes +
-             ctx->policy.weights.bytes + ctx->policy.arena.bytes + ctx->critic.weights.bytes + ctx->critic.arena.bytes;
+             ctx->policy.weights.bytes + ctx->policy.arena.bytes + ctx->critic.weights.bytes + ctx->critic.arena.bytes +
+             ctx->critic.master.bytes + ctx->critic.pack_ws.bytes;
   for (const auto& sl : ctx->train_ring) n += sl.arena.buf.bytes + sl.pre.bytes;
   return n;
 }

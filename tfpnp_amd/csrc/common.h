@@ -111,7 +111,9 @@ struct PolicyNet {
   int capB = 0, capH = 0, capW = 0;
 };
 
-// Value network (critic.hip): ResNet_wobn(num_inputs, 18, 1), weight-norm folded at load, frozen.  Layer index: 0 = stem,
+// Value network (critic.hip): ResNet_wobn(num_inputs, 18, 1).  The raw parameters live on the device (`master`); the packed
+// weights the launches read are derived from them, on the host by critic_load and on the device by every later refresh
+// (critic_load_device, critic_soft_update).  Layer index: 0 = stem,
 // 1 + 5 * stage + {0 entry conv1 (stride 2), 1 shortcut (1x1 stride 2), 2 conv2, 3 block-1 conv1, 4 block-1 conv2}.
 struct CriticNet {
   bool loaded = false;
@@ -125,6 +127,10 @@ struct CriticNet {
   float fc_wmax = 0.f;               // max |fc_w|: the backward pass scales its gradients to O(1)
   DeviceBuf weights, arena;          // arena: every forward activation + the gradient tensors, zero borders
   int capB = 0, capH = 0, capW = 0;
+  // live weights: the flat fp32 parameter vector (pnpx_critic_load's order) and what the device-side packing needs
+  DeviceBuf master;                  // [critic_num_params(num_inputs)] floats
+  DeviceBuf pack_ws;                 // layer table, per-channel fold scales and maxima, the block read back per refresh
+  float* readback = nullptr;         // pinned host copy of that block: 21 weight scales, 21 thresholds, max |fc_w|
 };
 
 // number of independent launch chains for a B-image denoiser forward (unet.hip; option "chains", 0 = automatic)
@@ -379,6 +385,9 @@ void policy_free(pnpx_ctx* ctx);
 // Value network (critic.hip)
 size_t critic_num_params(int num_inputs);
 int critic_load(pnpx_ctx* ctx, const float* params, size_t n, int num_inputs);
+int critic_load_device(pnpx_ctx* ctx, const float* params_dev, size_t n, int num_inputs, hipStream_t s);
+int critic_soft_update(pnpx_ctx* ctx, const float* src_dev, size_t n, float one_minus_tau, float tau, hipStream_t s);
+int critic_params(pnpx_ctx* ctx, float* dst_dev, size_t n, hipStream_t s);
 int critic_forward(pnpx_ctx* ctx, const float* ob, float* value, int B, int H, int W, hipStream_t s);
 int critic_backward(pnpx_ctx* ctx, const float* ob, const float* grad_value, float* grad_ob, int B, int H, int W, hipStream_t s);
 void critic_free(pnpx_ctx* ctx);

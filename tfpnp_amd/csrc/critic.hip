@@ -1,4 +1,12 @@
-// Value network (critic) forward and input gradient -- frozen weights.
+// Value network (critic) forward and input gradient, live weights (no weight gradients).
+//
+// Live weights: the context keeps the flat fp32 parameter vector on the device (CriticNet::master).  pnpx_critic_load folds
+// weight-norm and packs on the host; pnpx_critic_load_device and pnpx_critic_soft_update derive the same packed blob from
+// the device vector with four launches ("device-side packing" below) and refresh an already loaded critic in place -- no
+// allocation, no device-wide synchronisation, the arena is kept.  Thresholds, weight scales and max |fc_w| are launch
+// arguments, so each refresh ends with one small read-back and a synchronisation of the caller's stream: a refresh cannot be
+// captured into a graph and has to be issued on the stream the critic's other calls use.  Still missing: weight gradients,
+// value_loss, optimiser steps, a trainer; the same refresh for the actor (policy.hip).
 //
 // Replaces ResNet_wobn(num_inputs, 18, 1).forward (tfpnp/trainer/mddpg/critic.py:95-131) and the autograd pass through it
 // with respect to its INPUT, which is how the actor loss uses it (trainer/mddpg/trainer.py:180-192: V_next = critic(eval_ob2)
@@ -6,7 +14,7 @@
 //     x = TReLU(conv3x3(num_inputs, 64, stride 2)(ob))                       critic.py:102,122
 //     4 stages of 2 BasicBlocks (critic.py:37-60), each stage entered with stride 2 and a 1x1 stride-2 shortcut
 //     V = fc(adaptive_avg_pool2d(x, 1))                                      critic.py:128-130
-// Convolutions are weight-normalised with bias (w = g * v / ||v||, norm per output channel: folded on the host at load);
+// Convolutions are weight-normalised with bias (w = g * v / ||v||, norm per output channel: folded whenever the weights change);
 // TReLU(t) = relu(t - alpha) + alpha = max(t, alpha) with one scalar alpha per activation (critic.py:11-19).
 //
 // The topology is the actor's (policy.hip), so the forward runs on the same half-split launches: the stem and the stage
@@ -242,6 +250,296 @@ constexpr int NL = 21;
 inline int fwd_taps(int li) { return li == 0 ? 0x01B : ((li - 1) % 5 == 0 ? 0x01B : ((li - 1) % 5 == 1 ? 0x010 : 0x1FF)); }
 inline int bwd_taps(int li) { return li == 0 ? 0x1B0 : ((li - 1) % 5 == 0 ? 0x1B0 : ((li - 1) % 5 == 1 ? 0x010 : 0x1FF)); }
 
+// ------------------------------------------------------------------------------------------- device-side packing
+// The same weight blob from a parameter vector in DEVICE memory, bit for bit (header comment, "Live weights").  One table
+// describes all 21 convolutions; a refresh is four launches over it:
+//   critic_fold_kernel   per output channel: sc = g / ||v|| in double (the host's summation order) and max |folded weight|
+//   critic_scale_kernel  per convolution: the power-of-two weight scale; thresholds and max |fc_w| into the read-back block
+//   critic_pack_kernel   per 16-byte destination fragment pair (hi, lo): gathers its eight source elements, or zeros
+//   critic_copy_kernel   biases and fc
+struct FoldDesc {     // one weight-normalised convolution of the parameter vector
+  unsigned src_g, src_v;   // floats into the parameter vector
+  unsigned chan0;          // its first output channel in the per-channel arrays
+  int cout, fan;
+  int alpha_src;           // threshold of the TReLU behind it (floats into the parameter vector), -1: none (shortcuts)
+};
+struct PackDesc {     // one packing: [rows/mt][K/16][nt][hi,lo][kg][mt][8] f16 at blob + dst
+  unsigned src_v, chan0, dst;
+  unsigned items;          // (hi, lo) fragment pairs = rows * K / 8 * nt
+  int conv;                // convolution (scale index)
+  int rows, K, mt, nt;
+  int kind;                // 0: 3x3 stride 1 (put_conv_s1); 1: 3x3 stride 2 over the space-to-depth input (put_conv_s2); 2: 1x1 shortcut
+  int cin, Cp;             // source input channels; channels per phase of the space-to-depth input (kind 1)
+  int adj;                 // the adjoint: rows / K transposed, taps mirrored
+  int tap[9];
+};
+struct CopyDesc {
+  unsigned src, dst, n;
+};
+constexpr int NCOPY = NL + 2, NREAD = 2 * NL + 1;   // read-back block: NL weight scales, NL thresholds, max |fc_w|
+struct PackTable {
+  FoldDesc fold[NL];
+  PackDesc pack[2 * NL];   // 2 * li: forward, 2 * li + 1: adjoint
+  CopyDesc copy[NCOPY];
+  unsigned nchan, src_fcw;
+};
+struct CriticLayout {     // PackTable + the blob offsets (floats) the host needs
+  PackTable T;
+  size_t bias[NL], fcw, fcb, zero, total;
+  unsigned max_items;
+};
+
+// Offsets of HostBlob as critic_load fills it (256-float alignment before every entry), sources in registration order.
+bool make_layout(int num_inputs, CriticLayout& L) {
+  std::memset(&L, 0, sizeof(L));
+  const int cin_pad = (num_inputs + 7) / 8 * 8;
+  size_t src = 0, dst = 0;
+  unsigned chan = 0;
+  int ncopy = 0;
+  bool ok = true;
+  auto take = [&](size_t n) {
+    const size_t r = src;
+    src += n;
+    return (unsigned)r;
+  };
+  auto put = [&](size_t n) {
+    dst = (dst + 255) & ~(size_t)255;
+    const size_t r = dst;
+    dst += n;
+    return r;
+  };
+  struct Src {
+    unsigned b, g, v;
+    int cout, cin, ks;
+  };
+  auto take_wn = [&](int cout, int cin, int ks) {
+    Src c;
+    c.b = take(cout);
+    c.g = take(cout);
+    c.v = take((size_t)cout * cin * ks);
+    c.cout = cout;
+    c.cin = cin;
+    c.ks = ks;
+    return c;
+  };
+  auto finish = [&](int li, const Src& c, int kind, int Cp, int K) {
+    FoldDesc& F = L.T.fold[li];
+    F.src_g = c.g;
+    F.src_v = c.v;
+    F.chan0 = chan;
+    F.cout = c.cout;
+    F.fan = c.cin * c.ks;
+    F.alpha_src = -1;
+    for (int adj = 0; adj < 2; ++adj) {
+      PackDesc& P = L.T.pack[2 * li + adj];
+      P.src_v = c.v;
+      P.chan0 = chan;
+      P.conv = li;
+      P.rows = adj ? K : c.cout;
+      P.K = adj ? c.cout : K;
+      P.mt = (P.rows % 64 == 0) ? 64 : 32;
+      const int mask = adj ? bwd_taps(li) : fwd_taps(li);
+      for (int t = 0; t < 9; ++t)
+        if ((mask >> t) & 1) P.tap[P.nt++] = t;
+      P.kind = kind;
+      P.cin = c.cin;
+      P.Cp = Cp;
+      P.adj = adj;
+      P.items = (unsigned)((size_t)P.rows * (P.K / 8) * P.nt);
+      P.dst = (unsigned)put((size_t)P.rows * P.K * P.nt);
+      ok = ok && P.rows % P.mt == 0 && P.K % 16 == 0;
+      if (P.items > L.max_items) L.max_items = P.items;
+      if (!adj) {
+        L.bias[li] = put(c.cout);
+        L.T.copy[ncopy++] = CopyDesc{c.b, (unsigned)L.bias[li], (unsigned)c.cout};
+      }
+    }
+    chan += c.cout;
+  };
+  finish(0, take_wn(64, num_inputs, 9), 1, cin_pad, 4 * cin_pad);
+  int in_planes = 64;
+  for (int s = 0; s < 4; ++s) {
+    const int p = stage_planes(s), l0 = 1 + 5 * s;
+    const Src c1 = take_wn(p, in_planes, 9), c2 = take_wn(p, p, 9), cs = take_wn(p, in_planes, 1);
+    const unsigned a0 = take(1), a2 = take(1);
+    finish(l0 + 0, c1, 1, in_planes, 4 * in_planes);
+    finish(l0 + 1, cs, 2, 0, in_planes);
+    finish(l0 + 2, c2, 0, 0, p);
+    const Src d1 = take_wn(p, p, 9), d2 = take_wn(p, p, 9);
+    const unsigned a3 = take(1), a4 = take(1);
+    finish(l0 + 3, d1, 0, 0, p);
+    finish(l0 + 4, d2, 0, 0, p);
+    L.T.fold[l0 + 0].alpha_src = (int)a0;
+    L.T.fold[l0 + 2].alpha_src = (int)a2;
+    L.T.fold[l0 + 3].alpha_src = (int)a3;
+    L.T.fold[l0 + 4].alpha_src = (int)a4;
+    in_planes = p;
+  }
+  L.T.src_fcw = take(512);
+  L.fcw = put(512);
+  L.T.copy[ncopy++] = CopyDesc{L.T.src_fcw, (unsigned)L.fcw, 512u};
+  L.fcb = put(1);
+  L.T.copy[ncopy++] = CopyDesc{take(1), (unsigned)L.fcb, 1u};
+  L.T.fold[0].alpha_src = (int)take(1);
+  L.zero = put(1024);
+  L.total = dst + 8192;   // DMA over-read slack
+  L.T.nchan = chan;
+  return ok && ncopy == NCOPY && src == critic_num_params(num_inputs);
+}
+
+// device workspace: the table, then sc[nchan] (double), chmax[nchan], the read-back block
+struct PackWs {
+  PackTable* T;
+  double* sc;
+  float *chmax, *rb;
+};
+inline size_t pack_ws_table_bytes() { return (sizeof(PackTable) + 255) & ~(size_t)255; }
+inline size_t pack_ws_bytes(unsigned nchan) { return pack_ws_table_bytes() + (size_t)nchan * 12 + 64 * sizeof(float); }
+inline PackWs pack_ws(const CriticNet& N, unsigned nchan) {
+  char* p = static_cast<char*>(N.pack_ws.p);
+  PackWs w;
+  w.T = reinterpret_cast<PackTable*>(p);
+  w.sc = reinterpret_cast<double*>(p + pack_ws_table_bytes());
+  w.chmax = reinterpret_cast<float*>(w.sc + nchan);
+  w.rb = w.chmax + nchan;
+  return w;
+}
+
+// wn_fold's scale of one output channel.  One thread walks the channel's fan in index order: (double)v * v is exact, so the
+// sum has the host's bits whether or not the multiply-add is contracted; sqrt and divide are correctly rounded.  The largest
+// folded weight of the channel is the fold of the largest |v| (both roundings are monotonic); NaNs drop out of fmaxf as they
+// drop out of the host's std::fmax.
+__global__ __launch_bounds__(64) void critic_fold_kernel(const PackTable* __restrict__ T, const float* __restrict__ P,
+                                                         double* __restrict__ sc, float* __restrict__ chmax) {
+  const unsigned ch = blockIdx.x * 64 + threadIdx.x;
+  if (ch >= T->nchan) return;
+  int li = 0;
+  while (li + 1 < NL && T->fold[li + 1].chan0 <= ch) ++li;
+  const FoldDesc F = T->fold[li];
+  const unsigned co = ch - F.chan0;
+  const float* v = P + F.src_v + (size_t)co * F.fan;
+  double ss = 0.0;
+  float vmax = 0.f;
+  for (int i = 0; i < F.fan; ++i) {
+    const float x = v[i];
+    ss += (double)x * (double)x;
+    vmax = fmaxf(vmax, fabsf(x));
+  }
+  const double s = __ddiv_rn((double)P[F.src_g + co], __dsqrt_rn(ss));
+  sc[ch] = s;
+  chmax[ch] = fabsf((float)((double)vmax * s));
+}
+
+// blocks 0..NL-1: scale 2^(14 - exponent(max |w|)) of a convolution (pack_conv_weights_hs_taps) and its threshold;
+// block NL: max |fc_w|
+__global__ __launch_bounds__(256) void critic_scale_kernel(const PackTable* __restrict__ T, const float* __restrict__ P,
+                                                           const float* __restrict__ chmax, float* __restrict__ rb) {
+  __shared__ float part[256];
+  const int li = blockIdx.x, tid = threadIdx.x;
+  float m = 0.f;
+  if (li < NL) {
+    for (int c = tid; c < T->fold[li].cout; c += 256) m = fmaxf(m, chmax[T->fold[li].chan0 + c]);
+  } else {
+    for (int c = tid; c < 512; c += 256) m = fmaxf(m, fabsf(P[T->src_fcw + c]));
+  }
+  part[tid] = m;
+  __syncthreads();
+  for (int st = 128; st > 0; st >>= 1) {
+    if (tid < st) part[tid] = fmaxf(part[tid], part[tid + st]);
+    __syncthreads();
+  }
+  if (tid != 0) return;
+  m = part[0];
+  if (li < NL) {
+    int e = 0;
+    if (m > 0.f) {
+      (void)frexpf(m, &e);
+      e = 14 - e;
+    }
+    rb[li] = ldexpf(1.0f, e);
+    rb[NL + li] = T->fold[li].alpha_src >= 0 ? P[T->fold[li].alpha_src] : 0.f;
+  } else {
+    rb[2 * NL] = m;
+  }
+}
+
+__device__ inline int hs_row_channel_dev(int row) {   // conv_hs.hip::hs_row_channel
+  const int kg = (row >> 2) & 1, r = (row & 3) + 4 * (row >> 3);
+  return 16 * kg + r;
+}
+// element (co, k, tap) of the dense effective weights of a launch (put_conv_s1 / put_conv_s2 / put_shortcut), folded
+__device__ inline float critic_eff_at(const PackDesc& D, const float* __restrict__ P, const double* __restrict__ sc, int co, int k,
+                                      int tap) {
+  size_t off;
+  if (D.kind == 0) {
+    if (k >= D.cin) return 0.f;
+    off = ((size_t)co * D.cin + k) * 9 + tap;
+  } else if (D.kind == 1) {
+    const int ph = k / D.Cp, ci = k - ph * D.Cp, ty = tap / 3, tx = tap - 3 * ty;
+    if (ph >= 4 || ci >= D.cin || ty > 1 || tx > 1) return 0.f;
+    // phase 0 holds the centre row / column (window position 1); phase 1 the row above (position 0) and below (position 1)
+    const int dy = (ph >> 1) ? (ty ? 2 : 0) : (ty ? 1 : -1), dx = (ph & 1) ? (tx ? 2 : 0) : (tx ? 1 : -1);
+    if (dy < 0 || dx < 0) return 0.f;
+    off = ((size_t)co * D.cin + ci) * 9 + dy * 3 + dx;
+  } else {
+    if (tap != 4 || k >= D.cin) return 0.f;
+    off = (size_t)co * D.cin + k;
+  }
+  return (float)((double)P[D.src_v + off] * sc[D.chan0 + co]);
+}
+
+// One thread per (cout tile, K chunk, tap, K half, row): the hi and the lo fragment of eight consecutive K elements.
+__global__ __launch_bounds__(256) void critic_pack_kernel(const PackTable* __restrict__ T, const float* __restrict__ P,
+                                                          const double* __restrict__ sc, const float* __restrict__ rb,
+                                                          float* __restrict__ blob) {
+  const PackDesc& D = T->pack[blockIdx.y];
+  const unsigned i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= D.items) return;
+  const int mt = D.mt, nch = D.K / 16, nt = D.nt;
+  const int m = (int)(i % mt);
+  unsigned t = i / mt;
+  const int kg = (int)(t & 1);
+  t >>= 1;
+  const int ti = (int)(t % nt);
+  t /= nt;
+  const int ch = (int)(t % nch), ct = (int)(t / nch);
+  const int row = ct * mt + (m & ~31) + hs_row_channel_dev(m & 31), tap = D.tap[ti];
+  const float s = rb[D.conv];
+  union {
+    _Float16 h[8];
+    uint4 q;
+  } hi, lo;
+#pragma unroll
+  for (int el = 0; el < 8; ++el) {
+    const int k = ch * 16 + kg * 8 + el;
+    const float v = (D.adj ? critic_eff_at(D, P, sc, k, row, 8 - tap) : critic_eff_at(D, P, sc, row, k, tap)) * s;
+    hi.h[el] = (_Float16)v;
+    lo.h[el] = (_Float16)(v - (float)hi.h[el]);
+  }
+  uint16_t* dst = reinterpret_cast<uint16_t*>(blob + D.dst) + ((((size_t)ct * nch + ch) * nt + ti) * 2) * 2 * mt * 8;
+  *reinterpret_cast<uint4*>(dst + ((size_t)(0 * 2 + kg) * mt + m) * 8) = hi.q;
+  *reinterpret_cast<uint4*>(dst + ((size_t)(1 * 2 + kg) * mt + m) * 8) = lo.q;
+}
+
+__global__ __launch_bounds__(256) void critic_copy_kernel(const PackTable* __restrict__ T, const float* __restrict__ P,
+                                                          float* __restrict__ blob) {
+  const CopyDesc C = T->copy[blockIdx.y];
+  const unsigned i = blockIdx.x * 256 + threadIdx.x;
+  if (i < C.n) blob[C.dst + i] = P[C.src + i];
+}
+
+// utils/misc.py:81-85: target * (1.0 - tau) + source * tau on fp32 tensors -- two rounded products, one rounded sum.  A fused
+// multiply-add would differ in the last bit of about a quarter of the elements.
+__global__ __launch_bounds__(256) void critic_soft_update_kernel(float* __restrict__ master, const float* __restrict__ src, float a,
+                                                                 float b, size_t n) {
+#pragma clang fp contract(off)
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const float x = master[i] * a;
+  const float y = src[i] * b;
+  master[i] = x + y;
+}
+
 // ------------------------------------------------------------------------------------------- activation plan
 struct CAct {
   size_t off = 0;   // floats; an HS8 tensor [C/8][H+2][W+2] of 32-byte records takes C*(H+2)*(W+2) floats per image
@@ -436,7 +734,156 @@ void critic_free(pnpx_ctx* ctx) {
   CriticNet& N = ctx->critic;
   if (N.weights.p) (void)hipFree(N.weights.p);
   if (N.arena.p) (void)hipFree(N.arena.p);
+  if (N.master.p) (void)hipFree(N.master.p);
+  if (N.pack_ws.p) (void)hipFree(N.pack_ws.p);
+  if (N.readback) (void)hipHostFree(N.readback);
   N = CriticNet();
+}
+
+namespace {
+
+int alloc_dev(DeviceBuf& b, size_t bytes, const char* what) {
+  void* p = nullptr;
+  hipError_t e = hipMalloc(&p, bytes);
+  if (e != hipSuccess) {
+    set_error("critic %s allocation of %zu bytes failed: %s", what, bytes, hipGetErrorString(e));
+    return PNPX_ERR_ALLOC;
+  }
+  b.p = p;
+  b.bytes = bytes;
+  return PNPX_OK;
+}
+
+// the parameter vector on the device, the layer table and the read-back block (at a load that allocates)
+int alloc_live_state(CriticNet& N, const CriticLayout& L, size_t n) {
+  PNPX_TRY(alloc_dev(N.master, n * sizeof(float), "parameter"));
+  PNPX_TRY(alloc_dev(N.pack_ws, pack_ws_bytes(L.T.nchan), "packing workspace"));
+  void* h = nullptr;
+  PNPX_HIP(hipHostMalloc(&h, 64 * sizeof(float), hipHostMallocDefault));
+  N.readback = static_cast<float*>(h);
+  PNPX_HIP(hipMemcpy(N.pack_ws.p, &L.T, sizeof(PackTable), hipMemcpyHostToDevice));
+  return PNPX_OK;
+}
+
+// launch descriptors over the blob at `base`
+void bind_blob(CriticNet& N, const CriticLayout& L) {
+  float* base = static_cast<float*>(N.weights.p);
+  for (int i = 0; i < NL; ++i) {
+    for (int adj = 0; adj < 2; ++adj) {
+      const PackDesc& P = L.T.pack[2 * i + adj];
+      ConvLayerHsDev& D = adj ? N.bwd[i] : N.fwd[i];
+      D.cin = D.cin_pad = P.K;
+      D.cout = P.rows;
+      D.mt = P.mt;
+      D.w = reinterpret_cast<char*>(base + P.dst);
+    }
+    N.bias[i] = base + L.bias[i];
+  }
+  N.fc_w = base + L.fcw;
+  N.fc_b = base + L.fcb;
+  N.zero = base + L.zero;
+}
+
+// master -> weight blob on stream s, then the one read-back: scales, thresholds, max |fc_w|
+int repack(pnpx_ctx* ctx, const CriticLayout& L, hipStream_t s) {
+  CriticNet& N = ctx->critic;
+  const PackWs w = pack_ws(N, L.T.nchan);
+  const float* P = static_cast<const float*>(N.master.p);
+  float* blob = static_cast<float*>(N.weights.p);
+  hipLaunchKernelGGL(critic_fold_kernel, dim3((L.T.nchan + 63) / 64), dim3(64), 0, s, w.T, P, w.sc, w.chmax);
+  PNPX_LAUNCH_CHECK();
+  hipLaunchKernelGGL(critic_scale_kernel, dim3(NL + 1), dim3(256), 0, s, w.T, P, w.chmax, w.rb);
+  PNPX_LAUNCH_CHECK();
+  hipLaunchKernelGGL(critic_pack_kernel, dim3((L.max_items + 255) / 256, 2 * NL), dim3(256), 0, s, w.T, P, w.sc, w.rb, blob);
+  PNPX_LAUNCH_CHECK();
+  hipLaunchKernelGGL(critic_copy_kernel, dim3(2, NCOPY), dim3(256), 0, s, w.T, P, blob);
+  PNPX_LAUNCH_CHECK();
+  PNPX_HIP(hipMemcpyAsync(N.readback, w.rb, NREAD * sizeof(float), hipMemcpyDeviceToHost, s));
+  PNPX_HIP(hipStreamSynchronize(s));
+  for (int i = 0; i < NL; ++i)
+    if (!std::isfinite(N.readback[NL + i])) {
+      set_error("critic refresh: TReLU threshold %d is not finite", i);
+      PNPX_HIP(hipDeviceSynchronize());
+      critic_free(ctx);
+      return PNPX_ERR_ARG;
+    }
+  for (int i = 0; i < NL; ++i) {
+    N.fwd[i].inv_scale = N.bwd[i].inv_scale = 1.0f / (N.readback[i] * HS_ASCALE);
+    N.alpha[i] = N.readback[NL + i];
+  }
+  N.fc_wmax = N.readback[2 * NL];
+  N.loaded = true;
+  return PNPX_OK;
+}
+
+}  // namespace
+
+int critic_load_device(pnpx_ctx* ctx, const float* params_dev, size_t n, int num_inputs, hipStream_t s) {
+  if (!params_dev || num_inputs < 1 || num_inputs > 64 || n != critic_num_params(num_inputs)) {
+    set_error("pnpx_critic_load_device: expected %zu parameters for %d inputs (1..64), got %zu",
+              (num_inputs >= 1 && num_inputs <= 64) ? critic_num_params(num_inputs) : (size_t)0, num_inputs, n);
+    return PNPX_ERR_ARG;
+  }
+  CriticNet& N = ctx->critic;
+  CriticLayout L;
+  if (!make_layout(num_inputs, L)) {
+    set_error("pnpx_critic_load_device: internal layout error for %d inputs", num_inputs);
+    return PNPX_ERR_SHAPE;
+  }
+  if (!(N.loaded && N.num_inputs == num_inputs)) {   // first load / another network: allocate (a refresh allocates nothing)
+    PNPX_HIP(hipDeviceSynchronize());
+    critic_free(ctx);
+    N.num_inputs = num_inputs;
+    N.cin_pad = (num_inputs + 7) / 8 * 8;
+    int st = alloc_dev(N.weights, L.total * sizeof(float), "weight");
+    if (st == PNPX_OK) st = alloc_live_state(N, L, n);
+    if (st == PNPX_OK && hipMemset(N.weights.p, 0, N.weights.bytes) != hipSuccess) st = PNPX_ERR_HIP;   // padding and the zero block
+    if (st == PNPX_OK && hipDeviceSynchronize() != hipSuccess) st = PNPX_ERR_HIP;
+    if (st != PNPX_OK) {
+      if (st == PNPX_ERR_HIP) set_error("pnpx_critic_load_device: clearing the weight blob failed: %s", hipGetErrorString(hipGetLastError()));
+      critic_free(ctx);
+      return st;
+    }
+    bind_blob(N, L);
+  }
+  if (params_dev != N.master.p) PNPX_HIP(hipMemcpyAsync(N.master.p, params_dev, n * sizeof(float), hipMemcpyDeviceToDevice, s));
+  return repack(ctx, L, s);
+}
+
+int critic_soft_update(pnpx_ctx* ctx, const float* src_dev, size_t n, float one_minus_tau, float tau, hipStream_t s) {
+  CriticNet& N = ctx->critic;
+  if (!N.loaded) {
+    set_error("pnpx_critic_soft_update called before a critic was loaded");
+    return PNPX_ERR_NO_WEIGHTS;
+  }
+  if (!src_dev || n != critic_num_params(N.num_inputs)) {
+    set_error("pnpx_critic_soft_update: expected %zu parameters for the loaded critic (%d inputs), got %zu",
+              critic_num_params(N.num_inputs), N.num_inputs, n);
+    return PNPX_ERR_ARG;
+  }
+  CriticLayout L;
+  if (!make_layout(N.num_inputs, L)) {
+    set_error("pnpx_critic_soft_update: internal layout error for %d inputs", N.num_inputs);
+    return PNPX_ERR_SHAPE;
+  }
+  hipLaunchKernelGGL(critic_soft_update_kernel, g1(n), dim3(256), 0, s, static_cast<float*>(N.master.p), src_dev, one_minus_tau, tau, n);
+  PNPX_LAUNCH_CHECK();
+  return repack(ctx, L, s);
+}
+
+int critic_params(pnpx_ctx* ctx, float* dst_dev, size_t n, hipStream_t s) {
+  CriticNet& N = ctx->critic;
+  if (!N.loaded) {
+    set_error("pnpx_critic_params called before a critic was loaded");
+    return PNPX_ERR_NO_WEIGHTS;
+  }
+  if (!dst_dev || n != critic_num_params(N.num_inputs)) {
+    set_error("pnpx_critic_params: the loaded critic (%d inputs) has %zu parameters, got room for %zu", N.num_inputs,
+              critic_num_params(N.num_inputs), n);
+    return PNPX_ERR_ARG;
+  }
+  PNPX_HIP(hipMemcpyAsync(dst_dev, N.master.p, n * sizeof(float), hipMemcpyDeviceToDevice, s));
+  return PNPX_OK;
 }
 
 int critic_load(pnpx_ctx* ctx, const float* params, size_t n, int num_inputs) {
@@ -555,6 +1002,27 @@ int critic_load(pnpx_ctx* ctx, const float* params, size_t n, int num_inputs) {
   N.fc_b = base + o_fcb;
   N.zero = base + o_zero;
   N.fc_wmax = wmax;
+  // live weights: the raw parameters stay on the device as the master vector of pnpx_critic_soft_update, whose device-side
+  // packing writes into this blob -- so its layer table has to describe exactly the offsets used above
+  CriticLayout L;
+  bool same = make_layout(num_inputs, L) && L.total == H.f.size() && L.fcw == o_fcw && L.fcb == o_fcb && L.zero == o_zero;
+  for (int i = 0; same && i < NL; ++i)
+    same = L.T.pack[2 * i].dst == pf[i].w && L.T.pack[2 * i + 1].dst == pb[i].w && L.bias[i] == pf[i].b && L.T.pack[2 * i].mt == pf[i].mt &&
+           L.T.pack[2 * i + 1].mt == pb[i].mt && L.T.pack[2 * i].K == pf[i].cin && L.T.pack[2 * i + 1].K == pb[i].cin;
+  if (!same) {
+    set_error("pnpx_critic_load: the device packing table disagrees with the host layout (%d inputs)", num_inputs);
+    critic_free(ctx);
+    return PNPX_ERR_SHAPE;
+  }
+  int st = alloc_live_state(N, L, n);
+  if (st == PNPX_OK && hipMemcpy(N.master.p, params, n * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) {
+    set_error("pnpx_critic_load: uploading the parameter vector failed: %s", hipGetErrorString(hipGetLastError()));
+    st = PNPX_ERR_HIP;
+  }
+  if (st != PNPX_OK) {
+    critic_free(ctx);
+    return st;
+  }
   N.loaded = true;
   return PNPX_OK;
 }

@@ -126,10 +126,66 @@ class Context:
 
     def load_critic(self, state_dict, num_inputs):
         """state_dict of the reference's ResNet_wobn(num_inputs, 18, 1) (tfpnp/trainer/mddpg/critic.py) -> native critic
-        (key spellings: critic_flat_params).  The weights are frozen until the next load."""
+        (key spellings: critic_flat_params).  Folds and packs on the host: the path for a checkpoint.  Weights that change
+        between evaluations go through load_critic_device / critic_soft_update."""
         flat = critic_flat_params(state_dict, num_inputs)
         check(_lib.lib().pnpx_critic_load(self.handle, flat.ctypes.data_as(C.c_void_p), flat.size, int(num_inputs)))
         self._critic = int(num_inputs)
+
+    def _critic_vector(self, t, who, num_inputs):
+        """A flat critic parameter vector as the library takes it: fp32, contiguous, on this context's device, of the length
+        of a critic with `num_inputs` inputs (None: not checked here)."""
+        if not isinstance(t, torch.Tensor):
+            raise PnpxError(f"{who}: expected a torch.Tensor, got {type(t).__name__}")
+        if t.device != self.device:
+            raise PnpxError(f"{who}: parameter vector is on {t.device}, the context is on {self.device}")
+        if t.dtype != torch.float32:
+            raise PnpxError(f"{who}: expected float32, got {t.dtype}")
+        if t.dim() != 1 or not t.is_contiguous():
+            raise PnpxError(f"{who}: expected a contiguous 1-D vector, got shape {tuple(t.shape)} with strides {t.stride()}")
+        if num_inputs is not None:
+            want = int(_lib.lib().pnpx_critic_num_params(int(num_inputs)))
+            if t.numel() != want:
+                raise PnpxError(f"{who}: a critic with {num_inputs} inputs has {want} parameters, got {t.numel()}")
+        return t.detach()
+
+    def load_critic_device(self, flat, num_inputs=None):
+        """flat: the critic's parameters as one fp32 vector on this context's device, in synth.critic_param_specs order (the
+        order of module.parameters() of the reference's weight-normalised critic).  Weight-norm fold and packing run on the
+        device on the current stream; a critic with the same num_inputs already loaded is refreshed in place.  num_inputs
+        None: taken from the vector's length.  Ends with one small read-back (synchronises the current stream)."""
+        if num_inputs is None and isinstance(flat, torch.Tensor):
+            n = flat.numel()
+            num_inputs = next((c for c in range(1, 65) if int(_lib.lib().pnpx_critic_num_params(c)) == n), None)
+            if num_inputs is None:
+                raise PnpxError(f"load_critic_device: {n} floats is not the parameter count of a critic with 1..64 inputs "
+                                f"(9 inputs: {int(_lib.lib().pnpx_critic_num_params(9))})")
+        flat = self._critic_vector(flat, "load_critic_device", num_inputs)
+        with torch.cuda.device(self.device):
+            st = _lib.lib().pnpx_critic_load_device(self.handle, _p(flat), flat.numel(), int(num_inputs), _stream(flat))
+        if st != 0:
+            self._critic = None        # a failed load leaves the context without a critic
+        check(st)
+        self._critic = int(num_inputs)
+
+    def critic_soft_update(self, src_flat, tau):
+        """utils/misc.py:81-85 with the loaded critic as the target: params = params * (1.0 - tau) + src_flat * tau in the
+        reference's fp32 arithmetic (bit-equal to torch's), then the device-side re-packing of load_critic_device."""
+        src_flat = self._critic_vector(src_flat, "critic_soft_update", self._critic)
+        tau = float(tau)
+        with torch.cuda.device(self.device):
+            st = _lib.lib().pnpx_critic_soft_update(self.handle, _p(src_flat), src_flat.numel(), 1.0 - tau, tau, _stream(src_flat))
+        if st == 1:                    # PNPX_ERR_ARG from the refresh: a threshold went non-finite, the critic is unloaded
+            self._critic = None
+        check(st)
+
+    def critic_params(self):
+        """A copy of the live parameter vector (fp32, on this context's device, load_critic_device's order)."""
+        n = int(_lib.lib().pnpx_critic_num_params(self._critic)) if self._critic is not None else 1
+        out = torch.empty((n,), device=self.device, dtype=torch.float32)
+        with torch.cuda.device(self.device):
+            check(_lib.lib().pnpx_critic_params(self.handle, _p(out), n, _stream(out)))
+        return out
 
     def set_option(self, key, value):
         """e.g. set_option('conv_mode', 1) selects the fast half-split f16 MFMA convolutions (default 0 = fp32 arithmetic)."""
