@@ -192,6 +192,27 @@ int pnpx_policy_load(pnpx_ctx* ctx, const float* params_host, size_t n_params, i
  * det [B,n_det] (sigmoid outputs, before the action-range mapping of network.py:163-175). */
 int pnpx_policy_forward(pnpx_ctx* ctx, const float* ob, float* probs, float* det, int B, int H, int W,
                         void* stream);
+/* The weights are LIVE, as the critic's are: the context keeps the flat parameter vector on the device after either load entry.
+ * pnpx_policy_load_device is pnpx_policy_load from a vector in DEVICE memory (same order, same length): the BatchNorm fold
+ * (scale = weight / sqrt(running_var + 1e-5), shift = bias - running_mean * scale, in the host's fp32 roundings), the per-convolution
+ * half-split scales and every packed layout the forward reads -- both settings of option "policy_s2_hs" -- are derived by a handful
+ * of kernels on `stream`.  The outputs of pnpx_policy_forward equal those after pnpx_policy_load of the same values bit for bit.
+ * The first call on a context, or one with another (num_inputs, n_det, spi_head), allocates; every later call refreshes in place:
+ * no allocation, no device-wide synchronisation, the activation workspace is kept.  On a context that pnpx_policy_load loaded, the
+ * first call replaces the weight blob once (the host decides which fp32 tap slices exist by their values, the device by structure)
+ * and keeps the workspace.  Each call ends with one small stream-ordered read-back of the 21 weight scales and a synchronisation of
+ * `stream` (the launches take them by value).  A scale that is not finite -- running_var NaN or below -1e-5, a BatchNorm weight
+ * that is not finite, a NaN convolution weight -- returns PNPX_ERR_ARG and leaves the context without an actor; a wrong n_params
+ * returns PNPX_ERR_ARG and changes nothing.  Not capturable into a graph.
+ * Stream rule: issue it on the stream the actor's other calls use.  A forward that ran as several launch chains (option "chains")
+ * has joined its side streams back into its caller's stream by events before it returned, so a refresh on that stream is ordered
+ * behind every launch of an earlier forward and ahead of a later one; no other stream is ordered against it.
+ * params_dev may be dropped once the call returns. */
+int pnpx_policy_load_device(pnpx_ctx* ctx, const float* params_dev, size_t n_params, int num_inputs, int n_det, int spi_head,
+                            void* stream);
+/* Copies the live parameter vector (n_params floats, pnpx_policy_load's order) to dst_dev, ordered on `stream`.
+ * PNPX_ERR_NO_WEIGHTS before a load. */
+int pnpx_policy_params(pnpx_ctx* ctx, float* dst_dev, size_t n_params, void* stream);
 
 /* ---- value network / critic (tfpnp/trainer/mddpg/critic.py) --------------------------------------- */
 /* ResNet_wobn(num_inputs, 18, 1) (critic.py:95-131; the trainer never builds another one, trainer/mddpg/critic.py:95 via

@@ -184,6 +184,17 @@ int pnpx_policy_load(pnpx_ctx* ctx, const float* params_host, size_t n_params, i
   return policy_load(ctx, params_host, n_params, num_inputs, n_det, spi_head);
 }
 
+int pnpx_policy_load_device(pnpx_ctx* ctx, const float* params_dev, size_t n_params, int num_inputs, int n_det, int spi_head,
+                            void* stream) {
+  LOCK_CTX(ctx);
+  return policy_load_device(ctx, params_dev, n_params, num_inputs, n_det, spi_head, static_cast<hipStream_t>(stream));
+}
+
+int pnpx_policy_params(pnpx_ctx* ctx, float* dst_dev, size_t n_params, void* stream) {
+  LOCK_CTX(ctx);
+  return policy_params(ctx, dst_dev, n_params, static_cast<hipStream_t>(stream));
+}
+
 int pnpx_policy_forward(pnpx_ctx* ctx, const float* ob, float* probs, float* det, int B, int H, int W,
                         void* stream) {
   LOCK_CTX(ctx);
@@ -416,7 +427,7 @@ size_t pnpx_ctx_bytes(const pnpx_ctx* ctx) {
   size_t n = ctx->weights.bytes + ctx->arena.buf.bytes + ctx->arena_grad.buf.bytes + ctx->scratch.bytes +
              ctx->drunet.weights.bytes + ctx->drunet.arena.bytes + ctx->drunet.arena_grad.bytes + ctx->drunet.f32_weights.bytes +
              ctx->drunet.f32_arena.bytes + ctx->drunet.f32_weights_bwd.bytes + ctx->drunet.f32_arena_grad.bytes +
-             ctx->policy.weights.bytes + ctx->policy.arena.bytes + ctx->critic.weights.bytes + ctx->critic.arena.bytes +
+             ctx->policy.weights.bytes + ctx->policy.arena.bytes + ctx->policy.master.bytes + ctx->policy.pack_ws.bytes + ctx->critic.weights.bytes + ctx->critic.arena.bytes +
              ctx->critic.master.bytes + ctx->critic.pack_ws.bytes;
   for (const auto& sl : ctx->train_ring) n += sl.arena.buf.bytes + sl.pre.bytes;
   return n;

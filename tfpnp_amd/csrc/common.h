@@ -109,6 +109,11 @@ struct PolicyNet {
   DeviceBuf weights;
   DeviceBuf arena;           // activations for capB observations of capH x capW, zero borders
   int capB = 0, capH = 0, capW = 0;
+  // live weights (policy_pack.hip): the flat fp32 parameter vector in pnpx_policy_load's order, kept after either load entry
+  DeviceBuf master;
+  bool dev_layout = false;   // `weights` has the structural layout policy_load_device refreshes in place (else: policy_load's)
+  DeviceBuf pack_ws;         // layer table, per-channel BatchNorm scales / shifts / weight maxima, the block read back per refresh
+  float* readback = nullptr; // pinned host copy of that block: the 21 half-split weight scales
 };
 
 // Value network (critic.hip): ResNet_wobn(num_inputs, 18, 1).  The raw parameters live on the device (`master`); the packed
@@ -381,6 +386,10 @@ size_t policy_num_params(int num_inputs, int n_det, int spi_head);
 int policy_load(pnpx_ctx* ctx, const float* params, size_t n, int num_inputs, int n_det, int spi_head);
 int policy_forward(pnpx_ctx* ctx, const float* ob, float* probs, float* det, int B, int H, int W, hipStream_t s);
 void policy_free(pnpx_ctx* ctx);
+// live weights (policy_pack.hip)
+int policy_keep_params(pnpx_ctx* ctx, const float* params_host, size_t n);   // policy_load: the parameter vector stays on the device
+int policy_load_device(pnpx_ctx* ctx, const float* params_dev, size_t n, int num_inputs, int n_det, int spi_head, hipStream_t s);
+int policy_params(pnpx_ctx* ctx, float* dst_dev, size_t n, hipStream_t s);
 
 // Value network (critic.hip)
 size_t critic_num_params(int num_inputs);

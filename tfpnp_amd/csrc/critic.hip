@@ -6,7 +6,7 @@
 // allocation, no device-wide synchronisation, the arena is kept.  Thresholds, weight scales and max |fc_w| are launch
 // arguments, so each refresh ends with one small read-back and a synchronisation of the caller's stream: a refresh cannot be
 // captured into a graph and has to be issued on the stream the critic's other calls use.  Still missing: weight gradients,
-// value_loss, optimiser steps, a trainer; the same refresh for the actor (policy.hip).
+// value_loss, optimiser steps, a trainer.  (The actor's refresh: policy_pack.hip.)
 //
 // Replaces ResNet_wobn(num_inputs, 18, 1).forward (tfpnp/trainer/mddpg/critic.py:95-131) and the autograd pass through it
 // with respect to its INPUT, which is how the actor loss uses it (trainer/mddpg/trainer.py:180-192: V_next = critic(eval_ob2)
@@ -39,6 +39,7 @@
 #include "conv_hs.h"
 #include "hs_rec.h"
 #include "hs_relayout.h"
+#include "pack_desc.h"
 
 namespace pnpx {
 namespace {
@@ -263,19 +264,7 @@ struct FoldDesc {     // one weight-normalised convolution of the parameter vect
   int cout, fan;
   int alpha_src;           // threshold of the TReLU behind it (floats into the parameter vector), -1: none (shortcuts)
 };
-struct PackDesc {     // one packing: [rows/mt][K/16][nt][hi,lo][kg][mt][8] f16 at blob + dst
-  unsigned src_v, chan0, dst;
-  unsigned items;          // (hi, lo) fragment pairs = rows * K / 8 * nt
-  int conv;                // convolution (scale index)
-  int rows, K, mt, nt;
-  int kind;                // 0: 3x3 stride 1 (put_conv_s1); 1: 3x3 stride 2 over the space-to-depth input (put_conv_s2); 2: 1x1 shortcut
-  int cin, Cp;             // source input channels; channels per phase of the space-to-depth input (kind 1)
-  int adj;                 // the adjoint: rows / K transposed, taps mirrored
-  int tap[9];
-};
-struct CopyDesc {
-  unsigned src, dst, n;
-};
+// PackDesc (one packing, forward or adjoint) and CopyDesc: pack_desc.h
 constexpr int NCOPY = NL + 2, NREAD = 2 * NL + 1;   // read-back block: NL weight scales, NL thresholds, max |fc_w|
 struct PackTable {
   FoldDesc fold[NL];
@@ -463,28 +452,11 @@ __global__ __launch_bounds__(256) void critic_scale_kernel(const PackTable* __re
   }
 }
 
-__device__ inline int hs_row_channel_dev(int row) {   // conv_hs.hip::hs_row_channel
-  const int kg = (row >> 2) & 1, r = (row & 3) + 4 * (row >> 3);
-  return 16 * kg + r;
-}
 // element (co, k, tap) of the dense effective weights of a launch (put_conv_s1 / put_conv_s2 / put_shortcut), folded
 __device__ inline float critic_eff_at(const PackDesc& D, const float* __restrict__ P, const double* __restrict__ sc, int co, int k,
                                       int tap) {
-  size_t off;
-  if (D.kind == 0) {
-    if (k >= D.cin) return 0.f;
-    off = ((size_t)co * D.cin + k) * 9 + tap;
-  } else if (D.kind == 1) {
-    const int ph = k / D.Cp, ci = k - ph * D.Cp, ty = tap / 3, tx = tap - 3 * ty;
-    if (ph >= 4 || ci >= D.cin || ty > 1 || tx > 1) return 0.f;
-    // phase 0 holds the centre row / column (window position 1); phase 1 the row above (position 0) and below (position 1)
-    const int dy = (ph >> 1) ? (ty ? 2 : 0) : (ty ? 1 : -1), dx = (ph & 1) ? (tx ? 2 : 0) : (tx ? 1 : -1);
-    if (dy < 0 || dx < 0) return 0.f;
-    off = ((size_t)co * D.cin + ci) * 9 + dy * 3 + dx;
-  } else {
-    if (tap != 4 || k >= D.cin) return 0.f;
-    off = (size_t)co * D.cin + k;
-  }
+  const long long off = eff_src_offset(D, co, k, tap);
+  if (off < 0) return 0.f;
   return (float)((double)P[D.src_v + off] * sc[D.chan0 + co]);
 }
 
@@ -495,30 +467,9 @@ __global__ __launch_bounds__(256) void critic_pack_kernel(const PackTable* __res
   const PackDesc& D = T->pack[blockIdx.y];
   const unsigned i = blockIdx.x * 256 + threadIdx.x;
   if (i >= D.items) return;
-  const int mt = D.mt, nch = D.K / 16, nt = D.nt;
-  const int m = (int)(i % mt);
-  unsigned t = i / mt;
-  const int kg = (int)(t & 1);
-  t >>= 1;
-  const int ti = (int)(t % nt);
-  t /= nt;
-  const int ch = (int)(t % nch), ct = (int)(t / nch);
-  const int row = ct * mt + (m & ~31) + hs_row_channel_dev(m & 31), tap = D.tap[ti];
-  const float s = rb[D.conv];
-  union {
-    _Float16 h[8];
-    uint4 q;
-  } hi, lo;
-#pragma unroll
-  for (int el = 0; el < 8; ++el) {
-    const int k = ch * 16 + kg * 8 + el;
-    const float v = (D.adj ? critic_eff_at(D, P, sc, k, row, 8 - tap) : critic_eff_at(D, P, sc, row, k, tap)) * s;
-    hi.h[el] = (_Float16)v;
-    lo.h[el] = (_Float16)(v - (float)hi.h[el]);
-  }
-  uint16_t* dst = reinterpret_cast<uint16_t*>(blob + D.dst) + ((((size_t)ct * nch + ch) * nt + ti) * 2) * 2 * mt * 8;
-  *reinterpret_cast<uint4*>(dst + ((size_t)(0 * 2 + kg) * mt + m) * 8) = hi.q;
-  *reinterpret_cast<uint4*>(dst + ((size_t)(1 * 2 + kg) * mt + m) * 8) = lo.q;
+  hs_pack_item(D, i, rb[D.conv], blob, [&](int row, int k, int tap) {
+    return D.adj ? critic_eff_at(D, P, sc, k, row, 8 - tap) : critic_eff_at(D, P, sc, row, k, tap);
+  });
 }
 
 __global__ __launch_bounds__(256) void critic_copy_kernel(const PackTable* __restrict__ T, const float* __restrict__ P,

@@ -16,6 +16,8 @@
 //     non-zero -- a per-(cout tile, K-chunk) tap mask skips the other MFMAs, so no arithmetic is wasted on stride.
 //   * the 1x1 stride-2 shortcut is the centre tap of phase (0,0): it rides in the same launch as extra cout tiles
 //     (all other chunks masked out) and is written, without ReLU, to a second output.
+// policy_load folds and packs on the host (a checkpoint); policy_pack.hip derives the same layouts on the device from a live
+// parameter vector (pnpx_policy_load_device).
 #include <cmath>
 #include <cstring>
 
@@ -361,6 +363,9 @@ void policy_free(pnpx_ctx* ctx) {
   PolicyNet& N = ctx->policy;
   if (N.weights.p) (void)hipFree(N.weights.p);
   if (N.arena.p) (void)hipFree(N.arena.p);
+  if (N.master.p) (void)hipFree(N.master.p);
+  if (N.pack_ws.p) (void)hipFree(N.pack_ws.p);
+  if (N.readback) (void)hipHostFree(N.readback);
   N = PolicyNet();
 }
 
@@ -545,6 +550,12 @@ int policy_load(pnpx_ctx* ctx, const float* params, size_t n, int num_inputs, in
   N.fc_det_b = base + o_db;
   N.fc_det2_w = spi_head ? base + o_d2w : nullptr;
   N.fc_det2_b = spi_head ? base + o_d2b : nullptr;
+  // live weights: the raw parameters stay on the device for pnpx_policy_params / another device's context
+  const int st = policy_keep_params(ctx, params, n);
+  if (st != PNPX_OK) {
+    policy_free(ctx);
+    return st;
+  }
   N.loaded = true;
   return PNPX_OK;
 }

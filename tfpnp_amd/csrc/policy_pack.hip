@@ -1,0 +1,567 @@
+// Policy actor: live weights.  The context keeps the flat fp32 parameter vector on the device (PolicyNet::master, after
+// either load entry); pnpx_policy_load_device derives every packed layout the forward reads from it with five launches on
+// the caller's stream and refreshes an already loaded actor in place -- no allocation, no device-wide synchronisation, the
+// activation arena is kept.  The per-convolution weight scales are launch arguments of the half-split instances, so a
+// refresh ends with one small read-back and a synchronisation of that stream (not capturable).
+//
+// What is derived (policy.hip::policy_load is the host statement of the same arithmetic):
+//   pol_fold_kernel      per output channel: scale = g / sqrt(v + eps), shift = b - m * scale in the host's fp32 roundings
+//                        (correctly rounded sqrt -- taken in double and rounded once more -- and divide; the host object
+//                        code has no fused multiply-add, so the shift is two roundings: contraction is off), and
+//                        max |folded weight| = fl(max |w| * |scale|)
+//   pol_scale_kernel     per convolution: the power-of-two half-split scale 2^(14 - exponent(max |w|)) into the read-back block
+//   pol_pack_hs_kernel   the 12 stride-1 convolutions (9 taps), the stem and the 4 stage-entry conv1 as 2x2-window sparse-tap
+//                        launches over the space-to-depth input (0x01B), the 4 shortcuts (0x010): hi / lo f16 fragments
+//   pol_pack_f32_kernel  the stem and the 4 stage entries (conv1 + shortcut rows merged) as fp32 [8 channels][64 couts] tap
+//                        slices in PolStep order (option policy_s2_hs = 0)
+//   pol_copy_kernel      the shifts as biases, the head matrices
+//
+// The host decides which fp32 tap slices exist by looking at the values; here presence is STRUCTURAL: over the space-to-depth
+// input a 3x3 stride-2 convolution touches tap 4 of phase (0,0), taps 3, 4 of phase (0,1), taps 1, 4 of phase (1,0) and taps
+// 0, 1, 3, 4 of phase (1,1), in every 8-channel chunk that holds a real input channel; the shortcut touches tap 4 of the
+// phase-(0,0) chunks.  The step lists are therefore layout constants, written once when the blob is allocated.  A present
+// slice that happens to be all zero contributes exactly nothing, so both layouts compute the same outputs; for weights
+// without an all-zero slice they are the same bytes at the same offsets.
+#include <cmath>
+#include <cstring>
+
+#include "common.h"
+#include "conv_hs.h"
+#include "pack_desc.h"
+#include "policy_conv.h"
+
+namespace pnpx {
+namespace {
+
+constexpr float BN_EPS = 1e-5f;
+constexpr int NCV = 21;      // BatchNorm-ed convolutions in parameter order: 0 = stem,
+                             // 1 + 5 * stage + {0 entry conv1, 1 conv2, 2 shortcut, 3 block-1 conv1, 4 block-1 conv2}
+constexpr int NF32 = 5;      // fp32 PolStep launches: the stem and the four stage entries
+constexpr int MAXCOPY = 36, NRB = 32;
+inline int stage_planes(int n) { return 64 << n; }
+
+struct PolFoldDesc {
+  unsigned src_w, src_bn;    // floats into the parameter vector: weights; BatchNorm weight, bias, running_mean, running_var
+  unsigned chan0;            // first output channel in the per-channel arrays
+  int cout, fan;
+};
+struct PolF32Desc {          // one fp32 launch: nct1 cout tiles of a 3x3 stride-2 convolution, then nct2 of the 1x1 shortcut
+  unsigned dst, items;       // items: 16-byte fragments = slices * 128
+  int conv1, conv2;          // convolutions (conv2 = -1: none)
+  int nct1, nct2;
+  int nc, cin;               // 8-channel chunks per phase (Cp / 8); real input channels
+};
+struct PolPackTable {
+  PolFoldDesc fold[NCV];
+  PackDesc pack[NCV];
+  PolF32Desc f32[NF32];
+  CopyDesc copy[MAXCOPY];
+  unsigned nchan;
+  int ncopy;
+};
+struct PolicyLayout {        // the table + the blob offsets (floats) the host needs
+  PolPackTable T;
+  size_t f32_w[NF32], f32_bias[NF32], f32_steps[NF32], f32_nsteps[NF32];
+  int f32_cout[NF32], f32_K[NF32], f32_split[NF32];
+  size_t hs_bias[NCV];
+  size_t smw, smb, dw, db, d2w, d2b, total;
+  unsigned max_hs_items, max_f32_items, max_copy;
+  std::vector<PolStep> steps[NF32];
+  std::vector<int> nsteps[NF32];
+};
+
+// taps of phase ph of a 3x3 stride-2 convolution on the space-to-depth grid (policy.hip::put_conv_s2), ascending
+__host__ __device__ inline int phase_taps(int ph, int* taps) {
+  const int ty0 = (ph >> 1) ? 0 : 1, tx0 = (ph & 1) ? 0 : 1;
+  int n = 0;
+  for (int ty = ty0; ty < 2; ++ty)
+    for (int tx = tx0; tx < 2; ++tx) taps[n++] = ty * 3 + tx;
+  return n;
+}
+
+// Offsets of HostBlob as policy_load fills it when every structurally present slice holds a non-zero value (256-float
+// alignment before every entry), sources in pnpx_policy_load's order.
+bool make_layout(int num_inputs, int n_det, int spi_head, PolicyLayout& L) {
+  L = PolicyLayout();
+  const int cin_pad = (num_inputs + 7) / 8 * 8;
+  size_t src = 0, dst = 0;
+  unsigned chan = 0;
+  int ncopy = 0;
+  bool ok = true;
+  auto take = [&](size_t n) {
+    const size_t r = src;
+    src += n;
+    return (unsigned)r;
+  };
+  auto put = [&](size_t n) {
+    dst = (dst + 255) & ~(size_t)255;
+    const size_t r = dst;
+    dst += n;
+    return r;
+  };
+  auto copy = [&](unsigned from, size_t to, size_t n, unsigned space) {
+    if (ncopy < MAXCOPY) L.T.copy[ncopy] = CopyDesc{from, (unsigned)to, (unsigned)n, space};
+    ++ncopy;
+    if (n > L.max_copy) L.max_copy = (unsigned)n;
+  };
+  auto take_conv = [&](int ci, int cout, int cin, int ks) {
+    PolFoldDesc& F = L.T.fold[ci];
+    F.src_w = take((size_t)cout * cin * ks);
+    F.src_bn = take((size_t)4 * cout);
+    F.chan0 = chan;
+    F.cout = cout;
+    F.fan = cin * ks;
+    chan += cout;
+  };
+  // half-split packing of convolution ci + its bias
+  auto put_hs = [&](int ci, int kind, int cin, int Cp, int K, int mask) {
+    const PolFoldDesc& F = L.T.fold[ci];
+    PackDesc& P = L.T.pack[ci];
+    P.src_v = F.src_w;
+    P.chan0 = F.chan0;
+    P.conv = ci;
+    P.rows = F.cout;
+    P.K = K;
+    P.mt = 64;
+    for (int t = 0; t < 9; ++t)
+      if ((mask >> t) & 1) P.tap[P.nt++] = t;
+    P.kind = kind;
+    P.cin = cin;
+    P.Cp = Cp;
+    P.items = (unsigned)((size_t)P.rows * (P.K / 8) * P.nt);
+    P.dst = (unsigned)put((size_t)P.rows * P.K * P.nt);
+    ok = ok && P.rows % 64 == 0 && P.K % 16 == 0;
+    if (P.items > L.max_hs_items) L.max_hs_items = P.items;
+    L.hs_bias[ci] = put(F.cout);
+    copy(F.chan0, L.hs_bias[ci], F.cout, 1);
+  };
+  // fp32 PolStep launch fi: convolution c1 (3x3 stride 2) [+ shortcut c2]
+  auto put_f32 = [&](int fi, int c1, int c2, int cin, int Cp) {
+    PolF32Desc& D = L.T.f32[fi];
+    const int p = L.T.fold[c1].cout, nc = Cp / 8, nch = 4 * nc;
+    D.conv1 = c1;
+    D.conv2 = c2;
+    D.nct1 = p / 64;
+    D.nct2 = c2 >= 0 ? p / 64 : 0;
+    D.nc = nc;
+    D.cin = cin;
+    const int nct = D.nct1 + D.nct2;
+    std::vector<PolStep>& steps = L.steps[fi];
+    std::vector<int>& nsteps = L.nsteps[fi];
+    steps.assign((size_t)nct * nch, PolStep{0, 0, 0});
+    nsteps.assign(nct, 0);
+    unsigned nsl = 0;
+    for (int ct = 0; ct < nct; ++ct)
+      for (int ch = 0; ch < (ct < D.nct1 ? nch : nc); ++ch) {
+        int taps[4] = {4, 0, 0, 0};
+        const int n = ct < D.nct1 ? phase_taps(ch / nc, taps) : 1;
+        unsigned short mask = 0;
+        for (int t = 0; t < n; ++t) mask |= (unsigned short)(1u << taps[t]);
+        steps[(size_t)ct * nch + nsteps[ct]++] = PolStep{mask, (unsigned short)ch, nsl};
+        nsl += n;
+      }
+    ok = ok && nsl == (unsigned)(D.nct1 * nc * 9 + D.nct2 * nc);
+    D.items = nsl * 128;
+    if (D.items > L.max_f32_items) L.max_f32_items = D.items;
+    L.f32_w[fi] = put((size_t)nsl * 512 + 1024);   // + the guard behind the last slice
+    D.dst = (unsigned)L.f32_w[fi];
+    L.f32_cout[fi] = nct * 64;
+    L.f32_K[fi] = 4 * Cp;
+    L.f32_split[fi] = p;
+    L.f32_bias[fi] = put((size_t)nct * 64);
+    copy(L.T.fold[c1].chan0, L.f32_bias[fi], p, 1);
+    if (c2 >= 0) copy(L.T.fold[c2].chan0, L.f32_bias[fi] + p, p, 1);
+    L.f32_steps[fi] = put(steps.size() * 2);
+    L.f32_nsteps[fi] = put(nsteps.size());
+  };
+  take_conv(0, 64, num_inputs, 9);
+  put_f32(0, 0, -1, num_inputs, cin_pad);
+  put_hs(0, 1, num_inputs, cin_pad, 4 * cin_pad, 0x01B);
+  int in_planes = 64;
+  for (int s = 0; s < 4; ++s) {
+    const int p = stage_planes(s), c0 = 1 + 5 * s;
+    take_conv(c0 + 0, p, in_planes, 9);
+    take_conv(c0 + 1, p, p, 9);
+    take_conv(c0 + 2, p, in_planes, 1);
+    take_conv(c0 + 3, p, p, 9);
+    take_conv(c0 + 4, p, p, 9);
+    put_f32(1 + s, c0 + 0, c0 + 2, in_planes, in_planes);
+    put_hs(c0 + 0, 1, in_planes, in_planes, 4 * in_planes, 0x01B);
+    put_hs(c0 + 2, 2, in_planes, 0, in_planes, 0x010);
+    put_hs(c0 + 1, 0, p, 0, p, 0x1FF);
+    put_hs(c0 + 3, 0, p, 0, p, 0x1FF);
+    put_hs(c0 + 4, 0, p, 0, p, 0x1FF);
+    in_planes = p;
+  }
+  auto head = [&](size_t n) {
+    const size_t to = put(n);
+    copy(take(n), to, n, 0);
+    return to;
+  };
+  L.smw = head(2 * 512);
+  L.smb = head(2);
+  if (spi_head) {
+    L.dw = head((size_t)64 * 512);
+    L.db = head(64);
+    L.d2w = head((size_t)n_det * 64);
+    L.d2b = head(n_det);
+  } else {
+    L.dw = head((size_t)n_det * 512);
+    L.db = head(n_det);
+  }
+  L.total = dst + 8192;   // DMA over-read slack
+  L.T.nchan = chan;
+  L.T.ncopy = ncopy;
+  return ok && ncopy <= MAXCOPY && src == policy_num_params(num_inputs, n_det, spi_head) && L.total < ((size_t)1 << 32);
+}
+
+// device workspace: the table, then scale[nchan], shift[nchan], chmax[nchan], the read-back block
+struct PolPackWs {
+  PolPackTable* T;
+  float *sc, *sh, *chmax, *rb;
+};
+inline size_t ws_table_bytes() { return (sizeof(PolPackTable) + 255) & ~(size_t)255; }
+inline size_t ws_bytes(unsigned nchan) { return ws_table_bytes() + ((size_t)3 * nchan + NRB) * sizeof(float); }
+inline PolPackWs pack_ws(const PolicyNet& N, unsigned nchan) {
+  char* p = static_cast<char*>(N.pack_ws.p);
+  PolPackWs w;
+  w.T = reinterpret_cast<PolPackTable*>(p);
+  w.sc = reinterpret_cast<float*>(p + ws_table_bytes());
+  w.sh = w.sc + nchan;
+  w.chmax = w.sh + nchan;
+  w.rb = w.chmax + nchan;
+  return w;
+}
+
+// policy.hip::bn_fold of one output channel + the largest folded weight of that channel.  One 64-lane workgroup per channel
+// walks the channel's fan: a maximum does not depend on the order.  fl(|w| * |scale|) is monotonic in |w|, so the largest
+// folded weight is the fold of the largest |w|.  A NaN weight makes the channel's maximum NaN (the refresh is then refused).
+__global__ __launch_bounds__(64) void pol_fold_kernel(const PolPackTable* __restrict__ T, const float* __restrict__ P,
+                                                      float* __restrict__ sc, float* __restrict__ sh, float* __restrict__ chmax) {
+#pragma clang fp contract(off)
+  __shared__ float part[64];
+  __shared__ int nan_seen;
+  const unsigned ch = blockIdx.x;
+  const int tid = threadIdx.x;
+  int li = 0;
+  while (li + 1 < NCV && T->fold[li + 1].chan0 <= ch) ++li;
+  const PolFoldDesc F = T->fold[li];
+  const unsigned co = ch - F.chan0;
+  const float* w = P + F.src_w + (size_t)co * F.fan;
+  if (tid == 0) nan_seen = 0;
+  __syncthreads();
+  float vmax = 0.f;
+  bool bad = false;
+  for (int i = tid; i < F.fan; i += 64) {
+    const float x = w[i];
+    bad |= (x != x);
+    vmax = fmaxf(vmax, fabsf(x));
+  }
+  part[tid] = vmax;
+  if (bad) nan_seen = 1;
+  __syncthreads();
+  for (int st = 32; st > 0; st >>= 1) {
+    if (tid < st) part[tid] = fmaxf(part[tid], part[tid + st]);
+    __syncthreads();
+  }
+  if (tid != 0) return;
+  const float* bn = P + F.src_bn + co;
+  const float g = bn[0], b = bn[F.cout], m = bn[2 * (size_t)F.cout], v = bn[3 * (size_t)F.cout];
+  // the fp32 square root as the host's sqrtss rounds it: the correctly rounded double root, rounded once more (exact for 53 >= 2 * 24 + 2
+  // bits); the fp32 device intrinsic compiles to the 1-ulp hardware instruction
+  const float root = (float)__dsqrt_rn((double)(v + BN_EPS));
+  const float scale = __fdiv_rn(g, root);
+  const float prod = m * scale;
+  sc[ch] = scale;
+  sh[ch] = b - prod;
+  chmax[ch] = nan_seen ? NAN : fabsf(part[0] * scale);
+}
+
+// block li: the scale 2^(14 - exponent(max |w|)) of convolution li (pack_conv_weights_hs_taps); NaN unless the maximum is finite
+__global__ __launch_bounds__(256) void pol_scale_kernel(const PolPackTable* __restrict__ T, const float* __restrict__ chmax,
+                                                        float* __restrict__ rb) {
+  __shared__ float part[256];
+  __shared__ int bad_seen;
+  const int li = blockIdx.x, tid = threadIdx.x;
+  if (tid == 0) bad_seen = 0;
+  __syncthreads();
+  float m = 0.f;
+  bool bad = false;
+  for (int c = tid; c < T->fold[li].cout; c += 256) {
+    const float x = chmax[T->fold[li].chan0 + c];
+    bad |= !(fabsf(x) <= 3.402823466e38f);
+    m = fmaxf(m, x);
+  }
+  part[tid] = m;
+  if (bad) bad_seen = 1;
+  __syncthreads();
+  for (int st = 128; st > 0; st >>= 1) {
+    if (tid < st) part[tid] = fmaxf(part[tid], part[tid + st]);
+    __syncthreads();
+  }
+  if (tid != 0) return;
+  m = part[0];
+  int e = 0;
+  if (m > 0.f) {
+    (void)frexpf(m, &e);
+    e = 14 - e;
+  }
+  rb[li] = bad_seen ? NAN : ldexpf(1.0f, e);
+}
+
+// One thread per (cout tile, K chunk, tap, K half, row) of a half-split packing (pack_desc.h)
+__global__ __launch_bounds__(256) void pol_pack_hs_kernel(const PolPackTable* __restrict__ T, const float* __restrict__ P,
+                                                          const float* __restrict__ sc, const float* __restrict__ rb,
+                                                          float* __restrict__ blob) {
+  const PackDesc& D = T->pack[blockIdx.y];
+  const unsigned i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= D.items) return;
+  hs_pack_item(D, i, rb[D.conv], blob, [&](int row, int k, int tap) {
+    const long long off = eff_src_offset(D, row, k, tap);
+    return off < 0 ? 0.f : P[D.src_v + off] * sc[D.chan0 + row];
+  });
+}
+
+// One thread per 16-byte fragment of an fp32 tap slice [8 channels][64 couts]: four consecutive output channels of one input
+// channel.  Slices in PolStep order: per conv1 tile the chunks phase by phase (nc chunks of 1, 2, 2, 4 taps), then per
+// shortcut tile the nc phase-(0,0) chunks.
+__global__ __launch_bounds__(256) void pol_pack_f32_kernel(const PolPackTable* __restrict__ T, const float* __restrict__ P,
+                                                           const float* __restrict__ sc, float* __restrict__ blob) {
+  const PolF32Desc& D = T->f32[blockIdx.y];
+  const unsigned i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= D.items) return;
+  const int sl = (int)(i >> 7), c = (int)(i >> 4) & 7, m4 = (int)(i & 15) * 4;
+  const int nc = D.nc, per_tile = 9 * nc, n1 = D.nct1 * per_tile;
+  float4 out = make_float4(0.f, 0.f, 0.f, 0.f);
+  if (sl < n1) {
+    const int ct = sl / per_tile, j = sl - ct * per_tile;
+    // j -> (phase, chunk of the phase, tap of the phase): phases hold nc chunks of 1, 2, 2, 4 taps
+    int ph, q, ti;
+    if (j < nc) {
+      ph = 0, q = j, ti = 0;
+    } else if (j < 3 * nc) {
+      ph = 1, q = (j - nc) >> 1, ti = (j - nc) & 1;
+    } else if (j < 5 * nc) {
+      ph = 2, q = (j - 3 * nc) >> 1, ti = (j - 3 * nc) & 1;
+    } else {
+      ph = 3, q = (j - 5 * nc) >> 2, ti = (j - 5 * nc) & 3;
+    }
+    int taps[4];
+    (void)phase_taps(ph, taps);
+    const int tap = taps[ti], ty = tap / 3, tx = tap - 3 * ty, ci = q * 8 + c;
+    if (ci < D.cin) {
+      const int dy = (ph >> 1) ? (ty ? 2 : 0) : 1, dx = (ph & 1) ? (tx ? 2 : 0) : 1;
+      const PolFoldDesc& F = T->fold[D.conv1];
+      const int co = ct * 64 + m4;
+      const float* w = P + F.src_w + ((size_t)co * D.cin + ci) * 9 + dy * 3 + dx;
+      const size_t st = (size_t)D.cin * 9;
+      const float* s = sc + F.chan0 + co;
+      out = make_float4(w[0] * s[0], w[st] * s[1], w[2 * st] * s[2], w[3 * st] * s[3]);
+    }
+  } else {
+    const int r = sl - n1, ct = r / nc, ci = (r - ct * nc) * 8 + c;
+    if (ci < D.cin) {
+      const PolFoldDesc& F = T->fold[D.conv2];
+      const int co = ct * 64 + m4;
+      const float* w = P + F.src_w + (size_t)co * D.cin + ci;
+      const float* s = sc + F.chan0 + co;
+      out = make_float4(w[0] * s[0], w[D.cin] * s[1], w[2 * (size_t)D.cin] * s[2], w[3 * (size_t)D.cin] * s[3]);
+    }
+  }
+  *reinterpret_cast<float4*>(blob + D.dst + (size_t)sl * 512 + c * 64 + m4) = out;
+}
+
+__global__ __launch_bounds__(256) void pol_copy_kernel(const PolPackTable* __restrict__ T, const float* __restrict__ P,
+                                                       const float* __restrict__ sh, float* __restrict__ blob) {
+  const CopyDesc C = T->copy[blockIdx.y];
+  const unsigned i = blockIdx.x * 256 + threadIdx.x;
+  if (i < C.n) blob[C.dst + i] = (C.space ? sh : P)[C.src + i];
+}
+
+int alloc_dev(DeviceBuf& b, size_t bytes, const char* what) {
+  void* p = nullptr;
+  hipError_t e = hipMalloc(&p, bytes);
+  if (e != hipSuccess) {
+    set_error("policy %s allocation of %zu bytes failed: %s", what, bytes, hipGetErrorString(e));
+    return PNPX_ERR_ALLOC;
+  }
+  b.p = p;
+  b.bytes = bytes;
+  return PNPX_OK;
+}
+
+// a fresh blob in the structural layout: zero padding and guards, the step lists; the packing workspace with its table
+int alloc_device_layout(PolicyNet& N, const PolicyLayout& L) {
+  PNPX_TRY(alloc_dev(N.weights, L.total * sizeof(float), "weight"));
+  PNPX_TRY(alloc_dev(N.pack_ws, ws_bytes(L.T.nchan), "packing workspace"));
+  void* h = nullptr;
+  PNPX_HIP(hipHostMalloc(&h, NRB * sizeof(float), hipHostMallocDefault));
+  N.readback = static_cast<float*>(h);
+  PNPX_HIP(hipMemset(N.weights.p, 0, N.weights.bytes));
+  PNPX_HIP(hipMemcpy(N.pack_ws.p, &L.T, sizeof(PolPackTable), hipMemcpyHostToDevice));
+  float* base = static_cast<float*>(N.weights.p);
+  static_assert(sizeof(PolStep) == 8, "PolStep layout");
+  for (int i = 0; i < NF32; ++i) {
+    PNPX_HIP(hipMemcpy(base + L.f32_steps[i], L.steps[i].data(), L.steps[i].size() * sizeof(PolStep), hipMemcpyHostToDevice));
+    PNPX_HIP(hipMemcpy(base + L.f32_nsteps[i], L.nsteps[i].data(), L.nsteps[i].size() * sizeof(int), hipMemcpyHostToDevice));
+  }
+  PNPX_HIP(hipDeviceSynchronize());
+  return PNPX_OK;
+}
+
+// launch descriptors over the blob (the scales follow from the read-back)
+void bind_blob(PolicyNet& N, const PolicyLayout& L) {
+  float* base = static_cast<float*>(N.weights.p);
+  for (int i = 0; i < 17; ++i) {
+    N.conv[i] = PolicyConv();
+    N.conv[i].w = N.conv[i].bias = base;
+    N.conv[i].steps = reinterpret_cast<const PolStep*>(base);
+    N.conv[i].nsteps = reinterpret_cast<const int*>(base);
+  }
+  for (int fi = 0; fi < NF32; ++fi) {
+    PolicyConv& C = N.conv[fi == 0 ? 0 : 1 + 4 * (fi - 1)];
+    C.w = base + L.f32_w[fi];
+    C.bias = base + L.f32_bias[fi];
+    C.steps = reinterpret_cast<const PolStep*>(base + L.f32_steps[fi]);
+    C.nsteps = reinterpret_cast<const int*>(base + L.f32_nsteps[fi]);
+    C.cin = L.f32_K[fi];
+    C.cout = L.f32_cout[fi];
+    C.split_c = L.f32_split[fi];
+  }
+  auto dev = [&](ConvLayerHsDev& D, const float*& bias, int ci) {
+    const PackDesc& P = L.T.pack[ci];
+    D.cin = D.cin_pad = P.K;
+    D.cout = P.rows;
+    D.mt = P.mt;
+    D.w = reinterpret_cast<char*>(base + P.dst);
+    bias = base + L.hs_bias[ci];
+  };
+  dev(N.stem_hs, N.stem_hs_bias, 0);
+  for (int s = 0; s < 4; ++s) {
+    const int c0 = 1 + 5 * s;
+    dev(N.s2_hs[s][0], N.s2_bias[s][0], c0 + 0);
+    dev(N.s2_hs[s][1], N.s2_bias[s][1], c0 + 2);
+    dev(N.conv_hs[3 * s + 0], N.bias_hs[3 * s + 0], c0 + 1);
+    dev(N.conv_hs[3 * s + 1], N.bias_hs[3 * s + 1], c0 + 3);
+    dev(N.conv_hs[3 * s + 2], N.bias_hs[3 * s + 2], c0 + 4);
+  }
+  N.fc_sm_w = base + L.smw;
+  N.fc_sm_b = base + L.smb;
+  N.fc_det_w = base + L.dw;
+  N.fc_det_b = base + L.db;
+  N.fc_det2_w = N.spi_head ? base + L.d2w : nullptr;
+  N.fc_det2_b = N.spi_head ? base + L.d2b : nullptr;
+}
+
+// master -> weight blob on stream s, then the one read-back: the 21 half-split scales
+int repack(pnpx_ctx* ctx, const PolicyLayout& L, hipStream_t s) {
+  PolicyNet& N = ctx->policy;
+  const PolPackWs w = pack_ws(N, L.T.nchan);
+  const float* P = static_cast<const float*>(N.master.p);
+  float* blob = static_cast<float*>(N.weights.p);
+  hipLaunchKernelGGL(pol_fold_kernel, dim3(L.T.nchan), dim3(64), 0, s, w.T, P, w.sc, w.sh, w.chmax);
+  PNPX_LAUNCH_CHECK();
+  hipLaunchKernelGGL(pol_scale_kernel, dim3(NCV), dim3(256), 0, s, w.T, w.chmax, w.rb);
+  PNPX_LAUNCH_CHECK();
+  hipLaunchKernelGGL(pol_pack_hs_kernel, dim3((L.max_hs_items + 255) / 256, NCV), dim3(256), 0, s, w.T, P, w.sc, w.rb, blob);
+  PNPX_LAUNCH_CHECK();
+  hipLaunchKernelGGL(pol_pack_f32_kernel, dim3((L.max_f32_items + 255) / 256, NF32), dim3(256), 0, s, w.T, P, w.sc, blob);
+  PNPX_LAUNCH_CHECK();
+  hipLaunchKernelGGL(pol_copy_kernel, dim3((L.max_copy + 255) / 256, L.T.ncopy), dim3(256), 0, s, w.T, P, w.sh, blob);
+  PNPX_LAUNCH_CHECK();
+  PNPX_HIP(hipMemcpyAsync(N.readback, w.rb, NCV * sizeof(float), hipMemcpyDeviceToHost, s));
+  PNPX_HIP(hipStreamSynchronize(s));
+  for (int i = 0; i < NCV; ++i)
+    if (!std::isfinite(N.readback[i])) {
+      set_error("policy refresh: the weight scale of convolution %d is not finite (NaN weight, or a BatchNorm scale that is not finite: "
+                "running_var NaN or below -eps)", i);
+      PNPX_HIP(hipDeviceSynchronize());
+      policy_free(ctx);
+      return PNPX_ERR_ARG;
+    }
+  auto inv = [&](int ci) { return 1.0f / (N.readback[ci] * HS_ASCALE); };
+  N.stem_hs.inv_scale = inv(0);
+  for (int st = 0; st < 4; ++st) {
+    const int c0 = 1 + 5 * st;
+    N.s2_hs[st][0].inv_scale = inv(c0 + 0);
+    N.s2_hs[st][1].inv_scale = inv(c0 + 2);
+    N.conv_hs[3 * st + 0].inv_scale = inv(c0 + 1);
+    N.conv_hs[3 * st + 1].inv_scale = inv(c0 + 3);
+    N.conv_hs[3 * st + 2].inv_scale = inv(c0 + 4);
+  }
+  N.loaded = true;
+  return PNPX_OK;
+}
+
+}  // namespace
+
+int policy_keep_params(pnpx_ctx* ctx, const float* params_host, size_t n) {
+  PolicyNet& N = ctx->policy;
+  PNPX_TRY(alloc_dev(N.master, n * sizeof(float), "parameter"));
+  PNPX_HIP(hipMemcpy(N.master.p, params_host, n * sizeof(float), hipMemcpyHostToDevice));
+  return PNPX_OK;
+}
+
+int policy_load_device(pnpx_ctx* ctx, const float* params_dev, size_t n, int num_inputs, int n_det, int spi_head, hipStream_t s) {
+  spi_head = spi_head ? 1 : 0;
+  const bool shape_ok = num_inputs >= 1 && num_inputs <= 64 && n_det >= 1 && n_det <= 64;
+  if (!params_dev || !shape_ok || n != policy_num_params(num_inputs, n_det, spi_head)) {
+    set_error("pnpx_policy_load_device: expected %zu parameters for (%d inputs, %d outputs, spi %d), got %zu",
+              shape_ok ? policy_num_params(num_inputs, n_det, spi_head) : (size_t)0, num_inputs, n_det, spi_head, n);
+    return PNPX_ERR_ARG;
+  }
+  PolicyNet& N = ctx->policy;
+  PolicyLayout L;
+  if (!make_layout(num_inputs, n_det, spi_head, L)) {
+    set_error("pnpx_policy_load_device: internal layout error for (%d inputs, %d outputs, spi %d)", num_inputs, n_det, spi_head);
+    return PNPX_ERR_SHAPE;
+  }
+  const bool same_net = N.loaded && N.num_inputs == num_inputs && N.n_det == n_det && N.spi_head == spi_head;
+  if (!(same_net && N.dev_layout)) {
+    // first load / another network / a blob in the host's value-dependent layout: allocate (a refresh allocates nothing).
+    // The arena of the same network is kept: its layout depends on the padded input channels and the image size only.
+    PNPX_HIP(hipDeviceSynchronize());
+    const DeviceBuf arena = N.arena;
+    const int capB = N.capB, capH = N.capH, capW = N.capW;
+    if (same_net) N.arena = DeviceBuf();
+    policy_free(ctx);
+    if (same_net) {
+      N.arena = arena;
+      N.capB = capB;
+      N.capH = capH;
+      N.capW = capW;
+    }
+    N.num_inputs = num_inputs;
+    N.cin_pad = (num_inputs + 7) / 8 * 8;
+    N.n_det = n_det;
+    N.spi_head = spi_head;
+    int st = alloc_device_layout(N, L);
+    if (st == PNPX_OK) st = alloc_dev(N.master, n * sizeof(float), "parameter");
+    if (st != PNPX_OK) {
+      policy_free(ctx);
+      return st;
+    }
+    bind_blob(N, L);
+    N.dev_layout = true;
+  }
+  if (params_dev != N.master.p) PNPX_HIP(hipMemcpyAsync(N.master.p, params_dev, n * sizeof(float), hipMemcpyDeviceToDevice, s));
+  return repack(ctx, L, s);
+}
+
+int policy_params(pnpx_ctx* ctx, float* dst_dev, size_t n, hipStream_t s) {
+  PolicyNet& N = ctx->policy;
+  if (!N.loaded) {
+    set_error("pnpx_policy_params called before an actor was loaded");
+    return PNPX_ERR_NO_WEIGHTS;
+  }
+  const size_t want = policy_num_params(N.num_inputs, N.n_det, N.spi_head);
+  if (!dst_dev || n != want) {
+    set_error("pnpx_policy_params: the loaded actor (%d inputs, %d outputs, spi %d) has %zu parameters, got room for %zu",
+              N.num_inputs, N.n_det, N.spi_head, want, n);
+    return PNPX_ERR_ARG;
+  }
+  PNPX_HIP(hipMemcpyAsync(dst_dev, N.master.p, n * sizeof(float), hipMemcpyDeviceToDevice, s));
+  return PNPX_OK;
+}
+
+}  // namespace pnpx

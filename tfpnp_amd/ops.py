@@ -41,6 +41,22 @@ def critic_flat_params(state_dict, num_inputs):
     return np.concatenate(chunks)
 
 
+def policy_flat_params(state_dict, num_inputs, n_det, spi_head=False):
+    """The flat fp32 parameter vector pnpx_policy_load takes (synth.policy_param_specs order) from an actor state_dict; a
+    missing key or a wrong shape raises PnpxError naming it.  Integer num_batches_tracked entries are not part of it."""
+    from .synth import policy_param_specs
+    chunks = []
+    for key, shape in policy_param_specs(num_inputs, n_det, spi_head):
+        if key not in state_dict:
+            raise PnpxError(f"policy state_dict is missing '{key}'")
+        v = state_dict[key]
+        v = v.detach().cpu().numpy() if isinstance(v, torch.Tensor) else np.asarray(v)
+        if tuple(v.shape) != tuple(shape):
+            raise PnpxError(f"'{key}' has shape {tuple(v.shape)}, expected {tuple(shape)}")
+        chunks.append(np.ascontiguousarray(v, dtype=np.float32).reshape(-1))
+    return np.concatenate(chunks)
+
+
 def context_by_id(cid):
     """The live Context with integer handle `cid` (how contexts travel through torch.ops.pnpx.* schemas)."""
     try:
@@ -109,20 +125,49 @@ class Context:
 
     def load_policy(self, state_dict, num_inputs, n_det, spi_head=False):
         """state_dict with the reference's ResNetActor_* key names (tfpnp/policy/network.py) -> native actor."""
-        from .synth import policy_param_specs
-        chunks = []
-        for key, shape in policy_param_specs(num_inputs, n_det, spi_head):
-            if key not in state_dict:
-                raise PnpxError(f"policy state_dict is missing '{key}'")
-            v = state_dict[key]
-            v = v.detach().cpu().numpy() if isinstance(v, torch.Tensor) else np.asarray(v)
-            if tuple(v.shape) != tuple(shape):
-                raise PnpxError(f"'{key}' has shape {tuple(v.shape)}, expected {tuple(shape)}")
-            chunks.append(np.ascontiguousarray(v, dtype=np.float32).reshape(-1))
-        flat = np.concatenate(chunks)
+        flat = policy_flat_params(state_dict, num_inputs, n_det, spi_head)
         check(_lib.lib().pnpx_policy_load(self.handle, flat.ctypes.data_as(C.c_void_p), flat.size, int(num_inputs),
                                           int(n_det), int(bool(spi_head))))
-        self._policy = (int(num_inputs), int(n_det))
+        self._policy = (int(num_inputs), int(n_det), bool(spi_head))
+
+    def _policy_vector(self, t, who, num_inputs, n_det, spi_head):
+        """A flat actor parameter vector as the library takes it (the checks of _critic_vector): fp32, contiguous, on this
+        context's device, of the length of an actor with this head."""
+        if not isinstance(t, torch.Tensor):
+            raise PnpxError(f"{who}: expected a torch.Tensor, got {type(t).__name__}")
+        if t.device != self.device:
+            raise PnpxError(f"{who}: parameter vector is on {t.device}, the context is on {self.device}")
+        if t.dtype != torch.float32:
+            raise PnpxError(f"{who}: expected float32, got {t.dtype}")
+        if t.dim() != 1 or not t.is_contiguous():
+            raise PnpxError(f"{who}: expected a contiguous 1-D vector, got shape {tuple(t.shape)} with strides {t.stride()}")
+        want = int(_lib.lib().pnpx_policy_num_params(int(num_inputs), int(n_det), int(bool(spi_head))))
+        if t.numel() != want:
+            raise PnpxError(f"{who}: an actor with {num_inputs} inputs and {n_det} outputs"
+                            f"{' (SPI head)' if spi_head else ''} has {want} parameters, got {t.numel()}")
+        return t.detach()
+
+    def load_policy_device(self, flat, num_inputs, n_det, spi_head=False):
+        """flat: the actor's fp32 state as one vector on this context's device, in synth.policy_param_specs order (each
+        convolution followed by its BatchNorm weight, bias, running_mean, running_var; then the heads).  BatchNorm fold and
+        packing run on the device on the current stream; an actor with the same head already loaded here is refreshed in
+        place.  Ends with one small read-back (synchronises the current stream)."""
+        flat = self._policy_vector(flat, "load_policy_device", num_inputs, n_det, spi_head)
+        with torch.cuda.device(self.device):
+            st = _lib.lib().pnpx_policy_load_device(self.handle, _p(flat), flat.numel(), int(num_inputs), int(n_det),
+                                                    int(bool(spi_head)), _stream(flat))
+        if st != 0:
+            self._policy = None        # a failed load leaves the context without an actor
+        check(st)
+        self._policy = (int(num_inputs), int(n_det), bool(spi_head))
+
+    def policy_params(self):
+        """A copy of the live parameter vector (fp32, on this context's device, load_policy_device's order)."""
+        n = int(_lib.lib().pnpx_policy_num_params(*map(int, self._policy))) if self._policy is not None else 1
+        out = torch.empty((n,), device=self.device, dtype=torch.float32)
+        with torch.cuda.device(self.device):
+            check(_lib.lib().pnpx_policy_params(self.handle, _p(out), n, _stream(out)))
+        return out
 
     def load_critic(self, state_dict, num_inputs):
         """state_dict of the reference's ResNet_wobn(num_inputs, 18, 1) (tfpnp/trainer/mddpg/critic.py) -> native critic

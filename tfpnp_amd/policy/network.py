@@ -4,8 +4,14 @@ constructor arguments, same `forward(state, idx_stop, train, hidden)` contract a
 The ResNet-18 encoder and both heads run natively (pnpx_policy_forward: BatchNorm folded, stride-2 convolutions on a
 space-to-depth grid with tap masks, fp32 MFMA); what stays here is O(B) scalar work: sampling / arg-max of idx_stop,
 log-probability, entropy and the action-range mapping (network.py:149-175).  Eval-mode BatchNorm only -- that is how
-the reference runs the actor in rollouts (trainer.py:216-221) and in evaluation (evaluator.py:23); training the actor
-itself (batch statistics, weight gradients) is out of scope.
+the reference runs the actor in rollouts (trainer.py:216-221) and in evaluation (evaluator.py:23).
+
+The weights are LIVE, as the native critic's are: the context keeps the flat parameter vector (synth.policy_param_specs
+order: parameters AND BatchNorm running statistics) on the device, and `load_flat_` / utils.misc.hard_update replace it
+there and re-derive the packed weights on the device (BatchNorm fold included), so the native actor can follow a torch
+actor that an optimiser trains (trainer.py:201-204) and run the next rollout (:216-222) without a host reload.
+`load_state_dict` is the checkpoint path (folds and packs on the host).  Training the actor itself (batch statistics,
+weight gradients) is out of scope.
 """
 from collections import OrderedDict
 from typing import Optional
@@ -26,26 +32,94 @@ class ResNetActorBase(nn.Module):
         self.num_actions = num_actions
         self.action_range = None
         self.action_bundle = action_bundle
-        self._state = None
+        self._state = None      # CPU copy of the last load_state_dict; None once the weights were changed on a device
+        self._live = None       # key of the context whose device-resident parameters are the weights (then _state is None)
         self._ctx = {}
         if state_dict is not None:
             self.load_state_dict(state_dict)
 
+    @property
+    def n_det(self):
+        return self.action_bundle * self.num_actions
+
     # weights: the reference's own state_dict (torch.load of actor.pkl, trainer.py:254-261)
     def load_state_dict(self, state_dict, strict=True):
         self._state = {k: (v.detach().cpu() if isinstance(v, torch.Tensor) else v) for k, v in state_dict.items()}
+        self._live = None
         self._ctx = {}
+
+    @property
+    def device(self):
+        """The device the weights live on: where they were last changed, else the first device they were used on, else None."""
+        key = self._live if self._live is not None else next(iter(self._ctx), None)
+        return None if key is None else torch.device(*key)
 
     def context(self, device):
         device = torch.device(device)
         key = (device.type, device.index if device.index is not None else torch.cuda.current_device())
         if key not in self._ctx:
-            if self._state is None:
-                raise ValueError('actor weights were not loaded (load_state_dict)')
+            if self._live is None and self._state is None:
+                raise ValueError('actor weights were not loaded (load_state_dict / load_flat_)')
             ctx = ops.Context(device)
-            ctx.load_policy(self._state, self.in_dim, self.action_bundle * self.num_actions, self.spi_head)
+            if self._live is not None:
+                # the weights were changed on another device: that device's vector is the truth, not the stale CPU copy
+                ctx.load_policy_device(self._ctx[self._live].policy_params().to(ctx.device), self.in_dim, self.n_det, self.spi_head)
+            else:
+                ctx.load_policy(self._state, self.in_dim, self.n_det, self.spi_head)
             self._ctx[key] = ctx
         return self._ctx[key]
+
+    def parameters_flat(self, device):
+        """A copy of the weights as one fp32 vector on `device`, in synth.policy_param_specs order."""
+        return self.context(device).policy_params()
+
+    def load_flat_(self, flat):
+        """Load a flat fp32 vector that lives on a ROCm device (synth.policy_param_specs order: every fp32 state_dict entry
+        of the reference actor, running statistics included): BatchNorm fold and packing run on that device; a context that
+        already exists there is refreshed in place.  Returns self."""
+        if not isinstance(flat, torch.Tensor):
+            raise ops.PnpxError(f"load_flat_: expected a torch.Tensor, got {type(flat).__name__}")
+        if flat.device.type != "cuda":
+            raise ops.PnpxError(f"load_flat_: device {flat.device}; tfpnp_amd runs on MI355X only, there is no CPU path")
+        key = (flat.device.type, flat.device.index if flat.device.index is not None else torch.cuda.current_device())
+        ctx = self._ctx.get(key)
+        fresh = ctx is None
+        if fresh:
+            ctx = ops.Context(torch.device(*key))
+        try:
+            ctx.load_policy_device(flat, self.in_dim, self.n_det, self.spi_head)
+        except ops.PnpxError:
+            if not fresh and ctx._policy is None:      # the refresh itself failed: this context holds no actor any more
+                del self._ctx[key]
+                if self._live == key:
+                    self._live = None
+            raise
+        # every other copy is stale from here on
+        self._ctx = {key: ctx}
+        self._live = key
+        self._state = None
+        return self
+
+    def state_dict(self, *args, destination=None, prefix='', keep_vars=False):
+        """The fp32 entries of the reference actor's state_dict (synth.policy_param_specs), read from the live weights.
+        Loading it into a fresh native actor reproduces this one bit for bit.  The integer `num_batches_tracked` buffers of
+        the reference's BatchNorm layers are not kept: eval-mode BatchNorm does not read them."""
+        from ..synth import policy_param_specs
+        out = destination if destination is not None else OrderedDict()
+        if self._live is not None:
+            flat = self._ctx[self._live].policy_params()
+        elif self._state is not None:
+            flat = torch.from_numpy(ops.policy_flat_params(self._state, self.in_dim, self.n_det, self.spi_head))
+        else:
+            return out
+        pos = 0
+        for key, shape in policy_param_specs(self.in_dim, self.n_det, self.spi_head):
+            n = 1
+            for d in shape:
+                n *= d
+            out[prefix + key] = flat[pos:pos + n].view(shape).clone()
+            pos += n
+        return out
 
     def forward(self, state, idx_stop, train, hidden):
         """-> (action dict incl. 'idx_stop', log-prob of idx_stop [B,1], entropy of the stop head [B,1], hidden)"""
