@@ -288,6 +288,17 @@ int pnpx_rows_gather(pnpx_ctx* ctx, int n_tensors, const void* const* src_host, 
 /* Write-back `state[...][self.idx_left, ...] = value` (base.py:171-172): dst_t[idx[r]] = src_t[r]. */
 int pnpx_rows_scatter(pnpx_ctx* ctx, int n_tensors, const void* const* src_host, void* const* dst_host,
                       const size_t* row_bytes_host, const int64_t* idx, int n_rows, void* stream);
+/* Replay-memory store: what `for i in range(B): buffer.store(ob[i])` (trainer/mddpg/trainer.py:232-234 over
+ * tfpnp/utils/rpm.py:10-19) leaves behind, for every tensor of the observation at once:
+ * dst_t[(first_slot + r) % capacity] = src_t[r] for r < n_rows; ONE launch per 12 tensors (and per 65535 rows).  The slot is
+ * computed on the device in 64-bit integers -- no index array is built or uploaded -- and a store may wrap around the end of
+ * the ring in the middle of a batch.  dst_t holds `capacity` rows of row_bytes[t] bytes.
+ * Needs 0 <= first_slot < capacity and 0 <= n_rows <= capacity (two rows must never race for one slot): else PNPX_ERR_ARG
+ * and nothing is written.  first_slot and capacity are launch ARGUMENTS, so a captured graph replays the slot it was
+ * captured with: with a moving head this call is not graph-capturable.  Sampling needs no entry of its own: it is
+ * pnpx_rows_gather with a device list of slots. */
+int pnpx_ring_store(pnpx_ctx* ctx, int n_tensors, const void* const* src_host, void* const* dst_host,
+                    const size_t* row_bytes_host, int64_t first_slot, int64_t capacity, int n_rows, void* stream);
 /* `self.idx_left = self.idx_left[idx_stop == 0]; all_done = len(self.idx_left) == 0` (base.py:180-182) as a
  * device-side stream compaction: idx_out[0..n_live) = the idx_left[i] with idx_stop[i] == 0 (int64, in order).
  * *n_live_host receives the count: this call SYNCHRONISES `stream` -- it is the one host read of an env step

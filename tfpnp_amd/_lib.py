@@ -70,6 +70,8 @@ _SIGNATURES = {
                                    C.c_int, c_void_p]),
     "pnpx_rows_scatter": (C.c_int, [c_void_p, C.c_int, C.POINTER(c_void_p), C.POINTER(c_void_p), C.POINTER(C.c_size_t), _P,
                                     C.c_int, c_void_p]),
+    "pnpx_ring_store": (C.c_int, [c_void_p, C.c_int, C.POINTER(c_void_p), C.POINTER(c_void_p), C.POINTER(C.c_size_t),
+                                  C.c_int64, C.c_int64, C.c_int, c_void_p]),
     "pnpx_live_compact": (C.c_int, [c_void_p, _P, _P, C.c_int, _P, C.POINTER(C.c_int), c_void_p]),
     "pnpx_policy_ob_pack": (C.c_int, [c_void_p, C.c_int, C.POINTER(c_void_p), C.POINTER(C.c_int), C.POINTER(C.c_int), _P,
                                       C.c_int, C.c_int, C.c_int, _P, c_void_p]),

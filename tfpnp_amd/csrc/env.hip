@@ -5,6 +5,8 @@
 //     base.py:180-182) as a device-side stream compaction whose count is the ONE host read of a step,
 //   * the policy observation (`get_policy_ob`, tasks/csmri/env.py:14-23 and siblings: complex2real / complex2channel
 //     views concatenated on the channel axis) packed by one kernel straight from the state tensors.
+//   * the replay-memory store of a whole observation batch (`for i in range(B): buffer.store(ob[i])`,
+//     trainer/mddpg/trainer.py:224-234 over utils/rpm.py:10-19) as ONE launch into device-resident ring storage,
 // All of it is HBM-bound byte shuffling: 16-byte accesses, rows on grid.y, tensors on grid.z.
 #include "common.h"
 
@@ -20,6 +22,25 @@ struct RowsArgs {
   int n_rows;
 };
 
+// One row of nb bytes, spread over the blocks of grid.x.  `align` = row_bytes | src base | dst base of the tensor: every row
+// starts a multiple of row_bytes behind its base, so these bits decide the access width (16, 4 or 1 bytes) for all rows.
+// The grid-stride loop takes rows longer than one sweep of the grid.
+__device__ __forceinline__ void copy_row(const char* s, char* d, unsigned long long nb, unsigned long long align) {
+  const unsigned long long i0 = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x;
+  const unsigned long long stride = (unsigned long long)gridDim.x * blockDim.x;
+  if ((align & 15ull) == 0) {
+    const uint4* s4 = reinterpret_cast<const uint4*>(s);
+    uint4* d4 = reinterpret_cast<uint4*>(d);
+    for (unsigned long long i = i0; i < nb / 16; i += stride) d4[i] = s4[i];
+  } else if ((align & 3ull) == 0) {
+    const unsigned* s1 = reinterpret_cast<const unsigned*>(s);
+    unsigned* d1 = reinterpret_cast<unsigned*>(d);
+    for (unsigned long long i = i0; i < nb / 4; i += stride) d1[i] = s1[i];
+  } else {
+    for (unsigned long long i = i0; i < nb; i += stride) d[i] = s[i];
+  }
+}
+
 // SCATTER = false: dst[r] = src[idx[r]];  true: dst[idx[r]] = src[r]
 template <bool SCATTER>
 __global__ __launch_bounds__(256) void rows_copy_kernel(RowsArgs a) {
@@ -28,19 +49,25 @@ __global__ __launch_bounds__(256) void rows_copy_kernel(RowsArgs a) {
   const long long big = a.idx[r];
   const char* s = a.src[t] + (SCATTER ? (unsigned long long)r : (unsigned long long)big) * nb;
   char* d = a.dst[t] + (SCATTER ? (unsigned long long)big : (unsigned long long)r) * nb;
-  const unsigned long long i0 = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x;
-  const unsigned long long stride = (unsigned long long)gridDim.x * blockDim.x;
-  if (((nb | (unsigned long long)(uintptr_t)a.src[t] | (unsigned long long)(uintptr_t)a.dst[t]) & 15ull) == 0) {
-    const uint4* s4 = reinterpret_cast<const uint4*>(s);
-    uint4* d4 = reinterpret_cast<uint4*>(d);
-    for (unsigned long long i = i0; i < nb / 16; i += stride) d4[i] = s4[i];
-  } else if (((nb | (unsigned long long)(uintptr_t)a.src[t] | (unsigned long long)(uintptr_t)a.dst[t]) & 3ull) == 0) {
-    const unsigned* s1 = reinterpret_cast<const unsigned*>(s);
-    unsigned* d1 = reinterpret_cast<unsigned*>(d);
-    for (unsigned long long i = i0; i < nb / 4; i += stride) d1[i] = s1[i];
-  } else {
-    for (unsigned long long i = i0; i < nb; i += stride) d[i] = s[i];
-  }
+  copy_row(s, d, nb, nb | (unsigned long long)(uintptr_t)a.src[t] | (unsigned long long)(uintptr_t)a.dst[t]);
+}
+
+// Replay-memory store (tfpnp/utils/rpm.py:10-19 for a whole batch of rows): dst[(first_slot + r) % capacity] = src[r].
+// The slot is computed here, in 64-bit integers; no index tensor exists.  n_rows <= capacity (checked by the entry), so no
+// two rows of one launch share a slot.
+struct RingArgs {
+  const char* src[ENV_MAX_T];
+  char* dst[ENV_MAX_T];
+  unsigned long long row_bytes[ENV_MAX_T];
+  long long first_slot, capacity;
+};
+
+__global__ __launch_bounds__(256) void ring_store_kernel(RingArgs a) {
+  const int t = blockIdx.z, r = blockIdx.y;
+  const unsigned long long nb = a.row_bytes[t];
+  const unsigned long long slot = (unsigned long long)((a.first_slot + (long long)r) % a.capacity);
+  copy_row(a.src[t] + (unsigned long long)r * nb, a.dst[t] + slot * nb, nb,
+           nb | (unsigned long long)(uintptr_t)a.src[t] | (unsigned long long)(uintptr_t)a.dst[t]);
 }
 
 // idx_out[0..n_live) = idx_left[i] for the i with idx_stop[i] == 0, in order; one workgroup (batches are <= a few
@@ -167,6 +194,14 @@ using namespace pnpx;
   std::lock_guard<std::mutex> _lk((ctx)->mu); \
   PNPX_HIP(hipSetDevice((ctx)->device))
 
+// grid.x for rows of at most `mx` bytes: 64 x 256 lanes x 16 B = 256 KiB per sweep of a row; longer rows loop
+static unsigned rows_grid_x(size_t mx) {
+  size_t gx = (mx / 16 + 255) / 256;
+  if (gx < 1) gx = 1;
+  if (gx > 64) gx = 64;
+  return (unsigned)gx;
+}
+
 static int rows_copy(pnpx_ctx* ctx, bool scatter, int n_tensors, const void* const* src_host, void* const* dst_host,
                      const size_t* row_bytes_host, const int64_t* idx, int n_rows, void* stream) {
   LOCK_CTX(ctx);
@@ -193,10 +228,7 @@ static int rows_copy(pnpx_ctx* ctx, bool scatter, int n_tensors, const void* con
     }
     a.idx = reinterpret_cast<const long long*>(idx);
     a.n_rows = n_rows;
-    size_t gx = (mx / 16 + 255) / 256;
-    if (gx < 1) gx = 1;
-    if (gx > 64) gx = 64;   // 64 x 256 lanes x 16 B = 256 KiB per sweep of a row; longer rows loop
-    const dim3 grid((unsigned)gx, (unsigned)n_rows, (unsigned)nt);
+    const dim3 grid(rows_grid_x(mx), (unsigned)n_rows, (unsigned)nt);
     if (scatter)
       hipLaunchKernelGGL(rows_copy_kernel<true>, grid, dim3(256), 0, s, a);
     else
@@ -207,6 +239,42 @@ static int rows_copy(pnpx_ctx* ctx, bool scatter, int n_tensors, const void* con
 }
 
 extern "C" {
+
+int pnpx_ring_store(pnpx_ctx* ctx, int n_tensors, const void* const* src_host, void* const* dst_host,
+                    const size_t* row_bytes_host, int64_t first_slot, int64_t capacity, int n_rows, void* stream) {
+  LOCK_CTX(ctx);
+  if (n_tensors < 0 || n_rows < 0 || (n_tensors > 0 && (!src_host || !dst_host || !row_bytes_host)) || capacity <= 0 ||
+      first_slot < 0 || first_slot >= capacity || (int64_t)n_rows > capacity) {
+    set_error("pnpx_ring_store: bad arguments (need 0 <= first_slot < capacity and 0 <= n_rows <= capacity)");
+    return PNPX_ERR_ARG;
+  }
+  for (int t = 0; t < n_tensors; ++t)
+    if (!src_host[t] || !dst_host[t]) {
+      set_error("pnpx_ring_store: null tensor pointer");
+      return PNPX_ERR_ARG;
+    }
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  constexpr int MAX_GRID_Y = 65535;   // more rows than grid.y holds go out in further launches, each with its own first slot
+  for (int r0 = 0; r0 < n_rows; r0 += MAX_GRID_Y) {
+    const int nr = (n_rows - r0 < MAX_GRID_Y) ? (n_rows - r0) : MAX_GRID_Y;
+    for (int t0 = 0; t0 < n_tensors; t0 += ENV_MAX_T) {
+      const int nt = (n_tensors - t0 < ENV_MAX_T) ? (n_tensors - t0) : ENV_MAX_T;
+      RingArgs a{};
+      size_t mx = 0;
+      for (int t = 0; t < nt; ++t) {
+        a.row_bytes[t] = row_bytes_host[t0 + t];
+        a.src[t] = static_cast<const char*>(src_host[t0 + t]) + (size_t)r0 * a.row_bytes[t];
+        a.dst[t] = static_cast<char*>(dst_host[t0 + t]);
+        if (a.row_bytes[t] > mx) mx = a.row_bytes[t];
+      }
+      a.first_slot = (first_slot + r0) % capacity;
+      a.capacity = capacity;
+      hipLaunchKernelGGL(ring_store_kernel, dim3(rows_grid_x(mx), (unsigned)nr, (unsigned)nt), dim3(256), 0, s, a);
+      PNPX_LAUNCH_CHECK();
+    }
+  }
+  return PNPX_OK;
+}
 
 int pnpx_rows_gather(pnpx_ctx* ctx, int n_tensors, const void* const* src_host, void* const* dst_host,
                      const size_t* row_bytes_host, const int64_t* idx, int n_rows, void* stream) {

@@ -1135,6 +1135,43 @@ def rows_scatter(values, targets, idx, n_rows):
         _rows_call(_lib.lib().pnpx_rows_scatter, vals, list(targets), vals, idx, n_rows, idx.device)
 
 
+def ring_store(values, storages, first_slot, n_rows):
+    """storages[k][(first_slot + r) % capacity] = values[k][r] for r < n_rows and every k, in ONE launch per 12 tensors: the
+    replay-memory store of a whole batch (tfpnp/trainer/mddpg/trainer.py:232-234 over tfpnp/utils/rpm.py:10-19).  In place;
+    capacity = the storages' common leading dimension; 0 <= first_slot < capacity, 0 <= n_rows <= capacity.  The slot is
+    computed on the device, no index tensor is built.  Issued on the current stream of the storages' device."""
+    storages = list(storages)
+    values = list(values)
+    if len(values) != len(storages):
+        raise PnpxError(f"ring_store: {len(values)} values for {len(storages)} storages")
+    vals = []
+    for v, t in zip(values, storages):
+        if not isinstance(t, torch.Tensor) or t.device.type != "cuda" or not t.is_contiguous() or t.dim() < 1:
+            raise PnpxError("ring_store: storages must be contiguous device tensors")
+        if t.shape[0] != storages[0].shape[0] or t.device != storages[0].device:
+            raise PnpxError("ring_store: storages must share their leading dimension (the capacity) and their device")
+        v = _dense(v, "value")
+        if v.dtype != t.dtype or tuple(v.shape[1:]) != tuple(t.shape[1:]) or v.shape[0] < n_rows or v.device != t.device:
+            raise PnpxError(f"ring_store: value {tuple(v.shape)}/{v.dtype} does not fit storage {tuple(t.shape)}/{t.dtype}")
+        vals.append(v)
+    if not vals:
+        return
+    capacity = int(storages[0].shape[0])
+    first_slot, n_rows = int(first_slot), int(n_rows)
+    if not (0 <= first_slot < capacity and 0 <= n_rows <= capacity):
+        raise PnpxError(f"ring_store: first_slot {first_slot} / n_rows {n_rows} outside a ring of capacity {capacity}")
+    if n_rows == 0:
+        return
+    n = len(vals)
+    S = (C.c_void_p * n)(*[v.data_ptr() for v in vals])
+    D = (C.c_void_p * n)(*[t.data_ptr() for t in storages])
+    RB = (C.c_size_t * n)(*[(t.numel() // capacity) * t.element_size() for t in storages])
+    dev = storages[0].device
+    ctx = default_context(dev)
+    with torch.cuda.device(dev):
+        check(_lib.lib().pnpx_ring_store(ctx.handle, n, S, D, RB, first_slot, capacity, n_rows, _stream(storages[0])))
+
+
 def live_compact(idx_left, idx_stop, n):
     """(idx_left[:n][idx_stop == 0] in a buffer of capacity n, number of survivors as a Python int).
     Synchronises the current stream: the one host read of an env step (tfpnp/env/base.py:180-182)."""

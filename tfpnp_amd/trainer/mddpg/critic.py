@@ -11,8 +11,8 @@ utils.misc.soft_update / hard_update replace or move it there and re-pack on the
 target critic can follow a critic that a torch optimiser trains (trainer.py:182, :212) and the value term can be taken on
 the freshly stepped critic (:190) without a host reload.  `load_state_dict` is the checkpoint path (folds on the host).
 No weight gradient exists (the reference throws the critic's weight gradients from the actor loss away, trainer.py:206).
-Out of scope: critic weight gradients, value_loss, optimiser steps, replay, the MDDPG trainer loop, a trainable actor,
-depths other than 18.  (The native actor has the same live weights: policy/network.py.)
+Out of scope: critic weight gradients, value_loss, optimiser steps, the MDDPG trainer loop, a trainable actor,
+depths other than 18.  (The native actor has the same live weights: policy/network.py; the replay memory is utils/rpm.py.)
 """
 import torch
 import torch.nn as nn
