@@ -1,0 +1,57 @@
+"""The critic's side of the MDDPG update on native kernels (tfpnp/trainer/mddpg/trainer.py:198-212).
+
+    value_loss = criterion(Q_target, V_cur)          :195-198
+    value_loss.backward(); clip_grad_norm_           :207-208
+    critic_optim.step()                              :209
+    soft_update(critic_target, critic, tau)          :212
+
+The critic and its target are native ResNet_wobn modules.  The trainable state is ONE flat nn.Parameter on the device
+(synth.critic_param_specs order): `param_grad` writes value_loss.backward() into its .grad -- grad_value = d value_loss / d V
+= 2 (V - Q) / B for the mean squared error -- torch clips and steps it, `load_flat_` hands the stepped vector to the native
+critic (weight-norm fold and packing on the device) and `soft_update_` moves the target.  No torch copy of the network, no
+F.conv2d.
+
+usage (GPU box):  python examples/train_critic.py [steps] [B] [H]
+"""
+import os
+import sys
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import numpy as np
+import torch
+import torch.nn as nn
+
+from tfpnp_amd import synth
+from tfpnp_amd.trainer.mddpg.critic import ResNet_wobn
+
+
+def run(steps=5, B=2, H=64, num_inputs=9, tau=0.001, lr=1e-4, discount=0.99, seed=0, log=print):
+    """-> (value_loss per step, the native critic, the native target)"""
+    dev = torch.device("cuda:0")
+    torch.manual_seed(seed)
+    params = synth.make_critic_params(num_inputs, seed)
+    flat = nn.Parameter(torch.from_numpy(np.concatenate([params[k].reshape(-1) for k, _ in synth.critic_param_specs(num_inputs)])).to(dev))
+    critic = ResNet_wobn(num_inputs, 18, 1).load_flat_(flat.detach())
+    target = ResNet_wobn(num_inputs, 18, 1).load_flat_(flat.detach())             # hard_update, trainer.py:54-55
+    opt = torch.optim.Adam([flat], lr=lr)
+    ob, ob2 = torch.rand(B, num_inputs, H, H, device=dev), torch.rand(B, num_inputs, H, H, device=dev)
+    reward = torch.randn(B, 1, device=dev)
+    history = []
+    for it in range(steps):
+        with torch.no_grad():
+            Q = reward + discount * target(ob2)                                   # trainer.py:182-194
+            V = critic(ob)
+            loss = ((V - Q) ** 2).mean()                                          # :195-198
+        flat.grad = critic.param_grad(ob, 2.0 * (V - Q) / B)                      # value_loss.backward(), :207
+        torch.nn.utils.clip_grad_norm_([flat], 50)                                # :208
+        opt.step()                                                                # :209
+        critic.load_flat_(flat.detach())
+        target.soft_update_(flat.detach(), tau)                                   # :212
+        history.append(float(loss))
+        log(f"step {it}: value_loss {history[-1]:.6f}  |grad| {float(flat.grad.norm()):.4f}")
+    return history, critic, target
+
+
+if __name__ == "__main__":
+    a = [int(v) for v in sys.argv[1:4]]
+    run(*a)

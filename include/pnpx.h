@@ -219,8 +219,8 @@ int pnpx_policy_params(pnpx_ctx* ctx, float* dst_dev, size_t n_params, void* str
  * tasks/<task>/main.py): 3x3 stride-2 stem, four stages of two BasicBlocks (critic.py:37-60) each entered with stride 2 and a 1x1
  * stride-2 shortcut, adaptive_avg_pool2d(1), Linear(512, 1).  Convolutions are weight-normalised with bias
  * (weight = weight_g * weight_v / ||weight_v||, norm per output channel; critic.py:7-8); activations are TReLU
- * (relu(x - alpha) + alpha, one scalar alpha each; critic.py:11-19).  Only the gradient with respect to the observation is
- * computed; there are no weight gradients.  The weights are LIVE: the context keeps the raw parameter vector on the device, and
+ * (relu(x - alpha) + alpha, one scalar alpha each; critic.py:11-19).  Gradients: with respect to the observation
+ * (pnpx_critic_backward) and with respect to the parameters (pnpx_critic_param_grad).  The weights are LIVE: the context keeps the raw parameter vector on the device, and
  * pnpx_critic_load_device / pnpx_critic_soft_update (below) replace or move it and re-derive the packed weights on the device.
  * pnpx_critic_load folds weight-norm and packs on the host (once per checkpoint).  One critic per context.
  * params_host: the fp32 content of state_dict() in registration order (82 tensors),
@@ -259,6 +259,18 @@ int pnpx_critic_forward(pnpx_ctx* ctx, const float* ob, float* value, int B, int
  * kept between calls.  Exactly linear in grad_value (a zero entry gives a zero row). */
 int pnpx_critic_backward(pnpx_ctx* ctx, const float* ob, const float* grad_value, float* grad_ob, int B, int H, int W,
                          void* stream);
+
+/* Gradient of the critic's output with respect to its own parameters -- value_loss.backward() (trainer/mddpg/trainer.py:198,207):
+ * grad_params[i] = d(sum_b grad_value[b] * V_b) / d(params[i]), n_params = pnpx_critic_num_params(num_inputs) floats on the device in
+ * pnpx_critic_load's order (the 82 tensors, weight_g and weight_v separately, the 17 thresholds, fc).  Overwrites grad_params; does
+ * not accumulate.  ob, grad_value, the shape rules and the error codes are those of pnpx_critic_backward; an n_params that does
+ * not match the loaded critic returns PNPX_ERR_ARG.  The forward is re-computed internally and nothing is kept between calls.
+ * Deterministic (two calls return the same bytes: the pixel axis is split into pieces that are added in a fixed order, no
+ * atomics) and exactly linear in grad_value.  Its workspace belongs to the context and grows to the largest size seen; a call
+ * that does not grow it allocates nothing and does not synchronise the device.  No optimiser: step a flat parameter with the
+ * optimiser of your choice and hand it to pnpx_critic_load_device. */
+int pnpx_critic_param_grad(pnpx_ctx* ctx, const float* ob, const float* grad_value, float* grad_params, size_t n_params, int B,
+                           int H, int W, void* stream);
 
 /* ---- transforms (tfpnp/utils/transforms.py) ------------------------------------------------------ */
 /* fft2 / ifft2 (transforms.py:68-103): centered (ifftshift -> FFT -> fftshift), orthonormal, over the

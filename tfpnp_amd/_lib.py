@@ -59,6 +59,7 @@ _SIGNATURES = {
     "pnpx_critic_params": (C.c_int, [c_void_p, _P, C.c_size_t, c_void_p]),
     "pnpx_critic_forward": (C.c_int, [c_void_p, _P, _P, C.c_int, C.c_int, C.c_int, c_void_p]),
     "pnpx_critic_backward": (C.c_int, [c_void_p, _P, _P, _P, C.c_int, C.c_int, C.c_int, c_void_p]),
+    "pnpx_critic_param_grad": (C.c_int, [c_void_p, _P, _P, _P, C.c_size_t, C.c_int, C.c_int, C.c_int, c_void_p]),
     "pnpx_unet_profile": (C.c_int, [c_void_p, _P, _P, _P, C.c_int, C.c_int, C.c_int, c_void_p, C.c_int,
                                     c_float_p, C.POINTER(C.c_double), C.POINTER(C.c_char_p), C.POINTER(C.c_int)]),
     "pnpx_fft2": (C.c_int, [c_void_p, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_void_p]),

@@ -249,6 +249,16 @@ int pnpx_critic_backward(pnpx_ctx* ctx, const float* ob, const float* grad_value
   return critic_backward(ctx, ob, grad_value, grad_ob, B, H, W, static_cast<hipStream_t>(stream));
 }
 
+int pnpx_critic_param_grad(pnpx_ctx* ctx, const float* ob, const float* grad_value, float* grad_params, size_t n_params, int B, int H,
+                           int W, void* stream) {
+  LOCK_CTX(ctx);
+  if (!ob || !grad_value || !grad_params) {
+    set_error("pnpx_critic_param_grad: null pointer");
+    return PNPX_ERR_ARG;
+  }
+  return critic_param_grad(ctx, ob, grad_value, grad_params, n_params, B, H, W, static_cast<hipStream_t>(stream));
+}
+
 int pnpx_ctx_reserve(pnpx_ctx* ctx, int B, int H, int W) {
   LOCK_CTX(ctx);
   if (B <= 0 || H < 16 || W < 16) {

@@ -136,6 +136,9 @@ struct CriticNet {
   DeviceBuf master;                  // [critic_num_params(num_inputs)] floats
   DeviceBuf pack_ws;                 // layer table, per-channel fold scales and maxima, the block read back per refresh
   float* readback = nullptr;         // pinned host copy of that block: 21 weight scales, 21 thresholds, max |fc_w|
+  // parameter gradients (pnpx_critic_param_grad): clip indicator, W * indicator, K-split slabs + reduction blocks; each grows to
+  // the largest size seen
+  DeviceBuf grad_m, grad_wm, grad_slab;
 };
 
 // number of independent launch chains for a B-image denoiser forward (unet.hip; option "chains", 0 = automatic)
@@ -399,6 +402,8 @@ int critic_soft_update(pnpx_ctx* ctx, const float* src_dev, size_t n, float one_
 int critic_params(pnpx_ctx* ctx, float* dst_dev, size_t n, hipStream_t s);
 int critic_forward(pnpx_ctx* ctx, const float* ob, float* value, int B, int H, int W, hipStream_t s);
 int critic_backward(pnpx_ctx* ctx, const float* ob, const float* grad_value, float* grad_ob, int B, int H, int W, hipStream_t s);
+int critic_param_grad(pnpx_ctx* ctx, const float* ob, const float* grad_value, float* grad_params, size_t n, int B, int H, int W,
+                      hipStream_t s);
 void critic_free(pnpx_ctx* ctx);
 
 // FFT building blocks (fft.hip)

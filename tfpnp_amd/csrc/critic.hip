@@ -1,12 +1,12 @@
-// Value network (critic) forward and input gradient, live weights (no weight gradients).
+// Value network (critic) forward, input gradient and parameter gradients, live weights.
 //
 // Live weights: the context keeps the flat fp32 parameter vector on the device (CriticNet::master).  pnpx_critic_load folds
 // weight-norm and packs on the host; pnpx_critic_load_device and pnpx_critic_soft_update derive the same packed blob from
 // the device vector with four launches ("device-side packing" below) and refresh an already loaded critic in place -- no
 // allocation, no device-wide synchronisation, the arena is kept.  Thresholds, weight scales and max |fc_w| are launch
 // arguments, so each refresh ends with one small read-back and a synchronisation of the caller's stream: a refresh cannot be
-// captured into a graph and has to be issued on the stream the critic's other calls use.  Still missing: weight gradients,
-// value_loss, optimiser steps, a trainer.  (The actor's refresh: policy_pack.hip.)
+// captured into a graph and has to be issued on the stream the critic's other calls use.  Parameter gradients: critic_param_grad below,
+// kernels in critic_grad.hip.  Still missing: value_loss, optimiser steps, a trainer.  (The actor's refresh: policy_pack.hip.)
 //
 // Replaces ResNet_wobn(num_inputs, 18, 1).forward (tfpnp/trainer/mddpg/critic.py:95-131) and the autograd pass through it
 // with respect to its INPUT, which is how the actor loss uses it (trainer/mddpg/trainer.py:180-192: V_next = critic(eval_ob2)
@@ -32,11 +32,13 @@
 // shortcut's adjoint (1x1, existing linear instance) is its residual operand on the phase-(0,0) channel groups.
 // Gradients are carried as HS8 tensors of  s * dV/d(.)  with s a power of two that brings the head's largest entry into [1, 2);
 // grad_value[b] / s is applied by the last kernel in fp32, so the result is exactly linear in grad_value.
+#include <algorithm>
 #include <cmath>
 #include <cstring>
 
 #include "common.h"
 #include "conv_hs.h"
+#include "critic_grad.h"
 #include "hs_rec.h"
 #include "hs_relayout.h"
 #include "pack_desc.h"
@@ -592,7 +594,9 @@ struct Launch {   // one convolution launch of either pass
   const CAct* res = nullptr;
   const CAct* mask = nullptr;
 };
-int run_conv(pnpx_ctx* ctx, float* A, const Launch& L, const CAct& in, const CAct& out, int B, int h, int w, hipStream_t s) {
+// (tensors by address: the parameter-gradient pass keeps two of its own outside the arena)
+int run_conv_ptr(pnpx_ctx* ctx, const Launch& L, const char* in, int inC, char* out, int outC, const char* res, int resC, const char* mask,
+                 int maskC, int B, int h, int w, hipStream_t s) {
   ConvLayerHs Lh;
   Lh.cin = L.D->cin;
   Lh.cout = L.D->cout;
@@ -605,19 +609,23 @@ int run_conv(pnpx_ctx* ctx, float* A, const Launch& L, const CAct& in, const CAc
   f.slope = 1.f;           // (read by the plain instance only: linear)
   f.taps = L.taps;
   f.wreg = 0;
-  f.in0_groups = in.C / 8;
+  f.in0_groups = inC / 8;
   f.critic_epi = L.epi;
   f.alpha = L.alpha;
-  f.res = L.res ? reinterpret_cast<const char*>(A + L.res->off) : nullptr;
-  f.res_groups = L.res ? L.res->C / 8 : 0;
-  f.dmask = L.mask ? reinterpret_cast<const char*>(A + L.mask->off) : nullptr;
+  f.res = res;
+  f.res_groups = res ? resC / 8 : 0;
+  f.dmask = mask;
   f.range_flag = ctx->opt_range_guard ? ctx->range_flag_dev : nullptr;
-  if (L.D->cout != out.C || L.D->cin_pad > in.C || (L.mask && L.mask->C != out.C) || (L.res && L.res->C > out.C)) {
-    set_error("critic: internal launch geometry mismatch (%d -> %d channels over %d -> %d)", L.D->cin_pad, L.D->cout, in.C, out.C);
+  if (L.D->cout != outC || L.D->cin_pad > inC || (mask && maskC != outC) || (res && resC > outC)) {
+    set_error("critic: internal launch geometry mismatch (%d -> %d channels over %d -> %d)", L.D->cin_pad, L.D->cout, inC, outC);
     return PNPX_ERR_SHAPE;
   }
-  return launch_conv_hs(Lh, reinterpret_cast<const char*>(A + in.off), L.D->cin_pad / 8, nullptr, 0,
-                        reinterpret_cast<char*>(A + out.off), B, h, w, f, s);
+  return launch_conv_hs(Lh, in, L.D->cin_pad / 8, nullptr, 0, out, B, h, w, f, s);
+}
+int run_conv(pnpx_ctx* ctx, float* A, const Launch& L, const CAct& in, const CAct& out, int B, int h, int w, hipStream_t s) {
+  return run_conv_ptr(ctx, L, reinterpret_cast<const char*>(A + in.off), in.C, reinterpret_cast<char*>(A + out.off), out.C,
+                      L.res ? reinterpret_cast<const char*>(A + L.res->off) : nullptr, L.res ? L.res->C : 0,
+                      L.mask ? reinterpret_cast<const char*>(A + L.mask->off) : nullptr, L.mask ? L.mask->C : 0, B, h, w, s);
 }
 
 // forward over B observations; every activation stays in the arena
@@ -687,6 +695,9 @@ void critic_free(pnpx_ctx* ctx) {
   if (N.arena.p) (void)hipFree(N.arena.p);
   if (N.master.p) (void)hipFree(N.master.p);
   if (N.pack_ws.p) (void)hipFree(N.pack_ws.p);
+  if (N.grad_m.p) (void)hipFree(N.grad_m.p);
+  if (N.grad_wm.p) (void)hipFree(N.grad_wm.p);
+  if (N.grad_slab.p) (void)hipFree(N.grad_slab.p);
   if (N.readback) (void)hipHostFree(N.readback);
   N = CriticNet();
 }
@@ -991,12 +1002,33 @@ int critic_forward(pnpx_ctx* ctx, const float* ob, float* value, int B, int H, i
   return PNPX_OK;
 }
 
-int critic_backward(pnpx_ctx* ctx, const float* ob, const float* grad_value, float* grad_ob, int B, int H, int W, hipStream_t s) {
+namespace {
+
+// Parameter-gradient work interleaved with the adjoint chain (critic_param_grad); the input gradient runs the chain without one.
+// gM[st] is written twice per stage, so each gradient is launched while both of its operands are still in place.
+struct GradJob {
+  const CriticLayout* L;
+  const float* gv;     // grad_value [B]
+  float* out;          // grad_params
+  HsRec *m, *wm;       // clip indicator of one activation; the forward convolution of it
+  float* slab;         // K-split pieces of one layer
+  double* dots;        // [NL][B]: per threshold and image, <g, W m> + <res, m> as stored (times s * 256)
+};
+
+inline float grad_scale(const CriticNet& N, int hl, int wl) {
+  // a power of two that brings the head's largest entry max|fc_w| / (h w) into [1, 2)
+  float gs = 1.f;
+  if (N.fc_wmax > 0.f) {
+    int e = 0;
+    std::frexp(N.fc_wmax / (float)(hl * wl), &e);
+    gs = std::ldexp(1.0f, 1 - e);
+  }
+  return gs;
+}
+
+// head gradient and the four stages of the adjoint chain, down to g_stem (the forward has just run: every activation is in the arena)
+int run_chain(pnpx_ctx* ctx, const CriticPlan& P, float gs, int B, int H, int W, hipStream_t s, const GradJob* J) {
   CriticNet& N = ctx->critic;
-  PNPX_TRY(check_call(N, "critic backward", B, H, W));
-  PNPX_TRY(reserve(N, B, H, W));
-  const CriticPlan P = make_plan(N.capB, N.cin_pad, H, W);
-  PNPX_TRY(run_forward(ctx, P, ob, B, H, W, s));   // re-computation: every activation is now in the arena
   float* A = static_cast<float*>(N.arena.p);
   auto rec = [&](const CAct& d) { return reinterpret_cast<HsRec*>(A + d.off); };
   auto u4 = [&](const CAct& d) { return reinterpret_cast<uint4*>(A + d.off); };
@@ -1012,14 +1044,49 @@ int critic_backward(pnpx_ctx* ctx, const float* ob, const float* grad_value, flo
     L.mask = mask;
     return run_conv(ctx, A, L, in, out, B, h, w, s);
   };
-  // gradient scale: a power of two that brings the head's largest entry max|fc_w| / (h w) into [1, 2)
+  // gradient of convolution li: G = gradient with respect to its output, X = the tensor its forward launch read
+  auto wgrad = [&](int li, const CAct& G, const CAct& X, int h, int w) -> int {
+    if (!J) return PNPX_OK;
+    const PackDesc& D = J->L->T.pack[2 * li];
+    WgradJob Wj;
+    Wj.G = rec(G);
+    Wj.X = rec(X);
+    Wj.gv = J->gv;
+    Wj.Gg = G.C / 8;
+    Wj.Xg = X.C / 8;
+    Wj.cout = D.rows;
+    Wj.K = D.K;
+    Wj.nt = D.nt;
+    for (int t = 0; t < D.nt; ++t) Wj.tap[t] = D.tap[t];
+    Wj.B = B;
+    Wj.h = h;
+    Wj.w = w;
+    PNPX_TRY(launch_critic_wgrad(Wj, J->slab, s));
+    WnGradJob F;
+    F.D = D;
+    F.src_b = J->L->T.copy[li].src;
+    F.src_g = J->L->T.fold[li].src_g;
+    F.fan = J->L->T.fold[li].fan;
+    F.pieces = critic_wgrad_pieces(D.rows, D.K, B, h, w);
+    F.inv_w = 1.0f / (gs * HS_ASCALE * HS_ASCALE);
+    F.inv_b = 1.0f / (gs * HS_ASCALE);
+    return launch_critic_wn_grad(F, J->slab, static_cast<const float*>(N.master.p), J->out, s);
+  };
+  // threshold ali of the saved activation `act`, read by forward convolution cli whose output gradient is g; res: what the chain
+  // adds to W^T g before the mask
+  auto athr = [&](int ali, int cli, const CAct& act, const CAct& g, const CAct* res, int h, int w) -> int {
+    if (!J) return PNPX_OK;
+    PNPX_TRY(launch_critic_clip_mask(rec(act), J->m, hs_roundtrip16(N.alpha[ali]), B, act.C / 8, h, w, s));
+    Launch L;   // the plain linear instance, no bias
+    L.D = &N.fwd[cli];
+    L.bias = N.zero;
+    L.taps = fwd_taps(cli);
+    PNPX_TRY(run_conv_ptr(ctx, L, reinterpret_cast<const char*>(J->m), act.C, reinterpret_cast<char*>(J->wm), g.C, nullptr, 0, nullptr, 0, B,
+                          h, w, s));
+    return launch_critic_alpha_dot(rec(g), J->wm, g.C / 8, res ? rec(*res) : nullptr, res ? res->C / 8 : 0, J->m, act.C / 8, B, h, w,
+                                   J->dots + (size_t)ali * B, s);
+  };
   const int hl = H / 32, wl = W / 32;
-  float gs = 1.f;
-  if (N.fc_wmax > 0.f) {
-    int e = 0;
-    std::frexp(N.fc_wmax / (float)(hl * wl), &e);
-    gs = std::ldexp(1.0f, 1 - e);
-  }
   {
     const size_t n = (size_t)B * 64 * hl * wl;
     hipLaunchKernelGGL(critic_head_grad_kernel, g1(n), dim3(256), 0, s, rec(P.o1[3]), rec(P.gA[3]), N.fc_w, hs_roundtrip16(N.alpha[20]),
@@ -1029,9 +1096,17 @@ int critic_backward(pnpx_ctx* ctx, const float* ob, const float* grad_value, flo
   for (int st = 3; st >= 0; --st) {
     const int h = H >> (st + 2), w = W >> (st + 2), l0 = 1 + 5 * st;
     // block 1: o1 = TReLU(conv2(t2) + o0), t2 = TReLU(conv1(o0))
+    PNPX_TRY(wgrad(l0 + 4, P.gA[st], P.t2[st], h, w));
+    PNPX_TRY(athr(l0 + 3, l0 + 4, P.t2[st], P.gA[st], nullptr, h, w));
     PNPX_TRY(grad(l0 + 4, P.gA[st], P.gM[st], nullptr, &P.t2[st], l0 + 3, h, w));
+    PNPX_TRY(wgrad(l0 + 3, P.gM[st], P.o0[st], h, w));
+    PNPX_TRY(athr(l0 + 2, l0 + 3, P.o0[st], P.gM[st], &P.gA[st], h, w));
     PNPX_TRY(grad(l0 + 3, P.gM[st], P.gB[st], &P.gA[st], &P.o0[st], l0 + 2, h, w));
     // block 0: o0 = TReLU(conv2(t1) + shortcut(x)), t1 = TReLU(conv1(x)), x = space-to-depth input
+    const CAct& x = st == 0 ? P.stem_s : P.o1s[st - 1];
+    PNPX_TRY(wgrad(l0 + 2, P.gB[st], P.t1[st], h, w));
+    PNPX_TRY(wgrad(l0 + 1, P.gB[st], x, h, w));
+    PNPX_TRY(athr(l0 + 0, l0 + 2, P.t1[st], P.gB[st], nullptr, h, w));
     PNPX_TRY(grad(l0 + 2, P.gB[st], P.gM[st], nullptr, &P.t1[st], l0 + 0, h, w));
     {   // shortcut adjoint: 1x1, linear (the existing sparse-tap instance), to the phase-(0,0) channel groups
       Launch L;
@@ -1040,7 +1115,8 @@ int critic_backward(pnpx_ctx* ctx, const float* ob, const float* grad_value, flo
       L.taps = 0x010;
       PNPX_TRY(run_conv(ctx, A, L, P.gB[st], P.gR[st], B, h, w, s));
     }
-    const CAct& x = st == 0 ? P.stem_s : P.o1s[st - 1];
+    PNPX_TRY(wgrad(l0 + 0, P.gM[st], x, h, w));
+    PNPX_TRY(athr(st == 0 ? 0 : l0 - 1, l0 + 0, x, P.gM[st], &P.gR[st], h, w));
     PNPX_TRY(grad(l0 + 0, P.gM[st], P.gS[st], &P.gR[st], &x, st == 0 ? 0 : l0 - 1, h, w));
     const CAct& below = st == 0 ? P.g_stem : P.gA[st - 1];
     const int G = below.C / 8;
@@ -1048,12 +1124,120 @@ int critic_backward(pnpx_ctx* ctx, const float* ob, const float* grad_value, flo
     hipLaunchKernelGGL(hs_d2s_kernel, g1(n), dim3(256), 0, s, u4(P.gS[st]), u4(below), G, h, w, n);
     PNPX_LAUNCH_CHECK();
   }
-  PNPX_TRY(grad(0, P.g_stem, P.g_ob, nullptr, nullptr, 0, H / 2, W / 2));   // stem adjoint: linear
+  PNPX_TRY(wgrad(0, P.g_stem, P.ob_s, H / 2, W / 2));
+  return PNPX_OK;
+}
+
+}  // namespace
+
+int critic_backward(pnpx_ctx* ctx, const float* ob, const float* grad_value, float* grad_ob, int B, int H, int W, hipStream_t s) {
+  CriticNet& N = ctx->critic;
+  PNPX_TRY(check_call(N, "critic backward", B, H, W));
+  PNPX_TRY(reserve(N, B, H, W));
+  const CriticPlan P = make_plan(N.capB, N.cin_pad, H, W);
+  PNPX_TRY(run_forward(ctx, P, ob, B, H, W, s));   // re-computation: every activation is now in the arena
+  float* A = static_cast<float*>(N.arena.p);
+  auto rec = [&](const CAct& d) { return reinterpret_cast<HsRec*>(A + d.off); };
+  const float gs = grad_scale(N, H / 32, W / 32);
+  PNPX_TRY(run_chain(ctx, P, gs, B, H, W, s, nullptr));
+  {   // stem adjoint: linear
+    Launch L;
+    L.D = &N.bwd[0];
+    L.bias = N.zero;
+    L.taps = bwd_taps(0);
+    L.epi = 2;
+    PNPX_TRY(run_conv(ctx, A, L, P.g_stem, P.g_ob, B, H / 2, W / 2, s));
+  }
   const size_t n = (size_t)B * N.num_inputs * H * W;
   hipLaunchKernelGGL(critic_ob_grad_kernel, g1(n), dim3(256), 0, s, rec(P.g_ob), grad_value, grad_ob, N.num_inputs, N.cin_pad, H, W,
                      1.0f / (gs * HS_ASCALE), n);
   PNPX_LAUNCH_CHECK();
   return PNPX_OK;
+}
+
+namespace {
+
+// a buffer of the parameter-gradient workspace: grows to the largest size seen (the only place the call synchronises the device)
+int grow(DeviceBuf& b, size_t bytes, bool zero, const char* what) {
+  if (bytes <= b.bytes) return PNPX_OK;
+  PNPX_HIP(hipDeviceSynchronize());
+  if (b.p) PNPX_HIP(hipFree(b.p));
+  b = DeviceBuf();
+  PNPX_TRY(alloc_dev(b, bytes, what));
+  if (zero) {   // record buffers: what an overhanging tile reads past its tensor has to be finite
+    PNPX_HIP(hipMemset(b.p, 0, bytes));
+    PNPX_HIP(hipDeviceSynchronize());
+  }
+  return PNPX_OK;
+}
+
+}  // namespace
+
+// d(sum_b grad_value[b] * V_b) / d(params), pnpx_critic_load's order (value_loss.backward(), trainer/mddpg/trainer.py:198,207).
+// Forward re-computation, then the adjoint chain of critic_backward with the gradient launches between its steps (run_chain);
+// fc and the head's threshold are closed forms of the last activation.  Every element of grad_params is written.
+int critic_param_grad(pnpx_ctx* ctx, const float* ob, const float* grad_value, float* grad_params, size_t n, int B, int H, int W,
+                      hipStream_t s) {
+  CriticNet& N = ctx->critic;
+  PNPX_TRY(check_call(N, "critic parameter gradient", B, H, W));
+  if (n != critic_num_params(N.num_inputs)) {
+    set_error("pnpx_critic_param_grad: the loaded critic (%d inputs) has %zu parameters, got room for %zu", N.num_inputs,
+              critic_num_params(N.num_inputs), n);
+    return PNPX_ERR_ARG;
+  }
+  CriticLayout L;
+  if (!make_layout(N.num_inputs, L)) {
+    set_error("pnpx_critic_param_grad: internal layout error for %d inputs", N.num_inputs);
+    return PNPX_ERR_SHAPE;
+  }
+  PNPX_TRY(reserve(N, B, H, W));
+  const CriticPlan P = make_plan(N.capB, N.cin_pad, H, W);
+  // workspace: the largest clip indicator (the space-to-depth input of stage 0), the largest W * indicator, the largest layer's slabs
+  size_t m_floats = 0, wm_floats = 0, slab_floats = 0;
+  auto hs_floats = [&](int C, int h, int w) { return (size_t)C * (h + 2) * (w + 2) * B; };
+  auto slab_of = [&](int li, int h, int w) {
+    const PackDesc& D = L.T.pack[2 * li];
+    const size_t f = (size_t)critic_wgrad_pieces(D.rows, D.K, B, h, w) * critic_wgrad_piece_floats(D.rows, D.K, D.nt);
+    if (f > slab_floats) slab_floats = f;
+  };
+  slab_of(0, H / 2, W / 2);
+  int in_planes = 64;
+  for (int st = 0; st < 4; ++st) {
+    const int p = stage_planes(st), h = H >> (st + 2), w = W >> (st + 2);
+    m_floats = std::max(m_floats, std::max(hs_floats(4 * in_planes, h, w), hs_floats(p, h, w)));
+    wm_floats = std::max(wm_floats, hs_floats(p, h, w));
+    for (int k = 0; k < 5; ++k) slab_of(1 + 5 * st + k, h, w);
+    in_planes = p;
+  }
+  const size_t slack = (size_t)1 << 20;   // bytes: overhanging tiles read past their tensor (the arena's slack)
+  PNPX_TRY(grow(N.grad_m, m_floats * sizeof(float) + slack, true, "gradient mask"));
+  PNPX_TRY(grow(N.grad_wm, wm_floats * sizeof(float) + slack, true, "gradient mask convolution"));
+  const size_t slab_bytes = (slab_floats * sizeof(float) + 255) & ~(size_t)255;
+  PNPX_TRY(grow(N.grad_slab, slab_bytes + ((size_t)NL * B + 512) * sizeof(double), false, "gradient slab"));
+
+  PNPX_TRY(run_forward(ctx, P, ob, B, H, W, s));   // re-computation: every activation is now in the arena
+  GradJob J;
+  J.L = &L;
+  J.gv = grad_value;
+  J.out = grad_params;
+  J.m = static_cast<HsRec*>(N.grad_m.p);
+  J.wm = static_cast<HsRec*>(N.grad_wm.p);
+  J.slab = static_cast<float*>(N.grad_slab.p);
+  J.dots = reinterpret_cast<double*>(static_cast<char*>(N.grad_slab.p) + slab_bytes);
+  double* a20 = J.dots + (size_t)NL * B;
+  const int hl = H / 32, wl = W / 32;
+  const float gs = grad_scale(N, hl, wl);
+  PNPX_TRY(run_chain(ctx, P, gs, B, H, W, s, &J));
+  const float* A = static_cast<const float*>(N.arena.p);
+  PNPX_TRY(launch_critic_fc_grad(reinterpret_cast<const HsRec*>(A + P.o1[3].off), grad_value, N.fc_w, hs_roundtrip16(N.alpha[20]), B, hl, wl,
+                                 grad_params + L.T.src_fcw, a20, s));
+  AlphaFinishJob F;
+  for (int i = 0; i < NL; ++i) F.alpha_src[i] = i == NL - 1 ? -1 : L.T.fold[i].alpha_src;   // the head's threshold: closed form
+  F.head_src = L.T.fold[NL - 1].alpha_src;
+  F.fcb_src = (int)L.T.copy[NCOPY - 1].src;
+  F.B = B;
+  F.inv = 1.0f / (gs * HS_ASCALE * HS_ASCALE);
+  return launch_critic_alpha_finish(F, J.dots, a20, grad_value, grad_params, s);
 }
 
 }  // namespace pnpx

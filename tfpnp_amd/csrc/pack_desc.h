@@ -45,6 +45,23 @@ __device__ inline long long eff_src_offset(const PackDesc& D, int co, int k, int
   return (long long)co * D.cin + k;
 }
 
+// The inverse: raw element i of an output channel's fan ([cin][kh][kw], i < cin * kh * kw) sits at exactly one effective position
+// (k, tap) of the launch -- un-packing a gradient of the effective weights is a gather per raw element (critic_grad.hip).
+__device__ inline void eff_pos_of_src(const PackDesc& D, int i, int& k, int& tap) {
+  if (D.kind == 0) {
+    k = i / 9;
+    tap = i - 9 * k;
+  } else if (D.kind == 1) {
+    const int ci = i / 9, t = i - 9 * ci, dy = t / 3, dx = t - 3 * dy;
+    const int py = (dy == 1) ? 0 : 1, ty = (dy == 0) ? 0 : 1, px = (dx == 1) ? 0 : 1, tx = (dx == 0) ? 0 : 1;   // put_conv_s2
+    k = (py * 2 + px) * D.Cp + ci;
+    tap = ty * 3 + tx;
+  } else {
+    k = i;
+    tap = 4;
+  }
+}
+
 // Item i of packing D = (cout tile, K chunk, tap, K half, row): the hi and the lo fragment of eight consecutive K elements of
 // s * eff(row, k, tap), as pack_conv_weights_hs_taps lays them out.  The caller has checked i < D.items.
 template <class EffAt>

@@ -440,6 +440,24 @@ def critic_backward(ctx, ob, grad_value):
     return grad_ob
 
 
+def critic_param_grad(ctx, ob, grad_value):
+    """Flat fp32 vector [n_params] on ob's device, load_critic_device's order: d sum(grad_value * V) / d params of the loaded
+    critic -- value_loss.backward() of trainer/mddpg/trainer.py:198,207 with grad_value = d value_loss / d V.  Overwrites,
+    does not accumulate; the forward is re-computed natively."""
+    ob = _critic_ob(ctx, ob, "critic_param_grad")
+    grad_value = _f32(grad_value, "grad_value").reshape(-1)
+    B, _, H, W = ob.shape
+    if grad_value.numel() != B:
+        raise PnpxError(f"critic_param_grad: grad_value must have {B} entries, got {grad_value.numel()}")
+    n = int(_lib.lib().pnpx_critic_num_params(ctx._critic))
+    if B == 0:
+        return torch.zeros((n,), device=ob.device, dtype=torch.float32)
+    out = torch.empty((n,), device=ob.device, dtype=torch.float32)
+    with torch.cuda.device(ob.device):
+        check(_lib.lib().pnpx_critic_param_grad(ctx.handle, _p(ob), _p(grad_value), _p(out), n, B, H, W, _stream(ob)))
+    return out
+
+
 def unet_profile(ctx, x, sigma):
     """[(name, ms, flops)] per kernel launch of one denoiser forward (HIP events on the current stream)."""
     x = _f32(x, "x")

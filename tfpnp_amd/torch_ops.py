@@ -493,6 +493,18 @@ def _(ob, grad_value, ctx):
     return torch.empty_like(ob, memory_format=torch.contiguous_format)
 
 
+@_lib_def("pnpx::critic_param_grad", mutates_args=(), device_types="cuda")
+def critic_param_grad(ob: Tensor, grad_value: Tensor, ctx: int) -> Tensor:
+    """d sum(grad_value * critic_value(ob)) / d params as one flat vector (value_loss.backward(), trainer.py:198,207)."""
+    return ops.critic_param_grad(ops.context_by_id(ctx), ob, grad_value)
+
+
+@critic_param_grad.register_fake
+def _(ob, grad_value, ctx):
+    n = int(ops._lib.lib().pnpx_critic_num_params(ops.context_by_id(ctx)._critic))
+    return torch.empty((n,), dtype=torch.float32, device=ob.device)
+
+
 def _critic_setup(ctx, inputs, output):
     ob, cid = inputs
     ctx.save_for_backward(ob)
@@ -571,4 +583,4 @@ ALL_OPS = ("unet_denoise", "unet_denoise_preclamp", "unet_denoise_backward", "un
            "cdp_backward", "spi_inverse", "psnr", "radon_forward", "radon_backprojection", "csmri_admm", "csmri_admm_train",
            "csmri_admm_backward", "csmri_hqs", "csmri_amp",
            "csmri_pg", "csmri_apg", "csmri_redadmm", "pr_iadmm", "spi_admm", "ct_iadmm", "ct_pg", "pr_pg",
-           "critic_value", "critic_backward", "policy_ob_pack_diff", "policy_ob_unpack")
+           "critic_value", "critic_backward", "critic_param_grad", "policy_ob_pack_diff", "policy_ob_unpack")

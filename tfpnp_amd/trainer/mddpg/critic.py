@@ -2,16 +2,20 @@
 constructor arguments, `forward(x) -> [B, 1]`).
 
 ResNet_wobn(num_inputs, 18, 1): weight-normalised ResNet-18 without BatchNorm, TReLU activations, scalar head.  The
-forward (pnpx_critic_forward) and its gradient with respect to the INPUT (pnpx_critic_backward) run natively, so the value
-term of the reference's actor loss (trainer/mddpg/trainer.py:180-192: V_next = critic(get_eval_ob(ob2)), differentiated into
-the actions through ob2.variables) can be evaluated on the native kernels: `forward` is differentiable with respect to x.
+forward (pnpx_critic_forward) and its gradients with respect to the INPUT (pnpx_critic_backward) and to the PARAMETERS
+(pnpx_critic_param_grad) run natively, so the value term of the reference's actor loss (trainer/mddpg/trainer.py:180-192:
+V_next = critic(get_eval_ob(ob2)), differentiated into the actions through ob2.variables) can be evaluated on the native
+kernels: `forward` is differentiable with respect to x.
 
 The weights are LIVE: the native context keeps the flat parameter vector on the device, and `load_flat_`,
 utils.misc.soft_update / hard_update replace or move it there and re-pack on the device (weight-norm fold included), so a
 target critic can follow a critic that a torch optimiser trains (trainer.py:182, :212) and the value term can be taken on
 the freshly stepped critic (:190) without a host reload.  `load_state_dict` is the checkpoint path (folds on the host).
-No weight gradient exists (the reference throws the critic's weight gradients from the actor loss away, trainer.py:206).
-Out of scope: critic weight gradients, value_loss, optimiser steps, the MDDPG trainer loop, a trainable actor,
+`param_grad(x, grad_value)` is value_loss.backward() (trainer.py:198,207): the gradient of sum(grad_value * V) with respect to
+the parameters as one flat vector in synth.critic_param_specs order (pnpx_critic_param_grad: weight gradients on the fp32
+MFMA, thresholds, fc, weight-norm).  A flat nn.Parameter takes it as .grad, a torch optimiser steps it and `load_flat_`
+takes the result (examples/train_critic.py); `forward` stays differentiable with respect to x only.
+Out of scope: value_loss itself, optimiser steps, gradient clipping, the MDDPG trainer loop, a trainable actor,
 depths other than 18.  (The native actor has the same live weights: policy/network.py; the replay memory is utils/rpm.py.)
 """
 import torch
@@ -144,3 +148,12 @@ class ResNet_wobn(nn.Module):
         if isinstance(x, torch.Tensor) and not x.is_cuda:
             raise ops.PnpxError(f"ResNet_wobn: tensor on {x.device}; tfpnp_amd runs on MI355X only, there is no CPU path")
         return T.call("critic_value", x, self.context(x.device).cid)
+
+    def param_grad(self, x, grad_value):
+        """d sum(grad_value * V(x)) / d parameters -> flat fp32 [n_params] on x's device (synth.critic_param_specs order).
+        x [B, num_inputs, H, W] (H, W multiples of 32), grad_value [B] or [B, 1].  Overwrites nothing of the module: assign
+        the result to the .grad of a flat parameter and step it with a torch optimiser, then load_flat_."""
+        for t in (x, grad_value):
+            if isinstance(t, torch.Tensor) and not t.is_cuda:
+                raise ops.PnpxError(f"ResNet_wobn: tensor on {t.device}; tfpnp_amd runs on MI355X only, there is no CPU path")
+        return T.call("critic_param_grad", x.detach(), grad_value.detach().reshape(-1), self.context(x.device).cid)
