@@ -5,13 +5,17 @@
     critic_optim.step()                              :209
     soft_update(critic_target, critic, tau)          :212
 
-The critic and its target are native ResNet_wobn modules.  The trainable state is ONE flat nn.Parameter on the device
-(synth.critic_param_specs order): `param_grad` writes value_loss.backward() into its .grad -- grad_value = d value_loss / d V
-= 2 (V - Q) / B for the mean squared error -- torch clips and steps it, `load_flat_` hands the stepped vector to the native
-critic (weight-norm fold and packing on the device) and `soft_update_` moves the target.  No torch copy of the network, no
-F.conv2d.
+The critic and its target are native ResNet_wobn modules; no torch copy of the network, no F.conv2d.  Two paths:
 
-usage (GPU box):  python examples/train_critic.py [steps] [B] [H]
+native (default)   trainer/mddpg/critic_step.py::critic_update: one critic forward gives value, loss and gradient
+                   (value_loss_grad), clip + Adam + re-pack run inside the native context on its own parameter vector
+                   (adam_step_), soft_update moves the target.  No torch optimiser, no torch copy of the parameters.
+composed           the trainable state is ONE flat nn.Parameter on the device (synth.critic_param_specs order): `param_grad`
+                   writes value_loss.backward() into its .grad -- grad_value = d value_loss / d V = 2 (V - Q) / B -- torch clips
+                   and steps it, `load_flat_` hands the stepped vector to the native critic and `soft_update_` moves the target.
+                   Kept as the comparison of tools/time_critic_step.py and of the tests.
+
+usage (GPU box):  python examples/train_critic.py [steps] [B] [H] [native: 1 / 0]
 """
 import os
 import sys
@@ -23,35 +27,57 @@ import torch.nn as nn
 
 from tfpnp_amd import synth
 from tfpnp_amd.trainer.mddpg.critic import ResNet_wobn
+from tfpnp_amd.trainer.mddpg.critic_step import critic_update
 
 
-def run(steps=5, B=2, H=64, num_inputs=9, tau=0.001, lr=1e-4, discount=0.99, seed=0, log=print):
-    """-> (value_loss per step, the native critic, the native target)"""
+def setup(B=2, H=64, num_inputs=9, seed=0):
+    """-> (flat parameter vector, critic, target, ob, ob2, reward) on cuda:0"""
     dev = torch.device("cuda:0")
     torch.manual_seed(seed)
     params = synth.make_critic_params(num_inputs, seed)
-    flat = nn.Parameter(torch.from_numpy(np.concatenate([params[k].reshape(-1) for k, _ in synth.critic_param_specs(num_inputs)])).to(dev))
-    critic = ResNet_wobn(num_inputs, 18, 1).load_flat_(flat.detach())
-    target = ResNet_wobn(num_inputs, 18, 1).load_flat_(flat.detach())             # hard_update, trainer.py:54-55
-    opt = torch.optim.Adam([flat], lr=lr)
+    flat = torch.from_numpy(np.concatenate([params[k].reshape(-1) for k, _ in synth.critic_param_specs(num_inputs)])).to(dev)
+    critic = ResNet_wobn(num_inputs, 18, 1).load_flat_(flat)
+    target = ResNet_wobn(num_inputs, 18, 1).load_flat_(flat)                      # hard_update, trainer.py:54-55
     ob, ob2 = torch.rand(B, num_inputs, H, H, device=dev), torch.rand(B, num_inputs, H, H, device=dev)
     reward = torch.randn(B, 1, device=dev)
+    return flat, critic, target, ob, ob2, reward
+
+
+def composed_step(critic, target, flat, opt, ob, ob2, reward, discount, tau, max_norm=50):
+    """one update with torch's clip and optimiser on the flat nn.Parameter `flat` -> (value_loss, gradient norm), device tensors"""
+    B = ob.shape[0]
+    with torch.no_grad():
+        Q = reward + discount * target(ob2)                                       # trainer.py:182-194
+        V = critic(ob)
+        loss = ((V - Q) ** 2).mean()                                              # :195-198
+    flat.grad = critic.param_grad(ob, 2.0 * (V - Q) / B)                          # value_loss.backward(), :207
+    norm = torch.nn.utils.clip_grad_norm_([flat], max_norm)                       # :208
+    opt.step()                                                                    # :209
+    critic.load_flat_(flat.detach())
+    target.soft_update_(flat.detach(), tau)                                       # :212
+    return loss, norm
+
+
+def run(steps=5, B=2, H=64, native=True, num_inputs=9, tau=0.001, lr=1e-4, discount=0.99, seed=0, log=print):
+    """-> (value_loss per step, the native critic, the native target)"""
+    flat, critic, target, ob, ob2, reward = setup(B, H, num_inputs, seed)
     history = []
+    if native:
+        stop = torch.zeros(B, 1, device=ob.device)
+        for it in range(steps):
+            out = critic_update(critic, target, ob, ob2, reward, stop, discount, tau, lr)
+            history.append(float(out["value_loss"]))
+            log(f"step {it}: value_loss {history[-1]:.6f}  |grad| {float(out['critic_norm']):.4f}")
+        return history, critic, target
+    flat = nn.Parameter(flat)
+    opt = torch.optim.Adam([flat], lr=lr)
     for it in range(steps):
-        with torch.no_grad():
-            Q = reward + discount * target(ob2)                                   # trainer.py:182-194
-            V = critic(ob)
-            loss = ((V - Q) ** 2).mean()                                          # :195-198
-        flat.grad = critic.param_grad(ob, 2.0 * (V - Q) / B)                      # value_loss.backward(), :207
-        torch.nn.utils.clip_grad_norm_([flat], 50)                                # :208
-        opt.step()                                                                # :209
-        critic.load_flat_(flat.detach())
-        target.soft_update_(flat.detach(), tau)                                   # :212
+        loss, norm = composed_step(critic, target, flat, opt, ob, ob2, reward, discount, tau)
         history.append(float(loss))
-        log(f"step {it}: value_loss {history[-1]:.6f}  |grad| {float(flat.grad.norm()):.4f}")
+        log(f"step {it}: value_loss {history[-1]:.6f}  |grad| {float(norm):.4f}")
     return history, critic, target
 
 
 if __name__ == "__main__":
-    a = [int(v) for v in sys.argv[1:4]]
-    run(*a)
+    a = [int(v) for v in sys.argv[1:5]]
+    run(*a[:3], **({"native": bool(a[3])} if len(a) > 3 else {}))

@@ -220,7 +220,8 @@ int pnpx_policy_params(pnpx_ctx* ctx, float* dst_dev, size_t n_params, void* str
  * stride-2 shortcut, adaptive_avg_pool2d(1), Linear(512, 1).  Convolutions are weight-normalised with bias
  * (weight = weight_g * weight_v / ||weight_v||, norm per output channel; critic.py:7-8); activations are TReLU
  * (relu(x - alpha) + alpha, one scalar alpha each; critic.py:11-19).  Gradients: with respect to the observation
- * (pnpx_critic_backward) and with respect to the parameters (pnpx_critic_param_grad).  The weights are LIVE: the context keeps the raw parameter vector on the device, and
+ * (pnpx_critic_backward) and with respect to the parameters (pnpx_critic_param_grad, pnpx_critic_value_loss_grad); the optimiser step is
+ * pnpx_critic_adam_step.  The weights are LIVE: the context keeps the raw parameter vector on the device, and
  * pnpx_critic_load_device / pnpx_critic_soft_update (below) replace or move it and re-derive the packed weights on the device.
  * pnpx_critic_load folds weight-norm and packs on the host (once per checkpoint).  One critic per context.
  * params_host: the fp32 content of state_dict() in registration order (82 tensors),
@@ -267,10 +268,44 @@ int pnpx_critic_backward(pnpx_ctx* ctx, const float* ob, const float* grad_value
  * not match the loaded critic returns PNPX_ERR_ARG.  The forward is re-computed internally and nothing is kept between calls.
  * Deterministic (two calls return the same bytes: the pixel axis is split into pieces that are added in a fixed order, no
  * atomics) and exactly linear in grad_value.  Its workspace belongs to the context and grows to the largest size seen; a call
- * that does not grow it allocates nothing and does not synchronise the device.  No optimiser: step a flat parameter with the
- * optimiser of your choice and hand it to pnpx_critic_load_device. */
+ * that does not grow it allocates nothing and does not synchronise the device.  The native optimiser is pnpx_critic_adam_step;
+ * any other one steps a flat parameter of its own and hands it to pnpx_critic_load_device. */
 int pnpx_critic_param_grad(pnpx_ctx* ctx, const float* ob, const float* grad_value, float* grad_params, size_t n_params, int B,
                            int H, int W, void* stream);
+/* value_loss = nn.MSELoss()(Q_target, V_cur) and value_loss.backward() (trainer/mddpg/trainer.py:198,207) from ONE forward:
+ * value [B] receives the bytes pnpx_critic_forward returns for ob, loss [1] = (sum_b (value[b] - q_target[b])^2) / B (fp32
+ * squares added in index order), and grad_params what pnpx_critic_param_grad returns for
+ * grad_value[b] = (2.0f * (value[b] - q_target[b])) * (float)(1.0 / B) -- the fp32 steps of torch's `2.0 * (V - Q) / B` on a
+ * device tensor, which divides by a Python number as a product with the rounded reciprocal; that vector lives in the
+ * context's workspace.  q_target [B] (device) is the detached target of trainer.py:181-186: it is not differentiated.
+ * Shape rules, workspace growth, determinism and error codes are those of pnpx_critic_param_grad. */
+int pnpx_critic_value_loss_grad(pnpx_ctx* ctx, const float* ob, const float* q_target, float* value, float* loss, float* grad_params,
+                                size_t n_params, int B, int H, int W, void* stream);
+/* clip_grad_norm_(critic.parameters(), max_norm) followed by Adam.step() (trainer.py:208-209; no weight decay, no amsgrad),
+ * applied in place to the context's live parameter vector, then the device-side refresh pnpx_critic_load_device ends with.
+ * grad_dev: n_params floats on the device in pnpx_critic_load's order (any 4-byte alignment; the result does not depend on it).
+ * Element by element in fp32, torch's single-tensor Adam:
+ *   g = grad * c,  m += (g - m) * (1 - beta1),  v = v * beta2 + (1 - beta2) * g * g,  p -= step_size * m / (sqrt(v) / bc2_sqrt + eps)
+ * with step_size = lr / (1 - beta1^t) and bc2_sqrt = sqrt(1 - beta2^t) computed on the host in double from the context's step
+ * counter t, and c = min(1, max_norm / (||grad||_2 + 1e-6)) over the whole vector (what clip_grad_norm_ computes from the 82
+ * per-tensor norms); max_norm = INFINITY: no clipping.  The norm is summed in double in a fixed order (no atomics: two calls
+ * give the same bytes) and never visits the host between the norm and the update.  grad_norm_dev (may be NULL) receives the norm
+ * before clipping.  The moments exp_avg / exp_avg_sq (2 x n_params floats, zero-filled) and t live in the context: allocated by
+ * the first step (the only one that synchronises the device), kept by every refresh with the same num_inputs
+ * (pnpx_critic_load_device, pnpx_critic_soft_update) as overwriting param.data keeps a torch optimiser's state, dropped by a
+ * load with another num_inputs, by pnpx_critic_load and with the context.
+ * PNPX_ERR_NO_WEIGHTS before a load.  PNPX_ERR_ARG with nothing changed: a wrong n_params, lr negative or not finite, a beta
+ * outside [0, 1), eps <= 0, max_norm <= 0.  A gradient whose norm is not finite also returns PNPX_ERR_ARG: parameters, moments,
+ * packed weights and t are what they were and the critic stays usable.  Stream rules and "not capturable into a graph" are
+ * those of pnpx_critic_load_device (one small read-back, which carries the norm). */
+int pnpx_critic_adam_step(pnpx_ctx* ctx, const float* grad_dev, size_t n_params, float lr, float beta1, float beta2, float eps,
+                          float max_norm, float* grad_norm_dev, void* stream);
+/* Copies exp_avg and exp_avg_sq (n_params floats each, device) out, ordered on `stream`, and writes t to *step_host (may be
+ * NULL).  Before the first step: zeros and 0. */
+int pnpx_critic_optim_state(pnpx_ctx* ctx, float* exp_avg_dst, float* exp_avg_sq_dst, size_t n_params, long long* step_host,
+                            void* stream);
+/* Forgets the moments and t (the state before the first step).  Synchronises the device. */
+int pnpx_critic_optim_reset(pnpx_ctx* ctx);
 
 /* ---- transforms (tfpnp/utils/transforms.py) ------------------------------------------------------ */
 /* fft2 / ifft2 (transforms.py:68-103): centered (ifftshift -> FFT -> fftshift), orthonormal, over the

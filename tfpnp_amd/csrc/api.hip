@@ -259,6 +259,33 @@ int pnpx_critic_param_grad(pnpx_ctx* ctx, const float* ob, const float* grad_val
   return critic_param_grad(ctx, ob, grad_value, grad_params, n_params, B, H, W, static_cast<hipStream_t>(stream));
 }
 
+int pnpx_critic_value_loss_grad(pnpx_ctx* ctx, const float* ob, const float* q_target, float* value, float* loss, float* grad_params,
+                                size_t n_params, int B, int H, int W, void* stream) {
+  LOCK_CTX(ctx);
+  if (!ob || !q_target || !value || !loss || !grad_params) {
+    set_error("pnpx_critic_value_loss_grad: null pointer");
+    return PNPX_ERR_ARG;
+  }
+  return critic_value_loss_grad(ctx, ob, q_target, value, loss, grad_params, n_params, B, H, W, static_cast<hipStream_t>(stream));
+}
+
+int pnpx_critic_adam_step(pnpx_ctx* ctx, const float* grad_dev, size_t n_params, float lr, float beta1, float beta2, float eps,
+                          float max_norm, float* grad_norm_dev, void* stream) {
+  LOCK_CTX(ctx);
+  return critic_adam_step(ctx, grad_dev, n_params, lr, beta1, beta2, eps, max_norm, grad_norm_dev, static_cast<hipStream_t>(stream));
+}
+
+int pnpx_critic_optim_state(pnpx_ctx* ctx, float* exp_avg_dst, float* exp_avg_sq_dst, size_t n_params, long long* step_host,
+                            void* stream) {
+  LOCK_CTX(ctx);
+  return critic_optim_state(ctx, exp_avg_dst, exp_avg_sq_dst, n_params, step_host, static_cast<hipStream_t>(stream));
+}
+
+int pnpx_critic_optim_reset(pnpx_ctx* ctx) {
+  LOCK_CTX(ctx);
+  return critic_optim_reset(ctx);
+}
+
 int pnpx_ctx_reserve(pnpx_ctx* ctx, int B, int H, int W) {
   LOCK_CTX(ctx);
   if (B <= 0 || H < 16 || W < 16) {
@@ -438,7 +465,7 @@ size_t pnpx_ctx_bytes(const pnpx_ctx* ctx) {
              ctx->drunet.weights.bytes + ctx->drunet.arena.bytes + ctx->drunet.arena_grad.bytes + ctx->drunet.f32_weights.bytes +
              ctx->drunet.f32_arena.bytes + ctx->drunet.f32_weights_bwd.bytes + ctx->drunet.f32_arena_grad.bytes +
              ctx->policy.weights.bytes + ctx->policy.arena.bytes + ctx->policy.master.bytes + ctx->policy.pack_ws.bytes + ctx->critic.weights.bytes + ctx->critic.arena.bytes +
-             ctx->critic.master.bytes + ctx->critic.pack_ws.bytes;
+             ctx->critic.master.bytes + ctx->critic.pack_ws.bytes + ctx->critic.optim.bytes;
   for (const auto& sl : ctx->train_ring) n += sl.arena.buf.bytes + sl.pre.bytes;
   return n;
 }

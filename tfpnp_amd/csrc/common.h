@@ -139,6 +139,10 @@ struct CriticNet {
   // parameter gradients (pnpx_critic_param_grad): clip indicator, W * indicator, K-split slabs + reduction blocks; each grows to
   // the largest size seen
   DeviceBuf grad_m, grad_wm, grad_slab;
+  // optimiser state (pnpx_critic_adam_step; allocated zero-filled by the first step): exp_avg, exp_avg_sq (each padded to a
+  // multiple of four floats), then the sum-of-squares partials; kept by a refresh, dropped with the critic
+  DeviceBuf optim;
+  long long optim_step = 0;          // Adam's step counter t
 };
 
 // number of independent launch chains for a B-image denoiser forward (unet.hip; option "chains", 0 = automatic)
@@ -404,7 +408,22 @@ int critic_forward(pnpx_ctx* ctx, const float* ob, float* value, int B, int H, i
 int critic_backward(pnpx_ctx* ctx, const float* ob, const float* grad_value, float* grad_ob, int B, int H, int W, hipStream_t s);
 int critic_param_grad(pnpx_ctx* ctx, const float* ob, const float* grad_value, float* grad_params, size_t n, int B, int H, int W,
                       hipStream_t s);
+// value_loss = mean((V - q_target)^2) and its backward on one forward (critic.hip)
+int critic_value_loss_grad(pnpx_ctx* ctx, const float* ob, const float* q_target, float* value, float* loss, float* grad_params, size_t n,
+                           int B, int H, int W, hipStream_t s);
+// clip_grad_norm_ + Adam on the live vector, then the refresh (critic.hip; kernels: critic_optim.hip)
+int critic_adam_step(pnpx_ctx* ctx, const float* grad_dev, size_t n, float lr, float beta1, float beta2, float eps, float max_norm,
+                     float* grad_norm_dev, hipStream_t s);
+int critic_optim_state(pnpx_ctx* ctx, float* exp_avg_dst, float* exp_avg_sq_dst, size_t n, long long* step_host, hipStream_t s);
+int critic_optim_reset(pnpx_ctx* ctx);
 void critic_free(pnpx_ctx* ctx);
+// critic_optim.hip
+constexpr int CRITIC_OPTIM_PARTIALS = 1024;   // blocks of the sum-of-squares launch = doubles it writes
+int launch_critic_sumsq(const float* grad, size_t n, double* partials, hipStream_t s);
+// slot[0] = norm, slot[1] = min(1, max_norm / (norm + 1e-6)); norm_out (may be null) receives the norm as well
+int launch_critic_norm_finish(const double* partials, float max_norm, float* slot, float* norm_out, hipStream_t s);
+int launch_critic_adam(const float* grad, float* p, float* m, float* v, size_t n, const float* slot, float one_minus_b1, float b2,
+                       float one_minus_b2, float step_size, float bc2_sqrt, float eps, hipStream_t s);
 
 // FFT building blocks (fft.hip)
 int fft2(pnpx_ctx* ctx, const float* in, float* out, int n_img, int H, int W, bool inverse, bool centered,

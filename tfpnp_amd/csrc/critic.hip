@@ -6,7 +6,9 @@
 // allocation, no device-wide synchronisation, the arena is kept.  Thresholds, weight scales and max |fc_w| are launch
 // arguments, so each refresh ends with one small read-back and a synchronisation of the caller's stream: a refresh cannot be
 // captured into a graph and has to be issued on the stream the critic's other calls use.  Parameter gradients: critic_param_grad below,
-// kernels in critic_grad.hip.  Still missing: value_loss, optimiser steps, a trainer.  (The actor's refresh: policy_pack.hip.)
+// kernels in critic_grad.hip; critic_value_loss_grad takes value_loss and its backward from one forward.  The optimiser step
+// (critic_adam_step: clip + Adam on `master`, then the refresh; kernels in critic_optim.hip) keeps its moments in the context.
+// (The actor's refresh: policy_pack.hip.)
 //
 // Replaces ResNet_wobn(num_inputs, 18, 1).forward (tfpnp/trainer/mddpg/critic.py:95-131) and the autograd pass through it
 // with respect to its INPUT, which is how the actor loss uses it (trainer/mddpg/trainer.py:180-192: V_next = critic(eval_ob2)
@@ -147,6 +149,24 @@ __global__ __launch_bounds__(256) void critic_ob_grad_kernel(const HsRec* __rest
   grad_ob[i] = ((float)r.hi[c & 7] + (float)r.lo[c & 7]) * (grad_value[b] * inv);
 }
 
+// nn.MSELoss()(Q_target, V_cur) and d loss / d V (trainer/mddpg/trainer.py:198): gv[b] = 2 (V_b - Q_b) / B in the fp32 steps torch
+// takes for `2.0 * (V - Q) / B` on a device tensor, loss = (sum_b (V_b - Q_b)^2) / B with the fp32 squares added in index order in
+// double.  torch divides a device tensor by a Python number as a product with inv_b = (float)(1.0 / (double)B) (its
+// div_true kernel's scalar branch), which differs from the true quotient in the last bit for some operands unless B is a power of
+// two: to return the composed path's bytes the kernel does the same, with inv_b computed by the host.  One block.
+__global__ __launch_bounds__(256) void critic_mse_kernel(const float* __restrict__ value, const float* __restrict__ q, float* __restrict__ gv,
+                                                         float* __restrict__ loss, int B, float inv_b) {
+#pragma clang fp contract(off)
+  for (int b = threadIdx.x; b < B; b += 256) gv[b] = (2.0f * (value[b] - q[b])) * inv_b;
+  if (threadIdx.x != 0) return;
+  double acc = 0.0;
+  for (int b = 0; b < B; ++b) {
+    const float d = value[b] - q[b];
+    acc += (double)(d * d);
+  }
+  loss[0] = (float)(acc / (double)B);
+}
+
 // ------------------------------------------------------------------------------------------- parameter layout
 struct Reader {
   const float* p;
@@ -268,6 +288,7 @@ struct FoldDesc {     // one weight-normalised convolution of the parameter vect
 };
 // PackDesc (one packing, forward or adjoint) and CopyDesc: pack_desc.h
 constexpr int NCOPY = NL + 2, NREAD = 2 * NL + 1;   // read-back block: NL weight scales, NL thresholds, max |fc_w|
+constexpr int RB_NORM = NREAD;                      // behind it, written by critic_adam_step alone: gradient norm, clip coefficient
 struct PackTable {
   FoldDesc fold[NL];
   PackDesc pack[2 * NL];   // 2 * li: forward, 2 * li + 1: adjoint
@@ -698,6 +719,7 @@ void critic_free(pnpx_ctx* ctx) {
   if (N.grad_m.p) (void)hipFree(N.grad_m.p);
   if (N.grad_wm.p) (void)hipFree(N.grad_wm.p);
   if (N.grad_slab.p) (void)hipFree(N.grad_slab.p);
+  if (N.optim.p) (void)hipFree(N.optim.p);
   if (N.readback) (void)hipHostFree(N.readback);
   N = CriticNet();
 }
@@ -760,7 +782,7 @@ int repack(pnpx_ctx* ctx, const CriticLayout& L, hipStream_t s) {
   PNPX_LAUNCH_CHECK();
   hipLaunchKernelGGL(critic_copy_kernel, dim3(2, NCOPY), dim3(256), 0, s, w.T, P, blob);
   PNPX_LAUNCH_CHECK();
-  PNPX_HIP(hipMemcpyAsync(N.readback, w.rb, NREAD * sizeof(float), hipMemcpyDeviceToHost, s));
+  PNPX_HIP(hipMemcpyAsync(N.readback, w.rb, (NREAD + 1) * sizeof(float), hipMemcpyDeviceToHost, s));   // + the optimiser's norm
   PNPX_HIP(hipStreamSynchronize(s));
   for (int i = 0; i < NL; ++i)
     if (!std::isfinite(N.readback[NL + i])) {
@@ -1176,18 +1198,24 @@ int grow(DeviceBuf& b, size_t bytes, bool zero, const char* what) {
 // d(sum_b grad_value[b] * V_b) / d(params), pnpx_critic_load's order (value_loss.backward(), trainer/mddpg/trainer.py:198,207).
 // Forward re-computation, then the adjoint chain of critic_backward with the gradient launches between its steps (run_chain);
 // fc and the head's threshold are closed forms of the last activation.  Every element of grad_params is written.
-int critic_param_grad(pnpx_ctx* ctx, const float* ob, const float* grad_value, float* grad_params, size_t n, int B, int H, int W,
-                      hipStream_t s) {
+//
+// q_target != NULL (critic_value_loss_grad): grad_value is not an argument but d mean((V - q_target)^2) / d V, taken from the
+// forward this call runs anyway -- the head writes `value` as critic_forward does, critic_mse_kernel turns it into grad_value
+// (context-owned scratch behind the reduction blocks) and `loss`.
+namespace {
+
+int param_grad_run(pnpx_ctx* ctx, const char* entry, const char* who, const float* ob, const float* grad_value, const float* q_target,
+                   float* value, float* loss, float* grad_params, size_t n, int B, int H, int W, hipStream_t s) {
   CriticNet& N = ctx->critic;
-  PNPX_TRY(check_call(N, "critic parameter gradient", B, H, W));
+  PNPX_TRY(check_call(N, who, B, H, W));
   if (n != critic_num_params(N.num_inputs)) {
-    set_error("pnpx_critic_param_grad: the loaded critic (%d inputs) has %zu parameters, got room for %zu", N.num_inputs,
+    set_error("%s: the loaded critic (%d inputs) has %zu parameters, got room for %zu", entry, N.num_inputs,
               critic_num_params(N.num_inputs), n);
     return PNPX_ERR_ARG;
   }
   CriticLayout L;
   if (!make_layout(N.num_inputs, L)) {
-    set_error("pnpx_critic_param_grad: internal layout error for %d inputs", N.num_inputs);
+    set_error("%s: internal layout error for %d inputs", entry, N.num_inputs);
     return PNPX_ERR_SHAPE;
   }
   PNPX_TRY(reserve(N, B, H, W));
@@ -1213,9 +1241,21 @@ int critic_param_grad(pnpx_ctx* ctx, const float* ob, const float* grad_value, f
   PNPX_TRY(grow(N.grad_m, m_floats * sizeof(float) + slack, true, "gradient mask"));
   PNPX_TRY(grow(N.grad_wm, wm_floats * sizeof(float) + slack, true, "gradient mask convolution"));
   const size_t slab_bytes = (slab_floats * sizeof(float) + 255) & ~(size_t)255;
-  PNPX_TRY(grow(N.grad_slab, slab_bytes + ((size_t)NL * B + 512) * sizeof(double), false, "gradient slab"));
+  const size_t red_bytes = ((size_t)NL * B + 512) * sizeof(double);   // the reduction blocks; behind them grad_value of the loss entry
+  PNPX_TRY(grow(N.grad_slab, slab_bytes + red_bytes + (size_t)B * sizeof(float), false, "gradient slab"));
 
   PNPX_TRY(run_forward(ctx, P, ob, B, H, W, s));   // re-computation: every activation is now in the arena
+  const int hl = H / 32, wl = W / 32;
+  const float* A = static_cast<const float*>(N.arena.p);
+  if (q_target) {
+    float* gv = reinterpret_cast<float*>(static_cast<char*>(N.grad_slab.p) + slab_bytes + red_bytes);
+    hipLaunchKernelGGL(critic_pool_fc_kernel, dim3(B), dim3(256), 0, s, reinterpret_cast<const HsRec*>(A + P.o1[3].off), hl, wl, N.fc_w,
+                       N.fc_b, value);
+    PNPX_LAUNCH_CHECK();
+    hipLaunchKernelGGL(critic_mse_kernel, dim3(1), dim3(256), 0, s, value, q_target, gv, loss, B, (float)(1.0 / (double)B));
+    PNPX_LAUNCH_CHECK();
+    grad_value = gv;
+  }
   GradJob J;
   J.L = &L;
   J.gv = grad_value;
@@ -1225,10 +1265,8 @@ int critic_param_grad(pnpx_ctx* ctx, const float* ob, const float* grad_value, f
   J.slab = static_cast<float*>(N.grad_slab.p);
   J.dots = reinterpret_cast<double*>(static_cast<char*>(N.grad_slab.p) + slab_bytes);
   double* a20 = J.dots + (size_t)NL * B;
-  const int hl = H / 32, wl = W / 32;
   const float gs = grad_scale(N, hl, wl);
   PNPX_TRY(run_chain(ctx, P, gs, B, H, W, s, &J));
-  const float* A = static_cast<const float*>(N.arena.p);
   PNPX_TRY(launch_critic_fc_grad(reinterpret_cast<const HsRec*>(A + P.o1[3].off), grad_value, N.fc_w, hs_roundtrip16(N.alpha[20]), B, hl, wl,
                                  grad_params + L.T.src_fcw, a20, s));
   AlphaFinishJob F;
@@ -1238,6 +1276,127 @@ int critic_param_grad(pnpx_ctx* ctx, const float* ob, const float* grad_value, f
   F.B = B;
   F.inv = 1.0f / (gs * HS_ASCALE * HS_ASCALE);
   return launch_critic_alpha_finish(F, J.dots, a20, grad_value, grad_params, s);
+}
+
+}  // namespace
+
+int critic_param_grad(pnpx_ctx* ctx, const float* ob, const float* grad_value, float* grad_params, size_t n, int B, int H, int W,
+                      hipStream_t s) {
+  return param_grad_run(ctx, "pnpx_critic_param_grad", "critic parameter gradient", ob, grad_value, nullptr, nullptr, nullptr, grad_params,
+                        n, B, H, W, s);
+}
+
+int critic_value_loss_grad(pnpx_ctx* ctx, const float* ob, const float* q_target, float* value, float* loss, float* grad_params, size_t n,
+                           int B, int H, int W, hipStream_t s) {
+  return param_grad_run(ctx, "pnpx_critic_value_loss_grad", "critic value loss gradient", ob, nullptr, q_target, value, loss, grad_params, n,
+                        B, H, W, s);
+}
+
+// ------------------------------------------------------------------------------------------- optimiser
+// clip_grad_norm_(max_norm) + Adam.step() (trainer/mddpg/trainer.py:208-209) on `master`, then repack: sum of squares, finish
+// (norm and clip coefficient into the read-back block's spare floats), the fused update (critic_optim.hip), the refresh.  The
+// update reads the coefficient on the device and does nothing when the norm is not finite; the host learns the norm from the
+// refresh's own read-back and only then advances the step counter.
+namespace {
+
+struct OptimState {
+  float *m, *v;
+  double* partials;
+};
+inline size_t optim_stride(size_t n) { return (n + 3) & ~(size_t)3; }   // floats: exp_avg_sq starts 16-byte aligned
+inline size_t optim_bytes(size_t n) { return 2 * optim_stride(n) * sizeof(float) + CRITIC_OPTIM_PARTIALS * sizeof(double); }
+inline OptimState optim_state(const CriticNet& N, size_t n) {
+  OptimState o;
+  o.m = static_cast<float*>(N.optim.p);
+  o.v = o.m + optim_stride(n);
+  o.partials = reinterpret_cast<double*>(o.v + optim_stride(n));
+  return o;
+}
+
+}  // namespace
+
+int critic_adam_step(pnpx_ctx* ctx, const float* grad_dev, size_t n, float lr, float beta1, float beta2, float eps, float max_norm,
+                     float* grad_norm_dev, hipStream_t s) {
+  CriticNet& N = ctx->critic;
+  if (!N.loaded) {
+    set_error("pnpx_critic_adam_step called before a critic was loaded");
+    return PNPX_ERR_NO_WEIGHTS;
+  }
+  if (!grad_dev || n != critic_num_params(N.num_inputs)) {
+    set_error("pnpx_critic_adam_step: expected a gradient of %zu parameters for the loaded critic (%d inputs), got %zu",
+              critic_num_params(N.num_inputs), N.num_inputs, n);
+    return PNPX_ERR_ARG;
+  }
+  if (!(lr >= 0.f) || !std::isfinite(lr) || !(beta1 >= 0.f && beta1 < 1.f) || !(beta2 >= 0.f && beta2 < 1.f) || !(eps > 0.f) ||
+      !std::isfinite(eps) || !(max_norm > 0.f)) {
+    set_error("pnpx_critic_adam_step: need lr >= 0 and finite, betas in [0, 1), eps > 0 and finite, max_norm > 0 (got lr %g, betas %g %g, "
+              "eps %g, max_norm %g)", (double)lr, (double)beta1, (double)beta2, (double)eps, (double)max_norm);
+    return PNPX_ERR_ARG;
+  }
+  CriticLayout L;
+  if (!make_layout(N.num_inputs, L)) {
+    set_error("pnpx_critic_adam_step: internal layout error for %d inputs", N.num_inputs);
+    return PNPX_ERR_SHAPE;
+  }
+  if (!N.optim.p) {   // first step: zero-filled moments (the only place the call allocates or synchronises the device)
+    PNPX_HIP(hipDeviceSynchronize());
+    PNPX_TRY(alloc_dev(N.optim, optim_bytes(n), "optimiser state"));
+    PNPX_HIP(hipMemset(N.optim.p, 0, N.optim.bytes));
+    PNPX_HIP(hipDeviceSynchronize());
+    N.optim_step = 0;
+  }
+  const OptimState o = optim_state(N, n);
+  float* slot = pack_ws(N, L.T.nchan).rb + RB_NORM;
+  const double t = (double)(N.optim_step + 1);
+  const double step_size = (double)lr / (1.0 - std::pow((double)beta1, t));
+  const double bc2_sqrt = std::sqrt(1.0 - std::pow((double)beta2, t));
+  PNPX_TRY(launch_critic_sumsq(grad_dev, n, o.partials, s));
+  PNPX_TRY(launch_critic_norm_finish(o.partials, max_norm, slot, grad_norm_dev, s));
+  PNPX_TRY(launch_critic_adam(grad_dev, static_cast<float*>(N.master.p), o.m, o.v, n, slot, (float)(1.0 - (double)beta1), beta2,
+                              (float)(1.0 - (double)beta2), (float)step_size, (float)bc2_sqrt, eps, s));
+  PNPX_TRY(repack(ctx, L, s));   // (a threshold stepped to a non-finite value: the critic is gone, as after any such refresh)
+  const float norm = N.readback[RB_NORM];
+  if (!std::isfinite(norm)) {
+    set_error("pnpx_critic_adam_step: the gradient norm is not finite (%g); parameters and optimiser state are unchanged", (double)norm);
+    return PNPX_ERR_ARG;
+  }
+  ++N.optim_step;
+  return PNPX_OK;
+}
+
+int critic_optim_state(pnpx_ctx* ctx, float* exp_avg_dst, float* exp_avg_sq_dst, size_t n, long long* step_host, hipStream_t s) {
+  CriticNet& N = ctx->critic;
+  if (!N.loaded) {
+    set_error("pnpx_critic_optim_state called before a critic was loaded");
+    return PNPX_ERR_NO_WEIGHTS;
+  }
+  if (!exp_avg_dst || !exp_avg_sq_dst || n != critic_num_params(N.num_inputs)) {
+    set_error("pnpx_critic_optim_state: the loaded critic (%d inputs) has %zu parameters, got room for %zu", N.num_inputs,
+              critic_num_params(N.num_inputs), n);
+    return PNPX_ERR_ARG;
+  }
+  if (N.optim.p) {
+    const OptimState o = optim_state(N, n);
+    PNPX_HIP(hipMemcpyAsync(exp_avg_dst, o.m, n * sizeof(float), hipMemcpyDeviceToDevice, s));
+    PNPX_HIP(hipMemcpyAsync(exp_avg_sq_dst, o.v, n * sizeof(float), hipMemcpyDeviceToDevice, s));
+  } else {   // before the first step
+    PNPX_HIP(hipMemsetAsync(exp_avg_dst, 0, n * sizeof(float), s));
+    PNPX_HIP(hipMemsetAsync(exp_avg_sq_dst, 0, n * sizeof(float), s));
+  }
+  if (step_host) *step_host = N.optim.p ? N.optim_step : 0;
+  return PNPX_OK;
+}
+
+// back to "before the first step": the next step allocates zero-filled moments and counts as step 1
+int critic_optim_reset(pnpx_ctx* ctx) {
+  CriticNet& N = ctx->critic;
+  if (N.optim.p) {
+    PNPX_HIP(hipDeviceSynchronize());
+    PNPX_HIP(hipFree(N.optim.p));
+  }
+  N.optim = DeviceBuf();
+  N.optim_step = 0;
+  return PNPX_OK;
 }
 
 }  // namespace pnpx

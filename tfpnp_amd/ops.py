@@ -232,6 +232,62 @@ class Context:
             check(_lib.lib().pnpx_critic_params(self.handle, _p(out), n, _stream(out)))
         return out
 
+    def critic_adam_step(self, grad, lr, betas=(0.9, 0.999), eps=1e-8, max_norm=50.0):
+        """clip_grad_norm_(max_norm) + torch.optim.Adam.step() (trainer/mddpg/trainer.py:208-209; no weight decay, no amsgrad)
+        on the live parameter vector, then the device-side re-packing of load_critic_device.  grad: flat fp32 [n_params] on
+        this context's device (critic_param_grad's layout).  The moments and the step counter live in the native context.
+        -> the gradient norm before clipping, a 0-dim tensor on the device.  max_norm = float('inf'): no clipping."""
+        if not isinstance(grad, torch.Tensor):
+            raise PnpxError(f"critic_adam_step: expected a torch.Tensor, got {type(grad).__name__}")
+        try:
+            lr, eps, max_norm = float(lr), float(eps), float(max_norm)
+            b1, b2 = (float(b) for b in betas)
+        except (TypeError, ValueError):
+            raise PnpxError(f"critic_adam_step: lr, betas = (beta1, beta2), eps and max_norm must be numbers, got lr {lr!r}, "
+                            f"betas {betas!r}, eps {eps!r}, max_norm {max_norm!r}") from None
+        if not (0.0 <= lr < float("inf")):
+            raise PnpxError(f"critic_adam_step: lr must be finite and >= 0, got {lr}")
+        if not (0.0 <= b1 < 1.0 and 0.0 <= b2 < 1.0):
+            raise PnpxError(f"critic_adam_step: betas must lie in [0, 1), got {(b1, b2)}")
+        if not (0.0 < eps < float("inf")):
+            raise PnpxError(f"critic_adam_step: eps must be finite and > 0, got {eps}")
+        if not max_norm > 0.0:
+            raise PnpxError(f"critic_adam_step: max_norm must be > 0 (float('inf'): no clipping), got {max_norm}")
+        if self._critic is None:
+            raise PnpxError("critic_adam_step: no critic loaded")
+        want = int(_lib.lib().pnpx_critic_num_params(self._critic))
+        if grad.numel() != want:
+            raise PnpxError(f"critic_adam_step: a critic with {self._critic} inputs has {want} parameters, got a gradient of {grad.numel()}")
+        grad = self._critic_vector(grad, "critic_adam_step", None)
+        norm = torch.empty((), device=self.device, dtype=torch.float32)
+        with torch.cuda.device(self.device):
+            st = _lib.lib().pnpx_critic_adam_step(self.handle, _p(grad), grad.numel(), lr, b1, b2, eps, max_norm, _p(norm), _stream(grad))
+            if st == 1:                # PNPX_ERR_ARG: a non-finite gradient norm leaves the critic as it was; a threshold stepped to a
+                err = _lib.lib().pnpx_last_error()      # non-finite value unloads it, as after any refresh
+                if _lib.lib().pnpx_critic_params(self.handle, None, 0, None) == 3:     # PNPX_ERR_NO_WEIGHTS
+                    self._critic = None
+                raise PnpxError(f"pnpx call failed (status 1): {err.decode('utf-8', 'replace')}")
+        check(st)
+        return norm
+
+    def critic_optim_state(self):
+        """(exp_avg, exp_avg_sq, step): copies of Adam's moments (fp32 [n_params] on this context's device) and its step counter;
+        zeros and 0 before the first critic_adam_step."""
+        if self._critic is None:
+            raise PnpxError("critic_optim_state: no critic loaded")
+        n = int(_lib.lib().pnpx_critic_num_params(self._critic))
+        m = torch.empty((n,), device=self.device, dtype=torch.float32)
+        v = torch.empty((n,), device=self.device, dtype=torch.float32)
+        step = C.c_longlong(0)
+        with torch.cuda.device(self.device):
+            check(_lib.lib().pnpx_critic_optim_state(self.handle, _p(m), _p(v), n, C.byref(step), _stream(m)))
+        return m, v, int(step.value)
+
+    def critic_optim_reset(self):
+        """Forget Adam's moments and step counter (the state before the first critic_adam_step)."""
+        with torch.cuda.device(self.device):
+            check(_lib.lib().pnpx_critic_optim_reset(self.handle))
+
     def set_option(self, key, value):
         """e.g. set_option('conv_mode', 1) selects the fast half-split f16 MFMA convolutions (default 0 = fp32 arithmetic)."""
         check(_lib.lib().pnpx_ctx_set_option(self.handle, key.encode(), int(value)))
@@ -456,6 +512,29 @@ def critic_param_grad(ctx, ob, grad_value):
     with torch.cuda.device(ob.device):
         check(_lib.lib().pnpx_critic_param_grad(ctx.handle, _p(ob), _p(grad_value), _p(out), n, B, H, W, _stream(ob)))
     return out
+
+
+def critic_value_loss_grad(ctx, ob, q_target):
+    """(V [B,1], value_loss [], grad [n_params]) from one forward of the loaded critic: value_loss = nn.MSELoss()(q_target, V) and
+    value_loss.backward() (trainer/mddpg/trainer.py:198,207).  V has critic_forward's bytes, grad those of
+    critic_param_grad(ctx, ob, 2.0 * (V - q_target) / B); q_target [B] or [B,1] is the detached target."""
+    if not isinstance(ob, torch.Tensor) or not isinstance(q_target, torch.Tensor):
+        raise PnpxError("critic_value_loss_grad: ob and q_target must be torch.Tensors")
+    if ob.dim() == 4 and q_target.numel() != ob.shape[0]:
+        raise PnpxError(f"critic_value_loss_grad: q_target must have {ob.shape[0]} entries, got {q_target.numel()}")
+    ob = _critic_ob(ctx, ob, "critic_value_loss_grad")
+    q_target = _f32(q_target, "q_target").reshape(-1)
+    B, _, H, W = ob.shape
+    if B == 0:
+        raise PnpxError("critic_value_loss_grad: the mean over an empty batch is undefined")
+    n = int(_lib.lib().pnpx_critic_num_params(ctx._critic))
+    value = torch.empty((B, 1), device=ob.device, dtype=torch.float32)
+    loss = torch.empty((), device=ob.device, dtype=torch.float32)
+    grad = torch.empty((n,), device=ob.device, dtype=torch.float32)
+    with torch.cuda.device(ob.device):
+        check(_lib.lib().pnpx_critic_value_loss_grad(ctx.handle, _p(ob), _p(q_target), _p(value), _p(loss), _p(grad), n, B, H, W,
+                                                     _stream(ob)))
+    return value, loss, grad
 
 
 def unet_profile(ctx, x, sigma):

@@ -505,6 +505,20 @@ def _(ob, grad_value, ctx):
     return torch.empty((n,), dtype=torch.float32, device=ob.device)
 
 
+@_lib_def("pnpx::critic_value_loss_grad", mutates_args=(), device_types="cuda")
+def critic_value_loss_grad(ob: Tensor, q_target: Tensor, ctx: int) -> Tuple[Tensor, Tensor, Tensor]:
+    """(V [B,1], value_loss [], d value_loss / d params [n]) from one forward: nn.MSELoss()(q_target, V) and its backward()
+    (trainer.py:198,207); q_target is not differentiated."""
+    return ops.critic_value_loss_grad(ops.context_by_id(ctx), ob, q_target)
+
+
+@critic_value_loss_grad.register_fake
+def _(ob, q_target, ctx):
+    n = int(ops._lib.lib().pnpx_critic_num_params(ops.context_by_id(ctx)._critic))
+    return (torch.empty((ob.shape[0], 1), dtype=torch.float32, device=ob.device), torch.empty((), dtype=torch.float32, device=ob.device),
+            torch.empty((n,), dtype=torch.float32, device=ob.device))
+
+
 def _critic_setup(ctx, inputs, output):
     ob, cid = inputs
     ctx.save_for_backward(ob)
@@ -583,4 +597,4 @@ ALL_OPS = ("unet_denoise", "unet_denoise_preclamp", "unet_denoise_backward", "un
            "cdp_backward", "spi_inverse", "psnr", "radon_forward", "radon_backprojection", "csmri_admm", "csmri_admm_train",
            "csmri_admm_backward", "csmri_hqs", "csmri_amp",
            "csmri_pg", "csmri_apg", "csmri_redadmm", "pr_iadmm", "spi_admm", "ct_iadmm", "ct_pg", "pr_pg",
-           "critic_value", "critic_backward", "critic_param_grad", "policy_ob_pack_diff", "policy_ob_unpack")
+           "critic_value", "critic_backward", "critic_param_grad", "critic_value_loss_grad", "policy_ob_pack_diff", "policy_ob_unpack")

@@ -15,8 +15,14 @@ the freshly stepped critic (:190) without a host reload.  `load_state_dict` is t
 the parameters as one flat vector in synth.critic_param_specs order (pnpx_critic_param_grad: weight gradients on the fp32
 MFMA, thresholds, fc, weight-norm).  A flat nn.Parameter takes it as .grad, a torch optimiser steps it and `load_flat_`
 takes the result (examples/train_critic.py); `forward` stays differentiable with respect to x only.
-Out of scope: value_loss itself, optimiser steps, gradient clipping, the MDDPG trainer loop, a trainable actor,
-depths other than 18.  (The native actor has the same live weights: policy/network.py; the replay memory is utils/rpm.py.)
+The critic's whole update is native as well: `value_loss_grad(x, q_target)` takes nn.MSELoss()(q_target, V) and its
+backward() from ONE forward (pnpx_critic_value_loss_grad), and `adam_step_(grad, lr, ...)` is clip_grad_norm_ +
+torch.optim.Adam.step() on the context's own parameter vector followed by the re-pack (pnpx_critic_adam_step): the
+parameters and Adam's moments never leave the native context, no torch optimiser is involved (`optim_state`,
+`reset_optim_`; trainer/mddpg/critic_step.py::critic_update is the critic's half of trainer.py::_update).
+Out of scope: the actor's loss and a trainable actor, weight decay / amsgrad / other optimisers, checkpointing the moments
+(the reference's save_model does not save them either), a graph-capturable step, the MDDPG trainer loop, depths other
+than 18.  (The native actor has the same live weights: policy/network.py; the replay memory is utils/rpm.py.)
 """
 import torch
 import torch.nn as nn
@@ -157,3 +163,45 @@ class ResNet_wobn(nn.Module):
             if isinstance(t, torch.Tensor) and not t.is_cuda:
                 raise ops.PnpxError(f"ResNet_wobn: tensor on {t.device}; tfpnp_amd runs on MI355X only, there is no CPU path")
         return T.call("critic_param_grad", x.detach(), grad_value.detach().reshape(-1), self.context(x.device).cid)
+
+    def value_loss_grad(self, x, q_target):
+        """-> (value_loss [], V [B, 1], grad [n_params]) on x's device from one forward: value_loss = nn.MSELoss()(q_target, V)
+        and value_loss.backward() (trainer.py:198,207).  V has forward(x)'s bytes, grad those of
+        param_grad(x, 2.0 * (V - q_target) / B).  q_target [B] or [B, 1] is the detached target; nothing here takes part in
+        autograd."""
+        for t in (x, q_target):
+            if isinstance(t, torch.Tensor) and not t.is_cuda:
+                raise ops.PnpxError(f"ResNet_wobn: tensor on {t.device}; tfpnp_amd runs on MI355X only, there is no CPU path")
+        V, loss, grad = T.call("critic_value_loss_grad", x.detach(), q_target.detach().reshape(-1), self.context(x.device).cid)
+        return loss, V, grad
+
+    def adam_step_(self, grad, lr, betas=(0.9, 0.999), eps=1e-8, max_norm=50.0):
+        """clip_grad_norm_(parameters, max_norm) + torch.optim.Adam.step() (trainer.py:208-209) on grad's device, in place on
+        the native parameter vector, then the re-pack.  Adam's moments and step counter live in the native context; they
+        survive load_flat_ / soft_update_ of the same critic.  -> the gradient norm before clipping (0-dim device tensor), as
+        clip_grad_norm_ returns it.  A gradient with a non-finite norm raises PnpxError and changes nothing."""
+        if not isinstance(grad, torch.Tensor):
+            raise ops.PnpxError(f"adam_step_: expected a torch.Tensor, got {type(grad).__name__}")
+        key = _key(grad.device)
+        ctx = self.context(grad.device)
+        try:
+            norm = ctx.critic_adam_step(grad, lr, betas, eps, max_norm)
+        except ops.PnpxError:
+            if ctx._critic is None:
+                del self._ctx[key]
+                if self._live == key:
+                    self._live = None
+            raise
+        self._changed_on(key)
+        return norm
+
+    def optim_state(self, device):
+        """(exp_avg, exp_avg_sq, step) of the context on `device`: copies of Adam's moments as flat fp32 vectors
+        (synth.critic_param_specs order) and the step counter; zeros and 0 before the first adam_step_."""
+        return self.context(device).critic_optim_state()
+
+    def reset_optim_(self):
+        """Forget Adam's moments and step counter on every device this critic lives on.  Returns self."""
+        for ctx in self._ctx.values():
+            ctx.critic_optim_reset()
+        return self
