@@ -213,6 +213,30 @@ int pnpx_policy_load_device(pnpx_ctx* ctx, const float* params_dev, size_t n_par
 /* Copies the live parameter vector (n_params floats, pnpx_policy_load's order) to dst_dev, ordered on `stream`.
  * PNPX_ERR_NO_WEIGHTS before a load. */
 int pnpx_policy_params(pnpx_ctx* ctx, float* dst_dev, size_t n_params, void* stream);
+/* The same network in TRAIN mode, as MDDPGTrainer._update runs the actor (trainer.py:128,171): each of the 20 BatchNorm layers
+ * normalises with the statistics of the batch -- per channel over B * h * w raw convolution outputs z: mean, biased variance var_b,
+ * y = (z - mean) / sqrt(var_b + 1e-5) * weight + bias -- which is F.batch_norm(training=True, momentum, eps = 1e-5); in block 0 of a
+ * stage both summands of relu(bn2(conv2) + shortcut_bn(shortcut_conv)) use their own statistics.  Pool and heads are unchanged.
+ * update_running != 0 moves the running statistics IN THE LIVE PARAMETER VECTOR (what pnpx_policy_params reads):
+ *   running_mean <- (1 - momentum) * running_mean + momentum * mean,
+ *   running_var  <- (1 - momentum) * running_var  + momentum * var_b * n / (n - 1);
+ * the eval-mode packing is then re-derived once, by the next pnpx_policy_forward (not after every train forward).  With
+ * update_running == 0 the parameter vector stays bit-identical.  num_batches_tracked is not kept: momentum is a number.
+ * The convolutions run on a second, fold-free packing of the live vector, derived by the first call after a load (one stream
+ * synchronisation, as pnpx_policy_load_device) together with a workspace that grows with B; eval-only users pay for neither.
+ * Batch statistics couple the images: the call is ONE launch chain whatever option "chains" says, and its result is deterministic
+ * (fixed-order reductions in double, no atomics).  Both settings of option "policy_s2_hs" are served.  Not capturable into a graph.
+ * H, W multiples of 32 (else PNPX_ERR_SHAPE); PNPX_ERR_ARG when the last stage has B * (H/32) * (W/32) < 2 values per channel
+ * (torch raises there) or momentum is outside [0, 1]; PNPX_ERR_NO_WEIGHTS before a load.  Out of scope: gradients, the optimiser
+ * step, statistics synchronised across devices, activations kept for a backward pass. */
+int pnpx_policy_forward_train(pnpx_ctx* ctx, const float* ob, float* probs, float* det, int B, int H, int W, float momentum,
+                              int update_running, void* stream);
+/* BatchNorm channels of the actor over its 20 layers in state_dict order (stem bn1, then per stage L.0.bn1, L.0.bn2,
+ * L.0.shortcut.1, L.1.bn1, L.1.bn2): 4864. */
+size_t pnpx_policy_num_bn_channels(void);
+/* Batch mean and biased batch variance of the last pnpx_policy_forward_train, concatenated in that order, copied to mean_dev /
+ * var_dev (n = pnpx_policy_num_bn_channels() floats each), ordered on `stream`.  PNPX_ERR_NO_WEIGHTS before any train forward. */
+int pnpx_policy_bn_stats(pnpx_ctx* ctx, float* mean_dev, float* var_dev, size_t n, void* stream);
 
 /* ---- value network / critic (tfpnp/trainer/mddpg/critic.py) --------------------------------------- */
 /* ResNet_wobn(num_inputs, 18, 1) (critic.py:95-131; the trainer never builds another one, trainer/mddpg/critic.py:95 via

@@ -205,6 +205,23 @@ int pnpx_policy_forward(pnpx_ctx* ctx, const float* ob, float* probs, float* det
   return policy_forward(ctx, ob, probs, det, B, H, W, static_cast<hipStream_t>(stream));
 }
 
+int pnpx_policy_forward_train(pnpx_ctx* ctx, const float* ob, float* probs, float* det, int B, int H, int W, float momentum,
+                              int update_running, void* stream) {
+  LOCK_CTX(ctx);
+  if (!ob || !probs || !det) {
+    set_error("pnpx_policy_forward_train: null pointer");
+    return PNPX_ERR_ARG;
+  }
+  return policy_forward_train(ctx, ob, probs, det, B, H, W, momentum, update_running, static_cast<hipStream_t>(stream));
+}
+
+size_t pnpx_policy_num_bn_channels(void) { return POLICY_BN_CHANNELS; }
+
+int pnpx_policy_bn_stats(pnpx_ctx* ctx, float* mean_dev, float* var_dev, size_t n, void* stream) {
+  LOCK_CTX(ctx);
+  return policy_bn_stats(ctx, mean_dev, var_dev, n, static_cast<hipStream_t>(stream));
+}
+
 size_t pnpx_critic_num_params(int num_inputs) {
   return (num_inputs >= 1 && num_inputs <= 64) ? critic_num_params(num_inputs) : 0;
 }
@@ -326,6 +343,7 @@ int pnpx_ctx_set_option(pnpx_ctx* ctx, const char* key, int value) {
     PNPX_HIP(hipDeviceSynchronize());
     ctx->opt_policy_s2_hs = value;
     ctx->policy.capB = ctx->policy.capH = ctx->policy.capW = 0;
+    ctx->policy.tcapB = ctx->policy.tcapH = ctx->policy.tcapW = 0;
     return PNPX_OK;
   }
   if (is("fold_first") && (value == 0 || value == 1)) {
@@ -464,7 +482,8 @@ size_t pnpx_ctx_bytes(const pnpx_ctx* ctx) {
   size_t n = ctx->weights.bytes + ctx->arena.buf.bytes + ctx->arena_grad.buf.bytes + ctx->scratch.bytes +
              ctx->drunet.weights.bytes + ctx->drunet.arena.bytes + ctx->drunet.arena_grad.bytes + ctx->drunet.f32_weights.bytes +
              ctx->drunet.f32_arena.bytes + ctx->drunet.f32_weights_bwd.bytes + ctx->drunet.f32_arena_grad.bytes +
-             ctx->policy.weights.bytes + ctx->policy.arena.bytes + ctx->policy.master.bytes + ctx->policy.pack_ws.bytes + ctx->critic.weights.bytes + ctx->critic.arena.bytes +
+             ctx->policy.weights.bytes + ctx->policy.arena.bytes + ctx->policy.master.bytes + ctx->policy.pack_ws.bytes + ctx->policy.raw.weights.bytes + ctx->policy.raw_ws.bytes +
+             ctx->policy.train_ws.bytes + ctx->policy.bn_buf.bytes + ctx->critic.weights.bytes + ctx->critic.arena.bytes +
              ctx->critic.master.bytes + ctx->critic.pack_ws.bytes + ctx->critic.optim.bytes;
   for (const auto& sl : ctx->train_ring) n += sl.arena.buf.bytes + sl.pre.bytes;
   return n;

@@ -86,9 +86,8 @@ struct PolicyConv {
   int cout = 0;     // output channels over both outputs, multiple of 64
   int split_c = 0;  // channels written to the first output (ReLU); the rest go to the second output (linear)
 };
-struct PolicyNet {
-  bool loaded = false;
-  int num_inputs = 0, cin_pad = 0, n_det = 0, spi_head = 0;
+// the packed weights one forward reads: launch descriptors over one device blob
+struct PolicyPack {
   PolicyConv conv[17];       // stem, then per stage: conv1+shortcut, conv2, block-2 conv1, block-2 conv2
   // the twelve stride-1 convolutions (per stage: conv2, block-2 conv1, block-2 conv2) packed for the half-split
   // f16x3 MFMA kernel (conv_hs.hip); conv[] keeps their fp32 packing only for the stride-2 launches and the stem
@@ -107,6 +106,10 @@ struct PolicyNet {
   const float* fc_det2_w = nullptr; // SPI head only: [n_det][64]
   const float* fc_det2_b = nullptr;
   DeviceBuf weights;
+};
+struct PolicyNet : PolicyPack {   // the base: the eval-mode packing (BatchNorm folded from the running statistics)
+  bool loaded = false;
+  int num_inputs = 0, cin_pad = 0, n_det = 0, spi_head = 0;
   DeviceBuf arena;           // activations for capB observations of capH x capW, zero borders
   int capB = 0, capH = 0, capW = 0;
   // live weights (policy_pack.hip): the flat fp32 parameter vector in pnpx_policy_load's order, kept after either load entry
@@ -114,6 +117,17 @@ struct PolicyNet {
   bool dev_layout = false;   // `weights` has the structural layout policy_load_device refreshes in place (else: policy_load's)
   DeviceBuf pack_ws;         // layer table, per-channel BatchNorm scales / shifts / weight maxima, the block read back per refresh
   float* readback = nullptr; // pinned host copy of that block: the 21 half-split weight scales
+  // train-mode forward (policy_bn.hip): the same convolutions packed WITHOUT the fold (scale 1, shift 0), derived from `master` by the
+  // first train forward after a load; moving the running statistics does not stale it, but it stales the eval packing above, which the
+  // next eval forward re-derives once (eval_stale)
+  PolicyPack raw;
+  DeviceBuf raw_ws;
+  float* raw_readback = nullptr;
+  bool raw_valid = false, eval_stale = false;
+  DeviceBuf train_ws;        // raw convolution outputs + activations of the train forward, zero borders
+  int tcapB = 0, tcapH = 0, tcapW = 0;
+  DeviceBuf bn_buf;          // per BatchNorm channel: batch mean, biased batch variance, scale, shift; then the reduction partials
+  bool bn_have_stats = false;
 };
 
 // Value network (critic.hip): ResNet_wobn(num_inputs, 18, 1).  The raw parameters live on the device (`master`); the packed
@@ -397,6 +411,17 @@ void policy_free(pnpx_ctx* ctx);
 int policy_keep_params(pnpx_ctx* ctx, const float* params_host, size_t n);   // policy_load: the parameter vector stays on the device
 int policy_load_device(pnpx_ctx* ctx, const float* params_dev, size_t n, int num_inputs, int n_det, int spi_head, hipStream_t s);
 int policy_params(pnpx_ctx* ctx, float* dst_dev, size_t n, hipStream_t s);
+int policy_pack_raw(pnpx_ctx* ctx, hipStream_t s);       // master -> PolicyNet::raw (allocates on first use)
+int policy_refresh_eval(pnpx_ctx* ctx, hipStream_t s);   // master -> the eval packing, after the running statistics moved
+// pieces of the eval forward the train forward shares (policy.hip)
+int policy_launch_pack_ob(const float* ob, float* out_f32, char* out_hs, int C, int Cp, int B, int H, int W, hipStream_t s);
+int policy_launch_heads(const PolicyPack& P, int n_det, int spi_head, const char* feat_hs, int h, int w, int B, float* probs, float* det,
+                         hipStream_t s);
+// train-mode forward (policy_bn.hip)
+constexpr size_t POLICY_BN_CHANNELS = 4864;
+int policy_forward_train(pnpx_ctx* ctx, const float* ob, float* probs, float* det, int B, int H, int W, float momentum, int update_running,
+                         hipStream_t s);
+int policy_bn_stats(pnpx_ctx* ctx, float* mean_dev, float* var_dev, size_t n, hipStream_t s);
 
 // Value network (critic.hip)
 size_t critic_num_params(int num_inputs);

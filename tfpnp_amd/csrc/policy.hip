@@ -345,6 +345,26 @@ PolicyPlan make_policy_plan(int capB, int cin_pad, int H, int W) {
 
 }  // namespace
 
+int policy_launch_pack_ob(const float* ob, float* out_f32, char* out_hs, int C, int Cp, int B, int H, int W, hipStream_t s) {
+  if (out_hs) {
+    const size_t n = (size_t)B * 4 * (Cp / 8) * (H / 2) * (W / 2);
+    hipLaunchKernelGGL(pack_ob_s2d_hs_kernel, g1(n), dim3(256), 0, s, ob, reinterpret_cast<HsRec*>(out_hs), C, Cp, H, W, n);
+  } else {
+    const size_t n = (size_t)B * C * H * W;
+    hipLaunchKernelGGL(pack_ob_s2d_kernel, g1(n), dim3(256), 0, s, ob, out_f32, C, Cp, H, W, n);
+  }
+  PNPX_LAUNCH_CHECK();
+  return PNPX_OK;
+}
+
+int policy_launch_heads(const PolicyPack& P, int n_det, int spi_head, const char* feat_hs, int h, int w, int B, float* probs, float* det,
+                        hipStream_t s) {
+  hipLaunchKernelGGL(pool_heads_kernel, dim3(B), dim3(256), 0, s, reinterpret_cast<const HsRec*>(feat_hs), h, w, P.fc_sm_w, P.fc_sm_b,
+                     P.fc_det_w, P.fc_det_b, P.fc_det2_w, P.fc_det2_b, n_det, spi_head, probs, det);
+  PNPX_LAUNCH_CHECK();
+  return PNPX_OK;
+}
+
 size_t policy_num_params(int num_inputs, int n_det, int spi_head) {
   size_t n = (size_t)64 * num_inputs * 9 + 4 * 64;
   int in_planes = 64;
@@ -366,6 +386,11 @@ void policy_free(pnpx_ctx* ctx) {
   if (N.master.p) (void)hipFree(N.master.p);
   if (N.pack_ws.p) (void)hipFree(N.pack_ws.p);
   if (N.readback) (void)hipHostFree(N.readback);
+  if (N.raw.weights.p) (void)hipFree(N.raw.weights.p);
+  if (N.raw_ws.p) (void)hipFree(N.raw_ws.p);
+  if (N.raw_readback) (void)hipHostFree(N.raw_readback);
+  if (N.train_ws.p) (void)hipFree(N.train_ws.p);
+  if (N.bn_buf.p) (void)hipFree(N.bn_buf.p);
   N = PolicyNet();
 }
 
@@ -570,6 +595,8 @@ int policy_forward(pnpx_ctx* ctx, const float* ob, float* probs, float* det, int
     set_error("policy forward: need B > 0 and H, W positive multiples of 32 (got %d x %d x %d)", B, H, W);
     return PNPX_ERR_SHAPE;
   }
+  // a train forward moved the running statistics: fold and pack again, once, before the first eval forward that follows
+  if (N.eval_stale) PNPX_TRY(policy_refresh_eval(ctx, s));
   if (!(B <= N.capB && H == N.capH && W == N.capW)) {
     const bool same = (H == N.capH && W == N.capW);
     const int nb = same ? (B > N.capB ? B : N.capB) : B;

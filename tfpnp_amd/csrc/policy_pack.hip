@@ -222,8 +222,8 @@ struct PolPackWs {
 };
 inline size_t ws_table_bytes() { return (sizeof(PolPackTable) + 255) & ~(size_t)255; }
 inline size_t ws_bytes(unsigned nchan) { return ws_table_bytes() + ((size_t)3 * nchan + NRB) * sizeof(float); }
-inline PolPackWs pack_ws(const PolicyNet& N, unsigned nchan) {
-  char* p = static_cast<char*>(N.pack_ws.p);
+inline PolPackWs pack_ws(const DeviceBuf& buf, unsigned nchan) {
+  char* p = static_cast<char*>(buf.p);
   PolPackWs w;
   w.T = reinterpret_cast<PolPackTable*>(p);
   w.sc = reinterpret_cast<float*>(p + ws_table_bytes());
@@ -236,8 +236,9 @@ inline PolPackWs pack_ws(const PolicyNet& N, unsigned nchan) {
 // policy.hip::bn_fold of one output channel + the largest folded weight of that channel.  One 64-lane workgroup per channel
 // walks the channel's fan: a maximum does not depend on the order.  fl(|w| * |scale|) is monotonic in |w|, so the largest
 // folded weight is the fold of the largest |w|.  A NaN weight makes the channel's maximum NaN (the refresh is then refused).
+// raw != 0: no fold -- scale exactly 1, shift exactly 0, the maximum of the weights themselves (the train-mode packing, policy_bn.hip).
 __global__ __launch_bounds__(64) void pol_fold_kernel(const PolPackTable* __restrict__ T, const float* __restrict__ P,
-                                                      float* __restrict__ sc, float* __restrict__ sh, float* __restrict__ chmax) {
+                                                      float* __restrict__ sc, float* __restrict__ sh, float* __restrict__ chmax, int raw) {
 #pragma clang fp contract(off)
   __shared__ float part[64];
   __shared__ int nan_seen;
@@ -265,6 +266,12 @@ __global__ __launch_bounds__(64) void pol_fold_kernel(const PolPackTable* __rest
     __syncthreads();
   }
   if (tid != 0) return;
+  if (raw) {
+    sc[ch] = 1.f;
+    sh[ch] = 0.f;
+    chmax[ch] = nan_seen ? NAN : part[0];
+    return;
+  }
   const float* bn = P + F.src_bn + co;
   const float g = bn[0], b = bn[F.cout], m = bn[2 * (size_t)F.cout], v = bn[3 * (size_t)F.cout];
   // the fp32 square root as the host's sqrtss rounds it: the correctly rounded double root, rounded once more (exact for 53 >= 2 * 24 + 2
@@ -391,14 +398,14 @@ int alloc_dev(DeviceBuf& b, size_t bytes, const char* what) {
 }
 
 // a fresh blob in the structural layout: zero padding and guards, the step lists; the packing workspace with its table
-int alloc_device_layout(PolicyNet& N, const PolicyLayout& L) {
+int alloc_device_layout(PolicyPack& N, DeviceBuf& ws, float*& readback, const PolicyLayout& L) {
   PNPX_TRY(alloc_dev(N.weights, L.total * sizeof(float), "weight"));
-  PNPX_TRY(alloc_dev(N.pack_ws, ws_bytes(L.T.nchan), "packing workspace"));
+  PNPX_TRY(alloc_dev(ws, ws_bytes(L.T.nchan), "packing workspace"));
   void* h = nullptr;
   PNPX_HIP(hipHostMalloc(&h, NRB * sizeof(float), hipHostMallocDefault));
-  N.readback = static_cast<float*>(h);
+  readback = static_cast<float*>(h);
   PNPX_HIP(hipMemset(N.weights.p, 0, N.weights.bytes));
-  PNPX_HIP(hipMemcpy(N.pack_ws.p, &L.T, sizeof(PolPackTable), hipMemcpyHostToDevice));
+  PNPX_HIP(hipMemcpy(ws.p, &L.T, sizeof(PolPackTable), hipMemcpyHostToDevice));
   float* base = static_cast<float*>(N.weights.p);
   static_assert(sizeof(PolStep) == 8, "PolStep layout");
   for (int i = 0; i < NF32; ++i) {
@@ -410,7 +417,7 @@ int alloc_device_layout(PolicyNet& N, const PolicyLayout& L) {
 }
 
 // launch descriptors over the blob (the scales follow from the read-back)
-void bind_blob(PolicyNet& N, const PolicyLayout& L) {
+void bind_blob(PolicyPack& N, const PolicyLayout& L, int spi_head) {
   float* base = static_cast<float*>(N.weights.p);
   for (int i = 0; i < 17; ++i) {
     N.conv[i] = PolicyConv();
@@ -449,17 +456,19 @@ void bind_blob(PolicyNet& N, const PolicyLayout& L) {
   N.fc_sm_b = base + L.smb;
   N.fc_det_w = base + L.dw;
   N.fc_det_b = base + L.db;
-  N.fc_det2_w = N.spi_head ? base + L.d2w : nullptr;
-  N.fc_det2_b = N.spi_head ? base + L.d2b : nullptr;
+  N.fc_det2_w = spi_head ? base + L.d2w : nullptr;
+  N.fc_det2_b = spi_head ? base + L.d2b : nullptr;
 }
 
-// master -> weight blob on stream s, then the one read-back: the 21 half-split scales
-int repack(pnpx_ctx* ctx, const PolicyLayout& L, hipStream_t s) {
+// master -> weight blob on stream s, then the one read-back: the 21 half-split scales.  raw: the fold-free packing (PolicyNet::raw)
+int repack(pnpx_ctx* ctx, const PolicyLayout& L, hipStream_t s, bool raw = false) {
   PolicyNet& N = ctx->policy;
-  const PolPackWs w = pack_ws(N, L.T.nchan);
+  PolicyPack& K = raw ? N.raw : static_cast<PolicyPack&>(N);
+  float* const rb_host = raw ? N.raw_readback : N.readback;
+  const PolPackWs w = pack_ws(raw ? N.raw_ws : N.pack_ws, L.T.nchan);
   const float* P = static_cast<const float*>(N.master.p);
-  float* blob = static_cast<float*>(N.weights.p);
-  hipLaunchKernelGGL(pol_fold_kernel, dim3(L.T.nchan), dim3(64), 0, s, w.T, P, w.sc, w.sh, w.chmax);
+  float* blob = static_cast<float*>(K.weights.p);
+  hipLaunchKernelGGL(pol_fold_kernel, dim3(L.T.nchan), dim3(64), 0, s, w.T, P, w.sc, w.sh, w.chmax, raw ? 1 : 0);
   PNPX_LAUNCH_CHECK();
   hipLaunchKernelGGL(pol_scale_kernel, dim3(NCV), dim3(256), 0, s, w.T, w.chmax, w.rb);
   PNPX_LAUNCH_CHECK();
@@ -469,27 +478,32 @@ int repack(pnpx_ctx* ctx, const PolicyLayout& L, hipStream_t s) {
   PNPX_LAUNCH_CHECK();
   hipLaunchKernelGGL(pol_copy_kernel, dim3((L.max_copy + 255) / 256, L.T.ncopy), dim3(256), 0, s, w.T, P, w.sh, blob);
   PNPX_LAUNCH_CHECK();
-  PNPX_HIP(hipMemcpyAsync(N.readback, w.rb, NCV * sizeof(float), hipMemcpyDeviceToHost, s));
+  PNPX_HIP(hipMemcpyAsync(rb_host, w.rb, NCV * sizeof(float), hipMemcpyDeviceToHost, s));
   PNPX_HIP(hipStreamSynchronize(s));
   for (int i = 0; i < NCV; ++i)
-    if (!std::isfinite(N.readback[i])) {
+    if (!std::isfinite(rb_host[i])) {
       set_error("policy refresh: the weight scale of convolution %d is not finite (NaN weight, or a BatchNorm scale that is not finite: "
                 "running_var NaN or below -eps)", i);
       PNPX_HIP(hipDeviceSynchronize());
       policy_free(ctx);
       return PNPX_ERR_ARG;
     }
-  auto inv = [&](int ci) { return 1.0f / (N.readback[ci] * HS_ASCALE); };
-  N.stem_hs.inv_scale = inv(0);
+  auto inv = [&](int ci) { return 1.0f / (rb_host[ci] * HS_ASCALE); };
+  K.stem_hs.inv_scale = inv(0);
   for (int st = 0; st < 4; ++st) {
     const int c0 = 1 + 5 * st;
-    N.s2_hs[st][0].inv_scale = inv(c0 + 0);
-    N.s2_hs[st][1].inv_scale = inv(c0 + 2);
-    N.conv_hs[3 * st + 0].inv_scale = inv(c0 + 1);
-    N.conv_hs[3 * st + 1].inv_scale = inv(c0 + 3);
-    N.conv_hs[3 * st + 2].inv_scale = inv(c0 + 4);
+    K.s2_hs[st][0].inv_scale = inv(c0 + 0);
+    K.s2_hs[st][1].inv_scale = inv(c0 + 2);
+    K.conv_hs[3 * st + 0].inv_scale = inv(c0 + 1);
+    K.conv_hs[3 * st + 1].inv_scale = inv(c0 + 3);
+    K.conv_hs[3 * st + 2].inv_scale = inv(c0 + 4);
   }
-  N.loaded = true;
+  if (raw) {
+    N.raw_valid = true;
+  } else {
+    N.loaded = true;
+    N.eval_stale = false;
+  }
   return PNPX_OK;
 }
 
@@ -535,16 +549,53 @@ int policy_load_device(pnpx_ctx* ctx, const float* params_dev, size_t n, int num
     N.cin_pad = (num_inputs + 7) / 8 * 8;
     N.n_det = n_det;
     N.spi_head = spi_head;
-    int st = alloc_device_layout(N, L);
+    int st = alloc_device_layout(N, N.pack_ws, N.readback, L);
     if (st == PNPX_OK) st = alloc_dev(N.master, n * sizeof(float), "parameter");
     if (st != PNPX_OK) {
       policy_free(ctx);
       return st;
     }
-    bind_blob(N, L);
+    bind_blob(N, L, N.spi_head);
     N.dev_layout = true;
   }
+  N.raw_valid = false;   // new weights: the train-mode packing follows on the next train forward
   if (params_dev != N.master.p) PNPX_HIP(hipMemcpyAsync(N.master.p, params_dev, n * sizeof(float), hipMemcpyDeviceToDevice, s));
+  return repack(ctx, L, s);
+}
+
+int policy_pack_raw(pnpx_ctx* ctx, hipStream_t s) {
+  PolicyNet& N = ctx->policy;
+  PolicyLayout L;
+  if (!make_layout(N.num_inputs, N.n_det, N.spi_head, L)) {
+    set_error("policy train forward: internal layout error for (%d inputs, %d outputs, spi %d)", N.num_inputs, N.n_det, N.spi_head);
+    return PNPX_ERR_SHAPE;
+  }
+  if (!N.raw.weights.p) {
+    PNPX_TRY(alloc_device_layout(N.raw, N.raw_ws, N.raw_readback, L));
+    bind_blob(N.raw, L, N.spi_head);
+  }
+  return repack(ctx, L, s, true);
+}
+
+int policy_refresh_eval(pnpx_ctx* ctx, hipStream_t s) {
+  PolicyNet& N = ctx->policy;
+  PolicyLayout L;
+  if (!make_layout(N.num_inputs, N.n_det, N.spi_head, L)) {
+    set_error("policy refresh: internal layout error for (%d inputs, %d outputs, spi %d)", N.num_inputs, N.n_det, N.spi_head);
+    return PNPX_ERR_SHAPE;
+  }
+  if (!N.dev_layout) {   // a blob in policy_load's value-dependent layout: replace it by the structural one (the parameter vector stays)
+    PNPX_HIP(hipDeviceSynchronize());
+    if (N.weights.p) PNPX_HIP(hipFree(N.weights.p));
+    N.weights = DeviceBuf();
+    const int st = alloc_device_layout(N, N.pack_ws, N.readback, L);
+    if (st != PNPX_OK) {   // nothing left to run on: the context holds no actor any more
+      policy_free(ctx);
+      return st;
+    }
+    bind_blob(N, L, N.spi_head);
+    N.dev_layout = true;
+  }
   return repack(ctx, L, s);
 }
 

@@ -464,6 +464,33 @@ def policy_forward(ctx, ob):
     return probs, det
 
 
+def policy_forward_train(ctx, ob, momentum=0.1, update_running=True):
+    """ob [B,C,H,W] -> (probs [B,2], det [B,n_det]) of the loaded actor in TRAIN mode: every BatchNorm normalises with the
+    statistics of this batch (F.batch_norm(training=True, momentum, eps=1e-5)); update_running moves the running statistics
+    in the context's live parameter vector (policy_params), and the next eval-mode policy_forward uses them."""
+    ob = _f32(ob, "ob")
+    if ob.dim() != 4 or getattr(ctx, "_policy", None) is None or ob.shape[1] != ctx._policy[0]:
+        raise PnpxError("policy_forward_train: no policy loaded or observation has the wrong channel count")
+    B, _, H, W = ob.shape
+    probs = torch.empty((B, 2), device=ob.device, dtype=torch.float32)
+    det = torch.empty((B, ctx._policy[1]), device=ob.device, dtype=torch.float32)
+    with torch.cuda.device(ob.device):
+        check(_lib.lib().pnpx_policy_forward_train(ctx.handle, _p(ob), _p(probs), _p(det), B, H, W, float(momentum),
+                                                   int(bool(update_running)), _stream(ob)))
+    return probs, det
+
+
+def policy_bn_stats(ctx):
+    """(mean, var) of the last policy_forward_train on `ctx`: batch mean and biased batch variance of the actor's 4864
+    BatchNorm channels, concatenated in state_dict order (fp32, on the context's device)."""
+    n = int(_lib.lib().pnpx_policy_num_bn_channels())
+    mean = torch.empty((n,), device=ctx.device, dtype=torch.float32)
+    var = torch.empty((n,), device=ctx.device, dtype=torch.float32)
+    with torch.cuda.device(ctx.device):
+        check(_lib.lib().pnpx_policy_bn_stats(ctx.handle, _p(mean), _p(var), n, _stream(mean)))
+    return mean, var
+
+
 def _critic_ob(ctx, ob, who):
     ob = _f32(ob, "ob")
     if ob.dim() != 4 or getattr(ctx, "_critic", None) is None or ob.shape[1] != ctx._critic:

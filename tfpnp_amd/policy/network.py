@@ -10,8 +10,17 @@ The weights are LIVE, as the native critic's are: the context keeps the flat par
 order: parameters AND BatchNorm running statistics) on the device, and `load_flat_` / utils.misc.hard_update replace it
 there and re-derive the packed weights on the device (BatchNorm fold included), so the native actor can follow a torch
 actor that an optimiser trains (trainer.py:201-204) and run the next rollout (:216-222) without a host reload.
-`load_state_dict` is the checkpoint path (folds and packs on the host).  Training the actor itself (batch statistics,
-weight gradients) is out of scope.
+`load_state_dict` is the checkpoint path (folds and packs on the host).
+
+Train-mode BatchNorm is opt-in: an actor built with `bn_follows_mode=True` follows `self.training` as the reference module
+does.  After `.train()` its forward normalises every BatchNorm layer with the statistics of the batch and moves the running
+statistics (momentum 0.1) in the live parameter vector (pnpx_policy_forward_train); after `.eval()` it runs the path above,
+on the moved statistics -- so the reference's `run_policy` (eval -> forward -> train) and `_update` (trainer.py:128,171)
+behave as written, and `state_dict()` / `parameters_flat()` return the moved statistics.  The default `False` keeps the
+eval-mode forward whatever the mode: an nn.Module is in training mode from construction, and existing callers never call
+`.eval()`.  The train-mode forward carries no autograd graph.  Still out of scope: the actor's parameter and input
+gradients, its optimiser step and policy_loss, statistics synchronised across devices (dist.py), num_batches_tracked
+(momentum is a number, so torch never reads it), graph capture of the train forward.
 """
 from collections import OrderedDict
 from typing import Optional
@@ -26,8 +35,11 @@ from .. import torch_ops as T
 class ResNetActorBase(nn.Module):
     spi_head = False
 
-    def __init__(self, num_inputs, action_bundle, num_actions, state_dict=None):
+    bn_momentum = 0.1           # SynchronizedBatchNorm2d's default (sync_batchnorm/batchnorm.py)
+
+    def __init__(self, num_inputs, action_bundle, num_actions, state_dict=None, bn_follows_mode=False):
         super().__init__()
+        self.bn_follows_mode = bool(bn_follows_mode)
         self.in_dim = num_inputs
         self.num_actions = num_actions
         self.action_range = None
@@ -123,7 +135,16 @@ class ResNetActorBase(nn.Module):
 
     def forward(self, state, idx_stop, train, hidden):
         """-> (action dict incl. 'idx_stop', log-prob of idx_stop [B,1], entropy of the stop head [B,1], hidden)"""
-        p_stop, det = T.call("policy_forward", state, self.context(state.device).cid)   # [B,2] softmax, [B,n_det] sigmoid
+        ctx = self.context(state.device)
+        if self.bn_follows_mode and self.training:
+            # batch statistics; the running statistics move on this device: its vector is the truth from here on
+            p_stop, det = T.call("policy_forward_train", state, self.bn_momentum, True, ctx.cid)
+            key = next(k for k, c in self._ctx.items() if c is ctx)
+            self._ctx = {key: ctx}
+            self._live = key
+            self._state = None
+        else:
+            p_stop, det = T.call("policy_forward", state, ctx.cid)   # [B,2] softmax, [B,n_det] sigmoid
         logp = torch.log(p_stop.clamp_min(torch.finfo(p_stop.dtype).eps))     # Categorical's own clamp
         entropy = -torch.special.xlogy(p_stop, p_stop).sum(dim=1, keepdim=True)
         if idx_stop is None:      # stochastic while training, greedy otherwise (network.py:149-156)
@@ -144,8 +165,9 @@ class ResNetActorBase(nn.Module):
 
 
 def _actor(name, extra_inputs, num_actions, default_range, spi=False):
-    def __init__(self, num_aux_inputs, action_bundle, action_range: Optional[OrderedDict] = None, state_dict=None):
-        ResNetActorBase.__init__(self, num_aux_inputs + extra_inputs, action_bundle, num_actions, state_dict)
+    def __init__(self, num_aux_inputs, action_bundle, action_range: Optional[OrderedDict] = None, state_dict=None,
+                 bn_follows_mode=False):
+        ResNetActorBase.__init__(self, num_aux_inputs + extra_inputs, action_bundle, num_actions, state_dict, bn_follows_mode)
         self.action_range = OrderedDict(default_range) if action_range is None else action_range
     return type(name, (ResNetActorBase,), {"__init__": __init__, "spi_head": spi, "__doc__":
                                            f"tfpnp/policy/network.py {name}: same inputs / action ranges."})
