@@ -1,6 +1,6 @@
 """Cases and helpers of the actor live-weight tests: a torch stand-in for the reference's ResNetActor_* written from
 synth.policy_param_specs (same attribute names, so the same state_dict keys), flat-vector helpers, the output comparison,
-and a numpy restatement of the host's dense effective weights (csrc/policy.hip: Eff, put_conv_s2, put_shortcut, pack_eff)
+and a numpy restatement of the host's dense effective weights (csrc/resnet18_hs.hip: Eff, put_conv_s2, put_shortcut behind csrc/policy.hip: bn_folded; csrc/policy.hip: pack_eff)
 that checks the structural-presence rule of the device packing.  No GPU needed to import, no reference import."""
 import numpy as np
 import torch
@@ -131,7 +131,7 @@ def _bn_scale(P, pre):
 
 
 def _put_conv_s2(E, w, sc, Cp):
-    """csrc/policy.hip::put_conv_s2: 3x3 stride-2 convolution over a space-to-depth input with Cp channels per phase."""
+    """csrc/resnet18_hs.hip::put_conv_s2: 3x3 stride-2 convolution over a space-to-depth input with Cp channels per phase."""
     cout, cin = w.shape[:2]
     for dy in range(3):
         for dx in range(3):

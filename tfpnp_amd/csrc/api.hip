@@ -42,6 +42,18 @@ int ctx_scratch(pnpx_ctx* ctx, size_t bytes, void** out) {
   return PNPX_OK;
 }
 
+int alloc_dev(DeviceBuf& b, size_t bytes, const char* what) {
+  void* p = nullptr;
+  hipError_t e = hipMalloc(&p, bytes);
+  if (e != hipSuccess) {
+    set_error("%s allocation of %zu bytes failed: %s", what, bytes, hipGetErrorString(e));
+    return PNPX_ERR_ALLOC;
+  }
+  b.p = p;
+  b.bytes = bytes;
+  return PNPX_OK;
+}
+
 // UNet(2,1) layer table in state_dict order (tfpnp/pnp/denoiser/models/unet.py:37-46).
 struct LayerSpec {
   int cin, cout;

@@ -88,17 +88,12 @@ struct PolicyConv {
 };
 // the packed weights one forward reads: launch descriptors over one device blob
 struct PolicyPack {
-  PolicyConv conv[17];       // stem, then per stage: conv1+shortcut, conv2, block-2 conv1, block-2 conv2
-  // the twelve stride-1 convolutions (per stage: conv2, block-2 conv1, block-2 conv2) packed for the half-split
-  // f16x3 MFMA kernel (conv_hs.hip); conv[] keeps their fp32 packing only for the stride-2 launches and the stem
-  ConvLayerHsDev conv_hs[12];
-  const float* bias_hs[12] = {};
-  // stage entries (stride 2) on the sparse-tap half-split instances over the HS8 space-to-depth input:
-  // [st][0] = conv1 as a 2x2-window convolution (tap mask 0x01B), [st][1] = the 1x1 shortcut (0x010, first Cin channels)
-  ConvLayerHsDev s2_hs[4][2];
-  const float* s2_bias[4][2] = {};
-  ConvLayerHsDev stem_hs;          // the stem (3x3 stride 2) as a 2x2-window sparse-tap launch over the HS8 space-to-depth observation
-  const float* stem_hs_bias = nullptr;
+  // the 21 convolutions of the trunk packed for the half-split launches, in the layer numbering of resnet18_hs.h: the stem and the
+  // stage-entry conv1 as 2x2-window sparse-tap convolutions over the HS8 space-to-depth input (tap mask 0x01B), the 1x1 shortcuts
+  // (0x010, first Cin channels), the stride-1 convolutions (f16x3 MFMA kernel, conv_hs.hip)
+  ConvLayerHsDev hs[21];
+  const float* hs_bias[21] = {};
+  PolicyConv f32[5];         // option policy_s2_hs = 0: the stem, then per stage conv1 + shortcut as one fp32 tap-sparse launch
   const float* fc_sm_w = nullptr;   // [2][512], [2]
   const float* fc_sm_b = nullptr;
   const float* fc_det_w = nullptr;  // [n_det][512] ([64][512] with the SPI head)
@@ -132,8 +127,7 @@ struct PolicyNet : PolicyPack {   // the base: the eval-mode packing (BatchNorm 
 
 // Value network (critic.hip): ResNet_wobn(num_inputs, 18, 1).  The raw parameters live on the device (`master`); the packed
 // weights the launches read are derived from them, on the host by critic_load and on the device by every later refresh
-// (critic_load_device, critic_soft_update).  Layer index: 0 = stem,
-// 1 + 5 * stage + {0 entry conv1 (stride 2), 1 shortcut (1x1 stride 2), 2 conv2, 3 block-1 conv1, 4 block-1 conv2}.
+// (critic_load_device, critic_soft_update).  Layer index: the trunk's (resnet18_hs.h).
 struct CriticNet {
   bool loaded = false;
   int num_inputs = 0, cin_pad = 0;
@@ -334,6 +328,8 @@ int fan_out_chains(pnpx_ctx* ctx, int chains, int B, hipStream_t s, F&& run_slic
 int ctx_reserve_unet(pnpx_ctx* ctx, int B, int H, int W);   // main arena, ctx->conv_mode
 int reserve_arena(pnpx_ctx* ctx, UNetArena& ar, int mode, int B, int H, int W, size_t extra_bytes);
 int ctx_scratch(pnpx_ctx* ctx, size_t bytes, void** out);
+// hipMalloc into an empty DeviceBuf; on failure the error reads "<what> allocation of N bytes failed"
+int alloc_dev(DeviceBuf& b, size_t bytes, const char* what);
 int ctx_twiddle(pnpx_ctx* ctx, int N, const float2** out);
 // Half-split range guard (api.hip).  range_guard_enter: called at the top of every entry that runs the denoiser; if the
 // flag of an earlier call is set, latches the context to conv_mode 0.  range_guard_strict: option value 2 -- synchronise
@@ -413,8 +409,8 @@ int policy_load_device(pnpx_ctx* ctx, const float* params_dev, size_t n, int num
 int policy_params(pnpx_ctx* ctx, float* dst_dev, size_t n, hipStream_t s);
 int policy_pack_raw(pnpx_ctx* ctx, hipStream_t s);       // master -> PolicyNet::raw (allocates on first use)
 int policy_refresh_eval(pnpx_ctx* ctx, hipStream_t s);   // master -> the eval packing, after the running statistics moved
-// pieces of the eval forward the train forward shares (policy.hip)
-int policy_launch_pack_ob(const float* ob, float* out_f32, char* out_hs, int C, int Cp, int B, int H, int W, hipStream_t s);
+// pieces of the eval forward the train forward shares (policy.hip; the half-split ones: resnet18_hs.h)
+int policy_launch_pack_ob_f32(const float* ob, float* out, int C, int Cp, int B, int H, int W, hipStream_t s);   // option policy_s2_hs = 0
 int policy_launch_heads(const PolicyPack& P, int n_det, int spi_head, const char* feat_hs, int h, int w, int B, float* probs, float* det,
                          hipStream_t s);
 // train-mode forward (policy_bn.hip)

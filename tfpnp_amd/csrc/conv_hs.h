@@ -14,6 +14,18 @@ struct ConvLayerHs {
   const float* b = nullptr;   // device: [cout] fp32
   float inv_scale = 1.f;      // 1 / (weight_scale * HS_ASCALE)
 };
+// the launch descriptor of a packed layer kept in a context, with the bias operand of this launch
+inline ConvLayerHs hs_layer(const ConvLayerHsDev& D, const float* bias) {
+  ConvLayerHs L;
+  L.cin = D.cin;
+  L.cout = D.cout;
+  L.cin_pad = D.cin_pad;
+  L.mt = D.mt;
+  L.w = D.w;
+  L.b = bias;
+  L.inv_scale = D.inv_scale;
+  return L;
+}
 
 // n / d for small n by one multiply-high (exact for n * d < 2^32; checked at launch): the persistent tile walk
 // decodes its work items with these instead of hardware-less integer division sequences.

@@ -19,9 +19,10 @@
 // Convolutions are weight-normalised with bias (w = g * v / ||v||, norm per output channel: folded whenever the weights change);
 // TReLU(t) = relu(t - alpha) + alpha = max(t, alpha) with one scalar alpha per activation (critic.py:11-19).
 //
-// The topology is the actor's (policy.hip), so the forward runs on the same half-split launches: the stem and the stage
-// entries as 2x2-window convolutions (tap mask 0x01B) over HS8 space-to-depth tensors, the shortcut as the 1x1 instance
-// (linear epilogue), the stride-1 convolutions with the residual operand -- with the TReLU epilogue (conv_hs_trelu.hip).
+// The topology is the actor's, so the forward IS the actor's: resnet18_hs.hip::trunk_forward (layer numbering, host packing of a
+// layer, arena and plan of the forward tensors are shared there) -- the stem and the stage entries as 2x2-window convolutions
+// (tap mask 0x01B) over HS8 space-to-depth tensors, the shortcut as the 1x1 instance (linear epilogue), the stride-1
+// convolutions with the residual operand -- with the TReLU epilogue (conv_hs_trelu.hip) in place of ReLU.
 // alpha cannot be folded into the bias: `+ alpha` behind the rectifier would leak into the zero border of the next layer.
 //
 // Backward (dV/d ob times grad_value): the forward is re-computed (every activation stays in the arena; nothing is kept
@@ -44,43 +45,16 @@
 #include "hs_rec.h"
 #include "hs_relayout.h"
 #include "pack_desc.h"
+#include "resnet18_hs.h"
 
 namespace pnpx {
 namespace {
-
-inline dim3 g1(size_t n) { return dim3((unsigned)((n + 255) / 256)); }
-inline int stage_planes(int n) { return 64 << n; }   // n = 0..3
 
 // what a stored TReLU output equal to its threshold reads back as (the hi/lo split of 16 * alpha, conv_hs_kernel.h)
 inline float hs_roundtrip16(float alpha) {
   const float a16 = alpha * HS_ASCALE;
   const _Float16 hi = (_Float16)a16;
   return (float)hi + (float)(_Float16)(a16 - (float)hi);
-}
-
-// observation [B][C][H][W] fp32 -> HS8 space-to-depth tensor [B][4*Cp/8][H/2+2][W/2+2] (phase-major channel groups;
-// channels >= C are zero)
-__global__ __launch_bounds__(256) void critic_pack_ob_kernel(const float* __restrict__ ob, HsRec* __restrict__ out, int C, int Cp,
-                                                             int H, int W, size_t n) {
-  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  const int W2 = W >> 1, H2 = H >> 1, Gp = Cp >> 3;
-  const int x2 = (int)(i % W2);
-  size_t t = i / W2;
-  const int y2 = (int)(t % H2);
-  t /= H2;
-  const int g = (int)(t % Gp);
-  t /= Gp;
-  const int ph = (int)(t % 4);
-  const size_t b = t / 4;
-  const int y = 2 * y2 + (ph >> 1), x = 2 * x2 + (ph & 1);
-  float v[8];
-#pragma unroll
-  for (int k = 0; k < 8; ++k) {
-    const int c = g * 8 + k;
-    v[k] = c < C ? ob[((b * C + c) * H + y) * (size_t)W + x] * HS_ASCALE : 0.f;
-  }
-  out[((b * 4 * Gp + (size_t)ph * Gp + g) * (H2 + 2) + (y2 + 1)) * (size_t)(W2 + 2) + (x2 + 1)] = hs_pack(v);
 }
 
 // global average pool over HS8 [B][64 groups][h+2][w+2] + Linear(512, 1).  One workgroup per observation; fixed summation
@@ -92,16 +66,7 @@ __global__ __launch_bounds__(256) void critic_pool_fc_kernel(const HsRec* __rest
   const int b = blockIdx.x, tid = threadIdx.x;
   const float inv = 1.f / ((float)(h * w) * HS_ASCALE);
   float acc = 0.f;
-  for (int c = tid; c < 512; c += 256) {
-    const HsRec* p = feat + ((size_t)b * 64 + (c >> 3)) * (h + 2) * (w + 2);
-    float s = 0.f;
-    for (int y = 0; y < h; ++y)
-      for (int x = 0; x < w; ++x) {
-        const HsRec& r = p[(y + 1) * (w + 2) + x + 1];
-        s += (float)r.hi[c & 7] + (float)r.lo[c & 7];
-      }
-    acc = fmaf(s * inv, fc_w[c], acc);
-  }
+  for (int c = tid; c < 512; c += 256) acc = fmaf(hs_pooled(feat, b, 64, c, h, w, inv), fc_w[c], acc);
   part[tid] = acc;
   __syncthreads();
   for (int st = 128; st > 0; st >>= 1) {
@@ -168,24 +133,8 @@ __global__ __launch_bounds__(256) void critic_mse_kernel(const float* __restrict
 }
 
 // ------------------------------------------------------------------------------------------- parameter layout
-struct Reader {
-  const float* p;
-  const float* take(size_t n) {
-    const float* r = p;
-    p += n;
-    return r;
-  }
-};
 struct WnConv {   // registration order of a weight-normalised Conv2d: bias, weight_g, weight_v
   const float *b, *g, *v;
-};
-// Dense "effective" weights of one launch: E[cout][K][9] (+ bias[cout])
-struct Eff {
-  int cout, K;
-  std::vector<float> w, bias;
-  Eff(int cout_, int K_) : cout(cout_), K(K_), w((size_t)cout_ * K_ * 9, 0.f), bias(cout_, 0.f) {}
-  float& at(int co, int k, int tap) { return w[((size_t)co * K + k) * 9 + tap]; }
-  float at(int co, int k, int tap) const { return w[((size_t)co * K + k) * 9 + tap]; }
 };
 // weight = weight_g * weight_v / ||weight_v||, norm over everything but the output channel (torch.nn.utils.weight_norm, dim 0)
 std::vector<float> wn_fold(const WnConv& c, int cout, size_t fan) {
@@ -198,37 +147,6 @@ std::vector<float> wn_fold(const WnConv& c, int cout, size_t fan) {
   }
   return w;
 }
-void put_conv_s1(Eff& E, const WnConv& c, int cout, int cin) {
-  const std::vector<float> w = wn_fold(c, cout, (size_t)cin * 9);
-  for (int co = 0; co < cout; ++co) {
-    E.bias[co] = c.b[co];
-    for (int ci = 0; ci < cin; ++ci)
-      for (int t = 0; t < 9; ++t) E.at(co, ci, t) = w[((size_t)co * cin + ci) * 9 + t];
-  }
-}
-// 3x3 stride-2 conv over a space-to-depth input with Cp channels per phase (policy.hip::put_conv_s2): input row
-// 2*yo + (dy - 1) is phase 0 / same half-res row for dy = 1, phase 1 / previous row for dy = 0, phase 1 / same row for dy = 2
-void put_conv_s2(Eff& E, const WnConv& c, int cout, int cin, int Cp) {
-  const std::vector<float> w = wn_fold(c, cout, (size_t)cin * 9);
-  for (int co = 0; co < cout; ++co) {
-    E.bias[co] = c.b[co];
-    for (int ci = 0; ci < cin; ++ci)
-      for (int dy = 0; dy < 3; ++dy)
-        for (int dx = 0; dx < 3; ++dx) {
-          const int py = (dy == 1) ? 0 : 1, ty = (dy == 0) ? 0 : 1;
-          const int px = (dx == 1) ? 0 : 1, tx = (dx == 0) ? 0 : 1;
-          E.at(co, (py * 2 + px) * Cp + ci, ty * 3 + tx) = w[((size_t)co * cin + ci) * 9 + dy * 3 + dx];
-        }
-  }
-}
-// 1x1 stride-2 conv = centre tap over the phase-(0,0) channels
-void put_shortcut(Eff& E, const WnConv& c, int cout, int cin) {
-  const std::vector<float> w = wn_fold(c, cout, (size_t)cin);
-  for (int co = 0; co < cout; ++co) {
-    E.bias[co] = c.b[co];
-    for (int ci = 0; ci < cin; ++ci) E.at(co, ci, 4) = w[(size_t)co * cin + ci];
-  }
-}
 // adjoint with respect to the input: channels transposed, taps mirrored (tap t -> 8 - t), no bias
 Eff adjoint(const Eff& E) {
   Eff A(E.K, E.cout);
@@ -238,40 +156,7 @@ Eff adjoint(const Eff& E) {
   return A;
 }
 
-struct HostBlob {
-  std::vector<float> f;
-  void align() { f.resize((f.size() + 255) & ~(size_t)255, 0.f); }
-  size_t add(const float* p, size_t n) {
-    align();
-    const size_t off = f.size();
-    f.insert(f.end(), p, p + n);
-    return off;
-  }
-};
-struct Packed {
-  size_t w = 0, b = 0;
-  float scale = 1.f;
-  int cin = 0, cout = 0, mt = 0;
-};
-Packed pack_layer(HostBlob& H, const Eff& E, int tapmask, bool with_bias) {
-  Packed P;
-  int nt = 0;
-  for (int t = 0; t < 9; ++t) nt += (tapmask >> t) & 1;
-  H.align();
-  P.w = H.f.size();
-  const size_t n16 = (size_t)E.cout * E.K * nt * 2;
-  H.f.resize(H.f.size() + (n16 + 1) / 2, 0.f);
-  P.mt = (E.cout % 64 == 0) ? 64 : 32;
-  P.scale = pack_conv_weights_hs_taps(E.w.data(), E.cout, E.K, P.mt, tapmask, reinterpret_cast<uint16_t*>(H.f.data() + P.w));
-  if (with_bias) P.b = H.add(E.bias.data(), E.bias.size());
-  P.cin = E.K;
-  P.cout = E.cout;
-  return P;
-}
-
-constexpr int NL = 21;
-inline int fwd_taps(int li) { return li == 0 ? 0x01B : ((li - 1) % 5 == 0 ? 0x01B : ((li - 1) % 5 == 1 ? 0x010 : 0x1FF)); }
-inline int bwd_taps(int li) { return li == 0 ? 0x1B0 : ((li - 1) % 5 == 0 ? 0x1B0 : ((li - 1) % 5 == 1 ? 0x010 : 0x1FF)); }
+constexpr int NL = TRUNK_LAYERS;   // layer index: resnet18_hs.h
 
 // ------------------------------------------------------------------------------------------- device-side packing
 // The same weight blob from a parameter vector in DEVICE memory, bit for bit (header comment, "Live weights").  One table
@@ -324,7 +209,8 @@ bool make_layout(int num_inputs, CriticLayout& L) {
     unsigned b, g, v;
     int cout, cin, ks;
   };
-  auto take_wn = [&](int cout, int cin, int ks) {
+  // the next convolution of the parameter vector = layer li (registration order is the layer numbering)
+  auto take_wn = [&](int li, int cout, int cin, int ks) {
     Src c;
     c.b = take(cout);
     c.g = take(cout);
@@ -332,25 +218,28 @@ bool make_layout(int num_inputs, CriticLayout& L) {
     c.cout = cout;
     c.cin = cin;
     c.ks = ks;
-    return c;
-  };
-  auto finish = [&](int li, const Src& c, int kind, int Cp, int K) {
     FoldDesc& F = L.T.fold[li];
     F.src_g = c.g;
     F.src_v = c.v;
     F.chan0 = chan;
-    F.cout = c.cout;
-    F.fan = c.cin * c.ks;
+    F.cout = cout;
+    F.fan = cin * ks;
     F.alpha_src = -1;
+    chan += cout;
+    return c;
+  };
+  // its two packings and its bias, the next entries of the blob (critic_load's order: the shortcut before conv2)
+  auto finish = [&](int li, const Src& c, int kind, int Cp, int K) {
+    const unsigned chan0 = L.T.fold[li].chan0;
     for (int adj = 0; adj < 2; ++adj) {
       PackDesc& P = L.T.pack[2 * li + adj];
       P.src_v = c.v;
-      P.chan0 = chan;
+      P.chan0 = chan0;
       P.conv = li;
       P.rows = adj ? K : c.cout;
       P.K = adj ? c.cout : K;
       P.mt = (P.rows % 64 == 0) ? 64 : 32;
-      const int mask = adj ? bwd_taps(li) : fwd_taps(li);
+      const int mask = trunk_taps(li, adj != 0);
       for (int t = 0; t < 9; ++t)
         if ((mask >> t) & 1) P.tap[P.nt++] = t;
       P.kind = kind;
@@ -363,33 +252,33 @@ bool make_layout(int num_inputs, CriticLayout& L) {
       if (P.items > L.max_items) L.max_items = P.items;
       if (!adj) {
         L.bias[li] = put(c.cout);
-        L.T.copy[ncopy++] = CopyDesc{c.b, (unsigned)L.bias[li], (unsigned)c.cout};
+        L.T.copy[li] = CopyDesc{c.b, (unsigned)L.bias[li], (unsigned)c.cout};   // copy[li]: the bias of layer li
+        ++ncopy;
       }
     }
-    chan += c.cout;
   };
-  finish(0, take_wn(64, num_inputs, 9), 1, cin_pad, 4 * cin_pad);
+  finish(0, take_wn(0, 64, num_inputs, 9), 1, cin_pad, 4 * cin_pad);
   int in_planes = 64;
   for (int s = 0; s < 4; ++s) {
     const int p = stage_planes(s), l0 = 1 + 5 * s;
-    const Src c1 = take_wn(p, in_planes, 9), c2 = take_wn(p, p, 9), cs = take_wn(p, in_planes, 1);
-    const unsigned a0 = take(1), a2 = take(1);
+    const Src c1 = take_wn(l0 + 0, p, in_planes, 9), c2 = take_wn(l0 + 1, p, p, 9), cs = take_wn(l0 + 2, p, in_planes, 1);
+    const unsigned a0 = take(1), a1 = take(1);
     finish(l0 + 0, c1, 1, in_planes, 4 * in_planes);
-    finish(l0 + 1, cs, 2, 0, in_planes);
-    finish(l0 + 2, c2, 0, 0, p);
-    const Src d1 = take_wn(p, p, 9), d2 = take_wn(p, p, 9);
+    finish(l0 + 2, cs, 2, 0, in_planes);
+    finish(l0 + 1, c2, 0, 0, p);
+    const Src d1 = take_wn(l0 + 3, p, p, 9), d2 = take_wn(l0 + 4, p, p, 9);
     const unsigned a3 = take(1), a4 = take(1);
     finish(l0 + 3, d1, 0, 0, p);
     finish(l0 + 4, d2, 0, 0, p);
     L.T.fold[l0 + 0].alpha_src = (int)a0;
-    L.T.fold[l0 + 2].alpha_src = (int)a2;
+    L.T.fold[l0 + 1].alpha_src = (int)a1;
     L.T.fold[l0 + 3].alpha_src = (int)a3;
     L.T.fold[l0 + 4].alpha_src = (int)a4;
     in_planes = p;
   }
   L.T.src_fcw = take(512);
   L.fcw = put(512);
-  L.T.copy[ncopy++] = CopyDesc{L.T.src_fcw, (unsigned)L.fcw, 512u};
+  L.T.copy[ncopy++] = CopyDesc{L.T.src_fcw, (unsigned)L.fcw, 512u};   // (ncopy == NL here: behind the 21 biases)
   L.fcb = put(1);
   L.T.copy[ncopy++] = CopyDesc{take(1), (unsigned)L.fcb, 1u};
   L.T.fold[0].alpha_src = (int)take(1);
@@ -515,46 +404,40 @@ __global__ __launch_bounds__(256) void critic_soft_update_kernel(float* __restri
 }
 
 // ------------------------------------------------------------------------------------------- activation plan
-struct CAct {
-  size_t off = 0;   // floats; an HS8 tensor [C/8][H+2][W+2] of 32-byte records takes C*(H+2)*(W+2) floats per image
-  int C = 0, H = 0, W = 0;
-};
 struct CriticPlan {
-  // forward (all kept: the backward pass reads them as masks)
-  CAct ob_s, stem_o, stem_s;                  // space-to-depth observation; stem output (64, H/2); its space-to-depth copy
-  CAct t1[4], sc[4], o0[4], t2[4], o1[4];
-  CAct o1s[3];                                // space-to-depth copy of o1 (next stage's entry)
+  TrunkPlan T;                                // forward (all kept: the backward pass reads them as masks)
   // gradients with respect to pre-activations, scaled (header comment)
-  CAct gA[4], gB[4], gM[4];                   // planes x h x w: of o1, of o0, of t1 / t2
-  CAct gR[4], gS[4];                          // shortcut adjoint (in_planes x h x w), entry adjoint (4*in_planes x h x w)
-  CAct g_stem, g_ob;                          // of the stem output (64, H/2); of the space-to-depth observation
+  TrunkAct gA[4], gB[4], gM[4];                  // planes x h x w: of o1, of o0, of t1 / t2
+  TrunkAct gR[4], gS[4];                         // shortcut adjoint (in_planes x h x w), entry adjoint (4*in_planes x h x w)
+  TrunkAct g_stem, g_ob;                         // of the stem output (64, H/2); of the space-to-depth observation
   size_t total = 0;
 };
 CriticPlan make_plan(int capB, int cin_pad, int H, int W) {
   CriticPlan P;
+  TrunkPlan& T = P.T;
   size_t off = 0;
-  auto add = [&](CAct& d, int C, int h, int w) {
+  auto add = [&](TrunkAct& d, int C, int h, int w) {
     d.off = off;
     d.C = C;
     d.H = h;
     d.W = w;
-    off += (size_t)C * (h + 2) * (w + 2) * capB;
+    off += hs_act_floats(C, h, w) * capB;
     off = (off + 63) & ~(size_t)63;
   };
-  add(P.ob_s, 4 * cin_pad, H / 2, W / 2);
-  add(P.stem_o, 64, H / 2, W / 2);
-  add(P.stem_s, 4 * 64, H / 4, W / 4);
+  add(T.ob_s, 4 * cin_pad, H / 2, W / 2);
+  add(T.stem_o, 64, H / 2, W / 2);
+  add(T.stem_s, 4 * 64, H / 4, W / 4);
   add(P.g_stem, 64, H / 2, W / 2);
   add(P.g_ob, 4 * cin_pad, H / 2, W / 2);
   int in_planes = 64;
   for (int n = 0; n < 4; ++n) {
     const int p = stage_planes(n), h = H >> (n + 2), w = W >> (n + 2);
-    add(P.t1[n], p, h, w);
-    add(P.sc[n], p, h, w);
-    add(P.o0[n], p, h, w);
-    add(P.t2[n], p, h, w);
-    add(P.o1[n], p, h, w);
-    if (n < 3) add(P.o1s[n], 4 * p, h / 2, w / 2);
+    add(T.t1[n], p, h, w);
+    add(T.sc[n], p, h, w);
+    add(T.o0[n], p, h, w);
+    add(T.t2[n], p, h, w);
+    add(T.o1[n], p, h, w);
+    if (n < 3) add(T.o1s[n], 4 * p, h / 2, w / 2);
     add(P.gA[n], p, h, w);
     add(P.gB[n], p, h, w);
     add(P.gM[n], p, h, w);
@@ -578,122 +461,34 @@ int check_call(const CriticNet& N, const char* who, int B, int H, int W) {
   return PNPX_OK;
 }
 
-// arena for B observations of H x W (grows to the largest batch seen at one size; zero borders written once)
 int reserve(CriticNet& N, int B, int H, int W) {
-  if (B <= N.capB && H == N.capH && W == N.capW) return PNPX_OK;
-  const bool same = (H == N.capH && W == N.capW);
-  const int nb = same ? (B > N.capB ? B : N.capB) : B;
-  const CriticPlan P = make_plan(nb, N.cin_pad, H, W);
-  PNPX_HIP(hipDeviceSynchronize());
-  if (N.arena.bytes < P.total * sizeof(float)) {
-    if (N.arena.p) PNPX_HIP(hipFree(N.arena.p));
-    N.arena = DeviceBuf();
-    N.capB = N.capH = N.capW = 0;
-    void* p = nullptr;
-    hipError_t e = hipMalloc(&p, P.total * sizeof(float));
-    if (e != hipSuccess) {
-      set_error("critic arena allocation of %zu bytes failed: %s", P.total * sizeof(float), hipGetErrorString(e));
-      return PNPX_ERR_ALLOC;
-    }
-    N.arena.p = p;
-    N.arena.bytes = P.total * sizeof(float);
-  }
-  PNPX_HIP(hipMemset(N.arena.p, 0, P.total * sizeof(float)));
-  PNPX_HIP(hipDeviceSynchronize());
-  N.capB = nb;
-  N.capH = H;
-  N.capW = W;
-  return PNPX_OK;
+  return reserve_arena_hs(N.arena, N.capB, N.capH, N.capW, B, H, W, [&](int nb) { return make_plan(nb, N.cin_pad, H, W).total; },
+                          "critic arena");
 }
 
-struct Launch {   // one convolution launch of either pass
-  const ConvLayerHsDev* D = nullptr;
-  const float* bias = nullptr;
-  int taps = 0x1FF;
-  int epi = 0;            // ConvHsFuse::critic_epi (0: the plain linear instance)
-  float alpha = 0.f;
-  const CAct* res = nullptr;
-  const CAct* mask = nullptr;
-};
-// (tensors by address: the parameter-gradient pass keeps two of its own outside the arena)
-int run_conv_ptr(pnpx_ctx* ctx, const Launch& L, const char* in, int inC, char* out, int outC, const char* res, int resC, const char* mask,
-                 int maskC, int B, int h, int w, hipStream_t s) {
-  ConvLayerHs Lh;
-  Lh.cin = L.D->cin;
-  Lh.cout = L.D->cout;
-  Lh.cin_pad = L.D->cin_pad;
-  Lh.mt = L.D->mt;
-  Lh.w = L.D->w;
-  Lh.b = L.bias;
-  Lh.inv_scale = L.D->inv_scale;
-  ConvHsFuse f;
-  f.slope = 1.f;           // (read by the plain instance only: linear)
-  f.taps = L.taps;
-  f.wreg = 0;
-  f.in0_groups = inC / 8;
-  f.critic_epi = L.epi;
-  f.alpha = L.alpha;
-  f.res = res;
-  f.res_groups = res ? resC / 8 : 0;
-  f.dmask = mask;
-  f.range_flag = ctx->opt_range_guard ? ctx->range_flag_dev : nullptr;
-  if (L.D->cout != outC || L.D->cin_pad > inC || (mask && maskC != outC) || (res && resC > outC)) {
-    set_error("critic: internal launch geometry mismatch (%d -> %d channels over %d -> %d)", L.D->cin_pad, L.D->cout, inC, outC);
-    return PNPX_ERR_SHAPE;
-  }
-  return launch_conv_hs(Lh, in, L.D->cin_pad / 8, nullptr, 0, out, B, h, w, f, s);
+// one launch of the adjoint chain (or a plain forward instance): layer D, tap mask, epilogue
+HsLaunch chain_launch(pnpx_ctx* ctx, const ConvLayerHsDev& D, const float* bias, int taps, int epi, float alpha) {
+  HsLaunch L;
+  L.D = &D;
+  L.bias = bias;
+  L.taps = taps;
+  L.epi = epi;
+  L.alpha = alpha;
+  L.range_flag = ctx->opt_range_guard ? ctx->range_flag_dev : nullptr;
+  return L;
 }
-int run_conv(pnpx_ctx* ctx, float* A, const Launch& L, const CAct& in, const CAct& out, int B, int h, int w, hipStream_t s) {
-  return run_conv_ptr(ctx, L, reinterpret_cast<const char*>(A + in.off), in.C, reinterpret_cast<char*>(A + out.off), out.C,
-                      L.res ? reinterpret_cast<const char*>(A + L.res->off) : nullptr, L.res ? L.res->C : 0,
-                      L.mask ? reinterpret_cast<const char*>(A + L.mask->off) : nullptr, L.mask ? L.mask->C : 0, B, h, w, s);
+int run_conv(float* A, const HsLaunch& L, const TrunkAct& in, const TrunkAct& out, const TrunkAct* res, const TrunkAct* mask, int B, int h, int w,
+             hipStream_t s) {
+  return launch_hs_conv(L, reinterpret_cast<const char*>(A + in.off), in.C, reinterpret_cast<char*>(A + out.off), out.C,
+                        res ? reinterpret_cast<const char*>(A + res->off) : nullptr, res ? res->C : 0,
+                        mask ? reinterpret_cast<const char*>(A + mask->off) : nullptr, mask ? mask->C : 0, B, h, w, s);
 }
 
 // forward over B observations; every activation stays in the arena
 int run_forward(pnpx_ctx* ctx, const CriticPlan& P, const float* ob, int B, int H, int W, hipStream_t s) {
   CriticNet& N = ctx->critic;
-  float* A = static_cast<float*>(N.arena.p);
-  auto rec = [&](const CAct& d) { return reinterpret_cast<HsRec*>(A + d.off); };
-  auto u4 = [&](const CAct& d) { return reinterpret_cast<uint4*>(A + d.off); };
-  auto trelu = [&](int li, const CAct& in, const CAct& out, const CAct* res, int h, int w) -> int {
-    Launch L;
-    L.D = &N.fwd[li];
-    L.bias = N.bias[li];
-    L.taps = fwd_taps(li);
-    L.epi = 1;
-    L.alpha = N.alpha[li];
-    L.res = res;
-    return run_conv(ctx, A, L, in, out, B, h, w, s);
-  };
-  const size_t n = (size_t)B * 4 * (N.cin_pad / 8) * (H / 2) * (W / 2);
-  hipLaunchKernelGGL(critic_pack_ob_kernel, g1(n), dim3(256), 0, s, ob, rec(P.ob_s), N.num_inputs, N.cin_pad, H, W, n);
-  PNPX_LAUNCH_CHECK();
-  PNPX_TRY(trelu(0, P.ob_s, P.stem_o, nullptr, H / 2, W / 2));
-  const size_t n2 = (size_t)B * 4 * 8 * (H / 4) * (W / 4) * 2;
-  hipLaunchKernelGGL(hs_s2d_kernel, g1(n2), dim3(256), 0, s, u4(P.stem_o), u4(P.stem_s), 8, H / 2, W / 2, n2);
-  PNPX_LAUNCH_CHECK();
-  for (int st = 0; st < 4; ++st) {
-    const int h = H >> (st + 2), w = W >> (st + 2), l0 = 1 + 5 * st;
-    const CAct& s2in = st == 0 ? P.stem_s : P.o1s[st - 1];
-    PNPX_TRY(trelu(l0 + 0, s2in, P.t1[st], nullptr, h, w));
-    {   // shortcut: 1x1 over the phase-(0,0) channels, bias, no activation (the actor's instance)
-      Launch L;
-      L.D = &N.fwd[l0 + 1];
-      L.bias = N.bias[l0 + 1];
-      L.taps = 0x010;
-      PNPX_TRY(run_conv(ctx, A, L, s2in, P.sc[st], B, h, w, s));
-    }
-    PNPX_TRY(trelu(l0 + 2, P.t1[st], P.o0[st], &P.sc[st], h, w));
-    PNPX_TRY(trelu(l0 + 3, P.o0[st], P.t2[st], nullptr, h, w));
-    PNPX_TRY(trelu(l0 + 4, P.t2[st], P.o1[st], &P.o0[st], h, w));
-    if (st < 3) {
-      const int G = P.o1[st].C / 8;
-      const size_t n3 = (size_t)B * 4 * G * (h / 2) * (w / 2) * 2;
-      hipLaunchKernelGGL(hs_s2d_kernel, g1(n3), dim3(256), 0, s, u4(P.o1[st]), u4(P.o1s[st]), G, h, w, n3);
-      PNPX_LAUNCH_CHECK();
-    }
-  }
-  return PNPX_OK;
+  return trunk_forward(N.fwd, N.bias, P.T, static_cast<float*>(N.arena.p), 0, ob, N.num_inputs, N.cin_pad, B, H, W, 1, 1, N.alpha,
+                       ctx->opt_range_guard ? ctx->range_flag_dev : nullptr, s);
 }
 
 }  // namespace
@@ -726,22 +521,10 @@ void critic_free(pnpx_ctx* ctx) {
 
 namespace {
 
-int alloc_dev(DeviceBuf& b, size_t bytes, const char* what) {
-  void* p = nullptr;
-  hipError_t e = hipMalloc(&p, bytes);
-  if (e != hipSuccess) {
-    set_error("critic %s allocation of %zu bytes failed: %s", what, bytes, hipGetErrorString(e));
-    return PNPX_ERR_ALLOC;
-  }
-  b.p = p;
-  b.bytes = bytes;
-  return PNPX_OK;
-}
-
 // the parameter vector on the device, the layer table and the read-back block (at a load that allocates)
 int alloc_live_state(CriticNet& N, const CriticLayout& L, size_t n) {
-  PNPX_TRY(alloc_dev(N.master, n * sizeof(float), "parameter"));
-  PNPX_TRY(alloc_dev(N.pack_ws, pack_ws_bytes(L.T.nchan), "packing workspace"));
+  PNPX_TRY(alloc_dev(N.master, n * sizeof(float), "critic parameter"));
+  PNPX_TRY(alloc_dev(N.pack_ws, pack_ws_bytes(L.T.nchan), "critic packing workspace"));
   void* h = nullptr;
   PNPX_HIP(hipHostMalloc(&h, 64 * sizeof(float), hipHostMallocDefault));
   N.readback = static_cast<float*>(h);
@@ -819,7 +602,7 @@ int critic_load_device(pnpx_ctx* ctx, const float* params_dev, size_t n, int num
     critic_free(ctx);
     N.num_inputs = num_inputs;
     N.cin_pad = (num_inputs + 7) / 8 * 8;
-    int st = alloc_dev(N.weights, L.total * sizeof(float), "weight");
+    int st = alloc_dev(N.weights, L.total * sizeof(float), "critic weight");
     if (st == PNPX_OK) st = alloc_live_state(N, L, n);
     if (st == PNPX_OK && hipMemset(N.weights.p, 0, N.weights.bytes) != hipSuccess) st = PNPX_ERR_HIP;   // padding and the zero block
     if (st == PNPX_OK && hipDeviceSynchronize() != hipSuccess) st = PNPX_ERR_HIP;
@@ -893,13 +676,18 @@ int critic_load(pnpx_ctx* ctx, const float* params, size_t n, int num_inputs) {
   Packed pf[NL], pb[NL];
   float alpha[NL] = {};
   auto finish = [&](int li, const Eff& E) {
-    pf[li] = pack_layer(H, E, fwd_taps(li), true);
-    pb[li] = pack_layer(H, adjoint(E), bwd_taps(li), false);
+    pf[li] = pack_layer(H, E, trunk_taps(li, false), true);
+    pb[li] = pack_layer(H, adjoint(E), trunk_taps(li, true), false);
+  };
+  auto conv_s1 = [&](int li, const WnConv& c, int p) {
+    Eff E(p, p);
+    put_conv_s1(E, 0, wn_fold(c, p, (size_t)p * 9).data(), c.b, p, p);
+    finish(li, E);
   };
   {
     const WnConv c = take_wn(64, (size_t)num_inputs * 9);
     Eff E(64, 4 * N.cin_pad);
-    put_conv_s2(E, c, 64, num_inputs, N.cin_pad);
+    put_conv_s2(E, 0, wn_fold(c, 64, (size_t)num_inputs * 9).data(), c.b, 64, num_inputs, N.cin_pad);
     finish(0, E);
   }
   int in_planes = 64;
@@ -910,37 +698,25 @@ int critic_load(pnpx_ctx* ctx, const float* params, size_t n, int num_inputs) {
     const WnConv c2 = take_wn(p, (size_t)p * 9);
     const WnConv cs = take_wn(p, (size_t)in_planes);
     alpha[l0 + 0] = *R.take(1);
-    alpha[l0 + 2] = *R.take(1);
+    alpha[l0 + 1] = *R.take(1);
     {
       Eff E(p, 4 * in_planes);
-      put_conv_s2(E, c1, p, in_planes, in_planes);
+      put_conv_s2(E, 0, wn_fold(c1, p, (size_t)in_planes * 9).data(), c1.b, p, in_planes, in_planes);
       finish(l0 + 0, E);
     }
-    {
+    {   // (the blob keeps the shortcut in front of conv2)
       Eff E(p, in_planes);
-      put_shortcut(E, cs, p, in_planes);
-      finish(l0 + 1, E);
-    }
-    {
-      Eff E(p, p);
-      put_conv_s1(E, c2, p, p);
+      put_shortcut(E, 0, wn_fold(cs, p, (size_t)in_planes).data(), cs.b, p, in_planes);
       finish(l0 + 2, E);
     }
+    conv_s1(l0 + 1, c2, p);
     // block 1: conv1, conv2, relu_1.alpha, relu_2.alpha
     const WnConv d1 = take_wn(p, (size_t)p * 9);
     const WnConv d2 = take_wn(p, (size_t)p * 9);
     alpha[l0 + 3] = *R.take(1);
     alpha[l0 + 4] = *R.take(1);
-    {
-      Eff E(p, p);
-      put_conv_s1(E, d1, p, p);
-      finish(l0 + 3, E);
-    }
-    {
-      Eff E(p, p);
-      put_conv_s1(E, d2, p, p);
-      finish(l0 + 4, E);
-    }
+    conv_s1(l0 + 3, d1, p);
+    conv_s1(l0 + 4, d2, p);
     in_planes = p;
   }
   const float* fcw = R.take(512);
@@ -959,26 +735,12 @@ int critic_load(pnpx_ctx* ctx, const float* params, size_t n, int num_inputs) {
   const size_t o_zero = H.f.size();
   H.f.resize(H.f.size() + 1024, 0.f);
   H.f.resize(H.f.size() + 8192, 0.f);   // DMA over-read slack
-  void* d = nullptr;
-  hipError_t e = hipMalloc(&d, H.f.size() * sizeof(float));
-  if (e != hipSuccess) {
-    set_error("critic weight allocation of %zu bytes failed: %s", H.f.size() * sizeof(float), hipGetErrorString(e));
-    return PNPX_ERR_ALLOC;
-  }
-  N.weights.p = d;
-  N.weights.bytes = H.f.size() * sizeof(float);
-  PNPX_HIP(hipMemcpy(d, H.f.data(), N.weights.bytes, hipMemcpyHostToDevice));
-  const float* base = static_cast<const float*>(d);
-  auto dev = [&](ConvLayerHsDev& D, const Packed& P) {
-    D.cin = D.cin_pad = P.cin;
-    D.cout = P.cout;
-    D.mt = P.mt;
-    D.w = const_cast<char*>(reinterpret_cast<const char*>(base + P.w));
-    D.inv_scale = 1.0f / (P.scale * HS_ASCALE);
-  };
+  PNPX_TRY(alloc_dev(N.weights, H.f.size() * sizeof(float), "critic weight"));
+  PNPX_HIP(hipMemcpy(N.weights.p, H.f.data(), N.weights.bytes, hipMemcpyHostToDevice));
+  const float* base = static_cast<const float*>(N.weights.p);
   for (int i = 0; i < NL; ++i) {
-    dev(N.fwd[i], pf[i]);
-    dev(N.bwd[i], pb[i]);
+    bind_packed(N.fwd[i], pf[i], base);
+    bind_packed(N.bwd[i], pb[i], base);
     N.bias[i] = base + pf[i].b;
     N.alpha[i] = alpha[i];
   }
@@ -1018,7 +780,7 @@ int critic_forward(pnpx_ctx* ctx, const float* ob, float* value, int B, int H, i
   const CriticPlan P = make_plan(N.capB, N.cin_pad, H, W);
   PNPX_TRY(run_forward(ctx, P, ob, B, H, W, s));
   const float* A = static_cast<const float*>(N.arena.p);
-  hipLaunchKernelGGL(critic_pool_fc_kernel, dim3(B), dim3(256), 0, s, reinterpret_cast<const HsRec*>(A + P.o1[3].off), H / 32, W / 32,
+  hipLaunchKernelGGL(critic_pool_fc_kernel, dim3(B), dim3(256), 0, s, reinterpret_cast<const HsRec*>(A + P.T.o1[3].off), H / 32, W / 32,
                      N.fc_w, N.fc_b, value);
   PNPX_LAUNCH_CHECK();
   return PNPX_OK;
@@ -1052,22 +814,15 @@ inline float grad_scale(const CriticNet& N, int hl, int wl) {
 int run_chain(pnpx_ctx* ctx, const CriticPlan& P, float gs, int B, int H, int W, hipStream_t s, const GradJob* J) {
   CriticNet& N = ctx->critic;
   float* A = static_cast<float*>(N.arena.p);
-  auto rec = [&](const CAct& d) { return reinterpret_cast<HsRec*>(A + d.off); };
-  auto u4 = [&](const CAct& d) { return reinterpret_cast<uint4*>(A + d.off); };
+  auto rec = [&](const TrunkAct& d) { return reinterpret_cast<HsRec*>(A + d.off); };
+  auto u4 = [&](const TrunkAct& d) { return reinterpret_cast<uint4*>(A + d.off); };
   // (W^T g [+ res]) masked by the saved activation `mask` against the threshold of layer `mask_li`
-  auto grad = [&](int li, const CAct& in, const CAct& out, const CAct* res, const CAct* mask, int mask_li, int h, int w) -> int {
-    Launch L;
-    L.D = &N.bwd[li];
-    L.bias = N.zero;
-    L.taps = bwd_taps(li);
-    L.epi = 2;
-    L.alpha = mask ? N.alpha[mask_li] : 0.f;
-    L.res = res;
-    L.mask = mask;
-    return run_conv(ctx, A, L, in, out, B, h, w, s);
+  auto grad = [&](int li, const TrunkAct& in, const TrunkAct& out, const TrunkAct* res, const TrunkAct* mask, int mask_li, int h, int w) -> int {
+    return run_conv(A, chain_launch(ctx, N.bwd[li], N.zero, trunk_taps(li, true), 2, mask ? N.alpha[mask_li] : 0.f), in, out, res, mask, B, h,
+                    w, s);
   };
   // gradient of convolution li: G = gradient with respect to its output, X = the tensor its forward launch read
-  auto wgrad = [&](int li, const CAct& G, const CAct& X, int h, int w) -> int {
+  auto wgrad = [&](int li, const TrunkAct& G, const TrunkAct& X, int h, int w) -> int {
     if (!J) return PNPX_OK;
     const PackDesc& D = J->L->T.pack[2 * li];
     WgradJob Wj;
@@ -1096,57 +851,50 @@ int run_chain(pnpx_ctx* ctx, const CriticPlan& P, float gs, int B, int H, int W,
   };
   // threshold ali of the saved activation `act`, read by forward convolution cli whose output gradient is g; res: what the chain
   // adds to W^T g before the mask
-  auto athr = [&](int ali, int cli, const CAct& act, const CAct& g, const CAct* res, int h, int w) -> int {
+  auto athr = [&](int ali, int cli, const TrunkAct& act, const TrunkAct& g, const TrunkAct* res, int h, int w) -> int {
     if (!J) return PNPX_OK;
     PNPX_TRY(launch_critic_clip_mask(rec(act), J->m, hs_roundtrip16(N.alpha[ali]), B, act.C / 8, h, w, s));
-    Launch L;   // the plain linear instance, no bias
-    L.D = &N.fwd[cli];
-    L.bias = N.zero;
-    L.taps = fwd_taps(cli);
-    PNPX_TRY(run_conv_ptr(ctx, L, reinterpret_cast<const char*>(J->m), act.C, reinterpret_cast<char*>(J->wm), g.C, nullptr, 0, nullptr, 0, B,
-                          h, w, s));
+    // the plain linear instance, no bias (the two tensors live outside the arena)
+    PNPX_TRY(launch_hs_conv(chain_launch(ctx, N.fwd[cli], N.zero, trunk_taps(cli, false), 0, 0.f), reinterpret_cast<const char*>(J->m), act.C,
+                            reinterpret_cast<char*>(J->wm), g.C, nullptr, 0, nullptr, 0, B, h, w, s));
     return launch_critic_alpha_dot(rec(g), J->wm, g.C / 8, res ? rec(*res) : nullptr, res ? res->C / 8 : 0, J->m, act.C / 8, B, h, w,
                                    J->dots + (size_t)ali * B, s);
   };
   const int hl = H / 32, wl = W / 32;
   {
     const size_t n = (size_t)B * 64 * hl * wl;
-    hipLaunchKernelGGL(critic_head_grad_kernel, g1(n), dim3(256), 0, s, rec(P.o1[3]), rec(P.gA[3]), N.fc_w, hs_roundtrip16(N.alpha[20]),
+    hipLaunchKernelGGL(critic_head_grad_kernel, g1(n), dim3(256), 0, s, rec(P.T.o1[3]), rec(P.gA[3]), N.fc_w, hs_roundtrip16(N.alpha[20]),
                        gs * HS_ASCALE / (float)(hl * wl), hl, wl, n);
     PNPX_LAUNCH_CHECK();
   }
   for (int st = 3; st >= 0; --st) {
     const int h = H >> (st + 2), w = W >> (st + 2), l0 = 1 + 5 * st;
     // block 1: o1 = TReLU(conv2(t2) + o0), t2 = TReLU(conv1(o0))
-    PNPX_TRY(wgrad(l0 + 4, P.gA[st], P.t2[st], h, w));
-    PNPX_TRY(athr(l0 + 3, l0 + 4, P.t2[st], P.gA[st], nullptr, h, w));
-    PNPX_TRY(grad(l0 + 4, P.gA[st], P.gM[st], nullptr, &P.t2[st], l0 + 3, h, w));
-    PNPX_TRY(wgrad(l0 + 3, P.gM[st], P.o0[st], h, w));
-    PNPX_TRY(athr(l0 + 2, l0 + 3, P.o0[st], P.gM[st], &P.gA[st], h, w));
-    PNPX_TRY(grad(l0 + 3, P.gM[st], P.gB[st], &P.gA[st], &P.o0[st], l0 + 2, h, w));
+    PNPX_TRY(wgrad(l0 + 4, P.gA[st], P.T.t2[st], h, w));
+    PNPX_TRY(athr(l0 + 3, l0 + 4, P.T.t2[st], P.gA[st], nullptr, h, w));
+    PNPX_TRY(grad(l0 + 4, P.gA[st], P.gM[st], nullptr, &P.T.t2[st], l0 + 3, h, w));
+    PNPX_TRY(wgrad(l0 + 3, P.gM[st], P.T.o0[st], h, w));
+    PNPX_TRY(athr(l0 + 1, l0 + 3, P.T.o0[st], P.gM[st], &P.gA[st], h, w));
+    PNPX_TRY(grad(l0 + 3, P.gM[st], P.gB[st], &P.gA[st], &P.T.o0[st], l0 + 1, h, w));
     // block 0: o0 = TReLU(conv2(t1) + shortcut(x)), t1 = TReLU(conv1(x)), x = space-to-depth input
-    const CAct& x = st == 0 ? P.stem_s : P.o1s[st - 1];
-    PNPX_TRY(wgrad(l0 + 2, P.gB[st], P.t1[st], h, w));
-    PNPX_TRY(wgrad(l0 + 1, P.gB[st], x, h, w));
-    PNPX_TRY(athr(l0 + 0, l0 + 2, P.t1[st], P.gB[st], nullptr, h, w));
-    PNPX_TRY(grad(l0 + 2, P.gB[st], P.gM[st], nullptr, &P.t1[st], l0 + 0, h, w));
-    {   // shortcut adjoint: 1x1, linear (the existing sparse-tap instance), to the phase-(0,0) channel groups
-      Launch L;
-      L.D = &N.bwd[l0 + 1];
-      L.bias = N.zero;
-      L.taps = 0x010;
-      PNPX_TRY(run_conv(ctx, A, L, P.gB[st], P.gR[st], B, h, w, s));
-    }
+    const TrunkAct& x = st == 0 ? P.T.stem_s : P.T.o1s[st - 1];
+    PNPX_TRY(wgrad(l0 + 1, P.gB[st], P.T.t1[st], h, w));
+    PNPX_TRY(wgrad(l0 + 2, P.gB[st], x, h, w));
+    PNPX_TRY(athr(l0 + 0, l0 + 1, P.T.t1[st], P.gB[st], nullptr, h, w));
+    PNPX_TRY(grad(l0 + 1, P.gB[st], P.gM[st], nullptr, &P.T.t1[st], l0 + 0, h, w));
+    // shortcut adjoint: 1x1, linear (the existing sparse-tap instance), to the phase-(0,0) channel groups
+    PNPX_TRY(run_conv(A, chain_launch(ctx, N.bwd[l0 + 2], N.zero, trunk_taps(l0 + 2, true), 0, 0.f), P.gB[st], P.gR[st], nullptr, nullptr, B, h,
+                      w, s));
     PNPX_TRY(wgrad(l0 + 0, P.gM[st], x, h, w));
     PNPX_TRY(athr(st == 0 ? 0 : l0 - 1, l0 + 0, x, P.gM[st], &P.gR[st], h, w));
     PNPX_TRY(grad(l0 + 0, P.gM[st], P.gS[st], &P.gR[st], &x, st == 0 ? 0 : l0 - 1, h, w));
-    const CAct& below = st == 0 ? P.g_stem : P.gA[st - 1];
+    const TrunkAct& below = st == 0 ? P.g_stem : P.gA[st - 1];
     const int G = below.C / 8;
     const size_t n = (size_t)B * G * (2 * h) * (2 * w) * 2;
     hipLaunchKernelGGL(hs_d2s_kernel, g1(n), dim3(256), 0, s, u4(P.gS[st]), u4(below), G, h, w, n);
     PNPX_LAUNCH_CHECK();
   }
-  PNPX_TRY(wgrad(0, P.g_stem, P.ob_s, H / 2, W / 2));
+  PNPX_TRY(wgrad(0, P.g_stem, P.T.ob_s, H / 2, W / 2));
   return PNPX_OK;
 }
 
@@ -1159,17 +907,11 @@ int critic_backward(pnpx_ctx* ctx, const float* ob, const float* grad_value, flo
   const CriticPlan P = make_plan(N.capB, N.cin_pad, H, W);
   PNPX_TRY(run_forward(ctx, P, ob, B, H, W, s));   // re-computation: every activation is now in the arena
   float* A = static_cast<float*>(N.arena.p);
-  auto rec = [&](const CAct& d) { return reinterpret_cast<HsRec*>(A + d.off); };
+  auto rec = [&](const TrunkAct& d) { return reinterpret_cast<HsRec*>(A + d.off); };
   const float gs = grad_scale(N, H / 32, W / 32);
   PNPX_TRY(run_chain(ctx, P, gs, B, H, W, s, nullptr));
-  {   // stem adjoint: linear
-    Launch L;
-    L.D = &N.bwd[0];
-    L.bias = N.zero;
-    L.taps = bwd_taps(0);
-    L.epi = 2;
-    PNPX_TRY(run_conv(ctx, A, L, P.g_stem, P.g_ob, B, H / 2, W / 2, s));
-  }
+  // stem adjoint: linear
+  PNPX_TRY(run_conv(A, chain_launch(ctx, N.bwd[0], N.zero, trunk_taps(0, true), 2, 0.f), P.g_stem, P.g_ob, nullptr, nullptr, B, H / 2, W / 2, s));
   const size_t n = (size_t)B * N.num_inputs * H * W;
   hipLaunchKernelGGL(critic_ob_grad_kernel, g1(n), dim3(256), 0, s, rec(P.g_ob), grad_value, grad_ob, N.num_inputs, N.cin_pad, H, W,
                      1.0f / (gs * HS_ASCALE), n);
@@ -1238,18 +980,18 @@ int param_grad_run(pnpx_ctx* ctx, const char* entry, const char* who, const floa
     in_planes = p;
   }
   const size_t slack = (size_t)1 << 20;   // bytes: overhanging tiles read past their tensor (the arena's slack)
-  PNPX_TRY(grow(N.grad_m, m_floats * sizeof(float) + slack, true, "gradient mask"));
-  PNPX_TRY(grow(N.grad_wm, wm_floats * sizeof(float) + slack, true, "gradient mask convolution"));
+  PNPX_TRY(grow(N.grad_m, m_floats * sizeof(float) + slack, true, "critic gradient mask"));
+  PNPX_TRY(grow(N.grad_wm, wm_floats * sizeof(float) + slack, true, "critic gradient mask convolution"));
   const size_t slab_bytes = (slab_floats * sizeof(float) + 255) & ~(size_t)255;
   const size_t red_bytes = ((size_t)NL * B + 512) * sizeof(double);   // the reduction blocks; behind them grad_value of the loss entry
-  PNPX_TRY(grow(N.grad_slab, slab_bytes + red_bytes + (size_t)B * sizeof(float), false, "gradient slab"));
+  PNPX_TRY(grow(N.grad_slab, slab_bytes + red_bytes + (size_t)B * sizeof(float), false, "critic gradient slab"));
 
   PNPX_TRY(run_forward(ctx, P, ob, B, H, W, s));   // re-computation: every activation is now in the arena
   const int hl = H / 32, wl = W / 32;
   const float* A = static_cast<const float*>(N.arena.p);
   if (q_target) {
     float* gv = reinterpret_cast<float*>(static_cast<char*>(N.grad_slab.p) + slab_bytes + red_bytes);
-    hipLaunchKernelGGL(critic_pool_fc_kernel, dim3(B), dim3(256), 0, s, reinterpret_cast<const HsRec*>(A + P.o1[3].off), hl, wl, N.fc_w,
+    hipLaunchKernelGGL(critic_pool_fc_kernel, dim3(B), dim3(256), 0, s, reinterpret_cast<const HsRec*>(A + P.T.o1[3].off), hl, wl, N.fc_w,
                        N.fc_b, value);
     PNPX_LAUNCH_CHECK();
     hipLaunchKernelGGL(critic_mse_kernel, dim3(1), dim3(256), 0, s, value, q_target, gv, loss, B, (float)(1.0 / (double)B));
@@ -1267,7 +1009,7 @@ int param_grad_run(pnpx_ctx* ctx, const char* entry, const char* who, const floa
   double* a20 = J.dots + (size_t)NL * B;
   const float gs = grad_scale(N, hl, wl);
   PNPX_TRY(run_chain(ctx, P, gs, B, H, W, s, &J));
-  PNPX_TRY(launch_critic_fc_grad(reinterpret_cast<const HsRec*>(A + P.o1[3].off), grad_value, N.fc_w, hs_roundtrip16(N.alpha[20]), B, hl, wl,
+  PNPX_TRY(launch_critic_fc_grad(reinterpret_cast<const HsRec*>(A + P.T.o1[3].off), grad_value, N.fc_w, hs_roundtrip16(N.alpha[20]), B, hl, wl,
                                  grad_params + L.T.src_fcw, a20, s));
   AlphaFinishJob F;
   for (int i = 0; i < NL; ++i) F.alpha_src[i] = i == NL - 1 ? -1 : L.T.fold[i].alpha_src;   // the head's threshold: closed form
@@ -1340,7 +1082,7 @@ int critic_adam_step(pnpx_ctx* ctx, const float* grad_dev, size_t n, float lr, f
   }
   if (!N.optim.p) {   // first step: zero-filled moments (the only place the call allocates or synchronises the device)
     PNPX_HIP(hipDeviceSynchronize());
-    PNPX_TRY(alloc_dev(N.optim, optim_bytes(n), "optimiser state"));
+    PNPX_TRY(alloc_dev(N.optim, optim_bytes(n), "critic optimiser state"));
     PNPX_HIP(hipMemset(N.optim.p, 0, N.optim.bytes));
     PNPX_HIP(hipDeviceSynchronize());
     N.optim_step = 0;

@@ -349,14 +349,7 @@ int drunet_denoise(pnpx_ctx* ctx, const float* x, const float* sigma, int sigma_
   // one MFMA convolution launch: layer li, `in` (cin channels) -> `outp`
   auto conv = [&](const char* in, char* outp, int lvl_h, int lvl_w, float slope, const char* res, bool tail) -> int {
     const ConvLayerHsDev& D = N.layers[li];
-    ConvLayerHs Lh;
-    Lh.cin = D.cin;
-    Lh.cout = D.cout;
-    Lh.cin_pad = D.cin_pad;
-    Lh.mt = D.mt;
-    Lh.w = D.w;
-    Lh.b = N.zero;
-    Lh.inv_scale = D.inv_scale;
+    const ConvLayerHs Lh = hs_layer(D, N.zero);
     ConvHsFuse f;
     f.slope = slope;
     f.res = res;
@@ -521,14 +514,7 @@ int drunet_denoise_backward(pnpx_ctx* ctx, const float* x, const float* sigma, i
 
   auto conv = [&](int li, const char* in, char* outp, int h, int w, float slope, const char* dmask, const char* res) -> int {
     const ConvLayerHsDev& D = N.layers_bwd[li];
-    ConvLayerHs Lh;
-    Lh.cin = D.cin;
-    Lh.cout = D.cout;
-    Lh.cin_pad = D.cin_pad;
-    Lh.mt = D.mt;
-    Lh.w = D.w;
-    Lh.b = N.zero;
-    Lh.inv_scale = D.inv_scale;
+    const ConvLayerHs Lh = hs_layer(D, N.zero);
     ConvHsFuse f;
     f.slope = slope;
     f.dmask = dmask;

@@ -22,5 +22,17 @@ __device__ __forceinline__ HsRec hs_pack(const float v[8]) {
   }
   return r;
 }
+// global average pool: the sum of channel c of image b over the h x w interior of an HS8 tensor of G groups, times inv.
+// Fixed summation order (a result does not depend on the batch it arrives in).
+__device__ __forceinline__ float hs_pooled(const HsRec* __restrict__ feat, int b, int G, int c, int h, int w, float inv) {
+  const HsRec* p = feat + ((size_t)b * G + (c >> 3)) * (h + 2) * (w + 2);
+  float s = 0.f;
+  for (int y = 0; y < h; ++y)
+    for (int x = 0; x < w; ++x) {
+      const HsRec& r = p[(y + 1) * (w + 2) + x + 1];
+      s += (float)r.hi[c & 7] + (float)r.lo[c & 7];
+    }
+  return s * inv;
+}
 
 }  // namespace pnpx

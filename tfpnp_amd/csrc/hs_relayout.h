@@ -1,4 +1,4 @@
-// Space-to-depth / depth-to-space re-layouts of HS8 tensors (record copies; shared by drunet.hip and policy.hip; `static`:
+// Space-to-depth / depth-to-space re-layouts of HS8 tensors (record copies; shared by drunet.hip, resnet18_hs.hip and critic.hip; `static`:
 // one copy per translation unit).  Channel order is phase-major: group (dy*2+dx)*G + g.
 #pragma once
 #include "hs_rec.h"

@@ -21,16 +21,14 @@
 #include "conv_hs.h"
 #include "hs_rec.h"
 #include "policy_conv.h"
+#include "resnet18_hs.h"
 
 namespace pnpx {
 namespace {
 
 constexpr double BN_EPS = 1e-5;
-constexpr int NBN = 21;              // BatchNorm layers in parameter order: 0 = stem, 1 + 5 * stage + {0 entry bn1, 1 bn2, 2 shortcut.1,
-                                     // 3 block-1 bn1, 4 block-1 bn2}
+constexpr int NBN = TRUNK_LAYERS;    // one BatchNorm behind every convolution: the trunk's layer numbering (resnet18_hs.h)
 constexpr int BN_PIECE = 2048;       // pixels per partial sum: 256 threads x 8
-inline int stage_planes(int n) { return 64 << n; }
-inline dim3 g1(size_t n) { return dim3((unsigned)((n + 255) / 256)); }
 
 struct BnLayer {
   size_t bn;       // floats into the parameter vector: weight, bias, running_mean, running_var (cout each)
@@ -205,8 +203,8 @@ struct TrainPlan {
   size_t total = 0;
 };
 inline size_t bn_pieces(long long npix) { return (size_t)((npix + BN_PIECE - 1) / BN_PIECE); }
-// hs_stem: the observation / s2_hs: the space-to-depth activations are HS8 tensors (else fp32 planar)
-TrainPlan make_train_plan(int capB, int cin_pad, int H, int W, bool hs_stem, bool s2_hs) {
+// s2_hs: the observation and the space-to-depth activations are HS8 tensors (else fp32 planar)
+TrainPlan make_train_plan(int capB, int cin_pad, int H, int W, bool s2_hs) {
   TrainPlan P;
   size_t off = 0, part = 0;
   auto add = [&](size_t& d, int C, int h, int w, bool hs) {
@@ -218,7 +216,7 @@ TrainPlan make_train_plan(int capB, int cin_pad, int H, int W, bool hs_stem, boo
     const size_t n = bn_pieces((long long)capB * h * w) * C * 2;
     if (n > part) part = n;
   };
-  add(P.ob, 4 * cin_pad, H / 2, W / 2, hs_stem);
+  add(P.ob, 4 * cin_pad, H / 2, W / 2, s2_hs);
   add(P.zstem, 64, H / 2, W / 2, true);
   stat(64, H / 2, W / 2);
   add(P.stem_s, 4 * 64, H / 4, W / 4, s2_hs);
@@ -263,43 +261,10 @@ int policy_forward_train(pnpx_ctx* ctx, const float* ob, float* probs, float* de
   }
   if (!N.raw_valid) PNPX_TRY(policy_pack_raw(ctx, s));
   const bool s2_hs = ctx->opt_policy_s2_hs != 0;
-  const bool hs_stem = s2_hs && (N.raw.stem_hs.cin_pad % 16 == 0);
-  if (!N.bn_buf.p) {
-    void* p = nullptr;
-    const size_t bytes = 4 * POLICY_BN_CHANNELS * sizeof(float);
-    hipError_t e = hipMalloc(&p, bytes);
-    if (e != hipSuccess) {
-      set_error("policy batch-statistics allocation of %zu bytes failed: %s", bytes, hipGetErrorString(e));
-      return PNPX_ERR_ALLOC;
-    }
-    N.bn_buf.p = p;
-    N.bn_buf.bytes = bytes;
-  }
-  if (!(B <= N.tcapB && H == N.tcapH && W == N.tcapW)) {   // grows like the eval arena
-    const bool same = (H == N.tcapH && W == N.tcapW);
-    const int nb = same ? (B > N.tcapB ? B : N.tcapB) : B;
-    const TrainPlan P = make_train_plan(nb, N.cin_pad, H, W, hs_stem, s2_hs);
-    PNPX_HIP(hipDeviceSynchronize());
-    if (N.train_ws.bytes < P.total * sizeof(float)) {
-      if (N.train_ws.p) PNPX_HIP(hipFree(N.train_ws.p));
-      N.train_ws = DeviceBuf();
-      N.tcapB = N.tcapH = N.tcapW = 0;
-      void* p = nullptr;
-      hipError_t e = hipMalloc(&p, P.total * sizeof(float));
-      if (e != hipSuccess) {
-        set_error("policy train workspace allocation of %zu bytes failed: %s", P.total * sizeof(float), hipGetErrorString(e));
-        return PNPX_ERR_ALLOC;
-      }
-      N.train_ws.p = p;
-      N.train_ws.bytes = P.total * sizeof(float);
-    }
-    PNPX_HIP(hipMemset(N.train_ws.p, 0, P.total * sizeof(float)));
-    PNPX_HIP(hipDeviceSynchronize());
-    N.tcapB = nb;
-    N.tcapH = H;
-    N.tcapW = W;
-  }
-  const TrainPlan P = make_train_plan(N.tcapB, N.cin_pad, H, W, hs_stem, s2_hs);
+  if (!N.bn_buf.p) PNPX_TRY(alloc_dev(N.bn_buf, 4 * POLICY_BN_CHANNELS * sizeof(float), "policy batch-statistics"));
+  PNPX_TRY(reserve_arena_hs(N.train_ws, N.tcapB, N.tcapH, N.tcapW, B, H, W,
+                            [&](int nb) { return make_train_plan(nb, N.cin_pad, H, W, s2_hs).total; }, "policy train workspace"));
+  const TrainPlan P = make_train_plan(N.tcapB, N.cin_pad, H, W, s2_hs);
   float* A = static_cast<float*>(N.train_ws.p);
   auto hsc = [&](size_t off) { return reinterpret_cast<char*>(A + off); };
   auto rec = [&](size_t off) { return reinterpret_cast<HsRec*>(A + off); };
@@ -314,15 +279,9 @@ int policy_forward_train(pnpx_ctx* ctx, const float* ob, float* probs, float* de
   unsigned* range_flag = ctx->opt_range_guard ? ctx->range_flag_dev : nullptr;
 
   // the raw convolution: linear epilogue, zero bias (the fold-free packing's shifts)
-  auto conv_hs = [&](const ConvLayerHsDev& D, const float* bias, int taps, size_t in, int in_groups, size_t out, int h, int w) -> int {
-    ConvLayerHs Lh;
-    Lh.cin = D.cin;
-    Lh.cout = D.cout;
-    Lh.cin_pad = D.cin_pad;
-    Lh.mt = D.mt;
-    Lh.w = D.w;
-    Lh.b = bias;
-    Lh.inv_scale = D.inv_scale;
+  auto conv_hs = [&](int li, size_t in, int in_groups, size_t out, int h, int w) -> int {
+    const ConvLayerHsDev& D = N.raw.hs[li];
+    const int taps = trunk_taps(li, false);
     ConvHsFuse f;
     f.slope = 1.f;
     f.taps = taps;
@@ -331,7 +290,7 @@ int policy_forward_train(pnpx_ctx* ctx, const float* ob, float* probs, float* de
       f.in0_groups = in_groups;
     }
     f.range_flag = range_flag;
-    return launch_conv_hs(Lh, hsc(in), D.cin_pad / 8, nullptr, 0, hsc(out), B, h, w, f, s);
+    return launch_conv_hs(hs_layer(D, N.raw.hs_bias[li]), hsc(in), D.cin_pad / 8, nullptr, 0, hsc(out), B, h, w, f, s);
   };
   auto conv_f32 = [&](PolicyConv C, size_t in, size_t out, int h, int w) -> int {
     C.split_c = 0;   // every cout tile takes the linear epilogue and lands in ONE HS8 tensor of C.cout channels
@@ -393,11 +352,12 @@ int policy_forward_train(pnpx_ctx* ctx, const float* ob, float* probs, float* de
   const BnSrc no_src{nullptr, 0, 0, nullptr, nullptr, nullptr};
 
   // stem: conv3x3 stride 2 over the space-to-depth observation -> bn1 -> ReLU -> space-to-depth for the stage-0 entry
-  PNPX_TRY(policy_launch_pack_ob(ob, hs_stem ? nullptr : A + P.ob, hs_stem ? hsc(P.ob) : nullptr, N.num_inputs, N.cin_pad, B, H, W, s));
-  if (hs_stem) {
-    PNPX_TRY(conv_hs(N.raw.stem_hs, N.raw.stem_hs_bias, 0x01B, P.ob, N.raw.stem_hs.cin_pad / 8, P.zstem, H / 2, W / 2));
+  if (s2_hs) {
+    PNPX_TRY(launch_pack_ob_hs(ob, hsc(P.ob), N.num_inputs, N.cin_pad, B, H, W, s));
+    PNPX_TRY(conv_hs(0, P.ob, 4 * N.cin_pad / 8, P.zstem, H / 2, W / 2));
   } else {
-    PNPX_TRY(conv_f32(N.raw.conv[0], P.ob, P.zstem, H / 2, W / 2));
+    PNPX_TRY(policy_launch_pack_ob_f32(ob, A + P.ob, N.num_inputs, N.cin_pad, B, H, W, s));
+    PNPX_TRY(conv_f32(N.raw.f32[0], P.ob, P.zstem, H / 2, W / 2));
   }
   PNPX_TRY(stats(P.zstem, 64, H / 2, W / 2, 0, -1));
   PNPX_TRY(apply(src(P.zstem, 8, 0, 0), no_src, NONE, NONE, P.stem_s, 8, H / 2, W / 2));
@@ -408,28 +368,28 @@ int policy_forward_train(pnpx_ctx* ctx, const float* ob, float* probs, float* de
     BnSrc z1, zs;
     if (s2_hs) {   // conv1 and the 1x1 shortcut on the sparse-tap half-split instances: two tensors of p channels
       const size_t zs_off = P.za[st] + (size_t)B * p * (h + 2) * (w + 2);
-      PNPX_TRY(conv_hs(N.raw.s2_hs[st][0], N.raw.s2_bias[st][0], 0x01B, s2in, 4 * in_planes / 8, P.za[st], h, w));
-      PNPX_TRY(conv_hs(N.raw.s2_hs[st][1], N.raw.s2_bias[st][1], 0x010, s2in, 4 * in_planes / 8, zs_off, h, w));
+      PNPX_TRY(conv_hs(c0 + 0, s2in, 4 * in_planes / 8, P.za[st], h, w));
+      PNPX_TRY(conv_hs(c0 + 2, s2in, 4 * in_planes / 8, zs_off, h, w));
       PNPX_TRY(stats(P.za[st], p, h, w, c0 + 0, -1));
       PNPX_TRY(stats(zs_off, p, h, w, c0 + 2, -1));
       z1 = src(P.za[st], G, 0, c0 + 0);
       zs = src(zs_off, G, 0, c0 + 2);
     } else {       // one fp32 tap-sparse launch: conv1 in channels [0, p), the shortcut in [p, 2p) of one tensor
-      PNPX_TRY(conv_f32(N.raw.conv[1 + 4 * st], s2in, P.za[st], h, w));
+      PNPX_TRY(conv_f32(N.raw.f32[1 + st], s2in, P.za[st], h, w));
       PNPX_TRY(stats(P.za[st], 2 * p, h, w, c0 + 0, c0 + 2));
       z1 = src(P.za[st], 2 * G, 0, c0 + 0);
       zs = src(P.za[st], 2 * G, G, c0 + 2);
     }
     PNPX_TRY(apply(z1, no_src, NONE, P.t1[st], NONE, G, h, w));
     // block 0: relu(bn2(conv2) + shortcut_bn(shortcut_conv))
-    PNPX_TRY(conv_hs(N.raw.conv_hs[3 * st + 0], N.raw.bias_hs[3 * st + 0], 0x1FF, P.t1[st], 0, P.zb[st], h, w));
+    PNPX_TRY(conv_hs(c0 + 1, P.t1[st], 0, P.zb[st], h, w));
     PNPX_TRY(stats(P.zb[st], p, h, w, c0 + 1, -1));
     PNPX_TRY(apply(src(P.zb[st], G, 0, c0 + 1), zs, NONE, P.o0[st], NONE, G, h, w));
     // block 1: relu(bn2(conv2(relu(bn1(conv1(x))))) + x)
-    PNPX_TRY(conv_hs(N.raw.conv_hs[3 * st + 1], N.raw.bias_hs[3 * st + 1], 0x1FF, P.o0[st], 0, P.zb[st], h, w));
+    PNPX_TRY(conv_hs(c0 + 3, P.o0[st], 0, P.zb[st], h, w));
     PNPX_TRY(stats(P.zb[st], p, h, w, c0 + 3, -1));
     PNPX_TRY(apply(src(P.zb[st], G, 0, c0 + 3), no_src, NONE, P.t2[st], NONE, G, h, w));
-    PNPX_TRY(conv_hs(N.raw.conv_hs[3 * st + 2], N.raw.bias_hs[3 * st + 2], 0x1FF, P.t2[st], 0, P.zb[st], h, w));
+    PNPX_TRY(conv_hs(c0 + 4, P.t2[st], 0, P.zb[st], h, w));
     PNPX_TRY(stats(P.zb[st], p, h, w, c0 + 4, -1));
     PNPX_TRY(apply(src(P.zb[st], G, 0, c0 + 4), no_src, P.o0[st], P.o1[st], st < 3 ? P.o1s[st] : NONE, G, h, w));
   }

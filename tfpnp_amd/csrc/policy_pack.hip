@@ -29,16 +29,15 @@
 #include "conv_hs.h"
 #include "pack_desc.h"
 #include "policy_conv.h"
+#include "resnet18_hs.h"
 
 namespace pnpx {
 namespace {
 
 constexpr float BN_EPS = 1e-5f;
-constexpr int NCV = 21;      // BatchNorm-ed convolutions in parameter order: 0 = stem,
-                             // 1 + 5 * stage + {0 entry conv1, 1 conv2, 2 shortcut, 3 block-1 conv1, 4 block-1 conv2}
+constexpr int NCV = TRUNK_LAYERS;   // BatchNorm-ed convolutions in parameter order = the trunk's layer numbering (resnet18_hs.h)
 constexpr int NF32 = 5;      // fp32 PolStep launches: the stem and the four stage entries
 constexpr int MAXCOPY = 36, NRB = 32;
-inline int stage_planes(int n) { return 64 << n; }
 
 struct PolFoldDesc {
   unsigned src_w, src_bn;    // floats into the parameter vector: weights; BatchNorm weight, bias, running_mean, running_var
@@ -70,7 +69,7 @@ struct PolicyLayout {        // the table + the blob offsets (floats) the host n
   std::vector<int> nsteps[NF32];
 };
 
-// taps of phase ph of a 3x3 stride-2 convolution on the space-to-depth grid (policy.hip::put_conv_s2), ascending
+// taps of phase ph of a 3x3 stride-2 convolution on the space-to-depth grid (resnet18_hs.hip::put_conv_s2), ascending
 __host__ __device__ inline int phase_taps(int ph, int* taps) {
   const int ty0 = (ph >> 1) ? 0 : 1, tx0 = (ph & 1) ? 0 : 1;
   int n = 0;
@@ -385,22 +384,10 @@ __global__ __launch_bounds__(256) void pol_copy_kernel(const PolPackTable* __res
   if (i < C.n) blob[C.dst + i] = (C.space ? sh : P)[C.src + i];
 }
 
-int alloc_dev(DeviceBuf& b, size_t bytes, const char* what) {
-  void* p = nullptr;
-  hipError_t e = hipMalloc(&p, bytes);
-  if (e != hipSuccess) {
-    set_error("policy %s allocation of %zu bytes failed: %s", what, bytes, hipGetErrorString(e));
-    return PNPX_ERR_ALLOC;
-  }
-  b.p = p;
-  b.bytes = bytes;
-  return PNPX_OK;
-}
-
 // a fresh blob in the structural layout: zero padding and guards, the step lists; the packing workspace with its table
 int alloc_device_layout(PolicyPack& N, DeviceBuf& ws, float*& readback, const PolicyLayout& L) {
-  PNPX_TRY(alloc_dev(N.weights, L.total * sizeof(float), "weight"));
-  PNPX_TRY(alloc_dev(ws, ws_bytes(L.T.nchan), "packing workspace"));
+  PNPX_TRY(alloc_dev(N.weights, L.total * sizeof(float), "policy weight"));
+  PNPX_TRY(alloc_dev(ws, ws_bytes(L.T.nchan), "policy packing workspace"));
   void* h = nullptr;
   PNPX_HIP(hipHostMalloc(&h, NRB * sizeof(float), hipHostMallocDefault));
   readback = static_cast<float*>(h);
@@ -419,14 +406,8 @@ int alloc_device_layout(PolicyPack& N, DeviceBuf& ws, float*& readback, const Po
 // launch descriptors over the blob (the scales follow from the read-back)
 void bind_blob(PolicyPack& N, const PolicyLayout& L, int spi_head) {
   float* base = static_cast<float*>(N.weights.p);
-  for (int i = 0; i < 17; ++i) {
-    N.conv[i] = PolicyConv();
-    N.conv[i].w = N.conv[i].bias = base;
-    N.conv[i].steps = reinterpret_cast<const PolStep*>(base);
-    N.conv[i].nsteps = reinterpret_cast<const int*>(base);
-  }
   for (int fi = 0; fi < NF32; ++fi) {
-    PolicyConv& C = N.conv[fi == 0 ? 0 : 1 + 4 * (fi - 1)];
+    PolicyConv& C = N.f32[fi];
     C.w = base + L.f32_w[fi];
     C.bias = base + L.f32_bias[fi];
     C.steps = reinterpret_cast<const PolStep*>(base + L.f32_steps[fi]);
@@ -435,22 +416,14 @@ void bind_blob(PolicyPack& N, const PolicyLayout& L, int spi_head) {
     C.cout = L.f32_cout[fi];
     C.split_c = L.f32_split[fi];
   }
-  auto dev = [&](ConvLayerHsDev& D, const float*& bias, int ci) {
+  for (int ci = 0; ci < NCV; ++ci) {
     const PackDesc& P = L.T.pack[ci];
+    ConvLayerHsDev& D = N.hs[ci];
     D.cin = D.cin_pad = P.K;
     D.cout = P.rows;
     D.mt = P.mt;
     D.w = reinterpret_cast<char*>(base + P.dst);
-    bias = base + L.hs_bias[ci];
-  };
-  dev(N.stem_hs, N.stem_hs_bias, 0);
-  for (int s = 0; s < 4; ++s) {
-    const int c0 = 1 + 5 * s;
-    dev(N.s2_hs[s][0], N.s2_bias[s][0], c0 + 0);
-    dev(N.s2_hs[s][1], N.s2_bias[s][1], c0 + 2);
-    dev(N.conv_hs[3 * s + 0], N.bias_hs[3 * s + 0], c0 + 1);
-    dev(N.conv_hs[3 * s + 1], N.bias_hs[3 * s + 1], c0 + 3);
-    dev(N.conv_hs[3 * s + 2], N.bias_hs[3 * s + 2], c0 + 4);
+    N.hs_bias[ci] = base + L.hs_bias[ci];
   }
   N.fc_sm_w = base + L.smw;
   N.fc_sm_b = base + L.smb;
@@ -488,16 +461,7 @@ int repack(pnpx_ctx* ctx, const PolicyLayout& L, hipStream_t s, bool raw = false
       policy_free(ctx);
       return PNPX_ERR_ARG;
     }
-  auto inv = [&](int ci) { return 1.0f / (rb_host[ci] * HS_ASCALE); };
-  K.stem_hs.inv_scale = inv(0);
-  for (int st = 0; st < 4; ++st) {
-    const int c0 = 1 + 5 * st;
-    K.s2_hs[st][0].inv_scale = inv(c0 + 0);
-    K.s2_hs[st][1].inv_scale = inv(c0 + 2);
-    K.conv_hs[3 * st + 0].inv_scale = inv(c0 + 1);
-    K.conv_hs[3 * st + 1].inv_scale = inv(c0 + 3);
-    K.conv_hs[3 * st + 2].inv_scale = inv(c0 + 4);
-  }
+  for (int ci = 0; ci < NCV; ++ci) K.hs[ci].inv_scale = 1.0f / (rb_host[ci] * HS_ASCALE);
   if (raw) {
     N.raw_valid = true;
   } else {
@@ -511,7 +475,7 @@ int repack(pnpx_ctx* ctx, const PolicyLayout& L, hipStream_t s, bool raw = false
 
 int policy_keep_params(pnpx_ctx* ctx, const float* params_host, size_t n) {
   PolicyNet& N = ctx->policy;
-  PNPX_TRY(alloc_dev(N.master, n * sizeof(float), "parameter"));
+  PNPX_TRY(alloc_dev(N.master, n * sizeof(float), "policy parameter"));
   PNPX_HIP(hipMemcpy(N.master.p, params_host, n * sizeof(float), hipMemcpyHostToDevice));
   return PNPX_OK;
 }
@@ -550,7 +514,7 @@ int policy_load_device(pnpx_ctx* ctx, const float* params_dev, size_t n, int num
     N.n_det = n_det;
     N.spi_head = spi_head;
     int st = alloc_device_layout(N, N.pack_ws, N.readback, L);
-    if (st == PNPX_OK) st = alloc_dev(N.master, n * sizeof(float), "parameter");
+    if (st == PNPX_OK) st = alloc_dev(N.master, n * sizeof(float), "policy parameter");
     if (st != PNPX_OK) {
       policy_free(ctx);
       return st;

@@ -475,15 +475,7 @@ static int unet_forward_hs(pnpx_ctx* ctx, UNetArena& ar, const UNetPlan& P, cons
 
   auto conv = [&](int li, const Act& i0, const Act* i1, const Act& o, int b0, int nb, const ConvHsFuse& fuse) -> int {
     const ConvLayer& L = ctx->conv[li];
-    const ConvLayerHsDev& D = ctx->conv_hs[li];
-    ConvLayerHs Lh;
-    Lh.cin = D.cin;
-    Lh.cout = D.cout;
-    Lh.cin_pad = D.cin_pad;
-    Lh.mt = D.mt;
-    Lh.w = D.w;
-    Lh.b = L.b;
-    Lh.inv_scale = D.inv_scale;
+    const ConvLayerHs Lh = hs_layer(ctx->conv_hs[li], L.b);
     ConvHsFuse fz = fuse;
     fz.range_flag = range_flag;
     fz.wreg = ctx->opt_wreg;

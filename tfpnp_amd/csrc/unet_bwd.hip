@@ -586,14 +586,7 @@ int unet_denoise_backward(pnpx_ctx* ctx, const float* x, const float* sigma, int
     PNPX_LAUNCH_CHECK();
     auto convH = [&](int li, const Act& gin, const Act& gout, const Act* saved) -> int {
       const ConvLayerHsDev& D = ctx->conv_hs_bwd[li];
-      ConvLayerHs Lh;
-      Lh.cin = D.cin;
-      Lh.cout = D.cout;
-      Lh.cin_pad = D.cin_pad;
-      Lh.mt = D.mt;
-      Lh.w = D.w;
-      Lh.b = ctx->zero_bias;
-      Lh.inv_scale = D.inv_scale;
+      const ConvLayerHs Lh = hs_layer(D, ctx->zero_bias);
       if (gin.C != D.cin || gout.C != D.cout) {
         set_error("backward: gradient tensor channels %d -> %d do not match adjoint layer %d (%d -> %d)", gin.C, gout.C,
                   li, D.cin, D.cout);

@@ -24,8 +24,8 @@ NUM_INPUTS, WARMUP, REPS, INNER = 9, 3, 7, 5
 
 def stand_in_forward(net, x):
     """forward of the stand-in module (it registers parameters only): critic.py:121-131 through F.conv2d"""
-    def conv(m, v):
-        return F.conv2d(v, m.weight, m.bias, stride=m.stride, padding=m.padding)
+    def conv(m, v):   # (weight_norm's hook fills m.weight only inside m.forward, where the module was built: fold here)
+        return F.conv2d(v, torch._weight_norm(m.weight_v, m.weight_g, 0), m.bias, stride=m.stride, padding=m.padding)
 
     def trelu(m, v):
         return F.relu(v - m.alpha) + m.alpha
