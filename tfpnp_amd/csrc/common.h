@@ -58,6 +58,12 @@ struct DeviceBuf {
   void* p = nullptr;
   size_t bytes = 0;
 };
+// hipMalloc into an empty DeviceBuf; on failure the error reads "<what> allocation of N bytes failed"
+int alloc_dev(DeviceBuf& b, size_t bytes, const char* what);
+
+}  // namespace pnpx
+#include "live_params.h"   // LiveParams, PackWorkspace: the actor's and the critic's live weights
+namespace pnpx {
 
 struct UNetArena {
   DeviceBuf buf;
@@ -108,16 +114,14 @@ struct PolicyNet : PolicyPack {   // the base: the eval-mode packing (BatchNorm 
   DeviceBuf arena;           // activations for capB observations of capH x capW, zero borders
   int capB = 0, capH = 0, capW = 0;
   // live weights (policy_pack.hip): the flat fp32 parameter vector in pnpx_policy_load's order, kept after either load entry
-  DeviceBuf master;
+  LiveParams live;
   bool dev_layout = false;   // `weights` has the structural layout policy_load_device refreshes in place (else: policy_load's)
-  DeviceBuf pack_ws;         // layer table, per-channel BatchNorm scales / shifts / weight maxima, the block read back per refresh
-  float* readback = nullptr; // pinned host copy of that block: the 21 half-split weight scales
-  // train-mode forward (policy_bn.hip): the same convolutions packed WITHOUT the fold (scale 1, shift 0), derived from `master` by the
+  PackWorkspace pack_ws;     // layer table, per-channel BatchNorm scales / shifts / weight maxima; read back: the 21 half-split weight scales
+  // train-mode forward (policy_bn.hip): the same convolutions packed WITHOUT the fold (scale 1, shift 0), derived from `live` by the
   // first train forward after a load; moving the running statistics does not stale it, but it stales the eval packing above, which the
   // next eval forward re-derives once (eval_stale)
   PolicyPack raw;
-  DeviceBuf raw_ws;
-  float* raw_readback = nullptr;
+  PackWorkspace raw_ws;
   bool raw_valid = false, eval_stale = false;
   DeviceBuf train_ws;        // raw convolution outputs + activations of the train forward, zero borders
   int tcapB = 0, tcapH = 0, tcapW = 0;
@@ -125,7 +129,7 @@ struct PolicyNet : PolicyPack {   // the base: the eval-mode packing (BatchNorm 
   bool bn_have_stats = false;
 };
 
-// Value network (critic.hip): ResNet_wobn(num_inputs, 18, 1).  The raw parameters live on the device (`master`); the packed
+// Value network (critic.hip): ResNet_wobn(num_inputs, 18, 1).  The raw parameters live on the device (`live`); the packed
 // weights the launches read are derived from them, on the host by critic_load and on the device by every later refresh
 // (critic_load_device, critic_soft_update).  Layer index: the trunk's (resnet18_hs.h).
 struct CriticNet {
@@ -141,9 +145,8 @@ struct CriticNet {
   DeviceBuf weights, arena;          // arena: every forward activation + the gradient tensors, zero borders
   int capB = 0, capH = 0, capW = 0;
   // live weights: the flat fp32 parameter vector (pnpx_critic_load's order) and what the device-side packing needs
-  DeviceBuf master;                  // [critic_num_params(num_inputs)] floats
-  DeviceBuf pack_ws;                 // layer table, per-channel fold scales and maxima, the block read back per refresh
-  float* readback = nullptr;         // pinned host copy of that block: 21 weight scales, 21 thresholds, max |fc_w|
+  LiveParams live;                   // [critic_num_params(num_inputs)] floats
+  PackWorkspace pack_ws;             // layer table, per-channel fold scales and maxima; read back: 21 weight scales, 21 thresholds, max |fc_w|
   // parameter gradients (pnpx_critic_param_grad): clip indicator, W * indicator, K-split slabs + reduction blocks; each grows to
   // the largest size seen
   DeviceBuf grad_m, grad_wm, grad_slab;
@@ -328,8 +331,6 @@ int fan_out_chains(pnpx_ctx* ctx, int chains, int B, hipStream_t s, F&& run_slic
 int ctx_reserve_unet(pnpx_ctx* ctx, int B, int H, int W);   // main arena, ctx->conv_mode
 int reserve_arena(pnpx_ctx* ctx, UNetArena& ar, int mode, int B, int H, int W, size_t extra_bytes);
 int ctx_scratch(pnpx_ctx* ctx, size_t bytes, void** out);
-// hipMalloc into an empty DeviceBuf; on failure the error reads "<what> allocation of N bytes failed"
-int alloc_dev(DeviceBuf& b, size_t bytes, const char* what);
 int ctx_twiddle(pnpx_ctx* ctx, int N, const float2** out);
 // Half-split range guard (api.hip).  range_guard_enter: called at the top of every entry that runs the denoiser; if the
 // flag of an earlier call is set, latches the context to conv_mode 0.  range_guard_strict: option value 2 -- synchronise
@@ -404,11 +405,10 @@ int policy_load(pnpx_ctx* ctx, const float* params, size_t n, int num_inputs, in
 int policy_forward(pnpx_ctx* ctx, const float* ob, float* probs, float* det, int B, int H, int W, hipStream_t s);
 void policy_free(pnpx_ctx* ctx);
 // live weights (policy_pack.hip)
-int policy_keep_params(pnpx_ctx* ctx, const float* params_host, size_t n);   // policy_load: the parameter vector stays on the device
 int policy_load_device(pnpx_ctx* ctx, const float* params_dev, size_t n, int num_inputs, int n_det, int spi_head, hipStream_t s);
 int policy_params(pnpx_ctx* ctx, float* dst_dev, size_t n, hipStream_t s);
-int policy_pack_raw(pnpx_ctx* ctx, hipStream_t s);       // master -> PolicyNet::raw (allocates on first use)
-int policy_refresh_eval(pnpx_ctx* ctx, hipStream_t s);   // master -> the eval packing, after the running statistics moved
+int policy_pack_raw(pnpx_ctx* ctx, hipStream_t s);       // live vector -> PolicyNet::raw (allocates on first use)
+int policy_refresh_eval(pnpx_ctx* ctx, hipStream_t s);   // live vector -> the eval packing, after the running statistics moved
 // pieces of the eval forward the train forward shares (policy.hip; the half-split ones: resnet18_hs.h)
 int policy_launch_pack_ob_f32(const float* ob, float* out, int C, int Cp, int B, int H, int W, hipStream_t s);   // option policy_s2_hs = 0
 int policy_launch_heads(const PolicyPack& P, int n_det, int spi_head, const char* feat_hs, int h, int w, int B, float* probs, float* det,

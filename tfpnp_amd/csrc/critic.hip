@@ -1,13 +1,13 @@
 // Value network (critic) forward, input gradient and parameter gradients, live weights.
 //
-// Live weights: the context keeps the flat fp32 parameter vector on the device (CriticNet::master).  pnpx_critic_load folds
+// Live weights: the context keeps the flat fp32 parameter vector on the device (CriticNet::live).  pnpx_critic_load folds
 // weight-norm and packs on the host; pnpx_critic_load_device and pnpx_critic_soft_update derive the same packed blob from
 // the device vector with four launches ("device-side packing" below) and refresh an already loaded critic in place -- no
 // allocation, no device-wide synchronisation, the arena is kept.  Thresholds, weight scales and max |fc_w| are launch
 // arguments, so each refresh ends with one small read-back and a synchronisation of the caller's stream: a refresh cannot be
 // captured into a graph and has to be issued on the stream the critic's other calls use.  Parameter gradients: critic_param_grad below,
 // kernels in critic_grad.hip; critic_value_loss_grad takes value_loss and its backward from one forward.  The optimiser step
-// (critic_adam_step: clip + Adam on `master`, then the refresh; kernels in critic_optim.hip) keeps its moments in the context.
+// (critic_adam_step: clip + Adam on the live vector, then the refresh; kernels in critic_optim.hip) keeps its moments in the context.
 // (The actor's refresh: policy_pack.hip.)
 //
 // Replaces ResNet_wobn(num_inputs, 18, 1).forward (tfpnp/trainer/mddpg/critic.py:95-131) and the autograd pass through it
@@ -164,7 +164,7 @@ constexpr int NL = TRUNK_LAYERS;   // layer index: resnet18_hs.h
 //   critic_fold_kernel   per output channel: sc = g / ||v|| in double (the host's summation order) and max |folded weight|
 //   critic_scale_kernel  per convolution: the power-of-two weight scale; thresholds and max |fc_w| into the read-back block
 //   critic_pack_kernel   per 16-byte destination fragment pair (hi, lo): gathers its eight source elements, or zeros
-//   critic_copy_kernel   biases and fc
+//   live_copy_kernel     biases and fc (live_params.hip, shared with the actor)
 struct FoldDesc {     // one weight-normalised convolution of the parameter vector
   unsigned src_g, src_v;   // floats into the parameter vector
   unsigned chan0;          // its first output channel in the per-channel arrays
@@ -183,28 +183,17 @@ struct PackTable {
 struct CriticLayout {     // PackTable + the blob offsets (floats) the host needs
   PackTable T;
   size_t bias[NL], fcw, fcb, zero, total;
-  unsigned max_items;
+  PackDims dims;          // the launch dimensions of T (stored with the workspace the table is uploaded to)
 };
 
 // Offsets of HostBlob as critic_load fills it (256-float alignment before every entry), sources in registration order.
 bool make_layout(int num_inputs, CriticLayout& L) {
   std::memset(&L, 0, sizeof(L));
   const int cin_pad = (num_inputs + 7) / 8 * 8;
-  size_t src = 0, dst = 0;
+  BlobCursor cur;
   unsigned chan = 0;
   int ncopy = 0;
   bool ok = true;
-  auto take = [&](size_t n) {
-    const size_t r = src;
-    src += n;
-    return (unsigned)r;
-  };
-  auto put = [&](size_t n) {
-    dst = (dst + 255) & ~(size_t)255;
-    const size_t r = dst;
-    dst += n;
-    return r;
-  };
   struct Src {
     unsigned b, g, v;
     int cout, cin, ks;
@@ -212,9 +201,9 @@ bool make_layout(int num_inputs, CriticLayout& L) {
   // the next convolution of the parameter vector = layer li (registration order is the layer numbering)
   auto take_wn = [&](int li, int cout, int cin, int ks) {
     Src c;
-    c.b = take(cout);
-    c.g = take(cout);
-    c.v = take((size_t)cout * cin * ks);
+    c.b = cur.take(cout);
+    c.g = cur.take(cout);
+    c.v = cur.take((size_t)cout * cin * ks);
     c.cout = cout;
     c.cin = cin;
     c.ks = ks;
@@ -247,11 +236,11 @@ bool make_layout(int num_inputs, CriticLayout& L) {
       P.Cp = Cp;
       P.adj = adj;
       P.items = (unsigned)((size_t)P.rows * (P.K / 8) * P.nt);
-      P.dst = (unsigned)put((size_t)P.rows * P.K * P.nt);
+      P.dst = (unsigned)cur.put((size_t)P.rows * P.K * P.nt);
       ok = ok && P.rows % P.mt == 0 && P.K % 16 == 0;
-      if (P.items > L.max_items) L.max_items = P.items;
+      if (P.items > L.dims.max_items) L.dims.max_items = P.items;
       if (!adj) {
-        L.bias[li] = put(c.cout);
+        L.bias[li] = cur.put(c.cout);
         L.T.copy[li] = CopyDesc{c.b, (unsigned)L.bias[li], (unsigned)c.cout};   // copy[li]: the bias of layer li
         ++ncopy;
       }
@@ -262,12 +251,12 @@ bool make_layout(int num_inputs, CriticLayout& L) {
   for (int s = 0; s < 4; ++s) {
     const int p = stage_planes(s), l0 = 1 + 5 * s;
     const Src c1 = take_wn(l0 + 0, p, in_planes, 9), c2 = take_wn(l0 + 1, p, p, 9), cs = take_wn(l0 + 2, p, in_planes, 1);
-    const unsigned a0 = take(1), a1 = take(1);
+    const unsigned a0 = cur.take(1), a1 = cur.take(1);
     finish(l0 + 0, c1, 1, in_planes, 4 * in_planes);
     finish(l0 + 2, cs, 2, 0, in_planes);
     finish(l0 + 1, c2, 0, 0, p);
     const Src d1 = take_wn(l0 + 3, p, p, 9), d2 = take_wn(l0 + 4, p, p, 9);
-    const unsigned a3 = take(1), a4 = take(1);
+    const unsigned a3 = cur.take(1), a4 = cur.take(1);
     finish(l0 + 3, d1, 0, 0, p);
     finish(l0 + 4, d2, 0, 0, p);
     L.T.fold[l0 + 0].alpha_src = (int)a0;
@@ -276,16 +265,17 @@ bool make_layout(int num_inputs, CriticLayout& L) {
     L.T.fold[l0 + 4].alpha_src = (int)a4;
     in_planes = p;
   }
-  L.T.src_fcw = take(512);
-  L.fcw = put(512);
+  L.T.src_fcw = cur.take(512);
+  L.fcw = cur.put(512);
   L.T.copy[ncopy++] = CopyDesc{L.T.src_fcw, (unsigned)L.fcw, 512u};   // (ncopy == NL here: behind the 21 biases)
-  L.fcb = put(1);
-  L.T.copy[ncopy++] = CopyDesc{take(1), (unsigned)L.fcb, 1u};
-  L.T.fold[0].alpha_src = (int)take(1);
-  L.zero = put(1024);
-  L.total = dst + 8192;   // DMA over-read slack
-  L.T.nchan = chan;
-  return ok && ncopy == NCOPY && src == critic_num_params(num_inputs);
+  L.fcb = cur.put(1);
+  L.T.copy[ncopy++] = CopyDesc{cur.take(1), (unsigned)L.fcb, 1u};
+  L.T.fold[0].alpha_src = (int)cur.take(1);
+  L.zero = cur.put(1024);
+  L.total = cur.dst + 8192;   // DMA over-read slack
+  L.T.nchan = L.dims.nchan = chan;
+  L.dims.ncopy = ncopy;
+  return ok && ncopy == NCOPY && cur.src == critic_num_params(num_inputs);
 }
 
 // device workspace: the table, then sc[nchan] (double), chmax[nchan], the read-back block
@@ -295,9 +285,9 @@ struct PackWs {
   float *chmax, *rb;
 };
 inline size_t pack_ws_table_bytes() { return (sizeof(PackTable) + 255) & ~(size_t)255; }
-inline size_t pack_ws_bytes(unsigned nchan) { return pack_ws_table_bytes() + (size_t)nchan * 12 + 64 * sizeof(float); }
-inline PackWs pack_ws(const CriticNet& N, unsigned nchan) {
-  char* p = static_cast<char*>(N.pack_ws.p);
+inline PackWs pack_ws(const PackWorkspace& W) {
+  const unsigned nchan = W.dims.nchan;
+  char* p = static_cast<char*>(W.ws.p);
   PackWs w;
   w.T = reinterpret_cast<PackTable*>(p);
   w.sc = reinterpret_cast<double*>(p + pack_ws_table_bytes());
@@ -384,13 +374,6 @@ __global__ __launch_bounds__(256) void critic_pack_kernel(const PackTable* __res
   });
 }
 
-__global__ __launch_bounds__(256) void critic_copy_kernel(const PackTable* __restrict__ T, const float* __restrict__ P,
-                                                          float* __restrict__ blob) {
-  const CopyDesc C = T->copy[blockIdx.y];
-  const unsigned i = blockIdx.x * 256 + threadIdx.x;
-  if (i < C.n) blob[C.dst + i] = P[C.src + i];
-}
-
 // utils/misc.py:81-85: target * (1.0 - tau) + source * tau on fp32 tensors -- two rounded products, one rounded sum.  A fused
 // multiply-add would differ in the last bit of about a quarter of the elements.
 __global__ __launch_bounds__(256) void critic_soft_update_kernel(float* __restrict__ master, const float* __restrict__ src, float a,
@@ -461,6 +444,23 @@ int check_call(const CriticNet& N, const char* who, int B, int H, int W) {
   return PNPX_OK;
 }
 
+// the entries that take or fill a whole parameter vector of `n` floats: a critic is loaded, the pointers are there (`have`) and
+// n is its parameter count.  expected: "expected <expected>N parameters ..." for a vector taken ("" / "a gradient of "); null for
+// one filled.
+int check_vector(const CriticNet& N, const char* entry, bool have, size_t n, const char* expected) {
+  if (!N.loaded) {
+    set_error("%s called before a critic was loaded", entry);
+    return PNPX_ERR_NO_WEIGHTS;
+  }
+  const size_t want = critic_num_params(N.num_inputs);
+  if (have && n == want) return PNPX_OK;
+  if (expected)
+    set_error("%s: expected %s%zu parameters for the loaded critic (%d inputs), got %zu", entry, expected, want, N.num_inputs, n);
+  else
+    set_error("%s: the loaded critic (%d inputs) has %zu parameters, got room for %zu", entry, N.num_inputs, want, n);
+  return PNPX_ERR_ARG;
+}
+
 int reserve(CriticNet& N, int B, int H, int W) {
   return reserve_arena_hs(N.arena, N.capB, N.capH, N.capW, B, H, W, [&](int nb) { return make_plan(nb, N.cin_pad, H, W).total; },
                           "critic arena");
@@ -509,13 +509,12 @@ void critic_free(pnpx_ctx* ctx) {
   CriticNet& N = ctx->critic;
   if (N.weights.p) (void)hipFree(N.weights.p);
   if (N.arena.p) (void)hipFree(N.arena.p);
-  if (N.master.p) (void)hipFree(N.master.p);
-  if (N.pack_ws.p) (void)hipFree(N.pack_ws.p);
+  N.live.free();
+  N.pack_ws.free();
   if (N.grad_m.p) (void)hipFree(N.grad_m.p);
   if (N.grad_wm.p) (void)hipFree(N.grad_wm.p);
   if (N.grad_slab.p) (void)hipFree(N.grad_slab.p);
   if (N.optim.p) (void)hipFree(N.optim.p);
-  if (N.readback) (void)hipHostFree(N.readback);
   N = CriticNet();
 }
 
@@ -523,13 +522,8 @@ namespace {
 
 // the parameter vector on the device, the layer table and the read-back block (at a load that allocates)
 int alloc_live_state(CriticNet& N, const CriticLayout& L, size_t n) {
-  PNPX_TRY(alloc_dev(N.master, n * sizeof(float), "critic parameter"));
-  PNPX_TRY(alloc_dev(N.pack_ws, pack_ws_bytes(L.T.nchan), "critic packing workspace"));
-  void* h = nullptr;
-  PNPX_HIP(hipHostMalloc(&h, 64 * sizeof(float), hipHostMallocDefault));
-  N.readback = static_cast<float*>(h);
-  PNPX_HIP(hipMemcpy(N.pack_ws.p, &L.T, sizeof(PackTable), hipMemcpyHostToDevice));
-  return PNPX_OK;
+  PNPX_TRY(N.live.alloc(n, "critic parameter"));
+  return N.pack_ws.alloc(&L.T, sizeof(PackTable), (size_t)L.dims.nchan * 12, 64, L.dims, "critic packing workspace");
 }
 
 // launch descriptors over the blob at `base`
@@ -552,33 +546,34 @@ void bind_blob(CriticNet& N, const CriticLayout& L) {
 }
 
 // master -> weight blob on stream s, then the one read-back: scales, thresholds, max |fc_w|
-int repack(pnpx_ctx* ctx, const CriticLayout& L, hipStream_t s) {
+int repack(pnpx_ctx* ctx, hipStream_t s) {
   CriticNet& N = ctx->critic;
-  const PackWs w = pack_ws(N, L.T.nchan);
-  const float* P = static_cast<const float*>(N.master.p);
+  const PackDims& d = N.pack_ws.dims;
+  const PackWs w = pack_ws(N.pack_ws);
+  const float* P = N.live.p();
   float* blob = static_cast<float*>(N.weights.p);
-  hipLaunchKernelGGL(critic_fold_kernel, dim3((L.T.nchan + 63) / 64), dim3(64), 0, s, w.T, P, w.sc, w.chmax);
+  float* const rb_host = N.pack_ws.readback;
+  hipLaunchKernelGGL(critic_fold_kernel, dim3((d.nchan + 63) / 64), dim3(64), 0, s, w.T, P, w.sc, w.chmax);
   PNPX_LAUNCH_CHECK();
   hipLaunchKernelGGL(critic_scale_kernel, dim3(NL + 1), dim3(256), 0, s, w.T, P, w.chmax, w.rb);
   PNPX_LAUNCH_CHECK();
-  hipLaunchKernelGGL(critic_pack_kernel, dim3((L.max_items + 255) / 256, 2 * NL), dim3(256), 0, s, w.T, P, w.sc, w.rb, blob);
+  hipLaunchKernelGGL(critic_pack_kernel, dim3((d.max_items + 255) / 256, 2 * NL), dim3(256), 0, s, w.T, P, w.sc, w.rb, blob);
   PNPX_LAUNCH_CHECK();
-  hipLaunchKernelGGL(critic_copy_kernel, dim3(2, NCOPY), dim3(256), 0, s, w.T, P, blob);
-  PNPX_LAUNCH_CHECK();
-  PNPX_HIP(hipMemcpyAsync(N.readback, w.rb, (NREAD + 1) * sizeof(float), hipMemcpyDeviceToHost, s));   // + the optimiser's norm
+  PNPX_TRY(launch_live_copy(w.T->copy, dim3(2, NCOPY), P, nullptr, blob, s));
+  PNPX_HIP(hipMemcpyAsync(rb_host, w.rb, (NREAD + 1) * sizeof(float), hipMemcpyDeviceToHost, s));   // + the optimiser's norm
   PNPX_HIP(hipStreamSynchronize(s));
   for (int i = 0; i < NL; ++i)
-    if (!std::isfinite(N.readback[NL + i])) {
+    if (!std::isfinite(rb_host[NL + i])) {
       set_error("critic refresh: TReLU threshold %d is not finite", i);
       PNPX_HIP(hipDeviceSynchronize());
       critic_free(ctx);
       return PNPX_ERR_ARG;
     }
   for (int i = 0; i < NL; ++i) {
-    N.fwd[i].inv_scale = N.bwd[i].inv_scale = 1.0f / (N.readback[i] * HS_ASCALE);
-    N.alpha[i] = N.readback[NL + i];
+    N.fwd[i].inv_scale = N.bwd[i].inv_scale = 1.0f / (rb_host[i] * HS_ASCALE);
+    N.alpha[i] = rb_host[NL + i];
   }
-  N.fc_wmax = N.readback[2 * NL];
+  N.fc_wmax = rb_host[2 * NL];
   N.loaded = true;
   return PNPX_OK;
 }
@@ -592,12 +587,12 @@ int critic_load_device(pnpx_ctx* ctx, const float* params_dev, size_t n, int num
     return PNPX_ERR_ARG;
   }
   CriticNet& N = ctx->critic;
-  CriticLayout L;
-  if (!make_layout(num_inputs, L)) {
-    set_error("pnpx_critic_load_device: internal layout error for %d inputs", num_inputs);
-    return PNPX_ERR_SHAPE;
-  }
   if (!(N.loaded && N.num_inputs == num_inputs)) {   // first load / another network: allocate (a refresh allocates nothing)
+    CriticLayout L;
+    if (!make_layout(num_inputs, L)) {
+      set_error("pnpx_critic_load_device: internal layout error for %d inputs", num_inputs);
+      return PNPX_ERR_SHAPE;
+    }
     PNPX_HIP(hipDeviceSynchronize());
     critic_free(ctx);
     N.num_inputs = num_inputs;
@@ -613,44 +608,22 @@ int critic_load_device(pnpx_ctx* ctx, const float* params_dev, size_t n, int num
     }
     bind_blob(N, L);
   }
-  if (params_dev != N.master.p) PNPX_HIP(hipMemcpyAsync(N.master.p, params_dev, n * sizeof(float), hipMemcpyDeviceToDevice, s));
-  return repack(ctx, L, s);
+  PNPX_TRY(N.live.set_device(params_dev, s));
+  return repack(ctx, s);
 }
 
 int critic_soft_update(pnpx_ctx* ctx, const float* src_dev, size_t n, float one_minus_tau, float tau, hipStream_t s) {
   CriticNet& N = ctx->critic;
-  if (!N.loaded) {
-    set_error("pnpx_critic_soft_update called before a critic was loaded");
-    return PNPX_ERR_NO_WEIGHTS;
-  }
-  if (!src_dev || n != critic_num_params(N.num_inputs)) {
-    set_error("pnpx_critic_soft_update: expected %zu parameters for the loaded critic (%d inputs), got %zu",
-              critic_num_params(N.num_inputs), N.num_inputs, n);
-    return PNPX_ERR_ARG;
-  }
-  CriticLayout L;
-  if (!make_layout(N.num_inputs, L)) {
-    set_error("pnpx_critic_soft_update: internal layout error for %d inputs", N.num_inputs);
-    return PNPX_ERR_SHAPE;
-  }
-  hipLaunchKernelGGL(critic_soft_update_kernel, g1(n), dim3(256), 0, s, static_cast<float*>(N.master.p), src_dev, one_minus_tau, tau, n);
+  PNPX_TRY(check_vector(N, "pnpx_critic_soft_update", src_dev != nullptr, n, ""));
+  hipLaunchKernelGGL(critic_soft_update_kernel, g1(n), dim3(256), 0, s, N.live.p(), src_dev, one_minus_tau, tau, n);
   PNPX_LAUNCH_CHECK();
-  return repack(ctx, L, s);
+  return repack(ctx, s);
 }
 
 int critic_params(pnpx_ctx* ctx, float* dst_dev, size_t n, hipStream_t s) {
   CriticNet& N = ctx->critic;
-  if (!N.loaded) {
-    set_error("pnpx_critic_params called before a critic was loaded");
-    return PNPX_ERR_NO_WEIGHTS;
-  }
-  if (!dst_dev || n != critic_num_params(N.num_inputs)) {
-    set_error("pnpx_critic_params: the loaded critic (%d inputs) has %zu parameters, got room for %zu", N.num_inputs,
-              critic_num_params(N.num_inputs), n);
-    return PNPX_ERR_ARG;
-  }
-  PNPX_HIP(hipMemcpyAsync(dst_dev, N.master.p, n * sizeof(float), hipMemcpyDeviceToDevice, s));
-  return PNPX_OK;
+  PNPX_TRY(check_vector(N, "pnpx_critic_params", dst_dev != nullptr, n, nullptr));
+  return N.live.copy_out(dst_dev, s);
 }
 
 int critic_load(pnpx_ctx* ctx, const float* params, size_t n, int num_inputs) {
@@ -748,7 +721,7 @@ int critic_load(pnpx_ctx* ctx, const float* params, size_t n, int num_inputs) {
   N.fc_b = base + o_fcb;
   N.zero = base + o_zero;
   N.fc_wmax = wmax;
-  // live weights: the raw parameters stay on the device as the master vector of pnpx_critic_soft_update, whose device-side
+  // live weights: the raw parameters stay on the device as the vector pnpx_critic_soft_update moves, whose device-side
   // packing writes into this blob -- so its layer table has to describe exactly the offsets used above
   CriticLayout L;
   bool same = make_layout(num_inputs, L) && L.total == H.f.size() && L.fcw == o_fcw && L.fcb == o_fcb && L.zero == o_zero;
@@ -761,10 +734,7 @@ int critic_load(pnpx_ctx* ctx, const float* params, size_t n, int num_inputs) {
     return PNPX_ERR_SHAPE;
   }
   int st = alloc_live_state(N, L, n);
-  if (st == PNPX_OK && hipMemcpy(N.master.p, params, n * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) {
-    set_error("pnpx_critic_load: uploading the parameter vector failed: %s", hipGetErrorString(hipGetLastError()));
-    st = PNPX_ERR_HIP;
-  }
+  if (st == PNPX_OK) st = N.live.set_host(params);
   if (st != PNPX_OK) {
     critic_free(ctx);
     return st;
@@ -847,7 +817,7 @@ int run_chain(pnpx_ctx* ctx, const CriticPlan& P, float gs, int B, int H, int W,
     F.pieces = critic_wgrad_pieces(D.rows, D.K, B, h, w);
     F.inv_w = 1.0f / (gs * HS_ASCALE * HS_ASCALE);
     F.inv_b = 1.0f / (gs * HS_ASCALE);
-    return launch_critic_wn_grad(F, J->slab, static_cast<const float*>(N.master.p), J->out, s);
+    return launch_critic_wn_grad(F, J->slab, N.live.p(), J->out, s);
   };
   // threshold ali of the saved activation `act`, read by forward convolution cli whose output gradient is g; res: what the chain
   // adds to W^T g before the mask
@@ -950,11 +920,7 @@ int param_grad_run(pnpx_ctx* ctx, const char* entry, const char* who, const floa
                    float* value, float* loss, float* grad_params, size_t n, int B, int H, int W, hipStream_t s) {
   CriticNet& N = ctx->critic;
   PNPX_TRY(check_call(N, who, B, H, W));
-  if (n != critic_num_params(N.num_inputs)) {
-    set_error("%s: the loaded critic (%d inputs) has %zu parameters, got room for %zu", entry, N.num_inputs,
-              critic_num_params(N.num_inputs), n);
-    return PNPX_ERR_ARG;
-  }
+  PNPX_TRY(check_vector(N, entry, true, n, nullptr));
   CriticLayout L;
   if (!make_layout(N.num_inputs, L)) {
     set_error("%s: internal layout error for %d inputs", entry, N.num_inputs);
@@ -1035,7 +1001,7 @@ int critic_value_loss_grad(pnpx_ctx* ctx, const float* ob, const float* q_target
 }
 
 // ------------------------------------------------------------------------------------------- optimiser
-// clip_grad_norm_(max_norm) + Adam.step() (trainer/mddpg/trainer.py:208-209) on `master`, then repack: sum of squares, finish
+// clip_grad_norm_(max_norm) + Adam.step() (trainer/mddpg/trainer.py:208-209) on the live vector, then repack: sum of squares, finish
 // (norm and clip coefficient into the read-back block's spare floats), the fused update (critic_optim.hip), the refresh.  The
 // update reads the coefficient on the device and does nothing when the norm is not finite; the host learns the norm from the
 // refresh's own read-back and only then advances the step counter.
@@ -1060,25 +1026,12 @@ inline OptimState optim_state(const CriticNet& N, size_t n) {
 int critic_adam_step(pnpx_ctx* ctx, const float* grad_dev, size_t n, float lr, float beta1, float beta2, float eps, float max_norm,
                      float* grad_norm_dev, hipStream_t s) {
   CriticNet& N = ctx->critic;
-  if (!N.loaded) {
-    set_error("pnpx_critic_adam_step called before a critic was loaded");
-    return PNPX_ERR_NO_WEIGHTS;
-  }
-  if (!grad_dev || n != critic_num_params(N.num_inputs)) {
-    set_error("pnpx_critic_adam_step: expected a gradient of %zu parameters for the loaded critic (%d inputs), got %zu",
-              critic_num_params(N.num_inputs), N.num_inputs, n);
-    return PNPX_ERR_ARG;
-  }
+  PNPX_TRY(check_vector(N, "pnpx_critic_adam_step", grad_dev != nullptr, n, "a gradient of "));
   if (!(lr >= 0.f) || !std::isfinite(lr) || !(beta1 >= 0.f && beta1 < 1.f) || !(beta2 >= 0.f && beta2 < 1.f) || !(eps > 0.f) ||
       !std::isfinite(eps) || !(max_norm > 0.f)) {
     set_error("pnpx_critic_adam_step: need lr >= 0 and finite, betas in [0, 1), eps > 0 and finite, max_norm > 0 (got lr %g, betas %g %g, "
               "eps %g, max_norm %g)", (double)lr, (double)beta1, (double)beta2, (double)eps, (double)max_norm);
     return PNPX_ERR_ARG;
-  }
-  CriticLayout L;
-  if (!make_layout(N.num_inputs, L)) {
-    set_error("pnpx_critic_adam_step: internal layout error for %d inputs", N.num_inputs);
-    return PNPX_ERR_SHAPE;
   }
   if (!N.optim.p) {   // first step: zero-filled moments (the only place the call allocates or synchronises the device)
     PNPX_HIP(hipDeviceSynchronize());
@@ -1088,16 +1041,16 @@ int critic_adam_step(pnpx_ctx* ctx, const float* grad_dev, size_t n, float lr, f
     N.optim_step = 0;
   }
   const OptimState o = optim_state(N, n);
-  float* slot = pack_ws(N, L.T.nchan).rb + RB_NORM;
+  float* slot = pack_ws(N.pack_ws).rb + RB_NORM;
   const double t = (double)(N.optim_step + 1);
   const double step_size = (double)lr / (1.0 - std::pow((double)beta1, t));
   const double bc2_sqrt = std::sqrt(1.0 - std::pow((double)beta2, t));
   PNPX_TRY(launch_critic_sumsq(grad_dev, n, o.partials, s));
   PNPX_TRY(launch_critic_norm_finish(o.partials, max_norm, slot, grad_norm_dev, s));
-  PNPX_TRY(launch_critic_adam(grad_dev, static_cast<float*>(N.master.p), o.m, o.v, n, slot, (float)(1.0 - (double)beta1), beta2,
+  PNPX_TRY(launch_critic_adam(grad_dev, N.live.p(), o.m, o.v, n, slot, (float)(1.0 - (double)beta1), beta2,
                               (float)(1.0 - (double)beta2), (float)step_size, (float)bc2_sqrt, eps, s));
-  PNPX_TRY(repack(ctx, L, s));   // (a threshold stepped to a non-finite value: the critic is gone, as after any such refresh)
-  const float norm = N.readback[RB_NORM];
+  PNPX_TRY(repack(ctx, s));   // (a threshold stepped to a non-finite value: the critic is gone, as after any such refresh)
+  const float norm = N.pack_ws.readback[RB_NORM];
   if (!std::isfinite(norm)) {
     set_error("pnpx_critic_adam_step: the gradient norm is not finite (%g); parameters and optimiser state are unchanged", (double)norm);
     return PNPX_ERR_ARG;
@@ -1108,15 +1061,7 @@ int critic_adam_step(pnpx_ctx* ctx, const float* grad_dev, size_t n, float lr, f
 
 int critic_optim_state(pnpx_ctx* ctx, float* exp_avg_dst, float* exp_avg_sq_dst, size_t n, long long* step_host, hipStream_t s) {
   CriticNet& N = ctx->critic;
-  if (!N.loaded) {
-    set_error("pnpx_critic_optim_state called before a critic was loaded");
-    return PNPX_ERR_NO_WEIGHTS;
-  }
-  if (!exp_avg_dst || !exp_avg_sq_dst || n != critic_num_params(N.num_inputs)) {
-    set_error("pnpx_critic_optim_state: the loaded critic (%d inputs) has %zu parameters, got room for %zu", N.num_inputs,
-              critic_num_params(N.num_inputs), n);
-    return PNPX_ERR_ARG;
-  }
+  PNPX_TRY(check_vector(N, "pnpx_critic_optim_state", exp_avg_dst && exp_avg_sq_dst, n, nullptr));
   if (N.optim.p) {
     const OptimState o = optim_state(N, n);
     PNPX_HIP(hipMemcpyAsync(exp_avg_dst, o.m, n * sizeof(float), hipMemcpyDeviceToDevice, s));

@@ -20,6 +20,9 @@ struct CopyDesc {
   unsigned src, dst, n;
   unsigned space;          // source: 0 = the parameter vector; 1 = the folded BatchNorm shifts (actor only)
 };
+// blob[dst + i] = (space ? sh : P)[src + i] for the descriptors copy_dev[0 .. grid.y) (device memory), grid.x blocks of 256
+// elements each (live_params.hip).  sh may be null when no descriptor has space 1 (the critic).
+int launch_live_copy(const CopyDesc* copy_dev, dim3 grid, const float* P, const float* sh, float* blob, hipStream_t s);
 
 __device__ inline int hs_row_channel_dev(int row) {   // conv_hs.hip::hs_row_channel
   const int kg = (row >> 2) & 1, r = (row & 3) + 4 * (row >> 3);

@@ -265,12 +265,10 @@ void policy_free(pnpx_ctx* ctx) {
   PolicyNet& N = ctx->policy;
   if (N.weights.p) (void)hipFree(N.weights.p);
   if (N.arena.p) (void)hipFree(N.arena.p);
-  if (N.master.p) (void)hipFree(N.master.p);
-  if (N.pack_ws.p) (void)hipFree(N.pack_ws.p);
-  if (N.readback) (void)hipHostFree(N.readback);
+  N.live.free();
+  N.pack_ws.free();
   if (N.raw.weights.p) (void)hipFree(N.raw.weights.p);
-  if (N.raw_ws.p) (void)hipFree(N.raw_ws.p);
-  if (N.raw_readback) (void)hipHostFree(N.raw_readback);
+  N.raw_ws.free();
   if (N.train_ws.p) (void)hipFree(N.train_ws.p);
   if (N.bn_buf.p) (void)hipFree(N.bn_buf.p);
   N = PolicyNet();
@@ -388,7 +386,8 @@ int policy_load(pnpx_ctx* ctx, const float* params, size_t n, int num_inputs, in
   N.fc_det2_w = spi_head ? base + o_d2w : nullptr;
   N.fc_det2_b = spi_head ? base + o_d2b : nullptr;
   // live weights: the raw parameters stay on the device for pnpx_policy_params / another device's context
-  const int st = policy_keep_params(ctx, params, n);
+  int st = N.live.alloc(n, "policy parameter");
+  if (st == PNPX_OK) st = N.live.set_host(params);
   if (st != PNPX_OK) {
     policy_free(ctx);
     return st;

@@ -269,7 +269,7 @@ int policy_forward_train(pnpx_ctx* ctx, const float* ob, float* probs, float* de
   auto hsc = [&](size_t off) { return reinterpret_cast<char*>(A + off); };
   auto rec = [&](size_t off) { return reinterpret_cast<HsRec*>(A + off); };
   double* part = reinterpret_cast<double*>(A + P.part);
-  float* params = static_cast<float*>(N.master.p);
+  float* params = N.live.p();
   float* st_mean = static_cast<float*>(N.bn_buf.p);
   float* st_var = st_mean + POLICY_BN_CHANNELS;
   float* st_scale = st_var + POLICY_BN_CHANNELS;

@@ -1,4 +1,4 @@
-// Policy actor: live weights.  The context keeps the flat fp32 parameter vector on the device (PolicyNet::master, after
+// Policy actor: live weights.  The context keeps the flat fp32 parameter vector on the device (PolicyNet::live, after
 // either load entry); pnpx_policy_load_device derives every packed layout the forward reads from it with five launches on
 // the caller's stream and refreshes an already loaded actor in place -- no allocation, no device-wide synchronisation, the
 // activation arena is kept.  The per-convolution weight scales are launch arguments of the half-split instances, so a
@@ -14,7 +14,7 @@
 //                        launches over the space-to-depth input (0x01B), the 4 shortcuts (0x010): hi / lo f16 fragments
 //   pol_pack_f32_kernel  the stem and the 4 stage entries (conv1 + shortcut rows merged) as fp32 [8 channels][64 couts] tap
 //                        slices in PolStep order (option policy_s2_hs = 0)
-//   pol_copy_kernel      the shifts as biases, the head matrices
+//   live_copy_kernel     the shifts as biases, the head matrices (live_params.hip, shared with the critic)
 //
 // The host decides which fp32 tap slices exist by looking at the values; here presence is STRUCTURAL: over the space-to-depth
 // input a 3x3 stride-2 convolution touches tap 4 of phase (0,0), taps 3, 4 of phase (0,1), taps 1, 4 of phase (1,0) and taps
@@ -64,7 +64,7 @@ struct PolicyLayout {        // the table + the blob offsets (floats) the host n
   int f32_cout[NF32], f32_K[NF32], f32_split[NF32];
   size_t hs_bias[NCV];
   size_t smw, smb, dw, db, d2w, d2b, total;
-  unsigned max_hs_items, max_f32_items, max_copy;
+  PackDims dims;             // the launch dimensions of T (stored with the workspace the table is uploaded to)
   std::vector<PolStep> steps[NF32];
   std::vector<int> nsteps[NF32];
 };
@@ -83,30 +83,19 @@ __host__ __device__ inline int phase_taps(int ph, int* taps) {
 bool make_layout(int num_inputs, int n_det, int spi_head, PolicyLayout& L) {
   L = PolicyLayout();
   const int cin_pad = (num_inputs + 7) / 8 * 8;
-  size_t src = 0, dst = 0;
+  BlobCursor cur;
   unsigned chan = 0;
   int ncopy = 0;
   bool ok = true;
-  auto take = [&](size_t n) {
-    const size_t r = src;
-    src += n;
-    return (unsigned)r;
-  };
-  auto put = [&](size_t n) {
-    dst = (dst + 255) & ~(size_t)255;
-    const size_t r = dst;
-    dst += n;
-    return r;
-  };
   auto copy = [&](unsigned from, size_t to, size_t n, unsigned space) {
     if (ncopy < MAXCOPY) L.T.copy[ncopy] = CopyDesc{from, (unsigned)to, (unsigned)n, space};
     ++ncopy;
-    if (n > L.max_copy) L.max_copy = (unsigned)n;
+    if (n > L.dims.max_copy) L.dims.max_copy = (unsigned)n;
   };
   auto take_conv = [&](int ci, int cout, int cin, int ks) {
     PolFoldDesc& F = L.T.fold[ci];
-    F.src_w = take((size_t)cout * cin * ks);
-    F.src_bn = take((size_t)4 * cout);
+    F.src_w = cur.take((size_t)cout * cin * ks);
+    F.src_bn = cur.take((size_t)4 * cout);
     F.chan0 = chan;
     F.cout = cout;
     F.fan = cin * ks;
@@ -128,10 +117,10 @@ bool make_layout(int num_inputs, int n_det, int spi_head, PolicyLayout& L) {
     P.cin = cin;
     P.Cp = Cp;
     P.items = (unsigned)((size_t)P.rows * (P.K / 8) * P.nt);
-    P.dst = (unsigned)put((size_t)P.rows * P.K * P.nt);
+    P.dst = (unsigned)cur.put((size_t)P.rows * P.K * P.nt);
     ok = ok && P.rows % 64 == 0 && P.K % 16 == 0;
-    if (P.items > L.max_hs_items) L.max_hs_items = P.items;
-    L.hs_bias[ci] = put(F.cout);
+    if (P.items > L.dims.max_items) L.dims.max_items = P.items;
+    L.hs_bias[ci] = cur.put(F.cout);
     copy(F.chan0, L.hs_bias[ci], F.cout, 1);
   };
   // fp32 PolStep launch fi: convolution c1 (3x3 stride 2) [+ shortcut c2]
@@ -161,17 +150,17 @@ bool make_layout(int num_inputs, int n_det, int spi_head, PolicyLayout& L) {
       }
     ok = ok && nsl == (unsigned)(D.nct1 * nc * 9 + D.nct2 * nc);
     D.items = nsl * 128;
-    if (D.items > L.max_f32_items) L.max_f32_items = D.items;
-    L.f32_w[fi] = put((size_t)nsl * 512 + 1024);   // + the guard behind the last slice
+    if (D.items > L.dims.max_f32_items) L.dims.max_f32_items = D.items;
+    L.f32_w[fi] = cur.put((size_t)nsl * 512 + 1024);   // + the guard behind the last slice
     D.dst = (unsigned)L.f32_w[fi];
     L.f32_cout[fi] = nct * 64;
     L.f32_K[fi] = 4 * Cp;
     L.f32_split[fi] = p;
-    L.f32_bias[fi] = put((size_t)nct * 64);
+    L.f32_bias[fi] = cur.put((size_t)nct * 64);
     copy(L.T.fold[c1].chan0, L.f32_bias[fi], p, 1);
     if (c2 >= 0) copy(L.T.fold[c2].chan0, L.f32_bias[fi] + p, p, 1);
-    L.f32_steps[fi] = put(steps.size() * 2);
-    L.f32_nsteps[fi] = put(nsteps.size());
+    L.f32_steps[fi] = cur.put(steps.size() * 2);
+    L.f32_nsteps[fi] = cur.put(nsteps.size());
   };
   take_conv(0, 64, num_inputs, 9);
   put_f32(0, 0, -1, num_inputs, cin_pad);
@@ -193,8 +182,8 @@ bool make_layout(int num_inputs, int n_det, int spi_head, PolicyLayout& L) {
     in_planes = p;
   }
   auto head = [&](size_t n) {
-    const size_t to = put(n);
-    copy(take(n), to, n, 0);
+    const size_t to = cur.put(n);
+    copy(cur.take(n), to, n, 0);
     return to;
   };
   L.smw = head(2 * 512);
@@ -208,10 +197,16 @@ bool make_layout(int num_inputs, int n_det, int spi_head, PolicyLayout& L) {
     L.dw = head((size_t)n_det * 512);
     L.db = head(n_det);
   }
-  L.total = dst + 8192;   // DMA over-read slack
-  L.T.nchan = chan;
-  L.T.ncopy = ncopy;
-  return ok && ncopy <= MAXCOPY && src == policy_num_params(num_inputs, n_det, spi_head) && L.total < ((size_t)1 << 32);
+  L.total = cur.dst + 8192;   // DMA over-read slack
+  L.T.nchan = L.dims.nchan = chan;
+  L.T.ncopy = L.dims.ncopy = ncopy;
+  return ok && ncopy <= MAXCOPY && cur.src == policy_num_params(num_inputs, n_det, spi_head) && L.total < ((size_t)1 << 32);
+}
+
+int layout_of(const char* who, int num_inputs, int n_det, int spi_head, PolicyLayout& L) {
+  if (make_layout(num_inputs, n_det, spi_head, L)) return PNPX_OK;
+  set_error("%s: internal layout error for (%d inputs, %d outputs, spi %d)", who, num_inputs, n_det, spi_head);
+  return PNPX_ERR_SHAPE;
 }
 
 // device workspace: the table, then scale[nchan], shift[nchan], chmax[nchan], the read-back block
@@ -220,9 +215,9 @@ struct PolPackWs {
   float *sc, *sh, *chmax, *rb;
 };
 inline size_t ws_table_bytes() { return (sizeof(PolPackTable) + 255) & ~(size_t)255; }
-inline size_t ws_bytes(unsigned nchan) { return ws_table_bytes() + ((size_t)3 * nchan + NRB) * sizeof(float); }
-inline PolPackWs pack_ws(const DeviceBuf& buf, unsigned nchan) {
-  char* p = static_cast<char*>(buf.p);
+inline PolPackWs pack_ws(const PackWorkspace& W) {
+  const unsigned nchan = W.dims.nchan;
+  char* p = static_cast<char*>(W.ws.p);
   PolPackWs w;
   w.T = reinterpret_cast<PolPackTable*>(p);
   w.sc = reinterpret_cast<float*>(p + ws_table_bytes());
@@ -377,22 +372,11 @@ __global__ __launch_bounds__(256) void pol_pack_f32_kernel(const PolPackTable* _
   *reinterpret_cast<float4*>(blob + D.dst + (size_t)sl * 512 + c * 64 + m4) = out;
 }
 
-__global__ __launch_bounds__(256) void pol_copy_kernel(const PolPackTable* __restrict__ T, const float* __restrict__ P,
-                                                       const float* __restrict__ sh, float* __restrict__ blob) {
-  const CopyDesc C = T->copy[blockIdx.y];
-  const unsigned i = blockIdx.x * 256 + threadIdx.x;
-  if (i < C.n) blob[C.dst + i] = (C.space ? sh : P)[C.src + i];
-}
-
 // a fresh blob in the structural layout: zero padding and guards, the step lists; the packing workspace with its table
-int alloc_device_layout(PolicyPack& N, DeviceBuf& ws, float*& readback, const PolicyLayout& L) {
+int alloc_device_layout(PolicyPack& N, PackWorkspace& W, const PolicyLayout& L) {
   PNPX_TRY(alloc_dev(N.weights, L.total * sizeof(float), "policy weight"));
-  PNPX_TRY(alloc_dev(ws, ws_bytes(L.T.nchan), "policy packing workspace"));
-  void* h = nullptr;
-  PNPX_HIP(hipHostMalloc(&h, NRB * sizeof(float), hipHostMallocDefault));
-  readback = static_cast<float*>(h);
+  PNPX_TRY(W.alloc(&L.T, sizeof(PolPackTable), (size_t)3 * L.dims.nchan * sizeof(float), NRB, L.dims, "policy packing workspace"));
   PNPX_HIP(hipMemset(N.weights.p, 0, N.weights.bytes));
-  PNPX_HIP(hipMemcpy(ws.p, &L.T, sizeof(PolPackTable), hipMemcpyHostToDevice));
   float* base = static_cast<float*>(N.weights.p);
   static_assert(sizeof(PolStep) == 8, "PolStep layout");
   for (int i = 0; i < NF32; ++i) {
@@ -434,23 +418,24 @@ void bind_blob(PolicyPack& N, const PolicyLayout& L, int spi_head) {
 }
 
 // master -> weight blob on stream s, then the one read-back: the 21 half-split scales.  raw: the fold-free packing (PolicyNet::raw)
-int repack(pnpx_ctx* ctx, const PolicyLayout& L, hipStream_t s, bool raw = false) {
+int repack(pnpx_ctx* ctx, hipStream_t s, bool raw = false) {
   PolicyNet& N = ctx->policy;
   PolicyPack& K = raw ? N.raw : static_cast<PolicyPack&>(N);
-  float* const rb_host = raw ? N.raw_readback : N.readback;
-  const PolPackWs w = pack_ws(raw ? N.raw_ws : N.pack_ws, L.T.nchan);
-  const float* P = static_cast<const float*>(N.master.p);
+  const PackWorkspace& W = raw ? N.raw_ws : N.pack_ws;
+  const PackDims& d = W.dims;
+  float* const rb_host = W.readback;
+  const PolPackWs w = pack_ws(W);
+  const float* P = N.live.p();
   float* blob = static_cast<float*>(K.weights.p);
-  hipLaunchKernelGGL(pol_fold_kernel, dim3(L.T.nchan), dim3(64), 0, s, w.T, P, w.sc, w.sh, w.chmax, raw ? 1 : 0);
+  hipLaunchKernelGGL(pol_fold_kernel, dim3(d.nchan), dim3(64), 0, s, w.T, P, w.sc, w.sh, w.chmax, raw ? 1 : 0);
   PNPX_LAUNCH_CHECK();
   hipLaunchKernelGGL(pol_scale_kernel, dim3(NCV), dim3(256), 0, s, w.T, w.chmax, w.rb);
   PNPX_LAUNCH_CHECK();
-  hipLaunchKernelGGL(pol_pack_hs_kernel, dim3((L.max_hs_items + 255) / 256, NCV), dim3(256), 0, s, w.T, P, w.sc, w.rb, blob);
+  hipLaunchKernelGGL(pol_pack_hs_kernel, dim3((d.max_items + 255) / 256, NCV), dim3(256), 0, s, w.T, P, w.sc, w.rb, blob);
   PNPX_LAUNCH_CHECK();
-  hipLaunchKernelGGL(pol_pack_f32_kernel, dim3((L.max_f32_items + 255) / 256, NF32), dim3(256), 0, s, w.T, P, w.sc, blob);
+  hipLaunchKernelGGL(pol_pack_f32_kernel, dim3((d.max_f32_items + 255) / 256, NF32), dim3(256), 0, s, w.T, P, w.sc, blob);
   PNPX_LAUNCH_CHECK();
-  hipLaunchKernelGGL(pol_copy_kernel, dim3((L.max_copy + 255) / 256, L.T.ncopy), dim3(256), 0, s, w.T, P, w.sh, blob);
-  PNPX_LAUNCH_CHECK();
+  PNPX_TRY(launch_live_copy(w.T->copy, dim3((d.max_copy + 255) / 256, d.ncopy), P, w.sh, blob, s));
   PNPX_HIP(hipMemcpyAsync(rb_host, w.rb, NCV * sizeof(float), hipMemcpyDeviceToHost, s));
   PNPX_HIP(hipStreamSynchronize(s));
   for (int i = 0; i < NCV; ++i)
@@ -473,13 +458,6 @@ int repack(pnpx_ctx* ctx, const PolicyLayout& L, hipStream_t s, bool raw = false
 
 }  // namespace
 
-int policy_keep_params(pnpx_ctx* ctx, const float* params_host, size_t n) {
-  PolicyNet& N = ctx->policy;
-  PNPX_TRY(alloc_dev(N.master, n * sizeof(float), "policy parameter"));
-  PNPX_HIP(hipMemcpy(N.master.p, params_host, n * sizeof(float), hipMemcpyHostToDevice));
-  return PNPX_OK;
-}
-
 int policy_load_device(pnpx_ctx* ctx, const float* params_dev, size_t n, int num_inputs, int n_det, int spi_head, hipStream_t s) {
   spi_head = spi_head ? 1 : 0;
   const bool shape_ok = num_inputs >= 1 && num_inputs <= 64 && n_det >= 1 && n_det <= 64;
@@ -489,15 +467,12 @@ int policy_load_device(pnpx_ctx* ctx, const float* params_dev, size_t n, int num
     return PNPX_ERR_ARG;
   }
   PolicyNet& N = ctx->policy;
-  PolicyLayout L;
-  if (!make_layout(num_inputs, n_det, spi_head, L)) {
-    set_error("pnpx_policy_load_device: internal layout error for (%d inputs, %d outputs, spi %d)", num_inputs, n_det, spi_head);
-    return PNPX_ERR_SHAPE;
-  }
   const bool same_net = N.loaded && N.num_inputs == num_inputs && N.n_det == n_det && N.spi_head == spi_head;
   if (!(same_net && N.dev_layout)) {
     // first load / another network / a blob in the host's value-dependent layout: allocate (a refresh allocates nothing).
     // The arena of the same network is kept: its layout depends on the padded input channels and the image size only.
+    PolicyLayout L;
+    PNPX_TRY(layout_of("pnpx_policy_load_device", num_inputs, n_det, spi_head, L));
     PNPX_HIP(hipDeviceSynchronize());
     const DeviceBuf arena = N.arena;
     const int capB = N.capB, capH = N.capH, capW = N.capW;
@@ -513,8 +488,8 @@ int policy_load_device(pnpx_ctx* ctx, const float* params_dev, size_t n, int num
     N.cin_pad = (num_inputs + 7) / 8 * 8;
     N.n_det = n_det;
     N.spi_head = spi_head;
-    int st = alloc_device_layout(N, N.pack_ws, N.readback, L);
-    if (st == PNPX_OK) st = alloc_dev(N.master, n * sizeof(float), "policy parameter");
+    int st = alloc_device_layout(N, N.pack_ws, L);
+    if (st == PNPX_OK) st = N.live.alloc(n, "policy parameter");
     if (st != PNPX_OK) {
       policy_free(ctx);
       return st;
@@ -523,36 +498,30 @@ int policy_load_device(pnpx_ctx* ctx, const float* params_dev, size_t n, int num
     N.dev_layout = true;
   }
   N.raw_valid = false;   // new weights: the train-mode packing follows on the next train forward
-  if (params_dev != N.master.p) PNPX_HIP(hipMemcpyAsync(N.master.p, params_dev, n * sizeof(float), hipMemcpyDeviceToDevice, s));
-  return repack(ctx, L, s);
+  PNPX_TRY(N.live.set_device(params_dev, s));
+  return repack(ctx, s);
 }
 
 int policy_pack_raw(pnpx_ctx* ctx, hipStream_t s) {
   PolicyNet& N = ctx->policy;
-  PolicyLayout L;
-  if (!make_layout(N.num_inputs, N.n_det, N.spi_head, L)) {
-    set_error("policy train forward: internal layout error for (%d inputs, %d outputs, spi %d)", N.num_inputs, N.n_det, N.spi_head);
-    return PNPX_ERR_SHAPE;
-  }
   if (!N.raw.weights.p) {
-    PNPX_TRY(alloc_device_layout(N.raw, N.raw_ws, N.raw_readback, L));
+    PolicyLayout L;
+    PNPX_TRY(layout_of("policy train forward", N.num_inputs, N.n_det, N.spi_head, L));
+    PNPX_TRY(alloc_device_layout(N.raw, N.raw_ws, L));
     bind_blob(N.raw, L, N.spi_head);
   }
-  return repack(ctx, L, s, true);
+  return repack(ctx, s, true);
 }
 
 int policy_refresh_eval(pnpx_ctx* ctx, hipStream_t s) {
   PolicyNet& N = ctx->policy;
-  PolicyLayout L;
-  if (!make_layout(N.num_inputs, N.n_det, N.spi_head, L)) {
-    set_error("policy refresh: internal layout error for (%d inputs, %d outputs, spi %d)", N.num_inputs, N.n_det, N.spi_head);
-    return PNPX_ERR_SHAPE;
-  }
   if (!N.dev_layout) {   // a blob in policy_load's value-dependent layout: replace it by the structural one (the parameter vector stays)
+    PolicyLayout L;
+    PNPX_TRY(layout_of("policy refresh", N.num_inputs, N.n_det, N.spi_head, L));
     PNPX_HIP(hipDeviceSynchronize());
     if (N.weights.p) PNPX_HIP(hipFree(N.weights.p));
     N.weights = DeviceBuf();
-    const int st = alloc_device_layout(N, N.pack_ws, N.readback, L);
+    const int st = alloc_device_layout(N, N.pack_ws, L);
     if (st != PNPX_OK) {   // nothing left to run on: the context holds no actor any more
       policy_free(ctx);
       return st;
@@ -560,7 +529,7 @@ int policy_refresh_eval(pnpx_ctx* ctx, hipStream_t s) {
     bind_blob(N, L, N.spi_head);
     N.dev_layout = true;
   }
-  return repack(ctx, L, s);
+  return repack(ctx, s);
 }
 
 int policy_params(pnpx_ctx* ctx, float* dst_dev, size_t n, hipStream_t s) {
@@ -575,8 +544,7 @@ int policy_params(pnpx_ctx* ctx, float* dst_dev, size_t n, hipStream_t s) {
               N.num_inputs, N.n_det, N.spi_head, want, n);
     return PNPX_ERR_ARG;
   }
-  PNPX_HIP(hipMemcpyAsync(dst_dev, N.master.p, n * sizeof(float), hipMemcpyDeviceToDevice, s));
-  return PNPX_OK;
+  return N.live.copy_out(dst_dev, s);
 }
 
 }  // namespace pnpx

@@ -19,42 +19,40 @@ _ctx_ids = itertools.count(1)
 _ctx_by_id = weakref.WeakValueDictionary()
 
 
+def _flatten(state_dict, specs, what, alt=None):
+    """The entries of `state_dict` that `specs` ([(key, shape)]) names, in its order, as one contiguous fp32 numpy vector; a
+    missing key or a wrong shape raises PnpxError naming it (`what`: whose state_dict).  alt: {leaf: other leaf} -- a second
+    spelling of a key's last component, tried when the first is absent."""
+    chunks = []
+    for key, shape in specs:
+        v = state_dict.get(key)
+        stem, _, leaf = key.rpartition(".")
+        if v is None and alt and leaf in alt:
+            v = state_dict.get(f"{stem}.{alt[leaf]}")
+        if v is None:
+            raise PnpxError(f"{what} state_dict is missing '{key}'")
+        v = v.detach().cpu().numpy() if isinstance(v, torch.Tensor) else np.asarray(v)
+        if tuple(v.shape) != tuple(shape):
+            raise PnpxError(f"'{key}' has shape {tuple(v.shape)}, expected {tuple(shape)}")
+        chunks.append(np.ascontiguousarray(v, dtype=np.float32).reshape(-1))
+    return np.concatenate(chunks)
+
+
 def critic_flat_params(state_dict, num_inputs):
     """The flat fp32 parameter vector pnpx_critic_load takes (synth.critic_param_specs order) from a critic state_dict.
     Weight-norm entries are accepted under the reference's names (`*.weight_g` / `*.weight_v`) and under the names current
     PyTorch saves the same module with (`*.parametrizations.weight.original0` / `original1`); a missing key or a wrong shape
     raises PnpxError naming it."""
     from .synth import critic_param_specs
-    alt = {"weight_g": "parametrizations.weight.original0", "weight_v": "parametrizations.weight.original1"}
-    chunks = []
-    for key, shape in critic_param_specs(num_inputs):
-        v = state_dict.get(key)
-        if v is None:
-            stem, _, leaf = key.rpartition(".")
-            v = state_dict.get(f"{stem}.{alt[leaf]}") if leaf in alt else None
-        if v is None:
-            raise PnpxError(f"critic state_dict is missing '{key}'")
-        v = v.detach().cpu().numpy() if isinstance(v, torch.Tensor) else np.asarray(v)
-        if tuple(v.shape) != tuple(shape):
-            raise PnpxError(f"'{key}' has shape {tuple(v.shape)}, expected {tuple(shape)}")
-        chunks.append(np.ascontiguousarray(v, dtype=np.float32).reshape(-1))
-    return np.concatenate(chunks)
+    return _flatten(state_dict, critic_param_specs(num_inputs), "critic",
+                    {"weight_g": "parametrizations.weight.original0", "weight_v": "parametrizations.weight.original1"})
 
 
 def policy_flat_params(state_dict, num_inputs, n_det, spi_head=False):
     """The flat fp32 parameter vector pnpx_policy_load takes (synth.policy_param_specs order) from an actor state_dict; a
     missing key or a wrong shape raises PnpxError naming it.  Integer num_batches_tracked entries are not part of it."""
     from .synth import policy_param_specs
-    chunks = []
-    for key, shape in policy_param_specs(num_inputs, n_det, spi_head):
-        if key not in state_dict:
-            raise PnpxError(f"policy state_dict is missing '{key}'")
-        v = state_dict[key]
-        v = v.detach().cpu().numpy() if isinstance(v, torch.Tensor) else np.asarray(v)
-        if tuple(v.shape) != tuple(shape):
-            raise PnpxError(f"'{key}' has shape {tuple(v.shape)}, expected {tuple(shape)}")
-        chunks.append(np.ascontiguousarray(v, dtype=np.float32).reshape(-1))
-    return np.concatenate(chunks)
+    return _flatten(state_dict, policy_param_specs(num_inputs, n_det, spi_head), "policy")
 
 
 def context_by_id(cid):
@@ -92,16 +90,7 @@ class Context:
     def load_unet(self, state_dict):
         """state_dict: mapping with the reference's 56 key names -> tensors/ndarrays (any device)."""
         from .synth import unet_param_specs
-        chunks = []
-        for key, shape in unet_param_specs():
-            if key not in state_dict:
-                raise PnpxError(f"denoiser state_dict is missing '{key}'")
-            v = state_dict[key]
-            v = v.detach().cpu().numpy() if isinstance(v, torch.Tensor) else np.asarray(v)
-            if tuple(v.shape) != tuple(shape):
-                raise PnpxError(f"'{key}' has shape {tuple(v.shape)}, expected {tuple(shape)}")
-            chunks.append(np.ascontiguousarray(v, dtype=np.float32).reshape(-1))
-        flat = np.concatenate(chunks)
+        flat = _flatten(state_dict, unet_param_specs(), "denoiser")
         check(_lib.lib().pnpx_unet_load(self.handle, flat.ctypes.data_as(C.c_void_p), flat.size))
         self._has_weights = True
         self.is_drunet = False
@@ -109,16 +98,7 @@ class Context:
     def load_drunet(self, state_dict, nb=4):
         """state_dict with KAIR's UNetRes / DRUNet key names (synth.drunet_param_specs) -> the context's denoiser."""
         from .synth import drunet_param_specs
-        chunks = []
-        for key, shape in drunet_param_specs(nb=nb):
-            if key not in state_dict:
-                raise PnpxError(f"DRUNet state_dict is missing '{key}'")
-            v = state_dict[key]
-            v = v.detach().cpu().numpy() if isinstance(v, torch.Tensor) else np.asarray(v)
-            if tuple(v.shape) != tuple(shape):
-                raise PnpxError(f"'{key}' has shape {tuple(v.shape)}, expected {tuple(shape)}")
-            chunks.append(np.ascontiguousarray(v, dtype=np.float32).reshape(-1))
-        flat = np.concatenate(chunks)
+        flat = _flatten(state_dict, drunet_param_specs(nb=nb), "DRUNet")
         check(_lib.lib().pnpx_drunet_load(self.handle, flat.ctypes.data_as(C.c_void_p), flat.size, int(nb)))
         self._has_weights = True
         self.is_drunet = True
@@ -130,9 +110,9 @@ class Context:
                                           int(n_det), int(bool(spi_head))))
         self._policy = (int(num_inputs), int(n_det), bool(spi_head))
 
-    def _policy_vector(self, t, who, num_inputs, n_det, spi_head):
-        """A flat actor parameter vector as the library takes it (the checks of _critic_vector): fp32, contiguous, on this
-        context's device, of the length of an actor with this head."""
+    def _flat_vector(self, t, who, want, what):
+        """A flat parameter vector as the library takes it: fp32, contiguous, on this context's device, `want` floats long
+        (None: not checked here); `what` names the network that has `want` parameters."""
         if not isinstance(t, torch.Tensor):
             raise PnpxError(f"{who}: expected a torch.Tensor, got {type(t).__name__}")
         if t.device != self.device:
@@ -141,18 +121,26 @@ class Context:
             raise PnpxError(f"{who}: expected float32, got {t.dtype}")
         if t.dim() != 1 or not t.is_contiguous():
             raise PnpxError(f"{who}: expected a contiguous 1-D vector, got shape {tuple(t.shape)} with strides {t.stride()}")
-        want = int(_lib.lib().pnpx_policy_num_params(int(num_inputs), int(n_det), int(bool(spi_head))))
-        if t.numel() != want:
-            raise PnpxError(f"{who}: an actor with {num_inputs} inputs and {n_det} outputs"
-                            f"{' (SPI head)' if spi_head else ''} has {want} parameters, got {t.numel()}")
+        if want is not None and t.numel() != want:
+            raise PnpxError(f"{who}: {what} has {want} parameters, got {t.numel()}")
         return t.detach()
+
+    def _live_vector(self, entry, n):
+        """A copy of the live parameter vector of `n` floats that the library's `entry` writes (n None: no such network is
+        loaded, and the entry says so)."""
+        out = torch.empty((1 if n is None else n,), device=self.device, dtype=torch.float32)
+        with torch.cuda.device(self.device):
+            check(entry(self.handle, _p(out), out.numel(), _stream(out)))
+        return out
 
     def load_policy_device(self, flat, num_inputs, n_det, spi_head=False):
         """flat: the actor's fp32 state as one vector on this context's device, in synth.policy_param_specs order (each
         convolution followed by its BatchNorm weight, bias, running_mean, running_var; then the heads).  BatchNorm fold and
         packing run on the device on the current stream; an actor with the same head already loaded here is refreshed in
         place.  Ends with one small read-back (synchronises the current stream)."""
-        flat = self._policy_vector(flat, "load_policy_device", num_inputs, n_det, spi_head)
+        want = int(_lib.lib().pnpx_policy_num_params(int(num_inputs), int(n_det), int(bool(spi_head))))
+        flat = self._flat_vector(flat, "load_policy_device", want, f"an actor with {num_inputs} inputs and {n_det} outputs"
+                                                                    f"{' (SPI head)' if spi_head else ''}")
         with torch.cuda.device(self.device):
             st = _lib.lib().pnpx_policy_load_device(self.handle, _p(flat), flat.numel(), int(num_inputs), int(n_det),
                                                     int(bool(spi_head)), _stream(flat))
@@ -163,11 +151,9 @@ class Context:
 
     def policy_params(self):
         """A copy of the live parameter vector (fp32, on this context's device, load_policy_device's order)."""
-        n = int(_lib.lib().pnpx_policy_num_params(*map(int, self._policy))) if self._policy is not None else 1
-        out = torch.empty((n,), device=self.device, dtype=torch.float32)
-        with torch.cuda.device(self.device):
-            check(_lib.lib().pnpx_policy_params(self.handle, _p(out), n, _stream(out)))
-        return out
+        lib = _lib.lib()
+        return self._live_vector(lib.pnpx_policy_params,
+                                 None if self._policy is None else int(lib.pnpx_policy_num_params(*map(int, self._policy))))
 
     def load_critic(self, state_dict, num_inputs):
         """state_dict of the reference's ResNet_wobn(num_inputs, 18, 1) (tfpnp/trainer/mddpg/critic.py) -> native critic
@@ -176,23 +162,6 @@ class Context:
         flat = critic_flat_params(state_dict, num_inputs)
         check(_lib.lib().pnpx_critic_load(self.handle, flat.ctypes.data_as(C.c_void_p), flat.size, int(num_inputs)))
         self._critic = int(num_inputs)
-
-    def _critic_vector(self, t, who, num_inputs):
-        """A flat critic parameter vector as the library takes it: fp32, contiguous, on this context's device, of the length
-        of a critic with `num_inputs` inputs (None: not checked here)."""
-        if not isinstance(t, torch.Tensor):
-            raise PnpxError(f"{who}: expected a torch.Tensor, got {type(t).__name__}")
-        if t.device != self.device:
-            raise PnpxError(f"{who}: parameter vector is on {t.device}, the context is on {self.device}")
-        if t.dtype != torch.float32:
-            raise PnpxError(f"{who}: expected float32, got {t.dtype}")
-        if t.dim() != 1 or not t.is_contiguous():
-            raise PnpxError(f"{who}: expected a contiguous 1-D vector, got shape {tuple(t.shape)} with strides {t.stride()}")
-        if num_inputs is not None:
-            want = int(_lib.lib().pnpx_critic_num_params(int(num_inputs)))
-            if t.numel() != want:
-                raise PnpxError(f"{who}: a critic with {num_inputs} inputs has {want} parameters, got {t.numel()}")
-        return t.detach()
 
     def load_critic_device(self, flat, num_inputs=None):
         """flat: the critic's parameters as one fp32 vector on this context's device, in synth.critic_param_specs order (the
@@ -205,7 +174,8 @@ class Context:
             if num_inputs is None:
                 raise PnpxError(f"load_critic_device: {n} floats is not the parameter count of a critic with 1..64 inputs "
                                 f"(9 inputs: {int(_lib.lib().pnpx_critic_num_params(9))})")
-        flat = self._critic_vector(flat, "load_critic_device", num_inputs)
+        want = None if num_inputs is None else int(_lib.lib().pnpx_critic_num_params(int(num_inputs)))   # None: no tensor
+        flat = self._flat_vector(flat, "load_critic_device", want, f"a critic with {num_inputs} inputs")
         with torch.cuda.device(self.device):
             st = _lib.lib().pnpx_critic_load_device(self.handle, _p(flat), flat.numel(), int(num_inputs), _stream(flat))
         if st != 0:
@@ -216,7 +186,8 @@ class Context:
     def critic_soft_update(self, src_flat, tau):
         """utils/misc.py:81-85 with the loaded critic as the target: params = params * (1.0 - tau) + src_flat * tau in the
         reference's fp32 arithmetic (bit-equal to torch's), then the device-side re-packing of load_critic_device."""
-        src_flat = self._critic_vector(src_flat, "critic_soft_update", self._critic)
+        want = None if self._critic is None else int(_lib.lib().pnpx_critic_num_params(self._critic))   # None: the library refuses
+        src_flat = self._flat_vector(src_flat, "critic_soft_update", want, f"a critic with {self._critic} inputs")
         tau = float(tau)
         with torch.cuda.device(self.device):
             st = _lib.lib().pnpx_critic_soft_update(self.handle, _p(src_flat), src_flat.numel(), 1.0 - tau, tau, _stream(src_flat))
@@ -226,11 +197,9 @@ class Context:
 
     def critic_params(self):
         """A copy of the live parameter vector (fp32, on this context's device, load_critic_device's order)."""
-        n = int(_lib.lib().pnpx_critic_num_params(self._critic)) if self._critic is not None else 1
-        out = torch.empty((n,), device=self.device, dtype=torch.float32)
-        with torch.cuda.device(self.device):
-            check(_lib.lib().pnpx_critic_params(self.handle, _p(out), n, _stream(out)))
-        return out
+        lib = _lib.lib()
+        return self._live_vector(lib.pnpx_critic_params,
+                                 None if self._critic is None else int(lib.pnpx_critic_num_params(self._critic)))
 
     def critic_adam_step(self, grad, lr, betas=(0.9, 0.999), eps=1e-8, max_norm=50.0):
         """clip_grad_norm_(max_norm) + torch.optim.Adam.step() (trainer/mddpg/trainer.py:208-209; no weight decay, no amsgrad)
@@ -258,7 +227,7 @@ class Context:
         want = int(_lib.lib().pnpx_critic_num_params(self._critic))
         if grad.numel() != want:
             raise PnpxError(f"critic_adam_step: a critic with {self._critic} inputs has {want} parameters, got a gradient of {grad.numel()}")
-        grad = self._critic_vector(grad, "critic_adam_step", None)
+        grad = self._flat_vector(grad, "critic_adam_step", None, None)     # (its length: above)
         norm = torch.empty((), device=self.device, dtype=torch.float32)
         with torch.cuda.device(self.device):
             st = _lib.lib().pnpx_critic_adam_step(self.handle, _p(grad), grad.numel(), lr, b1, b2, eps, max_norm, _p(norm), _stream(grad))

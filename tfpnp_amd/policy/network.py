@@ -26,16 +26,24 @@ from collections import OrderedDict
 from typing import Optional
 
 import torch
-import torch.nn as nn
 
-from .. import ops
+from .. import ops, synth
 from .. import torch_ops as T
+from ..live import LiveWeights
 
 
-class ResNetActorBase(nn.Module):
+class ResNetActorBase(LiveWeights):
     spi_head = False
 
     bn_momentum = 0.1           # SynchronizedBatchNorm2d's default (sync_batchnorm/batchnorm.py)
+
+    # live weights (live.py): synth.policy_param_specs order -- every fp32 state_dict entry of the reference actor, running
+    # statistics included; the integer `num_batches_tracked` buffers are not kept (eval-mode BatchNorm does not read them)
+    _noun, _holds = "actor", "_policy"
+    _load, _load_device, _params = "load_policy", "load_policy_device", "policy_params"
+    _specs = staticmethod(synth.policy_param_specs)
+    _flat_params = staticmethod(ops.policy_flat_params)
+    _dict = OrderedDict
 
     def __init__(self, num_inputs, action_bundle, num_actions, state_dict=None, bn_follows_mode=False):
         super().__init__()
@@ -44,9 +52,6 @@ class ResNetActorBase(nn.Module):
         self.num_actions = num_actions
         self.action_range = None
         self.action_bundle = action_bundle
-        self._state = None      # CPU copy of the last load_state_dict; None once the weights were changed on a device
-        self._live = None       # key of the context whose device-resident parameters are the weights (then _state is None)
-        self._ctx = {}
         if state_dict is not None:
             self.load_state_dict(state_dict)
 
@@ -54,95 +59,16 @@ class ResNetActorBase(nn.Module):
     def n_det(self):
         return self.action_bundle * self.num_actions
 
-    # weights: the reference's own state_dict (torch.load of actor.pkl, trainer.py:254-261)
-    def load_state_dict(self, state_dict, strict=True):
-        self._state = {k: (v.detach().cpu() if isinstance(v, torch.Tensor) else v) for k, v in state_dict.items()}
-        self._live = None
-        self._ctx = {}
-
-    @property
-    def device(self):
-        """The device the weights live on: where they were last changed, else the first device they were used on, else None."""
-        key = self._live if self._live is not None else next(iter(self._ctx), None)
-        return None if key is None else torch.device(*key)
-
-    def context(self, device):
-        device = torch.device(device)
-        key = (device.type, device.index if device.index is not None else torch.cuda.current_device())
-        if key not in self._ctx:
-            if self._live is None and self._state is None:
-                raise ValueError('actor weights were not loaded (load_state_dict / load_flat_)')
-            ctx = ops.Context(device)
-            if self._live is not None:
-                # the weights were changed on another device: that device's vector is the truth, not the stale CPU copy
-                ctx.load_policy_device(self._ctx[self._live].policy_params().to(ctx.device), self.in_dim, self.n_det, self.spi_head)
-            else:
-                ctx.load_policy(self._state, self.in_dim, self.n_det, self.spi_head)
-            self._ctx[key] = ctx
-        return self._ctx[key]
-
-    def parameters_flat(self, device):
-        """A copy of the weights as one fp32 vector on `device`, in synth.policy_param_specs order."""
-        return self.context(device).policy_params()
-
-    def load_flat_(self, flat):
-        """Load a flat fp32 vector that lives on a ROCm device (synth.policy_param_specs order: every fp32 state_dict entry
-        of the reference actor, running statistics included): BatchNorm fold and packing run on that device; a context that
-        already exists there is refreshed in place.  Returns self."""
-        if not isinstance(flat, torch.Tensor):
-            raise ops.PnpxError(f"load_flat_: expected a torch.Tensor, got {type(flat).__name__}")
-        if flat.device.type != "cuda":
-            raise ops.PnpxError(f"load_flat_: device {flat.device}; tfpnp_amd runs on MI355X only, there is no CPU path")
-        key = (flat.device.type, flat.device.index if flat.device.index is not None else torch.cuda.current_device())
-        ctx = self._ctx.get(key)
-        fresh = ctx is None
-        if fresh:
-            ctx = ops.Context(torch.device(*key))
-        try:
-            ctx.load_policy_device(flat, self.in_dim, self.n_det, self.spi_head)
-        except ops.PnpxError:
-            if not fresh and ctx._policy is None:      # the refresh itself failed: this context holds no actor any more
-                del self._ctx[key]
-                if self._live == key:
-                    self._live = None
-            raise
-        # every other copy is stale from here on
-        self._ctx = {key: ctx}
-        self._live = key
-        self._state = None
-        return self
-
-    def state_dict(self, *args, destination=None, prefix='', keep_vars=False):
-        """The fp32 entries of the reference actor's state_dict (synth.policy_param_specs), read from the live weights.
-        Loading it into a fresh native actor reproduces this one bit for bit.  The integer `num_batches_tracked` buffers of
-        the reference's BatchNorm layers are not kept: eval-mode BatchNorm does not read them."""
-        from ..synth import policy_param_specs
-        out = destination if destination is not None else OrderedDict()
-        if self._live is not None:
-            flat = self._ctx[self._live].policy_params()
-        elif self._state is not None:
-            flat = torch.from_numpy(ops.policy_flat_params(self._state, self.in_dim, self.n_det, self.spi_head))
-        else:
-            return out
-        pos = 0
-        for key, shape in policy_param_specs(self.in_dim, self.n_det, self.spi_head):
-            n = 1
-            for d in shape:
-                n *= d
-            out[prefix + key] = flat[pos:pos + n].view(shape).clone()
-            pos += n
-        return out
+    def _shape(self):
+        return self.in_dim, self.n_det, self.spi_head
 
     def forward(self, state, idx_stop, train, hidden):
         """-> (action dict incl. 'idx_stop', log-prob of idx_stop [B,1], entropy of the stop head [B,1], hidden)"""
         ctx = self.context(state.device)
         if self.bn_follows_mode and self.training:
             # batch statistics; the running statistics move on this device: its vector is the truth from here on
-            p_stop, det = T.call("policy_forward_train", state, self.bn_momentum, True, ctx.cid)
-            key = next(k for k, c in self._ctx.items() if c is ctx)
-            self._ctx = {key: ctx}
-            self._live = key
-            self._state = None
+            p_stop, det = self._mutate(self._key(state.device),
+                                       lambda c: T.call("policy_forward_train", state, self.bn_momentum, True, c.cid))
         else:
             p_stop, det = T.call("policy_forward", state, ctx.cid)   # [B,2] softmax, [B,n_det] sigmoid
         logp = torch.log(p_stop.clamp_min(torch.finfo(p_stop.dtype).eps))     # Categorical's own clamp

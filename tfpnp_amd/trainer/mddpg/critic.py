@@ -25,129 +25,39 @@ Out of scope: the actor's loss and a trainable actor, weight decay / amsgrad / o
 than 18.  (The native actor has the same live weights: policy/network.py; the replay memory is utils/rpm.py.)
 """
 import torch
-import torch.nn as nn
 
-from ... import ops
+from ... import ops, synth
 from ... import torch_ops as T
+from ...live import LiveWeights
 
 
-def _key(device):
-    device = torch.device(device)
-    if device.type != "cuda":
-        raise ops.PnpxError(f"ResNet_wobn: device {device}; tfpnp_amd runs on MI355X only, there is no CPU path")
-    return (device.type, device.index if device.index is not None else torch.cuda.current_device())
+class ResNet_wobn(LiveWeights):
+    # live weights (live.py): synth.critic_param_specs order -- the 82 tensors of the reference critic under its key names
+    # (`*.weight_g` / `*.weight_v`; a state dict in either weight-norm spelling loads), e.g.
+    # torch.cat([p.flatten() for p in critic.parameters()])
+    _noun, _holds = "critic", "_critic"
+    _load, _load_device, _params = "load_critic", "load_critic_device", "critic_params"
+    _specs = staticmethod(synth.critic_param_specs)
+    _flat_params = staticmethod(ops.critic_flat_params)
 
-
-class ResNet_wobn(nn.Module):
     def __init__(self, num_inputs, depth, num_outputs, state_dict=None):
         super().__init__()
         if depth != 18 or num_outputs != 1:
             raise NotImplementedError(f"ResNet_wobn: only depth 18 with one output is implemented (the critic every task "
                                       f"builds), got depth {depth}, {num_outputs} outputs")
         self.in_dim = num_inputs
-        self._state = None      # CPU copy of the last load_state_dict; None once the weights were changed on a device
-        self._live = None       # key of the context whose device-resident parameters are the weights (then _state is None)
-        self._ctx = {}
         if state_dict is not None:
             self.load_state_dict(state_dict)
 
-    # weights: the reference's own state_dict (torch.load of critic.pkl, trainer.py:254-261), either weight-norm spelling
-    def load_state_dict(self, state_dict, strict=True):
-        self._state = {k: (v.detach().cpu() if isinstance(v, torch.Tensor) else v) for k, v in state_dict.items()}
-        self._live = None
-        self._ctx = {}
-
-    @property
-    def device(self):
-        """The device the weights live on: where they were last changed, else the first device they were used on, else None."""
-        key = self._live if self._live is not None else next(iter(self._ctx), None)
-        return None if key is None else torch.device(*key)
-
-    def context(self, device):
-        key = _key(device)
-        if key not in self._ctx:
-            ctx = ops.Context(torch.device(*key))
-            if self._live is not None:
-                # the weights were changed on another device: that device's vector is the truth, not the stale CPU copy
-                ctx.load_critic_device(self._ctx[self._live].critic_params().to(ctx.device), self.in_dim)
-            elif self._state is not None:
-                ctx.load_critic(self._state, self.in_dim)
-            else:
-                raise ValueError('critic weights were not loaded (load_state_dict / load_flat_)')
-            self._ctx[key] = ctx
-        return self._ctx[key]
-
-    def _changed_on(self, key):
-        """The parameters of context `key` were changed on its device: every other copy is stale from here on."""
-        self._ctx = {key: self._ctx[key]}
-        self._live = key
-        self._state = None
-
-    def parameters_flat(self, device):
-        """A copy of the parameters as one fp32 vector on `device`, in synth.critic_param_specs order."""
-        return self.context(device).critic_params()
-
-    def load_flat_(self, flat):
-        """Load a flat fp32 parameter vector that lives on a ROCm device (synth.critic_param_specs order, e.g.
-        torch.cat([p.flatten() for p in critic.parameters()]) of the reference critic): fold and packing run on that
-        device; a context that already exists there is refreshed in place.  Returns self."""
-        if not isinstance(flat, torch.Tensor):
-            raise ops.PnpxError(f"load_flat_: expected a torch.Tensor, got {type(flat).__name__}")
-        key = _key(flat.device)
-        ctx = self._ctx.get(key)
-        fresh = ctx is None
-        if fresh:
-            ctx = ops.Context(torch.device(*key))
-        try:
-            ctx.load_critic_device(flat, self.in_dim)
-        except ops.PnpxError:
-            if not fresh and ctx._critic is None:      # the refresh itself failed: this context holds no critic any more
-                del self._ctx[key]
-                if self._live == key:
-                    self._live = None
-            raise
-        self._ctx[key] = ctx
-        self._changed_on(key)
-        return self
+    def _shape(self):
+        return (self.in_dim,)
 
     def soft_update_(self, src_flat, tau):
         """parameters = parameters * (1.0 - tau) + src_flat * tau on src_flat's device (utils.misc.soft_update)."""
         if not isinstance(src_flat, torch.Tensor):
             raise ops.PnpxError(f"soft_update_: expected a torch.Tensor, got {type(src_flat).__name__}")
-        key = _key(src_flat.device)
-        ctx = self.context(src_flat.device)
-        try:
-            ctx.critic_soft_update(src_flat, tau)
-        except ops.PnpxError:
-            if ctx._critic is None:
-                del self._ctx[key]
-                if self._live == key:
-                    self._live = None
-            raise
-        self._changed_on(key)
+        self._mutate(self._key(src_flat.device), lambda ctx: ctx.critic_soft_update(src_flat, tau))
         return self
-
-    def state_dict(self, *args, destination=None, prefix='', keep_vars=False):
-        """The 82 tensors under the reference's key names (`*.weight_g` / `*.weight_v`), read from the live weights --
-        torch.save(critic.state_dict(), ...) of trainer.py:254-261.  Loading it into a fresh ResNet_wobn reproduces this
-        critic bit for bit."""
-        from ...synth import critic_param_specs
-        out = destination if destination is not None else {}
-        specs = critic_param_specs(self.in_dim)
-        if self._live is not None:
-            flat = self._ctx[self._live].critic_params()
-        elif self._state is not None:
-            flat = torch.from_numpy(ops.critic_flat_params(self._state, self.in_dim))
-        else:
-            return out
-        pos = 0
-        for key, shape in specs:
-            n = 1
-            for s in shape:
-                n *= s
-            out[prefix + key] = flat[pos:pos + n].view(shape).clone()
-            pos += n
-        return out
 
     def forward(self, x):
         """x [B, num_inputs, H, W] (H, W multiples of 32) -> V [B, 1]; differentiable with respect to x."""
@@ -182,18 +92,7 @@ class ResNet_wobn(nn.Module):
         clip_grad_norm_ returns it.  A gradient with a non-finite norm raises PnpxError and changes nothing."""
         if not isinstance(grad, torch.Tensor):
             raise ops.PnpxError(f"adam_step_: expected a torch.Tensor, got {type(grad).__name__}")
-        key = _key(grad.device)
-        ctx = self.context(grad.device)
-        try:
-            norm = ctx.critic_adam_step(grad, lr, betas, eps, max_norm)
-        except ops.PnpxError:
-            if ctx._critic is None:
-                del self._ctx[key]
-                if self._live == key:
-                    self._live = None
-            raise
-        self._changed_on(key)
-        return norm
+        return self._mutate(self._key(grad.device), lambda ctx: ctx.critic_adam_step(grad, lr, betas, eps, max_norm))
 
     def optim_state(self, device):
         """(exp_avg, exp_avg_sq, step) of the context on `device`: copies of Adam's moments as flat fp32 vectors

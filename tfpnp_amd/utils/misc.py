@@ -33,18 +33,25 @@ def check_param_order(params, num_inputs):
                             f"inputs (num_inputs of the target) has shape {tuple(want)}")
 
 
+def _native_source_vector(target, source, noun, mismatch):
+    """The vector of a native `source` for a native `target` of the same class: the same network shape on both sides
+    (`mismatch`: the refusal otherwise), on the device either of them lives on -- the same one if both do."""
+    if source._shape() != target._shape():
+        raise PnpxError(mismatch)
+    device = source.device if source.device is not None else target.device
+    if device is None:
+        raise PnpxError(f"neither {noun} has been used on a device yet; call source.context(device) first")
+    if target.device is not None and target.device != device:
+        raise PnpxError(f"source {noun} is on {device}, target on {target.device}: both must be on the same device")
+    return source.parameters_flat(device)
+
+
 def _source_vector(target, source):
     if not isinstance(target, ResNet_wobn):
         raise PnpxError(f"target must be a native ResNet_wobn (or, for hard_update, a native actor), got {type(target).__name__}")
     if isinstance(source, ResNet_wobn):
-        if source.in_dim != target.in_dim:
-            raise PnpxError(f"num_inputs mismatch: the source critic has {source.in_dim} inputs, the target {target.in_dim}")
-        device = source.device if source.device is not None else target.device
-        if device is None:
-            raise PnpxError("neither critic has been used on a device yet; call source.context(device) first")
-        if target.device is not None and target.device != device:
-            raise PnpxError(f"source critic is on {device}, target on {target.device}: both must be on the same device")
-        return source.parameters_flat(device)
+        return _native_source_vector(target, source, "critic", f"num_inputs mismatch: the source critic has {source.in_dim} "
+                                                               f"inputs, the target {target.in_dim}")
     params = [p.detach() for p in source.parameters()]
     check_param_order(params, target.in_dim)
     devices = {p.device for p in params}
@@ -78,15 +85,9 @@ def gather_actor_state(state, num_inputs, n_det, spi_head):
 
 def _actor_source_vector(target, source):
     if isinstance(source, ResNetActorBase):
-        if (source.in_dim, source.n_det, source.spi_head) != (target.in_dim, target.n_det, target.spi_head):
-            raise PnpxError(f"actor mismatch: the source has {source.in_dim} inputs / {source.n_det} outputs / spi_head "
-                            f"{source.spi_head}, the target {target.in_dim} / {target.n_det} / {target.spi_head}")
-        device = source.device if source.device is not None else target.device
-        if device is None:
-            raise PnpxError("neither actor has been used on a device yet; call source.context(device) first")
-        if target.device is not None and target.device != device:
-            raise PnpxError(f"source actor is on {device}, target on {target.device}: both must be on the same device")
-        return source.parameters_flat(device)
+        return _native_source_vector(target, source, "actor",
+                                     f"actor mismatch: the source has {source.in_dim} inputs / {source.n_det} outputs / spi_head "
+                                     f"{source.spi_head}, the target {target.in_dim} / {target.n_det} / {target.spi_head}")
     if not isinstance(source, torch.nn.Module):
         raise PnpxError(f"source must be a native actor or an nn.Module, got {type(source).__name__}")
     named = gather_actor_state(source.state_dict(keep_vars=True), target.in_dim, target.n_det, target.spi_head)
