@@ -227,8 +227,8 @@ int pnpx_policy_params(pnpx_ctx* ctx, float* dst_dev, size_t n_params, void* str
  * Batch statistics couple the images: the call is ONE launch chain whatever option "chains" says, and its result is deterministic
  * (fixed-order reductions in double, no atomics).  Both settings of option "policy_s2_hs" are served.  Not capturable into a graph.
  * H, W multiples of 32 (else PNPX_ERR_SHAPE); PNPX_ERR_ARG when the last stage has B * (H/32) * (W/32) < 2 values per channel
- * (torch raises there) or momentum is outside [0, 1]; PNPX_ERR_NO_WEIGHTS before a load.  Out of scope: gradients, the optimiser
- * step, statistics synchronised across devices, activations kept for a backward pass. */
+ * (torch raises there) or momentum is outside [0, 1]; PNPX_ERR_NO_WEIGHTS before a load.  Out of scope: the optimiser step, statistics
+ * synchronised across devices, activations kept for a backward pass (pnpx_policy_param_grad re-computes). */
 int pnpx_policy_forward_train(pnpx_ctx* ctx, const float* ob, float* probs, float* det, int B, int H, int W, float momentum,
                               int update_running, void* stream);
 /* BatchNorm channels of the actor over its 20 layers in state_dict order (stem bn1, then per stage L.0.bn1, L.0.bn2,
@@ -237,6 +237,22 @@ size_t pnpx_policy_num_bn_channels(void);
 /* Batch mean and biased batch variance of the last pnpx_policy_forward_train, concatenated in that order, copied to mean_dev /
  * var_dev (n = pnpx_policy_num_bn_channels() floats each), ordered on `stream`.  PNPX_ERR_NO_WEIGHTS before any train forward. */
 int pnpx_policy_bn_stats(pnpx_ctx* ctx, float* mean_dev, float* var_dev, size_t n, void* stream);
+/* d sum(grad_probs * probs + grad_det * det) / d params, probs / det being what pnpx_policy_forward_train returns for `ob`
+ * (batch-statistics BatchNorm): the actor's half of policy_loss.backward() (trainer.py:171-212), the counterpart of
+ * pnpx_critic_param_grad.  grad_params has the layout of pnpx_policy_params (n_params floats); every element is written, the
+ * running_mean / running_var slots as zeros.  All pointers are device pointers.  Changes no weights and no running statistics; the
+ * batch statistics pnpx_policy_bn_stats reads afterwards are those of a train forward on `ob`.
+ * The call re-computes the forward (nothing is kept from pnpx_policy_forward_train), ALWAYS on the half-split stage entries whatever
+ * option "policy_s2_hs" says (the weight-gradient kernel reads HS8 operands), then runs BatchNorm backward, the weight-gradient GEMM
+ * and the adjoint convolution per layer.  Deterministic: fixed-order reductions in double, no floating-point atomics; the same bytes
+ * on every call, whatever ran before.  Gradients travel scaled by a power of two chosen on the device from the upstream gradients:
+ * the result is exactly homogeneous in powers of two of (grad_probs, grad_det), all-zero upstream gradients give an all-zero vector,
+ * and there is no host read-back -- a call that grows no buffer allocates nothing and does not synchronise the device.  The first
+ * call after a load derives the adjoint packings (and, if no train forward ran yet, the fold-free packing: one stream synchronisation).
+ * Argument checks as pnpx_policy_forward_train; PNPX_ERR_ARG for a null pointer or n_params != pnpx_policy_num_params(...).
+ * Out of scope: the observation's gradient, the optimiser step, graph capture. */
+int pnpx_policy_param_grad(pnpx_ctx* ctx, const float* ob, const float* grad_probs /* [B][2] */, const float* grad_det /* [B][n_det] */,
+                           float* grad_params, size_t n_params, int B, int H, int W, void* stream);
 
 /* ---- value network / critic (tfpnp/trainer/mddpg/critic.py) --------------------------------------- */
 /* ResNet_wobn(num_inputs, 18, 1) (critic.py:95-131; the trainer never builds another one, trainer/mddpg/critic.py:95 via

@@ -227,6 +227,16 @@ int pnpx_policy_forward_train(pnpx_ctx* ctx, const float* ob, float* probs, floa
   return policy_forward_train(ctx, ob, probs, det, B, H, W, momentum, update_running, static_cast<hipStream_t>(stream));
 }
 
+int pnpx_policy_param_grad(pnpx_ctx* ctx, const float* ob, const float* grad_probs, const float* grad_det, float* grad_params,
+                           size_t n_params, int B, int H, int W, void* stream) {
+  LOCK_CTX(ctx);
+  if (!ob || !grad_probs || !grad_det || !grad_params) {
+    set_error("pnpx_policy_param_grad: null pointer");
+    return PNPX_ERR_ARG;
+  }
+  return policy_param_grad(ctx, ob, grad_probs, grad_det, grad_params, n_params, B, H, W, static_cast<hipStream_t>(stream));
+}
+
 size_t pnpx_policy_num_bn_channels(void) { return POLICY_BN_CHANNELS; }
 
 int pnpx_policy_bn_stats(pnpx_ctx* ctx, float* mean_dev, float* var_dev, size_t n, void* stream) {

@@ -127,6 +127,17 @@ struct PolicyNet : PolicyPack {   // the base: the eval-mode packing (BatchNorm 
   int tcapB = 0, tcapH = 0, tcapW = 0;
   DeviceBuf bn_buf;          // per BatchNorm channel: batch mean, biased batch variance, scale, shift; then the reduction partials
   bool bn_have_stats = false;
+  // parameter gradients (pnpx_policy_param_grad; policy_bn.hip, policy_grad.hip): the adjoint packings of `raw` (transposed, tap-mirrored;
+  // layers 1..20 -- the stem's adjoint is never run), derived by the first gradient call after a load; a workspace of its own that keeps
+  // every raw convolution output, every activation and the gradient tensors (zero borders); the K-split slabs and the head scratch.
+  // Forward-only users allocate none of it.
+  ConvLayerHsDev raw_bwd[21];
+  DeviceBuf raw_adj, raw_adj_table;
+  const float* raw_adj_zero = nullptr;   // [1024] zeros inside raw_adj: the bias operand of the adjoint launches
+  bool adj_valid = false;
+  DeviceBuf grad_ws;
+  int gcapB = 0, gcapH = 0, gcapW = 0;
+  DeviceBuf grad_slab;
 };
 
 // Value network (critic.hip): ResNet_wobn(num_inputs, 18, 1).  The raw parameters live on the device (`live`); the packed
@@ -418,6 +429,10 @@ constexpr size_t POLICY_BN_CHANNELS = 4864;
 int policy_forward_train(pnpx_ctx* ctx, const float* ob, float* probs, float* det, int B, int H, int W, float momentum, int update_running,
                          hipStream_t s);
 int policy_bn_stats(pnpx_ctx* ctx, float* mean_dev, float* var_dev, size_t n, hipStream_t s);
+// parameter gradients through the train-mode forward (driver: policy_bn.hip; kernels: policy_grad.hip; adjoint packings: policy_pack.hip)
+int policy_param_grad(pnpx_ctx* ctx, const float* ob, const float* grad_probs, const float* grad_det, float* grad_params, size_t n, int B,
+                      int H, int W, hipStream_t s);
+int policy_pack_adj(pnpx_ctx* ctx, hipStream_t s);       // live vector -> PolicyNet::raw_bwd (allocates on first use)
 
 // Value network (critic.hip)
 size_t critic_num_params(int num_inputs);

@@ -30,6 +30,7 @@
 #include "critic_grad.h"
 
 #include "conv_hs.h"
+#include "grad_common.h"
 
 namespace pnpx {
 namespace {
@@ -156,26 +157,14 @@ __global__ __launch_bounds__(256) void critic_wn_grad_kernel(const WnGradArgs a,
   __shared__ double sh[256];
   __shared__ int sTi[9];   // tap -> its index in the packing's window (-1: absent)
   const int tid = threadIdx.x, co = blockIdx.x;
-  if (tid < 9) {
-    int ti = -1;
-    for (int i = 0; i < a.D.nt; ++i)
-      if (a.D.tap[i] == tid) ti = i;
-    sTi[tid] = ti;
-  }
+  wgrad_tap_index(a.D, sTi);
   __syncthreads();
   const float* v = P + a.D.src_v + (size_t)co * a.fan;
   float* gout = grad + a.D.src_v + (size_t)co * a.fan;
   const int nt = a.D.nt, K = a.D.K;
   double dot = 0.0, nn = 0.0;
   for (int i = tid; i < a.fan; i += 256) {
-    int k, tap;
-    eff_pos_of_src(a.D, i, k, tap);
-    const int ti = sTi[tap];
-    double sum = 0.0;
-    if (ti >= 0) {
-      const float* src = slab + ((size_t)co * nt + ti) * K + k;
-      for (int pc = 0; pc < a.pieces; ++pc) sum += (double)src[(size_t)pc * a.stride];
-    }
+    const double sum = wgrad_gather(a.D, sTi, slab, a.stride, a.pieces, co, i);
     const float dw = (float)(sum * (double)a.inv_w);
     gout[i] = dw;   // parked: replaced by dv below (same thread)
     const double vi = (double)v[i];

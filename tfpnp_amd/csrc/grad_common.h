@@ -1,7 +1,9 @@
-// Kernels shared by the denoiser VJPs (unet_bwd.hip, drunet.hip); `static`: one copy per translation unit.
+// Kernels shared by the denoiser VJPs (unet_bwd.hip, drunet.hip) and pieces shared by the finishing kernels of the weight gradients
+// (critic_grad.hip, policy_grad.hip); `static`: one copy per translation unit.
 #pragma once
 #include "conv_hs.h"
 #include "hs_rec.h"
+#include "pack_desc.h"
 
 namespace pnpx {
 
@@ -54,6 +56,31 @@ static __global__ __launch_bounds__(256) void input_grad_hs_kernel(const HsRec* 
   if ((threadIdx.x & 63) == 0) w[threadIdx.x >> 6] = acc;
   __syncthreads();
   if (threadIdx.x == 0) part[b * SIG_CHUNKS + chunk] = ((w[0] + w[1]) + (w[2] + w[3])) * m;
+}
+
+// ---- finishing kernels of the K-split weight-gradient GEMM (critic_grad.hip::critic_wgrad_kernel): slab[piece][co][tap index][k]
+// tap -> its index in the window of packing D (-1: absent).  Threads 0..8 fill sTi[9]; the caller synchronises.
+__device__ inline void wgrad_tap_index(const PackDesc& D, int* sTi) {
+  const int tid = threadIdx.x;
+  if (tid < 9) {
+    int ti = -1;
+    for (int i = 0; i < D.nt; ++i)
+      if (D.tap[i] == tid) ti = i;
+    sTi[tid] = ti;
+  }
+}
+// Raw element i of output channel co's fan: its one effective position (eff_pos_of_src), the pieces added in piece order in double.
+__device__ inline double wgrad_gather(const PackDesc& D, const int* sTi, const float* __restrict__ slab, size_t stride, int pieces,
+                                      int co, int i) {
+  int k, tap;
+  eff_pos_of_src(D, i, k, tap);
+  const int ti = sTi[tap];
+  double sum = 0.0;
+  if (ti >= 0) {
+    const float* src = slab + ((size_t)co * D.nt + ti) * D.K + k;
+    for (int pc = 0; pc < pieces; ++pc) sum += (double)src[(size_t)pc * stride];
+  }
+  return sum;
 }
 
 }  // namespace pnpx

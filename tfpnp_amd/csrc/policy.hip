@@ -271,6 +271,10 @@ void policy_free(pnpx_ctx* ctx) {
   N.raw_ws.free();
   if (N.train_ws.p) (void)hipFree(N.train_ws.p);
   if (N.bn_buf.p) (void)hipFree(N.bn_buf.p);
+  if (N.raw_adj.p) (void)hipFree(N.raw_adj.p);
+  if (N.raw_adj_table.p) (void)hipFree(N.raw_adj_table.p);
+  if (N.grad_ws.p) (void)hipFree(N.grad_ws.p);
+  if (N.grad_slab.p) (void)hipFree(N.grad_slab.p);
   N = PolicyNet();
 }
 

@@ -15,12 +15,19 @@
 //                       policy_s2_hs = 0).  (z - mean) * scale + bias is z * scale + shift without the cancellation of two large terms.
 // Batch statistics couple the images: the forward is ONE launch chain whatever the "chains" option says.  Pool and heads are the
 // eval forward's.  Nothing is kept for a backward pass; fusing the passes into the convolutions is a later step.
+//
+// The same launch sequence (train_forward_launches) over a plan that keeps every z and every activation is the re-computation of
+// policy_param_grad at the end of this file, the driver of the parameter gradients (kernels: policy_grad.hip).
+#include <algorithm>
 #include <cmath>
 
 #include "common.h"
 #include "conv_hs.h"
+#include "critic_grad.h"
 #include "hs_rec.h"
+#include "hs_relayout.h"
 #include "policy_conv.h"
+#include "policy_grad.h"
 #include "resnet18_hs.h"
 
 namespace pnpx {
@@ -196,15 +203,23 @@ __global__ __launch_bounds__(256) void bn_apply_kernel(BnApplyArgs a) {
 }
 
 // ------------------------------------------------------------------------------------------- workspace plan (offsets in floats)
+constexpr size_t NONE = ~(size_t)0;
 struct TrainPlan {
   size_t ob = 0, zstem = 0, stem_s = 0;   // observation (space-to-depth), the stem's z, the stem's space-to-depth activation
-  size_t za[4], zb[4], t1[4], o0[4], t2[4], o1[4], o1s[3];
+  size_t za[4], t1[4], o0[4], t2[4], o1[4], o1s[3];
+  // the raw outputs of conv2 and of block 1's two convolutions: ONE buffer per stage reused three times in the forward's plan (nothing is
+  // kept), three buffers in the gradient's
+  size_t z2[4], z3[4], z4[4];
+  size_t stem_a = NONE;                   // gradient plan only: the stem's activation in place (the mask of its BatchNorm backward)
+  // gradient plan only, per stage at planes x h x w: the gradient of o1 / o0 / t1, t2; dz of the layer at hand, dz of the shortcut, the
+  // identity branch's dy; the shortcut's adjoint (in_planes x h x w) and the entry's (4 in_planes x h x w); of the stem's activation
+  size_t gA[4], gB[4], gM[4], dZ[4], dZs[4], dY[4], gR[4], gS[4], g_stem = 0, dz_stem = 0;
   size_t part = 0;                        // doubles: the partial sums of the largest layer
   size_t total = 0;
 };
 inline size_t bn_pieces(long long npix) { return (size_t)((npix + BN_PIECE - 1) / BN_PIECE); }
-// s2_hs: the observation and the space-to-depth activations are HS8 tensors (else fp32 planar)
-TrainPlan make_train_plan(int capB, int cin_pad, int H, int W, bool s2_hs) {
+// s2_hs: the observation and the space-to-depth activations are HS8 tensors (else fp32 planar).  keep: the gradient's plan (s2_hs only)
+TrainPlan make_train_plan(int capB, int cin_pad, int H, int W, bool s2_hs, bool keep = false) {
   TrainPlan P;
   size_t off = 0, part = 0;
   auto add = [&](size_t& d, int C, int h, int w, bool hs) {
@@ -220,16 +235,31 @@ TrainPlan make_train_plan(int capB, int cin_pad, int H, int W, bool s2_hs) {
   add(P.zstem, 64, H / 2, W / 2, true);
   stat(64, H / 2, W / 2);
   add(P.stem_s, 4 * 64, H / 4, W / 4, s2_hs);
+  if (keep) {
+    add(P.stem_a, 64, H / 2, W / 2, true);
+    add(P.g_stem, 64, H / 2, W / 2, true);
+    add(P.dz_stem, 64, H / 2, W / 2, true);
+  }
+  int in_planes = 64;
   for (int n = 0; n < 4; ++n) {
     const int p = stage_planes(n), h = H >> (n + 2), w = W >> (n + 2);
     add(P.za[n], 2 * p, h, w, true);   // the entry's two outputs: one tensor of 2p channels (fp32 launch) or two of p, back to back
-    add(P.zb[n], p, h, w, true);
+    add(P.z2[n], p, h, w, true);
+    P.z3[n] = P.z4[n] = P.z2[n];
     add(P.t1[n], p, h, w, true);
     add(P.o0[n], p, h, w, true);
     add(P.t2[n], p, h, w, true);
     add(P.o1[n], p, h, w, true);
     if (n < 3) add(P.o1s[n], 4 * p, h / 2, w / 2, s2_hs);
     stat(2 * p, h, w);
+    if (keep) {
+      add(P.z3[n], p, h, w, true);
+      add(P.z4[n], p, h, w, true);
+      for (size_t* g : {&P.gA[n], &P.gB[n], &P.gM[n], &P.dZ[n], &P.dZs[n], &P.dY[n]}) add(*g, p, h, w, true);
+      add(P.gR[n], in_planes, h, w, true);
+      add(P.gS[n], 4 * in_planes, h, w, true);
+    }
+    in_planes = p;
   }
   off = (off + 63) & ~(size_t)63;
   P.part = off;                      // 256-byte aligned: doubles
@@ -238,34 +268,28 @@ TrainPlan make_train_plan(int capB, int cin_pad, int H, int W, bool s2_hs) {
   return P;
 }
 
-}  // namespace
-
-int policy_forward_train(pnpx_ctx* ctx, const float* ob, float* probs, float* det, int B, int H, int W, float momentum,
-                         int update_running, hipStream_t s) {
-  PolicyNet& N = ctx->policy;
+int check_train_call(const PolicyNet& N, const char* who, int B, int H, int W) {
   if (!N.loaded) {
-    set_error("policy train forward called before pnpx_policy_load");
+    set_error("%s called before pnpx_policy_load", who);
     return PNPX_ERR_NO_WEIGHTS;
   }
   if (B <= 0 || H < 32 || W < 32 || (H % 32) || (W % 32)) {
-    set_error("policy train forward: need B > 0 and H, W positive multiples of 32 (got %d x %d x %d)", B, H, W);
+    set_error("%s: need B > 0 and H, W positive multiples of 32 (got %d x %d x %d)", who, B, H, W);
     return PNPX_ERR_SHAPE;
   }
   if ((long long)B * (H / 32) * (W / 32) < 2) {
-    set_error("policy train forward: batch statistics need more than 1 value per channel in the last stage (got %d x %d x %d)", B, H, W);
+    set_error("%s: batch statistics need more than 1 value per channel in the last stage (got %d x %d x %d)", who, B, H, W);
     return PNPX_ERR_ARG;
   }
-  if (!(momentum >= 0.f && momentum <= 1.f)) {
-    set_error("policy train forward: momentum %g outside [0, 1]", (double)momentum);
-    return PNPX_ERR_ARG;
-  }
-  if (!N.raw_valid) PNPX_TRY(policy_pack_raw(ctx, s));
-  const bool s2_hs = ctx->opt_policy_s2_hs != 0;
-  if (!N.bn_buf.p) PNPX_TRY(alloc_dev(N.bn_buf, 4 * POLICY_BN_CHANNELS * sizeof(float), "policy batch-statistics"));
-  PNPX_TRY(reserve_arena_hs(N.train_ws, N.tcapB, N.tcapH, N.tcapW, B, H, W,
-                            [&](int nb) { return make_train_plan(nb, N.cin_pad, H, W, s2_hs).total; }, "policy train workspace"));
-  const TrainPlan P = make_train_plan(N.tcapB, N.cin_pad, H, W, s2_hs);
-  float* A = static_cast<float*>(N.train_ws.p);
+  return PNPX_OK;
+}
+
+// The launch sequence of the train-mode forward over plan P in workspace A: shared by policy_forward_train (plan without `keep`: the
+// three stride-1 z of a stage share a buffer) and by the re-computation of policy_param_grad (everything kept; s2_hs always).
+// probs == null: no head launch.
+int train_forward_launches(pnpx_ctx* ctx, const TrainPlan& P, float* A, bool s2_hs, const float* ob, float* probs, float* det, int B, int H,
+                           int W, float momentum, int update_running, hipStream_t s) {
+  PolicyNet& N = ctx->policy;
   auto hsc = [&](size_t off) { return reinterpret_cast<char*>(A + off); };
   auto rec = [&](size_t off) { return reinterpret_cast<HsRec*>(A + off); };
   double* part = reinterpret_cast<double*>(A + P.part);
@@ -331,8 +355,7 @@ int policy_forward_train(pnpx_ctx* ctx, const float* ob, float* probs, float* de
     const BnLayer& L = BL[l];
     return BnSrc{rec(z), Gt, g0, st_mean + L.chan0, st_scale + L.chan0, params + L.bn + L.cout};
   };
-  // `sd`: the space-to-depth copy for a following stride-2 entry (offset; SIZE_MAX = none); out / res: SIZE_MAX = none
-  constexpr size_t NONE = ~(size_t)0;
+  // `sd`: the space-to-depth copy for a following stride-2 entry (offset; NONE = none); out / res: NONE = none
   auto apply = [&](BnSrc a0, BnSrc b0, size_t res, size_t out, size_t sd, int G, int h, int w) -> int {
     BnApplyArgs a;
     a.a = a0;
@@ -360,7 +383,7 @@ int policy_forward_train(pnpx_ctx* ctx, const float* ob, float* probs, float* de
     PNPX_TRY(conv_f32(N.raw.f32[0], P.ob, P.zstem, H / 2, W / 2));
   }
   PNPX_TRY(stats(P.zstem, 64, H / 2, W / 2, 0, -1));
-  PNPX_TRY(apply(src(P.zstem, 8, 0, 0), no_src, NONE, NONE, P.stem_s, 8, H / 2, W / 2));
+  PNPX_TRY(apply(src(P.zstem, 8, 0, 0), no_src, NONE, P.stem_a, P.stem_s, 8, H / 2, W / 2));
   for (int st = 0; st < 4; ++st) {
     const int h = H >> (st + 2), w = W >> (st + 2), p = stage_planes(st), G = p / 8, c0 = 1 + 5 * st;
     const size_t s2in = st == 0 ? P.stem_s : P.o1s[st - 1];
@@ -382,21 +405,245 @@ int policy_forward_train(pnpx_ctx* ctx, const float* ob, float* probs, float* de
     }
     PNPX_TRY(apply(z1, no_src, NONE, P.t1[st], NONE, G, h, w));
     // block 0: relu(bn2(conv2) + shortcut_bn(shortcut_conv))
-    PNPX_TRY(conv_hs(c0 + 1, P.t1[st], 0, P.zb[st], h, w));
-    PNPX_TRY(stats(P.zb[st], p, h, w, c0 + 1, -1));
-    PNPX_TRY(apply(src(P.zb[st], G, 0, c0 + 1), zs, NONE, P.o0[st], NONE, G, h, w));
+    PNPX_TRY(conv_hs(c0 + 1, P.t1[st], 0, P.z2[st], h, w));
+    PNPX_TRY(stats(P.z2[st], p, h, w, c0 + 1, -1));
+    PNPX_TRY(apply(src(P.z2[st], G, 0, c0 + 1), zs, NONE, P.o0[st], NONE, G, h, w));
     // block 1: relu(bn2(conv2(relu(bn1(conv1(x))))) + x)
-    PNPX_TRY(conv_hs(c0 + 3, P.o0[st], 0, P.zb[st], h, w));
-    PNPX_TRY(stats(P.zb[st], p, h, w, c0 + 3, -1));
-    PNPX_TRY(apply(src(P.zb[st], G, 0, c0 + 3), no_src, NONE, P.t2[st], NONE, G, h, w));
-    PNPX_TRY(conv_hs(c0 + 4, P.t2[st], 0, P.zb[st], h, w));
-    PNPX_TRY(stats(P.zb[st], p, h, w, c0 + 4, -1));
-    PNPX_TRY(apply(src(P.zb[st], G, 0, c0 + 4), no_src, P.o0[st], P.o1[st], st < 3 ? P.o1s[st] : NONE, G, h, w));
+    PNPX_TRY(conv_hs(c0 + 3, P.o0[st], 0, P.z3[st], h, w));
+    PNPX_TRY(stats(P.z3[st], p, h, w, c0 + 3, -1));
+    PNPX_TRY(apply(src(P.z3[st], G, 0, c0 + 3), no_src, NONE, P.t2[st], NONE, G, h, w));
+    PNPX_TRY(conv_hs(c0 + 4, P.t2[st], 0, P.z4[st], h, w));
+    PNPX_TRY(stats(P.z4[st], p, h, w, c0 + 4, -1));
+    PNPX_TRY(apply(src(P.z4[st], G, 0, c0 + 4), no_src, P.o0[st], P.o1[st], st < 3 ? P.o1s[st] : NONE, G, h, w));
   }
-  PNPX_TRY(policy_launch_heads(N.raw, N.n_det, N.spi_head, hsc(P.o1[3]), H / 32, W / 32, B, probs, det, s));
+  if (probs) PNPX_TRY(policy_launch_heads(N.raw, N.n_det, N.spi_head, hsc(P.o1[3]), H / 32, W / 32, B, probs, det, s));
   N.bn_have_stats = true;
   if (update_running) N.eval_stale = true;
   return PNPX_OK;
+}
+
+}  // namespace
+
+int policy_forward_train(pnpx_ctx* ctx, const float* ob, float* probs, float* det, int B, int H, int W, float momentum,
+                         int update_running, hipStream_t s) {
+  PolicyNet& N = ctx->policy;
+  PNPX_TRY(check_train_call(N, "policy train forward", B, H, W));
+  if (!(momentum >= 0.f && momentum <= 1.f)) {
+    set_error("policy train forward: momentum %g outside [0, 1]", (double)momentum);
+    return PNPX_ERR_ARG;
+  }
+  if (!N.raw_valid) PNPX_TRY(policy_pack_raw(ctx, s));
+  const bool s2_hs = ctx->opt_policy_s2_hs != 0;
+  if (!N.bn_buf.p) PNPX_TRY(alloc_dev(N.bn_buf, 4 * POLICY_BN_CHANNELS * sizeof(float), "policy batch-statistics"));
+  PNPX_TRY(reserve_arena_hs(N.train_ws, N.tcapB, N.tcapH, N.tcapW, B, H, W,
+                            [&](int nb) { return make_train_plan(nb, N.cin_pad, H, W, s2_hs).total; }, "policy train workspace"));
+  const TrainPlan P = make_train_plan(N.tcapB, N.cin_pad, H, W, s2_hs);
+  return train_forward_launches(ctx, P, static_cast<float*>(N.train_ws.p), s2_hs, ob, probs, det, B, H, W, momentum, update_running, s);
+}
+
+namespace {
+
+// a buffer outside the workspace: grows to the largest size seen (with the workspace, the only place the call synchronises the device)
+int grow(DeviceBuf& b, size_t bytes, const char* what) {
+  if (bytes <= b.bytes) return PNPX_OK;
+  PNPX_HIP(hipDeviceSynchronize());
+  if (b.p) PNPX_HIP(hipFree(b.p));
+  b = DeviceBuf();
+  return alloc_dev(b, bytes, what);
+}
+
+}  // namespace
+
+// d sum(grad_probs * probs + grad_det * det) / d params through the train-mode forward (policy_loss.backward(), trainer.py:171-212).
+// The forward is re-computed with update_running = 0 into a workspace of its own that keeps every z and every activation; ALWAYS on the
+// half-split stage entries (HS8 space-to-depth tensors) whatever policy_s2_hs says: the weight-gradient GEMM reads HS8 operands.  Then,
+// backwards (DESIGN.md section 9c has the table of launches): heads and the gradient range (policy_grad.hip), and per layer BatchNorm
+// backward -> weight gradient (critic_grad.hip's GEMM, G = dz, X = what the forward launch read) -> adjoint convolution.  The adjoint
+// convolutions are linear (the ReLU mask is taken by the BatchNorm backward of the layer below): the critic's input-gradient instance
+// without a mask (EPI_DTHR; windows 0x1FF, 0x1B0 with the shortcut's adjoint as residual on the phase-(0,0) groups, then depth-to-space)
+// and the plain 1x1 instance for the shortcut.  The stem's adjoint is not run (no observation gradient).  Every element of grad_params
+// is written; nothing is kept between calls; weights and running statistics do not change, the batch statistics in bn_buf are those of a
+// train forward on `ob`.
+int policy_param_grad(pnpx_ctx* ctx, const float* ob, const float* grad_probs, const float* grad_det, float* grad_params, size_t n, int B,
+                      int H, int W, hipStream_t s) {
+  PolicyNet& N = ctx->policy;
+  PNPX_TRY(check_train_call(N, "policy parameter gradient", B, H, W));
+  const size_t want = policy_num_params(N.num_inputs, N.n_det, N.spi_head);
+  if (n != want) {
+    set_error("pnpx_policy_param_grad: the loaded actor (%d inputs, %d outputs, spi %d) has %zu parameters, got room for %zu", N.num_inputs,
+              N.n_det, N.spi_head, want, n);
+    return PNPX_ERR_ARG;
+  }
+  if (!N.raw_valid) PNPX_TRY(policy_pack_raw(ctx, s));
+  if (!N.adj_valid) PNPX_TRY(policy_pack_adj(ctx, s));
+  PackDesc PD[NBN];
+  PNPX_TRY(policy_conv_descs(N, PD));
+  BnLayer BL[NBN];
+  bn_layers(N.num_inputs, BL);
+  if (!N.bn_buf.p) PNPX_TRY(alloc_dev(N.bn_buf, 4 * POLICY_BN_CHANNELS * sizeof(float), "policy batch-statistics"));
+  PNPX_TRY(reserve_arena_hs(N.grad_ws, N.gcapB, N.gcapH, N.gcapW, B, H, W,
+                            [&](int nb) { return make_train_plan(nb, N.cin_pad, H, W, true, true).total; }, "policy gradient workspace"));
+  const TrainPlan P = make_train_plan(N.gcapB, N.cin_pad, H, W, true, true);
+  float* A = static_cast<float*>(N.grad_ws.p);
+  auto rec = [&](size_t off) { return reinterpret_cast<HsRec*>(A + off); };
+  auto hsc = [&](size_t off) { return reinterpret_cast<char*>(A + off); };
+  const int hl = H / 32, wl = W / 32;
+
+  // outside the workspace: the K-split slabs of the largest layer; then g_f [B][512], the head scratch, gv [B], the BatchNorm-backward
+  // coefficients [3][4864], the scale slot and its bits; then (doubles) the BatchNorm-backward partial sums of the largest layer
+  size_t slab_floats = 0, part_doubles = 0;
+  auto shape_of = [&](int li, int& h, int& w) {
+    const int st = li == 0 ? -1 : (li - 1) / 5;
+    h = H >> (st + 2);
+    w = W >> (st + 2);
+  };
+  for (int li = 0; li < NBN; ++li) {
+    int h, w;
+    shape_of(li, h, w);
+    const PackDesc& D = PD[li];
+    slab_floats = std::max(slab_floats, (size_t)critic_wgrad_pieces(D.rows, D.K, B, h, w) * critic_wgrad_piece_floats(D.rows, D.K, D.nt));
+    part_doubles = std::max(part_doubles, bn_bwd_pieces((long long)B * h * w) * D.rows * 3);
+  }
+  const size_t slab_bytes = (slab_floats * sizeof(float) + 255) & ~(size_t)255;
+  const size_t small_floats = ((size_t)B * 512 + (size_t)B * POL_HEAD_STRIDE + B + 3 * POLICY_BN_CHANNELS + 4 + 63) & ~(size_t)63;
+  PNPX_TRY(grow(N.grad_slab, slab_bytes + small_floats * sizeof(float) + part_doubles * sizeof(double), "policy gradient slab"));
+  float* slab = static_cast<float*>(N.grad_slab.p);
+  float* gf = reinterpret_cast<float*>(static_cast<char*>(N.grad_slab.p) + slab_bytes);
+  float* head_rows = gf + (size_t)B * 512;
+  float* coef = head_rows + (size_t)B * POL_HEAD_STRIDE;
+  float2* slot = reinterpret_cast<float2*>(coef + 3 * POLICY_BN_CHANNELS);
+  unsigned* bits = reinterpret_cast<unsigned*>(slot + 1);
+  float* gv = reinterpret_cast<float*>(bits + 1) + 1;
+  double* part = reinterpret_cast<double*>(gf + small_floats);
+
+  // 1. forward re-computation (the batch statistics land in bn_buf)
+  PNPX_TRY(train_forward_launches(ctx, P, A, true, ob, nullptr, nullptr, B, H, W, 0.f, 0, s));
+  const float* st_mean = static_cast<const float*>(N.bn_buf.p);
+  const float* st_var = st_mean + POLICY_BN_CHANNELS;
+  unsigned* range_flag = ctx->opt_range_guard ? ctx->range_flag_dev : nullptr;
+
+  // 2. heads; 3. the gradient range: s from max |g_f| on the device, boost = 2^(1 + ceil(log2(h w))): the last activation's gradient
+  // s * boost * g_f / (h w) has its largest entry in [1, 4)
+  PolHeadGradJob HJ;
+  HJ.feat = rec(P.o1[3]);
+  HJ.h = hl;
+  HJ.w = wl;
+  HJ.B = B;
+  HJ.n_det = N.n_det;
+  HJ.spi = N.spi_head;
+  HJ.sm_w = N.raw.fc_sm_w;
+  HJ.sm_b = N.raw.fc_sm_b;
+  HJ.d_w = N.raw.fc_det_w;
+  HJ.d_b = N.raw.fc_det_b;
+  HJ.d2_w = N.raw.fc_det2_w;
+  HJ.d2_b = N.raw.fc_det2_b;
+  HJ.gp = grad_probs;
+  HJ.gd = grad_det;
+  HJ.gf = gf;
+  HJ.rows = head_rows;
+  HJ.grad = grad_params;
+  HJ.head_src = want - (2 * 512 + 2) -
+                (N.spi_head ? (size_t)64 * 512 + 64 + (size_t)N.n_det * 64 + N.n_det : (size_t)N.n_det * 512 + N.n_det);
+  PNPX_TRY(launch_pol_head_grad(HJ, s));
+  int e2 = 0;
+  while ((1 << e2) < hl * wl) ++e2;
+  const float boost = std::ldexp(1.0f, 1 + e2), inv_boost = 1.0f / boost;
+  PNPX_TRY(launch_pol_grad_seed(gf, bits, slot, rec(P.gA[3]), gv, boost, B, hl, wl, s));
+
+  // BatchNorm backward of layer l0 [and l1] from the activation gradient g masked by the saved activation act
+  auto bn_layer = [&](int li, size_t z, size_t dz) {
+    BnBwdLayer L;
+    L.z = rec(z);
+    L.mean = st_mean + BL[li].chan0;
+    L.var = st_var + BL[li].chan0;
+    L.bn = BL[li].bn;
+    L.coef = coef + 3 * (size_t)BL[li].chan0;
+    L.dz = rec(dz);
+    return L;
+  };
+  auto bn_bwd = [&](size_t g, size_t act, const BnBwdLayer& l0, const BnBwdLayer* l1, size_t dy_out, int G, int h, int w) -> int {
+    BnBwdJob J;
+    J.g = rec(g);
+    J.act = rec(act);
+    J.l0 = l0;
+    if (l1) J.l1 = *l1;
+    J.dy_out = dy_out == NONE ? nullptr : rec(dy_out);
+    J.G = G;
+    J.B = B;
+    J.h = h;
+    J.w = w;
+    J.part = part;
+    J.params = N.live.p();
+    J.grad = grad_params;
+    J.slot = slot;
+    J.inv_boost = inv_boost;
+    J.range_flag = range_flag;
+    return launch_bn_bwd(J, s);
+  };
+  // gradient of convolution li: G = dz (cout channels), X = the tensor its forward launch read (Xc channels)
+  auto wgrad = [&](int li, size_t G, size_t X, int Xc, int h, int w) -> int {
+    const PackDesc& D = PD[li];
+    WgradJob Wj;
+    Wj.G = rec(G);
+    Wj.X = rec(X);
+    Wj.gv = gv;
+    Wj.Gg = D.rows / 8;
+    Wj.Xg = Xc / 8;
+    Wj.cout = D.rows;
+    Wj.K = D.K;
+    Wj.nt = D.nt;
+    for (int t = 0; t < D.nt; ++t) Wj.tap[t] = D.tap[t];
+    Wj.B = B;
+    Wj.h = h;
+    Wj.w = w;
+    PNPX_TRY(launch_critic_wgrad(Wj, slab, s));
+    return launch_pol_wgrad_finish(D, (int)(BL[li].bn - D.src_v) / D.rows, critic_wgrad_pieces(D.rows, D.K, B, h, w),
+                                   1.0f / (HS_ASCALE * HS_ASCALE), slab, grad_params, s);
+  };
+  // adjoint convolution of layer li: out = W^T in [+ res on the first resC channels]; epi 2 = the critic's input-gradient instance
+  // (no mask), 0 = the plain linear one (the 1x1 shortcut)
+  auto adjoint = [&](int li, int epi, size_t in, int inC, size_t out, int outC, size_t res, int resC, int h, int w) -> int {
+    HsLaunch L;
+    L.D = &N.raw_bwd[li];
+    L.bias = N.raw_adj_zero;
+    L.taps = trunk_taps(li, true);
+    L.epi = epi;
+    L.range_flag = range_flag;
+    return launch_hs_conv(L, hsc(in), inC, hsc(out), outC, res == NONE ? nullptr : hsc(res), resC, nullptr, 0, B, h, w, s);
+  };
+
+  for (int st = 3; st >= 0; --st) {
+    const int h = H >> (st + 2), w = W >> (st + 2), p = stage_planes(st), G = p / 8, l0 = 1 + 5 * st;
+    const int in_planes = st == 0 ? 64 : stage_planes(st - 1);
+    const size_t x = st == 0 ? P.stem_s : P.o1s[st - 1];
+    const size_t zs = P.za[st] + (size_t)B * p * (h + 2) * (w + 2);
+    // block 1: o1 = relu(bn(conv2(t2)) + o0), t2 = relu(bn(conv1(o0)))
+    PNPX_TRY(bn_bwd(P.gA[st], P.o1[st], bn_layer(l0 + 4, P.z4[st], P.dZ[st]), nullptr, P.dY[st], G, h, w));
+    PNPX_TRY(wgrad(l0 + 4, P.dZ[st], P.t2[st], p, h, w));
+    PNPX_TRY(adjoint(l0 + 4, 2, P.dZ[st], p, P.gM[st], p, NONE, 0, h, w));
+    PNPX_TRY(bn_bwd(P.gM[st], P.t2[st], bn_layer(l0 + 3, P.z3[st], P.dZ[st]), nullptr, NONE, G, h, w));
+    PNPX_TRY(wgrad(l0 + 3, P.dZ[st], P.o0[st], p, h, w));
+    PNPX_TRY(adjoint(l0 + 3, 2, P.dZ[st], p, P.gB[st], p, P.dY[st], p, h, w));
+    // block 0: o0 = relu(bn(conv2(t1)) + bn(shortcut(x))), t1 = relu(bn(conv1(x))), x = space-to-depth input
+    const BnBwdLayer sc = bn_layer(l0 + 2, zs, P.dZs[st]);
+    PNPX_TRY(bn_bwd(P.gB[st], P.o0[st], bn_layer(l0 + 1, P.z2[st], P.dZ[st]), &sc, NONE, G, h, w));
+    PNPX_TRY(wgrad(l0 + 1, P.dZ[st], P.t1[st], p, h, w));
+    PNPX_TRY(wgrad(l0 + 2, P.dZs[st], x, 4 * in_planes, h, w));
+    PNPX_TRY(adjoint(l0 + 1, 2, P.dZ[st], p, P.gM[st], p, NONE, 0, h, w));
+    PNPX_TRY(bn_bwd(P.gM[st], P.t1[st], bn_layer(l0 + 0, P.za[st], P.dZ[st]), nullptr, NONE, G, h, w));
+    PNPX_TRY(wgrad(l0 + 0, P.dZ[st], x, 4 * in_planes, h, w));
+    // shortcut adjoint (1x1, to the phase-(0,0) groups) = the residual of the entry's adjoint (mirrored window); then depth-to-space
+    PNPX_TRY(adjoint(l0 + 2, 0, P.dZs[st], p, P.gR[st], in_planes, NONE, 0, h, w));
+    PNPX_TRY(adjoint(l0 + 0, 2, P.dZ[st], p, P.gS[st], 4 * in_planes, P.gR[st], in_planes, h, w));
+    const size_t below = st == 0 ? P.g_stem : P.gA[st - 1];
+    const int Gb = in_planes / 8;
+    const size_t nq = (size_t)B * Gb * (2 * h) * (2 * w) * 2;
+    hipLaunchKernelGGL(hs_d2s_kernel, g1(nq), dim3(256), 0, s, reinterpret_cast<const uint4*>(A + P.gS[st]), reinterpret_cast<uint4*>(A + below),
+                       Gb, h, w, nq);
+    PNPX_LAUNCH_CHECK();
+  }
+  PNPX_TRY(bn_bwd(P.g_stem, P.stem_a, bn_layer(0, P.zstem, P.dz_stem), nullptr, NONE, 8, H / 2, W / 2));
+  return wgrad(0, P.dz_stem, P.ob, 4 * N.cin_pad, H / 2, W / 2);
 }
 
 int policy_bn_stats(pnpx_ctx* ctx, float* mean_dev, float* var_dev, size_t n, hipStream_t s) {

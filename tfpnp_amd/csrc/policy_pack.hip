@@ -29,6 +29,7 @@
 #include "conv_hs.h"
 #include "pack_desc.h"
 #include "policy_conv.h"
+#include "policy_grad.h"
 #include "resnet18_hs.h"
 
 namespace pnpx {
@@ -372,6 +373,55 @@ __global__ __launch_bounds__(256) void pol_pack_f32_kernel(const PolPackTable* _
   *reinterpret_cast<float4*>(blob + D.dst + (size_t)sl * 512 + c * 64 + m4) = out;
 }
 
+// The adjoint packings of the fold-free table (parameter gradients, policy_bn.hip::policy_param_grad): layer li's input-gradient launch
+// reads the same raw weights with rows / K transposed and the taps mirrored (PackDesc::adj; windows 0x1FF / 0x1B0 / 0x010), in the same
+// power-of-two weight scale.  Layers 1..20: the stem's adjoint is never run.  A blob and a table of their own, so that eval-only and
+// forward-only users allocate none of it.
+struct PolAdjTable {
+  PackDesc pack[NCV];   // [0] unused (no items)
+};
+struct PolAdjLayout {
+  PolAdjTable T;
+  size_t zero = 0, total = 0;   // zero: 1024 zeros, the bias operand of the adjoint launches
+  unsigned max_items = 0;
+};
+bool make_adj_layout(const PolicyLayout& L, PolAdjLayout& A) {
+  A = PolAdjLayout();
+  BlobCursor cur;
+  bool ok = true;
+  for (int li = 1; li < NCV; ++li) {
+    const PackDesc& F = L.T.pack[li];
+    PackDesc& P = A.T.pack[li];
+    P = F;
+    P.rows = F.K;
+    P.K = F.rows;
+    P.mt = 64;
+    P.nt = 0;
+    const int mask = trunk_taps(li, true);
+    for (int t = 0; t < 9; ++t)
+      if ((mask >> t) & 1) P.tap[P.nt++] = t;
+    P.adj = 1;
+    P.items = (unsigned)((size_t)P.rows * (P.K / 8) * P.nt);
+    P.dst = (unsigned)cur.put((size_t)P.rows * P.K * P.nt);
+    ok = ok && P.rows % 64 == 0 && P.K % 16 == 0;
+    if (P.items > A.max_items) A.max_items = P.items;
+  }
+  A.zero = cur.put(1024);
+  A.total = cur.dst + 8192;   // DMA over-read slack
+  return ok && A.total < ((size_t)1 << 32);
+}
+// One thread per (cout tile, K chunk, tap, K half, row) of adjoint packing blockIdx.y + 1; rb: the raw packing's weight scales
+__global__ __launch_bounds__(256) void pol_pack_adj_kernel(const PolAdjTable* __restrict__ T, const float* __restrict__ P,
+                                                           const float* __restrict__ rb, float* __restrict__ blob) {
+  const PackDesc& D = T->pack[blockIdx.y + 1];
+  const unsigned i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= D.items) return;
+  hs_pack_item(D, i, rb[D.conv], blob, [&](int row, int k, int tap) {
+    const long long off = eff_src_offset(D, k, row, 8 - tap);
+    return off < 0 ? 0.f : P[D.src_v + off];
+  });
+}
+
 // a fresh blob in the structural layout: zero padding and guards, the step lists; the packing workspace with its table
 int alloc_device_layout(PolicyPack& N, PackWorkspace& W, const PolicyLayout& L) {
   PNPX_TRY(alloc_dev(N.weights, L.total * sizeof(float), "policy weight"));
@@ -498,6 +548,7 @@ int policy_load_device(pnpx_ctx* ctx, const float* params_dev, size_t n, int num
     N.dev_layout = true;
   }
   N.raw_valid = false;   // new weights: the train-mode packing follows on the next train forward
+  N.adj_valid = false;   // ... and its adjoints on the next gradient call
   PNPX_TRY(N.live.set_device(params_dev, s));
   return repack(ctx, s);
 }
@@ -511,6 +562,48 @@ int policy_pack_raw(pnpx_ctx* ctx, hipStream_t s) {
     bind_blob(N.raw, L, N.spi_head);
   }
   return repack(ctx, s, true);
+}
+
+int policy_pack_adj(pnpx_ctx* ctx, hipStream_t s) {
+  PolicyNet& N = ctx->policy;
+  if (!N.raw_valid) PNPX_TRY(policy_pack_raw(ctx, s));
+  PolicyLayout L;
+  PNPX_TRY(layout_of("policy parameter gradient", N.num_inputs, N.n_det, N.spi_head, L));
+  PolAdjLayout A;
+  if (!make_adj_layout(L, A)) {
+    set_error("policy parameter gradient: internal adjoint layout error for %d inputs", N.num_inputs);
+    return PNPX_ERR_SHAPE;
+  }
+  if (!N.raw_adj.p) {
+    PNPX_TRY(alloc_dev(N.raw_adj, A.total * sizeof(float), "policy adjoint weight"));
+    if (!N.raw_adj_table.p) PNPX_TRY(alloc_dev(N.raw_adj_table, sizeof(PolAdjTable), "policy adjoint table"));
+    PNPX_HIP(hipMemset(N.raw_adj.p, 0, N.raw_adj.bytes));
+    PNPX_HIP(hipMemcpy(N.raw_adj_table.p, &A.T, sizeof(PolAdjTable), hipMemcpyHostToDevice));
+    PNPX_HIP(hipDeviceSynchronize());
+  }
+  float* blob = static_cast<float*>(N.raw_adj.p);
+  for (int li = 1; li < NCV; ++li) {
+    const PackDesc& P = A.T.pack[li];
+    ConvLayerHsDev& D = N.raw_bwd[li];
+    D.cin = D.cin_pad = P.K;
+    D.cout = P.rows;
+    D.mt = P.mt;
+    D.w = reinterpret_cast<char*>(blob + P.dst);
+    D.inv_scale = N.raw.hs[li].inv_scale;
+  }
+  N.raw_adj_zero = blob + A.zero;
+  hipLaunchKernelGGL(pol_pack_adj_kernel, dim3((A.max_items + 255) / 256, NCV - 1), dim3(256), 0, s,
+                     static_cast<const PolAdjTable*>(N.raw_adj_table.p), N.live.p(), pack_ws(N.raw_ws).rb, blob);
+  PNPX_LAUNCH_CHECK();
+  N.adj_valid = true;
+  return PNPX_OK;
+}
+
+int policy_conv_descs(const PolicyNet& N, PackDesc* out21) {
+  PolicyLayout L;
+  PNPX_TRY(layout_of("policy parameter gradient", N.num_inputs, N.n_det, N.spi_head, L));
+  for (int li = 0; li < NCV; ++li) out21[li] = L.T.pack[li];
+  return PNPX_OK;
 }
 
 int policy_refresh_eval(pnpx_ctx* ctx, hipStream_t s) {

@@ -460,6 +460,35 @@ def policy_bn_stats(ctx):
     return mean, var
 
 
+def policy_flat_size(ctx):
+    """Length of the loaded actor's flat parameter vector (policy_params)."""
+    if getattr(ctx, "_policy", None) is None:
+        raise PnpxError("no policy loaded")
+    return int(_lib.lib().pnpx_policy_num_params(*map(int, ctx._policy)))
+
+
+def policy_param_grad(ctx, ob, grad_probs, grad_det):
+    """Flat fp32 vector [n_params] on ob's device, policy_params' order: d sum(grad_probs * probs + grad_det * det) / d params
+    of the loaded actor, (probs, det) being policy_forward_train(ctx, ob) -- the actor's half of policy_loss.backward()
+    (trainer/mddpg/trainer.py:171-212) with grad_probs / grad_det = d policy_loss / d probs, d det.  The running-statistics
+    slots are zero.  Overwrites, does not accumulate; the forward is re-computed natively; nothing in the context changes."""
+    ob = _f32(ob, "ob")
+    if ob.dim() != 4 or getattr(ctx, "_policy", None) is None or ob.shape[1] != ctx._policy[0]:
+        raise PnpxError("policy_param_grad: no policy loaded or observation has the wrong channel count")
+    B, _, H, W = ob.shape
+    grad_probs = _f32(grad_probs, "grad_probs")
+    grad_det = _f32(grad_det, "grad_det")
+    if tuple(grad_probs.shape) != (B, 2) or tuple(grad_det.shape) != (B, ctx._policy[1]):
+        raise PnpxError(f"policy_param_grad: grad_probs / grad_det must be [{B}, 2] / [{B}, {ctx._policy[1]}], got "
+                        f"{tuple(grad_probs.shape)} / {tuple(grad_det.shape)}")
+    n = policy_flat_size(ctx)
+    out = torch.empty((n,), device=ob.device, dtype=torch.float32)
+    with torch.cuda.device(ob.device):
+        check(_lib.lib().pnpx_policy_param_grad(ctx.handle, _p(ob), _p(grad_probs), _p(grad_det), _p(out), n, B, H, W,
+                                                _stream(ob)))
+    return out
+
+
 def _critic_ob(ctx, ob, who):
     ob = _f32(ob, "ob")
     if ob.dim() != 4 or getattr(ctx, "_critic", None) is None or ob.shape[1] != ctx._critic:

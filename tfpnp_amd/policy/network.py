@@ -18,9 +18,12 @@ statistics (momentum 0.1) in the live parameter vector (pnpx_policy_forward_trai
 on the moved statistics -- so the reference's `run_policy` (eval -> forward -> train) and `_update` (trainer.py:128,171)
 behave as written, and `state_dict()` / `parameters_flat()` return the moved statistics.  The default `False` keeps the
 eval-mode forward whatever the mode: an nn.Module is in training mode from construction, and existing callers never call
-`.eval()`.  The train-mode forward carries no autograd graph.  Still out of scope: the actor's parameter and input
-gradients, its optimiser step and policy_loss, statistics synchronised across devices (dist.py), num_batches_tracked
-(momentum is a number, so torch never reads it), graph capture of the train forward.
+`.eval()`.  The train-mode forward carries no autograd graph; `forward_train_raw(state)` returns its raw head outputs
+(probs, det) without moving anything, and `param_grad(state, grad_probs, grad_det)` is the backward pass through it
+(pnpx_policy_param_grad): the flat gradient of sum(grad_probs * probs + grad_det * det) in `parameters_flat()`'s order, so a
+flat nn.Parameter and a torch optimiser can train the native actor (examples/train_actor.py).  Still out of scope: the
+actor's input gradient, its optimiser step and policy_loss, statistics synchronised across devices (dist.py),
+num_batches_tracked (momentum is a number, so torch never reads it), graph capture of the train forward.
 """
 from collections import OrderedDict
 from typing import Optional
@@ -78,6 +81,15 @@ class ResNetActorBase(LiveWeights):
         action = self.action_mapping(det)
         action['idx_stop'] = idx_stop
         return action, logp.gather(1, idx_stop.view(-1, 1)), entropy, hidden
+
+    def forward_train_raw(self, state):
+        """(probs [B,2], det [B,n_det]) of the train-mode forward (batch-statistics BatchNorm) on `state`; moves nothing."""
+        return T.call("policy_forward_train", state, self.bn_momentum, False, self.context(state.device).cid)
+
+    def param_grad(self, state, grad_probs, grad_det):
+        """d sum(grad_probs * probs + grad_det * det) / d parameters_flat(), (probs, det) = forward_train_raw(state): flat fp32
+        [n_params] on state's device, the running-statistics slots zero.  Changes nothing (no LiveWeights._mutate)."""
+        return T.call("policy_param_grad", state.detach(), grad_probs.detach(), grad_det.detach(), self.context(state.device).cid)
 
     def action_mapping(self, action_deterministic):
         """Sigmoid outputs [B, num_actions * bundle] -> {name: [B, bundle] in the action's range} (network.py:163-175)."""

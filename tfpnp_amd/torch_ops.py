@@ -144,7 +144,7 @@ def policy_forward_train(ob: Tensor, momentum: float, update_running: bool, ctx:
     """ResNetActorBase.forward in train mode (batch-statistics BatchNorm): ob [B,C,H,W] -> (probs [B,2], det [B,n]).
     With update_running it moves the running statistics inside the native context `ctx` -- it mutates the context, none of
     its tensor arguments.  There is no autograd formula: under requires_grad inputs the outputs carry no graph, as for
-    policy_forward (the actor's gradients are not part of this package yet)."""
+    policy_forward (the actor's parameter gradient is a call of its own: policy_param_grad)."""
     return ops.policy_forward_train(ops.context_by_id(ctx), ob, momentum, update_running)
 
 
@@ -153,6 +153,18 @@ def _(ob, momentum, update_running, ctx):
     n_det = ops.context_by_id(ctx)._policy[1]
     return (torch.empty((ob.shape[0], 2), dtype=ob.dtype, device=ob.device),
             torch.empty((ob.shape[0], n_det), dtype=ob.dtype, device=ob.device))
+
+
+@_lib_def("pnpx::policy_param_grad", mutates_args=(), device_types="cuda")
+def policy_param_grad(ob: Tensor, grad_probs: Tensor, grad_det: Tensor, ctx: int) -> Tensor:
+    """d sum(grad_probs * probs + grad_det * det) / d params through the train-mode forward (ops.policy_param_grad): the flat
+    gradient vector in policy_params' order.  Mutates nothing; no autograd formula (it IS the backward pass)."""
+    return ops.policy_param_grad(ops.context_by_id(ctx), ob, grad_probs, grad_det)
+
+
+@policy_param_grad.register_fake
+def _(ob, grad_probs, grad_det, ctx):
+    return torch.empty((ops.policy_flat_size(ops.context_by_id(ctx)),), dtype=torch.float32, device=ob.device)
 
 
 # ------------------------------------------------------------------------------------------------- transforms
@@ -609,7 +621,7 @@ def call(name, *args):
 
 
 ALL_OPS = ("unet_denoise", "unet_denoise_preclamp", "unet_denoise_backward", "unet_denoise_train",
-           "unet_denoise_backward_ticket", "policy_forward", "policy_forward_train", "fft2", "cdp_forward",
+           "unet_denoise_backward_ticket", "policy_forward", "policy_forward_train", "policy_param_grad", "fft2", "cdp_forward",
            "cdp_backward", "spi_inverse", "psnr", "radon_forward", "radon_backprojection", "csmri_admm", "csmri_admm_train",
            "csmri_admm_backward", "csmri_hqs", "csmri_amp",
            "csmri_pg", "csmri_apg", "csmri_redadmm", "pr_iadmm", "spi_admm", "ct_iadmm", "ct_pg", "pr_pg",
