@@ -99,8 +99,8 @@ int pnpx_ctx_reserve(pnpx_ctx* ctx, int B, int H, int W);
  *  "fft_fast" (default 1): N = 256 lines on the register-radix-16 kernels (0 = the generic Stockham passes; same results to rounding).
  *  "fuse_first" (default 1): the half-split family's first convolution reads the fp32 image and the noise level directly (no padded
  *      two-channel input tensor); 0 = separate input preparation + the generic kernel (bit-identical).
- *  "policy_s2_hs" (default 1): the policy actor's stem and stride-2 stage entries on the sparse-tap half-split instances over space-to-depth
- *      tensors (0 = the fp32 space-to-depth convolution kernel of policy_conv.hip for those layers).
+ *  "policy_s2_hs": accepted (0 or 1, reads back as 1) and without effect -- the fp32 entry kernel that 0 used to select for the policy
+ *      actor's stem and stride-2 stage entries is gone, so a caller that sets it keeps running and gets the only path's results.
  *  "fold_first" (default 0): 1 = the network's first convolution is evaluated inside the tile loader of the second one
  *      (its output tensor is neither written nor read; bit-identical, time-neutral).
  *  "fuse_up" (default 1 since r5): 1 = the full-resolution decoder entry (96 -> 32 channels) up-samples its low-resolution source
@@ -195,12 +195,10 @@ int pnpx_policy_forward(pnpx_ctx* ctx, const float* ob, float* probs, float* det
 /* The weights are LIVE, as the critic's are: the context keeps the flat parameter vector on the device after either load entry.
  * pnpx_policy_load_device is pnpx_policy_load from a vector in DEVICE memory (same order, same length): the BatchNorm fold
  * (scale = weight / sqrt(running_var + 1e-5), shift = bias - running_mean * scale, in the host's fp32 roundings), the per-convolution
- * half-split scales and every packed layout the forward reads -- both settings of option "policy_s2_hs" -- are derived by a handful
- * of kernels on `stream`.  The outputs of pnpx_policy_forward equal those after pnpx_policy_load of the same values bit for bit.
+ * half-split scales and the packed layout the forward reads are derived by a handful of kernels on `stream`.  The outputs of pnpx_policy_forward equal those after pnpx_policy_load of the same values bit for bit.
  * The first call on a context, or one with another (num_inputs, n_det, spi_head), allocates; every later call refreshes in place:
- * no allocation, no device-wide synchronisation, the activation workspace is kept.  On a context that pnpx_policy_load loaded, the
- * first call replaces the weight blob once (the host decides which fp32 tap slices exist by their values, the device by structure)
- * and keeps the workspace.  Each call ends with one small stream-ordered read-back of the 21 weight scales and a synchronisation of
+ * no allocation, no device-wide synchronisation, the activation workspace is kept -- on a context that pnpx_policy_load loaded too
+ * (the host packs the blob at the offsets the device packing writes to).  Each call ends with one small stream-ordered read-back of the 21 weight scales and a synchronisation of
  * `stream` (the launches take them by value).  A scale that is not finite -- running_var NaN or below -1e-5, a BatchNorm weight
  * that is not finite, a NaN convolution weight -- returns PNPX_ERR_ARG and leaves the context without an actor; a wrong n_params
  * returns PNPX_ERR_ARG and changes nothing.  Not capturable into a graph.
@@ -225,7 +223,7 @@ int pnpx_policy_params(pnpx_ctx* ctx, float* dst_dev, size_t n_params, void* str
  * The convolutions run on a second, fold-free packing of the live vector, derived by the first call after a load (one stream
  * synchronisation, as pnpx_policy_load_device) together with a workspace that grows with B; eval-only users pay for neither.
  * Batch statistics couple the images: the call is ONE launch chain whatever option "chains" says, and its result is deterministic
- * (fixed-order reductions in double, no atomics).  Both settings of option "policy_s2_hs" are served.  Not capturable into a graph.
+ * (fixed-order reductions in double, no atomics).  Not capturable into a graph.
  * H, W multiples of 32 (else PNPX_ERR_SHAPE); PNPX_ERR_ARG when the last stage has B * (H/32) * (W/32) < 2 values per channel
  * (torch raises there) or momentum is outside [0, 1]; PNPX_ERR_NO_WEIGHTS before a load.  Out of scope: the optimiser step, statistics
  * synchronised across devices, activations kept for a backward pass (pnpx_policy_param_grad re-computes). */
@@ -242,9 +240,8 @@ int pnpx_policy_bn_stats(pnpx_ctx* ctx, float* mean_dev, float* var_dev, size_t 
  * pnpx_critic_param_grad.  grad_params has the layout of pnpx_policy_params (n_params floats); every element is written, the
  * running_mean / running_var slots as zeros.  All pointers are device pointers.  Changes no weights and no running statistics; the
  * batch statistics pnpx_policy_bn_stats reads afterwards are those of a train forward on `ob`.
- * The call re-computes the forward (nothing is kept from pnpx_policy_forward_train), ALWAYS on the half-split stage entries whatever
- * option "policy_s2_hs" says (the weight-gradient kernel reads HS8 operands), then runs BatchNorm backward, the weight-gradient GEMM
- * and the adjoint convolution per layer.  Deterministic: fixed-order reductions in double, no floating-point atomics; the same bytes
+ * The call re-computes the forward (nothing is kept from pnpx_policy_forward_train), then runs BatchNorm backward, the weight-gradient
+ * GEMM and the adjoint convolution per layer.  Deterministic: fixed-order reductions in double, no floating-point atomics; the same bytes
  * on every call, whatever ran before.  Gradients travel scaled by a power of two chosen on the device from the upstream gradients:
  * the result is exactly homogeneous in powers of two of (grad_probs, grad_det), all-zero upstream gradients give an all-zero vector,
  * and there is no host read-back -- a call that grows no buffer allocates nothing and does not synchronise the device.  The first

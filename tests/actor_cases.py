@@ -1,7 +1,6 @@
 """Cases and helpers of the actor live-weight tests: a torch stand-in for the reference's ResNetActor_* written from
-synth.policy_param_specs (same attribute names, so the same state_dict keys), flat-vector helpers, the output comparison,
-and a numpy restatement of the host's dense effective weights (csrc/resnet18_hs.hip: Eff, put_conv_s2, put_shortcut behind csrc/policy.hip: bn_folded; csrc/policy.hip: pack_eff)
-that checks the structural-presence rule of the device packing.  No GPU needed to import, no reference import."""
+synth.policy_param_specs (same attribute names, so the same state_dict keys), flat-vector helpers and the output comparison.
+No GPU needed to import, no reference import."""
 import numpy as np
 import torch
 import torch.nn as nn
@@ -13,7 +12,6 @@ from tfpnp_amd import synth
 CASES = [(9, 10, False), (7, 10, False), (17, 15, False), (6, 10, True)]
 _ACTORS = {(9, 10, False): ("ResNetActor_ADMM", 6), (7, 10, False): ("ResNetActor_HQS", 5),
            (17, 15, False): ("ResNetActor_IADMM", 14), (6, 10, True): ("ResNetActor_SPI", 3)}
-BN_EPS = np.float32(1e-5)
 
 
 def native_actor(case, state_dict=None):
@@ -124,59 +122,3 @@ def same_outputs(a, b, ob):
     varies = bool((pa[0] != pa[1]).any())
     return torch.equal(pa, pb) and torch.equal(da, db) and finite and varies
 
-
-# ------------------------------------------------------------------------------- structural presence of the fp32 tap slices
-def _bn_scale(P, pre):
-    return (P[pre + ".weight"] / np.sqrt(P[pre + ".running_var"] + BN_EPS)).astype(np.float32)
-
-
-def _put_conv_s2(E, w, sc, Cp):
-    """csrc/resnet18_hs.hip::put_conv_s2: 3x3 stride-2 convolution over a space-to-depth input with Cp channels per phase."""
-    cout, cin = w.shape[:2]
-    for dy in range(3):
-        for dx in range(3):
-            py, ty = (0 if dy == 1 else 1), (0 if dy == 0 else 1)
-            px, tx = (0 if dx == 1 else 1), (0 if dx == 0 else 1)
-            k0 = (py * 2 + px) * Cp
-            E[:cout, k0:k0 + cin, ty * 3 + tx] = w[:, :, dy, dx] * sc[:, None]
-
-
-def entry_launches(P, num_inputs):
-    """The five fp32 launches of policy_load as dense effective weights E[cout][K][9] (BatchNorm folded): the stem, then
-    per stage conv1 (rows [0, p)) merged with the 1x1 shortcut (rows [p, 2p), centre tap of phase (0,0)).
-    Yields (name, E, rows of conv1, real input channels, channels per phase)."""
-    cin_pad = (num_inputs + 7) // 8 * 8
-    E = np.zeros((64, 4 * cin_pad, 9), np.float32)
-    _put_conv_s2(E, P["actor_encoder.conv1.weight"], _bn_scale(P, "actor_encoder.bn1"), cin_pad)
-    yield "stem", E, 64, num_inputs, cin_pad
-    cin = 64
-    for li, p in enumerate((64, 128, 256, 512), start=1):
-        pre = f"actor_encoder.layer{li}.0"
-        E = np.zeros((2 * p, 4 * cin, 9), np.float32)
-        _put_conv_s2(E, P[pre + ".conv1.weight"], _bn_scale(P, pre + ".bn1"), cin)
-        E[p:, :cin, 4] = P[pre + ".shortcut.0.weight"][:, :, 0, 0] * _bn_scale(P, pre + ".shortcut.1")[:, None]
-        yield f"layer{li}", E, p, cin, cin
-        cin = p
-
-
-def present_by_value(E):
-    """pack_eff's rule: slice (cout tile, 8-channel chunk, tap) exists iff it holds a non-zero value -> bool [nct][nch][9]"""
-    cout, K, _ = E.shape
-    return (E.reshape(cout // 64, 64, K // 8, 8, 9) != 0).any(axis=(1, 3))
-
-
-def present_by_structure(cout, K, split, cin, Cp):
-    """The device packing's rule: a conv1 tile has tap 4 in phase (0,0), taps 3, 4 in (0,1), 1, 4 in (1,0) and 0, 1, 3, 4 in
-    (1,1), in every chunk of the phase that holds a real input channel; a shortcut tile has tap 4 in the phase-(0,0) chunks."""
-    taps = {0: (4,), 1: (3, 4), 2: (1, 4), 3: (0, 1, 3, 4)}
-    out = np.zeros((cout // 64, K // 8, 9), bool)
-    for ct in range(cout // 64):
-        for ch in range(K // 8):
-            ph, first = divmod(ch * 8, Cp)
-            if first >= cin:
-                continue
-            if ct * 64 < split:
-                out[ct, ch, list(taps[ph])] = True
-            elif ph == 0:
-                out[ct, ch, 4] = True
-    return out

@@ -1,6 +1,5 @@
 """Host-side checks of the actor's live-weight entries (no GPU): the C ABI / binding surface, the stand-in module against
-synth.policy_param_specs, the name-based gather of utils.misc.hard_update and its refusals, and the structural-presence rule
-of the device packing against the host's value-based one."""
+synth.policy_param_specs, and the name-based gather of utils.misc.hard_update and its refusals."""
 import os
 import re
 
@@ -97,17 +96,3 @@ def test_updates_refuse_cpu_and_non_fp32_sources():
         hard_update(target, ResNet_wobn(9, 18, 1))
     assert target.state_dict() == {} and target.device is None
 
-
-@pytest.mark.parametrize("case", A.CASES)
-def test_structural_presence_equals_value_presence(case):
-    """For synth.make_policy_params weights no structurally present fp32 tap slice is all zero (and no absent one holds a
-    value), so the device packing's layout is the host's."""
-    P = synth.make_policy_params(*case, seed=7)
-    n = 0
-    for name, E, split, cin, Cp in A.entry_launches(P, case[0]):
-        by_value = A.present_by_value(E)
-        by_structure = A.present_by_structure(E.shape[0], E.shape[1], split, cin, Cp)
-        assert (by_value == by_structure).all(), name
-        n += int(by_structure.sum())
-    nc = (case[0] + 7) // 8
-    assert n == 9 * nc + sum((p // 64) * (cin // 8) * 10 for p, cin in ((64, 64), (128, 64), (256, 128), (512, 256)))

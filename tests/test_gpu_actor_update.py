@@ -1,6 +1,6 @@
-"""GPU tests of the actor's live weights (csrc/policy_pack.hip): the device load against the host load (bitwise, both
-settings of policy_s2_hs), the in-place refresh, a module source against the CPU oracle, state_dict() / native -> native,
-ordering behind a chained forward, and the rejections.
+"""GPU tests of the actor's live weights (csrc/policy_pack.hip): the device load against the host load (bitwise), the
+in-place refresh (of a host-loaded actor too; the retired option policy_s2_hs changes nothing), a module source against the
+CPU oracle, state_dict() / native -> native, ordering behind a chained forward, and the rejections.
 
 "Bitwise" on results is torch.equal on probs and det of the same observations: both actors run the same kernels, so equal
 packed weights, biases and scales give equal bits, and an error in any packed weight that matters shows.  Parameter vectors
@@ -70,18 +70,14 @@ def bits_equal(a, b):
 
 
 # ------------------------------------------------------------------------------------------------ 1. device load == host load
-@pytest.mark.parametrize("s2_hs", [1, 0])
+@pytest.mark.parametrize("s2_hs", [1])     # the retired option's remaining value: accepted, without effect
 @pytest.mark.parametrize("case", A.CASES)
 def test_device_load_equals_host_load(case, s2_hs):
     host, devc = host_actor(case, 7), device_actor(case, 7)
-    ctxs = (host.context(dev()), devc.context(dev()))
-    try:
-        for c in ctxs:
-            c.set_option("policy_s2_hs", s2_hs)
-        assert A.same_outputs(host, devc, obs(case))
-        assert A.same_outputs(host, devc, obs(case, B=3, H=64, W=96))
-    finally:
-        host.context(dev()).set_option("policy_s2_hs", 1)
+    for c in (host.context(dev()), devc.context(dev())):
+        c.set_option("policy_s2_hs", s2_hs)
+    assert A.same_outputs(host, devc, obs(case))
+    assert A.same_outputs(host, devc, obs(case, B=3, H=64, W=96))
     assert bits_equal(devc.parameters_flat(dev()), flat_cpu(case, 7))
     assert bits_equal(host.parameters_flat(dev()), flat_cpu(case, 7))     # the host entry keeps the vector too
     torch.cuda.synchronize()
@@ -125,6 +121,50 @@ def test_refresh_of_a_host_loaded_actor():
     net.load_flat_(flat_cpu(ADMM, 7).to(dev()))
     p, d = forward(net, ob)
     assert torch.equal(p, p7) and torch.equal(d, d7)
+
+
+def test_retired_option_is_inert_and_a_host_load_refreshes_in_place():
+    """policy_s2_hs used to select an fp32 kernel for the stem and the stage entries and a second blob layout behind the host
+    load.  Now the key is accepted and changes nothing, and a host-loaded actor is refreshed in place like a device-loaded one.
+    B = 2 at 32 x 32: the smallest legal image, and the fewest observations the batch statistics accept."""
+    ob = obs(ADMM)
+
+    def run(setting):
+        ctx = A.native_actor(ADMM, state_dict=params(ADMM, 7)).context(dev())
+        ctx.set_option("policy_s2_hs", setting)
+        assert ctx.get_option("policy_s2_hs") == 1
+        out = [*ops.policy_forward(ctx, ob), *ops.policy_forward_train(ctx, ob), *ops.policy_bn_stats(ctx), ctx.policy_params()]
+        used = ctx.bytes()
+        ctx.set_option("policy_s2_hs", 0)
+        ctx.set_option("policy_s2_hs", 1)
+        assert ctx.bytes() == used
+        ops.policy_forward_train(ctx, ob, update_running=False)                  # no arena was dropped: nothing is reserved again
+        assert ctx.bytes() == used
+        return out
+
+    one, zero = run(1), run(0)
+    names = ("probs", "det", "train probs", "train det", "batch mean", "batch var", "live vector")
+    for name, a, b in zip(names, one, zero):
+        assert bits_equal(a, b), name
+    assert not bits_equal(one[6], flat_cpu(ADMM, 7))                             # the train forward did move the statistics
+
+    # test_refresh_in_place's check, starting from the host entry
+    refs = {s: forward(host_actor(ADMM, s), ob) for s in (8, 9)}
+    flats = {s: flat_cpu(ADMM, s).to(dev()) for s in (8, 9)}
+    net = A.native_actor(ADMM, state_dict=params(ADMM, 7))
+    ctx = net.context(dev())
+    forward(net, ob)                                                             # the arena exists from here on
+    free = []
+    for s in (8, 9, 8):
+        net.load_flat_(flats[s])
+        assert net.context(dev()) is ctx
+        p, d = forward(net, ob)
+        assert torch.equal(p, refs[s][0]) and torch.equal(d, refs[s][1]), s
+        del p, d
+        torch.cuda.synchronize()
+        free.append(torch.cuda.mem_get_info()[0])
+    print("free bytes after each refresh of a host-loaded actor:", free)
+    assert free[1] == free[2]                                                    # no reallocation, no leak
 
 
 # ------------------------------------------------------------------------------------------------ 3. module source

@@ -361,13 +361,7 @@ int pnpx_ctx_set_option(pnpx_ctx* ctx, const char* key, int value) {
     ctx->opt_fuse_first = value;
     return PNPX_OK;
   }
-  if (is("policy_s2_hs") && (value == 0 || value == 1)) {   // (the arena is re-zeroed: the two layouts share a buffer)
-    PNPX_HIP(hipDeviceSynchronize());
-    ctx->opt_policy_s2_hs = value;
-    ctx->policy.capB = ctx->policy.capH = ctx->policy.capW = 0;
-    ctx->policy.tcapB = ctx->policy.tcapH = ctx->policy.tcapW = 0;
-    return PNPX_OK;
-  }
+  if (is("policy_s2_hs") && (value == 0 || value == 1)) return PNPX_OK;   // accepted, without effect (include/pnpx.h)
   if (is("fold_first") && (value == 0 || value == 1)) {
     ctx->opt_fold_first = value;
     return PNPX_OK;
@@ -461,7 +455,7 @@ int pnpx_ctx_get_option(pnpx_ctx* ctx, const char* key, int* value) {
   else if (is("wreg")) *value = ctx->opt_wreg;
   else if (is("chains")) *value = ctx->opt_chains;
   else if (is("fold_first")) *value = ctx->opt_fold_first;
-  else if (is("policy_s2_hs")) *value = ctx->opt_policy_s2_hs;
+  else if (is("policy_s2_hs")) *value = 1;
   else if (is("fft_affine")) *value = ctx->opt_fft_affine;
   else if (is("fft_fast")) *value = ctx->opt_fft_fast;
   else if (is("fp32_winograd")) *value = ctx->opt_fp32_winograd;

@@ -79,19 +79,8 @@ struct ConvLayerHsDev {     // the same conv packed for the half-split f16 kerne
 enum ConvMode { CONV_F32 = 0, CONV_HS = 1 };
 
 // ---------------------------------------------------------------------------------------------------
-// Policy actor (ResNet-18 encoder + heads, eval mode) -- policy.hip.  One PolicyConv per launch: BatchNorm is folded
-// into weights/bias at load time; stride-2 convolutions run as stride-1 convolutions over a space-to-depth input
-// with per-(cout tile, K-chunk) tap masks; the 1x1 stride-2 shortcut rides in the same launch as extra cout tiles.
-struct PolStep;
-struct PolicyConv {
-  const float* w = nullptr;              // device: present tap slices [8][64], in PolStep order
-  const float* bias = nullptr;           // device: [cout]
-  const PolStep* steps = nullptr;        // device: [cout/64][cin/8] (first nsteps[ct] entries of each row valid)
-  const int* nsteps = nullptr;           // device: [cout/64]
-  int cin = 0;      // K channels of the (possibly space-to-depth) input, multiple of 8
-  int cout = 0;     // output channels over both outputs, multiple of 64
-  int split_c = 0;  // channels written to the first output (ReLU); the rest go to the second output (linear)
-};
+// Policy actor (ResNet-18 encoder + heads) -- policy.hip.  BatchNorm is folded into weights / bias when the eval packing is derived;
+// every convolution runs on the half-split launches of the trunk the critic shares (resnet18_hs.h).
 // the packed weights one forward reads: launch descriptors over one device blob
 struct PolicyPack {
   // the 21 convolutions of the trunk packed for the half-split launches, in the layer numbering of resnet18_hs.h: the stem and the
@@ -99,7 +88,6 @@ struct PolicyPack {
   // (0x010, first Cin channels), the stride-1 convolutions (f16x3 MFMA kernel, conv_hs.hip)
   ConvLayerHsDev hs[21];
   const float* hs_bias[21] = {};
-  PolicyConv f32[5];         // option policy_s2_hs = 0: the stem, then per stage conv1 + shortcut as one fp32 tap-sparse launch
   const float* fc_sm_w = nullptr;   // [2][512], [2]
   const float* fc_sm_b = nullptr;
   const float* fc_det_w = nullptr;  // [n_det][512] ([64][512] with the SPI head)
@@ -115,7 +103,6 @@ struct PolicyNet : PolicyPack {   // the base: the eval-mode packing (BatchNorm 
   int capB = 0, capH = 0, capW = 0;
   // live weights (policy_pack.hip): the flat fp32 parameter vector in pnpx_policy_load's order, kept after either load entry
   LiveParams live;
-  bool dev_layout = false;   // `weights` has the structural layout policy_load_device refreshes in place (else: policy_load's)
   PackWorkspace pack_ws;     // layer table, per-channel BatchNorm scales / shifts / weight maxima; read back: the 21 half-split weight scales
   // train-mode forward (policy_bn.hip): the same convolutions packed WITHOUT the fold (scale 1, shift 0), derived from `live` by the
   // first train forward after a load; moving the running statistics does not stale it, but it stales the eval packing above, which the
@@ -229,7 +216,6 @@ struct pnpx_ctx {
   int opt_fuse_first = 1;          // VALU first convolution straight from the fp32 image (no padded-input tensor)
   int opt_fuse_up = 1;             // bilinear x2 of the full-resolution decoder entry inside the conv kernel (producer waves): r5 default --
                                    // bit-identical to the separate kernel (tools/ab_fuse_up.py), forward 5.82 -> 5.76 ms at 48 x 256^2
-  int opt_policy_s2_hs = 1;        // policy actor: the stride-2 stage entries on the sparse-tap half-split instances
   int opt_fold_first = 0;          // opt-in: first convolution folded into the loader of the second one (conv_hs WREG == 2;
                                    // bit-identical, 400 MB less HBM traffic per forward, time-neutral: 5.835 vs 5.841 ms)
   int opt_fft_tile = 0;            // complex points per FFT workgroup tile (0 = FFT_TILE_POINTS)
@@ -420,8 +406,9 @@ int policy_load_device(pnpx_ctx* ctx, const float* params_dev, size_t n, int num
 int policy_params(pnpx_ctx* ctx, float* dst_dev, size_t n, hipStream_t s);
 int policy_pack_raw(pnpx_ctx* ctx, hipStream_t s);       // live vector -> PolicyNet::raw (allocates on first use)
 int policy_refresh_eval(pnpx_ctx* ctx, hipStream_t s);   // live vector -> the eval packing, after the running statistics moved
+struct Packed;                                           // one host packing (resnet18_hs.h)
+int policy_adopt_host_blob(pnpx_ctx* ctx, const Packed* pk21, const size_t* heads6, size_t total);   // policy_load's last step
 // pieces of the eval forward the train forward shares (policy.hip; the half-split ones: resnet18_hs.h)
-int policy_launch_pack_ob_f32(const float* ob, float* out, int C, int Cp, int B, int H, int W, hipStream_t s);   // option policy_s2_hs = 0
 int policy_launch_heads(const PolicyPack& P, int n_det, int spi_head, const char* feat_hs, int h, int w, int B, float* probs, float* det,
                          hipStream_t s);
 // train-mode forward (policy_bn.hip)

@@ -26,9 +26,9 @@ struct LiveParams {
 };
 
 struct PackDims {     // grid dimensions of the refresh launches over one table
-  unsigned nchan = 0;                          // output channels over all convolutions
-  unsigned max_items = 0, max_f32_items = 0;   // largest half-split packing; largest fp32 tap-slice packing (actor only)
-  unsigned max_copy = 0;                       // largest copy, of ncopy
+  unsigned nchan = 0;        // output channels over all convolutions
+  unsigned max_items = 0;    // largest half-split packing
+  unsigned max_copy = 0;     // largest copy, of ncopy
   int ncopy = 0;
 };
 struct PackWorkspace {

@@ -11,8 +11,8 @@
 //   bn_finish_kernel    per channel: the pieces in order -> mean, biased variance, scale = weight * rsqrt(var + eps),
 //                       shift = bias - mean * scale; optionally the running-statistics update, written into the live vector
 //   bn_apply_kernel     relu((z - mean) * scale + bias [+ the same of the shortcut's z | + residual]) -> the HS8 activation the next
-//                       convolution reads and, before a stride-2 entry, its space-to-depth copy (HS8, or fp32 planar with
-//                       policy_s2_hs = 0).  (z - mean) * scale + bias is z * scale + shift without the cancellation of two large terms.
+//                       convolution reads and, before a stride-2 entry, its HS8 space-to-depth copy.
+//                       (z - mean) * scale + bias is z * scale + shift without the cancellation of two large terms.
 // Batch statistics couple the images: the forward is ONE launch chain whatever the "chains" option says.  Pool and heads are the
 // eval forward's.  Nothing is kept for a backward pass; fusing the passes into the convolutions is a later step.
 //
@@ -26,7 +26,6 @@
 #include "critic_grad.h"
 #include "hs_rec.h"
 #include "hs_relayout.h"
-#include "policy_conv.h"
 #include "policy_grad.h"
 #include "resnet18_hs.h"
 
@@ -106,7 +105,7 @@ __global__ __launch_bounds__(256) void bn_partial_kernel(const HsRec* __restrict
 
 struct BnFinishArgs {
   const double* part;
-  int C, c_off, cout, npieces;   // channels of the tensor behind `part`; this layer's first channel in it and its size
+  int cout, npieces;             // channels of the layer = of the tensor behind `part`
   long long n;                   // values per channel
   float* params;                 // the live parameter vector
   size_t bn;                     // BnLayer::bn
@@ -119,7 +118,7 @@ __global__ __launch_bounds__(64) void bn_finish_kernel(BnFinishArgs a) {
   if (c >= a.cout) return;
   double s = 0.0, q = 0.0;
   for (int p = 0; p < a.npieces; ++p) {
-    const double* e = a.part + ((size_t)p * a.C + a.c_off + c) * 2;
+    const double* e = a.part + ((size_t)p * a.cout + c) * 2;
     s += e[0];
     q += e[1];
   }
@@ -142,8 +141,7 @@ __global__ __launch_bounds__(64) void bn_finish_kernel(BnFinishArgs a) {
 }
 
 struct BnSrc {
-  const HsRec* z;      // null: absent
-  int Gt, g0;          // channel groups per image of the tensor; the first group of this layer in it
+  const HsRec* z;      // the layer's raw output, HS8 [B][G][h+2][w+2]; null: absent
   const float *mean, *scale, *beta;   // at the layer's first channel
 };
 struct BnApplyArgs {
@@ -151,13 +149,12 @@ struct BnApplyArgs {
   const HsRec* res;    // identity residual, HS8 [B][G][h+2][w+2], or null
   HsRec* out;          // HS8 [B][G][h+2][w+2] or null
   HsRec* s2d_hs;       // HS8 [B][4G][h/2+2][w/2+2] (phase-major groups, hs_relayout.h) or null
-  float* s2d_f32;      // fp32 planar [B][4 * 8G][h/2+2][pol_wp(w/2)] or null
   int G, h, w;
   size_t n;            // B * G * h * w records
 };
-__device__ __forceinline__ void bn_term(const BnSrc& s, size_t b, int g, int y, int x, int h, int w, float v[8], bool add) {
+__device__ __forceinline__ void bn_term(const BnSrc& s, size_t b, int G, int g, int y, int x, int h, int w, float v[8], bool add) {
   float zz[8];
-  hs_unpack(s.z[((b * s.Gt + s.g0 + g) * (h + 2) + (y + 1)) * (size_t)(w + 2) + (x + 1)], zz);
+  hs_unpack(s.z[((b * G + g) * (h + 2) + (y + 1)) * (size_t)(w + 2) + (x + 1)], zz);
 #pragma unroll
   for (int e = 0; e < 8; ++e) {
     const int c = g * 8 + e;
@@ -176,8 +173,8 @@ __global__ __launch_bounds__(256) void bn_apply_kernel(BnApplyArgs a) {
   const int g = (int)(t % G);
   const size_t b = t / G;
   float v[8];
-  bn_term(a.a, b, g, y, x, h, w, v, false);
-  if (a.b.z) bn_term(a.b, b, g, y, x, h, w, v, true);
+  bn_term(a.a, b, G, g, y, x, h, w, v, false);
+  if (a.b.z) bn_term(a.b, b, G, g, y, x, h, w, v, true);
   if (a.res) {
     float r[8];
     hs_unpack(a.res[((b * G + g) * (h + 2) + (y + 1)) * (size_t)(w + 2) + (x + 1)], r);
@@ -194,12 +191,6 @@ __global__ __launch_bounds__(256) void bn_apply_kernel(BnApplyArgs a) {
   if (a.out) a.out[((b * G + g) * (h + 2) + (y + 1)) * (size_t)(w + 2) + (x + 1)] = rec;
   const int ph = (y & 1) * 2 + (x & 1), h2 = h >> 1, w2 = w >> 1;
   if (a.s2d_hs) a.s2d_hs[((b * 4 * G + (size_t)ph * G + g) * (h2 + 2) + ((y >> 1) + 1)) * (size_t)(w2 + 2) + (x >> 1) + 1] = rec;
-  if (a.s2d_f32) {
-    const int C = 8 * G, Hp2 = padded_h(h2), Wp2 = pol_wp(w2);
-    float* o = a.s2d_f32 + ((b * 4 * C + (size_t)ph * C + g * 8) * Hp2 + (y >> 1) + 1) * Wp2 + (x >> 1) + POL_PADL;
-#pragma unroll
-    for (int e = 0; e < 8; ++e) o[(size_t)e * Hp2 * Wp2] = v[e];
-  }
 }
 
 // ------------------------------------------------------------------------------------------- workspace plan (offsets in floats)
@@ -218,46 +209,46 @@ struct TrainPlan {
   size_t total = 0;
 };
 inline size_t bn_pieces(long long npix) { return (size_t)((npix + BN_PIECE - 1) / BN_PIECE); }
-// s2_hs: the observation and the space-to-depth activations are HS8 tensors (else fp32 planar).  keep: the gradient's plan (s2_hs only)
-TrainPlan make_train_plan(int capB, int cin_pad, int H, int W, bool s2_hs, bool keep = false) {
+// every tensor is HS8.  keep: the gradient's plan
+TrainPlan make_train_plan(int capB, int cin_pad, int H, int W, bool keep = false) {
   TrainPlan P;
   size_t off = 0, part = 0;
-  auto add = [&](size_t& d, int C, int h, int w, bool hs) {
+  auto add = [&](size_t& d, int C, int h, int w) {
     d = off;
-    off += (hs ? (size_t)C * (h + 2) * (w + 2) : (size_t)C * padded_h(h) * pol_wp(w)) * capB;
+    off += hs_act_floats(C, h, w) * capB;
     off = (off + 63) & ~(size_t)63;
   };
   auto stat = [&](int C, int h, int w) {
     const size_t n = bn_pieces((long long)capB * h * w) * C * 2;
     if (n > part) part = n;
   };
-  add(P.ob, 4 * cin_pad, H / 2, W / 2, s2_hs);
-  add(P.zstem, 64, H / 2, W / 2, true);
+  add(P.ob, 4 * cin_pad, H / 2, W / 2);
+  add(P.zstem, 64, H / 2, W / 2);
   stat(64, H / 2, W / 2);
-  add(P.stem_s, 4 * 64, H / 4, W / 4, s2_hs);
+  add(P.stem_s, 4 * 64, H / 4, W / 4);
   if (keep) {
-    add(P.stem_a, 64, H / 2, W / 2, true);
-    add(P.g_stem, 64, H / 2, W / 2, true);
-    add(P.dz_stem, 64, H / 2, W / 2, true);
+    add(P.stem_a, 64, H / 2, W / 2);
+    add(P.g_stem, 64, H / 2, W / 2);
+    add(P.dz_stem, 64, H / 2, W / 2);
   }
   int in_planes = 64;
   for (int n = 0; n < 4; ++n) {
     const int p = stage_planes(n), h = H >> (n + 2), w = W >> (n + 2);
-    add(P.za[n], 2 * p, h, w, true);   // the entry's two outputs: one tensor of 2p channels (fp32 launch) or two of p, back to back
-    add(P.z2[n], p, h, w, true);
+    add(P.za[n], 2 * p, h, w);   // the entry's two outputs, conv1 and the shortcut: two tensors of p channels back to back
+    add(P.z2[n], p, h, w);
     P.z3[n] = P.z4[n] = P.z2[n];
-    add(P.t1[n], p, h, w, true);
-    add(P.o0[n], p, h, w, true);
-    add(P.t2[n], p, h, w, true);
-    add(P.o1[n], p, h, w, true);
-    if (n < 3) add(P.o1s[n], 4 * p, h / 2, w / 2, s2_hs);
-    stat(2 * p, h, w);
+    add(P.t1[n], p, h, w);
+    add(P.o0[n], p, h, w);
+    add(P.t2[n], p, h, w);
+    add(P.o1[n], p, h, w);
+    if (n < 3) add(P.o1s[n], 4 * p, h / 2, w / 2);
+    stat(p, h, w);
     if (keep) {
-      add(P.z3[n], p, h, w, true);
-      add(P.z4[n], p, h, w, true);
-      for (size_t* g : {&P.gA[n], &P.gB[n], &P.gM[n], &P.dZ[n], &P.dZs[n], &P.dY[n]}) add(*g, p, h, w, true);
-      add(P.gR[n], in_planes, h, w, true);
-      add(P.gS[n], 4 * in_planes, h, w, true);
+      add(P.z3[n], p, h, w);
+      add(P.z4[n], p, h, w);
+      for (size_t* g : {&P.gA[n], &P.gB[n], &P.gM[n], &P.dZ[n], &P.dZs[n], &P.dY[n]}) add(*g, p, h, w);
+      add(P.gR[n], in_planes, h, w);
+      add(P.gS[n], 4 * in_planes, h, w);
     }
     in_planes = p;
   }
@@ -285,9 +276,9 @@ int check_train_call(const PolicyNet& N, const char* who, int B, int H, int W) {
 }
 
 // The launch sequence of the train-mode forward over plan P in workspace A: shared by policy_forward_train (plan without `keep`: the
-// three stride-1 z of a stage share a buffer) and by the re-computation of policy_param_grad (everything kept; s2_hs always).
+// three stride-1 z of a stage share a buffer) and by the re-computation of policy_param_grad (everything kept).
 // probs == null: no head launch.
-int train_forward_launches(pnpx_ctx* ctx, const TrainPlan& P, float* A, bool s2_hs, const float* ob, float* probs, float* det, int B, int H,
+int train_forward_launches(pnpx_ctx* ctx, const TrainPlan& P, float* A, const float* ob, float* probs, float* det, int B, int H,
                            int W, float momentum, int update_running, hipStream_t s) {
   PolicyNet& N = ctx->policy;
   auto hsc = [&](size_t off) { return reinterpret_cast<char*>(A + off); };
@@ -316,44 +307,33 @@ int train_forward_launches(pnpx_ctx* ctx, const TrainPlan& P, float* A, bool s2_
     f.range_flag = range_flag;
     return launch_conv_hs(hs_layer(D, N.raw.hs_bias[li]), hsc(in), D.cin_pad / 8, nullptr, 0, hsc(out), B, h, w, f, s);
   };
-  auto conv_f32 = [&](PolicyConv C, size_t in, size_t out, int h, int w) -> int {
-    C.split_c = 0;   // every cout tile takes the linear epilogue and lands in ONE HS8 tensor of C.cout channels
-    return launch_policy_conv(C, A + in, nullptr, A + out, nullptr, false, B, h, w, s, true);
-  };
-  // statistics of the C-channel tensor at `z` (h x w), finished for layers l0 [and l1: the second half of the channels]
-  auto stats = [&](size_t z, int C, int h, int w, int l0, int l1) -> int {
+  // statistics of layer l's raw output at `z` (h x w)
+  auto stats = [&](size_t z, int h, int w, int l) -> int {
+    const BnLayer& L = BL[l];
     const long long npix = (long long)B * h * w;
     const int np = (int)bn_pieces(npix);
-    hipLaunchKernelGGL(bn_partial_kernel, dim3(np, C / 8), dim3(256), 0, s, rec(z), C / 8, h, w, npix, part);
+    hipLaunchKernelGGL(bn_partial_kernel, dim3(np, L.cout / 8), dim3(256), 0, s, rec(z), L.cout / 8, h, w, npix, part);
     PNPX_LAUNCH_CHECK();
-    const int ls[2] = {l0, l1};
-    int c_off = 0;
-    for (int k = 0; k < 2 && ls[k] >= 0; ++k) {
-      const BnLayer& L = BL[ls[k]];
-      BnFinishArgs a;
-      a.part = part;
-      a.C = C;
-      a.c_off = c_off;
-      a.cout = L.cout;
-      a.npieces = np;
-      a.n = npix;
-      a.params = params;
-      a.bn = L.bn;
-      a.mean = st_mean + L.chan0;
-      a.var = st_var + L.chan0;
-      a.scale = st_scale + L.chan0;
-      a.shift = st_shift + L.chan0;
-      a.momentum = momentum;
-      a.update = update_running ? 1 : 0;
-      hipLaunchKernelGGL(bn_finish_kernel, dim3((L.cout + 63) / 64), dim3(64), 0, s, a);
-      PNPX_LAUNCH_CHECK();
-      c_off += L.cout;
-    }
+    BnFinishArgs a;
+    a.part = part;
+    a.cout = L.cout;
+    a.npieces = np;
+    a.n = npix;
+    a.params = params;
+    a.bn = L.bn;
+    a.mean = st_mean + L.chan0;
+    a.var = st_var + L.chan0;
+    a.scale = st_scale + L.chan0;
+    a.shift = st_shift + L.chan0;
+    a.momentum = momentum;
+    a.update = update_running ? 1 : 0;
+    hipLaunchKernelGGL(bn_finish_kernel, dim3((L.cout + 63) / 64), dim3(64), 0, s, a);
+    PNPX_LAUNCH_CHECK();
     return PNPX_OK;
   };
-  auto src = [&](size_t z, int Gt, int g0, int l) {
+  auto src = [&](size_t z, int l) {
     const BnLayer& L = BL[l];
-    return BnSrc{rec(z), Gt, g0, st_mean + L.chan0, st_scale + L.chan0, params + L.bn + L.cout};
+    return BnSrc{rec(z), st_mean + L.chan0, st_scale + L.chan0, params + L.bn + L.cout};
   };
   // `sd`: the space-to-depth copy for a following stride-2 entry (offset; NONE = none); out / res: NONE = none
   auto apply = [&](BnSrc a0, BnSrc b0, size_t res, size_t out, size_t sd, int G, int h, int w) -> int {
@@ -362,8 +342,7 @@ int train_forward_launches(pnpx_ctx* ctx, const TrainPlan& P, float* A, bool s2_
     a.b = b0;
     a.res = res == NONE ? nullptr : rec(res);
     a.out = out == NONE ? nullptr : rec(out);
-    a.s2d_hs = (sd != NONE && s2_hs) ? rec(sd) : nullptr;
-    a.s2d_f32 = (sd != NONE && !s2_hs) ? A + sd : nullptr;
+    a.s2d_hs = sd == NONE ? nullptr : rec(sd);
     a.G = G;
     a.h = h;
     a.w = w;
@@ -372,49 +351,35 @@ int train_forward_launches(pnpx_ctx* ctx, const TrainPlan& P, float* A, bool s2_
     PNPX_LAUNCH_CHECK();
     return PNPX_OK;
   };
-  const BnSrc no_src{nullptr, 0, 0, nullptr, nullptr, nullptr};
+  const BnSrc no_src{nullptr, nullptr, nullptr, nullptr};
 
   // stem: conv3x3 stride 2 over the space-to-depth observation -> bn1 -> ReLU -> space-to-depth for the stage-0 entry
-  if (s2_hs) {
-    PNPX_TRY(launch_pack_ob_hs(ob, hsc(P.ob), N.num_inputs, N.cin_pad, B, H, W, s));
-    PNPX_TRY(conv_hs(0, P.ob, 4 * N.cin_pad / 8, P.zstem, H / 2, W / 2));
-  } else {
-    PNPX_TRY(policy_launch_pack_ob_f32(ob, A + P.ob, N.num_inputs, N.cin_pad, B, H, W, s));
-    PNPX_TRY(conv_f32(N.raw.f32[0], P.ob, P.zstem, H / 2, W / 2));
-  }
-  PNPX_TRY(stats(P.zstem, 64, H / 2, W / 2, 0, -1));
-  PNPX_TRY(apply(src(P.zstem, 8, 0, 0), no_src, NONE, P.stem_a, P.stem_s, 8, H / 2, W / 2));
+  PNPX_TRY(launch_pack_ob_hs(ob, hsc(P.ob), N.num_inputs, N.cin_pad, B, H, W, s));
+  PNPX_TRY(conv_hs(0, P.ob, 4 * N.cin_pad / 8, P.zstem, H / 2, W / 2));
+  PNPX_TRY(stats(P.zstem, H / 2, W / 2, 0));
+  PNPX_TRY(apply(src(P.zstem, 0), no_src, NONE, P.stem_a, P.stem_s, 8, H / 2, W / 2));
   for (int st = 0; st < 4; ++st) {
     const int h = H >> (st + 2), w = W >> (st + 2), p = stage_planes(st), G = p / 8, c0 = 1 + 5 * st;
     const size_t s2in = st == 0 ? P.stem_s : P.o1s[st - 1];
     const int in_planes = st == 0 ? 64 : stage_planes(st - 1);
-    BnSrc z1, zs;
-    if (s2_hs) {   // conv1 and the 1x1 shortcut on the sparse-tap half-split instances: two tensors of p channels
-      const size_t zs_off = P.za[st] + (size_t)B * p * (h + 2) * (w + 2);
-      PNPX_TRY(conv_hs(c0 + 0, s2in, 4 * in_planes / 8, P.za[st], h, w));
-      PNPX_TRY(conv_hs(c0 + 2, s2in, 4 * in_planes / 8, zs_off, h, w));
-      PNPX_TRY(stats(P.za[st], p, h, w, c0 + 0, -1));
-      PNPX_TRY(stats(zs_off, p, h, w, c0 + 2, -1));
-      z1 = src(P.za[st], G, 0, c0 + 0);
-      zs = src(zs_off, G, 0, c0 + 2);
-    } else {       // one fp32 tap-sparse launch: conv1 in channels [0, p), the shortcut in [p, 2p) of one tensor
-      PNPX_TRY(conv_f32(N.raw.f32[1 + st], s2in, P.za[st], h, w));
-      PNPX_TRY(stats(P.za[st], 2 * p, h, w, c0 + 0, c0 + 2));
-      z1 = src(P.za[st], 2 * G, 0, c0 + 0);
-      zs = src(P.za[st], 2 * G, G, c0 + 2);
-    }
-    PNPX_TRY(apply(z1, no_src, NONE, P.t1[st], NONE, G, h, w));
+    // conv1 and the 1x1 shortcut on the sparse-tap half-split instances: two tensors of p channels, back to back in za
+    const size_t zs_off = P.za[st] + (size_t)B * p * (h + 2) * (w + 2);
+    PNPX_TRY(conv_hs(c0 + 0, s2in, 4 * in_planes / 8, P.za[st], h, w));
+    PNPX_TRY(conv_hs(c0 + 2, s2in, 4 * in_planes / 8, zs_off, h, w));
+    PNPX_TRY(stats(P.za[st], h, w, c0 + 0));
+    PNPX_TRY(stats(zs_off, h, w, c0 + 2));
+    PNPX_TRY(apply(src(P.za[st], c0 + 0), no_src, NONE, P.t1[st], NONE, G, h, w));
     // block 0: relu(bn2(conv2) + shortcut_bn(shortcut_conv))
     PNPX_TRY(conv_hs(c0 + 1, P.t1[st], 0, P.z2[st], h, w));
-    PNPX_TRY(stats(P.z2[st], p, h, w, c0 + 1, -1));
-    PNPX_TRY(apply(src(P.z2[st], G, 0, c0 + 1), zs, NONE, P.o0[st], NONE, G, h, w));
+    PNPX_TRY(stats(P.z2[st], h, w, c0 + 1));
+    PNPX_TRY(apply(src(P.z2[st], c0 + 1), src(zs_off, c0 + 2), NONE, P.o0[st], NONE, G, h, w));
     // block 1: relu(bn2(conv2(relu(bn1(conv1(x))))) + x)
     PNPX_TRY(conv_hs(c0 + 3, P.o0[st], 0, P.z3[st], h, w));
-    PNPX_TRY(stats(P.z3[st], p, h, w, c0 + 3, -1));
-    PNPX_TRY(apply(src(P.z3[st], G, 0, c0 + 3), no_src, NONE, P.t2[st], NONE, G, h, w));
+    PNPX_TRY(stats(P.z3[st], h, w, c0 + 3));
+    PNPX_TRY(apply(src(P.z3[st], c0 + 3), no_src, NONE, P.t2[st], NONE, G, h, w));
     PNPX_TRY(conv_hs(c0 + 4, P.t2[st], 0, P.z4[st], h, w));
-    PNPX_TRY(stats(P.z4[st], p, h, w, c0 + 4, -1));
-    PNPX_TRY(apply(src(P.z4[st], G, 0, c0 + 4), no_src, P.o0[st], P.o1[st], st < 3 ? P.o1s[st] : NONE, G, h, w));
+    PNPX_TRY(stats(P.z4[st], h, w, c0 + 4));
+    PNPX_TRY(apply(src(P.z4[st], c0 + 4), no_src, P.o0[st], P.o1[st], st < 3 ? P.o1s[st] : NONE, G, h, w));
   }
   if (probs) PNPX_TRY(policy_launch_heads(N.raw, N.n_det, N.spi_head, hsc(P.o1[3]), H / 32, W / 32, B, probs, det, s));
   N.bn_have_stats = true;
@@ -433,12 +398,11 @@ int policy_forward_train(pnpx_ctx* ctx, const float* ob, float* probs, float* de
     return PNPX_ERR_ARG;
   }
   if (!N.raw_valid) PNPX_TRY(policy_pack_raw(ctx, s));
-  const bool s2_hs = ctx->opt_policy_s2_hs != 0;
   if (!N.bn_buf.p) PNPX_TRY(alloc_dev(N.bn_buf, 4 * POLICY_BN_CHANNELS * sizeof(float), "policy batch-statistics"));
   PNPX_TRY(reserve_arena_hs(N.train_ws, N.tcapB, N.tcapH, N.tcapW, B, H, W,
-                            [&](int nb) { return make_train_plan(nb, N.cin_pad, H, W, s2_hs).total; }, "policy train workspace"));
-  const TrainPlan P = make_train_plan(N.tcapB, N.cin_pad, H, W, s2_hs);
-  return train_forward_launches(ctx, P, static_cast<float*>(N.train_ws.p), s2_hs, ob, probs, det, B, H, W, momentum, update_running, s);
+                            [&](int nb) { return make_train_plan(nb, N.cin_pad, H, W).total; }, "policy train workspace"));
+  const TrainPlan P = make_train_plan(N.tcapB, N.cin_pad, H, W);
+  return train_forward_launches(ctx, P, static_cast<float*>(N.train_ws.p), ob, probs, det, B, H, W, momentum, update_running, s);
 }
 
 namespace {
@@ -455,8 +419,8 @@ int grow(DeviceBuf& b, size_t bytes, const char* what) {
 }  // namespace
 
 // d sum(grad_probs * probs + grad_det * det) / d params through the train-mode forward (policy_loss.backward(), trainer.py:171-212).
-// The forward is re-computed with update_running = 0 into a workspace of its own that keeps every z and every activation; ALWAYS on the
-// half-split stage entries (HS8 space-to-depth tensors) whatever policy_s2_hs says: the weight-gradient GEMM reads HS8 operands.  Then,
+// The forward is re-computed with update_running = 0 into a workspace of its own that keeps every z and every activation; the
+// weight-gradient GEMM reads its HS8 operands (space-to-depth tensors included) from there.  Then,
 // backwards (DESIGN.md section 9c has the table of launches): heads and the gradient range (policy_grad.hip), and per layer BatchNorm
 // backward -> weight gradient (critic_grad.hip's GEMM, G = dz, X = what the forward launch read) -> adjoint convolution.  The adjoint
 // convolutions are linear (the ReLU mask is taken by the BatchNorm backward of the layer below): the critic's input-gradient instance
@@ -477,13 +441,13 @@ int policy_param_grad(pnpx_ctx* ctx, const float* ob, const float* grad_probs, c
   if (!N.raw_valid) PNPX_TRY(policy_pack_raw(ctx, s));
   if (!N.adj_valid) PNPX_TRY(policy_pack_adj(ctx, s));
   PackDesc PD[NBN];
-  PNPX_TRY(policy_conv_descs(N, PD));
+  PNPX_TRY(policy_pack_descs(N, PD));
   BnLayer BL[NBN];
   bn_layers(N.num_inputs, BL);
   if (!N.bn_buf.p) PNPX_TRY(alloc_dev(N.bn_buf, 4 * POLICY_BN_CHANNELS * sizeof(float), "policy batch-statistics"));
   PNPX_TRY(reserve_arena_hs(N.grad_ws, N.gcapB, N.gcapH, N.gcapW, B, H, W,
-                            [&](int nb) { return make_train_plan(nb, N.cin_pad, H, W, true, true).total; }, "policy gradient workspace"));
-  const TrainPlan P = make_train_plan(N.gcapB, N.cin_pad, H, W, true, true);
+                            [&](int nb) { return make_train_plan(nb, N.cin_pad, H, W, true).total; }, "policy gradient workspace"));
+  const TrainPlan P = make_train_plan(N.gcapB, N.cin_pad, H, W, true);
   float* A = static_cast<float*>(N.grad_ws.p);
   auto rec = [&](size_t off) { return reinterpret_cast<HsRec*>(A + off); };
   auto hsc = [&](size_t off) { return reinterpret_cast<char*>(A + off); };
@@ -517,7 +481,7 @@ int policy_param_grad(pnpx_ctx* ctx, const float* ob, const float* grad_probs, c
   double* part = reinterpret_cast<double*>(gf + small_floats);
 
   // 1. forward re-computation (the batch statistics land in bn_buf)
-  PNPX_TRY(train_forward_launches(ctx, P, A, true, ob, nullptr, nullptr, B, H, W, 0.f, 0, s));
+  PNPX_TRY(train_forward_launches(ctx, P, A, ob, nullptr, nullptr, B, H, W, 0.f, 0, s));
   const float* st_mean = static_cast<const float*>(N.bn_buf.p);
   const float* st_var = st_mean + POLICY_BN_CHANNELS;
   unsigned* range_flag = ctx->opt_range_guard ? ctx->range_flag_dev : nullptr;

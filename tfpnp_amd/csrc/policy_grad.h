@@ -8,7 +8,7 @@
 namespace pnpx {
 
 // the forward (fold-free) packing descriptors of the 21 convolutions, in the trunk's layer numbering (policy_pack.hip)
-int policy_conv_descs(const PolicyNet& N, PackDesc* out21);
+int policy_pack_descs(const PolicyNet& N, PackDesc* out21);
 
 // ------------------------------------------------------------------------------------------- heads
 // Per-image scratch of the head backward, POL_HEAD_STRIDE floats: the pooled feature f[512]; gl[2] (softmax logits' gradient);

@@ -1,5 +1,5 @@
 // Policy actor: live weights.  The context keeps the flat fp32 parameter vector on the device (PolicyNet::live, after
-// either load entry); pnpx_policy_load_device derives every packed layout the forward reads from it with five launches on
+// either load entry); pnpx_policy_load_device derives the packed layout the forward reads from it with four launches on
 // the caller's stream and refreshes an already loaded actor in place -- no allocation, no device-wide synchronisation, the
 // activation arena is kept.  The per-convolution weight scales are launch arguments of the half-split instances, so a
 // refresh ends with one small read-back and a synchronisation of that stream (not capturable).
@@ -12,23 +12,16 @@
 //   pol_scale_kernel     per convolution: the power-of-two half-split scale 2^(14 - exponent(max |w|)) into the read-back block
 //   pol_pack_hs_kernel   the 12 stride-1 convolutions (9 taps), the stem and the 4 stage-entry conv1 as 2x2-window sparse-tap
 //                        launches over the space-to-depth input (0x01B), the 4 shortcuts (0x010): hi / lo f16 fragments
-//   pol_pack_f32_kernel  the stem and the 4 stage entries (conv1 + shortcut rows merged) as fp32 [8 channels][64 couts] tap
-//                        slices in PolStep order (option policy_s2_hs = 0)
 //   live_copy_kernel     the shifts as biases, the head matrices (live_params.hip, shared with the critic)
 //
-// The host decides which fp32 tap slices exist by looking at the values; here presence is STRUCTURAL: over the space-to-depth
-// input a 3x3 stride-2 convolution touches tap 4 of phase (0,0), taps 3, 4 of phase (0,1), taps 1, 4 of phase (1,0) and taps
-// 0, 1, 3, 4 of phase (1,1), in every 8-channel chunk that holds a real input channel; the shortcut touches tap 4 of the
-// phase-(0,0) chunks.  The step lists are therefore layout constants, written once when the blob is allocated.  A present
-// slice that happens to be all zero contributes exactly nothing, so both layouts compute the same outputs; for weights
-// without an all-zero slice they are the same bytes at the same offsets.
+// ONE blob layout (make_layout): per convolution its half-split packing and its bias, then the head matrices, every entry
+// 256-float aligned.  It depends on the network's shape alone, so the blob policy_load packs on the host and the one a
+// device load allocates are the same bytes at the same offsets, and either is refreshed in place.
 #include <cmath>
-#include <cstring>
 
 #include "common.h"
 #include "conv_hs.h"
 #include "pack_desc.h"
-#include "policy_conv.h"
 #include "policy_grad.h"
 #include "resnet18_hs.h"
 
@@ -37,50 +30,28 @@ namespace {
 
 constexpr float BN_EPS = 1e-5f;
 constexpr int NCV = TRUNK_LAYERS;   // BatchNorm-ed convolutions in parameter order = the trunk's layer numbering (resnet18_hs.h)
-constexpr int NF32 = 5;      // fp32 PolStep launches: the stem and the four stage entries
-constexpr int MAXCOPY = 36, NRB = 32;
+constexpr int MAXCOPY = 27, NRB = 32;   // 21 biases + up to 6 head tensors; floats of the read-back block
 
 struct PolFoldDesc {
   unsigned src_w, src_bn;    // floats into the parameter vector: weights; BatchNorm weight, bias, running_mean, running_var
   unsigned chan0;            // first output channel in the per-channel arrays
   int cout, fan;
 };
-struct PolF32Desc {          // one fp32 launch: nct1 cout tiles of a 3x3 stride-2 convolution, then nct2 of the 1x1 shortcut
-  unsigned dst, items;       // items: 16-byte fragments = slices * 128
-  int conv1, conv2;          // convolutions (conv2 = -1: none)
-  int nct1, nct2;
-  int nc, cin;               // 8-channel chunks per phase (Cp / 8); real input channels
-};
 struct PolPackTable {
   PolFoldDesc fold[NCV];
   PackDesc pack[NCV];
-  PolF32Desc f32[NF32];
   CopyDesc copy[MAXCOPY];
   unsigned nchan;
   int ncopy;
 };
 struct PolicyLayout {        // the table + the blob offsets (floats) the host needs
   PolPackTable T;
-  size_t f32_w[NF32], f32_bias[NF32], f32_steps[NF32], f32_nsteps[NF32];
-  int f32_cout[NF32], f32_K[NF32], f32_split[NF32];
   size_t hs_bias[NCV];
   size_t smw, smb, dw, db, d2w, d2b, total;
   PackDims dims;             // the launch dimensions of T (stored with the workspace the table is uploaded to)
-  std::vector<PolStep> steps[NF32];
-  std::vector<int> nsteps[NF32];
 };
 
-// taps of phase ph of a 3x3 stride-2 convolution on the space-to-depth grid (resnet18_hs.hip::put_conv_s2), ascending
-__host__ __device__ inline int phase_taps(int ph, int* taps) {
-  const int ty0 = (ph >> 1) ? 0 : 1, tx0 = (ph & 1) ? 0 : 1;
-  int n = 0;
-  for (int ty = ty0; ty < 2; ++ty)
-    for (int tx = tx0; tx < 2; ++tx) taps[n++] = ty * 3 + tx;
-  return n;
-}
-
-// Offsets of HostBlob as policy_load fills it when every structurally present slice holds a non-zero value (256-float
-// alignment before every entry), sources in pnpx_policy_load's order.
+// Offsets of HostBlob as policy_load fills it (256-float alignment before every entry), sources in pnpx_policy_load's order.
 bool make_layout(int num_inputs, int n_det, int spi_head, PolicyLayout& L) {
   L = PolicyLayout();
   const int cin_pad = (num_inputs + 7) / 8 * 8;
@@ -124,47 +95,7 @@ bool make_layout(int num_inputs, int n_det, int spi_head, PolicyLayout& L) {
     L.hs_bias[ci] = cur.put(F.cout);
     copy(F.chan0, L.hs_bias[ci], F.cout, 1);
   };
-  // fp32 PolStep launch fi: convolution c1 (3x3 stride 2) [+ shortcut c2]
-  auto put_f32 = [&](int fi, int c1, int c2, int cin, int Cp) {
-    PolF32Desc& D = L.T.f32[fi];
-    const int p = L.T.fold[c1].cout, nc = Cp / 8, nch = 4 * nc;
-    D.conv1 = c1;
-    D.conv2 = c2;
-    D.nct1 = p / 64;
-    D.nct2 = c2 >= 0 ? p / 64 : 0;
-    D.nc = nc;
-    D.cin = cin;
-    const int nct = D.nct1 + D.nct2;
-    std::vector<PolStep>& steps = L.steps[fi];
-    std::vector<int>& nsteps = L.nsteps[fi];
-    steps.assign((size_t)nct * nch, PolStep{0, 0, 0});
-    nsteps.assign(nct, 0);
-    unsigned nsl = 0;
-    for (int ct = 0; ct < nct; ++ct)
-      for (int ch = 0; ch < (ct < D.nct1 ? nch : nc); ++ch) {
-        int taps[4] = {4, 0, 0, 0};
-        const int n = ct < D.nct1 ? phase_taps(ch / nc, taps) : 1;
-        unsigned short mask = 0;
-        for (int t = 0; t < n; ++t) mask |= (unsigned short)(1u << taps[t]);
-        steps[(size_t)ct * nch + nsteps[ct]++] = PolStep{mask, (unsigned short)ch, nsl};
-        nsl += n;
-      }
-    ok = ok && nsl == (unsigned)(D.nct1 * nc * 9 + D.nct2 * nc);
-    D.items = nsl * 128;
-    if (D.items > L.dims.max_f32_items) L.dims.max_f32_items = D.items;
-    L.f32_w[fi] = cur.put((size_t)nsl * 512 + 1024);   // + the guard behind the last slice
-    D.dst = (unsigned)L.f32_w[fi];
-    L.f32_cout[fi] = nct * 64;
-    L.f32_K[fi] = 4 * Cp;
-    L.f32_split[fi] = p;
-    L.f32_bias[fi] = cur.put((size_t)nct * 64);
-    copy(L.T.fold[c1].chan0, L.f32_bias[fi], p, 1);
-    if (c2 >= 0) copy(L.T.fold[c2].chan0, L.f32_bias[fi] + p, p, 1);
-    L.f32_steps[fi] = cur.put(steps.size() * 2);
-    L.f32_nsteps[fi] = cur.put(nsteps.size());
-  };
   take_conv(0, 64, num_inputs, 9);
-  put_f32(0, 0, -1, num_inputs, cin_pad);
   put_hs(0, 1, num_inputs, cin_pad, 4 * cin_pad, 0x01B);
   int in_planes = 64;
   for (int s = 0; s < 4; ++s) {
@@ -174,7 +105,6 @@ bool make_layout(int num_inputs, int n_det, int spi_head, PolicyLayout& L) {
     take_conv(c0 + 2, p, in_planes, 1);
     take_conv(c0 + 3, p, p, 9);
     take_conv(c0 + 4, p, p, 9);
-    put_f32(1 + s, c0 + 0, c0 + 2, in_planes, in_planes);
     put_hs(c0 + 0, 1, in_planes, in_planes, 4 * in_planes, 0x01B);
     put_hs(c0 + 2, 2, in_planes, 0, in_planes, 0x010);
     put_hs(c0 + 1, 0, p, 0, p, 0x1FF);
@@ -324,55 +254,6 @@ __global__ __launch_bounds__(256) void pol_pack_hs_kernel(const PolPackTable* __
   });
 }
 
-// One thread per 16-byte fragment of an fp32 tap slice [8 channels][64 couts]: four consecutive output channels of one input
-// channel.  Slices in PolStep order: per conv1 tile the chunks phase by phase (nc chunks of 1, 2, 2, 4 taps), then per
-// shortcut tile the nc phase-(0,0) chunks.
-__global__ __launch_bounds__(256) void pol_pack_f32_kernel(const PolPackTable* __restrict__ T, const float* __restrict__ P,
-                                                           const float* __restrict__ sc, float* __restrict__ blob) {
-  const PolF32Desc& D = T->f32[blockIdx.y];
-  const unsigned i = blockIdx.x * 256 + threadIdx.x;
-  if (i >= D.items) return;
-  const int sl = (int)(i >> 7), c = (int)(i >> 4) & 7, m4 = (int)(i & 15) * 4;
-  const int nc = D.nc, per_tile = 9 * nc, n1 = D.nct1 * per_tile;
-  float4 out = make_float4(0.f, 0.f, 0.f, 0.f);
-  if (sl < n1) {
-    const int ct = sl / per_tile, j = sl - ct * per_tile;
-    // j -> (phase, chunk of the phase, tap of the phase): phases hold nc chunks of 1, 2, 2, 4 taps
-    int ph, q, ti;
-    if (j < nc) {
-      ph = 0, q = j, ti = 0;
-    } else if (j < 3 * nc) {
-      ph = 1, q = (j - nc) >> 1, ti = (j - nc) & 1;
-    } else if (j < 5 * nc) {
-      ph = 2, q = (j - 3 * nc) >> 1, ti = (j - 3 * nc) & 1;
-    } else {
-      ph = 3, q = (j - 5 * nc) >> 2, ti = (j - 5 * nc) & 3;
-    }
-    int taps[4];
-    (void)phase_taps(ph, taps);
-    const int tap = taps[ti], ty = tap / 3, tx = tap - 3 * ty, ci = q * 8 + c;
-    if (ci < D.cin) {
-      const int dy = (ph >> 1) ? (ty ? 2 : 0) : 1, dx = (ph & 1) ? (tx ? 2 : 0) : 1;
-      const PolFoldDesc& F = T->fold[D.conv1];
-      const int co = ct * 64 + m4;
-      const float* w = P + F.src_w + ((size_t)co * D.cin + ci) * 9 + dy * 3 + dx;
-      const size_t st = (size_t)D.cin * 9;
-      const float* s = sc + F.chan0 + co;
-      out = make_float4(w[0] * s[0], w[st] * s[1], w[2 * st] * s[2], w[3 * st] * s[3]);
-    }
-  } else {
-    const int r = sl - n1, ct = r / nc, ci = (r - ct * nc) * 8 + c;
-    if (ci < D.cin) {
-      const PolFoldDesc& F = T->fold[D.conv2];
-      const int co = ct * 64 + m4;
-      const float* w = P + F.src_w + (size_t)co * D.cin + ci;
-      const float* s = sc + F.chan0 + co;
-      out = make_float4(w[0] * s[0], w[D.cin] * s[1], w[2 * (size_t)D.cin] * s[2], w[3 * (size_t)D.cin] * s[3]);
-    }
-  }
-  *reinterpret_cast<float4*>(blob + D.dst + (size_t)sl * 512 + c * 64 + m4) = out;
-}
-
 // The adjoint packings of the fold-free table (parameter gradients, policy_bn.hip::policy_param_grad): layer li's input-gradient launch
 // reads the same raw weights with rows / K transposed and the taps mirrored (PackDesc::adj; windows 0x1FF / 0x1B0 / 0x010), in the same
 // power-of-two weight scale.  Layers 1..20: the stem's adjoint is never run.  A blob and a table of their own, so that eval-only and
@@ -422,17 +303,15 @@ __global__ __launch_bounds__(256) void pol_pack_adj_kernel(const PolAdjTable* __
   });
 }
 
-// a fresh blob in the structural layout: zero padding and guards, the step lists; the packing workspace with its table
+// the packing workspace with its table
+int alloc_pack_ws(PackWorkspace& W, const PolicyLayout& L) {
+  return W.alloc(&L.T, sizeof(PolPackTable), (size_t)3 * L.dims.nchan * sizeof(float), NRB, L.dims, "policy packing workspace");
+}
+// a fresh blob (zero padding and over-read slack) and its packing workspace
 int alloc_device_layout(PolicyPack& N, PackWorkspace& W, const PolicyLayout& L) {
   PNPX_TRY(alloc_dev(N.weights, L.total * sizeof(float), "policy weight"));
-  PNPX_TRY(W.alloc(&L.T, sizeof(PolPackTable), (size_t)3 * L.dims.nchan * sizeof(float), NRB, L.dims, "policy packing workspace"));
+  PNPX_TRY(alloc_pack_ws(W, L));
   PNPX_HIP(hipMemset(N.weights.p, 0, N.weights.bytes));
-  float* base = static_cast<float*>(N.weights.p);
-  static_assert(sizeof(PolStep) == 8, "PolStep layout");
-  for (int i = 0; i < NF32; ++i) {
-    PNPX_HIP(hipMemcpy(base + L.f32_steps[i], L.steps[i].data(), L.steps[i].size() * sizeof(PolStep), hipMemcpyHostToDevice));
-    PNPX_HIP(hipMemcpy(base + L.f32_nsteps[i], L.nsteps[i].data(), L.nsteps[i].size() * sizeof(int), hipMemcpyHostToDevice));
-  }
   PNPX_HIP(hipDeviceSynchronize());
   return PNPX_OK;
 }
@@ -440,16 +319,6 @@ int alloc_device_layout(PolicyPack& N, PackWorkspace& W, const PolicyLayout& L) 
 // launch descriptors over the blob (the scales follow from the read-back)
 void bind_blob(PolicyPack& N, const PolicyLayout& L, int spi_head) {
   float* base = static_cast<float*>(N.weights.p);
-  for (int fi = 0; fi < NF32; ++fi) {
-    PolicyConv& C = N.f32[fi];
-    C.w = base + L.f32_w[fi];
-    C.bias = base + L.f32_bias[fi];
-    C.steps = reinterpret_cast<const PolStep*>(base + L.f32_steps[fi]);
-    C.nsteps = reinterpret_cast<const int*>(base + L.f32_nsteps[fi]);
-    C.cin = L.f32_K[fi];
-    C.cout = L.f32_cout[fi];
-    C.split_c = L.f32_split[fi];
-  }
   for (int ci = 0; ci < NCV; ++ci) {
     const PackDesc& P = L.T.pack[ci];
     ConvLayerHsDev& D = N.hs[ci];
@@ -482,8 +351,6 @@ int repack(pnpx_ctx* ctx, hipStream_t s, bool raw = false) {
   hipLaunchKernelGGL(pol_scale_kernel, dim3(NCV), dim3(256), 0, s, w.T, w.chmax, w.rb);
   PNPX_LAUNCH_CHECK();
   hipLaunchKernelGGL(pol_pack_hs_kernel, dim3((d.max_items + 255) / 256, NCV), dim3(256), 0, s, w.T, P, w.sc, w.rb, blob);
-  PNPX_LAUNCH_CHECK();
-  hipLaunchKernelGGL(pol_pack_f32_kernel, dim3((d.max_f32_items + 255) / 256, NF32), dim3(256), 0, s, w.T, P, w.sc, blob);
   PNPX_LAUNCH_CHECK();
   PNPX_TRY(launch_live_copy(w.T->copy, dim3((d.max_copy + 255) / 256, d.ncopy), P, w.sh, blob, s));
   PNPX_HIP(hipMemcpyAsync(rb_host, w.rb, NCV * sizeof(float), hipMemcpyDeviceToHost, s));
@@ -518,22 +385,11 @@ int policy_load_device(pnpx_ctx* ctx, const float* params_dev, size_t n, int num
   }
   PolicyNet& N = ctx->policy;
   const bool same_net = N.loaded && N.num_inputs == num_inputs && N.n_det == n_det && N.spi_head == spi_head;
-  if (!(same_net && N.dev_layout)) {
-    // first load / another network / a blob in the host's value-dependent layout: allocate (a refresh allocates nothing).
-    // The arena of the same network is kept: its layout depends on the padded input channels and the image size only.
+  if (!same_net) {   // first load / another network: allocate (a refresh allocates nothing)
     PolicyLayout L;
     PNPX_TRY(layout_of("pnpx_policy_load_device", num_inputs, n_det, spi_head, L));
     PNPX_HIP(hipDeviceSynchronize());
-    const DeviceBuf arena = N.arena;
-    const int capB = N.capB, capH = N.capH, capW = N.capW;
-    if (same_net) N.arena = DeviceBuf();
     policy_free(ctx);
-    if (same_net) {
-      N.arena = arena;
-      N.capB = capB;
-      N.capH = capH;
-      N.capW = capW;
-    }
     N.num_inputs = num_inputs;
     N.cin_pad = (num_inputs + 7) / 8 * 8;
     N.n_det = n_det;
@@ -545,7 +401,6 @@ int policy_load_device(pnpx_ctx* ctx, const float* params_dev, size_t n, int num
       return st;
     }
     bind_blob(N, L, N.spi_head);
-    N.dev_layout = true;
   }
   N.raw_valid = false;   // new weights: the train-mode packing follows on the next train forward
   N.adj_valid = false;   // ... and its adjoints on the next gradient call
@@ -599,30 +454,36 @@ int policy_pack_adj(pnpx_ctx* ctx, hipStream_t s) {
   return PNPX_OK;
 }
 
-int policy_conv_descs(const PolicyNet& N, PackDesc* out21) {
+int policy_pack_descs(const PolicyNet& N, PackDesc* out21) {
   PolicyLayout L;
   PNPX_TRY(layout_of("policy parameter gradient", N.num_inputs, N.n_det, N.spi_head, L));
   for (int li = 0; li < NCV; ++li) out21[li] = L.T.pack[li];
   return PNPX_OK;
 }
 
-int policy_refresh_eval(pnpx_ctx* ctx, hipStream_t s) {
+int policy_refresh_eval(pnpx_ctx* ctx, hipStream_t s) { return repack(ctx, s); }
+
+// policy_load's last step.  Every later refresh writes into the blob the host packed (the 21 packings pk, the head matrices at heads[]
+// in bind_blob's order, `total` floats), so the layout table has to describe exactly those offsets.
+int policy_adopt_host_blob(pnpx_ctx* ctx, const Packed* pk, const size_t* heads, size_t total) {
   PolicyNet& N = ctx->policy;
-  if (!N.dev_layout) {   // a blob in policy_load's value-dependent layout: replace it by the structural one (the parameter vector stays)
-    PolicyLayout L;
-    PNPX_TRY(layout_of("policy refresh", N.num_inputs, N.n_det, N.spi_head, L));
-    PNPX_HIP(hipDeviceSynchronize());
-    if (N.weights.p) PNPX_HIP(hipFree(N.weights.p));
-    N.weights = DeviceBuf();
-    const int st = alloc_device_layout(N, N.pack_ws, L);
-    if (st != PNPX_OK) {   // nothing left to run on: the context holds no actor any more
-      policy_free(ctx);
-      return st;
-    }
-    bind_blob(N, L, N.spi_head);
-    N.dev_layout = true;
+  PolicyLayout L;
+  PNPX_TRY(layout_of("pnpx_policy_load", N.num_inputs, N.n_det, N.spi_head, L));
+  const size_t want[6] = {L.smw, L.smb, L.dw, L.db, L.d2w, L.d2b};
+  bool same = L.total == total;
+  for (int i = 0; same && i < (N.spi_head ? 6 : 4); ++i) same = heads[i] == want[i];
+  for (int ci = 0; same && ci < NCV; ++ci) {
+    const PackDesc& P = L.T.pack[ci];
+    same = P.dst == pk[ci].w && L.hs_bias[ci] == pk[ci].b && P.mt == pk[ci].mt && P.K == pk[ci].cin && P.rows == pk[ci].cout;
   }
-  return repack(ctx, s);
+  if (!same) {
+    set_error("pnpx_policy_load: the device packing table disagrees with the host layout (%d inputs, %d outputs, spi %d)", N.num_inputs,
+              N.n_det, N.spi_head);
+    return PNPX_ERR_SHAPE;
+  }
+  bind_blob(N, L, N.spi_head);
+  for (int ci = 0; ci < NCV; ++ci) N.hs[ci].inv_scale = 1.0f / (pk[ci].scale * HS_ASCALE);
+  return alloc_pack_ws(N.pack_ws, L);
 }
 
 int policy_params(pnpx_ctx* ctx, float* dst_dev, size_t n, hipStream_t s) {
