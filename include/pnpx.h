@@ -61,6 +61,12 @@ int pnpx_ctx_reserve(pnpx_ctx* ctx, int B, int H, int W);
  *  "fp32_wino8_layers" (default: all 27 bits set): bit i = layer i of the UNet (state_dict order) runs on the 8-wave Winograd kernel
  *      (csrc/conv3x3_wino8.hip: the 16 positions of a block split over the two waves of a SIMD; forward and adjoint convolutions) where
  *      its geometry allows; 0 = the round-4 4-wave kernel (csrc/conv3x3_wino.hip) everywhere.  A DRUNet context: any bit.
+ *  "fp32_winof4_layers" (27-bit layer mask like fp32_wino8_layers): bit i = layer i runs as Winograd F(4x4,3x3) on v_mfma_f32_16x16x4_f32
+ *      (csrc/conv3x3_winof4.hip: 0.5625 x the MFMAs of F(2x2)) in forward passes (inference and training alike), when its fp32_wino8_layers bit is set too,
+ *      "fp32_winograd" is 1, the K-split does not claim the layer in this call and its geometry allows: a plain single-source layer with
+ *      cout % 64 == 0, >= 16 input channels in multiples of 8, H % 16 == 0, W % 32 == 0 (UNet levels 1-3).  The backward pass,
+ *      the DRUNet, the decoder entries, the 16 x 16 level and the 32-cout layers always keep the F(2x2) kernel.  0 = F(2x2)
+ *      everywhere (bit-identical to the library before the option existed).
  *  "fp32_chains" (default 2): in conv_mode 0 the denoiser forward runs as n independent launch chains over contiguous slices of the batch
  *      (caller's stream + side streams, joined before the entry returns; bit-identical per image): 2 measured best (-3.6 % at 48 x 256^2,
  *      -7 % at B = 24); 1 = only the bottom level's three launches fork two chains; 0 = one chain.  The VJP's adjoint chain forks exactly
@@ -594,6 +600,13 @@ int pnpx_ct_pg_backward(pnpx_ctx* ctx, int n_view, float opnorm, const float* si
                         int param_stride, const float* saved, const float* grad_vars_out, float* grad_vars_in,
                         float* grad_sigma_d, float* grad_tau, float* work, int B, int R, int T,
                         unsigned long long ticket, void* stream);
+
+/* Host-only helpers of the Winograd F(4x4,3x3) kernel (csrc/conv3x3_winof4.hip), for tests: the 1-D matrices the weight packer and the
+ * kernel use (G 6x3, B^T 6x6, A^T 4x6, row-major doubles), and the packer itself (w [cout][cin][3][3], cout % 64 == 0, cin % 8 == 0 ->
+ * dst 36 * cout * cin floats: [cout/64][cin/8][stage 3][row 2][column pair 3][cout block 4][channel group 4][cout 16][k-step 2][column 2],
+ * position (2 stage + row, 2 pair + column), channel 8 chunk + 2 group + k-step). */
+void pnpx_winof4_matrices(double* g18, double* bt36, double* at24);
+int pnpx_winof4_pack(const float* w, int cout, int cin, float* dst);
 
 #ifdef __cplusplus
 }

@@ -140,6 +140,8 @@ _SIGNATURES = {
                             [C.c_int] * 3 + [C.c_ulonglong, c_void_p]),
     "pnpx_ct_iadmm": (C.c_int, [c_void_p, _P, _P, _P, C.c_int, C.c_float, _P, _P, _P] + [C.c_int] * 4 + [c_void_p]),
     "pnpx_ct_pg": (C.c_int, [c_void_p, _P, _P, _P, C.c_int, C.c_float, _P, _P] + [C.c_int] * 4 + [c_void_p]),
+    "pnpx_winof4_matrices": (None, [c_void_p, c_void_p, c_void_p]),
+    "pnpx_winof4_pack": (C.c_int, [c_void_p, C.c_int, C.c_int, c_void_p]),
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 

@@ -394,6 +394,10 @@ int pnpx_ctx_set_option(pnpx_ctx* ctx, const char* key, int value) {
     ctx->opt_fp32_wino8 = value;
     return PNPX_OK;
   }
+  if (is("fp32_winof4_layers") && value >= 0 && value < (1 << 27)) {    // bit li: layer li on the F(4x4,3x3) kernel (forward passes)
+    ctx->opt_fp32_winof4 = value;
+    return PNPX_OK;
+  }
   if (is("fft_fast") && (value == 0 || value == 1)) {
     ctx->opt_fft_fast = value;
     return PNPX_OK;
@@ -460,6 +464,7 @@ int pnpx_ctx_get_option(pnpx_ctx* ctx, const char* key, int* value) {
   else if (is("fft_fast")) *value = ctx->opt_fft_fast;
   else if (is("fp32_winograd")) *value = ctx->opt_fp32_winograd;
   else if (is("fp32_wino8_layers")) *value = ctx->opt_fp32_wino8;
+  else if (is("fp32_winof4_layers")) *value = ctx->opt_fp32_winof4;
   else if (is("fp32_fuse_up")) *value = ctx->opt_fp32_fuse_up;
   else if (is("fp32_ksplit")) *value = ctx->opt_fp32_ksplit;
   else if (is("fp32_ksplit_rule")) *value = ctx->opt_ksplit_rule;
@@ -601,6 +606,23 @@ int pnpx_unet_load(pnpx_ctx* ctx, const float* params_host, size_t n_params) {
     ctx->conv_bwd[i].cc = 8;
   }
   // ... and the same adjoint convolutions for the half-split kernel family (backward pass of conv_mode 1)
+  // Winograd F(4x4,3x3) weights (conv3x3_winof4.hip) for the layers that can be eligible: the plain single-source 64-cout-tile layers of
+  // levels 1-3 (2.25 x the F(2x2) bytes, so not for the 16 x 16 level, whose layers the kernel is not used on)
+  size_t u4off[27];
+  {
+    const float* wsrc = params_host;
+    for (int i = 0; i < 27; ++i) {
+      u4off[i] = 0;
+      const bool plain = (i >= 3 && i <= 11) || i == 16 || i == 17 || i == 19 || i == 20 || i == 22 || i == 23;
+      if (plain && conv3x3_winof4_ok(L[i].cin, 0, L[i].cout, 16, 32)) {
+        align();
+        u4off[i] = host.size();
+        host.resize(host.size() + conv3x3_winof4_floats(L[i].cout, L[i].cin));
+        pack_conv_weights_winof4(wsrc, L[i].cout, L[i].cin, host.data() + u4off[i]);
+      }
+      wsrc += (size_t)L[i].cin * L[i].cout * 9 + L[i].cout;
+    }
+  }
   size_t thoff[27], tuoff[27];      // tuoff: the same adjoint layers as Winograd weights of the fp32 family (conv3x3_wino8.hip, r5)
   float thscale[27];
   {
@@ -666,6 +688,7 @@ int pnpx_unet_load(pnpx_ctx* ctx, const float* params_host, size_t n_params) {
     ctx->conv[i].b = d + boff[i];
     ctx->conv_wino_u[i] = uoff[i] ? d + uoff[i] : nullptr;
     ctx->conv_wino_u_bwd[i] = tuoff[i] ? d + tuoff[i] : nullptr;
+    ctx->conv_winof4_u[i] = u4off[i] ? d + u4off[i] : nullptr;
     ctx->conv_hs[i].w = reinterpret_cast<char*>(d + hoff[i]);
     ctx->conv_bwd[i].w = d + toff[i];
     ctx->conv_bwd[i].b = nullptr;

@@ -72,6 +72,14 @@ int launch_conv3x3_wino8_ups(const float* u, const float* bias, int cout, const 
                              float* out, int B, int H, int W, hipStream_t s, float slope = 0.2f);
 int launch_conv3x3_wino8_outc(const float* u, const float* bias, const float* in0, int cin, const float* outc_w, const float* outc_b,
                               const float* x_img, float* img, float* img_pre, int B, int H, int W, hipStream_t s);
+// Winograd F(4x4, 3x3) on v_mfma_f32_16x16x4_f32 (conv3x3_winof4.hip; option fp32_winof4_layers): plain single-source layers with cout a
+// multiple of 64, >= 16 input channels in multiples of 8, H a multiple of 16, W of 32.  u: pack_conv_weights_winof4's output
+// (conv3x3_winof4_floats(cout, cin) = 36 cout cin floats, 2.25 x the F(2x2) weights).
+bool conv3x3_winof4_ok(int C0, int C1, int cout, int H, int W);
+size_t conv3x3_winof4_floats(int cout, int cin);
+void pack_conv_weights_winof4(const float* w, int cout, int cin, float* dst);
+int launch_conv3x3_winof4(const float* u, const float* bias, int cout, const float* in0, int C0, float* out, int B, int H, int W, hipStream_t s,
+                          float slope = 0.2f, float* pool_out = nullptr);
 void pack_conv_weights_transposed(const float* w, int cout, int cin, int cout_pad, int mt, int cc, float* dst);
 
 }  // namespace pnpx

@@ -1,0 +1,435 @@
+// Winograd F(4x4, 3x3) on the exact-fp32 MFMA v_mfma_f32_16x16x4_f32: 36 products per 16 outputs instead of F(2x2)'s 16 per 4
+// = 0.5625 x the MFMAs of conv3x3_wino8.hip.  Plain 64-cout layers of the UNet's forward passes only (option fp32_winof4_layers;
+// no second source, no residual, no K-split, no fused up-sampling or out-conv).  Same activation layout (padded planar fp32), WinoArgs,
+// bias + LeakyReLU as max(y, slope y) and optional fused 2x2 max-pool as the F(2x2) kernels.
+//
+// Points (0, +-1, +-1/2, inf), rows scaled as tools/wino_f4_probe.py's cook_toom does (winof4_mats.h holds the matrices the packer uses;
+// tests/test_winof4_pack.py checks them against a direct convolution).
+//
+// Geometry.  A workgroup (512 threads = 8 waves, two per SIMD, the whole LDS) owns 64 couts x a region of 16 x 32 px = 32 tiles of 4 x 4
+// (4 tile rows x 8 tile columns).  The 16x16x4 MFMA keeps a 16 cout x 16 tile block in FOUR registers, so all 36 positions of such a
+// block are 144 registers and live in ONE wave: wave (P, sw) -- P = wave / 4, sw = wave % 4, waves sw and sw + 4 share a SIMD -- owns
+// couts 16 * (2 * (sw & 1) + P) .. + 15 and tiles 16 * (sw / 2) .. + 15.  The output transform A^T M A is then wave-local: no exchange
+// through LDS and no barrier in the epilogue.  (Splitting the position COLUMNS over the SIMD's pair instead, as conv3x3_wino8.hip does,
+// would share each V operand between two MFMAs -- 25 % fewer LDS operand bytes, at 256 B/clk not the limit here -- and pay for it with a
+// 96 KB exchange per tile.)  C/D layout: tile = lane & 15, cout = 4 * (lane >> 4) + register: a finished cout row of a tile is four
+// contiguous pixels = one 16-byte store.
+//
+// Pipeline.  8-channel chunks, two position rows per stage = 3 stages per chunk, 24 MFMAs per wave and stage (12 positions x 2 k-steps),
+// operands as 16-byte LDS reads (two positions x two k-steps each).  LDS: weights 3 x 24 KiB (ring, stage s of every chunk = slot s, fetched
+// two stages ahead by 16-byte LDS-DMA), V 3 x 12 KiB (stage s = slot s, written one stage ahead by the input transform), raw halo
+// 2 x 22.75 KiB (18 x 34 per channel in rows of 40 + 2 floats per plane: the transform's 8-byte reads are then conflict-free; dword
+// LDS-DMA gathers, fetched three stages ahead).  One counted vmcnt wait and one barrier per stage.  The accumulators and the stage
+// schedule are the compiler's (MFMA builtins; at two waves per SIMD every value lives in the 256 architectural VGPRs, there are no AGPRs).
+#include <cmath>
+#include <mutex>
+#include <utility>
+#include <vector>
+
+#include "common.h"
+#include "conv3x3.h"
+#include "wino_common.h"
+#include "winof4_mats.h"
+
+namespace pnpx {
+
+namespace {
+
+using namespace wino;
+
+struct CfgF4 {
+  static constexpr int CT = 64, CK = 8;
+  static constexpr int RWL = 40;                          // LDS row stride of the halo (34 used): tile rows land 32 banks apart
+  static constexpr int RPXL = 18 * RWL + 2;               // LDS plane stride: odd channels land on the bank pairs the even ones leave free
+  static constexpr int RAW_ELEMS = CK * RPXL;
+  static constexpr int RAW_INSTR = (RAW_ELEMS + 63) / 64; // dword gathers of 64 lanes: 91
+  static constexpr int RAW_BYTES = RAW_INSTR * 256;
+  static constexpr int RAW_PER_WAVE = (RAW_INSTR + 7) / 8;   // 12, of which the last exists for the first RAW_INSTR % 8 waves only
+  static constexpr int NRAW = RAW_INSTR / 8;                 // 11: gathers every wave issues
+  static constexpr int USTG = 2 * 6 * CK * CT * 4;        // bytes of one stage of weights (two position rows): 24 KiB
+  static constexpr int NUW = USTG / 8192;                 // 16-byte LDS-DMA instructions per wave and stage: 3
+  static constexpr int VSTG = 2 * 6 * CK * 32 * 4;        // bytes of one stage of V: 12 KiB
+  static constexpr int OFF_U = 0, OFF_V = 3 * USTG, OFF_RAW = OFF_V + 3 * VSTG;
+  static constexpr int LDS_USED = OFF_RAW + 2 * RAW_BYTES;   // 157184
+};
+constexpr int LDS_REQF4 = 160 * 1024;
+// -DWINOF4_ABL=bits (timing only, results wrong; tools/build_variant.sh): 1 no input transform, 2 no halo gathers, 4 no weight DMA,
+// 8 no epilogue, 16 no MFMAs, 32 epilogue without its global stores
+#ifndef WINOF4_ABL
+#define WINOF4_ABL 0
+#endif
+static_assert(CfgF4::LDS_USED <= LDS_REQF4, "LDS budget");
+
+// row A of B^T applied to six values (points 0, +-1, +-1/2, inf; winof4_mats.h WINOF4_BT)
+template <int A>
+__device__ __forceinline__ float bt_row(float d0, float d1, float d2, float d3, float d4, float d5) {
+  if (A == 0) return fmaf(0.25f, d0, fmaf(-1.25f, d2, d4));
+  if (A == 1) return fmaf(-0.25f, d2, d4) + fmaf(-0.25f, d1, d3);
+  if (A == 2) return fmaf(-0.25f, d2, d4) - fmaf(-0.25f, d1, d3);
+  if (A == 3) return fmaf(0.5f, d3 - d1, d4 - d2);
+  if (A == 4) return fmaf(-0.5f, d3 - d1, d4 - d2);
+  return fmaf(0.25f, d1, fmaf(-1.25f, d3, d5));
+}
+// A^T applied to six values (WINOF4_AT): four sums
+__device__ __forceinline__ void at_rows(float m0, float m1, float m2, float m3, float m4, float m5, float& o0, float& o1, float& o2, float& o3) {
+  const float p12 = m1 + m2, m12 = m1 - m2, p34 = m3 + m4, m34 = m3 - m4;
+  o0 = (m0 + p12) + p34;
+  o1 = fmaf(0.5f, m34, m12);
+  o2 = fmaf(0.25f, p34, p12);
+  o3 = fmaf(0.125f, m34, m12) + m5;
+}
+
+__global__ __launch_bounds__(512, 1) void conv3x3_winof4_f32_kernel(WinoArgs a) {
+  using C = CfgF4;
+  constexpr int CK = C::CK, RWL = C::RWL, RPXL = C::RPXL, RAW_BYTES = C::RAW_BYTES, RAW_PER_WAVE = C::RAW_PER_WAVE;
+  constexpr int USTG = C::USTG, NUW = C::NUW, VSTG = C::VSTG, OFF_U = C::OFF_U, OFF_V = C::OFF_V, OFF_RAW = C::OFF_RAW;
+  constexpr int UQ = USTG / 4;      // floats per weight stage
+  extern __shared__ __attribute__((aligned(16))) char lds[];
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int sw = wave & 3;
+  const int HpWp = a.Hp * a.Wp;
+  const unsigned lds0 = (unsigned)(size_t)(lptr_t)lds;
+  const int nregions = a.rx * a.ry * a.B;
+  const int nx = (gridDim.x % 8 == 0 && nregions >= 32) ? 8 : 1;       // XCD-grouped walk as conv3x3_wino8.hip (siblings share the halo in L2)
+  const int xcd = blockIdx.x % nx, slot = blockIdx.x / nx, nslot = gridDim.x / nx;
+
+  struct Tile {
+    const float* s0;   // halo origin in channel 0
+    const float* w;    // weights of the cout tile
+    int ct, b, x0, y0, ok, pad_;
+  };
+  auto decode = [&](int k) {
+    Tile T;
+    const int j = slot + nslot * k;
+    const int q = j / a.nct;
+    T.ct = j - q * a.nct;
+    const int reg = nx * q + xcd;
+    T.ok = reg < nregions;
+    T.pad_ = 0;
+    const int t1 = reg / a.rx;
+    const int tx = reg - t1 * a.rx;
+    const int t2 = t1 / a.ry;
+    const int ty = t1 - t2 * a.ry;
+    T.b = t2;
+    T.x0 = tx * 32;
+    T.y0 = ty * 16;
+    T.s0 = a.in0 + (size_t)T.b * a.C0 * HpWp + (size_t)T.y0 * a.Wp + T.x0 + (PADL - 1);
+    T.w = a.u + (size_t)T.ct * a.nch * 3 * UQ;
+    return T;
+  };
+  auto raw_of = [&](const Tile& X, int c) { return X.s0 + (size_t)CK * c * HpWp; };
+
+  auto sync_all = [&]() {
+    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+    __builtin_amdgcn_s_barrier();
+  };
+
+  // -- LDS-DMA, an eighth per wave: per-lane byte offsets of the halo elements from the chunk's origin
+  unsigned roff[RAW_PER_WAVE];
+#pragma unroll
+  for (int k = 0; k < RAW_PER_WAVE; ++k) {
+    const int idx = (wave + 8 * k) * 64 + lane;
+    const int c = idx / RPXL, r = idx - c * RPXL;
+    const int hy = r / RWL, hx = r - hy * RWL;
+    roff[k] = (c < CK && hy < 18 && hx < 34) ? 4u * (unsigned)(c * HpWp + hy * a.Wp + hx) : 0u;
+  }
+  const unsigned uoff = lane * 16u;
+  auto dma_u_piece = [&](const float* src, int uslot, int k) {     // piece k (of NUW per wave) of one stage's weights -> ring slot uslot
+    if (WINOF4_ABL & 4) return;
+    glds16(src + wave * 256 + k * 2048, uoff, lds0 + OFF_U + uslot * USTG + (wave + 8 * k) * 1024);
+  };
+  auto dma_raw_piece = [&](const float* src, int rbuf, int k) {     // gather k (of RAW_PER_WAVE per wave) of one chunk's halo
+    if (WINOF4_ABL & 2) return;
+    if (k < C::NRAW || wave + 8 * k < C::RAW_INSTR) glds4(src, roff[k], lds0 + OFF_RAW + rbuf * RAW_BYTES + (wave + 8 * k) * 256);
+  };
+  auto dma_u = [&](const float* src, int uslot) {
+#pragma unroll
+    for (int k = 0; k < NUW; ++k) dma_u_piece(src, uslot, k);
+  };
+  auto dma_raw = [&](const float* src, int rbuf) {
+#pragma unroll
+    for (int k = 0; k < RAW_PER_WAVE; ++k) dma_raw_piece(src, rbuf, k);
+  };
+
+  // The role P = wave / 4 is a compile-time parameter of the whole tile loop (one branch at the top): every stage stays one basic block.
+  // The two waves of a SIMD run a stage's two halves in opposite order -- P = 0: MFMAs, then the input transform; P = 1: the input
+  // transform, then MFMAs -- so that one wave's transform runs under the other's 24 MFMAs (24 x 32 clocks) and the matrix pipe never
+  // waits for one.  The stage's LDS-DMA pieces are issued between the wave's own MFMAs.
+  auto body = [&](auto role_tag) {
+  constexpr int P = decltype(role_tag)::value;
+
+  // -- input transform: one tile, one channel and one position row (row P of the stage's two) per thread.  Lanes: k-step bit, 16 tiles,
+  // low bit of the channel group (a wave's V writes of a position pair are 512 contiguous bytes); sw: high bit of the channel group,
+  // tile block.  Channel = 2 * group + k-step bit (the MFMA's k index is the group).
+  const int t_ks = lane & 1, t_t16 = (lane >> 1) & 15, t_kq = (lane >> 5) | ((sw & 1) << 1), t_wn = sw >> 1;
+  const int t_tile = t_wn * 16 + t_t16;
+  const int t_rd = ((2 * t_kq + t_ks) * RPXL + 4 * (t_tile >> 3) * RWL + 4 * (t_tile & 7)) * 4;
+  const int t_wr = (P * 3 * 2 + t_wn) * 1024 + (t_kq * 16 + t_t16) * 16 + t_ks * 8;       // + column pair * 2048 (+ slot)
+  auto transform = [&](auto a_tag, int rbuf, int vslot) {
+    constexpr int A = decltype(a_tag)::value;       // position row
+    const char* rb = lds + OFF_RAW + rbuf * RAW_BYTES + t_rd;
+    float d[6][6];
+#pragma unroll
+    for (int y = 0; y < 6; ++y) {
+      const bool need = (A == 0) ? (y % 2 == 0) : (A == 5) ? (y % 2 == 1) : (y >= 1 && y <= 4);
+#pragma unroll
+      for (int x = 0; x < 6; x += 2) {
+        if (need) {
+          const f32x2 v = *reinterpret_cast<const f32x2*>(rb + (y * RWL + x) * 4);
+          d[y][x] = v[0];
+          d[y][x + 1] = v[1];
+        } else {
+          d[y][x] = d[y][x + 1] = 0.f;
+        }
+      }
+    }
+    float t[6];
+#pragma unroll
+    for (int x = 0; x < 6; ++x) t[x] = bt_row<A>(d[0][x], d[1][x], d[2][x], d[3][x], d[4][x], d[5][x]);
+    char* vb = lds + OFF_V + vslot * VSTG + t_wr;
+    *reinterpret_cast<f32x2*>(vb) = (f32x2){bt_row<0>(t[0], t[1], t[2], t[3], t[4], t[5]), bt_row<1>(t[0], t[1], t[2], t[3], t[4], t[5])};
+    *reinterpret_cast<f32x2*>(vb + 2048) = (f32x2){bt_row<2>(t[0], t[1], t[2], t[3], t[4], t[5]), bt_row<3>(t[0], t[1], t[2], t[3], t[4], t[5])};
+    *reinterpret_cast<f32x2*>(vb + 4096) = (f32x2){bt_row<4>(t[0], t[1], t[2], t[3], t[4], t[5]), bt_row<5>(t[0], t[1], t[2], t[3], t[4], t[5])};
+  };
+  auto transform_row = [&](auto s_tag, int rbuf) {      // this thread's row of stage S's two, into V slot S
+    constexpr int S = decltype(s_tag)::value;
+    if (WINOF4_ABL & 1) return;
+    transform(std::integral_constant<int, 2 * S + P>{}, rbuf, S);
+  };
+
+  // -- MFMA operands: 16 bytes = (k-step 2) x (position 2 of a column pair) per lane; lane = 16 * channel group + cout / tile of the block
+  const int mb = 2 * (sw & 1) + P, wn = sw >> 1;
+  const int a_lane = mb * 1024 + lane * 16;      // + (row in stage * 3 + column pair) * 4096 (+ slot)
+  const int b_lane = wn * 1024 + lane * 16;      // + (row in stage * 3 + column pair) * 2048 (+ slot)
+  f32x4 acc[6][6];
+
+  // One pipeline stage S of a chunk: fetch the weights of the stage after next (and, S == 2, the halo of the chunk after next), 24 MFMAs,
+  // the input transform of the next stage, then the counted wait (WAITN = VMEM operations issued after the ones the next stage needs)
+  // and the barrier.
+  auto stage = [&](auto s_tag, auto wait_tag, const float* u_src, const float* raw_src, int raw_buf, int t_rbuf) {
+    constexpr int S = decltype(s_tag)::value, SN = (S + 1) % 3;
+    constexpr int WAITN = decltype(wait_tag)::value;
+    auto side = [&]() { transform_row(std::integral_constant<int, SN>{}, t_rbuf); };
+    // the stage's LDS-DMA pieces, one behind each MFMA (their issue cost then runs under the MFMAs): the weight slice behind MFMAs
+    // 0 .. 2, stage 2's halo gathers behind 4 .. 15
+    auto piece = [&](int m) {
+      if (m < NUW) dma_u_piece(u_src, (S + 2) % 3, m);
+      if (S == 2 && m >= 4 && m < 4 + RAW_PER_WAVE) dma_raw_piece(raw_src, raw_buf, m - 4);
+    };
+    auto mfmas = [&]() {
+      if (WINOF4_ABL & 16) return;
+      f32x4 af[6], bf[6];
+#pragma unroll
+      for (int q = 0; q < 6; ++q) {
+        af[q] = *reinterpret_cast<const f32x4*>(lds + OFF_U + S * USTG + q * 4096 + a_lane);
+        bf[q] = *reinterpret_cast<const f32x4*>(lds + OFF_V + S * VSTG + q * 2048 + b_lane);
+      }
+      static_for<6>([&](auto q_tag) {
+        constexpr int Q = decltype(q_tag)::value, R = Q / 3, CP = Q % 3;
+#pragma unroll
+        for (int ks = 0; ks < 2; ++ks)
+#pragma unroll
+          for (int pos = 0; pos < 2; ++pos)
+          {
+            acc[2 * S + R][2 * CP + pos] = __builtin_amdgcn_mfma_f32_16x16x4f32(af[Q][2 * ks + pos], bf[Q][2 * ks + pos], acc[2 * S + R][2 * CP + pos], 0, 0, 0);
+            if (!(WINOF4_ABL & 16)) {
+              piece(4 * Q + 2 * ks + pos);
+              __builtin_amdgcn_sched_barrier(0);
+            }
+          }
+      });
+    };
+    if (P == 0) {
+      mfmas();
+      __builtin_amdgcn_sched_barrier(0);
+      side();
+    } else {
+      side();
+      __builtin_amdgcn_sched_barrier(0);
+      mfmas();
+    }
+    asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(WAITN) : "memory");
+    __builtin_amdgcn_s_barrier();
+  };
+
+  // -- epilogue, wave-local: Y = A^T M A per accumulator register (= cout), bias + activation, one 16-byte store per tile row
+  auto epilogue = [&](const Tile& T) {
+    const int tile = wn * 16 + (lane & 15), ty = tile >> 3, tx = tile & 7;
+    const int cbase = T.ct * 64 + mb * 16 + 4 * (lane >> 4);
+    float* ob = a.out + ((size_t)T.b * a.Cout + cbase) * HpWp + (size_t)(T.y0 + 4 * ty + 1) * a.Wp + T.x0 + 4 * tx + PADL;
+    const int Hp_pool = padded_h(a.H / 2), Wp_pool = padded_w(a.W / 2);
+    const size_t HpWp_pool = (size_t)Hp_pool * Wp_pool;
+    float* pb = a.pool ? a.pool + ((size_t)T.b * a.Cout + cbase) * HpWp_pool + (size_t)(T.y0 / 2 + 2 * ty + 1) * Wp_pool + T.x0 / 2 + 2 * tx + PADL : nullptr;
+    float bias4[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) bias4[j] = a.bias[cbase + j];
+    static_for<4>([&](auto j_tag) {
+      constexpr int j = decltype(j_tag)::value;
+      float s[4][6];
+#pragma unroll
+      for (int b = 0; b < 6; ++b) at_rows(acc[0][b][j], acc[1][b][j], acc[2][b][j], acc[3][b][j], acc[4][b][j], acc[5][b][j], s[0][b], s[1][b], s[2][b], s[3][b]);
+      const float bias = bias4[j];
+      float* o = ob + (size_t)j * HpWp;
+      f32x4 y[4];
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        float y0, y1, y2, y3;
+        at_rows(s[i][0], s[i][1], s[i][2], s[i][3], s[i][4], s[i][5], y0, y1, y2, y3);
+        y0 += bias;
+        y1 += bias;
+        y2 += bias;
+        y3 += bias;
+        // LeakyReLU with 0 <= slope <= 1 as max(y, slope y)
+        y[i] = (f32x4){fmaxf(y0, y0 * a.slope), fmaxf(y1, y1 * a.slope), fmaxf(y2, y2 * a.slope), fmaxf(y3, y3 * a.slope)};
+        if (!(WINOF4_ABL & 32) || a.slope == 123.f) *reinterpret_cast<f32x4*>(o + i * a.Wp) = y[i];
+      }
+      if (a.pool && (!(WINOF4_ABL & 32) || a.slope == 123.f)) {      // four 2x2 windows per tile; same association as maxpool2_kernel
+        float* p = pb + (size_t)j * HpWp_pool;
+        *reinterpret_cast<f32x2*>(p) = (f32x2){fmaxf(fmaxf(y[0][0], y[0][1]), fmaxf(y[1][0], y[1][1])), fmaxf(fmaxf(y[0][2], y[0][3]), fmaxf(y[1][2], y[1][3]))};
+        *reinterpret_cast<f32x2*>(p + Wp_pool) = (f32x2){fmaxf(fmaxf(y[2][0], y[2][1]), fmaxf(y[3][0], y[3][1])), fmaxf(fmaxf(y[2][2], y[2][3]), fmaxf(y[3][2], y[3][3]))};
+      }
+    });
+  };
+
+  using I0 = std::integral_constant<int, 0>;
+  using I1 = std::integral_constant<int, 1>;
+  using I2 = std::integral_constant<int, 2>;
+  // VMEM operations a stage may leave in flight: its own weight slice (and, around stage 2, the halo gathers issued behind it)
+  using WaitHalo = std::integral_constant<int, NUW + C::NRAW>;
+  using WaitU = std::integral_constant<int, NUW>;
+
+  int k = 0;
+  Tile T = decode(0);
+  if (!T.ok) return;
+  // prologue: the first two halos and weight stages, the first transform
+  dma_raw(T.s0, 0);
+  dma_u(T.w, 0);
+  dma_u(T.w + UQ, 1);
+  dma_raw(raw_of(T, 1), 1);      // (nch >= 2: chunk 1 exists)
+  sync_all();
+  transform_row(I0{}, 0);
+  sync_all();
+
+  int cc = 0;
+  for (;;) {
+    Tile Tn = decode(k + 1);
+    const bool more = Tn.ok;
+    if (!more) Tn = T;      // after the walk's last chunks: surplus loads of this tile's first chunks into buffers nobody reads
+#pragma unroll
+    for (int i = 0; i < 6; ++i)
+#pragma unroll
+      for (int j = 0; j < 6; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
+    for (int c = 0; c < a.nch; ++c, ++cc) {
+      const float* w_c = T.w + (size_t)c * 3 * UQ;
+      const float* nu = (c + 1 < a.nch) ? w_c + 3 * UQ : Tn.w;                                    // the next chunk's weights
+      const float* nraw = (c + 2 < a.nch) ? raw_of(T, c + 2) : raw_of(Tn, c + 2 - a.nch);         // the halo of the chunk after next
+      const int rcur = cc & 1;
+      // stage g = 3 c + s reads weight and V slot s; the transform behind its MFMAs makes V of stage g + 1 (stage 2: from the next chunk's halo)
+      stage(I0{}, WaitHalo{}, w_c + 2 * UQ, nullptr, 0, rcur);
+      stage(I1{}, WaitU{}, nu, nullptr, 0, rcur);
+      stage(I2{}, WaitHalo{}, nu + UQ, nraw, rcur, rcur ^ 1);
+    }
+    if (!(WINOF4_ABL & 8)) epilogue(T);
+    if (!more) break;
+    T = Tn;
+    ++k;
+  }
+  sync_all();   // the surplus loads of the last chunk
+  };
+  if (wave < 4) body(std::integral_constant<int, 0>{});
+  else body(std::integral_constant<int, 1>{});
+}
+
+}  // namespace
+
+// ---------------------------------------------------------------------------------------------------------------------------------
+bool conv3x3_winof4_ok(int C0, int C1, int cout, int H, int W) {
+  return C1 == 0 && C0 >= 16 && C0 % 8 == 0 && cout > 0 && cout % 64 == 0 && H >= 16 && H % 16 == 0 && W >= 32 && W % 32 == 0;
+}
+size_t conv3x3_winof4_floats(int cout, int cin) { return (size_t)36 * cout * cin; }
+
+// U = G g G^T in double, rounded once; layout [cout / 64][cin / 8][stage 3][row in stage 2][column pair 3][cout block 4][channel group 4]
+// [cout 16][k-step 2][column in pair 2]: position (2 * stage + row, 2 * pair + column), channel 8 * chunk + 2 * group + k-step
+void pack_conv_weights_winof4(const float* w, int cout, int cin, float* dst) {
+  const int nch = cin / 8;
+  for (int co = 0; co < cout; ++co)
+    for (int ci = 0; ci < cin; ++ci) {
+      const float* g = w + ((size_t)co * cin + ci) * 9;
+      double gg[6][3], u[6][6];
+      for (int i = 0; i < 6; ++i)
+        for (int x = 0; x < 3; ++x) gg[i][x] = WINOF4_G[i][0] * g[0 * 3 + x] + WINOF4_G[i][1] * g[1 * 3 + x] + WINOF4_G[i][2] * g[2 * 3 + x];
+      for (int i = 0; i < 6; ++i)
+        for (int j = 0; j < 6; ++j) u[i][j] = gg[i][0] * WINOF4_G[j][0] + gg[i][1] * WINOF4_G[j][1] + gg[i][2] * WINOF4_G[j][2];
+      const int ct = co / 64, mb = (co % 64) / 16, m = co % 16, ch = ci / 8, kq = (ci % 8) / 2, ks = ci % 2;
+      for (int i = 0; i < 6; ++i)
+        for (int j = 0; j < 6; ++j) {
+          const size_t idx = (((((((((size_t)ct * nch + ch) * 3 + i / 2) * 2 + i % 2) * 3 + j / 2) * 4 + mb) * 4 + kq) * 16 + m) * 2 + ks) * 2 + j % 2;
+          dst[idx] = (float)u[i][j];
+        }
+    }
+}
+
+int launch_conv3x3_winof4(const float* u, const float* bias, int cout, const float* in0, int C0, float* out, int B, int H, int W, hipStream_t s,
+                          float slope, float* pool_out) {
+  if (!conv3x3_winof4_ok(C0, 0, cout, H, W)) {
+    set_error("conv3x3_winof4: unsupported geometry (%d -> %d channels, %d x %d)", C0, cout, H, W);
+    return PNPX_ERR_SHAPE;
+  }
+  WinoArgs a{};
+  a.in0 = in0;
+  a.in1 = in0;
+  a.u = u;
+  a.bias = bias;
+  a.pool = pool_out;
+  a.out = out;
+  a.B = B;
+  a.H = H;
+  a.W = W;
+  a.Hp = padded_h(H);
+  a.Wp = padded_w(W);
+  a.C0 = C0;
+  a.C1 = 0;
+  a.Cout = cout;
+  a.slope = slope;
+  a.nct = cout / 64;
+  a.nch = C0 / CfgF4::CK;
+  a.nch_all = a.nch;
+  a.ksplit = 1;
+  a.rx = W / 32;
+  a.ry = H / 16;
+  static std::once_flag attr_once[64];
+  int dev = 0;
+  PNPX_HIP(hipGetDevice(&dev));
+  if (dev >= 0 && dev < 64) {
+    hipError_t e = hipSuccess;
+    std::call_once(attr_once[dev], [&] {
+      e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3x3_winof4_f32_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_REQF4);
+    });
+    PNPX_HIP(e);
+  }
+  const long long nreg = (long long)a.rx * a.ry * a.B, ntiles = nreg * a.nct;
+  long long grid = 256;
+  if (grid >= ntiles) grid = ntiles;
+  else if ((grid / 8) % a.nct != 0 && grid >= 8LL * a.nct) grid -= grid % (8 * a.nct);
+  hipLaunchKernelGGL(conv3x3_winof4_f32_kernel, dim3((unsigned)grid), dim3(512), LDS_REQF4, s, a);
+  PNPX_LAUNCH_CHECK();
+  return PNPX_OK;
+}
+
+}  // namespace pnpx
+
+// the matrices the packer uses and the packer itself, for tests/test_winof4_pack.py (host only)
+extern "C" void pnpx_winof4_matrices(double* g18, double* bt36, double* at24) {
+  for (int i = 0; i < 6; ++i)
+    for (int j = 0; j < 3; ++j) g18[i * 3 + j] = pnpx::WINOF4_G[i][j];
+  for (int i = 0; i < 6; ++i)
+    for (int j = 0; j < 6; ++j) bt36[i * 6 + j] = pnpx::WINOF4_BT[i][j];
+  for (int i = 0; i < 4; ++i)
+    for (int j = 0; j < 6; ++j) at24[i * 6 + j] = pnpx::WINOF4_AT[i][j];
+}
+extern "C" int pnpx_winof4_pack(const float* w, int cout, int cin, float* dst) {
+  if (!w || !dst || cout <= 0 || cout % 64 != 0 || cin <= 0 || cin % 8 != 0) return PNPX_ERR_SHAPE;
+  pnpx::pack_conv_weights_winof4(w, cout, cin, dst);
+  return PNPX_OK;
+}

@@ -638,7 +638,16 @@ static int unet_forward_f32(pnpx_ctx* ctx, UNetArena& ar, const UNetPlan& P, con
     if (pooled_done) *pooled_done = false;
     if (ctx->opt_fp32_winograd && ctx->conv_wino_u[li] && conv3x3_wino_ok(i0.C, C1, L.cout, o.H, o.W)) {
       const bool w8 = ((ctx->opt_fp32_wino8 >> li) & 1) && conv3x3_wino8_ok(i0.C, C1, L.cout, o.H, o.W);
-      if (w8) {
+      // F(4x4,3x3) (conv3x3_winof4.hip): plain single-source layers whose bit is set in both masks and that the K-split does not claim in
+      // this call.  Training forwards (keep_all) take the same kernel as inference forwards: a solver's composed (differentiable) forward
+      // and its fused one then agree as closely as before (tests/test_gpu_amp.py holds them to 1e-5 through the Onsager term, which
+      // amplifies a layer-level 7e-7 difference past that bar); the backward pass keeps the F(2x2) adjoint kernels.
+      const bool f4 = w8 && ((ctx->opt_fp32_winof4 >> li) & 1) && ctx->conv_winof4_u[li] && !i1 &&
+                      conv3x3_winof4_ok(i0.C, 0, L.cout, o.H, o.W) &&
+                      !(ks_on(L.cout, o.H, o.W) && conv3x3_wino8_ksplit(i0.C, 0, L.cout, o.H, o.W, ctx->opt_ksplit_rule) > 1);
+      if (f4) {
+        PNPX_TRY(launch_conv3x3_winof4(ctx->conv_winof4_u[li], L.b, L.cout, fptr(i0), i0.C, fptr(o), B, o.H, o.W, s, 0.2f, pooled ? fptr(*pooled) : nullptr));
+      } else if (w8) {
         const bool ks = ks_on(L.cout, o.H, o.W);
         PNPX_TRY(launch_conv3x3_wino8(ctx->conv_wino_u[li], L.b, L.cout, fptr(i0), i0.C, i1 ? fptr(*i1) : nullptr, C1, fptr(o), B, o.H, o.W, s, 0.2f,
                                       nullptr, pooled ? fptr(*pooled) : nullptr, ks ? ks_part0 : nullptr, ctx->opt_ksplit_rule));
@@ -647,7 +656,7 @@ static int unet_forward_f32(pnpx_ctx* ctx, UNetArena& ar, const UNetPlan& P, con
         PNPX_TRY(launch_conv3x3_wino(ctx->conv_wino_u[li], L.b, L.cout, fptr(i0), i0.C, i1 ? fptr(*i1) : nullptr, C1, fptr(o), B, o.H, o.W, s, 0.2f,
                                      nullptr, pooled ? fptr(*pooled) : nullptr));
       if (pooled_done) *pooled_done = pooled != nullptr;
-      return rec.mark("conv3x3_wino", 2.0 * 9.0 * L.cin * L.cout * (double)o.H * o.W * B);   // algorithmic FLOPs; 4/9 of them executed
+      return rec.mark("conv3x3_wino", 2.0 * 9.0 * L.cin * L.cout * (double)o.H * o.W * B);   // algorithmic FLOPs; 4/9 of them executed (F(4x4): 1/4)
     } else {
       PNPX_TRY(launch_conv3x3(L, fptr(i0), i0.C, i1 ? fptr(*i1) : nullptr, C1, fptr(o), B, o.H, o.W, s));
     }

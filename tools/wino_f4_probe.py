@@ -8,7 +8,13 @@ and rounded once, as conv3x3_wino8.hip's packer does), no kernel is built before
       12 seeds) with every cout % 32 == 0 layer emulated as F(2x2,3x3) -- the stand-in for today's fp32 family, to be compared with
       profiles/r5_drift_seeds.md's conv_mode 0 rows -- and the same with the two deepest levels as F(4x4,3x3).
 
-usage: python tools/wino_f4_probe.py [n_seeds] > profiles/r6_wino_f4_probe.md"""
+usage: python tools/wino_f4_probe.py [n_seeds] > profiles/r6_wino_f4_probe.md
+
+  (3) --levels 1,2 [--points half|two] [--jobs N]: the drift table alone, with F(4x4) on a chosen layer set instead of the two deepest
+      levels: the UNet levels given (level k = 1 / 2^k of the image size), once under the eligibility rule of conv3x3_winof4.hip (plain
+      single-source layers with cout % 64 == 0, >= 16 input channels in multiples of 8, H % 16 == 0, W % 32 == 0) and once under the
+      superset "every cout % 32 == 0 layer of those levels" (what the kernel would run on larger images, where the same levels are
+      wider).  python tools/wino_f4_probe.py 12 --levels 1,2 > profiles/winof4_probe.md"""
 import os
 import sys
 
@@ -108,9 +114,22 @@ def layer_table(params):
     return worst
 
 
-def make_den(params, deep):
+def f4_layer(rule, levels, H0, inp_shape, w_shape):
+    """does this 3x3 layer run as F(4x4)?  rule "kernel": conv3x3_winof4_ok + the dispatch's plain single-source condition (a decoder
+    entry is the only layer with more input than output channels); "superset": every cout % 32 == 0 layer of the levels."""
+    h, w = inp_shape[-2], inp_shape[-1]
+    cout, cin = w_shape[0], w_shape[1]
+    lvl = {H0 >> k: k for k in range(5)}.get(h)
+    if lvl is None or lvl not in levels or h % 4 or w % 4:
+        return False
+    if rule == "superset":
+        return True
+    return cout % 64 == 0 and cin >= 16 and cin % 8 == 0 and cin <= cout and h % 16 == 0 and w % 32 == 0
+
+
+def make_den(params, deep, rule=None, levels=()):
     """fp32 CPU denoiser whose 3x3 layers with cout % 32 == 0 run as emulated F(2x2); `deep` (a MATS key) replaces the scheme on the two
-    deepest levels (spatial size <= 1/8 of the image)."""
+    deepest levels (spatial size <= 1/8 of the image) or, with `rule`, on the layers f4_layer() names."""
     p = {k: torch.as_tensor(v).float() for k, v in params.items()}
     orig = F.conv2d
 
@@ -121,7 +140,9 @@ def make_den(params, deep):
             def patched(inp, w, b=None, **kw):
                 if w.shape[-1] == 3 and w.shape[0] % 32 == 0 and w.shape[1] % 8 == 0 and inp.shape[-1] % 2 == 0:
                     key = "F2"
-                    if deep and inp.shape[-1] * 8 <= H0 and inp.shape[-1] % 4 == 0:
+                    if deep and rule and f4_layer(rule, levels, H0, inp.shape, w.shape):
+                        key = deep
+                    elif deep and not rule and inp.shape[-1] * 8 <= H0 and inp.shape[-1] % 4 == 0:
                         key = deep
                     m, mats = MATS[key]
                     return wino_conv(inp, w, b, m, mats)
@@ -136,33 +157,62 @@ def make_den(params, deep):
     return Den()
 
 
-def drift_table(params, n_seeds):
+def drift_schemes(levels, points):
+    schemes = {"emulated F(2x2) everywhere (= today's fp32 family)": (None, None)}
+    if levels:
+        key = "F4 (0,+-1,+-1/2,inf)" if points == "half" else "F4 (0,+-1,+-2,inf)"
+        lv = ",".join(str(l) for l in levels)
+        schemes[f"{key}, levels {lv}, the kernel's eligibility rule"] = (key, "kernel")
+        schemes[f"{key}, every cout % 32 layer of levels {lv}"] = (key, "superset")
+    else:
+        for k in MATS:
+            if k != "F2":
+                schemes[f"{k} on the two deepest levels"] = (k, None)
+    return schemes
+
+
+def drift_seed(job):
+    """one seed of the drift table: (seed, fp32-vs-fp64, {scheme: (vs fp64, vs fp32)})"""
+    seed, levels, points, threads = job
+    torch.set_num_threads(threads)
+    params = synth.make_unet_params(0)
     B, H, W = 2, 64, 64
     t = lambda a: torch.from_numpy(np.ascontiguousarray(a))
     acts = synth.make_actions(B)
-    schemes = {"emulated F(2x2) everywhere (= today's fp32 family)": None}
-    for k in MATS:
-        if k != "F2":
-            schemes[f"{k} on the two deepest levels"] = k
+    d = synth.make_csmri_batch(B, H, W, ratio=4, seed=seed)
+
+    def run(den, dtype):
+        c = lambda a: t(a).to(dtype) if a.dtype != np.bool_ else t(a)
+        v = O.admm_reset(c(d["x0"]))
+        with torch.no_grad():
+            for a in acts:
+                v = O.csmri_admm(den, v, c(d["y0"]), t(d["mask"]), c(a["sigma_d"]), c(a["mu"]))
+        return O.complex2real(v[:, :1]).double()
+
+    ref64 = run(O.Denoiser(params, dtype=torch.float64), torch.float64)
+    ref32 = run(O.Denoiser(params, dtype=torch.float32), torch.float32)
+    res = {}
+    for name, (deep, rule) in drift_schemes(levels, points).items():
+        out = run(make_den(params, deep, rule, levels), torch.float32)
+        res[name] = (rel(out, ref64), rel(out, ref32))
+    return seed, rel(ref32, ref64), res
+
+
+def drift_table(params, n_seeds, levels=(), points="half", jobs=1):
+    schemes = drift_schemes(levels, points)
     rows = {k: [] for k in schemes}
     ecpu = []
-    for seed in range(31, 31 + n_seeds):
-        d = synth.make_csmri_batch(B, H, W, ratio=4, seed=seed)
-
-        def run(den, dtype):
-            c = lambda a: t(a).to(dtype) if a.dtype != np.bool_ else t(a)
-            v = O.admm_reset(c(d["x0"]))
-            with torch.no_grad():
-                for a in acts:
-                    v = O.csmri_admm(den, v, c(d["y0"]), t(d["mask"]), c(a["sigma_d"]), c(a["mu"]))
-            return O.complex2real(v[:, :1]).double()
-
-        ref64 = run(O.Denoiser(params, dtype=torch.float64), torch.float64)
-        ref32 = run(O.Denoiser(params, dtype=torch.float32), torch.float32)
-        ecpu.append(rel(ref32, ref64))
-        for name, deep in schemes.items():
-            out = run(make_den(params, deep), torch.float32)
-            rows[name].append((seed, rel(out, ref64), rel(out, ref32)))
+    work = [(seed, tuple(levels), points, max(1, 8 // jobs) if jobs > 1 else 8) for seed in range(31, 31 + n_seeds)]
+    if jobs > 1:
+        import multiprocessing as mp
+        with mp.get_context("spawn").Pool(jobs) as pool:
+            done = pool.map(drift_seed, work)
+    else:
+        done = [drift_seed(w) for w in work]
+    for seed, e, res in done:
+        ecpu.append(e)
+        for name in schemes:
+            rows[name].append((seed, res[name][0], res[name][1]))
     print("\n| scheme | vs fp64: max / median | vs fp32 CPU oracle: max / median | seeds above 1e-4 (vs fp32 oracle) |")
     print("|---|---|---|---|")
     for name, r in rows.items():
@@ -177,7 +227,11 @@ def drift_table(params, n_seeds):
 
 
 if __name__ == "__main__":
-    n_seeds = int(sys.argv[1]) if len(sys.argv) > 1 else 12
+    pos = [a for a in sys.argv[1:] if not a.startswith("--")]
+    opt = lambda k, dflt: next((sys.argv[i + 1] for i, a in enumerate(sys.argv[:-1]) if a == k), dflt)
+    n_seeds = int(pos[0]) if pos else 12
+    levels = [int(v) for v in opt("--levels", "").split(",") if v]
+    points, jobs = opt("--points", "half"), int(opt("--jobs", "1"))
     torch.set_num_threads(8)
     params = synth.make_unet_params(0)
     # self-check of the generated matrices against an fp64 convolution
@@ -189,6 +243,13 @@ if __name__ == "__main__":
         Vv = np.einsum("ia,bcyxaz,jz->bcyxij", Bt, xp, Bt)
         Y = np.einsum("pi,ijkc,bcyxij,qj->bkyxpq", At, U, Vv, At).transpose(0, 1, 2, 4, 3, 5).reshape(1, 4, 8, 8) + bb.view(1, -1, 1, 1).numpy()
         assert rel(torch.from_numpy(Y), F.conv2d(xx, ww, bb, padding=1)) < 1e-12, k
+    if levels:
+        lv = ",".join(str(l) for l in levels)
+        print(f"# Numerics probe -- Winograd F(4x4,3x3) on UNet levels {lv} of the fp32 family (CPU emulation, `tools/wino_f4_probe.py {n_seeds} --levels {lv} --points {points}`)\n")
+        print(f"30-iteration CS-MRI ADMM episode (B = 2, 64 x 64, {n_seeds} seeds), relative L2 of the reconstructed image.  Bars of "
+              "tests/test_gpu_modes.py::test_csmri_episode_drift_not_worse_than_fp32: 1e-4 against the fp32 oracle, 8e-5 against fp64.")
+        drift_table(params, n_seeds, levels, points, jobs)
+        sys.exit(0)
     print("# r6: numerics probe -- Winograd F(4x4,3x3) on the 16^2 / 32^2 levels of the fp32 family (CPU emulation, `tools/wino_f4_probe.py`)\n")
     print("Per-layer relative L2 error against an fp64 convolution, real activations of the He-scaled UNet at 2 x 256 x 256:\n")
     worst = layer_table(params)
