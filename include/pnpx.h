@@ -231,8 +231,9 @@ int pnpx_policy_params(pnpx_ctx* ctx, float* dst_dev, size_t n_params, void* str
  * Batch statistics couple the images: the call is ONE launch chain whatever option "chains" says, and its result is deterministic
  * (fixed-order reductions in double, no atomics).  Not capturable into a graph.
  * H, W multiples of 32 (else PNPX_ERR_SHAPE); PNPX_ERR_ARG when the last stage has B * (H/32) * (W/32) < 2 values per channel
- * (torch raises there) or momentum is outside [0, 1]; PNPX_ERR_NO_WEIGHTS before a load.  Out of scope: the optimiser step, statistics
- * synchronised across devices, activations kept for a backward pass (pnpx_policy_param_grad re-computes). */
+ * (torch raises there) or momentum is outside [0, 1]; PNPX_ERR_NO_WEIGHTS before a load.  This call keeps nothing for a backward
+ * pass (pnpx_policy_param_grad re-computes; pnpx_policy_forward_train_keep is the forward that keeps); the optimiser step is
+ * pnpx_policy_adam_step.  Out of scope: statistics synchronised across devices. */
 int pnpx_policy_forward_train(pnpx_ctx* ctx, const float* ob, float* probs, float* det, int B, int H, int W, float momentum,
                               int update_running, void* stream);
 /* BatchNorm channels of the actor over its 20 layers in state_dict order (stem bn1, then per stage L.0.bn1, L.0.bn2,
@@ -253,9 +254,58 @@ int pnpx_policy_bn_stats(pnpx_ctx* ctx, float* mean_dev, float* var_dev, size_t 
  * and there is no host read-back -- a call that grows no buffer allocates nothing and does not synchronise the device.  The first
  * call after a load derives the adjoint packings (and, if no train forward ran yet, the fold-free packing: one stream synchronisation).
  * Argument checks as pnpx_policy_forward_train; PNPX_ERR_ARG for a null pointer or n_params != pnpx_policy_num_params(...).
- * Out of scope: the observation's gradient, the optimiser step, graph capture. */
+ * A forward kept by pnpx_policy_forward_train_keep is overwritten.  Out of scope: the observation's gradient, graph capture. */
 int pnpx_policy_param_grad(pnpx_ctx* ctx, const float* ob, const float* grad_probs /* [B][2] */, const float* grad_det /* [B][n_det] */,
                            float* grad_params, size_t n_params, int B, int H, int W, void* stream);
+/* The actor's update without the second forward (trainer.py:171, 201-204): a train-mode forward that is run once and keeps what the
+ * backward pass reads, that backward pass, and the optimiser step on the live vector.
+ *
+ * pnpx_policy_forward_train_keep is pnpx_policy_forward_train -- the same launches, the same arguments and checks, and bit for bit
+ * the same probs, det, batch statistics (pnpx_policy_bn_stats) and, with update_running, moved running statistics -- run in the
+ * gradient workspace, where every raw convolution output and every activation stays.  The context records that this forward is
+ * kept, for which B, H, W and for which capacity of the workspace.
+ * pnpx_policy_param_grad_kept is then pnpx_policy_param_grad without its re-computation: heads, gradient range, and per layer
+ * BatchNorm backward, weight-gradient GEMM and adjoint, on the kept tensors; grad_probs [B][2], grad_det [B][n_det] for the kept B.
+ * grad_params receives the bytes pnpx_policy_param_grad(ob, ...) writes for the observation of the kept forward.  The backward pass
+ * writes gradient tensors only, so it may be called any number of times on one kept forward (once per upstream gradient, say), each
+ * time with the result of the re-computing call.
+ * The kept forward ends with: any change of the trainable weights (pnpx_policy_load, pnpx_policy_load_device, pnpx_policy_adam_step
+ * with a finite norm); pnpx_policy_forward_train, which overwrites the batch statistics the backward pass reads;
+ * pnpx_policy_param_grad, which overwrites the workspace; a re-allocation of the workspace.  A later
+ * pnpx_policy_forward_train_keep replaces it.  Moving the running statistics (either train forward's update_running, which the kept
+ * forward itself may have asked for) does not end it: the backward pass reads neither them nor anything folded from them; nor do
+ * pnpx_policy_forward and pnpx_policy_params.  Without a kept forward pnpx_policy_param_grad_kept returns PNPX_ERR_ARG, with a
+ * message that says what ended it, and writes nothing.  PNPX_ERR_ARG also for a null pointer or a wrong n_params;
+ * PNPX_ERR_NO_WEIGHTS before a load. */
+int pnpx_policy_forward_train_keep(pnpx_ctx* ctx, const float* ob, float* probs, float* det, int B, int H, int W, float momentum,
+                                   int update_running, void* stream);
+int pnpx_policy_param_grad_kept(pnpx_ctx* ctx, const float* grad_probs /* [B][2] */, const float* grad_det /* [B][n_det] */,
+                                float* grad_params, size_t n_params, void* stream);
+/* clip_grad_norm_(actor.parameters(), max_norm) followed by Adam.step() (trainer.py:201-204; no weight decay, no amsgrad) in place on
+ * the actor's live parameter vector: argument for argument pnpx_critic_adam_step (below), the same kernels, the same arithmetic,
+ * the same rules for alignment, determinism, the moments' lifetime and the error codes, with two differences.
+ * FROZEN RANGES: the running_mean / running_var slots of the vector are buffers of the reference module, not parameters, and neither
+ * clip_grad_norm_ nor the optimiser sees them.  Whatever grad_dev holds there (pnpx_policy_param_grad writes zeros; garbage, an
+ * infinity or a NaN are as good) adds nothing to the norm; the running statistics are not written, and the moments at those slots
+ * stay zero.  pnpx_policy_frozen_ranges lists the ranges.
+ * THE REFRESH is the actor's: what pnpx_policy_load_device does on the vector itself -- the eval-mode packing is re-derived at once
+ * (its read-back carries the norm), the fold-free packing and its adjoints by the next train forward / gradient call, and a kept
+ * forward ends.  The next forward of any kind reads the stepped weights.  A gradient whose norm is not finite returns PNPX_ERR_ARG:
+ * parameters, moments, packed weights, the step counter and a kept forward are what they were.  The moments and the counter are
+ * kept by pnpx_policy_load_device of the same (num_inputs, n_det, spi_head) and dropped by pnpx_policy_load, by a load of another
+ * actor and with the context.
+ * Out of scope: policy_loss itself (environment, critic, advantage: it stays with the caller), the trainer loop, weight decay /
+ * amsgrad / other optimisers, loading the moments from a checkpoint, graph capture, statistics synchronised across devices. */
+int pnpx_policy_adam_step(pnpx_ctx* ctx, const float* grad_dev, size_t n_params, float lr, float beta1, float beta2, float eps,
+                          float max_norm, float* grad_norm_dev, void* stream);
+/* As pnpx_critic_optim_state / pnpx_critic_optim_reset, for the actor. */
+int pnpx_policy_optim_state(pnpx_ctx* ctx, float* exp_avg_dst, float* exp_avg_sq_dst, size_t n_params, long long* step_host,
+                            void* stream);
+int pnpx_policy_optim_reset(pnpx_ctx* ctx);
+/* The frozen ranges of an actor's vector, sorted, adjacent ones merged (running_mean and running_var of a BatchNorm layer are one
+ * range): elements [first[i], first[i] + count[i]).  Returns their number (21), writing at most `capacity` of them (first / count may
+ * be NULL with capacity 0); -1 for a shape pnpx_policy_num_params refuses.  Needs no context and no device. */
+int pnpx_policy_frozen_ranges(int num_inputs, int n_det, int spi_head, size_t* first, size_t* count, int capacity);
 
 /* ---- value network / critic (tfpnp/trainer/mddpg/critic.py) --------------------------------------- */
 /* ResNet_wobn(num_inputs, 18, 1) (critic.py:95-131; the trainer never builds another one, trainer/mddpg/critic.py:95 via

@@ -56,6 +56,12 @@ _SIGNATURES = {
     "pnpx_policy_num_bn_channels": (C.c_size_t, []),
     "pnpx_policy_bn_stats": (C.c_int, [c_void_p, _P, _P, C.c_size_t, c_void_p]),
     "pnpx_policy_param_grad": (C.c_int, [c_void_p, _P, _P, _P, _P, C.c_size_t, C.c_int, C.c_int, C.c_int, c_void_p]),
+    "pnpx_policy_forward_train_keep": (C.c_int, [c_void_p, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, c_void_p]),
+    "pnpx_policy_param_grad_kept": (C.c_int, [c_void_p, _P, _P, _P, C.c_size_t, c_void_p]),
+    "pnpx_policy_adam_step": (C.c_int, [c_void_p, _P, C.c_size_t] + [C.c_float] * 5 + [_P, c_void_p]),
+    "pnpx_policy_optim_state": (C.c_int, [c_void_p, _P, _P, C.c_size_t, C.POINTER(C.c_longlong), c_void_p]),
+    "pnpx_policy_optim_reset": (C.c_int, [c_void_p]),
+    "pnpx_policy_frozen_ranges": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), C.c_int]),
     "pnpx_critic_num_params": (C.c_size_t, [C.c_int]),
     "pnpx_critic_load": (C.c_int, [c_void_p, c_void_p, C.c_size_t, C.c_int]),
     "pnpx_critic_load_device": (C.c_int, [c_void_p, _P, C.c_size_t, C.c_int, c_void_p]),

@@ -237,6 +237,55 @@ int pnpx_policy_param_grad(pnpx_ctx* ctx, const float* ob, const float* grad_pro
   return policy_param_grad(ctx, ob, grad_probs, grad_det, grad_params, n_params, B, H, W, static_cast<hipStream_t>(stream));
 }
 
+int pnpx_policy_forward_train_keep(pnpx_ctx* ctx, const float* ob, float* probs, float* det, int B, int H, int W, float momentum,
+                                   int update_running, void* stream) {
+  LOCK_CTX(ctx);
+  if (!ob || !probs || !det) {
+    set_error("pnpx_policy_forward_train_keep: null pointer");
+    return PNPX_ERR_ARG;
+  }
+  return policy_forward_train_keep(ctx, ob, probs, det, B, H, W, momentum, update_running, static_cast<hipStream_t>(stream));
+}
+
+int pnpx_policy_param_grad_kept(pnpx_ctx* ctx, const float* grad_probs, const float* grad_det, float* grad_params, size_t n_params,
+                                void* stream) {
+  LOCK_CTX(ctx);
+  if (!grad_probs || !grad_det || !grad_params) {
+    set_error("pnpx_policy_param_grad_kept: null pointer");
+    return PNPX_ERR_ARG;
+  }
+  return policy_param_grad_kept(ctx, grad_probs, grad_det, grad_params, n_params, static_cast<hipStream_t>(stream));
+}
+
+int pnpx_policy_adam_step(pnpx_ctx* ctx, const float* grad_dev, size_t n_params, float lr, float beta1, float beta2, float eps,
+                          float max_norm, float* grad_norm_dev, void* stream) {
+  LOCK_CTX(ctx);
+  return policy_adam_step(ctx, grad_dev, n_params, lr, beta1, beta2, eps, max_norm, grad_norm_dev, static_cast<hipStream_t>(stream));
+}
+
+int pnpx_policy_optim_state(pnpx_ctx* ctx, float* exp_avg_dst, float* exp_avg_sq_dst, size_t n_params, long long* step_host,
+                            void* stream) {
+  LOCK_CTX(ctx);
+  return policy_optim_state(ctx, exp_avg_dst, exp_avg_sq_dst, n_params, step_host, static_cast<hipStream_t>(stream));
+}
+
+int pnpx_policy_optim_reset(pnpx_ctx* ctx) {
+  LOCK_CTX(ctx);
+  return policy_optim_reset(ctx);
+}
+
+int pnpx_policy_frozen_ranges(int num_inputs, int n_det, int spi_head, size_t* first, size_t* count, int capacity) {
+  if (num_inputs < 1 || num_inputs > 64 || n_det < 1 || n_det > 64) return -1;
+  FrozenRange r[LIVE_OPTIM_MAX_FROZEN];
+  int n = 0;
+  if (policy_frozen_ranges(num_inputs, n_det, spi_head, r, &n) != PNPX_OK) return -1;
+  for (int i = 0; i < n && i < capacity && first && count; ++i) {
+    first[i] = r[i].first;
+    count[i] = r[i].count;
+  }
+  return n;
+}
+
 size_t pnpx_policy_num_bn_channels(void) { return POLICY_BN_CHANNELS; }
 
 int pnpx_policy_bn_stats(pnpx_ctx* ctx, float* mean_dev, float* var_dev, size_t n, void* stream) {
@@ -504,8 +553,8 @@ size_t pnpx_ctx_bytes(const pnpx_ctx* ctx) {
              ctx->drunet.weights.bytes + ctx->drunet.arena.bytes + ctx->drunet.arena_grad.bytes + ctx->drunet.f32_weights.bytes +
              ctx->drunet.f32_arena.bytes + ctx->drunet.f32_weights_bwd.bytes + ctx->drunet.f32_arena_grad.bytes +
              ctx->policy.weights.bytes + ctx->policy.arena.bytes + ctx->policy.live.master.bytes + ctx->policy.pack_ws.ws.bytes + ctx->policy.raw.weights.bytes + ctx->policy.raw_ws.ws.bytes +
-             ctx->policy.train_ws.bytes + ctx->policy.bn_buf.bytes + ctx->critic.weights.bytes + ctx->critic.arena.bytes +
-             ctx->critic.live.master.bytes + ctx->critic.pack_ws.ws.bytes + ctx->critic.optim.bytes;
+             ctx->policy.train_ws.bytes + ctx->policy.bn_buf.bytes + ctx->policy.optim.state.bytes + ctx->critic.weights.bytes + ctx->critic.arena.bytes +
+             ctx->critic.live.master.bytes + ctx->critic.pack_ws.ws.bytes + ctx->critic.optim.state.bytes;
   for (const auto& sl : ctx->train_ring) n += sl.arena.buf.bytes + sl.pre.bytes;
   return n;
 }

@@ -125,7 +125,21 @@ struct PolicyNet : PolicyPack {   // the base: the eval-mode packing (BatchNorm 
   DeviceBuf grad_ws;
   int gcapB = 0, gcapH = 0, gcapW = 0;
   DeviceBuf grad_slab;
+  // kept forward (pnpx_policy_forward_train_keep): every raw output and activation of ONE train forward sits in grad_ws, its batch
+  // statistics in bn_buf, and pnpx_policy_param_grad_kept may run on them.  Valid for the observation shape and the workspace capacity
+  // (the plan's offsets) it was run with; kept_lost says what ended it (policy_kept_drop: a change of the trainable weights, a train
+  // forward or a re-computing gradient call, which overwrite bn_buf / grad_ws).  Moving the running statistics does not end it.
+  bool kept_valid = false;
+  int keptB = 0, keptH = 0, keptW = 0, kept_capB = 0, kept_capH = 0, kept_capW = 0;
+  const char* kept_lost = "no pnpx_policy_forward_train_keep has run on this actor";
+  // optimiser state (pnpx_policy_adam_step; live_params.h): kept by a refresh of the same actor, dropped with the actor; the frozen
+  // ranges are the running statistics
+  LiveOptim optim;
 };
+inline void policy_kept_drop(PolicyNet& N, const char* why) {
+  if (N.kept_valid) N.kept_lost = why;
+  N.kept_valid = false;
+}
 
 // Value network (critic.hip): ResNet_wobn(num_inputs, 18, 1).  The raw parameters live on the device (`live`); the packed
 // weights the launches read are derived from them, on the host by critic_load and on the device by every later refresh
@@ -148,10 +162,8 @@ struct CriticNet {
   // parameter gradients (pnpx_critic_param_grad): clip indicator, W * indicator, K-split slabs + reduction blocks; each grows to
   // the largest size seen
   DeviceBuf grad_m, grad_wm, grad_slab;
-  // optimiser state (pnpx_critic_adam_step; allocated zero-filled by the first step): exp_avg, exp_avg_sq (each padded to a
-  // multiple of four floats), then the sum-of-squares partials; kept by a refresh, dropped with the critic
-  DeviceBuf optim;
-  long long optim_step = 0;          // Adam's step counter t
+  // optimiser state (pnpx_critic_adam_step; live_params.h): kept by a refresh, dropped with the critic; no frozen ranges
+  LiveOptim optim;
 };
 
 // number of independent launch chains for a B-image denoiser forward (unet.hip; option "chains", 0 = automatic)
@@ -425,6 +437,17 @@ int policy_bn_stats(pnpx_ctx* ctx, float* mean_dev, float* var_dev, size_t n, hi
 int policy_param_grad(pnpx_ctx* ctx, const float* ob, const float* grad_probs, const float* grad_det, float* grad_params, size_t n, int B,
                       int H, int W, hipStream_t s);
 int policy_pack_adj(pnpx_ctx* ctx, hipStream_t s);       // live vector -> PolicyNet::raw_bwd (allocates on first use)
+// the same forward kept for the backward pass, and the backward pass on what it kept (policy_bn.hip)
+int policy_forward_train_keep(pnpx_ctx* ctx, const float* ob, float* probs, float* det, int B, int H, int W, float momentum,
+                              int update_running, hipStream_t s);
+int policy_param_grad_kept(pnpx_ctx* ctx, const float* grad_probs, const float* grad_det, float* grad_params, size_t n, hipStream_t s);
+// clip_grad_norm_ + Adam on the live vector (running statistics frozen), then the refresh (policy_pack.hip; kernels: live_optim.hip)
+int policy_frozen_ranges(int num_inputs, int n_det, int spi_head, FrozenRange* out, int* n_out);   // merged; out: LIVE_OPTIM_MAX_FROZEN
+int policy_upload_frozen(pnpx_ctx* ctx);                 // ... of the loaded actor -> PolicyNet::optim, at a load that allocates
+int policy_adam_step(pnpx_ctx* ctx, const float* grad_dev, size_t n, float lr, float beta1, float beta2, float eps, float max_norm,
+                     float* grad_norm_dev, hipStream_t s);
+int policy_optim_state(pnpx_ctx* ctx, float* exp_avg_dst, float* exp_avg_sq_dst, size_t n, long long* step_host, hipStream_t s);
+int policy_optim_reset(pnpx_ctx* ctx);
 
 // Value network (critic.hip)
 size_t critic_num_params(int num_inputs);
@@ -439,19 +462,12 @@ int critic_param_grad(pnpx_ctx* ctx, const float* ob, const float* grad_value, f
 // value_loss = mean((V - q_target)^2) and its backward on one forward (critic.hip)
 int critic_value_loss_grad(pnpx_ctx* ctx, const float* ob, const float* q_target, float* value, float* loss, float* grad_params, size_t n,
                            int B, int H, int W, hipStream_t s);
-// clip_grad_norm_ + Adam on the live vector, then the refresh (critic.hip; kernels: critic_optim.hip)
+// clip_grad_norm_ + Adam on the live vector, then the refresh (critic.hip; kernels: live_optim.hip)
 int critic_adam_step(pnpx_ctx* ctx, const float* grad_dev, size_t n, float lr, float beta1, float beta2, float eps, float max_norm,
                      float* grad_norm_dev, hipStream_t s);
 int critic_optim_state(pnpx_ctx* ctx, float* exp_avg_dst, float* exp_avg_sq_dst, size_t n, long long* step_host, hipStream_t s);
 int critic_optim_reset(pnpx_ctx* ctx);
 void critic_free(pnpx_ctx* ctx);
-// critic_optim.hip
-constexpr int CRITIC_OPTIM_PARTIALS = 1024;   // blocks of the sum-of-squares launch = doubles it writes
-int launch_critic_sumsq(const float* grad, size_t n, double* partials, hipStream_t s);
-// slot[0] = norm, slot[1] = min(1, max_norm / (norm + 1e-6)); norm_out (may be null) receives the norm as well
-int launch_critic_norm_finish(const double* partials, float max_norm, float* slot, float* norm_out, hipStream_t s);
-int launch_critic_adam(const float* grad, float* p, float* m, float* v, size_t n, const float* slot, float one_minus_b1, float b2,
-                       float one_minus_b2, float step_size, float bc2_sqrt, float eps, hipStream_t s);
 
 // FFT building blocks (fft.hip)
 int fft2(pnpx_ctx* ctx, const float* in, float* out, int n_img, int H, int W, bool inverse, bool centered,

@@ -7,7 +7,7 @@
 // arguments, so each refresh ends with one small read-back and a synchronisation of the caller's stream: a refresh cannot be
 // captured into a graph and has to be issued on the stream the critic's other calls use.  Parameter gradients: critic_param_grad below,
 // kernels in critic_grad.hip; critic_value_loss_grad takes value_loss and its backward from one forward.  The optimiser step
-// (critic_adam_step: clip + Adam on the live vector, then the refresh; kernels in critic_optim.hip) keeps its moments in the context.
+// (critic_adam_step: clip + Adam on the live vector, then the refresh; kernels in live_optim.hip) keeps its moments in the context.
 // (The actor's refresh: policy_pack.hip.)
 //
 // Replaces ResNet_wobn(num_inputs, 18, 1).forward (tfpnp/trainer/mddpg/critic.py:95-131) and the autograd pass through it
@@ -514,7 +514,7 @@ void critic_free(pnpx_ctx* ctx) {
   if (N.grad_m.p) (void)hipFree(N.grad_m.p);
   if (N.grad_wm.p) (void)hipFree(N.grad_wm.p);
   if (N.grad_slab.p) (void)hipFree(N.grad_slab.p);
-  if (N.optim.p) (void)hipFree(N.optim.p);
+  N.optim.free();
   N = CriticNet();
 }
 
@@ -1002,27 +1002,9 @@ int critic_value_loss_grad(pnpx_ctx* ctx, const float* ob, const float* q_target
 
 // ------------------------------------------------------------------------------------------- optimiser
 // clip_grad_norm_(max_norm) + Adam.step() (trainer/mddpg/trainer.py:208-209) on the live vector, then repack: sum of squares, finish
-// (norm and clip coefficient into the read-back block's spare floats), the fused update (critic_optim.hip), the refresh.  The
+// (norm and clip coefficient into the read-back block's spare floats), the fused update (LiveOptim, live_optim.hip), the refresh.  The
 // update reads the coefficient on the device and does nothing when the norm is not finite; the host learns the norm from the
 // refresh's own read-back and only then advances the step counter.
-namespace {
-
-struct OptimState {
-  float *m, *v;
-  double* partials;
-};
-inline size_t optim_stride(size_t n) { return (n + 3) & ~(size_t)3; }   // floats: exp_avg_sq starts 16-byte aligned
-inline size_t optim_bytes(size_t n) { return 2 * optim_stride(n) * sizeof(float) + CRITIC_OPTIM_PARTIALS * sizeof(double); }
-inline OptimState optim_state(const CriticNet& N, size_t n) {
-  OptimState o;
-  o.m = static_cast<float*>(N.optim.p);
-  o.v = o.m + optim_stride(n);
-  o.partials = reinterpret_cast<double*>(o.v + optim_stride(n));
-  return o;
-}
-
-}  // namespace
-
 int critic_adam_step(pnpx_ctx* ctx, const float* grad_dev, size_t n, float lr, float beta1, float beta2, float eps, float max_norm,
                      float* grad_norm_dev, hipStream_t s) {
   CriticNet& N = ctx->critic;
@@ -1033,57 +1015,27 @@ int critic_adam_step(pnpx_ctx* ctx, const float* grad_dev, size_t n, float lr, f
               "eps %g, max_norm %g)", (double)lr, (double)beta1, (double)beta2, (double)eps, (double)max_norm);
     return PNPX_ERR_ARG;
   }
-  if (!N.optim.p) {   // first step: zero-filled moments (the only place the call allocates or synchronises the device)
-    PNPX_HIP(hipDeviceSynchronize());
-    PNPX_TRY(alloc_dev(N.optim, optim_bytes(n), "critic optimiser state"));
-    PNPX_HIP(hipMemset(N.optim.p, 0, N.optim.bytes));
-    PNPX_HIP(hipDeviceSynchronize());
-    N.optim_step = 0;
-  }
-  const OptimState o = optim_state(N, n);
   float* slot = pack_ws(N.pack_ws).rb + RB_NORM;
-  const double t = (double)(N.optim_step + 1);
-  const double step_size = (double)lr / (1.0 - std::pow((double)beta1, t));
-  const double bc2_sqrt = std::sqrt(1.0 - std::pow((double)beta2, t));
-  PNPX_TRY(launch_critic_sumsq(grad_dev, n, o.partials, s));
-  PNPX_TRY(launch_critic_norm_finish(o.partials, max_norm, slot, grad_norm_dev, s));
-  PNPX_TRY(launch_critic_adam(grad_dev, N.live.p(), o.m, o.v, n, slot, (float)(1.0 - (double)beta1), beta2,
-                              (float)(1.0 - (double)beta2), (float)step_size, (float)bc2_sqrt, eps, s));
+  PNPX_TRY(N.optim.launch_step(N.live, grad_dev, lr, beta1, beta2, eps, max_norm, slot, grad_norm_dev, "critic optimiser state", s));
   PNPX_TRY(repack(ctx, s));   // (a threshold stepped to a non-finite value: the critic is gone, as after any such refresh)
   const float norm = N.pack_ws.readback[RB_NORM];
   if (!std::isfinite(norm)) {
     set_error("pnpx_critic_adam_step: the gradient norm is not finite (%g); parameters and optimiser state are unchanged", (double)norm);
     return PNPX_ERR_ARG;
   }
-  ++N.optim_step;
+  N.optim.commit();
   return PNPX_OK;
 }
 
 int critic_optim_state(pnpx_ctx* ctx, float* exp_avg_dst, float* exp_avg_sq_dst, size_t n, long long* step_host, hipStream_t s) {
   CriticNet& N = ctx->critic;
   PNPX_TRY(check_vector(N, "pnpx_critic_optim_state", exp_avg_dst && exp_avg_sq_dst, n, nullptr));
-  if (N.optim.p) {
-    const OptimState o = optim_state(N, n);
-    PNPX_HIP(hipMemcpyAsync(exp_avg_dst, o.m, n * sizeof(float), hipMemcpyDeviceToDevice, s));
-    PNPX_HIP(hipMemcpyAsync(exp_avg_sq_dst, o.v, n * sizeof(float), hipMemcpyDeviceToDevice, s));
-  } else {   // before the first step
-    PNPX_HIP(hipMemsetAsync(exp_avg_dst, 0, n * sizeof(float), s));
-    PNPX_HIP(hipMemsetAsync(exp_avg_sq_dst, 0, n * sizeof(float), s));
-  }
-  if (step_host) *step_host = N.optim.p ? N.optim_step : 0;
-  return PNPX_OK;
+  return N.optim.copy_state(n, exp_avg_dst, exp_avg_sq_dst, step_host, s);
 }
 
 // back to "before the first step": the next step allocates zero-filled moments and counts as step 1
 int critic_optim_reset(pnpx_ctx* ctx) {
-  CriticNet& N = ctx->critic;
-  if (N.optim.p) {
-    PNPX_HIP(hipDeviceSynchronize());
-    PNPX_HIP(hipFree(N.optim.p));
-  }
-  N.optim = DeviceBuf();
-  N.optim_step = 0;
-  return PNPX_OK;
+  return ctx->critic.optim.reset();
 }
 
 }  // namespace pnpx

@@ -169,6 +169,7 @@ void policy_free(pnpx_ctx* ctx) {
   if (N.raw_adj_table.p) (void)hipFree(N.raw_adj_table.p);
   if (N.grad_ws.p) (void)hipFree(N.grad_ws.p);
   if (N.grad_slab.p) (void)hipFree(N.grad_slab.p);
+  N.optim.free();
   N = PolicyNet();
 }
 
@@ -243,6 +244,7 @@ int policy_load(pnpx_ctx* ctx, const float* params, size_t n, int num_inputs, in
   int st = policy_adopt_host_blob(ctx, pk, heads, H.f.size());
   if (st == PNPX_OK) st = N.live.alloc(n, "policy parameter");
   if (st == PNPX_OK) st = N.live.set_host(params);
+  if (st == PNPX_OK) st = policy_upload_frozen(ctx);
   if (st != PNPX_OK) {
     policy_free(ctx);
     return st;

@@ -17,7 +17,8 @@
 // eval forward's.  Nothing is kept for a backward pass; fusing the passes into the convolutions is a later step.
 //
 // The same launch sequence (train_forward_launches) over a plan that keeps every z and every activation is the re-computation of
-// policy_param_grad at the end of this file, the driver of the parameter gradients (kernels: policy_grad.hip).
+// policy_param_grad at the end of this file, the driver of the parameter gradients (kernels: policy_grad.hip), and
+// policy_forward_train_keep, after which policy_param_grad_kept runs that driver's backward half on what was kept.
 #include <algorithm>
 #include <cmath>
 
@@ -399,6 +400,7 @@ int policy_forward_train(pnpx_ctx* ctx, const float* ob, float* probs, float* de
   }
   if (!N.raw_valid) PNPX_TRY(policy_pack_raw(ctx, s));
   if (!N.bn_buf.p) PNPX_TRY(alloc_dev(N.bn_buf, 4 * POLICY_BN_CHANNELS * sizeof(float), "policy batch-statistics"));
+  policy_kept_drop(N, "pnpx_policy_forward_train overwrote the batch statistics of the kept forward");
   PNPX_TRY(reserve_arena_hs(N.train_ws, N.tcapB, N.tcapH, N.tcapW, B, H, W,
                             [&](int nb) { return make_train_plan(nb, N.cin_pad, H, W).total; }, "policy train workspace"));
   const TrainPlan P = make_train_plan(N.tcapB, N.cin_pad, H, W);
@@ -419,36 +421,28 @@ int grow(DeviceBuf& b, size_t bytes, const char* what) {
 }  // namespace
 
 // d sum(grad_probs * probs + grad_det * det) / d params through the train-mode forward (policy_loss.backward(), trainer.py:171-212).
-// The forward is re-computed with update_running = 0 into a workspace of its own that keeps every z and every activation; the
-// weight-gradient GEMM reads its HS8 operands (space-to-depth tensors included) from there.  Then,
-// backwards (DESIGN.md section 9c has the table of launches): heads and the gradient range (policy_grad.hip), and per layer BatchNorm
+// policy_param_grad re-computes the forward with update_running = 0 into a workspace of its own that keeps every z and every activation;
+// policy_forward_train_keep is that forward as a call of its own (heads and running-statistics update included), after which
+// policy_param_grad_kept runs the backward pass alone.  The weight-gradient GEMM reads its HS8 operands (space-to-depth tensors
+// included) from the workspace.  Backwards (DESIGN.md section 9c has the table of launches): heads and the gradient range
+// (policy_grad.hip), and per layer BatchNorm
 // backward -> weight gradient (critic_grad.hip's GEMM, G = dz, X = what the forward launch read) -> adjoint convolution.  The adjoint
 // convolutions are linear (the ReLU mask is taken by the BatchNorm backward of the layer below): the critic's input-gradient instance
 // without a mask (EPI_DTHR; windows 0x1FF, 0x1B0 with the shortcut's adjoint as residual on the phase-(0,0) groups, then depth-to-space)
 // and the plain 1x1 instance for the shortcut.  The stem's adjoint is not run (no observation gradient).  Every element of grad_params
-// is written; nothing is kept between calls; weights and running statistics do not change, the batch statistics in bn_buf are those of a
-// train forward on `ob`.
-int policy_param_grad(pnpx_ctx* ctx, const float* ob, const float* grad_probs, const float* grad_det, float* grad_params, size_t n, int B,
-                      int H, int W, hipStream_t s) {
+// is written.  The backward pass reads the forward's tensors and the batch statistics and writes gradient tensors only: it can run any
+// number of times on one forward.
+namespace {
+
+// steps 2 onward on the forward kept under plan P in workspace A (batch statistics in bn_buf)
+int param_grad_backward(pnpx_ctx* ctx, const TrainPlan& P, float* A, const float* grad_probs, const float* grad_det, float* grad_params,
+                        int B, int H, int W, hipStream_t s) {
   PolicyNet& N = ctx->policy;
-  PNPX_TRY(check_train_call(N, "policy parameter gradient", B, H, W));
   const size_t want = policy_num_params(N.num_inputs, N.n_det, N.spi_head);
-  if (n != want) {
-    set_error("pnpx_policy_param_grad: the loaded actor (%d inputs, %d outputs, spi %d) has %zu parameters, got room for %zu", N.num_inputs,
-              N.n_det, N.spi_head, want, n);
-    return PNPX_ERR_ARG;
-  }
-  if (!N.raw_valid) PNPX_TRY(policy_pack_raw(ctx, s));
-  if (!N.adj_valid) PNPX_TRY(policy_pack_adj(ctx, s));
   PackDesc PD[NBN];
   PNPX_TRY(policy_pack_descs(N, PD));
   BnLayer BL[NBN];
   bn_layers(N.num_inputs, BL);
-  if (!N.bn_buf.p) PNPX_TRY(alloc_dev(N.bn_buf, 4 * POLICY_BN_CHANNELS * sizeof(float), "policy batch-statistics"));
-  PNPX_TRY(reserve_arena_hs(N.grad_ws, N.gcapB, N.gcapH, N.gcapW, B, H, W,
-                            [&](int nb) { return make_train_plan(nb, N.cin_pad, H, W, true).total; }, "policy gradient workspace"));
-  const TrainPlan P = make_train_plan(N.gcapB, N.cin_pad, H, W, true);
-  float* A = static_cast<float*>(N.grad_ws.p);
   auto rec = [&](size_t off) { return reinterpret_cast<HsRec*>(A + off); };
   auto hsc = [&](size_t off) { return reinterpret_cast<char*>(A + off); };
   const int hl = H / 32, wl = W / 32;
@@ -480,8 +474,6 @@ int policy_param_grad(pnpx_ctx* ctx, const float* ob, const float* grad_probs, c
   float* gv = reinterpret_cast<float*>(bits + 1) + 1;
   double* part = reinterpret_cast<double*>(gf + small_floats);
 
-  // 1. forward re-computation (the batch statistics land in bn_buf)
-  PNPX_TRY(train_forward_launches(ctx, P, A, ob, nullptr, nullptr, B, H, W, 0.f, 0, s));
   const float* st_mean = static_cast<const float*>(N.bn_buf.p);
   const float* st_var = st_mean + POLICY_BN_CHANNELS;
   unsigned* range_flag = ctx->opt_range_guard ? ctx->range_flag_dev : nullptr;
@@ -608,6 +600,88 @@ int policy_param_grad(pnpx_ctx* ctx, const float* ob, const float* grad_probs, c
   }
   PNPX_TRY(bn_bwd(P.g_stem, P.stem_a, bn_layer(0, P.zstem, P.dz_stem), nullptr, NONE, 8, H / 2, W / 2));
   return wgrad(0, P.dz_stem, P.ob, 4 * N.cin_pad, H / 2, W / 2);
+}
+
+int check_grad_room(const PolicyNet& N, const char* who, size_t n) {
+  const size_t want = policy_num_params(N.num_inputs, N.n_det, N.spi_head);
+  if (n != want) {
+    set_error("%s: the loaded actor (%d inputs, %d outputs, spi %d) has %zu parameters, got room for %zu", who, N.num_inputs, N.n_det,
+              N.spi_head, want, n);
+    return PNPX_ERR_ARG;
+  }
+  return PNPX_OK;
+}
+
+// the gradient workspace for B x H x W under the keep plan; whatever was kept in it is gone from here on
+int reserve_grad_ws(PolicyNet& N, int B, int H, int W, const char* lost) {
+  policy_kept_drop(N, lost);
+  if (!N.bn_buf.p) PNPX_TRY(alloc_dev(N.bn_buf, 4 * POLICY_BN_CHANNELS * sizeof(float), "policy batch-statistics"));
+  return reserve_arena_hs(N.grad_ws, N.gcapB, N.gcapH, N.gcapW, B, H, W,
+                          [&](int nb) { return make_train_plan(nb, N.cin_pad, H, W, true).total; }, "policy gradient workspace");
+}
+
+}  // namespace
+
+// Nothing is kept between calls; weights and running statistics do not change, the batch statistics in bn_buf are those of a train
+// forward on `ob`.  A kept forward is overwritten.
+int policy_param_grad(pnpx_ctx* ctx, const float* ob, const float* grad_probs, const float* grad_det, float* grad_params, size_t n, int B,
+                      int H, int W, hipStream_t s) {
+  PolicyNet& N = ctx->policy;
+  PNPX_TRY(check_train_call(N, "policy parameter gradient", B, H, W));
+  PNPX_TRY(check_grad_room(N, "pnpx_policy_param_grad", n));
+  if (!N.raw_valid) PNPX_TRY(policy_pack_raw(ctx, s));
+  if (!N.adj_valid) PNPX_TRY(policy_pack_adj(ctx, s));
+  PNPX_TRY(reserve_grad_ws(N, B, H, W, "pnpx_policy_param_grad overwrote the workspace of the kept forward"));
+  const TrainPlan P = make_train_plan(N.gcapB, N.cin_pad, H, W, true);
+  float* A = static_cast<float*>(N.grad_ws.p);
+  // 1. forward re-computation (the batch statistics land in bn_buf)
+  PNPX_TRY(train_forward_launches(ctx, P, A, ob, nullptr, nullptr, B, H, W, 0.f, 0, s));
+  return param_grad_backward(ctx, P, A, grad_probs, grad_det, grad_params, B, H, W, s);
+}
+
+// policy_forward_train's launch sequence over the keep plan in the gradient workspace: the same probs, det, batch statistics and moved
+// running statistics, and every raw output and activation left where policy_param_grad_kept reads them.
+int policy_forward_train_keep(pnpx_ctx* ctx, const float* ob, float* probs, float* det, int B, int H, int W, float momentum,
+                              int update_running, hipStream_t s) {
+  PolicyNet& N = ctx->policy;
+  PNPX_TRY(check_train_call(N, "policy kept train forward", B, H, W));
+  if (!(momentum >= 0.f && momentum <= 1.f)) {
+    set_error("policy kept train forward: momentum %g outside [0, 1]", (double)momentum);
+    return PNPX_ERR_ARG;
+  }
+  if (!N.raw_valid) PNPX_TRY(policy_pack_raw(ctx, s));
+  PNPX_TRY(reserve_grad_ws(N, B, H, W, "a later pnpx_policy_forward_train_keep failed"));
+  const TrainPlan P = make_train_plan(N.gcapB, N.cin_pad, H, W, true);
+  PNPX_TRY(train_forward_launches(ctx, P, static_cast<float*>(N.grad_ws.p), ob, probs, det, B, H, W, momentum, update_running, s));
+  N.kept_valid = true;
+  N.keptB = B;
+  N.keptH = H;
+  N.keptW = W;
+  N.kept_capB = N.gcapB;
+  N.kept_capH = N.gcapH;
+  N.kept_capW = N.gcapW;
+  return PNPX_OK;
+}
+
+int policy_param_grad_kept(pnpx_ctx* ctx, const float* grad_probs, const float* grad_det, float* grad_params, size_t n, hipStream_t s) {
+  PolicyNet& N = ctx->policy;
+  if (!N.loaded) {
+    set_error("pnpx_policy_param_grad_kept called before pnpx_policy_load");
+    return PNPX_ERR_NO_WEIGHTS;
+  }
+  if (!N.kept_valid) {
+    set_error("pnpx_policy_param_grad_kept: there is no kept forward: %s", N.kept_lost);
+    return PNPX_ERR_ARG;
+  }
+  if (!N.raw_valid || !N.grad_ws.p || N.kept_capB != N.gcapB || N.kept_capH != N.gcapH || N.kept_capW != N.gcapW) {
+    policy_kept_drop(N, "the gradient workspace was allocated again or the weights changed after the kept forward");
+    set_error("pnpx_policy_param_grad_kept: there is no kept forward: %s", N.kept_lost);
+    return PNPX_ERR_ARG;
+  }
+  PNPX_TRY(check_grad_room(N, "pnpx_policy_param_grad_kept", n));
+  if (!N.adj_valid) PNPX_TRY(policy_pack_adj(ctx, s));
+  const TrainPlan P = make_train_plan(N.kept_capB, N.cin_pad, N.keptH, N.keptW, true);
+  return param_grad_backward(ctx, P, static_cast<float*>(N.grad_ws.p), grad_probs, grad_det, grad_params, N.keptB, N.keptH, N.keptW, s);
 }
 
 int policy_bn_stats(pnpx_ctx* ctx, float* mean_dev, float* var_dev, size_t n, hipStream_t s) {

@@ -31,6 +31,7 @@ namespace {
 constexpr float BN_EPS = 1e-5f;
 constexpr int NCV = TRUNK_LAYERS;   // BatchNorm-ed convolutions in parameter order = the trunk's layer numbering (resnet18_hs.h)
 constexpr int MAXCOPY = 27, NRB = 32;   // 21 biases + up to 6 head tensors; floats of the read-back block
+constexpr int RB_NORM = NCV;            // behind the 21 scales, written by policy_adam_step alone: gradient norm, clip coefficient
 
 struct PolFoldDesc {
   unsigned src_w, src_bn;    // floats into the parameter vector: weights; BatchNorm weight, bias, running_mean, running_var
@@ -353,7 +354,7 @@ int repack(pnpx_ctx* ctx, hipStream_t s, bool raw = false) {
   hipLaunchKernelGGL(pol_pack_hs_kernel, dim3((d.max_items + 255) / 256, NCV), dim3(256), 0, s, w.T, P, w.sc, w.rb, blob);
   PNPX_LAUNCH_CHECK();
   PNPX_TRY(launch_live_copy(w.T->copy, dim3((d.max_copy + 255) / 256, d.ncopy), P, w.sh, blob, s));
-  PNPX_HIP(hipMemcpyAsync(rb_host, w.rb, NCV * sizeof(float), hipMemcpyDeviceToHost, s));
+  PNPX_HIP(hipMemcpyAsync(rb_host, w.rb, (raw ? NCV : RB_NORM + 1) * sizeof(float), hipMemcpyDeviceToHost, s));   // + the optimiser's norm
   PNPX_HIP(hipStreamSynchronize(s));
   for (int i = 0; i < NCV; ++i)
     if (!std::isfinite(rb_host[i])) {
@@ -396,6 +397,7 @@ int policy_load_device(pnpx_ctx* ctx, const float* params_dev, size_t n, int num
     N.spi_head = spi_head;
     int st = alloc_device_layout(N, N.pack_ws, L);
     if (st == PNPX_OK) st = N.live.alloc(n, "policy parameter");
+    if (st == PNPX_OK) st = policy_upload_frozen(ctx);
     if (st != PNPX_OK) {
       policy_free(ctx);
       return st;
@@ -404,9 +406,93 @@ int policy_load_device(pnpx_ctx* ctx, const float* params_dev, size_t n, int num
   }
   N.raw_valid = false;   // new weights: the train-mode packing follows on the next train forward
   N.adj_valid = false;   // ... and its adjoints on the next gradient call
+  policy_kept_drop(N, "the weights were loaded again (pnpx_policy_load_device) after the kept forward");
   PNPX_TRY(N.live.set_device(params_dev, s));
   return repack(ctx, s);
 }
+
+// ------------------------------------------------------------------------------------------- optimiser
+// The running statistics are buffers of the reference module, not parameters: clip_grad_norm_ and Adam (trainer.py:201-204) never see
+// them.  In the live vector they follow each BatchNorm's weight and bias: one frozen range of 2 cout floats per BatchNorm layer.
+int policy_frozen_ranges(int num_inputs, int n_det, int spi_head, FrozenRange* out, int* n_out) {
+  PolicyLayout L;
+  PNPX_TRY(layout_of("policy frozen ranges", num_inputs, n_det, spi_head ? 1 : 0, L));
+  FrozenRange r[2 * NCV];
+  for (int ci = 0; ci < NCV; ++ci) {
+    const PolFoldDesc& F = L.T.fold[ci];
+    r[2 * ci] = FrozenRange{(size_t)F.src_bn + 2 * (size_t)F.cout, (size_t)F.cout};       // running_mean
+    r[2 * ci + 1] = FrozenRange{(size_t)F.src_bn + 3 * (size_t)F.cout, (size_t)F.cout};   // running_var
+  }
+  if (live_merge_frozen(r, 2 * NCV, policy_num_params(num_inputs, n_det, spi_head ? 1 : 0), out, n_out) != PNPX_OK) {
+    set_error("policy frozen ranges: internal layout error for (%d inputs, %d outputs, spi %d)", num_inputs, n_det, spi_head);
+    return PNPX_ERR_SHAPE;
+  }
+  return PNPX_OK;
+}
+
+int policy_upload_frozen(pnpx_ctx* ctx) {
+  PolicyNet& N = ctx->policy;
+  FrozenRange r[LIVE_OPTIM_MAX_FROZEN];
+  int n = 0;
+  PNPX_TRY(policy_frozen_ranges(N.num_inputs, N.n_det, N.spi_head, r, &n));
+  return N.optim.set_frozen(r, n, N.live.n, "policy frozen-range table");
+}
+
+namespace {
+
+int check_vector(const PolicyNet& N, const char* who, bool ptrs, size_t n, const char* what) {
+  if (!N.loaded) {
+    set_error("%s called before an actor was loaded", who);
+    return PNPX_ERR_NO_WEIGHTS;
+  }
+  const size_t want = policy_num_params(N.num_inputs, N.n_det, N.spi_head);
+  if (!ptrs || n != want) {
+    set_error("%s: the loaded actor (%d inputs, %d outputs, spi %d) has %zu parameters, got %s%zu", who, N.num_inputs, N.n_det, N.spi_head,
+              want, what, n);
+    return PNPX_ERR_ARG;
+  }
+  return PNPX_OK;
+}
+
+}  // namespace
+
+// clip_grad_norm_(max_norm) + Adam.step() (trainer/mddpg/trainer.py:201-204) on the live vector, the running statistics frozen, then
+// what pnpx_policy_load_device does on the vector itself: the eval packing is re-derived now (its read-back brings the norm), the
+// fold-free packing, its adjoints and a kept forward are stale.  The update reads the coefficient on the device and does nothing when
+// the norm is not finite; the host learns the norm from the refresh's read-back and only then advances the step counter.
+int policy_adam_step(pnpx_ctx* ctx, const float* grad_dev, size_t n, float lr, float beta1, float beta2, float eps, float max_norm,
+                     float* grad_norm_dev, hipStream_t s) {
+  PolicyNet& N = ctx->policy;
+  PNPX_TRY(check_vector(N, "pnpx_policy_adam_step", grad_dev != nullptr, n, "a gradient of "));
+  if (!(lr >= 0.f) || !std::isfinite(lr) || !(beta1 >= 0.f && beta1 < 1.f) || !(beta2 >= 0.f && beta2 < 1.f) || !(eps > 0.f) ||
+      !std::isfinite(eps) || !(max_norm > 0.f)) {
+    set_error("pnpx_policy_adam_step: need lr >= 0 and finite, betas in [0, 1), eps > 0 and finite, max_norm > 0 (got lr %g, betas %g %g, "
+              "eps %g, max_norm %g)", (double)lr, (double)beta1, (double)beta2, (double)eps, (double)max_norm);
+    return PNPX_ERR_ARG;
+  }
+  float* slot = pack_ws(N.pack_ws).rb + RB_NORM;
+  PNPX_TRY(N.optim.launch_step(N.live, grad_dev, lr, beta1, beta2, eps, max_norm, slot, grad_norm_dev, "policy optimiser state", s));
+  PNPX_TRY(repack(ctx, s));   // (a weight stepped to a non-finite value: the actor is gone, as after any such refresh)
+  const float norm = N.pack_ws.readback[RB_NORM];
+  if (!std::isfinite(norm)) {   // nothing was written: every packing and a kept forward are still those of the weights
+    set_error("pnpx_policy_adam_step: the gradient norm is not finite (%g); parameters and optimiser state are unchanged", (double)norm);
+    return PNPX_ERR_ARG;
+  }
+  N.raw_valid = false;
+  N.adj_valid = false;
+  policy_kept_drop(N, "the weights were stepped (pnpx_policy_adam_step) after the kept forward");
+  N.optim.commit();
+  return PNPX_OK;
+}
+
+int policy_optim_state(pnpx_ctx* ctx, float* exp_avg_dst, float* exp_avg_sq_dst, size_t n, long long* step_host, hipStream_t s) {
+  PolicyNet& N = ctx->policy;
+  PNPX_TRY(check_vector(N, "pnpx_policy_optim_state", exp_avg_dst && exp_avg_sq_dst, n, "room for "));
+  return N.optim.copy_state(n, exp_avg_dst, exp_avg_sq_dst, step_host, s);
+}
+
+// back to "before the first step": the next step allocates zero-filled moments and counts as step 1
+int policy_optim_reset(pnpx_ctx* ctx) { return ctx->policy.optim.reset(); }
 
 int policy_pack_raw(pnpx_ctx* ctx, hipStream_t s) {
   PolicyNet& N = ctx->policy;

@@ -6,7 +6,8 @@ it; `_state` is then None and every other context is dropped, so it cannot serve
 weights on a device goes through `_mutate`.
 
 A subclass supplies the names of the ops.Context entries of its network, its shape arguments, its spec list and the flattening
-of a CPU state dict; nothing here knows which network it owns.
+of a CPU state dict; nothing here knows which network it owns.  The native optimiser step (adam_step_, optim_state,
+reset_optim_) is one of those calls, written once for both networks.
 """
 import torch
 import torch.nn as nn
@@ -20,6 +21,9 @@ class LiveWeights(nn.Module):
     _load = None                # ops.Context methods: load from a state dict,
     _load_device = None         # ... from a flat vector on the device,
     _params = None              # ... a copy of the live vector
+    _adam_step = None           # ... clip + Adam on the live vector, its moments and step counter, forgetting them
+    _optim_state = None
+    _optim_reset = None
     _specs = None               # synth.*_param_specs(*shape): [(key, shape)] in the vector's order
     _flat_params = None         # ops.*_flat_params(state_dict, *shape): the vector of a CPU state dict (numpy)
     _dict = dict                # what state_dict() returns
@@ -99,6 +103,27 @@ class LiveWeights(nn.Module):
         if not isinstance(flat, torch.Tensor):
             raise ops.PnpxError(f"load_flat_: expected a torch.Tensor, got {type(flat).__name__}")
         self._mutate(self._key(flat.device), lambda ctx: getattr(ctx, self._load_device)(flat, *self._shape()), empty=True)
+        return self
+
+    def adam_step_(self, grad, lr, betas=(0.9, 0.999), eps=1e-8, max_norm=50.0):
+        """clip_grad_norm_(parameters, max_norm) + torch.optim.Adam.step() (trainer.py:201-204 / :208-209) on grad's device, in
+        place on the native parameter vector, then the re-pack.  Adam's moments and step counter live in the native context;
+        they survive every refresh of the same network (load_flat_, the critic's soft_update_).  -> the gradient norm before
+        clipping (0-dim device tensor), as clip_grad_norm_ returns it.  A gradient with a non-finite norm raises PnpxError and
+        changes nothing."""
+        if not isinstance(grad, torch.Tensor):
+            raise ops.PnpxError(f"adam_step_: expected a torch.Tensor, got {type(grad).__name__}")
+        return self._mutate(self._key(grad.device), lambda ctx: getattr(ctx, self._adam_step)(grad, lr, betas, eps, max_norm))
+
+    def optim_state(self, device):
+        """(exp_avg, exp_avg_sq, step) of the context on `device`: copies of Adam's moments as flat fp32 vectors (the order of
+        parameters_flat) and the step counter; zeros and 0 before the first adam_step_."""
+        return getattr(self.context(device), self._optim_state)()
+
+    def reset_optim_(self):
+        """Forget Adam's moments and step counter on every device this network lives on.  Returns self."""
+        for ctx in self._ctx.values():
+            getattr(ctx, self._optim_reset)()
         return self
 
     def state_dict(self, *args, destination=None, prefix='', keep_vars=False):

@@ -77,6 +77,7 @@ class Context:
         self._has_weights = False
         self.is_drunet = False
         self._policy = None
+        self._kept_rows = None             # observations of the last policy_forward_train_keep (its gradients have that many rows)
         self._critic = None
         self.cid = next(_ctx_ids)          # integer handle for the dispatcher-registered ops (torch_ops.py)
         _ctx_by_id[self.cid] = self
@@ -201,61 +202,93 @@ class Context:
         return self._live_vector(lib.pnpx_critic_params,
                                  None if self._critic is None else int(lib.pnpx_critic_num_params(self._critic)))
 
+    def _adam_step(self, who, net, noun, n_params, what, step_entry, params_entry, grad, lr, betas, eps, max_norm):
+        """critic_adam_step / policy_adam_step: the checks, the call and what a PNPX_ERR_ARG means.  net, noun: "_critic", "critic" /
+        "_policy", "actor"; n_params: the loaded network's parameter count (None: none loaded); what: the network in words."""
+        if not isinstance(grad, torch.Tensor):
+            raise PnpxError(f"{who}: expected a torch.Tensor, got {type(grad).__name__}")
+        try:
+            lr, eps, max_norm = float(lr), float(eps), float(max_norm)
+            b1, b2 = (float(b) for b in betas)
+        except (TypeError, ValueError):
+            raise PnpxError(f"{who}: lr, betas = (beta1, beta2), eps and max_norm must be numbers, got lr {lr!r}, "
+                            f"betas {betas!r}, eps {eps!r}, max_norm {max_norm!r}") from None
+        if not (0.0 <= lr < float("inf")):
+            raise PnpxError(f"{who}: lr must be finite and >= 0, got {lr}")
+        if not (0.0 <= b1 < 1.0 and 0.0 <= b2 < 1.0):
+            raise PnpxError(f"{who}: betas must lie in [0, 1), got {(b1, b2)}")
+        if not (0.0 < eps < float("inf")):
+            raise PnpxError(f"{who}: eps must be finite and > 0, got {eps}")
+        if not max_norm > 0.0:
+            raise PnpxError(f"{who}: max_norm must be > 0 (float('inf'): no clipping), got {max_norm}")
+        if n_params is None:
+            raise PnpxError(f"{who}: no {noun} loaded")
+        if grad.numel() != n_params:
+            raise PnpxError(f"{who}: {what} has {n_params} parameters, got a gradient of {grad.numel()}")
+        grad = self._flat_vector(grad, who, None, None)     # (its length: above)
+        norm = torch.empty((), device=self.device, dtype=torch.float32)
+        with torch.cuda.device(self.device):
+            st = step_entry(self.handle, _p(grad), grad.numel(), lr, b1, b2, eps, max_norm, _p(norm), _stream(grad))
+            if st == 1:                # PNPX_ERR_ARG: a non-finite gradient norm leaves the network as it was; a refresh that meets a
+                err = _lib.lib().pnpx_last_error()      # non-finite value unloads it, as any refresh does
+                if params_entry(self.handle, None, 0, None) == 3:     # PNPX_ERR_NO_WEIGHTS
+                    setattr(self, net, None)
+                raise PnpxError(f"pnpx call failed (status 1): {err.decode('utf-8', 'replace')}")
+        check(st)
+        return norm
+
+    def _optim_state(self, n, entry):
+        m = torch.empty((n,), device=self.device, dtype=torch.float32)
+        v = torch.empty((n,), device=self.device, dtype=torch.float32)
+        step = C.c_longlong(0)
+        with torch.cuda.device(self.device):
+            check(entry(self.handle, _p(m), _p(v), n, C.byref(step), _stream(m)))
+        return m, v, int(step.value)
+
     def critic_adam_step(self, grad, lr, betas=(0.9, 0.999), eps=1e-8, max_norm=50.0):
         """clip_grad_norm_(max_norm) + torch.optim.Adam.step() (trainer/mddpg/trainer.py:208-209; no weight decay, no amsgrad)
         on the live parameter vector, then the device-side re-packing of load_critic_device.  grad: flat fp32 [n_params] on
         this context's device (critic_param_grad's layout).  The moments and the step counter live in the native context.
         -> the gradient norm before clipping, a 0-dim tensor on the device.  max_norm = float('inf'): no clipping."""
-        if not isinstance(grad, torch.Tensor):
-            raise PnpxError(f"critic_adam_step: expected a torch.Tensor, got {type(grad).__name__}")
-        try:
-            lr, eps, max_norm = float(lr), float(eps), float(max_norm)
-            b1, b2 = (float(b) for b in betas)
-        except (TypeError, ValueError):
-            raise PnpxError(f"critic_adam_step: lr, betas = (beta1, beta2), eps and max_norm must be numbers, got lr {lr!r}, "
-                            f"betas {betas!r}, eps {eps!r}, max_norm {max_norm!r}") from None
-        if not (0.0 <= lr < float("inf")):
-            raise PnpxError(f"critic_adam_step: lr must be finite and >= 0, got {lr}")
-        if not (0.0 <= b1 < 1.0 and 0.0 <= b2 < 1.0):
-            raise PnpxError(f"critic_adam_step: betas must lie in [0, 1), got {(b1, b2)}")
-        if not (0.0 < eps < float("inf")):
-            raise PnpxError(f"critic_adam_step: eps must be finite and > 0, got {eps}")
-        if not max_norm > 0.0:
-            raise PnpxError(f"critic_adam_step: max_norm must be > 0 (float('inf'): no clipping), got {max_norm}")
-        if self._critic is None:
-            raise PnpxError("critic_adam_step: no critic loaded")
-        want = int(_lib.lib().pnpx_critic_num_params(self._critic))
-        if grad.numel() != want:
-            raise PnpxError(f"critic_adam_step: a critic with {self._critic} inputs has {want} parameters, got a gradient of {grad.numel()}")
-        grad = self._flat_vector(grad, "critic_adam_step", None, None)     # (its length: above)
-        norm = torch.empty((), device=self.device, dtype=torch.float32)
-        with torch.cuda.device(self.device):
-            st = _lib.lib().pnpx_critic_adam_step(self.handle, _p(grad), grad.numel(), lr, b1, b2, eps, max_norm, _p(norm), _stream(grad))
-            if st == 1:                # PNPX_ERR_ARG: a non-finite gradient norm leaves the critic as it was; a threshold stepped to a
-                err = _lib.lib().pnpx_last_error()      # non-finite value unloads it, as after any refresh
-                if _lib.lib().pnpx_critic_params(self.handle, None, 0, None) == 3:     # PNPX_ERR_NO_WEIGHTS
-                    self._critic = None
-                raise PnpxError(f"pnpx call failed (status 1): {err.decode('utf-8', 'replace')}")
-        check(st)
-        return norm
+        lib = _lib.lib()
+        n = None if self._critic is None else int(lib.pnpx_critic_num_params(self._critic))
+        return self._adam_step("critic_adam_step", "_critic", "critic", n, f"a critic with {self._critic} inputs", lib.pnpx_critic_adam_step,
+                               lib.pnpx_critic_params, grad, lr, betas, eps, max_norm)
 
     def critic_optim_state(self):
         """(exp_avg, exp_avg_sq, step): copies of Adam's moments (fp32 [n_params] on this context's device) and its step counter;
         zeros and 0 before the first critic_adam_step."""
         if self._critic is None:
             raise PnpxError("critic_optim_state: no critic loaded")
-        n = int(_lib.lib().pnpx_critic_num_params(self._critic))
-        m = torch.empty((n,), device=self.device, dtype=torch.float32)
-        v = torch.empty((n,), device=self.device, dtype=torch.float32)
-        step = C.c_longlong(0)
-        with torch.cuda.device(self.device):
-            check(_lib.lib().pnpx_critic_optim_state(self.handle, _p(m), _p(v), n, C.byref(step), _stream(m)))
-        return m, v, int(step.value)
+        return self._optim_state(int(_lib.lib().pnpx_critic_num_params(self._critic)), _lib.lib().pnpx_critic_optim_state)
 
     def critic_optim_reset(self):
         """Forget Adam's moments and step counter (the state before the first critic_adam_step)."""
         with torch.cuda.device(self.device):
             check(_lib.lib().pnpx_critic_optim_reset(self.handle))
+
+    def policy_adam_step(self, grad, lr, betas=(0.9, 0.999), eps=1e-8, max_norm=50.0):
+        """clip_grad_norm_(max_norm) + torch.optim.Adam.step() (trainer/mddpg/trainer.py:201-204) on the actor's live parameter
+        vector, then the refresh of load_policy_device.  grad: flat fp32 [n_params] on this context's device (policy_param_grad's
+        layout).  The running statistics are frozen: what grad holds at their slots is ignored, they do not move and their
+        moments stay zero.  -> the gradient norm before clipping, a 0-dim tensor on the device."""
+        lib = _lib.lib()
+        n = None if self._policy is None else int(lib.pnpx_policy_num_params(*map(int, self._policy)))
+        what = None if self._policy is None else (f"an actor with {self._policy[0]} inputs and {self._policy[1]} outputs"
+                                                        f"{' (SPI head)' if self._policy[2] else ''}")
+        return self._adam_step("policy_adam_step", "_policy", "actor", n, what, lib.pnpx_policy_adam_step, lib.pnpx_policy_params, grad, lr,
+                               betas, eps, max_norm)
+
+    def policy_optim_state(self):
+        """(exp_avg, exp_avg_sq, step) of the actor's optimiser, as critic_optim_state."""
+        if self._policy is None:
+            raise PnpxError("policy_optim_state: no actor loaded")
+        return self._optim_state(policy_flat_size(self), _lib.lib().pnpx_policy_optim_state)
+
+    def policy_optim_reset(self):
+        """Forget the actor's moments and step counter (the state before the first policy_adam_step)."""
+        with torch.cuda.device(self.device):
+            check(_lib.lib().pnpx_policy_optim_reset(self.handle))
 
     def set_option(self, key, value):
         """e.g. set_option('conv_mode', 1) selects the fast half-split f16 MFMA convolutions (default 0 = fp32 arithmetic)."""
@@ -487,6 +520,59 @@ def policy_param_grad(ctx, ob, grad_probs, grad_det):
         check(_lib.lib().pnpx_policy_param_grad(ctx.handle, _p(ob), _p(grad_probs), _p(grad_det), _p(out), n, B, H, W,
                                                 _stream(ob)))
     return out
+
+
+def policy_forward_train_keep(ctx, ob, momentum=0.1, update_running=True):
+    """policy_forward_train, bit for bit, run where the backward pass reads: the context keeps every activation of this forward
+    until the weights change, a plain train forward or policy_param_grad runs, or the next kept forward replaces it.
+    policy_param_grad_kept(ctx, grad_probs, grad_det) is then the backward pass alone."""
+    ob = _f32(ob, "ob")
+    if ob.dim() != 4 or getattr(ctx, "_policy", None) is None or ob.shape[1] != ctx._policy[0]:
+        raise PnpxError("policy_forward_train_keep: no policy loaded or observation has the wrong channel count")
+    B, _, H, W = ob.shape
+    probs = torch.empty((B, 2), device=ob.device, dtype=torch.float32)
+    det = torch.empty((B, ctx._policy[1]), device=ob.device, dtype=torch.float32)
+    with torch.cuda.device(ob.device):
+        check(_lib.lib().pnpx_policy_forward_train_keep(ctx.handle, _p(ob), _p(probs), _p(det), B, H, W, float(momentum),
+                                                        int(bool(update_running)), _stream(ob)))
+    ctx._kept_rows = B
+    return probs, det
+
+
+def policy_param_grad_kept(ctx, grad_probs, grad_det, out=None):
+    """policy_param_grad's bytes for the observation of the last policy_forward_train_keep, without re-computing the forward.
+    Raises PnpxError, naming the reason, when no kept forward is valid.  May be called more than once per kept forward.
+    out: a flat fp32 [n_params] vector on the device to write into (left untouched by a refused call)."""
+    if getattr(ctx, "_policy", None) is None:
+        raise PnpxError("policy_param_grad_kept: no policy loaded")
+    grad_probs = _f32(grad_probs, "grad_probs")
+    grad_det = _f32(grad_det, "grad_det")
+    # the library reads one row per observation of the kept forward; without one it refuses before it reads anything
+    B = getattr(ctx, "_kept_rows", None)
+    if B is None:
+        B = grad_probs.shape[0] if grad_probs.dim() == 2 else -1
+    if tuple(grad_probs.shape) != (B, 2) or tuple(grad_det.shape) != (B, ctx._policy[1]):
+        raise PnpxError(f"policy_param_grad_kept: grad_probs / grad_det must be [{B}, 2] / [{B}, {ctx._policy[1]}] (one row per "
+                        f"observation of the kept forward), got {tuple(grad_probs.shape)} / {tuple(grad_det.shape)}")
+    n = policy_flat_size(ctx)
+    if out is None:
+        out = torch.empty((n,), device=grad_probs.device, dtype=torch.float32)
+    else:
+        ctx._flat_vector(out, "policy_param_grad_kept", n, "the loaded actor")
+    with torch.cuda.device(grad_probs.device):
+        check(_lib.lib().pnpx_policy_param_grad_kept(ctx.handle, _p(grad_probs), _p(grad_det), _p(out), n, _stream(grad_probs)))
+    return out
+
+
+def policy_frozen_ranges(num_inputs, n_det, spi_head=False):
+    """[(first, count)] of the actor's flat vector that policy_adam_step leaves alone: the running statistics, sorted, adjacent
+    ranges merged.  Needs no device."""
+    cap = 64
+    first, count = (C.c_size_t * cap)(), (C.c_size_t * cap)()
+    n = int(_lib.lib().pnpx_policy_frozen_ranges(int(num_inputs), int(n_det), int(bool(spi_head)), first, count, cap))
+    if n < 0 or n > cap:
+        raise PnpxError(f"policy_frozen_ranges: no actor with {num_inputs} inputs and {n_det} outputs")
+    return [(int(first[i]), int(count[i])) for i in range(n)]
 
 
 def _critic_ob(ctx, ob, who):

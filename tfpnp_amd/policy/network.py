@@ -21,9 +21,19 @@ eval-mode forward whatever the mode: an nn.Module is in training mode from const
 `.eval()`.  The train-mode forward carries no autograd graph; `forward_train_raw(state)` returns its raw head outputs
 (probs, det) without moving anything, and `param_grad(state, grad_probs, grad_det)` is the backward pass through it
 (pnpx_policy_param_grad): the flat gradient of sum(grad_probs * probs + grad_det * det) in `parameters_flat()`'s order, so a
-flat nn.Parameter and a torch optimiser can train the native actor (examples/train_actor.py).  Still out of scope: the
-actor's input gradient, its optimiser step and policy_loss, statistics synchronised across devices (dist.py),
-num_batches_tracked (momentum is a number, so torch never reads it), graph capture of the train forward.
+flat nn.Parameter and a torch optimiser can train the native actor (examples/train_actor.py).
+
+The actor's whole update is native as well, as the critic's is: `forward_train_keep(state)` is the train-mode forward run once,
+where the backward pass reads (pnpx_policy_forward_train_keep: the same bytes, every activation kept in the context);
+`param_grad_kept(grad_probs, grad_det)` is `param_grad` without its re-computation (pnpx_policy_param_grad_kept: the same bytes;
+refused with the reason once the weights changed or another train forward / param_grad ran); `adam_step_(grad, lr, ...)` is
+clip_grad_norm_ + torch.optim.Adam.step() on the context's own vector followed by the refresh (pnpx_policy_adam_step): the
+running statistics are frozen ranges of that vector -- the optimiser neither reads their gradient slots nor moves them -- and
+Adam's moments never leave the context (`optim_state`, `reset_optim_`).  `head(p_stop, det, idx_stop, train)` is the O(B) part of
+`forward`, shared with trainer/mddpg/actor_step.py::actor_update, the actor's half of trainer.py::_update (:171, :201-204).
+Still out of scope: policy_loss itself (environment, critic, advantage: the caller's closure), the MDDPG trainer loop, the
+actor's input gradient, weight decay / amsgrad / other optimisers, loading Adam's moments from a checkpoint, statistics
+synchronised across devices (dist.py), num_batches_tracked (momentum is a number, so torch never reads it), graph capture.
 """
 from collections import OrderedDict
 from typing import Optional
@@ -44,6 +54,7 @@ class ResNetActorBase(LiveWeights):
     # statistics included; the integer `num_batches_tracked` buffers are not kept (eval-mode BatchNorm does not read them)
     _noun, _holds = "actor", "_policy"
     _load, _load_device, _params = "load_policy", "load_policy_device", "policy_params"
+    _adam_step, _optim_state, _optim_reset = "policy_adam_step", "policy_optim_state", "policy_optim_reset"
     _specs = staticmethod(synth.policy_param_specs)
     _flat_params = staticmethod(ops.policy_flat_params)
     _dict = OrderedDict
@@ -74,13 +85,18 @@ class ResNetActorBase(LiveWeights):
                                        lambda c: T.call("policy_forward_train", state, self.bn_momentum, True, c.cid))
         else:
             p_stop, det = T.call("policy_forward", state, ctx.cid)   # [B,2] softmax, [B,n_det] sigmoid
+        return self.head(p_stop, det, idx_stop, train) + (hidden,)
+
+    def head(self, p_stop, det, idx_stop, train):
+        """The O(B) work behind the network: (p_stop [B,2], det [B,n_det]) -> (action dict incl. 'idx_stop', log-prob of
+        idx_stop [B,1], entropy of the stop head [B,1]).  Plain torch: differentiable with respect to p_stop and det."""
         logp = torch.log(p_stop.clamp_min(torch.finfo(p_stop.dtype).eps))     # Categorical's own clamp
         entropy = -torch.special.xlogy(p_stop, p_stop).sum(dim=1, keepdim=True)
         if idx_stop is None:      # stochastic while training, greedy otherwise (network.py:149-156)
             idx_stop = torch.multinomial(p_stop, 1).squeeze(1) if train else p_stop.argmax(dim=1)
         action = self.action_mapping(det)
         action['idx_stop'] = idx_stop
-        return action, logp.gather(1, idx_stop.view(-1, 1)), entropy, hidden
+        return action, logp.gather(1, idx_stop.view(-1, 1)), entropy
 
     def forward_train_raw(self, state):
         """(probs [B,2], det [B,n_det]) of the train-mode forward (batch-statistics BatchNorm) on `state`; moves nothing."""
@@ -90,6 +106,29 @@ class ResNetActorBase(LiveWeights):
         """d sum(grad_probs * probs + grad_det * det) / d parameters_flat(), (probs, det) = forward_train_raw(state): flat fp32
         [n_params] on state's device, the running-statistics slots zero.  Changes nothing (no LiveWeights._mutate)."""
         return T.call("policy_param_grad", state.detach(), grad_probs.detach(), grad_det.detach(), self.context(state.device).cid)
+
+    def forward_train_keep(self, state, update_running=True):
+        """forward_train_raw's (probs, det), bit for bit, from the forward that keeps its activations in the context of state's
+        device for param_grad_kept; update_running moves the running statistics there (momentum bn_momentum), as the reference's
+        train-mode forward does, and makes that device's vector the truth."""
+        if not isinstance(state, torch.Tensor):
+            raise ops.PnpxError(f"forward_train_keep: expected a torch.Tensor, got {type(state).__name__}")
+        if not state.is_cuda:
+            raise ops.PnpxError(f"forward_train_keep: tensor on {state.device}; tfpnp_amd runs on MI355X only, there is no CPU path")
+        run = lambda c: T.call("policy_forward_train_keep", state.detach(), self.bn_momentum, bool(update_running), c.cid)
+        return self._mutate(self._key(state.device), run) if update_running else run(self.context(state.device))
+
+    def param_grad_kept(self, grad_probs, grad_det):
+        """param_grad(state, grad_probs, grad_det) for the state of the last forward_train_keep, without re-computing the forward:
+        the same bytes.  Raises PnpxError, with the reason, if that forward is no longer kept (the weights changed, a train-mode
+        forward or param_grad ran since) or none was run.  May be called more than once per kept forward."""
+        for t in (grad_probs, grad_det):
+            if not isinstance(t, torch.Tensor):
+                raise ops.PnpxError(f"param_grad_kept: expected a torch.Tensor, got {type(t).__name__}")
+        for t in (grad_probs, grad_det):
+            if not t.is_cuda:
+                raise ops.PnpxError(f"param_grad_kept: tensor on {t.device}; tfpnp_amd runs on MI355X only, there is no CPU path")
+        return T.call("policy_param_grad_kept", grad_probs.detach(), grad_det.detach(), self.context(grad_probs.device).cid)
 
     def action_mapping(self, action_deterministic):
         """Sigmoid outputs [B, num_actions * bundle] -> {name: [B, bundle] in the action's range} (network.py:163-175)."""

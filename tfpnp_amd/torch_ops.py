@@ -167,6 +167,33 @@ def _(ob, grad_probs, grad_det, ctx):
     return torch.empty((ops.policy_flat_size(ops.context_by_id(ctx)),), dtype=torch.float32, device=ob.device)
 
 
+@_lib_def("pnpx::policy_forward_train_keep", mutates_args=(), device_types="cuda")
+def policy_forward_train_keep(ob: Tensor, momentum: float, update_running: bool, ctx: int) -> Tuple[Tensor, Tensor]:
+    """policy_forward_train's outputs from the forward that keeps its activations inside the native context `ctx` for
+    policy_param_grad_kept (ops.policy_forward_train_keep).  It mutates the context, none of its tensor arguments; no autograd
+    formula."""
+    return ops.policy_forward_train_keep(ops.context_by_id(ctx), ob, momentum, update_running)
+
+
+@policy_forward_train_keep.register_fake
+def _(ob, momentum, update_running, ctx):
+    n_det = ops.context_by_id(ctx)._policy[1]
+    return (torch.empty((ob.shape[0], 2), dtype=ob.dtype, device=ob.device),
+            torch.empty((ob.shape[0], n_det), dtype=ob.dtype, device=ob.device))
+
+
+@_lib_def("pnpx::policy_param_grad_kept", mutates_args=(), device_types="cuda")
+def policy_param_grad_kept(grad_probs: Tensor, grad_det: Tensor, ctx: int) -> Tensor:
+    """policy_param_grad on the forward the context `ctx` kept (ops.policy_param_grad_kept): the flat gradient vector in
+    policy_params' order.  Mutates nothing; no autograd formula (it IS the backward pass)."""
+    return ops.policy_param_grad_kept(ops.context_by_id(ctx), grad_probs, grad_det)
+
+
+@policy_param_grad_kept.register_fake
+def _(grad_probs, grad_det, ctx):
+    return torch.empty((ops.policy_flat_size(ops.context_by_id(ctx)),), dtype=torch.float32, device=grad_probs.device)
+
+
 # ------------------------------------------------------------------------------------------------- transforms
 @_lib_def("pnpx::fft2", mutates_args=(), device_types="cuda")
 def fft2(x: Tensor, inverse: bool, centered: bool) -> Tensor:
@@ -621,7 +648,8 @@ def call(name, *args):
 
 
 ALL_OPS = ("unet_denoise", "unet_denoise_preclamp", "unet_denoise_backward", "unet_denoise_train",
-           "unet_denoise_backward_ticket", "policy_forward", "policy_forward_train", "policy_param_grad", "fft2", "cdp_forward",
+           "unet_denoise_backward_ticket", "policy_forward", "policy_forward_train", "policy_param_grad", "policy_forward_train_keep",
+           "policy_param_grad_kept", "fft2", "cdp_forward",
            "cdp_backward", "spi_inverse", "psnr", "radon_forward", "radon_backprojection", "csmri_admm", "csmri_admm_train",
            "csmri_admm_backward", "csmri_hqs", "csmri_amp",
            "csmri_pg", "csmri_apg", "csmri_redadmm", "pr_iadmm", "spi_admm", "ct_iadmm", "ct_pg", "pr_pg",

@@ -20,9 +20,9 @@ backward() from ONE forward (pnpx_critic_value_loss_grad), and `adam_step_(grad,
 torch.optim.Adam.step() on the context's own parameter vector followed by the re-pack (pnpx_critic_adam_step): the
 parameters and Adam's moments never leave the native context, no torch optimiser is involved (`optim_state`,
 `reset_optim_`; trainer/mddpg/critic_step.py::critic_update is the critic's half of trainer.py::_update).
-Out of scope: the actor's loss and a trainable actor, weight decay / amsgrad / other optimisers, checkpointing the moments
+Out of scope: the actor's loss, weight decay / amsgrad / other optimisers, checkpointing the moments
 (the reference's save_model does not save them either), a graph-capturable step, the MDDPG trainer loop, depths other
-than 18.  (The native actor has the same live weights: policy/network.py; the replay memory is utils/rpm.py.)
+than 18.  (The native actor has the same live weights and the same optimiser step: policy/network.py, trainer/mddpg/actor_step.py; the replay memory is utils/rpm.py.)
 """
 import torch
 
@@ -37,6 +37,9 @@ class ResNet_wobn(LiveWeights):
     # torch.cat([p.flatten() for p in critic.parameters()])
     _noun, _holds = "critic", "_critic"
     _load, _load_device, _params = "load_critic", "load_critic_device", "critic_params"
+    # adam_step_ / optim_state / reset_optim_ (live.py): trainer.py:208-209 on the context's own vector; the moments also survive
+    # soft_update_
+    _adam_step, _optim_state, _optim_reset = "critic_adam_step", "critic_optim_state", "critic_optim_reset"
     _specs = staticmethod(synth.critic_param_specs)
     _flat_params = staticmethod(ops.critic_flat_params)
 
@@ -84,23 +87,3 @@ class ResNet_wobn(LiveWeights):
                 raise ops.PnpxError(f"ResNet_wobn: tensor on {t.device}; tfpnp_amd runs on MI355X only, there is no CPU path")
         V, loss, grad = T.call("critic_value_loss_grad", x.detach(), q_target.detach().reshape(-1), self.context(x.device).cid)
         return loss, V, grad
-
-    def adam_step_(self, grad, lr, betas=(0.9, 0.999), eps=1e-8, max_norm=50.0):
-        """clip_grad_norm_(parameters, max_norm) + torch.optim.Adam.step() (trainer.py:208-209) on grad's device, in place on
-        the native parameter vector, then the re-pack.  Adam's moments and step counter live in the native context; they
-        survive load_flat_ / soft_update_ of the same critic.  -> the gradient norm before clipping (0-dim device tensor), as
-        clip_grad_norm_ returns it.  A gradient with a non-finite norm raises PnpxError and changes nothing."""
-        if not isinstance(grad, torch.Tensor):
-            raise ops.PnpxError(f"adam_step_: expected a torch.Tensor, got {type(grad).__name__}")
-        return self._mutate(self._key(grad.device), lambda ctx: ctx.critic_adam_step(grad, lr, betas, eps, max_norm))
-
-    def optim_state(self, device):
-        """(exp_avg, exp_avg_sq, step) of the context on `device`: copies of Adam's moments as flat fp32 vectors
-        (synth.critic_param_specs order) and the step counter; zeros and 0 before the first adam_step_."""
-        return self.context(device).critic_optim_state()
-
-    def reset_optim_(self):
-        """Forget Adam's moments and step counter on every device this critic lives on.  Returns self."""
-        for ctx in self._ctx.values():
-            ctx.critic_optim_reset()
-        return self
