@@ -49,6 +49,12 @@ int main(void) {
   /* state_dict order: 27 x (weight[cout][cin][3][3], bias[cout]) + outc; a uniform He-like scale is enough here */
   for (size_t i = 0; i < n; ++i) wts[i] = unif() * 0.04f;
 
+  /* host-only plan of the test-only single-layer probe: the 8-wave Winograd kernel runs 64 -> 64 channels at 16 x 16 on a 64-wide tile */
+  if (pnpx_conv3x3_probe_plan(PNPX_PROBE_WINO8, 64, 0, 64, 16, 16, 1) != 64 || pnpx_conv3x3_probe_plan(PNPX_PROBE_WINOF4, 64, 0, 64, 16, 16, 1) != 0) {
+    fprintf(stderr, "pnpx_conv3x3_probe_plan: unexpected plan\n");
+    return 1;
+  }
+
   pnpx_ctx* ctx = NULL;
   CHECK(pnpx_ctx_create(0, &ctx));
   CHECK(pnpx_unet_load(ctx, wts, n));

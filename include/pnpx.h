@@ -658,6 +658,35 @@ int pnpx_ct_pg_backward(pnpx_ctx* ctx, int n_view, float opnorm, const float* si
 void pnpx_winof4_matrices(double* g18, double* bt36, double* at24);
 int pnpx_winof4_pack(const float* w, int cout, int cin, float* dst);
 
+/* Single-layer probe of the fp32 3x3 convolution kernels of conv_mode 0 (csrc/conv_probe.hip), for tests: one layer's HOST weights are
+ * packed by the packers pnpx_unet_load uses and ONE kernel of the chosen kind runs on DEVICE tensors the caller laid out in the denoiser's
+ * internal padded planar layout: [B][C][H + 2][W + 8] fp32, pixel (y, x) at row y + 1, column x + 4, every other cell zero.  The call pads
+ * and unpads nothing, allocates its own K-split scratch, and waits for its launch before it returns (the packed weights are its own).
+ *   forward kinds: out = LeakyReLU_slope(conv3x3(cat(in0, in1), w [cout][C0 + C1][3][3]) + bias [cout]) (+ res, same geometry as out);
+ *     pool_out (where the kind has the fused epilogue): also MaxPool2d(2) of out, [B][cout][H/2 + 2][W/2 + 8].
+ *     WINO8_KSPLIT: the 8-wave kernel handed the K-split scratch (ks_rule: conv3x3_wino8.hip; 1 = the default rule); WINO8_UPS: in1 is
+ *     the LOW-resolution second source [B][C1][H/2 + 2][W/2 + 8], up-sampled x2 (bilinear, align_corners) inside the kernel.
+ *   adjoint kinds: w is the FORWARD layer's [C0][cout][3][3]; in0 = the gradient of its output (C0 channels), out = the gradient of its
+ *     input (cout channels, a multiple of 32) = conv_transpose(in0, w), times (mask > 0 ? 1 : slope) when mask (out's geometry) is given;
+ *     no bias.
+ * A geometry the kind's launcher refuses returns PNPX_ERR_SHAPE with the launcher's message and launches nothing.
+ * pnpx_conv3x3_probe_plan (host only, no context): 0 when the kind refuses the geometry, else the cout-tile width (32 / 64); for
+ * WINO8_KSPLIT plus 256 x the number of K-split pieces (1 = the layer does not split). */
+enum pnpx_probe_kind {
+  PNPX_PROBE_DIRECT = 0,
+  PNPX_PROBE_WINO4 = 1,
+  PNPX_PROBE_WINO8 = 2,
+  PNPX_PROBE_WINO8_KSPLIT = 3,
+  PNPX_PROBE_WINOF4 = 4,
+  PNPX_PROBE_WINO8_UPS = 5,
+  PNPX_PROBE_DIRECT_GRAD = 6,
+  PNPX_PROBE_WINO8_GRAD = 7
+};
+int pnpx_conv3x3_probe(pnpx_ctx* ctx, int kind, const float* w_host, const float* bias_host, int cout, const float* in0, int C0,
+                       const float* in1, int C1, float* out, const float* res, const float* mask, float slope, float* pool_out,
+                       int ks_rule, int B, int H, int W, void* stream);
+int pnpx_conv3x3_probe_plan(int kind, int C0, int C1, int cout, int H, int W, int ks_rule);
+
 #ifdef __cplusplus
 }
 #endif

@@ -148,6 +148,9 @@ _SIGNATURES = {
     "pnpx_ct_pg": (C.c_int, [c_void_p, _P, _P, _P, C.c_int, C.c_float, _P, _P] + [C.c_int] * 4 + [c_void_p]),
     "pnpx_winof4_matrices": (None, [c_void_p, c_void_p, c_void_p]),
     "pnpx_winof4_pack": (C.c_int, [c_void_p, C.c_int, C.c_int, c_void_p]),
+    "pnpx_conv3x3_probe": (C.c_int, [c_void_p, C.c_int, c_void_p, c_void_p, C.c_int, _P, C.c_int, _P, C.c_int, _P, _P, _P, C.c_float, _P,
+                                     C.c_int, C.c_int, C.c_int, C.c_int, c_void_p]),
+    "pnpx_conv3x3_probe_plan": (C.c_int, [C.c_int] * 7),
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 

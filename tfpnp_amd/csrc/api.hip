@@ -682,11 +682,7 @@ int pnpx_unet_load(pnpx_ctx* ctx, const float* params_host, size_t n_params) {
       const int mt = (cout_t % 64 == 0) ? 64 : 32;
       const float* wsrc = params_host;
       for (int k = 0; k < i; ++k) wsrc += (size_t)L[k].cin * L[k].cout * 9 + L[k].cout;
-      wt.assign((size_t)cout_t * cin_t * 9, 0.f);
-      for (int ci = 0; ci < L[i].cin; ++ci)
-        for (int co = 0; co < cin_t; ++co)
-          for (int tap = 0; tap < 9; ++tap)
-            wt[((size_t)ci * cin_t + co) * 9 + tap] = wsrc[((size_t)co * L[i].cin + ci) * 9 + (8 - tap)];
+      transpose_flip_conv_weights(wsrc, L[i].cout, L[i].cin, cout_t, wt);
       align();
       thoff[i] = host.size();
       const size_t n16 = (size_t)cout_t * cin_t * 9 * 2;

@@ -81,5 +81,8 @@ void pack_conv_weights_winof4(const float* w, int cout, int cin, float* dst);
 int launch_conv3x3_winof4(const float* u, const float* bias, int cout, const float* in0, int C0, float* out, int B, int H, int W, hipStream_t s,
                           float slope = 0.2f, float* pool_out = nullptr);
 void pack_conv_weights_transposed(const float* w, int cout, int cin, int cout_pad, int mt, int cc, float* dst);
+// ... and the same transposition as plain [cout_pad][cout][3][3] weights, for the packers of the other kernel families (the adjoint
+// layers' pack_conv_weights_hs / pack_conv_weights_wino input)
+void transpose_flip_conv_weights(const float* w, int cout, int cin, int cout_pad, std::vector<float>& wt);
 
 }  // namespace pnpx

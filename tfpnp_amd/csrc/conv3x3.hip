@@ -357,6 +357,15 @@ void pack_conv_weights_transposed(const float* w, int cout, int cin, int cout_pa
           }
 }
 
+// w[cout][cin][3][3] -> the adjoint convolution's own weights wt[cout_pad][cout][3][3], wt[ci][co][tap] = w[co][ci][8 - tap], rows
+// cin .. cout_pad - 1 zero: what the half-split and the Winograd packers are handed for an adjoint layer
+void transpose_flip_conv_weights(const float* w, int cout, int cin, int cout_pad, std::vector<float>& wt) {
+  wt.assign((size_t)cout_pad * cout * 9, 0.f);
+  for (int ci = 0; ci < cin; ++ci)
+    for (int co = 0; co < cout; ++co)
+      for (int tap = 0; tap < 9; ++tap) wt[((size_t)ci * cout + co) * 9 + tap] = w[((size_t)co * cin + ci) * 9 + (8 - tap)];
+}
+
 // Host-side repack: w[cout][cin][3][3] -> [cout/mt][cin/cc][tap][cc][mt]
 void pack_conv_weights(const float* w, int cout, int cin, int mt, int cc, float* dst) {
   const int nct = cout / mt, nch = cin / cc;
