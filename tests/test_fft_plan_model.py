@@ -117,7 +117,7 @@ def test_option_legs_reach_a_generic_pass_and_stay_in_the_option_range():
         assert s in M.FFT_CASES and M.plan(*s).partial_group
     assert max(M.FFT_TILES) == 8192                  # the documented range of option fft_tile (include/pnpx.h, api.hip)
     api = _src("api.hip")
-    assert re.search(r'is\("fft_tile"\)\s*&&\s*value\s*>=\s*0\s*&&\s*value\s*<=\s*8192', api)
+    assert re.search(r'\{"fft_tile",\s*&pnpx_ctx::opt_fft_tile,\s*0,\s*8192\}', api)       # its row of the option table: name, field, min, max
     for s, t in M.FFT_OVERSIZE_LEGS:
         p = M.plan(*s, tile=t, lds_limit=0)
         assert p.rows != "fast256" and p.cols != "fast256" and max(p.lds_rows, p.lds_cols) > 64 * 1024

@@ -150,7 +150,8 @@ def test_every_context_option_is_documented_in_the_header():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     api = open(os.path.join(root, "tfpnp_amd", "csrc", "api.hip")).read()
     header = open(os.path.join(root, "include", "pnpx.h")).read()
-    keys = sorted(set(re.findall(r'is\("([a-z0-9_]+)"\)', api)))
+    # the explicit cases, and the rows of the table of plain options
+    keys = sorted(set(re.findall(r'is\("([a-z0-9_]+)"\)', api) + re.findall(r'\{"([a-z0-9_]+)", &pnpx_ctx::', api)))
     assert len(keys) >= 20
     missing = [k for k in keys if f'"{k}"' not in header]
     assert not missing, f"options accepted by pnpx_ctx_set_option but not described in include/pnpx.h: {missing}"

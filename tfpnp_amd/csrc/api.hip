@@ -1,5 +1,6 @@
 // C-ABI entry points of libpnpx.so: context, weights, denoiser, generic transforms.  (Solver loops live next to
 // their kernels in csmri.hip / tasks.hip.)
+#include <climits>
 #include <cstring>
 
 #include "common.h"
@@ -383,90 +384,56 @@ int pnpx_ctx_reserve(pnpx_ctx* ctx, int B, int H, int W) {
   return ctx_reserve_unet(ctx, B, H, W);
 }
 
+// The plain integer options: a field of the context and its accepted range, read by pnpx_ctx_set_option and pnpx_ctx_get_option alike
+// (include/pnpx.h describes each).  Options with a side effect or another rule are explicit cases of the two functions.
+namespace {
+struct PlainOption {
+  const char* name;
+  int pnpx_ctx::*field;
+  int lo, hi;
+};
+const PlainOption PLAIN_OPTIONS[] = {
+    {"conv_mode", &pnpx_ctx::conv_mode, CONV_F32, CONV_HS},
+    {"subbatch", &pnpx_ctx::opt_subbatch, 0, INT_MAX},
+    {"fuse_pool", &pnpx_ctx::opt_fuse_pool, 0, 1},
+    {"fuse_outc", &pnpx_ctx::opt_fuse_outc, 0, 1},
+    {"fuse_first", &pnpx_ctx::opt_fuse_first, 0, 1},
+    {"fold_first", &pnpx_ctx::opt_fold_first, 0, 1},
+    {"fft_tile", &pnpx_ctx::opt_fft_tile, 0, 8192},
+    {"fft_fast", &pnpx_ctx::opt_fft_fast, 0, 1},
+    {"fft_affine", &pnpx_ctx::opt_fft_affine, 0, 1},
+    {"chains", &pnpx_ctx::opt_chains, 0, 8},
+    {"wreg", &pnpx_ctx::opt_wreg, 0, 2},
+    {"fuse_up", &pnpx_ctx::opt_fuse_up, 0, 2},
+    {"fp32_winograd", &pnpx_ctx::opt_fp32_winograd, 0, 1},
+    {"fp32_chains", &pnpx_ctx::opt_fp32_chains, 0, 8},
+    {"fp32_fuse_up", &pnpx_ctx::opt_fp32_fuse_up, 0, 1},
+    {"fp32_ksplit", &pnpx_ctx::opt_fp32_ksplit, 0, 2},
+    {"fp32_ksplit_rule", &pnpx_ctx::opt_ksplit_rule, 1, 255},      // tuning: 1 the default rule, else pieces per tile class (conv3x3_wino8_ksplit)
+    {"fp32_wino8_layers", &pnpx_ctx::opt_fp32_wino8, 0, (1 << 27) - 1},      // bit li: layer li on the 8-wave Winograd kernel
+    {"fp32_winof4_layers", &pnpx_ctx::opt_fp32_winof4, 0, (1 << 27) - 1},    // bit li: layer li on the F(4x4,3x3) kernel (forward passes)
+};
+const PlainOption* plain_option(const char* key) {
+  for (const PlainOption& o : PLAIN_OPTIONS)
+    if (key && !std::strcmp(key, o.name)) return &o;
+  return nullptr;
+}
+}  // namespace
+
 int pnpx_ctx_set_option(pnpx_ctx* ctx, const char* key, int value) {
   LOCK_CTX(ctx);
   auto is = [&](const char* k) { return key && !std::strcmp(key, k); };
-  if (is("conv_mode") && (value == CONV_F32 || value == CONV_HS)) {
-    ctx->conv_mode = value;
-    return PNPX_OK;
+  if (const PlainOption* o = plain_option(key)) {
+    if (value >= o->lo && value <= o->hi) {
+      ctx->*(o->field) = value;
+      return PNPX_OK;
+    }
   }
   if (is("drunet_shift") && value >= 0 && value <= 8 && (value & 3) == 0) {   // DRUNet passes run on inputs scaled by 2^-value
     ctx->drunet.shift = value;                                                 // (raised by 4 whenever the range guard trips)
     return PNPX_OK;
   }
-  if (is("subbatch") && value >= 0) {
-    ctx->opt_subbatch = value;
-    return PNPX_OK;
-  }
-  if (is("fuse_pool") && (value == 0 || value == 1)) {
-    ctx->opt_fuse_pool = value;
-    return PNPX_OK;
-  }
-  if (is("fuse_outc") && (value == 0 || value == 1)) {
-    ctx->opt_fuse_outc = value;
-    return PNPX_OK;
-  }
-  if (is("fuse_first") && (value == 0 || value == 1)) {
-    ctx->opt_fuse_first = value;
-    return PNPX_OK;
-  }
   if (is("policy_s2_hs") && (value == 0 || value == 1)) return PNPX_OK;   // accepted, without effect (include/pnpx.h)
-  if (is("fold_first") && (value == 0 || value == 1)) {
-    ctx->opt_fold_first = value;
-    return PNPX_OK;
-  }
-  if (is("fft_tile") && value >= 0 && value <= 8192) {
-    ctx->opt_fft_tile = value;
-    return PNPX_OK;
-  }
-  if (is("fp32_winograd") && (value == 0 || value == 1)) {
-    ctx->opt_fp32_winograd = value;
-    return PNPX_OK;
-  }
-  if (is("fp32_chains") && value >= 0 && value <= 8) {
-    ctx->opt_fp32_chains = value;
-    return PNPX_OK;
-  }
-  if (is("fp32_fuse_up") && (value == 0 || value == 1)) {
-    ctx->opt_fp32_fuse_up = value;
-    return PNPX_OK;
-  }
-  if (is("fp32_ksplit") && value >= 0 && value <= 2) {
-    ctx->opt_fp32_ksplit = value;
-    return PNPX_OK;
-  }
-  if (is("fp32_ksplit_rule") && value >= 1 && value < 256) {      // tuning: 1 the default rule, else pieces per tile class (conv3x3_wino8_ksplit)
-    ctx->opt_ksplit_rule = value;
-    return PNPX_OK;
-  }
-  if (is("fp32_wino8_layers") && value >= 0 && value < (1 << 27)) {     // bit li: layer li on the 8-wave Winograd kernel
-    ctx->opt_fp32_wino8 = value;
-    return PNPX_OK;
-  }
-  if (is("fp32_winof4_layers") && value >= 0 && value < (1 << 27)) {    // bit li: layer li on the F(4x4,3x3) kernel (forward passes)
-    ctx->opt_fp32_winof4 = value;
-    return PNPX_OK;
-  }
-  if (is("fft_fast") && (value == 0 || value == 1)) {
-    ctx->opt_fft_fast = value;
-    return PNPX_OK;
-  }
-  if (is("fft_affine") && (value == 0 || value == 1)) {
-    ctx->opt_fft_affine = value;
-    return PNPX_OK;
-  }
-  if (is("chains") && value >= 0 && value <= 8) {
-    ctx->opt_chains = value;
-    return PNPX_OK;
-  }
-  if (is("wreg") && value >= 0 && value <= 2) {
-    ctx->opt_wreg = value;
-    return PNPX_OK;
-  }
-  if (is("fuse_up") && (value >= 0 && value <= 2)) {
-    ctx->opt_fuse_up = value;
-    return PNPX_OK;
-  }
   if (is("range_guard") && value >= 0 && value <= 2) {   // also re-arms a tripped guard
     PNPX_HIP(hipDeviceSynchronize());
     ctx->opt_range_guard = value;
@@ -498,27 +465,9 @@ int pnpx_ctx_get_option(pnpx_ctx* ctx, const char* key, int* value) {
     set_error("pnpx_ctx_get_option: null value pointer");
     return PNPX_ERR_ARG;
   }
-  if (is("conv_mode")) *value = ctx->conv_mode;
+  if (const PlainOption* o = plain_option(key)) *value = ctx->*(o->field);
   else if (is("drunet_shift")) *value = ctx->drunet.shift;
-  else if (is("subbatch")) *value = ctx->opt_subbatch;
-  else if (is("fuse_pool")) *value = ctx->opt_fuse_pool;
-  else if (is("fuse_outc")) *value = ctx->opt_fuse_outc;
-  else if (is("fuse_first")) *value = ctx->opt_fuse_first;
-  else if (is("fuse_up")) *value = ctx->opt_fuse_up;
-  else if (is("wreg")) *value = ctx->opt_wreg;
-  else if (is("chains")) *value = ctx->opt_chains;
-  else if (is("fold_first")) *value = ctx->opt_fold_first;
   else if (is("policy_s2_hs")) *value = 1;
-  else if (is("fft_affine")) *value = ctx->opt_fft_affine;
-  else if (is("fft_fast")) *value = ctx->opt_fft_fast;
-  else if (is("fp32_winograd")) *value = ctx->opt_fp32_winograd;
-  else if (is("fp32_wino8_layers")) *value = ctx->opt_fp32_wino8;
-  else if (is("fp32_winof4_layers")) *value = ctx->opt_fp32_winof4;
-  else if (is("fp32_fuse_up")) *value = ctx->opt_fp32_fuse_up;
-  else if (is("fp32_ksplit")) *value = ctx->opt_fp32_ksplit;
-  else if (is("fp32_ksplit_rule")) *value = ctx->opt_ksplit_rule;
-  else if (is("fp32_chains")) *value = ctx->opt_fp32_chains;
-  else if (is("fft_tile")) *value = ctx->opt_fft_tile;
   else if (is("range_guard")) *value = ctx->opt_range_guard;
   else if (is("train_cache_gb")) *value = ctx->opt_train_cache_gb;
   else {
@@ -663,7 +612,7 @@ int pnpx_unet_load(pnpx_ctx* ctx, const float* params_host, size_t n_params) {
     for (int i = 0; i < 27; ++i) {
       u4off[i] = 0;
       const bool plain = (i >= 3 && i <= 11) || i == 16 || i == 17 || i == 19 || i == 20 || i == 22 || i == 23;
-      if (plain && conv3x3_winof4_ok(L[i].cin, 0, L[i].cout, 16, 32)) {
+      if (plain && conv3x3_winof4_packs(L[i].cout, L[i].cin)) {
         align();
         u4off[i] = host.size();
         host.resize(host.size() + conv3x3_winof4_floats(L[i].cout, L[i].cin));

@@ -39,8 +39,6 @@ void pack_conv_weights_1x1(const float* w, int cout, int cin, float* dst);
 // Input-gradient convolution: L holds the transposed, tap-flipped weights (pack_conv_weights_transposed).
 int launch_conv3x3_grad(const ConvLayer& L, const float* gin, float* gout, const float* dmask, int B, int H, int W,
                         hipStream_t s, const char* dmask_hs = nullptr, float mask_slope = 0.2f);   // mask_slope: LeakyReLU' below zero (0 = ReLU)
-// w[cout][cin][3][3] -> packed weights of the adjoint convolution: wt[ci][co][tap] = w[co][ci][8 - tap], with the
-// adjoint's output channels (= cin) zero-padded to cout_pad.
 // Winograd F(2x2, 3x3) variant of the same layer on the fp32 MFMA (conv3x3_wino.hip; option fp32_winograd).  cout a multiple of 64:
 // both sources multiples of 16 channels, H and W multiples of 16; otherwise cout a multiple of 32: sources multiples of 8 channels,
 // H a multiple of 16, W of 32.  u: pack_conv_weights_wino's output.
@@ -76,10 +74,13 @@ int launch_conv3x3_wino8_outc(const float* u, const float* bias, const float* in
 // multiple of 64, >= 16 input channels in multiples of 8, H a multiple of 16, W of 32.  u: pack_conv_weights_winof4's output
 // (conv3x3_winof4_floats(cout, cin) = 36 cout cin floats, 2.25 x the F(2x2) weights).
 bool conv3x3_winof4_ok(int C0, int C1, int cout, int H, int W);
+bool conv3x3_winof4_packs(int cout, int cin);   // the layer can get F(4x4,3x3) weights at load time
 size_t conv3x3_winof4_floats(int cout, int cin);
 void pack_conv_weights_winof4(const float* w, int cout, int cin, float* dst);
 int launch_conv3x3_winof4(const float* u, const float* bias, int cout, const float* in0, int C0, float* out, int B, int H, int W, hipStream_t s,
                           float slope = 0.2f, float* pool_out = nullptr);
+// w[cout][cin][3][3] -> packed weights of the adjoint convolution: wt[ci][co][tap] = w[co][ci][8 - tap], with the
+// adjoint's output channels (= cin) zero-padded to cout_pad.
 void pack_conv_weights_transposed(const float* w, int cout, int cin, int cout_pad, int mt, int cc, float* dst);
 // ... and the same transposition as plain [cout_pad][cout][3][3] weights, for the packers of the other kernel families (the adjoint
 // layers' pack_conv_weights_hs / pack_conv_weights_wino input)

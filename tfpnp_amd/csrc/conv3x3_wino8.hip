@@ -917,7 +917,7 @@ bool conv3x3_wino8_ok(int C0, int C1, int cout, int H, int W) { return wino8_ct(
 
 // r6: which layers CAN split their channel chunks over several work items, and into how many pieces.  A rule of the LAYER'S geometry alone
 // (never of the batch): whenever a layer splits, the summation tree of an output is the same, and per-image results are bit-identical across
-// batch sizes, slices and launch chains among the calls that split (unet.hip decides per call WHETHER the deep levels split: option
+// batch sizes, slices and launch chains among the calls that split (conv_f32_select.hip decides per call WHETHER the deep levels split: option
 // fp32_ksplit).  t = tiles per image: <= 8 (the 16 x 16 level of a 256 x 256 input: one region x 8 cout tiles) -> 4 pieces, <= 16
 // (32 x 32: four regions x 4) -> 2; every piece keeps >= 4 chunks.  At B = 6 this puts 192 instead of 48 / 96 workgroups on the chip
 // (measured per batch size in profiles/r6_ksplit.txt).

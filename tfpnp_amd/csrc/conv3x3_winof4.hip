@@ -347,6 +347,7 @@ __global__ __launch_bounds__(512, 1) void conv3x3_winof4_f32_kernel(WinoArgs a) 
 bool conv3x3_winof4_ok(int C0, int C1, int cout, int H, int W) {
   return C1 == 0 && C0 >= 16 && C0 % 8 == 0 && cout > 0 && cout % 64 == 0 && H >= 16 && H % 16 == 0 && W >= 32 && W % 32 == 0;
 }
+bool conv3x3_winof4_packs(int cout, int cin) { return conv3x3_winof4_ok(cin, 0, cout, 16, 32); }
 size_t conv3x3_winof4_floats(int cout, int cin) { return (size_t)36 * cout * cin; }
 
 // U = G g G^T in double, rounded once; layout [cout / 64][cin / 8][stage 3][row in stage 2][column pair 3][cout block 4][channel group 4]

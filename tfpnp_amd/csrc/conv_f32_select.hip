@@ -1,0 +1,109 @@
+// Kernel selection of the exact-fp32 convolution family (conv_f32_select.h).  Host code only.
+#include "conv_f32_select.h"
+
+namespace pnpx {
+
+ConvF32Sel conv_f32_sel(const pnpx_ctx* ctx, int li) {
+  ConvF32Sel v;
+  v.winograd = ctx->opt_fp32_winograd != 0;
+  v.wino8 = (ctx->opt_fp32_wino8 >> li) & 1;
+  v.winof4 = (ctx->opt_fp32_winof4 >> li) & 1;
+  v.ksplit = ctx->opt_fp32_ksplit;
+  v.ksplit_rule = ctx->opt_ksplit_rule;
+  v.fuse_up = ctx->opt_fp32_fuse_up != 0;
+  v.u = ctx->conv_wino_u[li];
+  v.u_f4 = ctx->conv_winof4_u[li];
+  v.u_bwd = ctx->conv_wino_u_bwd[li];
+  return v;
+}
+
+// The DRUNet's layers are not numbered like the UNet's: any fp32_wino8_layers bit switches the 8-wave kernel on for all of them, and they
+// run neither F(4x4,3x3) nor the K-split.
+ConvF32Sel conv_f32_sel_drunet(const pnpx_ctx* ctx, const float* u, const float* u_bwd) {
+  ConvF32Sel v;
+  v.winograd = ctx->opt_fp32_winograd != 0;
+  v.wino8 = ctx->opt_fp32_wino8 != 0;
+  v.u = u;
+  v.u_bwd = u_bwd;
+  return v;
+}
+
+// Option fp32_ksplit: 0 = never; 1 (default) = the layers whose unsplit tiles cannot fill the chip for THIS call's batch (tiles per image x
+// B_call < 256); 2 = every layer the geometry rule names, at every batch size (per-image results then bit-identical across ALL batch
+// sizes; costs 4 % at 48 x 256^2, where the extra epilogues and the slab round trip buy nothing: profiles/r6_ksplit.txt)
+static bool ksplit_on(const ConvF32Sel& v, int cout, int H, int W, int B_call) {
+  if (v.ksplit == 2) return true;
+  return v.ksplit == 1 && (long long)(H / 16) * (W / 16) * (cout / 64) * B_call < 256;
+}
+
+ConvF32Choice conv_f32_forward(const ConvF32Sel& v, int C0, int C1, int cout, int H, int W, int B_call) {
+  ConvF32Choice c;
+  if (!v.winograd || !v.u || !conv3x3_wino_ok(C0, C1, cout, H, W)) return c;
+  c.fused = true;      // all three Winograd kernels write the pooled tensor too (one 2x2 output tile = one lane's four values)
+  c.kernel = ConvF32Kernel::Wino4;
+  if (!v.wino8 || !conv3x3_wino8_ok(C0, C1, cout, H, W)) return c;
+  c.kernel = ConvF32Kernel::Wino8;
+  if (ksplit_on(v, cout, H, W, B_call)) c.pieces = conv3x3_wino8_ksplit(C0, C1, cout, H, W, v.ksplit_rule);
+  // F(4x4,3x3): plain single-source layers whose bit is set in both masks and that the K-split does not claim in this call.  Training
+  // forwards take the same kernel as inference forwards: a solver's composed (differentiable) forward and its fused one then agree as
+  // closely as before (tests/test_gpu_amp.py holds them to 1e-5 through the Onsager term, which amplifies a layer-level 7e-7 difference
+  // past that bar); the backward pass keeps the F(2x2) adjoint kernels.
+  if (c.pieces == 1 && v.winof4 && v.u_f4 && C1 == 0 && conv3x3_winof4_ok(C0, 0, cout, H, W)) c.kernel = ConvF32Kernel::WinoF4;
+  return c;
+}
+
+// A decoder entry that the K-split takes in this call (the 32 x 32 level's 768 -> 256 entry when the call cannot fill the chip: its
+// 48-chunk tiles are the longest of the forward) runs UNFUSED -- the separate up-sampling kernel + the plain two-source instance, which
+// splits; the fused instance's interpolation pipeline assumes a tile starts in its first, full-resolution source.  (The two forms agree to
+// 2-5e-7; like the K-split itself this is a property of the call's class, not of the batch.)
+ConvF32Choice conv_f32_entry(const ConvF32Sel& v, int C0, int C1, int cout, int H, int W, int B_call) {
+  ConvF32Choice c = conv_f32_forward(v, C0, C1, cout, H, W, B_call);
+  c.fused = c.kernel == ConvF32Kernel::Wino8 && c.pieces == 1 && v.fuse_up && conv3x3_wino8_ups_ok(C0, C1, cout, H, W);
+  return c;
+}
+
+ConvF32Choice conv_f32_last(const ConvF32Sel& v, int cin, int cout, int H, int W, int B_call) {
+  ConvF32Choice c = conv_f32_forward(v, cin, 0, cout, H, W, B_call);
+  c.fused = false;
+  if (v.winograd && v.u && conv3x3_wino_outc_ok(cin, cout, H, W)) {      // 32 output channels: no K-split, no F(4x4,3x3)
+    c.fused = true;
+    c.kernel = v.wino8 && conv3x3_wino8_ok(cin, 0, cout, H, W) ? ConvF32Kernel::Wino8 : ConvF32Kernel::Wino4;
+  }
+  return c;
+}
+
+ConvF32Choice conv_f32_adjoint(const ConvF32Sel& v, int cin, int cout, int H, int W) {
+  ConvF32Choice c;
+  if (v.winograd && v.wino8 && v.u_bwd && conv3x3_wino8_ok(cin, 0, cout, H, W)) c.kernel = ConvF32Kernel::Wino8;
+  return c;
+}
+
+// The fork's slices are 8-wave launches, so the three layers are decided with their F(4x4,3x3) weights withheld.
+bool conv_f32_bottom_all8(const pnpx_ctx* ctx, int H, int W, int B_call, ConvF32Sel v[3], ConvF32Choice c[3]) {
+  bool all8 = true;
+  for (int k = 0; k < 3; ++k) {
+    const ConvLayer& L = ctx->conv[12 + k];
+    v[k] = conv_f32_sel(ctx, 12 + k);
+    v[k].u_f4 = nullptr;
+    c[k] = conv_f32_forward(v[k], L.cin, 0, L.cout, H, W, B_call);
+    all8 = all8 && c[k].kernel == ConvF32Kernel::Wino8;
+  }
+  return all8;
+}
+
+int launch_conv_f32(const ConvF32Choice& c, const ConvF32Sel& v, const ConvLayer& L, const ConvF32Operands& a, hipStream_t s) {
+  switch (c.kernel) {
+    case ConvF32Kernel::WinoF4:      // single source, no residual operand
+      return launch_conv3x3_winof4(v.u_f4, L.b, L.cout, a.in0, a.C0, a.out, a.B, a.H, a.W, s, a.slope, a.pool_out);
+    case ConvF32Kernel::Wino8:
+      return launch_conv3x3_wino8(v.u, L.b, L.cout, a.in0, a.C0, a.in1, a.C1, a.out, a.B, a.H, a.W, s, a.slope, a.res, a.pool_out,
+                                  c.pieces > 1 ? a.ks_part : nullptr, v.ksplit_rule);
+    case ConvF32Kernel::Wino4:
+      return launch_conv3x3_wino(v.u, L.b, L.cout, a.in0, a.C0, a.in1, a.C1, a.out, a.B, a.H, a.W, s, a.slope, a.res, a.pool_out);
+    case ConvF32Kernel::Direct:
+      break;
+  }
+  return launch_conv3x3_act(L, a.in0, a.C0, a.in1, a.C1, a.out, a.B, a.H, a.W, a.slope, a.res, s);
+}
+
+}  // namespace pnpx

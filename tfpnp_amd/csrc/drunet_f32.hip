@@ -19,7 +19,7 @@
 #include <vector>
 
 #include "common.h"
-#include "conv3x3.h"
+#include "conv_f32_select.h"
 #include "conv_first.h"
 #include "grad_common.h"
 
@@ -411,17 +411,12 @@ int drunet_denoise_f32(pnpx_ctx* ctx, const float* x, const float* sigma, int si
   // layer li: `in` -> `outp` at h x w, negative slope (0 ReLU / 1 linear), optional residual
   auto conv = [&](const float* in, float* outp, int h, int w, float slope, const float* res) -> int {
     const ConvLayer& Lc = N.f32_layers[li];
-    const float* u = N.f32_wino[li];
+    const ConvF32Sel v = conv_f32_sel_drunet(ctx, N.f32_wino[li], nullptr);
     const int kind = L[li].kind;
     ++li;
     if (kind == 3 || kind == 4) return launch_conv1x1_act(Lc, in, outp, B, h, w, slope, res, s);
-    if (u && ctx->opt_fp32_winograd && conv3x3_wino_ok(Lc.cin, 0, Lc.cout, h, w))
-    {
-      if (ctx->opt_fp32_wino8 && conv3x3_wino8_ok(Lc.cin, 0, Lc.cout, h, w))
-        return launch_conv3x3_wino8(u, Lc.b, Lc.cout, in, Lc.cin, nullptr, 0, outp, B, h, w, s, slope, res, nullptr);
-      return launch_conv3x3_wino(u, Lc.b, Lc.cout, in, Lc.cin, nullptr, 0, outp, B, h, w, s, slope, res, nullptr);
-    }
-    return launch_conv3x3_act(Lc, in, Lc.cin, nullptr, 0, outp, B, h, w, slope, res, s);
+    ConvF32Operands a{in, Lc.cin, nullptr, 0, outp, B, h, w, slope, res};
+    return launch_conv_f32(conv_f32_forward(v, Lc.cin, 0, Lc.cout, h, w, B), v, Lc, a, s);
   };
   auto resblocks = [&](int l, int dec, float* cur, float** result) -> int {
     const int h = H >> l, w = W >> l;
@@ -537,13 +532,16 @@ int drunet_denoise_backward_f32(pnpx_ctx* ctx, const float* x, const float* sigm
     const ConvLayer& Lc = N.f32_layers_bwd[li];
     const int kind = L[li].kind;
     if (kind == 3 || kind == 4) return launch_conv1x1_act(Lc, in, outp, B, h, w, 1.f, res, s);
+    // the adjoint layer is a packed layer of its own: its Winograd weights serve the decision (u_bwd) and the launch helper (u)
     const float* u = N.f32_wino_bwd[li];
-    if (u && ctx->opt_fp32_winograd && ctx->opt_fp32_wino8 && conv3x3_wino8_ok(Lc.cin, 0, Lc.cout, h, w)) {
-      if (dmask) return launch_conv3x3_wino8_grad(u, Lc.b, Lc.cout, in, Lc.cin, outp, dmask, 0.f, B, h, w, s);
-      return launch_conv3x3_wino8(u, Lc.b, Lc.cout, in, Lc.cin, nullptr, 0, outp, B, h, w, s, 1.f, res, nullptr);
+    const ConvF32Sel v = conv_f32_sel_drunet(ctx, u, u);
+    const ConvF32Choice c = conv_f32_adjoint(v, Lc.cin, Lc.cout, h, w);
+    if (!dmask) {      // linear, + res
+      ConvF32Operands a{in, Lc.cin, nullptr, 0, outp, B, h, w, 1.f, res};
+      return launch_conv_f32(c, v, Lc, a, s);
     }
-    if (dmask) return launch_conv3x3_grad(Lc, in, outp, dmask, B, h, w, s, nullptr, 0.f);
-    return launch_conv3x3_act(Lc, in, Lc.cin, nullptr, 0, outp, B, h, w, 1.f, res, s);
+    if (c.wino()) return launch_conv3x3_wino8_grad(u, Lc.b, Lc.cout, in, Lc.cin, outp, dmask, 0.f, B, h, w, s);
+    return launch_conv3x3_grad(Lc, in, outp, dmask, B, h, w, s, nullptr, 0.f);
   };
   auto resblocks_bwd = [&](int l, int dec, int idx0, float* cur, float** result) -> int {
     const int h = H >> l, w = W >> l;

@@ -10,7 +10,7 @@
 #include <cstdlib>
 
 #include "common.h"
-#include "conv3x3.h"
+#include "conv_f32_select.h"
 #include "conv_hs.h"
 #include "conv_first.h"
 #include "hs_rec.h"
@@ -612,15 +612,8 @@ static int unet_forward_f32(pnpx_ctx* ctx, UNetArena& ar, const UNetPlan& P, con
   // ---- plain-fp32 path (conv_mode 0): padded planar fp32 activations, whole batch per launch
   char* A = static_cast<char*>(ar.buf.p);
   auto fptr = [&](const Act& d) { return reinterpret_cast<float*>(A + d.off + (size_t)b_base * act_bytes_per_image(CONV_F32, d.C, d.H, d.W)); };
-  // r6: scratch of the K-split launches (this slice's images).  Option fp32_ksplit: 0 = never; 1 (default) = the layers whose unsplit
-  // tiles cannot fill the chip for THIS call's batch (tiles per image x B_call < 256: launch chains beside each other count as one call);
-  // 2 = every layer the geometry rule names, at every batch size (per-image results then bit-identical across ALL batch sizes; costs
-  // 4 % at 48 x 256^2, where the extra epilogues and the slab round trip buy nothing: profiles/r6_ksplit.txt)
+  // r6: scratch of the K-split launches (this slice's images; conv_f32_select.hip decides per call which layers split)
   float* const ks_part0 = reinterpret_cast<float*>(A + P.ks_part + (size_t)b_base * P.ks_part_per_image);
-  auto ks_on = [&](int cout, int h, int w) {
-    if (ctx->opt_fp32_ksplit == 2) return true;
-    return ctx->opt_fp32_ksplit == 1 && (long long)(h / 16) * (w / 16) * (cout / 64) * B_call < 256;
-  };
   // the first convolution (2 -> 32 channels) straight from the fp32 image on the vector ALU (training forwards too: the VJP needs the
   // layer's output, not its padded input tensor)
   const bool first_valu = ctx->opt_fuse_first && W % 4 == 0 && ctx->conv[0].cout == 32;
@@ -635,32 +628,15 @@ static int unet_forward_f32(pnpx_ctx* ctx, UNetArena& ar, const UNetPlan& P, con
   auto conv = [&](int li, const Act& i0, const Act* i1, const Act& o, const Act* pooled = nullptr, bool* pooled_done = nullptr) -> int {
     const ConvLayer& L = ctx->conv[li];
     const int C1 = i1 ? i1->C : 0;
-    if (pooled_done) *pooled_done = false;
-    if (ctx->opt_fp32_winograd && ctx->conv_wino_u[li] && conv3x3_wino_ok(i0.C, C1, L.cout, o.H, o.W)) {
-      const bool w8 = ((ctx->opt_fp32_wino8 >> li) & 1) && conv3x3_wino8_ok(i0.C, C1, L.cout, o.H, o.W);
-      // F(4x4,3x3) (conv3x3_winof4.hip): plain single-source layers whose bit is set in both masks and that the K-split does not claim in
-      // this call.  Training forwards (keep_all) take the same kernel as inference forwards: a solver's composed (differentiable) forward
-      // and its fused one then agree as closely as before (tests/test_gpu_amp.py holds them to 1e-5 through the Onsager term, which
-      // amplifies a layer-level 7e-7 difference past that bar); the backward pass keeps the F(2x2) adjoint kernels.
-      const bool f4 = w8 && ((ctx->opt_fp32_winof4 >> li) & 1) && ctx->conv_winof4_u[li] && !i1 &&
-                      conv3x3_winof4_ok(i0.C, 0, L.cout, o.H, o.W) &&
-                      !(ks_on(L.cout, o.H, o.W) && conv3x3_wino8_ksplit(i0.C, 0, L.cout, o.H, o.W, ctx->opt_ksplit_rule) > 1);
-      if (f4) {
-        PNPX_TRY(launch_conv3x3_winof4(ctx->conv_winof4_u[li], L.b, L.cout, fptr(i0), i0.C, fptr(o), B, o.H, o.W, s, 0.2f, pooled ? fptr(*pooled) : nullptr));
-      } else if (w8) {
-        const bool ks = ks_on(L.cout, o.H, o.W);
-        PNPX_TRY(launch_conv3x3_wino8(ctx->conv_wino_u[li], L.b, L.cout, fptr(i0), i0.C, i1 ? fptr(*i1) : nullptr, C1, fptr(o), B, o.H, o.W, s, 0.2f,
-                                      nullptr, pooled ? fptr(*pooled) : nullptr, ks ? ks_part0 : nullptr, ctx->opt_ksplit_rule));
-      }
-      else
-        PNPX_TRY(launch_conv3x3_wino(ctx->conv_wino_u[li], L.b, L.cout, fptr(i0), i0.C, i1 ? fptr(*i1) : nullptr, C1, fptr(o), B, o.H, o.W, s, 0.2f,
-                                     nullptr, pooled ? fptr(*pooled) : nullptr));
-      if (pooled_done) *pooled_done = pooled != nullptr;
-      return rec.mark("conv3x3_wino", 2.0 * 9.0 * L.cin * L.cout * (double)o.H * o.W * B);   // algorithmic FLOPs; 4/9 of them executed (F(4x4): 1/4)
-    } else {
-      PNPX_TRY(launch_conv3x3(L, fptr(i0), i0.C, i1 ? fptr(*i1) : nullptr, C1, fptr(o), B, o.H, o.W, s));
-    }
-    return rec.mark("conv3x3", 2.0 * 9.0 * L.cin * L.cout * (double)o.H * o.W * B);
+    const ConvF32Sel v = conv_f32_sel(ctx, li);
+    const ConvF32Choice c = conv_f32_forward(v, i0.C, C1, L.cout, o.H, o.W, B_call);
+    ConvF32Operands a{fptr(i0), i0.C, i1 ? fptr(*i1) : nullptr, C1, fptr(o), B, o.H, o.W};
+    a.pool_out = pooled ? fptr(*pooled) : nullptr;
+    a.ks_part = ks_part0;
+    PNPX_TRY(launch_conv_f32(c, v, L, a, s));
+    if (pooled_done) *pooled_done = pooled && c.fused;
+    // algorithmic FLOPs; the Winograd kernels execute 4/9 of them (F(4x4): 1/4)
+    return rec.mark(c.wino() ? "conv3x3_wino" : "conv3x3", 2.0 * 9.0 * L.cin * L.cout * (double)o.H * o.W * B);
   };
   auto block = [&](int li, const Act& i0, const Act* i1, int lvl, const Act& o, const Act* pooled = nullptr, bool* pooled_done = nullptr) -> int {
     const Act& ta = i1 ? P.da[lvl] : P.a[lvl];
@@ -691,18 +667,17 @@ static int unet_forward_f32(pnpx_ctx* ctx, UNetArena& ar, const UNetPlan& P, con
     // not depend on the slicing (same kernel, independent tiles).
     if (l == 4 && level_chains && B >= 2) {
       const Act& o4 = P.x[4];
-      bool all8 = ctx->opt_fp32_winograd != 0;
-      for (int li = 12; li < 15; ++li)
-        all8 = all8 && ctx->conv_wino_u[li] && ((ctx->opt_fp32_wino8 >> li) & 1) && conv3x3_wino8_ok(ctx->conv[li].cin, 0, ctx->conv[li].cout, o4.H, o4.W);
+      ConvF32Sel v4[3];
+      ConvF32Choice c4[3];
+      const bool all8 = conv_f32_bottom_all8(ctx, o4.H, o4.W, B_call, v4, c4);
       const long long ntiles = (long long)(o4.H / 16) * (o4.W / 16) * B * (ctx->conv[13].cout / 64);
       if (all8 && ntiles > 256 && ntiles < 768 && ntiles % 256 != 0) {
         PNPX_TRY(fan_out_chains(ctx, 2, B, s, [&](int lo, int hi, hipStream_t st) -> int {
           auto slice = [&](int li, const Act& i, const Act& o) -> int {
-            const ConvLayer& L = ctx->conv[li];
-            return launch_conv3x3_wino8(ctx->conv_wino_u[li], L.b, L.cout, fptr(i) + (size_t)lo * i.C * padded_h(i.H) * padded_w(i.W), i.C, nullptr, 0,
-                                        fptr(o) + (size_t)lo * o.C * padded_h(o.H) * padded_w(o.W), hi - lo, o.H, o.W, st, 0.2f, nullptr, nullptr,
-                                        ks_on(o.C, o.H, o.W) ? ks_part0 + (size_t)lo * (P.ks_part_per_image / sizeof(float)) : nullptr,
-                                        ctx->opt_ksplit_rule);
+            ConvF32Operands a{fptr(i) + (size_t)lo * i.C * padded_h(i.H) * padded_w(i.W), i.C, nullptr, 0,
+                              fptr(o) + (size_t)lo * o.C * padded_h(o.H) * padded_w(o.W), hi - lo, o.H, o.W};
+            a.ks_part = ks_part0 + (size_t)lo * (P.ks_part_per_image / sizeof(float));
+            return launch_conv_f32(c4[li - 12], v4[li - 12], ctx->conv[li], a, st);
           };
           PNPX_TRY(slice(12, P.p[4], P.a[4]));
           PNPX_TRY(slice(13, P.a[4], P.b[4]));
@@ -714,6 +689,7 @@ static int unet_forward_f32(pnpx_ctx* ctx, UNetArena& ar, const UNetPlan& P, con
     }
     PNPX_TRY(block(3 * l, P.p[l], nullptr, l, P.x[l], l < 4 ? &P.p[l + 1] : nullptr, &pooled));
   }
+  const ConvF32Choice c26 = conv_f32_last(conv_f32_sel(ctx, 26), ctx->conv[26].cin, ctx->conv[26].cout, H, W, B_call);
   const Act* below = &P.x[4];
   for (int l = 3; l >= 0; --l) {
     const int h = below->H, w = below->W;
@@ -724,14 +700,10 @@ static int unet_forward_f32(pnpx_ctx* ctx, UNetArena& ar, const UNetPlan& P, con
     // chunk's halo staged in LDS, bilinear x2 into the halo buffer) -- no up-sampled tensor in HBM (models/unet.py:92-121)
     const int li0 = 15 + 3 * (3 - l);
     // (training forwards too: the VJP of the up-sampling is linear in the gradient and reads no up-sampled activation)
-    // r6: a decoder entry that the K-split would take in this call (the 32 x 32 level's 768 -> 256 entry when the call cannot fill the chip:
-    // its 48-chunk tiles are the longest of the forward) runs UNFUSED -- the separate up-sampling kernel + the plain two-source instance,
-    // which splits; the fused instance's interpolation pipeline assumes a tile starts in its first, full-resolution source.  (The two
-    // forms agree to 2-5e-7; like the K-split itself this is a property of the call's class, not of the batch.)
-    const bool entry_splits = ks_on(ctx->conv[li0].cout, 2 * h, 2 * w) &&
-                              conv3x3_wino8_ksplit(P.x[l].C, below->C, ctx->conv[li0].cout, 2 * h, 2 * w, ctx->opt_ksplit_rule) > 1;
-    const bool ups_fused = !entry_splits && ctx->opt_fp32_fuse_up && ctx->opt_fp32_winograd && ctx->conv_wino_u[li0] && ((ctx->opt_fp32_wino8 >> li0) & 1) &&
-                           P.x[l].H == 2 * h && P.x[l].W == 2 * w && conv3x3_wino8_ups_ok(P.x[l].C, below->C, ctx->conv[li0].cout, 2 * h, 2 * w);
+    // (odd sizes: the up-sampled 2h x 2w image sits inside a larger tensor -- separate kernel)
+    const ConvF32Sel v0 = conv_f32_sel(ctx, li0);
+    const bool ups_fused = P.x[l].H == 2 * h && P.x[l].W == 2 * w &&
+                           conv_f32_entry(v0, P.x[l].C, below->C, ctx->conv[li0].cout, 2 * h, 2 * w, B_call).fused;
     if (ups_fused) {
       // nothing to launch
     } else if ((2 * w) % 4 == 0 && (size_t)B * below->C <= 65535) {
@@ -755,14 +727,11 @@ static int unet_forward_f32(pnpx_ctx* ctx, UNetArena& ar, const UNetPlan& P, con
     };
     // the network's last 3x3 layer takes the 1x1 out-conv + residual + clamp into its epilogue when the Winograd kernel runs it
     // (inference passes only: a training forward keeps the layer's output for the VJP)
-    const bool fuse_outc = l == 0 && !keep_all && ctx->opt_fuse_outc && ctx->opt_fp32_winograd && ctx->conv_wino_u[26] &&
-                           conv3x3_wino_outc_ok(ctx->conv[26].cin, ctx->conv[26].cout, H, W);
-    if (fuse_outc) {
+    if (l == 0 && !keep_all && ctx->opt_fuse_outc && c26.fused) {
       PNPX_TRY(entry(P.da[0]));
       PNPX_TRY(conv(25, P.da[0], nullptr, P.db[0]));
-      const bool w8 = ((ctx->opt_fp32_wino8 >> 26) & 1) && conv3x3_wino8_ok(ctx->conv[26].cin, 0, ctx->conv[26].cout, H, W);
-      PNPX_TRY((w8 ? launch_conv3x3_wino8_outc : launch_conv3x3_wino_outc)(ctx->conv_wino_u[26], ctx->conv[26].b, fptr(P.db[0]), ctx->conv[26].cin,
-                                                                          ctx->outc_w, ctx->outc_b, x, out, out_pre, B, H, W, s));
+      PNPX_TRY((c26.kernel == ConvF32Kernel::Wino8 ? launch_conv3x3_wino8_outc : launch_conv3x3_wino_outc)(
+          ctx->conv_wino_u[26], ctx->conv[26].b, fptr(P.db[0]), ctx->conv[26].cin, ctx->outc_w, ctx->outc_b, x, out, out_pre, B, H, W, s));
       return rec.mark("conv3x3_wino", 2.0 * 9.0 * ctx->conv[26].cin * ctx->conv[26].cout * (double)H * W * B);
     }
     PNPX_TRY(entry(P.da[l]));

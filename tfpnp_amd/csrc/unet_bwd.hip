@@ -11,7 +11,7 @@
 // layout, so every input-gradient convolution is the SAME MFMA kernel run on transposed, tap-flipped weights
 // (pack_conv_weights_transposed) with the LeakyReLU derivative of the saved activation fused in its epilogue.
 #include "common.h"
-#include "conv3x3.h"
+#include "conv_f32_select.h"
 #include "conv_hs.h"
 #include "hs_rec.h"
 #include "unet_plan.h"
@@ -659,8 +659,7 @@ int unet_denoise_backward(pnpx_ctx* ctx, const float* x, const float* sigma, int
     const float* dm = saved ? reinterpret_cast<const float*>(FA + saved->off + (size_t)lo * act_bytes_per_image(fmode, saved->C, saved->H, saved->W)) : nullptr;
     const char* dmh = nullptr;
     // r5: Winograd F(2x2,3x3) for the adjoint convolutions too (8-wave kernel, LeakyReLU' mask in its epilogue)
-    if (!hs && ctx->opt_fp32_winograd && ((ctx->opt_fp32_wino8 >> li) & 1) && ctx->conv_wino_u_bwd[li] && gout.C == ctx->conv_bwd[li].cout &&
-        conv3x3_wino8_ok(gin.C, 0, gout.C, gout.H, gout.W))
+    if (!hs && gout.C == ctx->conv_bwd[li].cout && conv_f32_adjoint(conv_f32_sel(ctx, li), gin.C, gout.C, gout.H, gout.W).wino())
       return launch_conv3x3_wino8_grad(ctx->conv_wino_u_bwd[li], ctx->zero_bias, gout.C, gp(gin), gin.C, gp(gout), dm, 0.2f, B, gout.H, gout.W, s);
     return launch_conv3x3_grad(ctx->conv_bwd[li], gp(gin), gp(gout), dm, B, gout.H, gout.W, s, dmh);
   };
