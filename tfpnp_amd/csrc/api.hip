@@ -412,6 +412,7 @@ const PlainOption PLAIN_OPTIONS[] = {
     {"fp32_ksplit_rule", &pnpx_ctx::opt_ksplit_rule, 1, 255},      // tuning: 1 the default rule, else pieces per tile class (conv3x3_wino8_ksplit)
     {"fp32_wino8_layers", &pnpx_ctx::opt_fp32_wino8, 0, (1 << 27) - 1},      // bit li: layer li on the 8-wave Winograd kernel
     {"fp32_winof4_layers", &pnpx_ctx::opt_fp32_winof4, 0, (1 << 27) - 1},    // bit li: layer li on the F(4x4,3x3) kernel (forward passes)
+    {"fp32_winof4_entries", &pnpx_ctx::opt_fp32_winof4_entries, 0, (1 << 27) - 1},      // bits 15, 18, 21: that decoder entry on it
 };
 const PlainOption* plain_option(const char* key) {
   for (const PlainOption& o : PLAIN_OPTIONS)
@@ -605,14 +606,16 @@ int pnpx_unet_load(pnpx_ctx* ctx, const float* params_host, size_t n_params) {
   }
   // ... and the same adjoint convolutions for the half-split kernel family (backward pass of conv_mode 1)
   // Winograd F(4x4,3x3) weights (conv3x3_winof4.hip) for the layers that can be eligible: the plain single-source 64-cout-tile layers of
-  // levels 1-3 (2.25 x the F(2x2) bytes, so not for the 16 x 16 level, whose layers the kernel is not used on)
+  // levels 1-3 (2.25 x the F(2x2) bytes, so not for the 16 x 16 level, whose layers the kernel is not used on) and the decoder entries
+  // of the same levels (15, 18, 21: packed over both sources' channels; 28 MB for layer 15)
   size_t u4off[27];
   {
     const float* wsrc = params_host;
     for (int i = 0; i < 27; ++i) {
       u4off[i] = 0;
       const bool plain = (i >= 3 && i <= 11) || i == 16 || i == 17 || i == 19 || i == 20 || i == 22 || i == 23;
-      if (plain && conv3x3_winof4_packs(L[i].cout, L[i].cin)) {
+      const bool entry = i == 15 || i == 18 || i == 21;
+      if ((plain || entry) && conv3x3_winof4_packs(L[i].cout, L[i].cin)) {
         align();
         u4off[i] = host.size();
         host.resize(host.size() + conv3x3_winof4_floats(L[i].cout, L[i].cin));

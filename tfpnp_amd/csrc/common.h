@@ -257,11 +257,14 @@ struct pnpx_ctx {
   int opt_fp32_winograd = 1;       // conv_mode 0: run those layers as F(2x2,3x3) (fp32 arithmetic, 2.25x fewer MFMAs; 0 = the direct kernel everywhere)
   int opt_fp32_wino8 = (1 << 27) - 1;   // bit li: layer li runs on the 8-wave Winograd kernel (conv3x3_wino8.hip) where its geometry allows; a DRUNet
                                    // context: any bit = its ResBlock layers do
-  float* conv_winof4_u[27] = {};   // Winograd F(4x4,3x3) weights of the layers conv3x3_winof4.hip can run in the UNet (levels 1-3, plain 64-cout layers; else null)
+  float* conv_winof4_u[27] = {};   // Winograd F(4x4,3x3) weights of the layers conv3x3_winof4.hip can run in the UNet (levels 1-3: plain 64-cout layers and the decoder entries; else null)
   // bit li: layer li runs on the F(4x4,3x3) kernel in forward passes, where its geometry allows, its fp32_wino8_layers bit is set and
   // the K-split does not claim it.  Default: the plain 64-cout-tile layers of levels 1-3 (3-11, 16, 17, 19, 20, 22, 23), every one of
   // which measured faster than on the F(2x2) kernel at 48 x 256^2 (profiles/winof4.md; drift table profiles/winof4_probe.md)
   int opt_fp32_winof4 = (0x1ff << 3) | (3 << 16) | (3 << 19) | (3 << 22);
+  // bits 15, 18, 21: that decoder entry (768 -> 256, 384 -> 128, 192 -> 64) runs on the F(4x4,3x3) kernel's two-source instance, behind
+  // the separate up-sampling kernel, where the fused F(2x2) instance would run it in one piece (profiles/winof4_entries.md)
+  int opt_fp32_winof4_entries = (1 << 15) | (1 << 18) | (1 << 21);
   int opt_fp32_chains = 2;         // conv_mode 0: n >= 2 = the forward as n launch chains over slices of the batch (default 2: this family is not
                                    // power-capped, a second chain fills the other's tails and partial rounds: 8.76 -> 8.44 ms at 48 x 256^2, -7 % at
                                    // B = 24; 3 and 4 chains measured slower); 1 = only the bottom level forks two chains; 0 = one chain

@@ -74,11 +74,14 @@ int launch_conv3x3_wino8_outc(const float* u, const float* bias, const float* in
 // multiple of 64, >= 16 input channels in multiples of 8, H a multiple of 16, W of 32.  u: pack_conv_weights_winof4's output
 // (conv3x3_winof4_floats(cout, cin) = 36 cout cin floats, 2.25 x the F(2x2) weights).
 bool conv3x3_winof4_ok(int C0, int C1, int cout, int H, int W);
+// ... and its two-source instance (the UNet's decoder entries on an up-sampled second source; option fp32_winof4_entries): the same rules
+// on cout, H and W, both sources whole 8-channel chunks and at least one chunk each.  C1 = 0 launches the single-source instance.
+bool conv3x3_winof4_entry_ok(int C0, int C1, int cout, int H, int W);
 bool conv3x3_winof4_packs(int cout, int cin);   // the layer can get F(4x4,3x3) weights at load time
 size_t conv3x3_winof4_floats(int cout, int cin);
 void pack_conv_weights_winof4(const float* w, int cout, int cin, float* dst);
-int launch_conv3x3_winof4(const float* u, const float* bias, int cout, const float* in0, int C0, float* out, int B, int H, int W, hipStream_t s,
-                          float slope = 0.2f, float* pool_out = nullptr);
+int launch_conv3x3_winof4(const float* u, const float* bias, int cout, const float* in0, int C0, const float* in1, int C1, float* out, int B,
+                          int H, int W, hipStream_t s, float slope = 0.2f, float* pool_out = nullptr);
 // w[cout][cin][3][3] -> packed weights of the adjoint convolution: wt[ci][co][tap] = w[co][ci][8 - tap], with the
 // adjoint's output channels (= cin) zero-padded to cout_pad.
 void pack_conv_weights_transposed(const float* w, int cout, int cin, int cout_pad, int mt, int cc, float* dst);

@@ -1,6 +1,7 @@
 // Winograd F(4x4, 3x3) on the exact-fp32 MFMA v_mfma_f32_16x16x4_f32: 36 products per 16 outputs instead of F(2x2)'s 16 per 4
-// = 0.5625 x the MFMAs of conv3x3_wino8.hip.  Plain 64-cout layers of the UNet's forward passes only (option fp32_winof4_layers;
-// no second source, no residual, no K-split, no fused up-sampling or out-conv).  Same activation layout (padded planar fp32), WinoArgs,
+// = 0.5625 x the MFMAs of conv3x3_wino8.hip.  64-cout-tile layers of the UNet's forward passes only: the plain single-source layers
+// (option fp32_winof4_layers) and, as a second instance, the two-source decoder entries on an already up-sampled second source (option
+// fp32_winof4_entries); no residual, no K-split, no fused up-sampling or out-conv.  Same activation layout (padded planar fp32), WinoArgs,
 // bias + LeakyReLU as max(y, slope y) and optional fused 2x2 max-pool as the F(2x2) kernels.
 //
 // Points (0, +-1, +-1/2, inf), rows scaled as tools/wino_f4_probe.py's cook_toom does (winof4_mats.h holds the matrices the packer uses;
@@ -79,6 +80,9 @@ __device__ __forceinline__ void at_rows(float m0, float m1, float m2, float m3, 
   o3 = fmaf(0.125f, m34, m12) + m5;
 }
 
+// TWO: the channel chunks C0 / 8 .. of a tile come from in1 (C1 channels, same geometry as in0); the weights are packed over C0 + C1 and
+// a.nch counts both sources' chunks.  A chunk lies in one source (C0 % 8 == 0), so only its halo origin differs.
+template <bool TWO>
 __global__ __launch_bounds__(512, 1) void conv3x3_winof4_f32_kernel(WinoArgs a) {
   using C = CfgF4;
   constexpr int CK = C::CK, RWL = C::RWL, RPXL = C::RPXL, RAW_BYTES = C::RAW_BYTES, RAW_PER_WAVE = C::RAW_PER_WAVE;
@@ -96,6 +100,7 @@ __global__ __launch_bounds__(512, 1) void conv3x3_winof4_f32_kernel(WinoArgs a) 
 
   struct Tile {
     const float* s0;   // halo origin in channel 0
+    const float* s1;   // ... of the second source (TWO)
     const float* w;    // weights of the cout tile
     int ct, b, x0, y0, ok, pad_;
   };
@@ -115,10 +120,15 @@ __global__ __launch_bounds__(512, 1) void conv3x3_winof4_f32_kernel(WinoArgs a) 
     T.x0 = tx * 32;
     T.y0 = ty * 16;
     T.s0 = a.in0 + (size_t)T.b * a.C0 * HpWp + (size_t)T.y0 * a.Wp + T.x0 + (PADL - 1);
+    T.s1 = TWO ? a.in1 + (size_t)T.b * a.C1 * HpWp + (size_t)T.y0 * a.Wp + T.x0 + (PADL - 1) : nullptr;
     T.w = a.u + (size_t)T.ct * a.nch * 3 * UQ;
     return T;
   };
-  auto raw_of = [&](const Tile& X, int c) { return X.s0 + (size_t)CK * c * HpWp; };
+  const int nch0 = a.C0 / CK;      // chunks of the first source
+  auto raw_of = [&](const Tile& X, int c) {
+    if (TWO && c >= nch0) return X.s1 + (size_t)CK * (c - nch0) * HpWp;
+    return X.s0 + (size_t)CK * c * HpWp;
+  };
 
   auto sync_all = [&]() {
     asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
@@ -306,7 +316,7 @@ __global__ __launch_bounds__(512, 1) void conv3x3_winof4_f32_kernel(WinoArgs a) 
   dma_raw(T.s0, 0);
   dma_u(T.w, 0);
   dma_u(T.w + UQ, 1);
-  dma_raw(raw_of(T, 1), 1);      // (nch >= 2: chunk 1 exists)
+  dma_raw(raw_of(T, 1), 1);      // (nch >= 2: chunk 1 exists; chunk 0 lies in the first source)
   sync_all();
   transform_row(I0{}, 0);
   sync_all();
@@ -347,6 +357,11 @@ __global__ __launch_bounds__(512, 1) void conv3x3_winof4_f32_kernel(WinoArgs a) 
 bool conv3x3_winof4_ok(int C0, int C1, int cout, int H, int W) {
   return C1 == 0 && C0 >= 16 && C0 % 8 == 0 && cout > 0 && cout % 64 == 0 && H >= 16 && H % 16 == 0 && W >= 32 && W % 32 == 0;
 }
+// Decoder entry: C0 channels of in0 and C1 of in1, whole chunks of each.  The pipeline needs ONE chunk of the first source (the prologue
+// fetches chunk 0 from it) and two chunks in all; C0 = 0 is refused.
+bool conv3x3_winof4_entry_ok(int C0, int C1, int cout, int H, int W) {
+  return conv3x3_winof4_ok(16, 0, cout, H, W) && H % 2 == 0 && W % 2 == 0 && C0 >= 8 && C0 % 8 == 0 && C1 >= 8 && C1 % 8 == 0;
+}
 bool conv3x3_winof4_packs(int cout, int cin) { return conv3x3_winof4_ok(cin, 0, cout, 16, 32); }
 size_t conv3x3_winof4_floats(int cout, int cin) { return (size_t)36 * cout * cin; }
 
@@ -371,15 +386,16 @@ void pack_conv_weights_winof4(const float* w, int cout, int cin, float* dst) {
     }
 }
 
-int launch_conv3x3_winof4(const float* u, const float* bias, int cout, const float* in0, int C0, float* out, int B, int H, int W, hipStream_t s,
-                          float slope, float* pool_out) {
-  if (!conv3x3_winof4_ok(C0, 0, cout, H, W)) {
-    set_error("conv3x3_winof4: unsupported geometry (%d -> %d channels, %d x %d)", C0, cout, H, W);
+int launch_conv3x3_winof4(const float* u, const float* bias, int cout, const float* in0, int C0, const float* in1, int C1, float* out, int B,
+                          int H, int W, hipStream_t s, float slope, float* pool_out) {
+  const bool two = C1 != 0;
+  if (!(two ? conv3x3_winof4_entry_ok(C0, C1, cout, H, W) : conv3x3_winof4_ok(C0, 0, cout, H, W))) {
+    set_error("conv3x3_winof4: unsupported geometry (%d + %d -> %d channels, %d x %d)", C0, C1, cout, H, W);
     return PNPX_ERR_SHAPE;
   }
   WinoArgs a{};
   a.in0 = in0;
-  a.in1 = in0;
+  a.in1 = two ? in1 : in0;
   a.u = u;
   a.bias = bias;
   a.pool = pool_out;
@@ -390,11 +406,11 @@ int launch_conv3x3_winof4(const float* u, const float* bias, int cout, const flo
   a.Hp = padded_h(H);
   a.Wp = padded_w(W);
   a.C0 = C0;
-  a.C1 = 0;
+  a.C1 = C1;
   a.Cout = cout;
   a.slope = slope;
   a.nct = cout / 64;
-  a.nch = C0 / CfgF4::CK;
+  a.nch = (C0 + C1) / CfgF4::CK;
   a.nch_all = a.nch;
   a.ksplit = 1;
   a.rx = W / 32;
@@ -405,7 +421,9 @@ int launch_conv3x3_winof4(const float* u, const float* bias, int cout, const flo
   if (dev >= 0 && dev < 64) {
     hipError_t e = hipSuccess;
     std::call_once(attr_once[dev], [&] {
-      e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3x3_winof4_f32_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_REQF4);
+      e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3x3_winof4_f32_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_REQF4);
+      if (e == hipSuccess)
+        e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3x3_winof4_f32_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_REQF4);
     });
     PNPX_HIP(e);
   }
@@ -413,7 +431,8 @@ int launch_conv3x3_winof4(const float* u, const float* bias, int cout, const flo
   long long grid = 256;
   if (grid >= ntiles) grid = ntiles;
   else if ((grid / 8) % a.nct != 0 && grid >= 8LL * a.nct) grid -= grid % (8 * a.nct);
-  hipLaunchKernelGGL(conv3x3_winof4_f32_kernel, dim3((unsigned)grid), dim3(512), LDS_REQF4, s, a);
+  if (two) hipLaunchKernelGGL(conv3x3_winof4_f32_kernel<true>, dim3((unsigned)grid), dim3(512), LDS_REQF4, s, a);
+  else hipLaunchKernelGGL(conv3x3_winof4_f32_kernel<false>, dim3((unsigned)grid), dim3(512), LDS_REQF4, s, a);
   PNPX_LAUNCH_CHECK();
   return PNPX_OK;
 }

@@ -21,6 +21,7 @@ struct ConvF32Sel {
   bool winograd = false;   // fp32_winograd
   bool wino8 = false;      // the layer's fp32_wino8_layers bit (DRUNet: any bit)
   bool winof4 = false;     // the layer's fp32_winof4_layers bit (DRUNet: never)
+  bool winof4_entry = false;   // the layer's fp32_winof4_entries bit (decoder entries 15, 18, 21; DRUNet: never)
   int ksplit = 0;          // fp32_ksplit (DRUNet: 0)
   int ksplit_rule = 1;     // fp32_ksplit_rule
   bool fuse_up = false;    // fp32_fuse_up
@@ -33,7 +34,8 @@ ConvF32Sel conv_f32_sel_drunet(const pnpx_ctx* ctx, const float* u, const float*
 
 // B_call: the batch of the whole call (launch chains beside each other count as one call), which the fp32_ksplit = 1 rule reads
 ConvF32Choice conv_f32_forward(const ConvF32Sel& v, int C0, int C1, int cout, int H, int W, int B_call);
-// decoder entry (second source at H/2 x W/2): fused = the instance that up-samples it in the kernel runs; else the forward decision
+// decoder entry (second source at H/2 x W/2): fused = the instance that up-samples it in the kernel runs; else the forward decision, or
+// WinoF4 (two-source instance on the up-sampled tensor) where fp32_winof4_entries puts the entry
 ConvF32Choice conv_f32_entry(const ConvF32Sel& v, int C0, int C1, int cout, int H, int W, int B_call);
 // the UNet's last 3x3 layer: fused = the 1x1 out-conv + residual + clamp ride on `kernel`'s epilogue; else the forward decision
 ConvF32Choice conv_f32_last(const ConvF32Sel& v, int cin, int cout, int H, int W, int B_call);

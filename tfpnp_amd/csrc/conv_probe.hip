@@ -38,6 +38,8 @@ extern "C" int pnpx_conv3x3_probe_plan(int kind, int C0, int C1, int cout, int H
     case PNPX_PROBE_WINO8_UPS: return conv3x3_wino8_ups_ok(C0, C1, cout, H, W) ? wct : 0;
     case PNPX_PROBE_DIRECT_GRAD: return C1 == 0 ? direct_grad_ct(C0, cout) : 0;
     case PNPX_PROBE_WINO8_GRAD: return C1 == 0 && conv3x3_wino8_ok(C0, 0, cout, H, W) ? wct : 0;
+    case PNPX_PROBE_WINOF4_2SRC: return C1 > 0 && conv3x3_winof4_entry_ok(C0, C1, cout, H, W) ? 64 : 0;
+    case PNPX_PROBE_WINOF4_UPS: return 0;      // the F(4x4,3x3) kernel has no up-sampling instance
   }
   return 0;
 }
@@ -53,7 +55,7 @@ extern "C" int pnpx_conv3x3_probe(pnpx_ctx* ctx, int kind, const float* w_host, 
   PNPX_HIP(hipSetDevice(ctx->device));
   hipStream_t s = static_cast<hipStream_t>(stream);
   const bool grad = is_grad(kind);
-  if (kind < PNPX_PROBE_DIRECT || kind > PNPX_PROBE_WINO8_GRAD) {
+  if (kind < PNPX_PROBE_DIRECT || kind > PNPX_PROBE_WINOF4_UPS) {
     set_error("pnpx_conv3x3_probe: unknown kind %d", kind);
     return PNPX_ERR_ARG;
   }
@@ -63,13 +65,18 @@ extern "C" int pnpx_conv3x3_probe(pnpx_ctx* ctx, int kind, const float* w_host, 
   }
   // operands a kind has no place for are refused, never dropped
   const bool takes_res = kind == PNPX_PROBE_DIRECT || kind == PNPX_PROBE_WINO4 || kind == PNPX_PROBE_WINO8;
-  const bool takes_pool = kind == PNPX_PROBE_WINO4 || kind == PNPX_PROBE_WINO8 || kind == PNPX_PROBE_WINOF4;
+  const bool takes_pool = kind == PNPX_PROBE_WINO4 || kind == PNPX_PROBE_WINO8 || kind == PNPX_PROBE_WINOF4 || kind == PNPX_PROBE_WINOF4_2SRC;
   if ((res && !takes_res) || (pool_out && !takes_pool) || (mask && !grad) || (res && pool_out)) {
     set_error("pnpx_conv3x3_probe: kind %d takes no %s operand", kind, res && !takes_res ? "res" : (mask && !grad ? "mask" : "pool_out"));
     return PNPX_ERR_ARG;
   }
   if ((grad || kind == PNPX_PROBE_WINOF4) && C1 != 0) {
     set_error("pnpx_conv3x3_probe: kind %d is single-source (C1 = %d)", kind, C1);
+    return PNPX_ERR_SHAPE;
+  }
+  if (kind == PNPX_PROBE_WINOF4_UPS || (kind == PNPX_PROBE_WINOF4_2SRC && C1 == 0)) {
+    set_error(kind == PNPX_PROBE_WINOF4_UPS ? "pnpx_conv3x3_probe: unsupported geometry (kind %d has no instance)"
+                                            : "pnpx_conv3x3_probe: unsupported geometry (kind %d needs a second source)", kind);
     return PNPX_ERR_SHAPE;
   }
   const int cin = C0 + C1;
@@ -90,7 +97,8 @@ extern "C" int pnpx_conv3x3_probe(pnpx_ctx* ctx, int kind, const float* w_host, 
       case PNPX_PROBE_WINO4: return launch_conv3x3_wino(pk, b, cout, in0, C0, in1, C1, out, B, H, W, s, slope, res, pool_out);
       case PNPX_PROBE_WINO8: return launch_conv3x3_wino8(pk, b, cout, in0, C0, in1, C1, out, B, H, W, s, slope, res, pool_out, nullptr, ks_rule);
       case PNPX_PROBE_WINO8_KSPLIT: return launch_conv3x3_wino8(pk, b, cout, in0, C0, in1, C1, out, B, H, W, s, slope, nullptr, nullptr, ks, ks_rule);
-      case PNPX_PROBE_WINOF4: return launch_conv3x3_winof4(pk, b, cout, in0, C0, out, B, H, W, s, slope, pool_out);
+      case PNPX_PROBE_WINOF4: return launch_conv3x3_winof4(pk, b, cout, in0, C0, nullptr, 0, out, B, H, W, s, slope, pool_out);
+      case PNPX_PROBE_WINOF4_2SRC: return launch_conv3x3_winof4(pk, b, cout, in0, C0, in1, C1, out, B, H, W, s, slope, pool_out);
       case PNPX_PROBE_WINO8_UPS: return launch_conv3x3_wino8_ups(pk, b, cout, in0, C0, in1, C1, out, B, H, W, s, slope);
       case PNPX_PROBE_DIRECT_GRAD:
         L.mt = cout % 64 == 0 ? 64 : 32;
@@ -117,6 +125,7 @@ extern "C" int pnpx_conv3x3_probe(pnpx_ctx* ctx, int kind, const float* w_host, 
       pack_conv_weights(w_host, cout, cin, conv_pack_mt(cout), conv_pack_cc(cin), host.data());
       break;
     case PNPX_PROBE_WINOF4:
+    case PNPX_PROBE_WINOF4_2SRC:
       host.resize(conv3x3_winof4_floats(cout, cin));
       pack_conv_weights_winof4(w_host, cout, cin, host.data());
       break;

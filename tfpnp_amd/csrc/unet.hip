@@ -702,8 +702,9 @@ static int unet_forward_f32(pnpx_ctx* ctx, UNetArena& ar, const UNetPlan& P, con
     // (training forwards too: the VJP of the up-sampling is linear in the gradient and reads no up-sampled activation)
     // (odd sizes: the up-sampled 2h x 2w image sits inside a larger tensor -- separate kernel)
     const ConvF32Sel v0 = conv_f32_sel(ctx, li0);
-    const bool ups_fused = P.x[l].H == 2 * h && P.x[l].W == 2 * w &&
-                           conv_f32_entry(v0, P.x[l].C, below->C, ctx->conv[li0].cout, 2 * h, 2 * w, B_call).fused;
+    const bool even = P.x[l].H == 2 * h && P.x[l].W == 2 * w;
+    const ConvF32Choice c0 = even ? conv_f32_entry(v0, P.x[l].C, below->C, ctx->conv[li0].cout, 2 * h, 2 * w, B_call) : ConvF32Choice();
+    const bool ups_fused = c0.fused;
     if (ups_fused) {
       // nothing to launch
     } else if ((2 * w) % 4 == 0 && (size_t)B * below->C <= 65535) {
@@ -720,8 +721,13 @@ static int unet_forward_f32(pnpx_ctx* ctx, UNetArena& ar, const UNetPlan& P, con
     }
     // first convolution of a decoder block: the fused instance reads the low-resolution tensor
     auto entry = [&](const Act& ta) -> int {
-      if (!ups_fused) return conv(li0, P.x[l], &P.u[l], ta);
       const ConvLayer& L = ctx->conv[li0];
+      if (c0.kernel == ConvF32Kernel::WinoF4) {      // the F(4x4,3x3) two-source instance on the up-sampled tensor
+        ConvF32Operands a{fptr(P.x[l]), P.x[l].C, fptr(P.u[l]), P.u[l].C, fptr(ta), B, ta.H, ta.W};
+        PNPX_TRY(launch_conv_f32(c0, v0, L, a, s));
+        return rec.mark("conv3x3_wino", 2.0 * 9.0 * L.cin * L.cout * (double)ta.H * ta.W * B);
+      }
+      if (!ups_fused) return conv(li0, P.x[l], &P.u[l], ta);
       PNPX_TRY(launch_conv3x3_wino8_ups(ctx->conv_wino_u[li0], L.b, L.cout, fptr(P.x[l]), P.x[l].C, fptr(*below), below->C, fptr(ta), B, 2 * h, 2 * w, s));
       return rec.mark("conv3x3_wino", 2.0 * 9.0 * L.cin * L.cout * (double)(2 * h) * (2 * w) * B);
     };
