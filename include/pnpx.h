@@ -71,9 +71,16 @@ int pnpx_ctx_reserve(pnpx_ctx* ctx, int B, int H, int W);
  *      profiles/winof4_entries.md): bit i = decoder entry i (768 -> 256 at H/8, 384 -> 128 at H/4, 192 -> 64 at H/2) runs on the
  *      two-source instance of the F(4x4,3x3) kernel in forward passes, in the calls in which the 8-wave kernel would run it in one piece
  *      (its fp32_wino8_layers bit set, "fp32_winograd" 1, the K-split does not claim it) and where its geometry allows (cout % 64 == 0,
- *      H % 16 == 0, W % 32 == 0, both sources whole 8-channel chunks, at least one chunk of the first).  That kernel does not up-sample:
- *      the separate up-sampling kernel runs first, whatever "fp32_fuse_up" says.  "fp32_winof4_layers" never moves an entry.  0 = the
- *      entries keep the F(2x2) kernel (bit-identical to the library before the option existed).
+ *      H % 16 == 0, W % 32 == 0, both sources whole 8-channel chunks, at least one chunk of the first).  Unless
+ *      "fp32_winof4_fuse_up" says otherwise the separate up-sampling kernel runs first, whatever "fp32_fuse_up" says.
+ *      "fp32_winof4_layers" never moves an entry.  0 = the entries keep the F(2x2) kernel (bit-identical to the library before the option
+ *      existed).
+ *  "fp32_winof4_fuse_up" (layer mask numbered like fp32_winof4_entries, 0 .. 2^27 - 1; only bits 15, 18 and 21 mean anything; default:
+ *      see profiles/winof4_fuse_up.md): bit i = where "fp32_winof4_entries" puts decoder entry i on the F(4x4,3x3) kernel, that kernel's
+ *      third instance runs it: it takes the LOW-resolution second source, interpolates the bilinear x2 (align_corners) into its halo buffer
+ *      itself and the up-sampling kernel is not launched.  It needs two 8-channel chunks of the first source (C0 >= 16); an entry without
+ *      them, and every call in which the K-split claims the entry, stay as they are.  The result is bit-identical to the two-launch form
+ *      (same floats for positions and weights, same rounding sequence), so 0 = the up-sampling kernel + the two-source instance, same bits.
  *  "fp32_chains" (default 2): in conv_mode 0 the denoiser forward runs as n independent launch chains over contiguous slices of the batch
  *      (caller's stream + side streams, joined before the entry returns; bit-identical per image): 2 measured best (-3.6 % at 48 x 256^2,
  *      -7 % at B = 24); 1 = only the bottom level's three launches fork two chains; 0 = one chain.  The VJP's adjoint chain forks exactly
@@ -674,7 +681,9 @@ int pnpx_winof4_pack(const float* w, int cout, int cin, float* dst);
  *     WINO8_KSPLIT: the 8-wave kernel handed the K-split scratch (ks_rule: conv3x3_wino8.hip; 1 = the default rule); WINO8_UPS: in1 is
  *     the LOW-resolution second source [B][C1][H/2 + 2][W/2 + 8], up-sampled x2 (bilinear, align_corners) inside the kernel;
  *     WINOF4 is single-source (C1 = 0), WINOF4_2SRC the same kernel's two-source instance (C1 > 0, in1 at full resolution; takes
- *     pool_out); WINOF4_UPS is reserved (its plan is 0 for every geometry and the probe returns PNPX_ERR_SHAPE).
+ *     pool_out); WINOF4_UPS is reserved (its plan is 0 for every geometry and the probe returns PNPX_ERR_SHAPE) and stays so: the
+ *     instance that up-samples in1 (LOW-resolution [B][C1][H/2 + 2][W/2 + 8], like WINO8_UPS) is kind WINOF4_FUSE_UP = 11, and 10 is
+ *     unknown.
  *   adjoint kinds: w is the FORWARD layer's [C0][cout][3][3]; in0 = the gradient of its output (C0 channels), out = the gradient of its
  *     input (cout channels, a multiple of 32) = conv_transpose(in0, w), times (mask > 0 ? 1 : slope) when mask (out's geometry) is given;
  *     no bias.
@@ -691,17 +700,23 @@ enum pnpx_probe_kind {
   PNPX_PROBE_DIRECT_GRAD = 6,
   PNPX_PROBE_WINO8_GRAD = 7,
   PNPX_PROBE_WINOF4_2SRC = 8,   /* the F(4x4,3x3) kernel's two-source instance: in1 at full resolution, C1 > 0 */
-  PNPX_PROBE_WINOF4_UPS = 9     /* reserved for an F(4x4,3x3) instance that up-samples in1 itself: none exists, every geometry is refused */
+  PNPX_PROBE_WINOF4_UPS = 9,    /* reserved before an F(4x4,3x3) instance that up-samples in1 existed: still refuses every geometry */
+  /* 10 is no kind */
+  PNPX_PROBE_WINOF4_FUSE_UP = 11   /* the F(4x4,3x3) kernel's up-sampling instance: in1 at H/2 x W/2, C1 > 0, C0 >= 16; no pool_out */
 };
 int pnpx_conv3x3_probe(pnpx_ctx* ctx, int kind, const float* w_host, const float* bias_host, int cout, const float* in0, int C0,
                        const float* in1, int C1, float* out, const float* res, const float* mask, float slope, float* pool_out,
                        int ks_rule, int B, int H, int W, void* stream);
 int pnpx_conv3x3_probe_plan(int kind, int C0, int C1, int cout, int H, int W, int ks_rule);
+/* For tests: the separate bilinear x2 (align_corners) up-sampling launch of conv_mode 0 on device tensors in the same padded planar layout:
+ * src [planes][h + 2][w + 8] -> the interior of dst [planes][2h + 2][2w + 8] (its border cells are not written).  Asynchronous on `stream`. */
+int pnpx_upsample2x_probe(pnpx_ctx* ctx, const float* src, float* dst, int planes, int h, int w, void* stream);
 
 /* Host-only, for tests: which kernel a UNet decoder entry of conv_mode 0 gets (csrc/conv_f32_select.hip, conv_f32_entry) for a set of
  * options, a geometry (second source C1 > 0 at H/2 x W/2, output H x W) and the batch of the whole call.
  * opts: bit 0 "fp32_winograd", bit 1 the layer's "fp32_wino8_layers" bit, bit 2 its "fp32_winof4_layers" bit, bit 3 its
- * "fp32_winof4_entries" bit, bit 4 "fp32_fuse_up", bit 5 the layer's F(2x2) weights are packed, bit 6 its F(4x4) weights are packed.
+ * "fp32_winof4_entries" bit, bit 4 "fp32_fuse_up", bit 5 the layer's F(2x2) weights are packed, bit 6 its F(4x4) weights are packed,
+ * bit 7 its "fp32_winof4_fuse_up" bit.
  * Returns kernel + 16 x K-split pieces + 256 x fused, kernel 0 = direct, 1 = 4-wave F(2x2), 2 = 8-wave F(2x2), 3 = F(4x4); fused = the
  * instance that up-samples the second source itself runs (else the separate up-sampling kernel runs first); -1 = a non-positive size. */
 int pnpx_conv_f32_entry_plan(int opts, int ksplit, int ksplit_rule, int C0, int C1, int cout, int H, int W, int B_call);

@@ -151,6 +151,7 @@ _SIGNATURES = {
     "pnpx_conv3x3_probe": (C.c_int, [c_void_p, C.c_int, c_void_p, c_void_p, C.c_int, _P, C.c_int, _P, C.c_int, _P, _P, _P, C.c_float, _P,
                                      C.c_int, C.c_int, C.c_int, C.c_int, c_void_p]),
     "pnpx_conv3x3_probe_plan": (C.c_int, [C.c_int] * 7),
+    "pnpx_upsample2x_probe": (C.c_int, [c_void_p, _P, _P, C.c_int, C.c_int, C.c_int, c_void_p]),
     "pnpx_conv_f32_entry_plan": (C.c_int, [C.c_int] * 9),
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)

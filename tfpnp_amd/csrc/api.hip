@@ -413,6 +413,7 @@ const PlainOption PLAIN_OPTIONS[] = {
     {"fp32_wino8_layers", &pnpx_ctx::opt_fp32_wino8, 0, (1 << 27) - 1},      // bit li: layer li on the 8-wave Winograd kernel
     {"fp32_winof4_layers", &pnpx_ctx::opt_fp32_winof4, 0, (1 << 27) - 1},    // bit li: layer li on the F(4x4,3x3) kernel (forward passes)
     {"fp32_winof4_entries", &pnpx_ctx::opt_fp32_winof4_entries, 0, (1 << 27) - 1},      // bits 15, 18, 21: that decoder entry on it
+    {"fp32_winof4_fuse_up", &pnpx_ctx::opt_fp32_winof4_fuse_up, 0, (1 << 27) - 1},      // bits 15, 18, 21: ... up-sampling its second source itself
 };
 const PlainOption* plain_option(const char* key) {
   for (const PlainOption& o : PLAIN_OPTIONS)

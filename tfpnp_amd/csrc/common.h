@@ -265,6 +265,10 @@ struct pnpx_ctx {
   // bits 15, 18, 21: that decoder entry (768 -> 256, 384 -> 128, 192 -> 64) runs on the F(4x4,3x3) kernel's two-source instance, behind
   // the separate up-sampling kernel, where the fused F(2x2) instance would run it in one piece (profiles/winof4_entries.md)
   int opt_fp32_winof4_entries = (1 << 15) | (1 << 18) | (1 << 21);
+  // bits 15, 18, 21: where fp32_winof4_entries puts that entry on the F(4x4,3x3) kernel, the instance that up-samples the low-resolution
+  // second source itself runs it and the up-sampling launch is skipped; same bits in the result.  Default: entry 21 alone, the one whose
+  // up-sampling launch costs more than the interpolation in the kernel does (profiles/winof4_fuse_up.md)
+  int opt_fp32_winof4_fuse_up = 1 << 21;
   int opt_fp32_chains = 2;         // conv_mode 0: n >= 2 = the forward as n launch chains over slices of the batch (default 2: this family is not
                                    // power-capped, a second chain fills the other's tails and partial rounds: 8.76 -> 8.44 ms at 48 x 256^2, -7 % at
                                    // B = 24; 3 and 4 chains measured slower); 1 = only the bottom level forks two chains; 0 = one chain

@@ -1,7 +1,8 @@
 // Winograd F(4x4, 3x3) on the exact-fp32 MFMA v_mfma_f32_16x16x4_f32: 36 products per 16 outputs instead of F(2x2)'s 16 per 4
 // = 0.5625 x the MFMAs of conv3x3_wino8.hip.  64-cout-tile layers of the UNet's forward passes only: the plain single-source layers
 // (option fp32_winof4_layers) and, as a second instance, the two-source decoder entries on an already up-sampled second source (option
-// fp32_winof4_entries); no residual, no K-split, no fused up-sampling or out-conv.  Same activation layout (padded planar fp32), WinoArgs,
+// fp32_winof4_entries) or, as a third, on the low-resolution second source itself, up-sampled in the kernel (option fp32_winof4_fuse_up); no
+// residual, no K-split, no out-conv.  Same activation layout (padded planar fp32), WinoArgs,
 // bias + LeakyReLU as max(y, slope y) and optional fused 2x2 max-pool as the F(2x2) kernels.
 //
 // Points (0, +-1, +-1/2, inf), rows scaled as tools/wino_f4_probe.py's cook_toom does (winof4_mats.h holds the matrices the packer uses;
@@ -52,6 +53,17 @@ struct CfgF4 {
   static constexpr int VSTG = 2 * 6 * CK * 32 * 4;        // bytes of one stage of V: 12 KiB
   static constexpr int OFF_U = 0, OFF_V = 3 * USTG, OFF_RAW = OFF_V + 3 * VSTG;
   static constexpr int LDS_USED = OFF_RAW + 2 * RAW_BYTES;   // 157184
+  // UPS instance: a V ring of TWO slots (below) makes room for two staging windows of the low-resolution second source -- 11 rows x 20
+  // columns per channel, [channel quad 2][row][column][channel 4] so that a halo pixel's tap is one 16-byte read per quad -- and the
+  // per-tile interpolation tables (18 halo rows + 34 halo columns, 16 bytes each)
+  static constexpr int SR = 11, SC = 20;
+  static constexpr int QPLANE = SR * SC * 16;                // bytes of one channel quad's window: 3520
+  static constexpr int ST_INSTR = (2 * QPLANE + 255) / 256;  // dword gathers of 64 lanes: 28 (the last one half used)
+  static constexpr int ST_STRIDE = ST_INSTR * 256;           // 7168
+  static constexpr int ST_PER_WAVE = (ST_INSTR + 7) / 8;     // 4, of which the last exists for the first ST_INSTR % 8 waves only
+  static constexpr int NST = ST_INSTR / 8;                   // 3: gathers every wave issues
+  static constexpr int OFF_RAW_UPS = OFF_V + 2 * VSTG, OFF_ST = OFF_RAW_UPS + 2 * RAW_BYTES, OFF_TAB = OFF_ST + 2 * ST_STRIDE;
+  static constexpr int LDS_USED_UPS = OFF_TAB + (18 + 34) * 16;   // 160064
 };
 constexpr int LDS_REQF4 = 160 * 1024;
 // -DWINOF4_ABL=bits (timing only, results wrong; tools/build_variant.sh): 1 no input transform, 2 no halo gathers, 4 no weight DMA,
@@ -59,7 +71,7 @@ constexpr int LDS_REQF4 = 160 * 1024;
 #ifndef WINOF4_ABL
 #define WINOF4_ABL 0
 #endif
-static_assert(CfgF4::LDS_USED <= LDS_REQF4, "LDS budget");
+static_assert(CfgF4::LDS_USED <= LDS_REQF4 && CfgF4::LDS_USED_UPS <= LDS_REQF4, "LDS budget");
 
 // row A of B^T applied to six values (points 0, +-1, +-1/2, inf; winof4_mats.h WINOF4_BT)
 template <int A>
@@ -82,11 +94,22 @@ __device__ __forceinline__ void at_rows(float m0, float m1, float m2, float m3, 
 
 // TWO: the channel chunks C0 / 8 .. of a tile come from in1 (C1 channels, same geometry as in0); the weights are packed over C0 + C1 and
 // a.nch counts both sources' chunks.  A chunk lies in one source (C0 % 8 == 0), so only its halo origin differs.
-template <bool TWO>
+//
+// UPS (with TWO): in1 is the LOW-resolution second source (C1 channels at H/2 x W/2, padded planar) and the kernel interpolates its
+// bilinear x2 (align_corners) itself, to the bits upsample2x_v4_kernel (unet.hip) writes.  A chunk of the second source never goes through
+// the halo gathers: the low-resolution window of its 18 x 34 halo is staged by dword LDS-DMA (issued in stage 2 of the chunk three before
+// it, beside the halo gathers of the chunk two before it, and waited for with them) and interpolated into the raw halo buffer in the side
+// work of the three stages that buffer is free: stage 2 of the chunk two before (channels 0-3 of halo pixels 0 .. 511), stage 0 (channels
+// 4-7 of them) and stage 1 (pixels 512 .. 611, two channels per thread) of the chunk before -- every wave the same amount.  From the
+// halo buffer on nothing differs.  The V ring has two slots here (stage g reads slot g & 1 and writes the other one; the barrier between
+// two stages separates a slot's last read from its next write), which is where the staging windows' LDS comes from.
+template <bool TWO, bool UPS = false>
 __global__ __launch_bounds__(512, 1) void conv3x3_winof4_f32_kernel(WinoArgs a) {
+  static_assert(TWO || !UPS, "the up-sampled source is the second one");
   using C = CfgF4;
   constexpr int CK = C::CK, RWL = C::RWL, RPXL = C::RPXL, RAW_BYTES = C::RAW_BYTES, RAW_PER_WAVE = C::RAW_PER_WAVE;
-  constexpr int USTG = C::USTG, NUW = C::NUW, VSTG = C::VSTG, OFF_U = C::OFF_U, OFF_V = C::OFF_V, OFF_RAW = C::OFF_RAW;
+  constexpr int USTG = C::USTG, NUW = C::NUW, VSTG = C::VSTG, OFF_U = C::OFF_U, OFF_V = C::OFF_V, OFF_RAW = UPS ? C::OFF_RAW_UPS : C::OFF_RAW;
+  constexpr int SC = C::SC, QPLANE = C::QPLANE, ST_STRIDE = C::ST_STRIDE, ST_PER_WAVE = C::ST_PER_WAVE, OFF_ST = C::OFF_ST, OFF_TAB = C::OFF_TAB;
   constexpr int UQ = USTG / 4;      // floats per weight stage
   extern __shared__ __attribute__((aligned(16))) char lds[];
   const int tid = threadIdx.x, lane = tid & 63;
@@ -103,7 +126,17 @@ __global__ __launch_bounds__(512, 1) void conv3x3_winof4_f32_kernel(WinoArgs a) 
     const float* s1;   // ... of the second source (TWO)
     const float* w;    // weights of the cout tile
     int ct, b, x0, y0, ok, pad_;
+    int rs, cs;        // UPS: padded row / column of the low-resolution tensor at which the tile's staging window starts (s1 points there)
   };
+  struct UpsStage {      // UPS: what differs from chunk to chunk in a pipeline stage
+    int vrd;             // V slot the stage reads; its transform writes the other one
+    int wait_n;          // stages 0 and 2: VMEM operations the stage may leave in flight
+    bool raw, st, ip;    // stage 2 gathers the halo of the chunk after next / stages the chunk three ahead; the stage's interpolation step runs
+    const float* st_src;
+    int st_buf, ip_sbuf, ip_rbuf;
+  };
+  // UPS: geometry of the low-resolution source
+  const int h_lo = a.ups_h, w_lo = a.ups_w, hp_lo = padded_h(a.ups_h), wp_lo = padded_w(a.ups_w), hpwp_lo = hp_lo * wp_lo;
   auto decode = [&](int k) {
     Tile T;
     const int j = slot + nslot * k;
@@ -120,15 +153,27 @@ __global__ __launch_bounds__(512, 1) void conv3x3_winof4_f32_kernel(WinoArgs a) 
     T.x0 = tx * 32;
     T.y0 = ty * 16;
     T.s0 = a.in0 + (size_t)T.b * a.C0 * HpWp + (size_t)T.y0 * a.Wp + T.x0 + (PADL - 1);
-    T.s1 = TWO ? a.in1 + (size_t)T.b * a.C1 * HpWp + (size_t)T.y0 * a.Wp + T.x0 + (PADL - 1) : nullptr;
+    if constexpr (UPS) {
+      // The window starts at the first tap of the first halo row / column inside the image (the taps' indices grow with the halo index:
+      // 18 rows span at most 10 source rows + the second tap, 34 columns at most 18 + 1), pulled back so that its SR rows and SC columns
+      // stay inside the padded plane; a plane of fewer than SR rows (h = 8) repeats its last row instead (stoff below).
+      const int rl = (int)__fmul_rn(a.ups_sy, (float)max(T.y0 - 1, 0)) + 1, cl = (int)__fmul_rn(a.ups_sx, (float)max(T.x0 - 1, 0)) + PADL;
+      T.rs = min(rl, max(hp_lo - C::SR, 0));
+      T.cs = min(cl, wp_lo - SC);
+      T.s1 = a.in1 + (size_t)T.b * a.C1 * hpwp_lo + (size_t)T.rs * wp_lo + T.cs;
+    } else {
+      T.rs = T.cs = 0;
+      T.s1 = TWO ? a.in1 + (size_t)T.b * a.C1 * HpWp + (size_t)T.y0 * a.Wp + T.x0 + (PADL - 1) : nullptr;
+    }
     T.w = a.u + (size_t)T.ct * a.nch * 3 * UQ;
     return T;
   };
   const int nch0 = a.C0 / CK;      // chunks of the first source
   auto raw_of = [&](const Tile& X, int c) {
-    if (TWO && c >= nch0) return X.s1 + (size_t)CK * (c - nch0) * HpWp;
+    if (TWO && !UPS && c >= nch0) return X.s1 + (size_t)CK * (c - nch0) * HpWp;
     return X.s0 + (size_t)CK * c * HpWp;
   };
+  auto st_of = [&](const Tile& X, int c) { return X.s1 + (size_t)CK * (c - nch0) * hpwp_lo; };      // UPS: window origin of second-source chunk c
 
   auto sync_all = [&]() {
     asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
@@ -160,6 +205,80 @@ __global__ __launch_bounds__(512, 1) void conv3x3_winof4_f32_kernel(WinoArgs a) 
   auto dma_raw = [&](const float* src, int rbuf) {
 #pragma unroll
     for (int k = 0; k < RAW_PER_WAVE; ++k) dma_raw_piece(src, rbuf, k);
+  };
+
+  // -- UPS: the staging window of a second-source chunk, an eighth per wave: per-lane byte offsets from the window's origin in the
+  // chunk's channel 0 (lanes past the window read its first element into the slack behind it)
+  unsigned stoff[UPS ? ST_PER_WAVE : 1];
+  if constexpr (UPS) {
+#pragma unroll
+    for (int k = 0; k < ST_PER_WAVE; ++k) {
+      const int idx = (wave + 8 * k) * 64 + lane;
+      const int e = idx & 3, g = idx >> 2;
+      const int sc = g % SC, g2 = g / SC;
+      const int sr = g2 % C::SR, q = g2 / C::SR;
+      stoff[k] = (q < CK / 4) ? 4u * (unsigned)((4 * q + e) * hpwp_lo + min(sr, hp_lo - 1) * wp_lo + sc) : 0u;
+    }
+  }
+  auto dma_st_piece = [&](const float* src, int sbuf, int k) {      // gather k (of ST_PER_WAVE per wave) of one chunk's window
+    if (WINOF4_ABL & 2) return;
+    if (k < C::NST || wave + 8 * k < C::ST_INSTR) glds4(src, stoff[UPS ? k : 0], lds0 + OFF_ST + sbuf * ST_STRIDE + (wave + 8 * k) * 256);
+  };
+  // Per-tile tables of the interpolation, halo rows 0 .. 17 then halo columns 0 .. 33: (byte offset of the first tap in a staging plane,
+  // its weight h, the second tap's weight l, byte offset of the second tap); h = -1 marks a row / column outside the image (the
+  // convolution's zero padding).  The floats are upsample2x_v4_kernel's, operation by operation (its disassembly: no contraction here):
+  // f = s * index, i0 = (int) f, l = f - i0, h = 1 - l, second tap i0 + (i0 < n - 1).
+  auto write_tables = [&](const Tile& X) {
+    if (tid < 18 + 34) {
+      const bool row = tid < 18;
+      const int g = (row ? X.y0 : X.x0) - 1 + (row ? tid : tid - 18);      // image coordinate of the halo row / column
+      const bool valid = g >= 0 && g < (row ? a.H : a.W);
+      const float f = __fmul_rn(row ? a.ups_sy : a.ups_sx, (float)g);
+      const int i0 = (int)f;
+      const int i1 = i0 + (i0 < (row ? h_lo : w_lo) - 1 ? 1 : 0);
+      const float l = __fsub_rn(f, (float)i0), h = __fsub_rn(1.f, l);
+      f32x4 ent;
+      ent[0] = __int_as_float(valid ? (row ? (i0 + 1 - X.rs) * SC * 16 : (i0 + PADL - X.cs) * 16) : 0);
+      ent[1] = valid ? h : -1.f;
+      ent[2] = valid ? l : 0.f;
+      ent[3] = __int_as_float(valid ? (row ? (i1 + 1 - X.rs) * SC * 16 : (i1 + PADL - X.cs) * 16) : 0);
+      *reinterpret_cast<f32x4*>(lds + OFF_TAB + tid * 16) = ent;
+    }
+  };
+  // One interpolated value, in upsample2x_v4_kernel's rounding sequence (read in its disassembly): the products with l round on their own,
+  // the products with h are fused into them: fma(hy, fma(hx, v00, lx v01), ly fma(hx, v10, lx v11))
+  auto blend = [](float hy, float ly, float hx, float lx, float v00, float v01, float v10, float v11) {
+    return fmaf(hy, fmaf(hx, v00, __fmul_rn(lx, v01)), __fmul_rn(ly, fmaf(hx, v10, __fmul_rn(lx, v11))));
+  };
+  // The three steps of a chunk's interpolation from staging window sbuf into halo buffer rbuf.  Steps 0 and 1: halo pixel `tid`, channel
+  // quad 0 / 1 (four 16-byte taps, four values).  Step 2: the remaining 100 pixels 512 + tid / 4, channels 2 (tid % 4) and + 1 (four
+  // 8-byte taps, two values; threads 400 .. repeat the last pixel).  A pixel outside the image gets +0 and forms no product.
+  auto interp = [&](auto step_tag, int sbuf, int rbuf) {
+    constexpr int STEP = decltype(step_tag)::value;
+    if (WINOF4_ABL & 1) return;
+    const int pix = STEP < 2 ? tid : min(512 + (tid >> 2), 18 * 34 - 1);
+    const int hyi = pix / 34, hxi = pix - hyi * 34;
+    const f32x4 rt = *reinterpret_cast<const f32x4*>(lds + OFF_TAB + hyi * 16);
+    const f32x4 ct = *reinterpret_cast<const f32x4*>(lds + OFF_TAB + (18 + hxi) * 16);
+    const bool inside = rt[1] >= 0.f && ct[1] >= 0.f;
+    const int r0 = __float_as_int(rt[0]), r1 = __float_as_int(rt[3]), c0 = __float_as_int(ct[0]), c1 = __float_as_int(ct[3]);
+    char* ob = lds + OFF_RAW + rbuf * RAW_BYTES + (hyi * RWL + hxi) * 4;
+    if (STEP < 2) {
+      const char* sb = lds + OFF_ST + sbuf * ST_STRIDE + STEP * QPLANE;
+      const f32x4 v00 = *reinterpret_cast<const f32x4*>(sb + r0 + c0), v01 = *reinterpret_cast<const f32x4*>(sb + r0 + c1);
+      const f32x4 v10 = *reinterpret_cast<const f32x4*>(sb + r1 + c0), v11 = *reinterpret_cast<const f32x4*>(sb + r1 + c1);
+#pragma unroll
+      for (int e = 0; e < 4; ++e)
+        *reinterpret_cast<float*>(ob + (4 * STEP + e) * RPXL * 4) = inside ? blend(rt[1], rt[2], ct[1], ct[2], v00[e], v01[e], v10[e], v11[e]) : 0.f;
+    } else {
+      const int ch = 2 * (tid & 3);
+      const char* sb = lds + OFF_ST + sbuf * ST_STRIDE + (ch >> 2) * QPLANE + (ch & 3) * 4;
+      const f32x2 v00 = *reinterpret_cast<const f32x2*>(sb + r0 + c0), v01 = *reinterpret_cast<const f32x2*>(sb + r0 + c1);
+      const f32x2 v10 = *reinterpret_cast<const f32x2*>(sb + r1 + c0), v11 = *reinterpret_cast<const f32x2*>(sb + r1 + c1);
+#pragma unroll
+      for (int e = 0; e < 2; ++e)
+        *reinterpret_cast<float*>(ob + (ch + e) * RPXL * 4) = inside ? blend(rt[1], rt[2], ct[1], ct[2], v00[e], v01[e], v10[e], v11[e]) : 0.f;
+    }
   };
 
   // The role P = wave / 4 is a compile-time parameter of the whole tile loop (one branch at the top): every stage stays one basic block.
@@ -202,10 +321,10 @@ __global__ __launch_bounds__(512, 1) void conv3x3_winof4_f32_kernel(WinoArgs a) 
     *reinterpret_cast<f32x2*>(vb + 2048) = (f32x2){bt_row<2>(t[0], t[1], t[2], t[3], t[4], t[5]), bt_row<3>(t[0], t[1], t[2], t[3], t[4], t[5])};
     *reinterpret_cast<f32x2*>(vb + 4096) = (f32x2){bt_row<4>(t[0], t[1], t[2], t[3], t[4], t[5]), bt_row<5>(t[0], t[1], t[2], t[3], t[4], t[5])};
   };
-  auto transform_row = [&](auto s_tag, int rbuf) {      // this thread's row of stage S's two, into V slot S
+  auto transform_row = [&](auto s_tag, int rbuf, int vslot_ups = 0) {      // this thread's row of stage S's two, into V slot S (UPS: vslot_ups)
     constexpr int S = decltype(s_tag)::value;
     if (WINOF4_ABL & 1) return;
-    transform(std::integral_constant<int, 2 * S + P>{}, rbuf, S);
+    transform(std::integral_constant<int, 2 * S + P>{}, rbuf, UPS ? vslot_ups : S);
   };
 
   // -- MFMA operands: 16 bytes = (k-step 2) x (position 2 of a column pair) per lane; lane = 16 * channel group + cout / tile of the block
@@ -217,15 +336,25 @@ __global__ __launch_bounds__(512, 1) void conv3x3_winof4_f32_kernel(WinoArgs a) 
   // One pipeline stage S of a chunk: fetch the weights of the stage after next (and, S == 2, the halo of the chunk after next), 24 MFMAs,
   // the input transform of the next stage, then the counted wait (WAITN = VMEM operations issued after the ones the next stage needs)
   // and the barrier.
-  auto stage = [&](auto s_tag, auto wait_tag, const float* u_src, const float* raw_src, int raw_buf, int t_rbuf) {
+  // UPS: x holds what differs from chunk to chunk there (the other instances ignore it).
+  auto stage = [&](auto s_tag, auto wait_tag, const float* u_src, const float* raw_src, int raw_buf, int t_rbuf, const UpsStage& x) {
     constexpr int S = decltype(s_tag)::value, SN = (S + 1) % 3;
     constexpr int WAITN = decltype(wait_tag)::value;
-    auto side = [&]() { transform_row(std::integral_constant<int, SN>{}, t_rbuf); };
+    auto side = [&]() {
+      transform_row(std::integral_constant<int, SN>{}, t_rbuf, x.vrd ^ 1);
+      if constexpr (UPS) {      // step 0 in stage 2, step 1 in stage 0, step 2 in stage 1
+        if (x.ip) interp(std::integral_constant<int, SN>{}, x.ip_sbuf, x.ip_rbuf);
+      }
+    };
     // the stage's LDS-DMA pieces, one behind each MFMA (their issue cost then runs under the MFMAs): the weight slice behind MFMAs
-    // 0 .. 2, stage 2's halo gathers behind 4 .. 15
+    // 0 .. 2, stage 2's halo gathers behind 4 .. 15 (UPS: when the chunk after next is gathered) and, UPS, the staging window of the
+    // chunk three ahead behind 16 .. 19
     auto piece = [&](int m) {
       if (m < NUW) dma_u_piece(u_src, (S + 2) % 3, m);
-      if (S == 2 && m >= 4 && m < 4 + RAW_PER_WAVE) dma_raw_piece(raw_src, raw_buf, m - 4);
+      if (S == 2 && m >= 4 && m < 4 + RAW_PER_WAVE && (!UPS || x.raw)) dma_raw_piece(raw_src, raw_buf, m - 4);
+      if constexpr (UPS) {
+        if (S == 2 && m >= 16 && m < 16 + ST_PER_WAVE && x.st) dma_st_piece(x.st_src, x.st_buf, m - 16);
+      }
     };
     auto mfmas = [&]() {
       if (WINOF4_ABL & 16) return;
@@ -233,7 +362,7 @@ __global__ __launch_bounds__(512, 1) void conv3x3_winof4_f32_kernel(WinoArgs a) 
 #pragma unroll
       for (int q = 0; q < 6; ++q) {
         af[q] = *reinterpret_cast<const f32x4*>(lds + OFF_U + S * USTG + q * 4096 + a_lane);
-        bf[q] = *reinterpret_cast<const f32x4*>(lds + OFF_V + S * VSTG + q * 2048 + b_lane);
+        bf[q] = *reinterpret_cast<const f32x4*>(lds + OFF_V + (UPS ? x.vrd : S) * VSTG + q * 2048 + b_lane);
       }
       static_for<6>([&](auto q_tag) {
         constexpr int Q = decltype(q_tag)::value, R = Q / 3, CP = Q % 3;
@@ -259,7 +388,17 @@ __global__ __launch_bounds__(512, 1) void conv3x3_winof4_f32_kernel(WinoArgs a) 
       __builtin_amdgcn_sched_barrier(0);
       mfmas();
     }
-    asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(WAITN) : "memory");
+    if constexpr (UPS && S != 1) {
+      // The operations behind the weight slice the next stage needs: this stage's slice (stage 0: and, before it, what stage 2 issued
+      // behind its own) + NRAW halo gathers when the chunk after next was gathered + NST staging gathers when the chunk three ahead was
+      // staged = 3 + {0, 11} + {0, 3}.  The count is per wave and the smallest any wave issues, so no wave waits for too little.
+      if (x.wait_n == NUW + C::NRAW + C::NST) asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(NUW + C::NRAW + C::NST) : "memory");
+      else if (x.wait_n == NUW + C::NRAW) asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(NUW + C::NRAW) : "memory");
+      else if (x.wait_n == NUW + C::NST) asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(NUW + C::NST) : "memory");
+      else asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(NUW) : "memory");
+    } else {
+      asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(WAITN) : "memory");
+    }
     __builtin_amdgcn_s_barrier();
   };
 
@@ -317,15 +456,25 @@ __global__ __launch_bounds__(512, 1) void conv3x3_winof4_f32_kernel(WinoArgs a) 
   dma_u(T.w, 0);
   dma_u(T.w + UQ, 1);
   dma_raw(raw_of(T, 1), 1);      // (nch >= 2: chunk 1 exists; chunk 0 lies in the first source)
+  if constexpr (UPS) {           // (UPS: nch0 >= 2, chunks 0 and 1 are gathered; chunk 2 is staged here when it is the second source's first)
+    if (nch0 == 2) {
+#pragma unroll
+      for (int q = 0; q < ST_PER_WAVE; ++q) dma_st_piece(st_of(T, 2), 0, q);
+    }
+  }
   sync_all();
   transform_row(I0{}, 0);
   sync_all();
 
   int cc = 0;
+  int wait_prev = NUW;      // UPS: what the last stage 2 left in flight (nothing before the first chunk)
   for (;;) {
     Tile Tn = decode(k + 1);
     const bool more = Tn.ok;
     if (!more) Tn = T;      // after the walk's last chunks: surplus loads of this tile's first chunks into buffers nobody reads
+    // UPS: the tile's tables.  Their last readers were the previous tile's last interpolation steps, two barriers back; their first
+    // reader is stage 2 of chunk nch0 - 2, two barriers ahead.
+    if constexpr (UPS) write_tables(T);
 #pragma unroll
     for (int i = 0; i < 6; ++i)
 #pragma unroll
@@ -335,10 +484,39 @@ __global__ __launch_bounds__(512, 1) void conv3x3_winof4_f32_kernel(WinoArgs a) 
       const float* nu = (c + 1 < a.nch) ? w_c + 3 * UQ : Tn.w;                                    // the next chunk's weights
       const float* nraw = (c + 2 < a.nch) ? raw_of(T, c + 2) : raw_of(Tn, c + 2 - a.nch);         // the halo of the chunk after next
       const int rcur = cc & 1;
+      if constexpr (UPS) {
+        // Chunk c + 1 is interpolated in stages 0 and 1 (into the other halo buffer, from the staging window of its parity), chunk c + 2
+        // in stage 2 (into this chunk's halo buffer, free since stage 1's barrier), when they lie in the second source of THIS tile:
+        // the next tile's chunks 0 and 1 are gathered (nch0 >= 2).  Chunk c + 3 is staged in stage 2 into the window chunk c + 1 had
+        // (last read in stage 1); it may be the next tile's chunk 2.  Halo buffers, staging windows and V slots alternate with the
+        // running chunk count cc, which the tile boundary does not reset.
+        const bool up1 = c + 1 < a.nch && c + 1 >= nch0, up2 = c + 2 < a.nch && c + 2 >= nch0;
+        const bool up3 = c + 3 < a.nch ? c + 3 >= nch0 : c + 3 - a.nch >= nch0;
+        const float* nst = c + 3 < a.nch ? st_of(T, c + 3) : st_of(Tn, c + 3 - a.nch);
+        const int wait_cur = NUW + (up2 ? 0 : C::NRAW) + (up3 ? C::NST : 0);
+        UpsStage x{};
+        x.ip = up1;
+        x.ip_sbuf = x.ip_rbuf = rcur ^ 1;
+        x.vrd = rcur;      // stage g = 3 cc + s reads V slot g & 1 = (cc + s) & 1
+        x.wait_n = wait_prev;
+        stage(I0{}, WaitHalo{}, w_c + 2 * UQ, nullptr, 0, rcur, x);
+        x.vrd = rcur ^ 1;
+        stage(I1{}, WaitU{}, nu, nullptr, 0, rcur, x);
+        x.vrd = rcur;
+        x.ip = up2;
+        x.ip_sbuf = x.ip_rbuf = rcur;
+        x.raw = !up2;
+        x.st = up3;
+        x.st_src = nst;
+        x.st_buf = rcur ^ 1;
+        x.wait_n = wait_prev = wait_cur;
+        stage(I2{}, WaitHalo{}, nu + UQ, nraw, rcur, rcur ^ 1, x);
+        continue;
+      }
       // stage g = 3 c + s reads weight and V slot s; the transform behind its MFMAs makes V of stage g + 1 (stage 2: from the next chunk's halo)
-      stage(I0{}, WaitHalo{}, w_c + 2 * UQ, nullptr, 0, rcur);
-      stage(I1{}, WaitU{}, nu, nullptr, 0, rcur);
-      stage(I2{}, WaitHalo{}, nu + UQ, nraw, rcur, rcur ^ 1);
+      stage(I0{}, WaitHalo{}, w_c + 2 * UQ, nullptr, 0, rcur, UpsStage{});
+      stage(I1{}, WaitU{}, nu, nullptr, 0, rcur, UpsStage{});
+      stage(I2{}, WaitHalo{}, nu + UQ, nraw, rcur, rcur ^ 1, UpsStage{});
     }
     if (!(WINOF4_ABL & 8)) epilogue(T);
     if (!more) break;
@@ -362,6 +540,10 @@ bool conv3x3_winof4_ok(int C0, int C1, int cout, int H, int W) {
 bool conv3x3_winof4_entry_ok(int C0, int C1, int cout, int H, int W) {
   return conv3x3_winof4_ok(16, 0, cout, H, W) && H % 2 == 0 && W % 2 == 0 && C0 >= 8 && C0 % 8 == 0 && C1 >= 8 && C1 % 8 == 0;
 }
+// ... with the second source at H/2 x W/2, up-sampled in the kernel: the pipeline gathers the first TWO chunks of every tile before it can
+// interpolate one (the prologue and the tile boundary fetch chunks 0 and 1 from the first source), so C0 >= 16.  H and W are even
+// (multiples of 16 and 32): the target is exactly twice the low-resolution size.
+bool conv3x3_winof4_ups_ok(int C0, int C1, int cout, int H, int W) { return conv3x3_winof4_entry_ok(C0, C1, cout, H, W) && C0 >= 16; }
 bool conv3x3_winof4_packs(int cout, int cin) { return conv3x3_winof4_ok(cin, 0, cout, 16, 32); }
 size_t conv3x3_winof4_floats(int cout, int cin) { return (size_t)36 * cout * cin; }
 
@@ -386,10 +568,11 @@ void pack_conv_weights_winof4(const float* w, int cout, int cin, float* dst) {
     }
 }
 
-int launch_conv3x3_winof4(const float* u, const float* bias, int cout, const float* in0, int C0, const float* in1, int C1, float* out, int B,
-                          int H, int W, hipStream_t s, float slope, float* pool_out) {
+// ups: in1 is the low-resolution second source (H/2 x W/2) and the kernel up-samples it (launch_conv3x3_winof4_ups)
+static int launch_winof4(const float* u, const float* bias, int cout, const float* in0, int C0, const float* in1, int C1, float* out, int B,
+                         int H, int W, hipStream_t s, float slope, float* pool_out, bool ups) {
   const bool two = C1 != 0;
-  if (!(two ? conv3x3_winof4_entry_ok(C0, C1, cout, H, W) : conv3x3_winof4_ok(C0, 0, cout, H, W))) {
+  if (!(ups ? conv3x3_winof4_ups_ok(C0, C1, cout, H, W) : two ? conv3x3_winof4_entry_ok(C0, C1, cout, H, W) : conv3x3_winof4_ok(C0, 0, cout, H, W))) {
     set_error("conv3x3_winof4: unsupported geometry (%d + %d -> %d channels, %d x %d)", C0, C1, cout, H, W);
     return PNPX_ERR_SHAPE;
   }
@@ -415,6 +598,13 @@ int launch_conv3x3_winof4(const float* u, const float* bias, int cout, const flo
   a.ksplit = 1;
   a.rx = W / 32;
   a.ry = H / 16;
+  if (ups) {
+    a.ups_h = H / 2;
+    a.ups_w = W / 2;
+    // models/unet.py:99 (align_corners = True): source = destination * (in - 1) / (out - 1); the same two floats as unet.hip hands upsample2x_v4_kernel
+    a.ups_sy = (float)(H / 2 - 1) / (float)(H - 1);
+    a.ups_sx = (float)(W / 2 - 1) / (float)(W - 1);
+  }
   static std::once_flag attr_once[64];
   int dev = 0;
   PNPX_HIP(hipGetDevice(&dev));
@@ -424,6 +614,8 @@ int launch_conv3x3_winof4(const float* u, const float* bias, int cout, const flo
       e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3x3_winof4_f32_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_REQF4);
       if (e == hipSuccess)
         e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3x3_winof4_f32_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_REQF4);
+      if (e == hipSuccess)
+        e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3x3_winof4_f32_kernel<true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_REQF4);
     });
     PNPX_HIP(e);
   }
@@ -431,10 +623,20 @@ int launch_conv3x3_winof4(const float* u, const float* bias, int cout, const flo
   long long grid = 256;
   if (grid >= ntiles) grid = ntiles;
   else if ((grid / 8) % a.nct != 0 && grid >= 8LL * a.nct) grid -= grid % (8 * a.nct);
-  if (two) hipLaunchKernelGGL(conv3x3_winof4_f32_kernel<true>, dim3((unsigned)grid), dim3(512), LDS_REQF4, s, a);
+  if (ups) hipLaunchKernelGGL((conv3x3_winof4_f32_kernel<true, true>), dim3((unsigned)grid), dim3(512), LDS_REQF4, s, a);
+  else if (two) hipLaunchKernelGGL(conv3x3_winof4_f32_kernel<true>, dim3((unsigned)grid), dim3(512), LDS_REQF4, s, a);
   else hipLaunchKernelGGL(conv3x3_winof4_f32_kernel<false>, dim3((unsigned)grid), dim3(512), LDS_REQF4, s, a);
   PNPX_LAUNCH_CHECK();
   return PNPX_OK;
+}
+
+int launch_conv3x3_winof4(const float* u, const float* bias, int cout, const float* in0, int C0, const float* in1, int C1, float* out, int B,
+                          int H, int W, hipStream_t s, float slope, float* pool_out) {
+  return launch_winof4(u, bias, cout, in0, C0, in1, C1, out, B, H, W, s, slope, pool_out, false);
+}
+int launch_conv3x3_winof4_ups(const float* u, const float* bias, int cout, const float* in0, int C0, const float* in1_lowres, int C1,
+                              float* out, int B, int H, int W, hipStream_t s, float slope) {
+  return launch_winof4(u, bias, cout, in0, C0, in1_lowres, C1, out, B, H, W, s, slope, nullptr, true);
 }
 
 }  // namespace pnpx

@@ -22,6 +22,7 @@ struct ConvF32Sel {
   bool wino8 = false;      // the layer's fp32_wino8_layers bit (DRUNet: any bit)
   bool winof4 = false;     // the layer's fp32_winof4_layers bit (DRUNet: never)
   bool winof4_entry = false;   // the layer's fp32_winof4_entries bit (decoder entries 15, 18, 21; DRUNet: never)
+  bool winof4_fuse_up = false; // the layer's fp32_winof4_fuse_up bit (the same entries)
   int ksplit = 0;          // fp32_ksplit (DRUNet: 0)
   int ksplit_rule = 1;     // fp32_ksplit_rule
   bool fuse_up = false;    // fp32_fuse_up
@@ -35,7 +36,8 @@ ConvF32Sel conv_f32_sel_drunet(const pnpx_ctx* ctx, const float* u, const float*
 // B_call: the batch of the whole call (launch chains beside each other count as one call), which the fp32_ksplit = 1 rule reads
 ConvF32Choice conv_f32_forward(const ConvF32Sel& v, int C0, int C1, int cout, int H, int W, int B_call);
 // decoder entry (second source at H/2 x W/2): fused = the instance that up-samples it in the kernel runs; else the forward decision, or
-// WinoF4 (two-source instance on the up-sampled tensor) where fp32_winof4_entries puts the entry
+// WinoF4 where fp32_winof4_entries puts the entry (fused where fp32_winof4_fuse_up and the geometry allow, else the two-source instance
+// on the up-sampled tensor)
 ConvF32Choice conv_f32_entry(const ConvF32Sel& v, int C0, int C1, int cout, int H, int W, int B_call);
 // the UNet's last 3x3 layer: fused = the 1x1 out-conv + residual + clamp ride on `kernel`'s epilogue; else the forward decision
 ConvF32Choice conv_f32_last(const ConvF32Sel& v, int cin, int cout, int H, int W, int B_call);
@@ -55,6 +57,7 @@ struct ConvF32Operands {
   const float* res = nullptr;
   float* pool_out = nullptr;   // MaxPool2d(2) of the output too (Winograd kernels only: ConvF32Choice::fused)
   float* ks_part = nullptr;    // K-split scratch of these B images (used when c.pieces > 1)
+  bool in1_lowres = false;     // decoder entry whose choice is fused on the F(4x4,3x3) kernel: in1 is the second source at H/2 x W/2
 };
 int launch_conv_f32(const ConvF32Choice& c, const ConvF32Sel& v, const ConvLayer& L, const ConvF32Operands& a, hipStream_t s);
 

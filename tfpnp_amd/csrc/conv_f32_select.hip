@@ -9,6 +9,7 @@ ConvF32Sel conv_f32_sel(const pnpx_ctx* ctx, int li) {
   v.wino8 = (ctx->opt_fp32_wino8 >> li) & 1;
   v.winof4 = (ctx->opt_fp32_winof4 >> li) & 1;
   v.winof4_entry = (ctx->opt_fp32_winof4_entries >> li) & 1;
+  v.winof4_fuse_up = (ctx->opt_fp32_winof4_fuse_up >> li) & 1;
   v.ksplit = ctx->opt_fp32_ksplit;
   v.ksplit_rule = ctx->opt_ksplit_rule;
   v.fuse_up = ctx->opt_fp32_fuse_up != 0;
@@ -58,13 +59,15 @@ ConvF32Choice conv_f32_forward(const ConvF32Sel& v, int C0, int C1, int cout, in
 // splits; the fused instance's interpolation pipeline assumes a tile starts in its first, full-resolution source.  (The two forms agree to
 // 2-5e-7; like the K-split itself this is a property of the call's class, not of the batch.)
 // An entry that the 8-wave kernel would run in one piece goes to the F(4x4,3x3) kernel's two-source instance instead when its
-// fp32_winof4_entries bit is set and its weights are packed (levels 1-3).  That kernel has no up-sampling instance: the entry then runs
-// behind the separate up-sampling kernel (fused = false) whatever fp32_fuse_up says.  fp32_winof4_layers is not read here.
+// fp32_winof4_entries bit is set and its weights are packed (levels 1-3).  There the instance that up-samples the low-resolution second
+// source itself runs (fused = true) when the entry's fp32_winof4_fuse_up bit is set and the geometry gives it two chunks of the first source
+// (conv3x3_winof4_ups_ok); otherwise the entry runs behind the separate up-sampling kernel (fused = false).  Both forms write the same bits,
+// and fp32_fuse_up has no say in either.  fp32_winof4_layers is not read here.
 ConvF32Choice conv_f32_entry(const ConvF32Sel& v, int C0, int C1, int cout, int H, int W, int B_call) {
   ConvF32Choice c = conv_f32_forward(v, C0, C1, cout, H, W, B_call);
   if (c.kernel == ConvF32Kernel::Wino8 && c.pieces == 1 && v.winof4_entry && v.u_f4 && conv3x3_winof4_entry_ok(C0, C1, cout, H, W)) {
     c.kernel = ConvF32Kernel::WinoF4;
-    c.fused = false;
+    c.fused = v.winof4_fuse_up && conv3x3_winof4_ups_ok(C0, C1, cout, H, W);
     return c;
   }
   c.fused = c.kernel == ConvF32Kernel::Wino8 && c.pieces == 1 && v.fuse_up && conv3x3_wino8_ups_ok(C0, C1, cout, H, W);
@@ -103,6 +106,7 @@ bool conv_f32_bottom_all8(const pnpx_ctx* ctx, int H, int W, int B_call, ConvF32
 int launch_conv_f32(const ConvF32Choice& c, const ConvF32Sel& v, const ConvLayer& L, const ConvF32Operands& a, hipStream_t s) {
   switch (c.kernel) {
     case ConvF32Kernel::WinoF4:      // no residual operand
+      if (a.in1_lowres) return launch_conv3x3_winof4_ups(v.u_f4, L.b, L.cout, a.in0, a.C0, a.in1, a.C1, a.out, a.B, a.H, a.W, s, a.slope);
       return launch_conv3x3_winof4(v.u_f4, L.b, L.cout, a.in0, a.C0, a.in1, a.C1, a.out, a.B, a.H, a.W, s, a.slope, a.pool_out);
     case ConvF32Kernel::Wino8:
       return launch_conv3x3_wino8(v.u, L.b, L.cout, a.in0, a.C0, a.in1, a.C1, a.out, a.B, a.H, a.W, s, a.slope, a.res, a.pool_out,
@@ -128,6 +132,7 @@ extern "C" int pnpx_conv_f32_entry_plan(int opts, int ksplit, int ksplit_rule, i
   v.fuse_up = opts & 16;
   v.u = (opts & 32) ? &packed : nullptr;
   v.u_f4 = (opts & 64) ? &packed : nullptr;
+  v.winof4_fuse_up = opts & 128;
   v.ksplit = ksplit;
   v.ksplit_rule = ksplit_rule;
   if (C0 <= 0 || C1 <= 0 || cout <= 0 || H <= 0 || W <= 0 || B_call <= 0) return -1;

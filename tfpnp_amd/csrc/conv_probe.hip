@@ -39,7 +39,8 @@ extern "C" int pnpx_conv3x3_probe_plan(int kind, int C0, int C1, int cout, int H
     case PNPX_PROBE_DIRECT_GRAD: return C1 == 0 ? direct_grad_ct(C0, cout) : 0;
     case PNPX_PROBE_WINO8_GRAD: return C1 == 0 && conv3x3_wino8_ok(C0, 0, cout, H, W) ? wct : 0;
     case PNPX_PROBE_WINOF4_2SRC: return C1 > 0 && conv3x3_winof4_entry_ok(C0, C1, cout, H, W) ? 64 : 0;
-    case PNPX_PROBE_WINOF4_UPS: return 0;      // the F(4x4,3x3) kernel has no up-sampling instance
+    case PNPX_PROBE_WINOF4_UPS: return 0;      // reserved before the up-sampling instance existed: still refuses every geometry
+    case PNPX_PROBE_WINOF4_FUSE_UP: return C1 > 0 && conv3x3_winof4_ups_ok(C0, C1, cout, H, W) ? 64 : 0;
   }
   return 0;
 }
@@ -55,7 +56,7 @@ extern "C" int pnpx_conv3x3_probe(pnpx_ctx* ctx, int kind, const float* w_host, 
   PNPX_HIP(hipSetDevice(ctx->device));
   hipStream_t s = static_cast<hipStream_t>(stream);
   const bool grad = is_grad(kind);
-  if (kind < PNPX_PROBE_DIRECT || kind > PNPX_PROBE_WINOF4_UPS) {
+  if (kind < PNPX_PROBE_DIRECT || (kind > PNPX_PROBE_WINOF4_UPS && kind != PNPX_PROBE_WINOF4_FUSE_UP)) {      // (10 is no kind)
     set_error("pnpx_conv3x3_probe: unknown kind %d", kind);
     return PNPX_ERR_ARG;
   }
@@ -74,7 +75,7 @@ extern "C" int pnpx_conv3x3_probe(pnpx_ctx* ctx, int kind, const float* w_host, 
     set_error("pnpx_conv3x3_probe: kind %d is single-source (C1 = %d)", kind, C1);
     return PNPX_ERR_SHAPE;
   }
-  if (kind == PNPX_PROBE_WINOF4_UPS || (kind == PNPX_PROBE_WINOF4_2SRC && C1 == 0)) {
+  if (kind == PNPX_PROBE_WINOF4_UPS || ((kind == PNPX_PROBE_WINOF4_2SRC || kind == PNPX_PROBE_WINOF4_FUSE_UP) && C1 == 0)) {
     set_error(kind == PNPX_PROBE_WINOF4_UPS ? "pnpx_conv3x3_probe: unsupported geometry (kind %d has no instance)"
                                             : "pnpx_conv3x3_probe: unsupported geometry (kind %d needs a second source)", kind);
     return PNPX_ERR_SHAPE;
@@ -100,6 +101,7 @@ extern "C" int pnpx_conv3x3_probe(pnpx_ctx* ctx, int kind, const float* w_host, 
       case PNPX_PROBE_WINOF4: return launch_conv3x3_winof4(pk, b, cout, in0, C0, nullptr, 0, out, B, H, W, s, slope, pool_out);
       case PNPX_PROBE_WINOF4_2SRC: return launch_conv3x3_winof4(pk, b, cout, in0, C0, in1, C1, out, B, H, W, s, slope, pool_out);
       case PNPX_PROBE_WINO8_UPS: return launch_conv3x3_wino8_ups(pk, b, cout, in0, C0, in1, C1, out, B, H, W, s, slope);
+      case PNPX_PROBE_WINOF4_FUSE_UP: return launch_conv3x3_winof4_ups(pk, b, cout, in0, C0, in1, C1, out, B, H, W, s, slope);
       case PNPX_PROBE_DIRECT_GRAD:
         L.mt = cout % 64 == 0 ? 64 : 32;
         L.cc = 8;
@@ -126,6 +128,7 @@ extern "C" int pnpx_conv3x3_probe(pnpx_ctx* ctx, int kind, const float* w_host, 
       break;
     case PNPX_PROBE_WINOF4:
     case PNPX_PROBE_WINOF4_2SRC:
+    case PNPX_PROBE_WINOF4_FUSE_UP:
       host.resize(conv3x3_winof4_floats(cout, cin));
       pack_conv_weights_winof4(w_host, cout, cin, host.data());
       break;
@@ -165,4 +168,18 @@ extern "C" int pnpx_conv3x3_probe(pnpx_ctx* ctx, int kind, const float* w_host, 
   release();
   if (rc == PNPX_OK && e != hipSuccess) rc = hip_fail(e, "hipStreamSynchronize(probe)", __FILE__, __LINE__);
   return rc;
+}
+
+// The fp32 family's separate up-sampling launch on tensors the caller laid out, for tests: what a decoder entry's second source is when
+// no kernel up-samples it itself.
+extern "C" int pnpx_upsample2x_probe(pnpx_ctx* ctx, const float* src, float* dst, int planes, int h, int w, void* stream) {
+  if (!ctx || !src || !dst || planes <= 0 || h <= 0 || w <= 0) {
+    set_error("pnpx_upsample2x_probe: null pointer or non-positive size");
+    return PNPX_ERR_ARG;
+  }
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  PNPX_HIP(hipSetDevice(ctx->device));
+  launch_upsample2x_f32(src, dst, (size_t)planes, h, w, 2 * h, 2 * w, static_cast<hipStream_t>(stream));
+  PNPX_LAUNCH_CHECK();
+  return PNPX_OK;
 }

@@ -435,6 +435,21 @@ inline dim3 g1d(size_t n) { return dim3((unsigned)((n + 255) / 256)); }
 
 }  // namespace
 
+// The fp32 family's up-sampling launch: bc planes of h x w into the 2h x 2w corner of planes of Ht x Wt (unet_forward_f32 and, for tests,
+// pnpx_upsample2x_probe).  The caller checks the launch.
+void launch_upsample2x_f32(const float* src, float* dst, size_t bc, int h, int w, int Ht, int Wt, hipStream_t s) {
+  const float sy = (2 * h > 1) ? (float)(h - 1) / (float)(2 * h - 1) : 0.f;
+  const float sx = (2 * w > 1) ? (float)(w - 1) / (float)(2 * w - 1) : 0.f;
+  if ((2 * w) % 4 == 0 && bc <= 65535) {
+    const int quads = w / 2, bx = quads >= 64 ? 64 : quads, by = 256 / bx;
+    hipLaunchKernelGGL(upsample2x_v4_kernel, dim3((quads + bx - 1) / bx, (2 * h + by * UPS_ROWS - 1) / (by * UPS_ROWS), (unsigned)bc), dim3(bx, by), 0, s,
+                       src, dst, h, w, Ht, Wt, sy, sx);
+  } else {
+    const size_t n_up = bc * (2 * h) * (2 * w);
+    hipLaunchKernelGGL(upsample2x_kernel, g1d(n_up), dim3(256), 0, s, src, dst, n_up, h, w, Ht, Wt, sy, sx);
+  }
+}
+
 // Half-split forward pass.  Levels 0 and 1 (the memory-bound, shallow-K layers) can be processed in sub-batches so
 // that a ConvBlock's temporaries are re-read soon after they were written (PNPX_SUBBATCH images at level 0, twice
 // that at level 1; 0 = whole batch).  Measured (B=48, 256^2): r1 6.58 ms whole batch, 6.38 ms at 24; with the r3 kernels
@@ -693,9 +708,6 @@ static int unet_forward_f32(pnpx_ctx* ctx, UNetArena& ar, const UNetPlan& P, con
   const Act* below = &P.x[4];
   for (int l = 3; l >= 0; --l) {
     const int h = below->H, w = below->W;
-    const float sy = (2 * h > 1) ? (float)(h - 1) / (float)(2 * h - 1) : 0.f;
-    const float sx = (2 * w > 1) ? (float)(w - 1) / (float)(2 * w - 1) : 0.f;
-    const size_t n_up = (size_t)B * below->C * (2 * h) * (2 * w);
     // r5: the decoder entry interpolates its second source itself (conv3x3_wino8.hip UPS instances: the low-resolution window of a
     // chunk's halo staged in LDS, bilinear x2 into the halo buffer) -- no up-sampled tensor in HBM (models/unet.py:92-121)
     const int li0 = 15 + 3 * (3 - l);
@@ -705,25 +717,17 @@ static int unet_forward_f32(pnpx_ctx* ctx, UNetArena& ar, const UNetPlan& P, con
     const bool even = P.x[l].H == 2 * h && P.x[l].W == 2 * w;
     const ConvF32Choice c0 = even ? conv_f32_entry(v0, P.x[l].C, below->C, ctx->conv[li0].cout, 2 * h, 2 * w, B_call) : ConvF32Choice();
     const bool ups_fused = c0.fused;
-    if (ups_fused) {
-      // nothing to launch
-    } else if ((2 * w) % 4 == 0 && (size_t)B * below->C <= 65535) {
-      const int quads = w / 2, bx = quads >= 64 ? 64 : quads, by = 256 / bx;
-      hipLaunchKernelGGL(upsample2x_v4_kernel, dim3((quads + bx - 1) / bx, (2 * h + by * UPS_ROWS - 1) / (by * UPS_ROWS), B * below->C), dim3(bx, by), 0, s,
-                         fptr(*below), fptr(P.u[l]), h, w, P.u[l].H, P.u[l].W, sy, sx);
-    } else {
-      hipLaunchKernelGGL(upsample2x_kernel, g1d(n_up), dim3(256), 0, s, fptr(*below), fptr(P.u[l]), n_up, h, w, P.u[l].H,
-                         P.u[l].W, sy, sx);
-    }
     if (!ups_fused) {
+      launch_upsample2x_f32(fptr(*below), fptr(P.u[l]), (size_t)B * below->C, h, w, P.u[l].H, P.u[l].W, s);
       PNPX_LAUNCH_CHECK();
       PNPX_TRY(rec.mark("upsample2x", 0));
     }
     // first convolution of a decoder block: the fused instance reads the low-resolution tensor
     auto entry = [&](const Act& ta) -> int {
       const ConvLayer& L = ctx->conv[li0];
-      if (c0.kernel == ConvF32Kernel::WinoF4) {      // the F(4x4,3x3) two-source instance on the up-sampled tensor
-        ConvF32Operands a{fptr(P.x[l]), P.x[l].C, fptr(P.u[l]), P.u[l].C, fptr(ta), B, ta.H, ta.W};
+      if (c0.kernel == ConvF32Kernel::WinoF4) {      // the F(4x4,3x3) kernel: on the up-sampled tensor, or (fused) on the low-resolution one
+        ConvF32Operands a{fptr(P.x[l]), P.x[l].C, ups_fused ? fptr(*below) : fptr(P.u[l]), P.u[l].C, fptr(ta), B, ta.H, ta.W};
+        a.in1_lowres = ups_fused;
         PNPX_TRY(launch_conv_f32(c0, v0, L, a, s));
         return rec.mark("conv3x3_wino", 2.0 * 9.0 * L.cin * L.cout * (double)ta.H * ta.W * B);
       }
