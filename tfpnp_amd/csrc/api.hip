@@ -6,6 +6,7 @@
 #include "common.h"
 #include "conv3x3.h"
 #include "conv_hs.h"
+#include "solver_loop.h"   // LOCK_CTX
 
 namespace pnpx {
 
@@ -116,14 +117,6 @@ int range_guard_strict(pnpx_ctx* ctx, hipStream_t s, bool* rerun) {
 }  // namespace pnpx
 
 using namespace pnpx;
-
-#define LOCK_CTX(ctx)                         \
-  if (!(ctx)) {                               \
-    pnpx::set_error("null context");          \
-    return PNPX_ERR_ARG;                      \
-  }                                           \
-  std::lock_guard<std::mutex> _lk((ctx)->mu); \
-  PNPX_HIP(hipSetDevice((ctx)->device))
 
 extern "C" {
 

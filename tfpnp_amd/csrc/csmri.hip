@@ -9,6 +9,7 @@
 // operation order, e.g. temp = ((mu * k) + y0) / (1 + mu)  (tasks/csmri/solver.py:50).
 #include "common.h"
 #include "fft_lds.h"
+#include "solver_loop.h"
 
 namespace pnpx {
 
@@ -436,10 +437,8 @@ inline dim3 g1(size_t n) { return dim3((unsigned)((n + 255) / 256)); }
 
 int check_common(const void* a, const void* b, const void* c, const void* d, const void* e, int B, int H, int W,
                  int T, int stride) {
-  if (!a || !b || !c || !d || !e || B <= 0 || T < 0 || stride < T) {
-    set_error("csmri: bad argument (null pointer, B<=0 or param_stride < T)");
-    return PNPX_ERR_ARG;
-  }
+  REQUIRE(a && b && c && d && e && B > 0 && T >= 0 && stride >= T,
+          "csmri: bad argument (null pointer, B<=0 or param_stride < T)");
   (void)H;
   (void)W;
   return PNPX_OK;
@@ -451,14 +450,6 @@ int check_common(const void* a, const void* b, const void* c, const void* d, con
 
 using namespace pnpx;
 
-#define LOCK_CTX(ctx)                                  \
-  if (!(ctx)) {                                        \
-    pnpx::set_error("null context");                   \
-    return PNPX_ERR_ARG;                               \
-  }                                                    \
-  std::lock_guard<std::mutex> _lk((ctx)->mu);          \
-  PNPX_HIP(hipSetDevice((ctx)->device))
-
 // ADMM forward; `saved` != NULL (training path) keeps, per iteration, the denoiser input d_i [T][B][HW] floats followed
 // by the k-space image before the blend k_i [T][B][HW] complex, and parks the denoiser activations of every iteration
 // in the context's training ring (unet_denoise_train): iteration i holds ticket *ticket_out + i (tickets are handed
@@ -467,37 +458,24 @@ static int admm_forward(pnpx_ctx* ctx, const float* vars_in, float* vars_out, co
                         const float* sigma_d, const float* mu, int param_stride, int B, int H, int W, int T,
                         float* saved, hipStream_t s, unsigned long long* ticket_out = nullptr) {
   PNPX_TRY(check_common(vars_in, vars_out, y0, mask, sigma_d, B, H, W, T, param_stride));
-  if (ticket_out) *ticket_out = 0;
-  const bool park = saved && ticket_out;
-  const int HW = H * W;
-  const size_t is = 3 * (size_t)HW;
+  const Prox px = prox_begin(ctx, sigma_d, param_stride, B, H, W, saved, ticket_out, s);
+  const auto [HW, is, n] = state_dims(B, H, W, 3);
   Scratch S;
   PNPX_TRY(get_scratch(ctx, B, H, W, &S));
   FftPlan2D P;
   PNPX_TRY(make_fft_plan(ctx, B, H, W, true, &P));
   const float2* vin = reinterpret_cast<const float2*>(vars_in);
   float2* vout = reinterpret_cast<float2*>(vars_out);
-  if (T == 0) {
-    PNPX_HIP(hipMemcpyAsync(vars_out, vars_in, sizeof(float2) * is * B, hipMemcpyDeviceToDevice, s));
-    return PNPX_OK;
-  }
+  if (T == 0) return copy_state(vars_out, vars_in, sizeof(float2) * is * B, s);
   // d0 = Re(z - u)                                                   tasks/csmri/solver.py:45
-  hipLaunchKernelGGL(real_of_diff_kernel, g1((size_t)HW * B), dim3(256), 0, s, vin + HW, vin + 2 * HW, is, S.d, HW, B);
+  hipLaunchKernelGGL(real_of_diff_kernel, g1(n), dim3(256), 0, s, vin + HW, vin + 2 * HW, is, S.d, HW, B);
   PNPX_LAUNCH_CHECK();
   RealImg xr{S.xr, W, HW}, d{S.d, W, HW};
   Slot xo{vout, is, W, HW}, zo{vout + HW, is, W, HW}, uo{vout + 2 * HW, is, W, HW};
   StoreC kst{S.k, H, W};
   LoadC kld{S.k, H, W};
   for (int i = 0; i < T; ++i) {
-    if (saved)
-      PNPX_HIP(hipMemcpyAsync(saved + (size_t)i * B * HW, S.d, sizeof(float) * B * HW, hipMemcpyDeviceToDevice, s));
-    if (park) {
-      unsigned long long tk = 0;
-      PNPX_TRY(unet_denoise_train(ctx, S.d, sigma_d + i, param_stride, S.xr, B, H, W, s, &tk));
-      if (i == 0) *ticket_out = tk;
-    } else {
-      PNPX_TRY(unet_denoise(ctx, S.d, sigma_d + i, param_stride, S.xr, nullptr, B, H, W, s, nullptr));
-    }
+    PNPX_TRY(prox_step(px, i, S.d, S.xr, saved ? saved + (size_t)i * n : nullptr));
     CSlot ui{(i == 0 ? vin : vout) + 2 * HW, is, W, HW};
     PNPX_TRY((launch_rows<false>(P, LoadXrPlusU{xr, ui}, kst, s)));
     KSpace ks{reinterpret_cast<const float2*>(y0), mask, mu + i, param_stride, W, HW};
@@ -515,9 +493,7 @@ static int admm_forward(pnpx_ctx* ctx, const float* vars_in, float* vars_out, co
 extern "C" int pnpx_csmri_admm(pnpx_ctx* ctx, const float* vars_in, float* vars_out, const float* y0,
                                const uint8_t* mask, const float* sigma_d, const float* mu, int param_stride, int B,
                                int H, int W, int T, void* stream) {
-  LOCK_CTX(ctx);
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  return pnpx::guarded(ctx, s, [&]() -> int {
+  return solver_entry(ctx, stream, [&](hipStream_t s) {
     return admm_forward(ctx, vars_in, vars_out, y0, mask, sigma_d, mu, param_stride, B, H, W, T, nullptr, s);
   });
 }
@@ -526,13 +502,7 @@ extern "C" int pnpx_csmri_admm_train(pnpx_ctx* ctx, const float* vars_in, float*
                                      const uint8_t* mask, const float* sigma_d, const float* mu, int param_stride,
                                      int B, int H, int W, int T, float* saved, unsigned long long* ticket,
                                      void* stream) {
-  LOCK_CTX(ctx);
-  if ((!saved && T > 0) || !ticket) {
-    pnpx::set_error("csmri_admm_train: saved / ticket is null");
-    return PNPX_ERR_ARG;
-  }
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  return pnpx::guarded(ctx, s, [&]() -> int {
+  return solver_train_entry(ctx, "csmri_admm_train", saved || T <= 0, ticket, stream, [&](hipStream_t s) {
     return admm_forward(ctx, vars_in, vars_out, y0, mask, sigma_d, mu, param_stride, B, H, W, T, saved, s, ticket);
   });
 }
@@ -546,23 +516,16 @@ extern "C" int pnpx_csmri_admm_backward(pnpx_ctx* ctx, const float* y0, const ui
                                         const float* grad_vars_out, float* grad_vars_in, float* grad_sigma_d,
                                         float* grad_mu, float* work, int B, int H, int W, int T,
                                         unsigned long long ticket, void* stream) {
-  LOCK_CTX(ctx);
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  return pnpx::guarded(ctx, s, [&]() -> int {
+  return solver_entry(ctx, stream, [&](hipStream_t s) -> int {
     PNPX_TRY(check_common(grad_vars_out, grad_vars_in, y0, mask, sigma_d, B, H, W, T, param_stride));
-    if (T > 0 && (!saved || !grad_sigma_d || !grad_mu || !work || !mu)) {
-      set_error("csmri_admm_backward: null pointer");
-      return PNPX_ERR_ARG;
-    }
-    const int HW = H * W;
-    const size_t is = 3 * (size_t)HW, n = (size_t)B * HW;
-    PNPX_HIP(hipMemcpyAsync(grad_vars_in, grad_vars_out, sizeof(float2) * is * B, hipMemcpyDeviceToDevice, s));
+    REQUIRE(T <= 0 || (saved && grad_sigma_d && grad_mu && work && mu), "csmri_admm_backward: null pointer");
+    const auto [HW, is, n] = state_dims(B, H, W, 3);
+    PNPX_TRY(copy_state(grad_vars_in, grad_vars_out, sizeof(float2) * is * B, s));
     if (T == 0) return PNPX_OK;
     FftPlan2D P;
     PNPX_TRY(make_fft_plan(ctx, B, H, W, true, &P));
     float2* g = reinterpret_cast<float2*>(grad_vars_in);
     float *gxr = work, *gd = work + n, *contrib = work + 2 * n;
-    const float* saved_d = saved;
     const float2* saved_k = reinterpret_cast<const float2*>(saved + (size_t)T * n);
 
     for (int i = T - 1; i >= 0; --i) {
@@ -578,9 +541,7 @@ extern "C" int pnpx_csmri_admm_backward(pnpx_ctx* ctx, const float* y0, const ui
       PNPX_TRY((launch_rows<true>(P, kld, StoreAdmmAdjoint{gu, gx, RealImg{gxr, W, HW}}, s)));
       hipLaunchKernelGGL(item_sum_kernel, dim3(B), dim3(256), 0, s, contrib, grad_mu + (size_t)i * B, HW);
       PNPX_LAUNCH_CHECK();
-      // iteration i parked its activations under ticket + i (if the ring still holds them; else re-computation)
-      PNPX_TRY(unet_denoise_backward_ticket(ctx, saved_d + (size_t)i * n, sigma_d + i, param_stride, gxr, gd,
-                                            grad_sigma_d + (size_t)i * B, B, H, W, s, ticket ? ticket + i : 0));
+      PNPX_TRY(prox_vjp(ctx, i, saved, sigma_d, param_stride, gxr, gd, grad_sigma_d, B, H, W, s, ticket));
       hipLaunchKernelGGL(admm_adjoint_finish_kernel, g1(n), dim3(256), 0, s, gd, g, is, HW, B);
       PNPX_LAUNCH_CHECK();
     }
@@ -594,37 +555,23 @@ static int hqs_forward(pnpx_ctx* ctx, const float* vars_in, float* vars_out, con
                        const float* sigma_d, const float* mu, int param_stride, int B, int H, int W, int T, float* saved,
                        hipStream_t s, unsigned long long* ticket_out = nullptr) {
   PNPX_TRY(check_common(vars_in, vars_out, y0, mask, sigma_d, B, H, W, T, param_stride));
-  if (ticket_out) *ticket_out = 0;
-  const bool park = saved && ticket_out;
-  const int HW = H * W;
-  const size_t is = 2 * (size_t)HW;
+  const Prox px = prox_begin(ctx, sigma_d, param_stride, B, H, W, saved, ticket_out, s);
+  const auto [HW, is, n] = state_dims(B, H, W, 2);
   Scratch S;
   PNPX_TRY(get_scratch(ctx, B, H, W, &S));
   FftPlan2D P;
   PNPX_TRY(make_fft_plan(ctx, B, H, W, true, &P));
   const float2* vin = reinterpret_cast<const float2*>(vars_in);
   float2* vout = reinterpret_cast<float2*>(vars_out);
-  if (T == 0) {
-    PNPX_HIP(hipMemcpyAsync(vars_out, vars_in, sizeof(float2) * is * B, hipMemcpyDeviceToDevice, s));
-    return PNPX_OK;
-  }
-  hipLaunchKernelGGL(real_of_diff_kernel, g1((size_t)HW * B), dim3(256), 0, s, vin + HW, (const float2*)nullptr, is,
-                     S.d, HW, B);
+  if (T == 0) return copy_state(vars_out, vars_in, sizeof(float2) * is * B, s);
+  hipLaunchKernelGGL(real_of_diff_kernel, g1(n), dim3(256), 0, s, vin + HW, (const float2*)nullptr, is, S.d, HW, B);
   PNPX_LAUNCH_CHECK();
   RealImg xr{S.xr, W, HW}, d{S.d, W, HW};
   Slot xo{vout, is, W, HW}, zo{vout + HW, is, W, HW};
   StoreC kst{S.k, H, W};
   LoadC kld{S.k, H, W};
   for (int i = 0; i < T; ++i) {
-    if (saved)
-      PNPX_HIP(hipMemcpyAsync(saved + (size_t)i * B * HW, S.d, sizeof(float) * B * HW, hipMemcpyDeviceToDevice, s));
-    if (park) {
-      unsigned long long tk = 0;
-      PNPX_TRY(unet_denoise_train(ctx, S.d, sigma_d + i, param_stride, S.xr, B, H, W, s, &tk));
-      if (i == 0) *ticket_out = tk;
-    } else {
-      PNPX_TRY(unet_denoise(ctx, S.d, sigma_d + i, param_stride, S.xr, nullptr, B, H, W, s, nullptr));
-    }
+    PNPX_TRY(prox_step(px, i, S.d, S.xr, saved ? saved + (size_t)i * n : nullptr));
     PNPX_TRY((launch_rows<false>(P, LoadXr{xr}, kst, s)));
     KSpace ks{reinterpret_cast<const float2*>(y0), mask, mu + i, param_stride, W, HW};
     if (saved) {
@@ -641,9 +588,7 @@ static int hqs_forward(pnpx_ctx* ctx, const float* vars_in, float* vars_out, con
 extern "C" int pnpx_csmri_hqs(pnpx_ctx* ctx, const float* vars_in, float* vars_out, const float* y0,
                               const uint8_t* mask, const float* sigma_d, const float* mu, int param_stride, int B,
                               int H, int W, int T, void* stream) {
-  LOCK_CTX(ctx);
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  return pnpx::guarded(ctx, s, [&]() -> int {
+  return solver_entry(ctx, stream, [&](hipStream_t s) {
     return hqs_forward(ctx, vars_in, vars_out, y0, mask, sigma_d, mu, param_stride, B, H, W, T, nullptr, s);
   });
 }
@@ -651,13 +596,7 @@ extern "C" int pnpx_csmri_hqs(pnpx_ctx* ctx, const float* vars_in, float* vars_o
 extern "C" int pnpx_csmri_hqs_train(pnpx_ctx* ctx, const float* vars_in, float* vars_out, const float* y0,
                                     const uint8_t* mask, const float* sigma_d, const float* mu, int param_stride, int B,
                                     int H, int W, int T, float* saved, unsigned long long* ticket, void* stream) {
-  LOCK_CTX(ctx);
-  if ((!saved && T > 0) || !ticket) {
-    pnpx::set_error("csmri_hqs_train: saved / ticket is null");
-    return PNPX_ERR_ARG;
-  }
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  return pnpx::guarded(ctx, s, [&]() -> int {
+  return solver_train_entry(ctx, "csmri_hqs_train", saved || T <= 0, ticket, stream, [&](hipStream_t s) {
     return hqs_forward(ctx, vars_in, vars_out, y0, mask, sigma_d, mu, param_stride, B, H, W, T, saved, s, ticket);
   });
 }
@@ -671,23 +610,16 @@ extern "C" int pnpx_csmri_hqs_backward(pnpx_ctx* ctx, const float* y0, const uin
                                        const float* grad_vars_out, float* grad_vars_in, float* grad_sigma_d,
                                        float* grad_mu, float* work, int B, int H, int W, int T,
                                        unsigned long long ticket, void* stream) {
-  LOCK_CTX(ctx);
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  return pnpx::guarded(ctx, s, [&]() -> int {
+  return solver_entry(ctx, stream, [&](hipStream_t s) -> int {
     PNPX_TRY(check_common(grad_vars_out, grad_vars_in, y0, mask, sigma_d, B, H, W, T, param_stride));
-    if (T > 0 && (!saved || !grad_sigma_d || !grad_mu || !work || !mu)) {
-      set_error("csmri_hqs_backward: null pointer");
-      return PNPX_ERR_ARG;
-    }
-    const int HW = H * W;
-    const size_t is = 2 * (size_t)HW, n = (size_t)B * HW;
-    PNPX_HIP(hipMemcpyAsync(grad_vars_in, grad_vars_out, sizeof(float2) * is * B, hipMemcpyDeviceToDevice, s));
+    REQUIRE(T <= 0 || (saved && grad_sigma_d && grad_mu && work && mu), "csmri_hqs_backward: null pointer");
+    const auto [HW, is, n] = state_dims(B, H, W, 2);
+    PNPX_TRY(copy_state(grad_vars_in, grad_vars_out, sizeof(float2) * is * B, s));
     if (T == 0) return PNPX_OK;
     FftPlan2D P;
     PNPX_TRY(make_fft_plan(ctx, B, H, W, true, &P));
     float2* g = reinterpret_cast<float2*>(grad_vars_in);
     float *gxr = work, *gd = work + n, *contrib = work + 2 * n;
-    const float* saved_d = saved;
     const float2* saved_k = reinterpret_cast<const float2*>(saved + (size_t)T * n);
     for (int i = T - 1; i >= 0; --i) {
       Scratch S;
@@ -701,8 +633,7 @@ extern "C" int pnpx_csmri_hqs_backward(pnpx_ctx* ctx, const float* y0, const uin
       PNPX_TRY((launch_rows<true>(P, kld, StoreHqsAdjoint{gx, RealImg{gxr, W, HW}}, s)));
       hipLaunchKernelGGL(item_sum_kernel, dim3(B), dim3(256), 0, s, contrib, grad_mu + (size_t)i * B, HW);
       PNPX_LAUNCH_CHECK();
-      PNPX_TRY(unet_denoise_backward_ticket(ctx, saved_d + (size_t)i * n, sigma_d + i, param_stride, gxr, gd,
-                                            grad_sigma_d + (size_t)i * B, B, H, W, s, ticket ? ticket + i : 0));
+      PNPX_TRY(prox_vjp(ctx, i, saved, sigma_d, param_stride, gxr, gd, grad_sigma_d, B, H, W, s, ticket));
       hipLaunchKernelGGL(hqs_adjoint_finish_kernel, g1(n), dim3(256), 0, s, gd, g, is, HW, B);
       PNPX_LAUNCH_CHECK();
     }
@@ -716,20 +647,15 @@ static int pg_forward(pnpx_ctx* ctx, const float* vars_in, float* vars_out, cons
                       const float* sigma_d, const float* tau, int param_stride, int B, int H, int W, int T, float* saved,
                       hipStream_t s, unsigned long long* ticket_out = nullptr) {
   PNPX_TRY(check_common(vars_in, vars_out, y0, mask, sigma_d, B, H, W, T, param_stride));
-  if (ticket_out) *ticket_out = 0;
-  const bool park = saved && ticket_out;
-  const int HW = H * W;
-  const size_t is = (size_t)HW;
+  const Prox px = prox_begin(ctx, sigma_d, param_stride, B, H, W, saved, ticket_out, s);
+  const auto [HW, is, n] = state_dims(B, H, W, 1);
   Scratch S;
   PNPX_TRY(get_scratch(ctx, B, H, W, &S));
   FftPlan2D P;
   PNPX_TRY(make_fft_plan(ctx, B, H, W, true, &P));
   const float2* vin = reinterpret_cast<const float2*>(vars_in);
   float2* vout = reinterpret_cast<float2*>(vars_out);
-  if (T == 0) {
-    PNPX_HIP(hipMemcpyAsync(vars_out, vars_in, sizeof(float2) * is * B, hipMemcpyDeviceToDevice, s));
-    return PNPX_OK;
-  }
+  if (T == 0) return copy_state(vars_out, vars_in, sizeof(float2) * is * B, s);
   RealImg xr{S.xr, W, HW}, d{S.d, W, HW};
   StoreC kst{S.k, H, W};
   LoadC kld{S.k, H, W};
@@ -740,19 +666,11 @@ static int pg_forward(pnpx_ctx* ctx, const float* vars_in, float* vars_out, cons
     else PNPX_TRY((launch_rows<false>(P, LoadXr{xr}, kst, s)));
     KSpace ks{reinterpret_cast<const float2*>(y0), mask, tau + i, param_stride, W, HW};
     PNPX_TRY((launch_cols<false, true>(P, kld, MidResidual{ks}, kst, s)));
-    float* wsave = saved ? saved + ((size_t)T + i) * B * HW : nullptr;
+    float* wsave = saved ? saved + ((size_t)T + i) * n : nullptr;
     PNPX_TRY((launch_rows<true>(P, kld, StoreGrad{x0, xr, i != 0, tau + i, param_stride, d, wsave}, s)));
-    if (saved)
-      PNPX_HIP(hipMemcpyAsync(saved + (size_t)i * B * HW, S.d, sizeof(float) * B * HW, hipMemcpyDeviceToDevice, s));
-    if (park) {
-      unsigned long long tk = 0;
-      PNPX_TRY(unet_denoise_train(ctx, S.d, sigma_d + i, param_stride, S.xr, B, H, W, s, &tk));
-      if (i == 0) *ticket_out = tk;
-    } else {
-      PNPX_TRY(unet_denoise(ctx, S.d, sigma_d + i, param_stride, S.xr, nullptr, B, H, W, s, nullptr));
-    }
+    PNPX_TRY(prox_step(px, i, S.d, S.xr, saved ? saved + (size_t)i * n : nullptr));
   }
-  hipLaunchKernelGGL(real_to_slot_kernel, g1((size_t)HW * B), dim3(256), 0, s, S.xr, vout, is, HW, B);
+  hipLaunchKernelGGL(real_to_slot_kernel, g1(n), dim3(256), 0, s, S.xr, vout, is, HW, B);
   PNPX_LAUNCH_CHECK();
   return PNPX_OK;
 }
@@ -760,9 +678,7 @@ static int pg_forward(pnpx_ctx* ctx, const float* vars_in, float* vars_out, cons
 extern "C" int pnpx_csmri_pg(pnpx_ctx* ctx, const float* vars_in, float* vars_out, const float* y0,
                              const uint8_t* mask, const float* sigma_d, const float* tau, int param_stride, int B,
                              int H, int W, int T, void* stream) {
-  LOCK_CTX(ctx);
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  return pnpx::guarded(ctx, s, [&]() -> int {
+  return solver_entry(ctx, stream, [&](hipStream_t s) {
     return pg_forward(ctx, vars_in, vars_out, y0, mask, sigma_d, tau, param_stride, B, H, W, T, nullptr, s);
   });
 }
@@ -770,13 +686,7 @@ extern "C" int pnpx_csmri_pg(pnpx_ctx* ctx, const float* vars_in, float* vars_ou
 extern "C" int pnpx_csmri_pg_train(pnpx_ctx* ctx, const float* vars_in, float* vars_out, const float* y0,
                                    const uint8_t* mask, const float* sigma_d, const float* tau, int param_stride, int B,
                                    int H, int W, int T, float* saved, unsigned long long* ticket, void* stream) {
-  LOCK_CTX(ctx);
-  if ((!saved && T > 0) || !ticket) {
-    pnpx::set_error("csmri_pg_train: saved / ticket is null");
-    return PNPX_ERR_ARG;
-  }
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  return pnpx::guarded(ctx, s, [&]() -> int {
+  return solver_train_entry(ctx, "csmri_pg_train", saved || T <= 0, ticket, stream, [&](hipStream_t s) {
     return pg_forward(ctx, vars_in, vars_out, y0, mask, sigma_d, tau, param_stride, B, H, W, T, saved, s, ticket);
   });
 }
@@ -790,20 +700,11 @@ extern "C" int pnpx_csmri_pg_backward(pnpx_ctx* ctx, const float* y0, const uint
                                       const float* grad_vars_out, float* grad_vars_in, float* grad_sigma_d,
                                       float* grad_tau, float* work, int B, int H, int W, int T,
                                       unsigned long long ticket, void* stream) {
-  LOCK_CTX(ctx);
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  return pnpx::guarded(ctx, s, [&]() -> int {
+  return solver_entry(ctx, stream, [&](hipStream_t s) -> int {
     PNPX_TRY(check_common(grad_vars_out, grad_vars_in, y0, mask, sigma_d, B, H, W, T, param_stride));
-    if (T > 0 && (!saved || !grad_sigma_d || !grad_tau || !work || !tau)) {
-      set_error("csmri_pg_backward: null pointer");
-      return PNPX_ERR_ARG;
-    }
-    const int HW = H * W;
-    const size_t is = (size_t)HW, n = (size_t)B * HW;
-    if (T == 0) {
-      PNPX_HIP(hipMemcpyAsync(grad_vars_in, grad_vars_out, sizeof(float2) * is * B, hipMemcpyDeviceToDevice, s));
-      return PNPX_OK;
-    }
+    REQUIRE(T <= 0 || (saved && grad_sigma_d && grad_tau && work && tau), "csmri_pg_backward: null pointer");
+    const auto [HW, is, n] = state_dims(B, H, W, 1);
+    if (T == 0) return copy_state(grad_vars_in, grad_vars_out, sizeof(float2) * is * B, s);
     FftPlan2D P;
     PNPX_TRY(make_fft_plan(ctx, B, H, W, true, &P));
     float *gxr = work, *gd = work + n, *contrib = work + 2 * n;
@@ -812,8 +713,7 @@ extern "C" int pnpx_csmri_pg_backward(pnpx_ctx* ctx, const float* y0, const uint
                        (const float2*)nullptr, is, gxr, HW, B);
     PNPX_LAUNCH_CHECK();
     for (int i = T - 1; i >= 0; --i) {
-      PNPX_TRY(unet_denoise_backward_ticket(ctx, saved + (size_t)i * n, sigma_d + i, param_stride, gxr, gd,
-                                            grad_sigma_d + (size_t)i * B, B, H, W, s, ticket ? ticket + i : 0));
+      PNPX_TRY(prox_vjp(ctx, i, saved, sigma_d, param_stride, gxr, gd, grad_sigma_d, B, H, W, s, ticket));
       Scratch S;
       PNPX_TRY(get_scratch(ctx, B, H, W, &S));
       StoreC kst{S.k, H, W};
@@ -838,20 +738,15 @@ static int apg_forward(pnpx_ctx* ctx, const float* vars_in, float* vars_out, con
                        const float* sigma_d, const float* tau, const float* beta, int param_stride, int B, int H, int W,
                        int T, float* saved, hipStream_t s, unsigned long long* ticket_out = nullptr) {
   PNPX_TRY(check_common(vars_in, vars_out, y0, mask, sigma_d, B, H, W, T, param_stride));
-  if (!beta || !tau) {
-    set_error("csmri_apg: null tau/beta");
-    return PNPX_ERR_ARG;
-  }
-  if (ticket_out) *ticket_out = 0;
-  const bool park = saved && ticket_out;
-  const int HW = H * W;
-  const size_t is = 2 * (size_t)HW, n = (size_t)B * HW;
+  REQUIRE(beta && tau, "csmri_apg: null tau/beta");
+  const Prox px = prox_begin(ctx, sigma_d, param_stride, B, H, W, saved, ticket_out, s);
+  const auto [HW, is, n] = state_dims(B, H, W, 2);
   Scratch S;
   PNPX_TRY(get_scratch(ctx, B, H, W, &S));
   FftPlan2D P;
   PNPX_TRY(make_fft_plan(ctx, B, H, W, true, &P));
   float2* vout = reinterpret_cast<float2*>(vars_out);
-  PNPX_HIP(hipMemcpyAsync(vars_out, vars_in, sizeof(float2) * is * B, hipMemcpyDeviceToDevice, s));
+  PNPX_TRY(copy_state(vars_out, vars_in, sizeof(float2) * is * B, s));   // the loop updates the state in place
   RealImg xr{S.xr, W, HW}, d{S.d, W, HW};
   StoreC kst{S.k, H, W};
   LoadC kld{S.k, H, W};
@@ -862,14 +757,7 @@ static int apg_forward(pnpx_ctx* ctx, const float* vars_in, float* vars_out, con
     PNPX_TRY((launch_cols<false, true>(P, kld, MidResidual{ks}, kst, s)));
     float* wsave = saved ? saved + ((size_t)T + i) * n : nullptr;
     PNPX_TRY((launch_rows<true>(P, kld, StoreGrad{sc, xr, 0, tau + i, param_stride, d, wsave}, s)));
-    if (saved) PNPX_HIP(hipMemcpyAsync(saved + (size_t)i * n, S.d, sizeof(float) * n, hipMemcpyDeviceToDevice, s));
-    if (park) {
-      unsigned long long tk = 0;
-      PNPX_TRY(unet_denoise_train(ctx, S.d, sigma_d + i, param_stride, S.xr, B, H, W, s, &tk));
-      if (i == 0) *ticket_out = tk;
-    } else {
-      PNPX_TRY(unet_denoise(ctx, S.d, sigma_d + i, param_stride, S.xr, nullptr, B, H, W, s, nullptr));
-    }
+    PNPX_TRY(prox_step(px, i, S.d, S.xr, saved ? saved + (size_t)i * n : nullptr));
     if (saved) {
       float2* diff = reinterpret_cast<float2*>(saved + 2 * (size_t)T * n) + (size_t)i * n;
       hipLaunchKernelGGL(apg_update_save_kernel, g1(n), dim3(256), 0, s, S.xr, vout, vout, vout + HW, is, beta + i,
@@ -886,9 +774,7 @@ static int apg_forward(pnpx_ctx* ctx, const float* vars_in, float* vars_out, con
 extern "C" int pnpx_csmri_apg(pnpx_ctx* ctx, const float* vars_in, float* vars_out, const float* y0,
                               const uint8_t* mask, const float* sigma_d, const float* tau, const float* beta,
                               int param_stride, int B, int H, int W, int T, void* stream) {
-  LOCK_CTX(ctx);
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  return pnpx::guarded(ctx, s, [&]() -> int {
+  return solver_entry(ctx, stream, [&](hipStream_t s) {
     return apg_forward(ctx, vars_in, vars_out, y0, mask, sigma_d, tau, beta, param_stride, B, H, W, T, nullptr, s);
   });
 }
@@ -897,13 +783,7 @@ extern "C" int pnpx_csmri_apg_train(pnpx_ctx* ctx, const float* vars_in, float* 
                                     const uint8_t* mask, const float* sigma_d, const float* tau, const float* beta,
                                     int param_stride, int B, int H, int W, int T, float* saved,
                                     unsigned long long* ticket, void* stream) {
-  LOCK_CTX(ctx);
-  if ((!saved && T > 0) || !ticket) {
-    pnpx::set_error("csmri_apg_train: saved / ticket is null");
-    return PNPX_ERR_ARG;
-  }
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  return pnpx::guarded(ctx, s, [&]() -> int {
+  return solver_train_entry(ctx, "csmri_apg_train", saved || T <= 0, ticket, stream, [&](hipStream_t s) {
     return apg_forward(ctx, vars_in, vars_out, y0, mask, sigma_d, tau, beta, param_stride, B, H, W, T, saved, s, ticket);
   });
 }
@@ -917,17 +797,12 @@ extern "C" int pnpx_csmri_apg_backward(pnpx_ctx* ctx, const float* y0, const uin
                                        const float* grad_vars_out, float* grad_vars_in, float* grad_sigma_d,
                                        float* grad_tau, float* grad_beta, float* work, int B, int H, int W, int T,
                                        unsigned long long ticket, void* stream) {
-  LOCK_CTX(ctx);
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  return pnpx::guarded(ctx, s, [&]() -> int {
+  return solver_entry(ctx, stream, [&](hipStream_t s) -> int {
     PNPX_TRY(check_common(grad_vars_out, grad_vars_in, y0, mask, sigma_d, B, H, W, T, param_stride));
-    if (T > 0 && (!saved || !grad_sigma_d || !grad_tau || !grad_beta || !work || !tau || !beta)) {
-      set_error("csmri_apg_backward: null pointer");
-      return PNPX_ERR_ARG;
-    }
-    const int HW = H * W;
-    const size_t is = 2 * (size_t)HW, n = (size_t)B * HW;
-    PNPX_HIP(hipMemcpyAsync(grad_vars_in, grad_vars_out, sizeof(float2) * is * B, hipMemcpyDeviceToDevice, s));
+    REQUIRE(T <= 0 || (saved && grad_sigma_d && grad_tau && grad_beta && work && tau && beta),
+            "csmri_apg_backward: null pointer");
+    const auto [HW, is, n] = state_dims(B, H, W, 2);
+    PNPX_TRY(copy_state(grad_vars_in, grad_vars_out, sizeof(float2) * is * B, s));
     if (T == 0) return PNPX_OK;
     FftPlan2D P;
     PNPX_TRY(make_fft_plan(ctx, B, H, W, true, &P));
@@ -940,8 +815,7 @@ extern "C" int pnpx_csmri_apg_backward(pnpx_ctx* ctx, const float* y0, const uin
       PNPX_LAUNCH_CHECK();
       hipLaunchKernelGGL(item_sum_kernel, dim3(B), dim3(256), 0, s, contrib_b, grad_beta + (size_t)i * B, HW);
       PNPX_LAUNCH_CHECK();
-      PNPX_TRY(unet_denoise_backward_ticket(ctx, saved + (size_t)i * n, sigma_d + i, param_stride, gxr, gd,
-                                            grad_sigma_d + (size_t)i * B, B, H, W, s, ticket ? ticket + i : 0));
+      PNPX_TRY(prox_vjp(ctx, i, saved, sigma_d, param_stride, gxr, gd, grad_sigma_d, B, H, W, s, ticket));
       Scratch S;
       PNPX_TRY(get_scratch(ctx, B, H, W, &S));
       StoreC kst{S.k, H, W};
@@ -967,20 +841,15 @@ static int red_forward(pnpx_ctx* ctx, const float* vars_in, float* vars_out, con
                        const float* sigma_d, const float* mu, const float* lamda, int param_stride, int B, int H, int W,
                        int T, float* saved, hipStream_t s, unsigned long long* ticket_out = nullptr) {
   PNPX_TRY(check_common(vars_in, vars_out, y0, mask, sigma_d, B, H, W, T, param_stride));
-  if (!mu || !lamda) {
-    set_error("csmri_redadmm: null mu/lamda");
-    return PNPX_ERR_ARG;
-  }
-  if (ticket_out) *ticket_out = 0;
-  const bool park = saved && ticket_out;
-  const int HW = H * W;
-  const size_t is = 3 * (size_t)HW, n = (size_t)B * HW;
+  REQUIRE(mu && lamda, "csmri_redadmm: null mu/lamda");
+  const Prox px = prox_begin(ctx, sigma_d, param_stride, B, H, W, saved, ticket_out, s);
+  const auto [HW, is, n] = state_dims(B, H, W, 3);
   Scratch S;
   PNPX_TRY(get_scratch(ctx, B, H, W, &S));
   FftPlan2D P;
   PNPX_TRY(make_fft_plan(ctx, B, H, W, true, &P));
   float2* vout = reinterpret_cast<float2*>(vars_out);
-  PNPX_HIP(hipMemcpyAsync(vars_out, vars_in, sizeof(float2) * is * B, hipMemcpyDeviceToDevice, s));
+  PNPX_TRY(copy_state(vars_out, vars_in, sizeof(float2) * is * B, s));   // the loop updates the state in place
   StoreC kst{S.k, H, W};
   LoadC kld{S.k, H, W};
   Slot zo{vout + HW, is, W, HW}, uo{vout + 2 * HW, is, W, HW};
@@ -988,14 +857,7 @@ static int red_forward(pnpx_ctx* ctx, const float* vars_in, float* vars_out, con
   for (int i = 0; i < T; ++i) {
     hipLaunchKernelGGL(real_of_diff_kernel, g1(n), dim3(256), 0, s, vout, (const float2*)nullptr, is, S.d, HW, B);
     PNPX_LAUNCH_CHECK();
-    if (saved) PNPX_HIP(hipMemcpyAsync(saved + (size_t)i * n, S.d, sizeof(float) * n, hipMemcpyDeviceToDevice, s));
-    if (park) {
-      unsigned long long tk = 0;
-      PNPX_TRY(unet_denoise_train(ctx, S.d, sigma_d + i, param_stride, S.xr, B, H, W, s, &tk));
-      if (i == 0) *ticket_out = tk;
-    } else {
-      PNPX_TRY(unet_denoise(ctx, S.d, sigma_d + i, param_stride, S.xr, nullptr, B, H, W, s, nullptr));
-    }
+    PNPX_TRY(prox_step(px, i, S.d, S.xr, saved ? saved + (size_t)i * n : nullptr));
     if (saved) {
       float2* q1 = reinterpret_cast<float2*>(saved + 3 * (size_t)T * n) + (size_t)i * n;
       float2* q2 = reinterpret_cast<float2*>(saved + 5 * (size_t)T * n) + (size_t)i * n;
@@ -1022,9 +884,7 @@ static int red_forward(pnpx_ctx* ctx, const float* vars_in, float* vars_out, con
 extern "C" int pnpx_csmri_redadmm(pnpx_ctx* ctx, const float* vars_in, float* vars_out, const float* y0,
                                   const uint8_t* mask, const float* sigma_d, const float* mu, const float* lamda,
                                   int param_stride, int B, int H, int W, int T, void* stream) {
-  LOCK_CTX(ctx);
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  return pnpx::guarded(ctx, s, [&]() -> int {
+  return solver_entry(ctx, stream, [&](hipStream_t s) {
     return red_forward(ctx, vars_in, vars_out, y0, mask, sigma_d, mu, lamda, param_stride, B, H, W, T, nullptr, s);
   });
 }
@@ -1033,13 +893,7 @@ extern "C" int pnpx_csmri_redadmm_train(pnpx_ctx* ctx, const float* vars_in, flo
                                         const uint8_t* mask, const float* sigma_d, const float* mu, const float* lamda,
                                         int param_stride, int B, int H, int W, int T, float* saved,
                                         unsigned long long* ticket, void* stream) {
-  LOCK_CTX(ctx);
-  if ((!saved && T > 0) || !ticket) {
-    pnpx::set_error("csmri_redadmm_train: saved / ticket is null");
-    return PNPX_ERR_ARG;
-  }
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  return pnpx::guarded(ctx, s, [&]() -> int {
+  return solver_train_entry(ctx, "csmri_redadmm_train", saved || T <= 0, ticket, stream, [&](hipStream_t s) {
     return red_forward(ctx, vars_in, vars_out, y0, mask, sigma_d, mu, lamda, param_stride, B, H, W, T, saved, s, ticket);
   });
 }
@@ -1053,17 +907,12 @@ extern "C" int pnpx_csmri_redadmm_backward(pnpx_ctx* ctx, const float* y0, const
                                            const float* grad_vars_out, float* grad_vars_in, float* grad_sigma_d,
                                            float* grad_mu, float* grad_lamda, float* work, int B, int H, int W, int T,
                                            unsigned long long ticket, void* stream) {
-  LOCK_CTX(ctx);
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  return pnpx::guarded(ctx, s, [&]() -> int {
+  return solver_entry(ctx, stream, [&](hipStream_t s) -> int {
     PNPX_TRY(check_common(grad_vars_out, grad_vars_in, y0, mask, sigma_d, B, H, W, T, param_stride));
-    if (T > 0 && (!saved || !grad_sigma_d || !grad_mu || !grad_lamda || !work || !mu || !lamda)) {
-      set_error("csmri_redadmm_backward: null pointer");
-      return PNPX_ERR_ARG;
-    }
-    const int HW = H * W;
-    const size_t is = 3 * (size_t)HW, n = (size_t)B * HW;
-    PNPX_HIP(hipMemcpyAsync(grad_vars_in, grad_vars_out, sizeof(float2) * is * B, hipMemcpyDeviceToDevice, s));
+    REQUIRE(T <= 0 || (saved && grad_sigma_d && grad_mu && grad_lamda && work && mu && lamda),
+            "csmri_redadmm_backward: null pointer");
+    const auto [HW, is, n] = state_dims(B, H, W, 3);
+    PNPX_TRY(copy_state(grad_vars_in, grad_vars_out, sizeof(float2) * is * B, s));
     if (T == 0) return PNPX_OK;
     FftPlan2D P;
     PNPX_TRY(make_fft_plan(ctx, B, H, W, true, &P));
@@ -1090,8 +939,7 @@ extern "C" int pnpx_csmri_redadmm_backward(pnpx_ctx* ctx, const float* y0, const
       PNPX_LAUNCH_CHECK();
       hipLaunchKernelGGL(item_sum_kernel, dim3(B), dim3(256), 0, s, contrib_l, grad_lamda + (size_t)i * B, HW);
       PNPX_LAUNCH_CHECK();
-      PNPX_TRY(unet_denoise_backward_ticket(ctx, saved + (size_t)i * n, sigma_d + i, param_stride, gxh, gd,
-                                            grad_sigma_d + (size_t)i * B, B, H, W, s, ticket ? ticket + i : 0));
+      PNPX_TRY(prox_vjp(ctx, i, saved, sigma_d, param_stride, gxh, gd, grad_sigma_d, B, H, W, s, ticket));
       hipLaunchKernelGGL(red_adjoint_finish_kernel, g1(n), dim3(256), 0, s, gd, g, is, HW, B);
       PNPX_LAUNCH_CHECK();
     }
@@ -1267,18 +1115,11 @@ static int amp_forward(pnpx_ctx* ctx, const float* vars_in, float* vars_out, con
                        const float* sigma_d, const float* probe, int param_stride, int B, int H, int W, int T,
                        hipStream_t s) {
   PNPX_TRY(check_common(vars_in, vars_out, y0, mask, sigma_d, B, H, W, T, param_stride));
-  if (!probe && T > 0) {
-    set_error("csmri_amp: probe is null");
-    return PNPX_ERR_ARG;
-  }
-  const int HW = H * W;
-  const size_t is = 2 * (size_t)HW, n = (size_t)B * HW;
+  REQUIRE(probe || T <= 0, "csmri_amp: probe is null");
+  const auto [HW, is, n] = state_dims(B, H, W, 2);
   FftPlan2D P;
   PNPX_TRY(make_fft_plan(ctx, B, H, W, true, &P));
-  if (T == 0) {
-    PNPX_HIP(hipMemcpyAsync(vars_out, vars_in, sizeof(float2) * is * B, hipMemcpyDeviceToDevice, s));
-    return PNPX_OK;
-  }
+  if (T == 0) return copy_state(vars_out, vars_in, sizeof(float2) * is * B, s);
   AmpScratch S;
   PNPX_TRY(get_amp_scratch(ctx, B, H, W, &S));
   const float2* vin = reinterpret_cast<const float2*>(vars_in);
@@ -1304,6 +1145,7 @@ static int amp_forward(pnpx_ctx* ctx, const float* vars_in, float* vars_out, con
     hipLaunchKernelGGL(amp_probe_kernel, g1(n), dim3(256), 0, s, S.d, dl, n, S.slab, nslab, S.zn2, sigma_d + i,
                        param_stride, B, HW, S.sig, S.eps);
     PNPX_LAUNCH_CHECK();
+    // (not a prox_step: 2B items, and noise levels the loop computes itself rather than column i of sigma_d)
     PNPX_TRY(unet_denoise(ctx, S.d, S.sig, 1, S.xr, nullptr, 2 * B, H, W, s, nullptr));
     PNPX_TRY((launch_rows<false>(P, LoadAmpX{S.xr, dl, S.c, xo, n, i == T - 1}, kst, s)));
     hipLaunchKernelGGL(item_sum_kernel, dim3(B), dim3(256), 0, s, S.c, S.div, HW);
@@ -1327,9 +1169,7 @@ static int amp_forward(pnpx_ctx* ctx, const float* vars_in, float* vars_out, con
 extern "C" int pnpx_csmri_amp(pnpx_ctx* ctx, const float* vars_in, float* vars_out, const float* y0,
                               const uint8_t* mask, const float* sigma_d, const float* probe, int param_stride, int B,
                               int H, int W, int T, void* stream) {
-  LOCK_CTX(ctx);
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  return pnpx::guarded(ctx, s, [&]() -> int {
+  return solver_entry(ctx, stream, [&](hipStream_t s) {
     return amp_forward(ctx, vars_in, vars_out, y0, mask, sigma_d, probe, param_stride, B, H, W, T, s);
   });
 }

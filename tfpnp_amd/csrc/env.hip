@@ -9,6 +9,7 @@
 //     trainer/mddpg/trainer.py:224-234 over utils/rpm.py:10-19) as ONE launch into device-resident ring storage,
 // All of it is HBM-bound byte shuffling: 16-byte accesses, rows on grid.y, tensors on grid.z.
 #include "common.h"
+#include "solver_loop.h"   // LOCK_CTX
 
 namespace pnpx {
 
@@ -185,14 +186,6 @@ __global__ __launch_bounds__(256) void policy_ob_unpack_kernel(UnpackArgs a) {
 }  // namespace pnpx
 
 using namespace pnpx;
-
-#define LOCK_CTX(ctx)                         \
-  if (!(ctx)) {                               \
-    pnpx::set_error("null context");          \
-    return PNPX_ERR_ARG;                      \
-  }                                           \
-  std::lock_guard<std::mutex> _lk((ctx)->mu); \
-  PNPX_HIP(hipSetDevice((ctx)->device))
 
 // grid.x for rows of at most `mx` bytes: 64 x 256 lanes x 16 B = 256 KiB per sweep of a row; longer rows loop
 static unsigned rows_grid_x(size_t mx) {

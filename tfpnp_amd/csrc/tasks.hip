@@ -6,6 +6,7 @@
 
 #include "common.h"
 #include "fft_lds.h"
+#include "solver_loop.h"
 
 namespace pnpx {
 namespace {
@@ -817,19 +818,6 @@ struct Carver {
 
 using namespace pnpx;
 
-#define LOCK_CTX(ctx)                         \
-  if (!(ctx)) {                               \
-    pnpx::set_error("null context");          \
-    return PNPX_ERR_ARG;                      \
-  }                                           \
-  std::lock_guard<std::mutex> _lk((ctx)->mu); \
-  PNPX_HIP(hipSetDevice((ctx)->device))
-#define REQUIRE(cond, msg)     \
-  if (!(cond)) {               \
-    pnpx::set_error(msg);      \
-    return PNPX_ERR_ARG;       \
-  }
-
 extern "C" {
 
 // ------------------------------------------------------------------------------------------- CDP
@@ -872,15 +860,11 @@ static int pr_forward(pnpx_ctx* ctx, const float* vars_in, float* vars_out, cons
                       int T, float* saved, unsigned long long* ticket_out, hipStream_t s) {
   REQUIRE(vars_in && vars_out && y0 && mask && sigma_d && mu && tau && B > 0 && S > 0 && T >= 0 && param_stride >= T,
           "pnpx_pr_iadmm: bad argument");
-  if (ticket_out) *ticket_out = 0;
-  const int HW = H * W;
-  const size_t is = 3 * (size_t)HW, n = (size_t)HW * B;
+  const Prox px = prox_begin(ctx, sigma_d, param_stride, B, H, W, saved, ticket_out, s);
+  const auto [HW, is, n] = state_dims(B, H, W, 3);
   const float2* vin = reinterpret_cast<const float2*>(vars_in);
   float2* vout = reinterpret_cast<float2*>(vars_out);
-  if (T == 0) {
-    PNPX_HIP(hipMemcpyAsync(vars_out, vars_in, sizeof(float2) * is * B, hipMemcpyDeviceToDevice, s));
-    return PNPX_OK;
-  }
+  if (T == 0) return copy_state(vars_out, vars_in, sizeof(float2) * is * B, s);
   void* p;
   PNPX_TRY(ctx_scratch(ctx, n * S * sizeof(float2) + 2 * n * sizeof(float) + 4096, &p));
   Carver cv{static_cast<char*>(p)};
@@ -891,21 +875,13 @@ static int pr_forward(pnpx_ctx* ctx, const float* vars_in, float* vars_out, cons
   PNPX_TRY(make_fft_plan(ctx, B * S, H, W, false, &P));
   StoreC kst{k, H, W};
   LoadC kld{k, H, W};
-  float* sv_d = saved;
   float2* sv_w = saved ? reinterpret_cast<float2*>(saved + (size_t)T * n) : nullptr;
   float2* sv_G = saved ? reinterpret_cast<float2*>(saved + (size_t)T * n * (1 + 2 * S)) : nullptr;
   float2* sv_q = saved ? reinterpret_cast<float2*>(saved + (size_t)T * n * (3 + 2 * S)) : nullptr;
   hipLaunchKernelGGL(real_of_diff_kernel, g1(n), dim3(256), 0, s, vin + HW, vin + 2 * HW, is, d, HW, B);
   PNPX_LAUNCH_CHECK();
   for (int i = 0; i < T; ++i) {
-    if (saved) {
-      PNPX_HIP(hipMemcpyAsync(sv_d + (size_t)i * n, d, sizeof(float) * n, hipMemcpyDeviceToDevice, s));
-      unsigned long long tk = 0;
-      PNPX_TRY(unet_denoise_train(ctx, d, sigma_d + i, param_stride, xr, B, H, W, s, &tk));
-      if (i == 0 && ticket_out) *ticket_out = tk;
-    } else {
-      PNPX_TRY(unet_denoise(ctx, d, sigma_d + i, param_stride, xr, nullptr, B, H, W, s, nullptr));
-    }
+    PNPX_TRY(prox_step(px, i, d, xr, saved ? saved + (size_t)i * n : nullptr));
     const float2* zi = (i == 0 ? vin : vout) + HW;
     const float2* ui = (i == 0 ? vin : vout) + 2 * HW;
     LoadCdp ld{zi, is, reinterpret_cast<const float2*>(mask), S, W, HW};
@@ -938,9 +914,7 @@ static int pr_forward(pnpx_ctx* ctx, const float* vars_in, float* vars_out, cons
 int pnpx_pr_iadmm(pnpx_ctx* ctx, const float* vars_in, float* vars_out, const float* y0, const float* mask,
                   const float* sigma_d, const float* mu, const float* tau, int param_stride, int B, int S, int H, int W,
                   int T, void* stream) {
-  LOCK_CTX(ctx);
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  return pnpx::guarded(ctx, s, [&]() -> int {
+  return solver_entry(ctx, stream, [&](hipStream_t s) {
     return pr_forward(ctx, vars_in, vars_out, y0, mask, sigma_d, mu, tau, param_stride, B, S, H, W, T, nullptr, nullptr, s);
   });
 }
@@ -948,10 +922,7 @@ int pnpx_pr_iadmm(pnpx_ctx* ctx, const float* vars_in, float* vars_out, const fl
 int pnpx_pr_iadmm_train(pnpx_ctx* ctx, const float* vars_in, float* vars_out, const float* y0, const float* mask,
                         const float* sigma_d, const float* mu, const float* tau, int param_stride, int B, int S, int H,
                         int W, int T, float* saved, unsigned long long* ticket, void* stream) {
-  LOCK_CTX(ctx);
-  REQUIRE((saved || T == 0) && ticket, "pnpx_pr_iadmm_train: saved / ticket is null");
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  return pnpx::guarded(ctx, s, [&]() -> int {
+  return solver_train_entry(ctx, "pnpx_pr_iadmm_train", saved || T == 0, ticket, stream, [&](hipStream_t s) {
     return pr_forward(ctx, vars_in, vars_out, y0, mask, sigma_d, mu, tau, param_stride, B, S, H, W, T, saved, ticket, s);
   });
 }
@@ -965,22 +936,18 @@ int pnpx_pr_iadmm_backward(pnpx_ctx* ctx, const float* y0, const float* mask, co
                            const float* tau, int param_stride, const float* saved, const float* grad_vars_out,
                            float* grad_vars_in, float* grad_sigma_d, float* grad_mu, float* grad_tau, float* work, int B,
                            int S, int H, int W, int T, unsigned long long ticket, void* stream) {
-  LOCK_CTX(ctx);
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  return pnpx::guarded(ctx, s, [&]() -> int {
+  return solver_entry(ctx, stream, [&](hipStream_t s) -> int {
     REQUIRE(y0 && mask && sigma_d && mu && tau && grad_vars_out && grad_vars_in && B > 0 && S > 0 && T >= 0 &&
                 param_stride >= T && (T == 0 || (saved && grad_sigma_d && grad_mu && grad_tau && work)),
             "pnpx_pr_iadmm_backward: bad argument");
-    const int HW = H * W;
-    const size_t is = 3 * (size_t)HW, n = (size_t)HW * B;
-    PNPX_HIP(hipMemcpyAsync(grad_vars_in, grad_vars_out, sizeof(float2) * is * B, hipMemcpyDeviceToDevice, s));
+    const auto [HW, is, n] = state_dims(B, H, W, 3);
+    PNPX_TRY(copy_state(grad_vars_in, grad_vars_out, sizeof(float2) * is * B, s));
     if (T == 0) return PNPX_OK;
     FftPlan2D P;
     PNPX_TRY(make_fft_plan(ctx, B * S, H, W, false, &P));
     float2* g = reinterpret_cast<float2*>(grad_vars_in);
     const float2* mk = reinterpret_cast<const float2*>(mask);
     float *gxr = work, *gd = work + n, *c_tau = work + 2 * n, *c_mu = work + 3 * n;
-    const float* sv_d = saved;
     const float2* sv_w = reinterpret_cast<const float2*>(saved + (size_t)T * n);
     const float2* sv_G = reinterpret_cast<const float2*>(saved + (size_t)T * n * (1 + 2 * S));
     const float2* sv_q = reinterpret_cast<const float2*>(saved + (size_t)T * n * (3 + 2 * S));
@@ -1001,8 +968,7 @@ int pnpx_pr_iadmm_backward(pnpx_ctx* ctx, const float* y0, const float* mask, co
       hipLaunchKernelGGL(pr_item_sum_kernel, dim3(B), dim3(256), 0, s, c_tau, grad_tau + (size_t)i * B, HW);
       hipLaunchKernelGGL(pr_item_sum_kernel, dim3(B), dim3(256), 0, s, c_mu, grad_mu + (size_t)i * B, HW);
       PNPX_LAUNCH_CHECK();
-      PNPX_TRY(unet_denoise_backward_ticket(ctx, sv_d + (size_t)i * n, sigma_d + i, param_stride, gxr, gd,
-                                            grad_sigma_d + (size_t)i * B, B, H, W, s, ticket ? ticket + i : 0));
+      PNPX_TRY(prox_vjp(ctx, i, saved, sigma_d, param_stride, gxr, gd, grad_sigma_d, B, H, W, s, ticket));
       hipLaunchKernelGGL(pr_adjoint_finish_kernel, g1(n), dim3(256), 0, s, gd, g, is, HW, B);
       PNPX_LAUNCH_CHECK();
     }
@@ -1018,13 +984,9 @@ static int pr_pg_forward(pnpx_ctx* ctx, const float* vars_in, float* vars_out, c
                          float* saved, unsigned long long* ticket_out, hipStream_t s) {
   REQUIRE(vars_in && vars_out && y0 && mask && sigma_d && tau && B > 0 && S > 0 && H > 0 && W > 0 && T >= 0 && param_stride >= T,
           "pnpx_pr_pg: bad argument");
-  if (ticket_out) *ticket_out = 0;
-  const int HW = H * W;
-  const size_t n = (size_t)HW * B;
-  if (T == 0) {
-    PNPX_HIP(hipMemcpyAsync(vars_out, vars_in, sizeof(float2) * n, hipMemcpyDeviceToDevice, s));
-    return PNPX_OK;
-  }
+  const Prox px = prox_begin(ctx, sigma_d, param_stride, B, H, W, saved, ticket_out, s);
+  const auto [HW, is, n] = state_dims(B, H, W, 1);
+  if (T == 0) return copy_state(vars_out, vars_in, sizeof(float2) * is * B, s);
   void* p;
   PNPX_TRY(ctx_scratch(ctx, n * S * sizeof(float2) + 2 * n * sizeof(float) + 4096, &p));
   Carver cv{static_cast<char*>(p)};
@@ -1064,13 +1026,7 @@ static int pr_pg_forward(pnpx_ctx* ctx, const float* vars_in, float* vars_out, c
       hipLaunchKernelGGL(pr_pg_step_kernel, g1(n), dim3(256), 0, s, k, mk, xre, xes, d, gs, tau + i, param_stride, S, HW, B);
       PNPX_LAUNCH_CHECK();
     }
-    if (saved) {
-      unsigned long long tk = 0;
-      PNPX_TRY(unet_denoise_train(ctx, d, sigma_d + i, param_stride, xr, B, H, W, s, &tk));
-      if (i == 0 && ticket_out) *ticket_out = tk;
-    } else {
-      PNPX_TRY(unet_denoise(ctx, d, sigma_d + i, param_stride, xr, nullptr, B, H, W, s, nullptr));
-    }
+    PNPX_TRY(prox_step(px, i, d, xr));   // d stands in `saved` already
   }
   // the last denoiser output becomes the state (imaginary part +0)
   hipLaunchKernelGGL(real_to_complex_kernel, g1(n), dim3(256), 0, s, xr, reinterpret_cast<float2*>(vars_out), n);
@@ -1080,9 +1036,7 @@ static int pr_pg_forward(pnpx_ctx* ctx, const float* vars_in, float* vars_out, c
 
 int pnpx_pr_pg(pnpx_ctx* ctx, const float* vars_in, float* vars_out, const float* y0, const float* mask, const float* sigma_d,
                const float* tau, int param_stride, int B, int S, int H, int W, int T, void* stream) {
-  LOCK_CTX(ctx);
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  return pnpx::guarded(ctx, s, [&]() -> int {
+  return solver_entry(ctx, stream, [&](hipStream_t s) {
     return pr_pg_forward(ctx, vars_in, vars_out, y0, mask, sigma_d, tau, param_stride, B, S, H, W, T, nullptr, nullptr, s);
   });
 }
@@ -1090,10 +1044,7 @@ int pnpx_pr_pg(pnpx_ctx* ctx, const float* vars_in, float* vars_out, const float
 int pnpx_pr_pg_train(pnpx_ctx* ctx, const float* vars_in, float* vars_out, const float* y0, const float* mask,
                      const float* sigma_d, const float* tau, int param_stride, int B, int S, int H, int W, int T, float* saved,
                      unsigned long long* ticket, void* stream) {
-  LOCK_CTX(ctx);
-  REQUIRE((saved || T == 0) && ticket, "pnpx_pr_pg_train: saved / ticket is null");
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  return pnpx::guarded(ctx, s, [&]() -> int {
+  return solver_train_entry(ctx, "pnpx_pr_pg_train", saved || T == 0, ticket, stream, [&](hipStream_t s) {
     return pr_pg_forward(ctx, vars_in, vars_out, y0, mask, sigma_d, tau, param_stride, B, S, H, W, T, saved, ticket, s);
   });
 }
@@ -1107,18 +1058,12 @@ int pnpx_pr_pg_backward(pnpx_ctx* ctx, const float* y0, const float* mask, const
                         int param_stride, const float* saved, const float* grad_vars_out, float* grad_vars_in,
                         float* grad_sigma_d, float* grad_tau, float* work, int B, int S, int H, int W, int T,
                         unsigned long long ticket, void* stream) {
-  LOCK_CTX(ctx);
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  return pnpx::guarded(ctx, s, [&]() -> int {
+  return solver_entry(ctx, stream, [&](hipStream_t s) -> int {
     REQUIRE(y0 && mask && sigma_d && tau && grad_vars_out && grad_vars_in && B > 0 && S > 0 && H > 0 && W > 0 && T >= 0 &&
                 param_stride >= T && (T == 0 || (saved && grad_sigma_d && grad_tau && work)),
             "pnpx_pr_pg_backward: bad argument");
-    const int HW = H * W;
-    const size_t n = (size_t)HW * B;
-    if (T == 0) {
-      PNPX_HIP(hipMemcpyAsync(grad_vars_in, grad_vars_out, sizeof(float2) * n, hipMemcpyDeviceToDevice, s));
-      return PNPX_OK;
-    }
+    const auto [HW, is, n] = state_dims(B, H, W, 1);
+    if (T == 0) return copy_state(grad_vars_in, grad_vars_out, sizeof(float2) * is * B, s);
     FftPlan2D P;
     PNPX_TRY(make_fft_plan(ctx, B * S, H, W, false, &P));
     const float2* mk = reinterpret_cast<const float2*>(mask);
@@ -1129,8 +1074,7 @@ int pnpx_pr_pg_backward(pnpx_ctx* ctx, const float* y0, const float* mask, const
     hipLaunchKernelGGL(complex_real_part_kernel, g1(n), dim3(256), 0, s, reinterpret_cast<const float2*>(grad_vars_out), gx, n);
     PNPX_LAUNCH_CHECK();
     for (int i = T - 1; i >= 0; --i) {
-      PNPX_TRY(unet_denoise_backward_ticket(ctx, sv_d + (size_t)i * n, sigma_d + i, param_stride, gx, gd,
-                                            grad_sigma_d + (size_t)i * B, B, H, W, s, ticket ? ticket + i : 0));
+      PNPX_TRY(prox_vjp(ctx, i, sv_d, sigma_d, param_stride, gx, gd, grad_sigma_d, B, H, W, s, ticket));
       // the context's scratch is shared with the denoiser's VJP above, which may also GROW (= re-allocate) it: the k-space
       // buffer is carved anew every iteration and nothing in it has to survive that call
       void* p;
@@ -1168,13 +1112,9 @@ static int spi_forward(pnpx_ctx* ctx, const float* vars_in, float* vars_out, con
                        unsigned long long* ticket_out, hipStream_t s) {
   REQUIRE(vars_in && vars_out && x0 && Kmap && sigma_d && mu && B > 0 && T >= 0 && param_stride >= T,
           "pnpx_spi_admm: bad argument");
-  if (ticket_out) *ticket_out = 0;
-  const int HW = H * W;
-  const size_t is = 3 * (size_t)HW, n = (size_t)HW * B;
-  if (T == 0) {
-    PNPX_HIP(hipMemcpyAsync(vars_out, vars_in, sizeof(float) * is * B, hipMemcpyDeviceToDevice, s));
-    return PNPX_OK;
-  }
+  const Prox px = prox_begin(ctx, sigma_d, param_stride, B, H, W, saved, ticket_out, s);
+  const auto [HW, is, n] = state_dims(B, H, W, 3);
+  if (T == 0) return copy_state(vars_out, vars_in, sizeof(float) * is * B, s);
   void* p;
   PNPX_TRY(ctx_scratch(ctx, 2 * n * sizeof(float) + 4096, &p));
   Carver cv{static_cast<char*>(p)};
@@ -1185,20 +1125,16 @@ static int spi_forward(pnpx_ctx* ctx, const float* vars_in, float* vars_out, con
     const float* xin = (i == 0) ? vars_in : xr;
     const size_t xs = (i == 0) ? is : (size_t)HW;
     const float* uin = ((i == 0) ? vars_in : vars_out) + 2 * HW;
+    float* d = saved ? saved + ((size_t)T + i) * n : dscr;   // the training path denoises straight out of `saved`
     if (saved) {
-      float* d = saved + ((size_t)T + i) * n;
       hipLaunchKernelGGL(spi_step_save_kernel, g1(n), dim3(256), 0, s, xin, xs, uin, is, x0, Kmap, vars_out + HW,
                          vars_out + 2 * HW, d, mu + i, param_stride, HW, B, saved + (size_t)i * n);
-      PNPX_LAUNCH_CHECK();
-      unsigned long long tk = 0;
-      PNPX_TRY(unet_denoise_train(ctx, d, sigma_d + i, param_stride, xr, B, H, W, s, &tk));
-      if (i == 0 && ticket_out) *ticket_out = tk;
     } else {
       hipLaunchKernelGGL(spi_step_kernel, g1(n), dim3(256), 0, s, xin, xs, uin, is, x0, Kmap, vars_out + HW,
-                         vars_out + 2 * HW, dscr, mu + i, param_stride, HW, B);
-      PNPX_LAUNCH_CHECK();
-      PNPX_TRY(unet_denoise(ctx, dscr, sigma_d + i, param_stride, xr, nullptr, B, H, W, s, nullptr));
+                         vars_out + 2 * HW, d, mu + i, param_stride, HW, B);
     }
+    PNPX_LAUNCH_CHECK();
+    PNPX_TRY(prox_step(px, i, d, xr));
   }
   // the last denoiser output becomes the state's x (the only copy of the call)
   hipLaunchKernelGGL(copy_real_slot_kernel, g1(n), dim3(256), 0, s, xr, vars_out, is, HW, B);
@@ -1208,9 +1144,7 @@ static int spi_forward(pnpx_ctx* ctx, const float* vars_in, float* vars_out, con
 
 int pnpx_spi_admm(pnpx_ctx* ctx, const float* vars_in, float* vars_out, const float* x0, const float* Kmap,
                   const float* sigma_d, const float* mu, int param_stride, int B, int H, int W, int T, void* stream) {
-  LOCK_CTX(ctx);
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  return pnpx::guarded(ctx, s, [&]() -> int {
+  return solver_entry(ctx, stream, [&](hipStream_t s) {
     return spi_forward(ctx, vars_in, vars_out, x0, Kmap, sigma_d, mu, param_stride, B, H, W, T, nullptr, nullptr, s);
   });
 }
@@ -1218,10 +1152,7 @@ int pnpx_spi_admm(pnpx_ctx* ctx, const float* vars_in, float* vars_out, const fl
 int pnpx_spi_admm_train(pnpx_ctx* ctx, const float* vars_in, float* vars_out, const float* x0, const float* Kmap,
                         const float* sigma_d, const float* mu, int param_stride, int B, int H, int W, int T, float* saved,
                         unsigned long long* ticket, void* stream) {
-  LOCK_CTX(ctx);
-  REQUIRE((saved || T == 0) && ticket, "pnpx_spi_admm_train: saved / ticket is null");
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  return pnpx::guarded(ctx, s, [&]() -> int {
+  return solver_train_entry(ctx, "pnpx_spi_admm_train", saved || T == 0, ticket, stream, [&](hipStream_t s) {
     return spi_forward(ctx, vars_in, vars_out, x0, Kmap, sigma_d, mu, param_stride, B, H, W, T, saved, ticket, s);
   });
 }
@@ -1232,21 +1163,17 @@ int pnpx_spi_admm_backward(pnpx_ctx* ctx, const float* x0, const float* Kmap, co
                            int param_stride, const float* saved, const float* grad_vars_out, float* grad_vars_in,
                            float* grad_sigma_d, float* grad_mu, float* work, int B, int H, int W, int T,
                            unsigned long long ticket, void* stream) {
-  LOCK_CTX(ctx);
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  return pnpx::guarded(ctx, s, [&]() -> int {
+  return solver_entry(ctx, stream, [&](hipStream_t s) -> int {
     REQUIRE(x0 && Kmap && sigma_d && mu && grad_vars_out && grad_vars_in && B > 0 && T >= 0 && param_stride >= T &&
                 (T == 0 || (saved && grad_sigma_d && grad_mu && work)),
             "pnpx_spi_admm_backward: bad argument");
-    const int HW = H * W;
-    const size_t is = 3 * (size_t)HW, n = (size_t)HW * B;
-    PNPX_HIP(hipMemcpyAsync(grad_vars_in, grad_vars_out, sizeof(float) * is * B, hipMemcpyDeviceToDevice, s));
+    const auto [HW, is, n] = state_dims(B, H, W, 3);
+    PNPX_TRY(copy_state(grad_vars_in, grad_vars_out, sizeof(float) * is * B, s));
     float *gxr = work, *gd = work + n, *c_mu = work + 2 * n;
     for (int i = T - 1; i >= 0; --i) {
       hipLaunchKernelGGL(slot_to_rows_kernel, g1(n), dim3(256), 0, s, grad_vars_in, is, gxr, HW, B);
       PNPX_LAUNCH_CHECK();
-      PNPX_TRY(unet_denoise_backward_ticket(ctx, saved + ((size_t)T + i) * n, sigma_d + i, param_stride, gxr, gd,
-                                            grad_sigma_d + (size_t)i * B, B, H, W, s, ticket ? ticket + i : 0));
+      PNPX_TRY(prox_vjp(ctx, i, saved + (size_t)T * n, sigma_d, param_stride, gxr, gd, grad_sigma_d, B, H, W, s, ticket));
       hipLaunchKernelGGL(spi_adjoint_kernel, g1(n), dim3(256), 0, s, grad_vars_in, is, gd, saved + (size_t)i * n, x0, Kmap,
                          mu + i, param_stride, HW, B, c_mu);
       PNPX_LAUNCH_CHECK();
@@ -1372,13 +1299,9 @@ static int ct_iadmm_forward(pnpx_ctx* ctx, const float* vars_in, float* vars_out
   REQUIRE(vars_in && vars_out && y0 && sigma_d && mu && tau && B > 0 && R > 0 && n_view > 0 && T >= 0 &&
               param_stride >= T && opnorm > 0.f,
           "pnpx_ct_iadmm: bad argument");
-  if (ticket_out) *ticket_out = 0;
-  const int HW = R * R;
-  const size_t is = 3 * (size_t)HW, n = (size_t)HW * B;
-  if (T == 0) {
-    PNPX_HIP(hipMemcpyAsync(vars_out, vars_in, sizeof(float) * is * B, hipMemcpyDeviceToDevice, s));
-    return PNPX_OK;
-  }
+  const Prox px = prox_begin(ctx, sigma_d, param_stride, B, R, R, saved, ticket_out, s);
+  const auto [HW, is, n] = state_dims(B, R, R, 3);
+  if (T == 0) return copy_state(vars_out, vars_in, sizeof(float) * is * B, s);
   CtScratch C;
   PNPX_TRY(ct_scratch(ctx, B, R, n_view, 3, s, &C));
   float *d = C.img[0], *xr = C.img[1], *g = C.img[2];
@@ -1386,14 +1309,7 @@ static int ct_iadmm_forward(pnpx_ctx* ctx, const float* vars_in, float* vars_out
   hipLaunchKernelGGL(real_diff_slots_kernel, g1(n), dim3(256), 0, s, vars_in + HW, vars_in + 2 * HW, is, d, HW, B);
   PNPX_LAUNCH_CHECK();
   for (int i = 0; i < T; ++i) {
-    if (saved) {
-      PNPX_HIP(hipMemcpyAsync(saved + (size_t)i * n, d, sizeof(float) * n, hipMemcpyDeviceToDevice, s));
-      unsigned long long tk = 0;
-      PNPX_TRY(unet_denoise_train(ctx, d, sigma_d + i, param_stride, xr, B, R, R, s, &tk));
-      if (i == 0 && ticket_out) *ticket_out = tk;
-    } else {
-      PNPX_TRY(unet_denoise(ctx, d, sigma_d + i, param_stride, xr, nullptr, B, R, R, s, nullptr));
-    }
+    PNPX_TRY(prox_step(px, i, d, xr, saved ? saved + (size_t)i * n : nullptr));
     const float* zi = ((i == 0) ? vars_in : vars_out) + HW;
     const float* ui = ((i == 0) ? vars_in : vars_out) + 2 * HW;
     PNPX_TRY(ct_normal_op(C, zi, is, y0, g, op2, R, n_view, B, s));
@@ -1413,9 +1329,7 @@ static int ct_iadmm_forward(pnpx_ctx* ctx, const float* vars_in, float* vars_out
 int pnpx_ct_iadmm(pnpx_ctx* ctx, const float* vars_in, float* vars_out, const float* y0, int n_view, float opnorm,
                   const float* sigma_d, const float* mu, const float* tau, int param_stride, int B, int R, int T,
                   void* stream) {
-  LOCK_CTX(ctx);
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  return pnpx::guarded(ctx, s, [&]() -> int {
+  return solver_entry(ctx, stream, [&](hipStream_t s) {
     return ct_iadmm_forward(ctx, vars_in, vars_out, y0, n_view, opnorm, sigma_d, mu, tau, param_stride, B, R, T, nullptr,
                             nullptr, s);
   });
@@ -1424,10 +1338,7 @@ int pnpx_ct_iadmm(pnpx_ctx* ctx, const float* vars_in, float* vars_out, const fl
 int pnpx_ct_iadmm_train(pnpx_ctx* ctx, const float* vars_in, float* vars_out, const float* y0, int n_view, float opnorm,
                         const float* sigma_d, const float* mu, const float* tau, int param_stride, int B, int R, int T,
                         float* saved, unsigned long long* ticket, void* stream) {
-  LOCK_CTX(ctx);
-  REQUIRE((saved || T == 0) && ticket, "pnpx_ct_iadmm_train: saved / ticket is null");
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  return pnpx::guarded(ctx, s, [&]() -> int {
+  return solver_train_entry(ctx, "pnpx_ct_iadmm_train", saved || T == 0, ticket, stream, [&](hipStream_t s) {
     return ct_iadmm_forward(ctx, vars_in, vars_out, y0, n_view, opnorm, sigma_d, mu, tau, param_stride, B, R, T, saved,
                             ticket, s);
   });
@@ -1439,15 +1350,12 @@ int pnpx_ct_iadmm_backward(pnpx_ctx* ctx, int n_view, float opnorm, const float*
                            int param_stride, const float* saved, const float* grad_vars_out, float* grad_vars_in,
                            float* grad_sigma_d, float* grad_mu, float* grad_tau, float* work, int B, int R, int T,
                            unsigned long long ticket, void* stream) {
-  LOCK_CTX(ctx);
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  return pnpx::guarded(ctx, s, [&]() -> int {
+  return solver_entry(ctx, stream, [&](hipStream_t s) -> int {
     REQUIRE(sigma_d && mu && tau && grad_vars_out && grad_vars_in && B > 0 && R > 0 && n_view > 0 && T >= 0 &&
                 param_stride >= T && opnorm > 0.f && (T == 0 || (saved && grad_sigma_d && grad_mu && grad_tau && work)),
             "pnpx_ct_iadmm_backward: bad argument");
-    const int HW = R * R;
-    const size_t is = 3 * (size_t)HW, n = (size_t)HW * B;
-    PNPX_HIP(hipMemcpyAsync(grad_vars_in, grad_vars_out, sizeof(float) * is * B, hipMemcpyDeviceToDevice, s));
+    const auto [HW, is, n] = state_dims(B, R, R, 3);
+    PNPX_TRY(copy_state(grad_vars_in, grad_vars_out, sizeof(float) * is * B, s));
     if (T == 0) return PNPX_OK;
     CtScratch C;
     float2* cs_home = reinterpret_cast<float2*>(work + 6 * n);       // the table outlives the VJP calls in the work buffer
@@ -1465,8 +1373,7 @@ int pnpx_ct_iadmm_backward(pnpx_ctx* ctx, int n_view, float opnorm, const float*
       hipLaunchKernelGGL(pr_item_sum_kernel, dim3(B), dim3(256), 0, s, c_tau, grad_tau + (size_t)i * B, HW);
       hipLaunchKernelGGL(pr_item_sum_kernel, dim3(B), dim3(256), 0, s, c_mu, grad_mu + (size_t)i * B, HW);
       PNPX_LAUNCH_CHECK();
-      PNPX_TRY(unet_denoise_backward_ticket(ctx, saved + (size_t)i * n, sigma_d + i, param_stride, gxr, gd,
-                                            grad_sigma_d + (size_t)i * B, B, R, R, s, ticket ? ticket + i : 0));
+      PNPX_TRY(prox_vjp(ctx, i, saved, sigma_d, param_stride, gxr, gd, grad_sigma_d, B, R, R, s, ticket));
       hipLaunchKernelGGL(ct_adjoint_finish_kernel, g1(n), dim3(256), 0, s, gd, grad_vars_in, is, HW, B);
       PNPX_LAUNCH_CHECK();
     }
@@ -1481,13 +1388,9 @@ static int ct_pg_forward(pnpx_ctx* ctx, const float* vars_in, float* vars_out, c
   REQUIRE(vars_in && vars_out && y0 && sigma_d && tau && B > 0 && R > 0 && n_view > 0 && T >= 0 &&
               param_stride >= T && opnorm > 0.f,
           "pnpx_ct_pg: bad argument");
-  if (ticket_out) *ticket_out = 0;
-  const int HW = R * R;
-  const size_t n = (size_t)HW * B;
-  if (T == 0) {
-    PNPX_HIP(hipMemcpyAsync(vars_out, vars_in, sizeof(float) * n, hipMemcpyDeviceToDevice, s));
-    return PNPX_OK;
-  }
+  const Prox px = prox_begin(ctx, sigma_d, param_stride, B, R, R, saved, ticket_out, s);
+  const auto [HW, is, n] = state_dims(B, R, R, 1);
+  if (T == 0) return copy_state(vars_out, vars_in, sizeof(float) * is * B, s);
   CtScratch C;
   PNPX_TRY(ct_scratch(ctx, B, R, n_view, 2, s, &C));
   const float op2 = (float)((double)opnorm * (double)opnorm);
@@ -1498,22 +1401,14 @@ static int ct_pg_forward(pnpx_ctx* ctx, const float* vars_in, float* vars_out, c
     PNPX_TRY(ct_normal_op(C, xi, (size_t)HW, y0, g, op2, R, n_view, B, s));
     hipLaunchKernelGGL(ct_pg_step_kernel, g1(n), dim3(256), 0, s, g, xi, d, tau + i, param_stride, HW, B);
     PNPX_LAUNCH_CHECK();
-    if (saved) {
-      unsigned long long tk = 0;
-      PNPX_TRY(unet_denoise_train(ctx, d, sigma_d + i, param_stride, vars_out, B, R, R, s, &tk));
-      if (i == 0 && ticket_out) *ticket_out = tk;
-    } else {
-      PNPX_TRY(unet_denoise(ctx, d, sigma_d + i, param_stride, vars_out, nullptr, B, R, R, s, nullptr));
-    }
+    PNPX_TRY(prox_step(px, i, d, vars_out));   // d stands in `saved` already; the denoiser writes the state itself
   }
   return PNPX_OK;
 }
 
 int pnpx_ct_pg(pnpx_ctx* ctx, const float* vars_in, float* vars_out, const float* y0, int n_view, float opnorm,
                const float* sigma_d, const float* tau, int param_stride, int B, int R, int T, void* stream) {
-  LOCK_CTX(ctx);
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  return pnpx::guarded(ctx, s, [&]() -> int {
+  return solver_entry(ctx, stream, [&](hipStream_t s) {
     return ct_pg_forward(ctx, vars_in, vars_out, y0, n_view, opnorm, sigma_d, tau, param_stride, B, R, T, nullptr, nullptr, s);
   });
 }
@@ -1521,10 +1416,7 @@ int pnpx_ct_pg(pnpx_ctx* ctx, const float* vars_in, float* vars_out, const float
 int pnpx_ct_pg_train(pnpx_ctx* ctx, const float* vars_in, float* vars_out, const float* y0, int n_view, float opnorm,
                      const float* sigma_d, const float* tau, int param_stride, int B, int R, int T, float* saved,
                      unsigned long long* ticket, void* stream) {
-  LOCK_CTX(ctx);
-  REQUIRE((saved || T == 0) && ticket, "pnpx_ct_pg_train: saved / ticket is null");
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  return pnpx::guarded(ctx, s, [&]() -> int {
+  return solver_train_entry(ctx, "pnpx_ct_pg_train", saved || T == 0, ticket, stream, [&](hipStream_t s) {
     return ct_pg_forward(ctx, vars_in, vars_out, y0, n_view, opnorm, sigma_d, tau, param_stride, B, R, T, saved, ticket, s);
   });
 }
@@ -1534,15 +1426,12 @@ int pnpx_ct_pg_train(pnpx_ctx* ctx, const float* vars_in, float* vars_out, const
 int pnpx_ct_pg_backward(pnpx_ctx* ctx, int n_view, float opnorm, const float* sigma_d, const float* tau, int param_stride,
                         const float* saved, const float* grad_vars_out, float* grad_vars_in, float* grad_sigma_d,
                         float* grad_tau, float* work, int B, int R, int T, unsigned long long ticket, void* stream) {
-  LOCK_CTX(ctx);
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  return pnpx::guarded(ctx, s, [&]() -> int {
+  return solver_entry(ctx, stream, [&](hipStream_t s) -> int {
     REQUIRE(sigma_d && tau && grad_vars_out && grad_vars_in && B > 0 && R > 0 && n_view > 0 && T >= 0 &&
                 param_stride >= T && opnorm > 0.f && (T == 0 || (saved && grad_sigma_d && grad_tau && work)),
             "pnpx_ct_pg_backward: bad argument");
-    const int HW = R * R;
-    const size_t n = (size_t)HW * B;
-    PNPX_HIP(hipMemcpyAsync(grad_vars_in, grad_vars_out, sizeof(float) * n, hipMemcpyDeviceToDevice, s));
+    const auto [HW, is, n] = state_dims(B, R, R, 1);
+    PNPX_TRY(copy_state(grad_vars_in, grad_vars_out, sizeof(float) * is * B, s));
     if (T == 0) return PNPX_OK;
     CtScratch C;
     // (cos, sin) table behind the three n-float buffers, at an EVEN float offset: 3 * n is odd for odd B * R * R and a float2
@@ -1552,8 +1441,7 @@ int pnpx_ct_pg_backward(pnpx_ctx* ctx, int n_view, float opnorm, const float* si
     const float op2 = (float)((double)opnorm * (double)opnorm);
     float *gd = work, *J = work + n, *c_tau = work + 2 * n;
     for (int i = T - 1; i >= 0; --i) {
-      PNPX_TRY(unet_denoise_backward_ticket(ctx, saved + (size_t)i * n, sigma_d + i, param_stride, grad_vars_in, gd,
-                                            grad_sigma_d + (size_t)i * B, B, R, R, s, ticket ? ticket + i : 0));
+      PNPX_TRY(prox_vjp(ctx, i, saved, sigma_d, param_stride, grad_vars_in, gd, grad_sigma_d, B, R, R, s, ticket));
       PNPX_TRY(ct_scratch(ctx, B, R, n_view, 0, s, &C, cs_home, false));   // re-carve after the VJP (shared, growable scratch)
       PNPX_TRY(ct_normal_op(C, gd, (size_t)HW, nullptr, J, op2, R, n_view, B, s));
       hipLaunchKernelGGL(ct_pg_adjoint_kernel, g1(n), dim3(256), 0, s, gd, J, saved + ((size_t)T + i) * n, tau + i,

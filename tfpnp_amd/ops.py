@@ -7,6 +7,7 @@ import ctypes as C
 import itertools
 import threading
 import weakref
+from typing import Callable, NamedTuple
 
 import numpy as np
 import torch
@@ -744,171 +745,185 @@ def _vars(variables, nvar, complex_):
     return v
 
 
-def _csmri_common(fn_name, nvar, ctx, variables, y0, mask, params, iter_num):
-    v = _vars(variables, nvar, True)
-    B, _, H, W, _ = v.shape
-    y0 = _f32(y0, "y0")
-    m = _mask_u8(mask)
-    if y0.numel() != B * H * W * 2 or m.numel() != B * H * W:
-        raise PnpxError("y0/mask do not match the state's [B,H,W]")
+def _train_T(B, params, iter_num):
     ps, T = _params(B, *params)
     if iter_num is not None:
         if iter_num > T:
             raise PnpxError(f"iter_num {iter_num} exceeds the {T} hyper-parameter columns provided")
         T = iter_num
+    return ps, T
+
+
+class _Loop(NamedTuple):
+    """One native solver loop (pnpx_<name>, pnpx_<name>_train, pnpx_<name>_backward) as the two call helpers below see it."""
+    name: str                      # entry name without the pnpx_ prefix
+    nvar: int                      # state variables ...
+    complex_: bool                 # ... complex [B,nvar,H,W,2] or real [B,nvar,H,W]
+    aux: Callable                  # (loop, state, aux arguments, backward) -> (leading C arguments, size arguments, pixels, S):
+                                   # validates the measurement tensors and the extra integers (S, n_view, opnorm)
+    nhyper: int                    # hyper-parameter tensors, sigma_d first
+    saved_px: Callable             # S -> floats of `saved` per pixel and iteration
+    work_px: int                   # floats of the backward's work buffer per pixel ...
+    work_tail: Callable = None     # ... plus this many, from the backward's aux arguments (CT keeps its (cos, sin) table there)
+    fwd_checks_iter: bool = True   # the inference wrapper rejects iter_num > T (the train wrapper always does, the backward never)
+
+
+def _c_args(lead):
+    return [_p(a) if isinstance(a, torch.Tensor) else a for a in lead]
+
+
+def _solver_forward(L, ctx, variables, aux_args, params, iter_num, train):
+    """pnpx_<name> -> next state, or pnpx_<name>_train -> (next state, saved [saved_px*T*B*pixels], ticket of the context's
+    activation cache (int, 0 = not cached))."""
+    v = _vars(variables, L.nvar, L.complex_)
+    lead, dims, px, S = L.aux(L, v, aux_args, False)
+    B = dims[0]
+    if train or L.fwd_checks_iter:
+        ps, T = _train_T(B, params, iter_num)
+    else:
+        ps, T = _params(B, *params)
+        T = T if iter_num is None else iter_num
     out = torch.empty_like(v)
+    saved = torch.empty(L.saved_px(S) * T * B * px, dtype=torch.float32, device=v.device) if train else None
     if B == 0:
-        return out
-    stride = ps[0].shape[1]
-    fn = getattr(_lib.lib(), fn_name)
+        return (out, saved, 0) if train else out
+    ticket = C.c_ulonglong(0)
+    fn = getattr(_lib.lib(), f"pnpx_{L.name}_train" if train else f"pnpx_{L.name}")
     with torch.cuda.device(v.device):
-        check(fn(ctx.handle, _p(v), _p(out), _p(y0), _p(m), *[_p(p) for p in ps], stride, B, H, W, T, _stream(v)))
-    return out
+        check(fn(ctx.handle, _p(v), _p(out), *_c_args(lead), *[_p(p) for p in ps], ps[0].shape[1], *dims, T,
+                 *((_p(saved), C.byref(ticket)) if train else ()), _stream(v)))
+    return (out, saved, int(ticket.value)) if train else out
+
+
+def _solver_backward(L, ctx, aux_args, params, saved, grad_out, iter_num, ticket):
+    """pnpx_<name>_backward -> (grad variables, one gradient [B,T] per hyper-parameter)."""
+    g = _vars(grad_out, L.nvar, L.complex_)
+    lead, dims, px, S = L.aux(L, g, aux_args, True)
+    B = dims[0]
+    ps, T = _params(B, *params)
+    T = T if iter_num is None else iter_num
+    if saved.numel() != L.saved_px(S) * T * B * px:
+        raise PnpxError("saved does not belong to a forward of this shape / iteration count")
+    gin = torch.empty_like(g)
+    gs = [torch.zeros(T, B, dtype=torch.float32, device=g.device) for _ in range(L.nhyper)]
+    if B and T:
+        tail = L.work_tail(*aux_args) if L.work_tail else 0
+        work = torch.empty(L.work_px * B * px + tail, dtype=torch.float32, device=g.device)
+        with torch.cuda.device(g.device):
+            check(getattr(_lib.lib(), f"pnpx_{L.name}_backward")(
+                ctx.handle, *_c_args(lead), *[_p(p) for p in ps], ps[0].shape[1], _p(saved), _p(g), _p(gin),
+                *[_p(x) for x in gs], _p(work), *dims, T, int(ticket), _stream(g)))
+    elif B:
+        gin.copy_(g)
+    return (gin, *[x.t().contiguous() for x in gs])
+
+
+def _aux_csmri(L, v, args, backward):
+    B, H, W = v.shape[0], v.shape[2], v.shape[3]
+    y0, m = _f32(args[0], "y0"), _mask_u8(args[1])
+    if not backward and (y0.numel() != B * H * W * 2 or m.numel() != B * H * W):
+        raise PnpxError("y0/mask do not match the state's [B,H,W]")
+    return [y0, m], (B, H, W), H * W, 1
+
+
+def _aux_pr(L, v, args, backward):
+    B, H, W = v.shape[0], v.shape[2], v.shape[3]
+    y0, mask = _f32(args[0], "y0"), _f32(args[1], "mask")
+    # pr_iadmm reads S unguarded (a mask of fewer than two dimensions is an IndexError there), pr_pg does not
+    S = mask.shape[1] if L.name == "pr_iadmm" or mask.dim() == 5 else 0
+    if tuple(mask.shape) != (B, S, H, W, 2) or tuple(y0.shape) != (B, S, H, W):
+        raise PnpxError(f"{L.name}: y0 must be [B,S,H,W] and mask [B,S,H,W,2]")
+    return [y0, mask], (B, S, H, W), H * W, S
+
+
+def _aux_spi(L, v, args, backward):
+    B, H, W = v.shape[0], v.shape[2], v.shape[3]
+    x0, Kmap = _f32(args[0], "x0"), _f32(args[1], "K")
+    if not backward and (x0.numel() != B * H * W or Kmap.numel() != B * H * W):
+        raise PnpxError("spi_admm: x0 and K must be [B,1,H,W]")
+    return [x0, Kmap], (B, H, W), H * W, 1
+
+
+_CSMRI_ADMM = _Loop("csmri_admm", 3, True, _aux_csmri, 2, lambda S: 3, 3)
+_CSMRI_HQS = _Loop("csmri_hqs", 2, True, _aux_csmri, 2, lambda S: 3, 3)
+_CSMRI_PG = _Loop("csmri_pg", 1, True, _aux_csmri, 2, lambda S: 2, 3)
+_CSMRI_APG = _Loop("csmri_apg", 2, True, _aux_csmri, 3, lambda S: 4, 4)
+_CSMRI_RED = _Loop("csmri_redadmm", 3, True, _aux_csmri, 3, lambda S: 7, 4)
+_PR_IADMM = _Loop("pr_iadmm", 3, True, _aux_pr, 3, lambda S: 2 * S + 5, 4, fwd_checks_iter=False)
+_PR_PG = _Loop("pr_pg", 1, True, _aux_pr, 2, lambda S: 2 * S + 2, 3)
+_SPI_ADMM = _Loop("spi_admm", 3, False, _aux_spi, 2, lambda S: 2, 3, fwd_checks_iter=False)
 
 
 def csmri_admm(ctx, variables, y0, mask, sigma_d, mu, iter_num=None):
-    return _csmri_common("pnpx_csmri_admm", 3, ctx, variables, y0, mask, (sigma_d, mu), iter_num)
+    return _solver_forward(_CSMRI_ADMM, ctx, variables, (y0, mask), (sigma_d, mu), iter_num, False)
 
 
-def csmri_admm_train(ctx, variables, y0, mask, sigma_d, mu, iter_num=None, _entry="pnpx_csmri_admm_train", _nvar=3,
-                     _saved_per=3):
+def csmri_admm_train(ctx, variables, y0, mask, sigma_d, mu, iter_num=None):
     """pnpx_csmri_admm_train: the ADMM forward that also returns what its VJP needs -> (next state, saved [3*T*B*H*W],
     ticket of the context's activation cache (int, 0 = not cached))."""
-    v = _vars(variables, _nvar, True)
-    B, _, H, W, _ = v.shape
-    y0, m = _f32(y0, "y0"), _mask_u8(mask)
-    if y0.numel() != B * H * W * 2 or m.numel() != B * H * W:
-        raise PnpxError("y0/mask do not match the state's [B,H,W]")
-    ps, T = _params(B, sigma_d, mu)
-    if iter_num is not None:
-        if iter_num > T:
-            raise PnpxError(f"iter_num {iter_num} exceeds the {T} hyper-parameter columns provided")
-        T = iter_num
-    out = torch.empty_like(v)
-    saved = torch.empty(_saved_per * T * B * H * W, dtype=torch.float32, device=v.device)
-    if B == 0:
-        return out, saved, 0
-    ticket = C.c_ulonglong(0)
-    with torch.cuda.device(v.device):
-        check(getattr(_lib.lib(), _entry)(ctx.handle, _p(v), _p(out), _p(y0), _p(m), _p(ps[0]), _p(ps[1]),
-                                          ps[0].shape[1], B, H, W, T, _p(saved), C.byref(ticket), _stream(v)))
-    return out, saved, int(ticket.value)
+    return _solver_forward(_CSMRI_ADMM, ctx, variables, (y0, mask), (sigma_d, mu), iter_num, True)
+
+
+def csmri_admm_backward(ctx, y0, mask, sigma_d, mu, saved, grad_out, iter_num=None, ticket=0):
+    """pnpx_csmri_admm_backward -> (grad variables [B,3,H,W,2], grad sigma_d [B,T], grad mu [B,T])."""
+    return _solver_backward(_CSMRI_ADMM, ctx, (y0, mask), (sigma_d, mu), saved, grad_out, iter_num, ticket)
+
+
+def csmri_hqs(ctx, variables, y0, mask, sigma_d, mu, iter_num=None):
+    return _solver_forward(_CSMRI_HQS, ctx, variables, (y0, mask), (sigma_d, mu), iter_num, False)
 
 
 def csmri_hqs_train(ctx, variables, y0, mask, sigma_d, mu, iter_num=None):
     """pnpx_csmri_hqs_train: HQSSolver_CSMRI.forward for autograd (state [B,2,H,W,2]); same returns as csmri_admm_train."""
-    return csmri_admm_train(ctx, variables, y0, mask, sigma_d, mu, iter_num, "pnpx_csmri_hqs_train", 2)
+    return _solver_forward(_CSMRI_HQS, ctx, variables, (y0, mask), (sigma_d, mu), iter_num, True)
 
 
 def csmri_hqs_backward(ctx, y0, mask, sigma_d, mu, saved, grad_out, iter_num=None, ticket=0):
     """pnpx_csmri_hqs_backward -> (grad variables [B,2,H,W,2], grad sigma_d [B,T], grad mu [B,T])."""
-    return csmri_admm_backward(ctx, y0, mask, sigma_d, mu, saved, grad_out, iter_num, ticket, "pnpx_csmri_hqs_backward", 2)
+    return _solver_backward(_CSMRI_HQS, ctx, (y0, mask), (sigma_d, mu), saved, grad_out, iter_num, ticket)
+
+
+def csmri_pg(ctx, variables, y0, mask, sigma_d, tau, iter_num=None):
+    return _solver_forward(_CSMRI_PG, ctx, variables, (y0, mask), (sigma_d, tau), iter_num, False)
 
 
 def csmri_pg_train(ctx, variables, y0, mask, sigma_d, tau, iter_num=None):
     """pnpx_csmri_pg_train: PGSolver_CSMRI.forward for autograd (state [B,1,H,W,2]); saved = 2*T*B*H*W floats."""
-    return csmri_admm_train(ctx, variables, y0, mask, sigma_d, tau, iter_num, "pnpx_csmri_pg_train", 1, 2)
+    return _solver_forward(_CSMRI_PG, ctx, variables, (y0, mask), (sigma_d, tau), iter_num, True)
 
 
 def csmri_pg_backward(ctx, y0, mask, sigma_d, tau, saved, grad_out, iter_num=None, ticket=0):
     """pnpx_csmri_pg_backward -> (grad x [B,1,H,W,2], grad sigma_d [B,T], grad tau [B,T])."""
-    return csmri_admm_backward(ctx, y0, mask, sigma_d, tau, saved, grad_out, iter_num, ticket, "pnpx_csmri_pg_backward", 1, 2)
+    return _solver_backward(_CSMRI_PG, ctx, (y0, mask), (sigma_d, tau), saved, grad_out, iter_num, ticket)
 
 
-def csmri_admm_backward(ctx, y0, mask, sigma_d, mu, saved, grad_out, iter_num=None, ticket=0,
-                        _entry="pnpx_csmri_admm_backward", _nvar=3, _saved_per=3):
-    """pnpx_csmri_admm_backward -> (grad variables [B,3,H,W,2], grad sigma_d [B,T], grad mu [B,T])."""
-    g = _vars(grad_out, _nvar, True)
-    B, _, H, W, _ = g.shape
-    y0, m = _f32(y0, "y0"), _mask_u8(mask)
-    ps, T = _params(B, sigma_d, mu)
-    T = T if iter_num is None else iter_num
-    if saved.numel() != _saved_per * T * B * H * W:
-        raise PnpxError("saved does not belong to a forward of this shape / iteration count")
-    gin = torch.empty_like(g)
-    gs = torch.zeros(T, B, dtype=torch.float32, device=g.device)
-    gm = torch.zeros(T, B, dtype=torch.float32, device=g.device)
-    if B and T:
-        work = torch.empty(3 * B * H * W, dtype=torch.float32, device=g.device)
-        with torch.cuda.device(g.device):
-            check(getattr(_lib.lib(), _entry)(ctx.handle, _p(y0), _p(m), _p(ps[0]), _p(ps[1]), ps[0].shape[1],
-                                              _p(saved), _p(g), _p(gin), _p(gs), _p(gm), _p(work), B, H, W, T,
-                                              int(ticket), _stream(g)))
-    elif B:
-        gin.copy_(g)
-    return gin, gs.t().contiguous(), gm.t().contiguous()
-
-
-def _csmri_train3(entry, nvar, per, ctx, variables, y0, mask, params, iter_num):
-    """Training forward of a CS-MRI solver with three hyper-parameter rows -> (next state, saved [per*T*B*H*W], ticket)."""
-    v = _vars(variables, nvar, True)
-    B, _, H, W, _ = v.shape
-    y0, m = _f32(y0, "y0"), _mask_u8(mask)
-    if y0.numel() != B * H * W * 2 or m.numel() != B * H * W:
-        raise PnpxError("y0/mask do not match the state's [B,H,W]")
-    ps, T = _params(B, *params)
-    if iter_num is not None:
-        if iter_num > T:
-            raise PnpxError(f"iter_num {iter_num} exceeds the {T} hyper-parameter columns provided")
-        T = iter_num
-    out = torch.empty_like(v)
-    saved = torch.empty(per * T * B * H * W, dtype=torch.float32, device=v.device)
-    if B == 0:
-        return out, saved, 0
-    ticket = C.c_ulonglong(0)
-    with torch.cuda.device(v.device):
-        check(getattr(_lib.lib(), entry)(ctx.handle, _p(v), _p(out), _p(y0), _p(m), _p(ps[0]), _p(ps[1]), _p(ps[2]),
-                                         ps[0].shape[1], B, H, W, T, _p(saved), C.byref(ticket), _stream(v)))
-    return out, saved, int(ticket.value)
-
-
-def _csmri_backward3(entry, nvar, per, ctx, y0, mask, params, saved, grad_out, iter_num, ticket):
-    """Fused VJP of the same -> (grad variables, three hyper-parameter gradients, each [B,T])."""
-    g = _vars(grad_out, nvar, True)
-    B, _, H, W, _ = g.shape
-    y0, m = _f32(y0, "y0"), _mask_u8(mask)
-    ps, T = _params(B, *params)
-    T = T if iter_num is None else iter_num
-    if saved.numel() != per * T * B * H * W:
-        raise PnpxError("saved does not belong to a forward of this shape / iteration count")
-    gin = torch.empty_like(g)
-    g0, g1, g2 = (torch.zeros(T, B, dtype=torch.float32, device=g.device) for _ in range(3))
-    if B and T:
-        work = torch.empty(4 * B * H * W, dtype=torch.float32, device=g.device)
-        with torch.cuda.device(g.device):
-            check(getattr(_lib.lib(), entry)(ctx.handle, _p(y0), _p(m), _p(ps[0]), _p(ps[1]), _p(ps[2]), ps[0].shape[1],
-                                             _p(saved), _p(g), _p(gin), _p(g0), _p(g1), _p(g2), _p(work), B, H, W, T,
-                                             int(ticket), _stream(g)))
-    elif B:
-        gin.copy_(g)
-    return gin, g0.t().contiguous(), g1.t().contiguous(), g2.t().contiguous()
+def csmri_apg(ctx, variables, y0, mask, sigma_d, tau, beta, iter_num=None):
+    return _solver_forward(_CSMRI_APG, ctx, variables, (y0, mask), (sigma_d, tau, beta), iter_num, False)
 
 
 def csmri_apg_train(ctx, variables, y0, mask, sigma_d, tau, beta, iter_num=None):
     """pnpx_csmri_apg_train: APGSolver_CSMRI.forward for autograd -> (next state [B,2,H,W,2], saved [4*T*B*H*W], ticket)."""
-    return _csmri_train3("pnpx_csmri_apg_train", 2, 4, ctx, variables, y0, mask, (sigma_d, tau, beta), iter_num)
+    return _solver_forward(_CSMRI_APG, ctx, variables, (y0, mask), (sigma_d, tau, beta), iter_num, True)
 
 
 def csmri_apg_backward(ctx, y0, mask, sigma_d, tau, beta, saved, grad_out, iter_num=None, ticket=0):
     """pnpx_csmri_apg_backward -> (grad variables [B,2,H,W,2], grad sigma_d, grad tau, grad beta, each [B,T])."""
-    return _csmri_backward3("pnpx_csmri_apg_backward", 2, 4, ctx, y0, mask, (sigma_d, tau, beta), saved, grad_out, iter_num,
-                            ticket)
+    return _solver_backward(_CSMRI_APG, ctx, (y0, mask), (sigma_d, tau, beta), saved, grad_out, iter_num, ticket)
+
+
+def csmri_redadmm(ctx, variables, y0, mask, sigma_d, mu, lamda, iter_num=None):
+    return _solver_forward(_CSMRI_RED, ctx, variables, (y0, mask), (sigma_d, mu, lamda), iter_num, False)
 
 
 def csmri_redadmm_train(ctx, variables, y0, mask, sigma_d, mu, lamda, iter_num=None):
     """pnpx_csmri_redadmm_train: REDADMMSolver_CSMRI.forward for autograd -> (next state [B,3,H,W,2], saved [7*T*B*H*W],
     ticket)."""
-    return _csmri_train3("pnpx_csmri_redadmm_train", 3, 7, ctx, variables, y0, mask, (sigma_d, mu, lamda), iter_num)
+    return _solver_forward(_CSMRI_RED, ctx, variables, (y0, mask), (sigma_d, mu, lamda), iter_num, True)
 
 
 def csmri_redadmm_backward(ctx, y0, mask, sigma_d, mu, lamda, saved, grad_out, iter_num=None, ticket=0):
     """pnpx_csmri_redadmm_backward -> (grad variables [B,3,H,W,2], grad sigma_d, grad mu, grad lamda, each [B,T])."""
-    return _csmri_backward3("pnpx_csmri_redadmm_backward", 3, 7, ctx, y0, mask, (sigma_d, mu, lamda), saved, grad_out,
-                            iter_num, ticket)
-
-
-def csmri_hqs(ctx, variables, y0, mask, sigma_d, mu, iter_num=None):
-    return _csmri_common("pnpx_csmri_hqs", 2, ctx, variables, y0, mask, (sigma_d, mu), iter_num)
+    return _solver_backward(_CSMRI_RED, ctx, (y0, mask), (sigma_d, mu, lamda), saved, grad_out, iter_num, ticket)
 
 
 def csmri_amp(ctx, variables, y0, mask, sigma_d, probe, iter_num=None):
@@ -917,11 +932,7 @@ def csmri_amp(ctx, variables, y0, mask, sigma_d, probe, iter_num=None):
     delta of each iteration (the reference's torch.randn_like(r))."""
     v = _vars(variables, 2, True)
     B, _, H, W, _ = v.shape
-    ps, T = _params(B, sigma_d)
-    if iter_num is not None:
-        if iter_num > T:
-            raise PnpxError(f"iter_num {iter_num} exceeds the {T} hyper-parameter columns provided")
-        T = iter_num
+    ps, T = _train_T(B, (sigma_d,), iter_num)
     d = _f32(probe, "probe")
     if d.dim() != 5 or d.shape[0] < T or tuple(d.shape[1:]) != (B, 1, H, W):
         raise PnpxError(f"probe must be [{T}, {B}, 1, {H}, {W}], got {tuple(d.shape)}")
@@ -938,214 +949,47 @@ def csmri_amp(ctx, variables, y0, mask, sigma_d, probe, iter_num=None):
     return out
 
 
-def csmri_pg(ctx, variables, y0, mask, sigma_d, tau, iter_num=None):
-    return _csmri_common("pnpx_csmri_pg", 1, ctx, variables, y0, mask, (sigma_d, tau), iter_num)
-
-
-def csmri_apg(ctx, variables, y0, mask, sigma_d, tau, beta, iter_num=None):
-    return _csmri_common("pnpx_csmri_apg", 2, ctx, variables, y0, mask, (sigma_d, tau, beta), iter_num)
-
-
-def csmri_redadmm(ctx, variables, y0, mask, sigma_d, mu, lamda, iter_num=None):
-    return _csmri_common("pnpx_csmri_redadmm", 3, ctx, variables, y0, mask, (sigma_d, mu, lamda), iter_num)
-
-
 def pr_iadmm(ctx, variables, y0, mask, sigma_d, mu, tau, iter_num=None):
-    v = _vars(variables, 3, True)
-    B, _, H, W, _ = v.shape
-    y0 = _f32(y0, "y0")
-    mask = _f32(mask, "mask")
-    S = mask.shape[1]
-    if tuple(mask.shape) != (B, S, H, W, 2) or tuple(y0.shape) != (B, S, H, W):
-        raise PnpxError("pr_iadmm: y0 must be [B,S,H,W] and mask [B,S,H,W,2]")
-    ps, T = _params(B, sigma_d, mu, tau)
-    T = T if iter_num is None else iter_num
-    out = torch.empty_like(v)
-    if B == 0:
-        return out
-    with torch.cuda.device(v.device):
-        check(_lib.lib().pnpx_pr_iadmm(ctx.handle, _p(v), _p(out), _p(y0), _p(mask), *[_p(p) for p in ps],
-                                       ps[0].shape[1], B, S, H, W, T, _stream(v)))
-    return out
-
-
-def _pr_args(variables, y0, mask):
-    v = _vars(variables, 3, True)
-    B, _, H, W, _ = v.shape
-    y0, mask = _f32(y0, "y0"), _f32(mask, "mask")
-    S = mask.shape[1]
-    if tuple(mask.shape) != (B, S, H, W, 2) or tuple(y0.shape) != (B, S, H, W):
-        raise PnpxError("pr_iadmm: y0 must be [B,S,H,W] and mask [B,S,H,W,2]")
-    return v, y0, mask, B, S, H, W
+    return _solver_forward(_PR_IADMM, ctx, variables, (y0, mask), (sigma_d, mu, tau), iter_num, False)
 
 
 def pr_iadmm_train(ctx, variables, y0, mask, sigma_d, mu, tau, iter_num=None):
     """pnpx_pr_iadmm_train: IADMMSolver_PR.forward for autograd -> (next state [B,3,H,W,2], saved [(2S+5)*T*B*H*W], ticket)."""
-    v, y0, mask, B, S, H, W = _pr_args(variables, y0, mask)
-    ps, T = _params(B, sigma_d, mu, tau)
-    if iter_num is not None:
-        if iter_num > T:
-            raise PnpxError(f"iter_num {iter_num} exceeds the {T} hyper-parameter columns provided")
-        T = iter_num
-    out = torch.empty_like(v)
-    saved = torch.empty((2 * S + 5) * T * B * H * W, dtype=torch.float32, device=v.device)
-    if B == 0:
-        return out, saved, 0
-    ticket = C.c_ulonglong(0)
-    with torch.cuda.device(v.device):
-        check(_lib.lib().pnpx_pr_iadmm_train(ctx.handle, _p(v), _p(out), _p(y0), _p(mask), *[_p(p) for p in ps],
-                                             ps[0].shape[1], B, S, H, W, T, _p(saved), C.byref(ticket), _stream(v)))
-    return out, saved, int(ticket.value)
+    return _solver_forward(_PR_IADMM, ctx, variables, (y0, mask), (sigma_d, mu, tau), iter_num, True)
 
 
 def pr_iadmm_backward(ctx, y0, mask, sigma_d, mu, tau, saved, grad_out, iter_num=None, ticket=0):
     """pnpx_pr_iadmm_backward -> (grad variables [B,3,H,W,2], grad sigma_d, grad mu, grad tau, each [B,T])."""
-    g, y0, mask, B, S, H, W = _pr_args(grad_out, y0, mask)
-    ps, T = _params(B, sigma_d, mu, tau)
-    T = T if iter_num is None else iter_num
-    if saved.numel() != (2 * S + 5) * T * B * H * W:
-        raise PnpxError("saved does not belong to a forward of this shape / iteration count")
-    gin = torch.empty_like(g)
-    g0, g1, g2 = (torch.zeros(T, B, dtype=torch.float32, device=g.device) for _ in range(3))
-    if B and T:
-        work = torch.empty(4 * B * H * W, dtype=torch.float32, device=g.device)
-        with torch.cuda.device(g.device):
-            check(_lib.lib().pnpx_pr_iadmm_backward(ctx.handle, _p(y0), _p(mask), *[_p(p) for p in ps], ps[0].shape[1],
-                                                    _p(saved), _p(g), _p(gin), _p(g0), _p(g1), _p(g2), _p(work), B, S, H, W,
-                                                    T, int(ticket), _stream(g)))
-    elif B:
-        gin.copy_(g)
-    return gin, g0.t().contiguous(), g1.t().contiguous(), g2.t().contiguous()
-
-
-def _pr_pg_args(variables, y0, mask):
-    v = _vars(variables, 1, True)
-    B, _, H, W, _ = v.shape
-    y0, mask = _f32(y0, "y0"), _f32(mask, "mask")
-    S = mask.shape[1] if mask.dim() == 5 else 0
-    if tuple(mask.shape) != (B, S, H, W, 2) or tuple(y0.shape) != (B, S, H, W):
-        raise PnpxError("pr_pg: y0 must be [B,S,H,W] and mask [B,S,H,W,2]")
-    return v, y0, mask, B, S, H, W
+    return _solver_backward(_PR_IADMM, ctx, (y0, mask), (sigma_d, mu, tau), saved, grad_out, iter_num, ticket)
 
 
 def pr_pg(ctx, variables, y0, mask, sigma_d, tau, iter_num=None):
     """pnpx_pr_pg: PGSolver_PR.forward, x [B,1,H,W,2] -> next x (imaginary part 0)."""
-    v, y0, mask, B, S, H, W = _pr_pg_args(variables, y0, mask)
-    ps, T = _train_T(B, (sigma_d, tau), iter_num)
-    out = torch.empty_like(v)
-    if B == 0:
-        return out
-    with torch.cuda.device(v.device):
-        check(_lib.lib().pnpx_pr_pg(ctx.handle, _p(v), _p(out), _p(y0), _p(mask), *[_p(p) for p in ps], ps[0].shape[1],
-                                    B, S, H, W, T, _stream(v)))
-    return out
+    return _solver_forward(_PR_PG, ctx, variables, (y0, mask), (sigma_d, tau), iter_num, False)
 
 
 def pr_pg_train(ctx, variables, y0, mask, sigma_d, tau, iter_num=None):
     """pnpx_pr_pg_train: PGSolver_PR.forward for autograd -> (next x [B,1,H,W,2], saved [(2S+2)*T*B*H*W], ticket)."""
-    v, y0, mask, B, S, H, W = _pr_pg_args(variables, y0, mask)
-    ps, T = _train_T(B, (sigma_d, tau), iter_num)
-    out = torch.empty_like(v)
-    saved = torch.empty((2 * S + 2) * T * B * H * W, dtype=torch.float32, device=v.device)
-    if B == 0:
-        return out, saved, 0
-    ticket = C.c_ulonglong(0)
-    with torch.cuda.device(v.device):
-        check(_lib.lib().pnpx_pr_pg_train(ctx.handle, _p(v), _p(out), _p(y0), _p(mask), *[_p(p) for p in ps],
-                                          ps[0].shape[1], B, S, H, W, T, _p(saved), C.byref(ticket), _stream(v)))
-    return out, saved, int(ticket.value)
+    return _solver_forward(_PR_PG, ctx, variables, (y0, mask), (sigma_d, tau), iter_num, True)
 
 
 def pr_pg_backward(ctx, y0, mask, sigma_d, tau, saved, grad_out, iter_num=None, ticket=0):
     """pnpx_pr_pg_backward -> (grad x [B,1,H,W,2], grad sigma_d, grad tau, each [B,T])."""
-    g, y0, mask, B, S, H, W = _pr_pg_args(grad_out, y0, mask)
-    ps, T = _params(B, sigma_d, tau)
-    T = T if iter_num is None else iter_num
-    if saved.numel() != (2 * S + 2) * T * B * H * W:
-        raise PnpxError("saved does not belong to a forward of this shape / iteration count")
-    gin = torch.empty_like(g)
-    gs = _hyper_grads(T, B, 2, g.device)
-    if B and T:
-        work = torch.empty(3 * B * H * W, dtype=torch.float32, device=g.device)
-        with torch.cuda.device(g.device):
-            check(_lib.lib().pnpx_pr_pg_backward(ctx.handle, _p(y0), _p(mask), *[_p(p) for p in ps], ps[0].shape[1],
-                                                 _p(saved), _p(g), _p(gin), *[_p(x) for x in gs], _p(work), B, S, H, W, T,
-                                                 int(ticket), _stream(g)))
-    elif B:
-        gin.copy_(g)
-    return (gin, *[x.t().contiguous() for x in gs])
+    return _solver_backward(_PR_PG, ctx, (y0, mask), (sigma_d, tau), saved, grad_out, iter_num, ticket)
 
 
 def spi_admm(ctx, variables, x0, Kmap, sigma_d, mu, iter_num=None):
-    v = _vars(variables, 3, False)
-    B, _, H, W = v.shape
-    x0 = _f32(x0, "x0")
-    Kmap = _f32(Kmap, "K")
-    if x0.numel() != B * H * W or Kmap.numel() != B * H * W:
-        raise PnpxError("spi_admm: x0 and K must be [B,1,H,W]")
-    ps, T = _params(B, sigma_d, mu)
-    T = T if iter_num is None else iter_num
-    out = torch.empty_like(v)
-    if B == 0:
-        return out
-    with torch.cuda.device(v.device):
-        check(_lib.lib().pnpx_spi_admm(ctx.handle, _p(v), _p(out), _p(x0), _p(Kmap), *[_p(p) for p in ps],
-                                       ps[0].shape[1], B, H, W, T, _stream(v)))
-    return out
-
-
-def _train_T(B, params, iter_num):
-    ps, T = _params(B, *params)
-    if iter_num is not None:
-        if iter_num > T:
-            raise PnpxError(f"iter_num {iter_num} exceeds the {T} hyper-parameter columns provided")
-        T = iter_num
-    return ps, T
-
-
-def _hyper_grads(T, B, k, device):
-    return [torch.zeros(T, B, dtype=torch.float32, device=device) for _ in range(k)]
+    return _solver_forward(_SPI_ADMM, ctx, variables, (x0, Kmap), (sigma_d, mu), iter_num, False)
 
 
 def spi_admm_train(ctx, variables, x0, Kmap, sigma_d, mu, iter_num=None):
     """pnpx_spi_admm_train: ADMMSolver_SPI.forward for autograd -> (next state [B,3,H,W], saved [2*T*B*H*W], ticket)."""
-    v = _vars(variables, 3, False)
-    B, _, H, W = v.shape
-    x0, Kmap = _f32(x0, "x0"), _f32(Kmap, "K")
-    if x0.numel() != B * H * W or Kmap.numel() != B * H * W:
-        raise PnpxError("spi_admm: x0 and K must be [B,1,H,W]")
-    ps, T = _train_T(B, (sigma_d, mu), iter_num)
-    out = torch.empty_like(v)
-    saved = torch.empty(2 * T * B * H * W, dtype=torch.float32, device=v.device)
-    if B == 0:
-        return out, saved, 0
-    ticket = C.c_ulonglong(0)
-    with torch.cuda.device(v.device):
-        check(_lib.lib().pnpx_spi_admm_train(ctx.handle, _p(v), _p(out), _p(x0), _p(Kmap), *[_p(p) for p in ps],
-                                             ps[0].shape[1], B, H, W, T, _p(saved), C.byref(ticket), _stream(v)))
-    return out, saved, int(ticket.value)
+    return _solver_forward(_SPI_ADMM, ctx, variables, (x0, Kmap), (sigma_d, mu), iter_num, True)
 
 
 def spi_admm_backward(ctx, x0, Kmap, sigma_d, mu, saved, grad_out, iter_num=None, ticket=0):
     """pnpx_spi_admm_backward -> (grad variables [B,3,H,W], grad sigma_d, grad mu, each [B,T])."""
-    g = _vars(grad_out, 3, False)
-    B, _, H, W = g.shape
-    x0, Kmap = _f32(x0, "x0"), _f32(Kmap, "K")
-    ps, T = _params(B, sigma_d, mu)
-    T = T if iter_num is None else iter_num
-    if saved.numel() != 2 * T * B * H * W:
-        raise PnpxError("saved does not belong to a forward of this shape / iteration count")
-    gin = torch.empty_like(g)
-    gs = _hyper_grads(T, B, 2, g.device)
-    if B and T:
-        work = torch.empty(3 * B * H * W, dtype=torch.float32, device=g.device)
-        with torch.cuda.device(g.device):
-            check(_lib.lib().pnpx_spi_admm_backward(ctx.handle, _p(x0), _p(Kmap), _p(ps[0]), _p(ps[1]), ps[0].shape[1],
-                                                    _p(saved), _p(g), _p(gin), _p(gs[0]), _p(gs[1]), _p(work), B, H, W, T,
-                                                    int(ticket), _stream(g)))
-    elif B:
-        gin.copy_(g)
-    return (gin, *[x.t().contiguous() for x in gs])
+    return _solver_backward(_SPI_ADMM, ctx, (x0, Kmap), (sigma_d, mu), saved, grad_out, iter_num, ticket)
 
 
 # ------------------------------------------------------------------------------------------------- CT
@@ -1186,112 +1030,46 @@ def _ct_sino(y0, B, R, n_view):
     return y0
 
 
+def _aux_ct(L, v, args, backward):
+    B, R = v.shape[0], v.shape[2]
+    lead = [] if backward else [_ct_sino(args[0], B, R, args[1])]   # the backward entries take no sinogram
+    n_view, opnorm = args[-2:]
+    return lead + [int(n_view), float(opnorm)], (B, R), R * R, 1
+
+
+_CT_IADMM = _Loop("ct_iadmm", 3, False, _aux_ct, 3, lambda S: 3, 6, lambda n_view, opnorm: 2 * int(n_view),
+                  fwd_checks_iter=False)
+# +1: the float2 table stands at an even float offset
+_CT_PG = _Loop("ct_pg", 1, False, _aux_ct, 2, lambda S: 2, 3, lambda n_view, opnorm: 1 + 2 * int(n_view),
+               fwd_checks_iter=False)
+
+
 def ct_iadmm(ctx, variables, y0, n_view, opnorm, sigma_d, mu, tau, iter_num=None):
-    v = _vars(variables, 3, False)
-    B, _, R, _ = v.shape
-    y0 = _ct_sino(y0, B, R, n_view)
-    ps, T = _params(B, sigma_d, mu, tau)
-    T = T if iter_num is None else iter_num
-    out = torch.empty_like(v)
-    if B == 0:
-        return out
-    with torch.cuda.device(v.device):
-        check(_lib.lib().pnpx_ct_iadmm(ctx.handle, _p(v), _p(out), _p(y0), int(n_view), float(opnorm),
-                                       *[_p(p) for p in ps], ps[0].shape[1], B, R, T, _stream(v)))
-    return out
+    return _solver_forward(_CT_IADMM, ctx, variables, (y0, n_view, opnorm), (sigma_d, mu, tau), iter_num, False)
 
 
 def ct_pg(ctx, variables, y0, n_view, opnorm, sigma_d, tau, iter_num=None):
-    v = _vars(variables, 1, False)
-    B, _, R, _ = v.shape
-    y0 = _ct_sino(y0, B, R, n_view)
-    ps, T = _params(B, sigma_d, tau)
-    T = T if iter_num is None else iter_num
-    out = torch.empty_like(v)
-    if B == 0:
-        return out
-    with torch.cuda.device(v.device):
-        check(_lib.lib().pnpx_ct_pg(ctx.handle, _p(v), _p(out), _p(y0), int(n_view), float(opnorm),
-                                    *[_p(p) for p in ps], ps[0].shape[1], B, R, T, _stream(v)))
-    return out
+    return _solver_forward(_CT_PG, ctx, variables, (y0, n_view, opnorm), (sigma_d, tau), iter_num, False)
 
 
 def ct_iadmm_train(ctx, variables, y0, n_view, opnorm, sigma_d, mu, tau, iter_num=None):
     """pnpx_ct_iadmm_train: IADMMSolver_CT.forward for autograd -> (next state [B,3,R,R], saved [3*T*B*R*R], ticket)."""
-    v = _vars(variables, 3, False)
-    B, _, R, _ = v.shape
-    y0 = _ct_sino(y0, B, R, n_view)
-    ps, T = _train_T(B, (sigma_d, mu, tau), iter_num)
-    out = torch.empty_like(v)
-    saved = torch.empty(3 * T * B * R * R, dtype=torch.float32, device=v.device)
-    if B == 0:
-        return out, saved, 0
-    ticket = C.c_ulonglong(0)
-    with torch.cuda.device(v.device):
-        check(_lib.lib().pnpx_ct_iadmm_train(ctx.handle, _p(v), _p(out), _p(y0), int(n_view), float(opnorm),
-                                             *[_p(p) for p in ps], ps[0].shape[1], B, R, T, _p(saved), C.byref(ticket),
-                                             _stream(v)))
-    return out, saved, int(ticket.value)
+    return _solver_forward(_CT_IADMM, ctx, variables, (y0, n_view, opnorm), (sigma_d, mu, tau), iter_num, True)
 
 
 def ct_iadmm_backward(ctx, n_view, opnorm, sigma_d, mu, tau, saved, grad_out, iter_num=None, ticket=0):
     """pnpx_ct_iadmm_backward -> (grad variables [B,3,R,R], grad sigma_d, grad mu, grad tau, each [B,T])."""
-    g = _vars(grad_out, 3, False)
-    B, _, R, _ = g.shape
-    ps, T = _params(B, sigma_d, mu, tau)
-    T = T if iter_num is None else iter_num
-    if saved.numel() != 3 * T * B * R * R:
-        raise PnpxError("saved does not belong to a forward of this shape / iteration count")
-    gin = torch.empty_like(g)
-    gs = _hyper_grads(T, B, 3, g.device)
-    if B and T:
-        work = torch.empty(6 * B * R * R + 2 * int(n_view), dtype=torch.float32, device=g.device)
-        with torch.cuda.device(g.device):
-            check(_lib.lib().pnpx_ct_iadmm_backward(ctx.handle, int(n_view), float(opnorm), *[_p(p) for p in ps],
-                                                    ps[0].shape[1], _p(saved), _p(g), _p(gin), *[_p(x) for x in gs], _p(work),
-                                                    B, R, T, int(ticket), _stream(g)))
-    elif B:
-        gin.copy_(g)
-    return (gin, *[x.t().contiguous() for x in gs])
+    return _solver_backward(_CT_IADMM, ctx, (n_view, opnorm), (sigma_d, mu, tau), saved, grad_out, iter_num, ticket)
 
 
 def ct_pg_train(ctx, variables, y0, n_view, opnorm, sigma_d, tau, iter_num=None):
     """pnpx_ct_pg_train: PGSolver_CT.forward for autograd -> (next x [B,1,R,R], saved [2*T*B*R*R], ticket)."""
-    v = _vars(variables, 1, False)
-    B, _, R, _ = v.shape
-    y0 = _ct_sino(y0, B, R, n_view)
-    ps, T = _train_T(B, (sigma_d, tau), iter_num)
-    out = torch.empty_like(v)
-    saved = torch.empty(2 * T * B * R * R, dtype=torch.float32, device=v.device)
-    if B == 0:
-        return out, saved, 0
-    ticket = C.c_ulonglong(0)
-    with torch.cuda.device(v.device):
-        check(_lib.lib().pnpx_ct_pg_train(ctx.handle, _p(v), _p(out), _p(y0), int(n_view), float(opnorm),
-                                          *[_p(p) for p in ps], ps[0].shape[1], B, R, T, _p(saved), C.byref(ticket),
-                                          _stream(v)))
-    return out, saved, int(ticket.value)
+    return _solver_forward(_CT_PG, ctx, variables, (y0, n_view, opnorm), (sigma_d, tau), iter_num, True)
 
 
 def ct_pg_backward(ctx, n_view, opnorm, sigma_d, tau, saved, grad_out, iter_num=None, ticket=0):
     """pnpx_ct_pg_backward -> (grad x [B,1,R,R], grad sigma_d, grad tau, each [B,T])."""
-    g = _vars(grad_out, 1, False)
-    B, _, R, _ = g.shape
-    ps, T = _params(B, sigma_d, tau)
-    T = T if iter_num is None else iter_num
-    if saved.numel() != 2 * T * B * R * R:
-        raise PnpxError("saved does not belong to a forward of this shape / iteration count")
-    gin = torch.empty_like(g)
-    gs = _hyper_grads(T, B, 2, g.device)
-    if B and T:
-        work = torch.empty(3 * B * R * R + 1 + 2 * int(n_view), dtype=torch.float32, device=g.device)   # +1: float2 table at an even offset
-        with torch.cuda.device(g.device):
-            check(_lib.lib().pnpx_ct_pg_backward(ctx.handle, int(n_view), float(opnorm), *[_p(p) for p in ps], ps[0].shape[1],
-                                                 _p(saved), _p(g), _p(gin), *[_p(x) for x in gs], _p(work), B, R, T,
-                                                 int(ticket), _stream(g)))
-    elif B:
-        gin.copy_(g)
-    return (gin, *[x.t().contiguous() for x in gs])
+    return _solver_backward(_CT_PG, ctx, (n_view, opnorm), (sigma_d, tau), saved, grad_out, iter_num, ticket)
 
 
 # ------------------------------------------------------------------------------------- episode orchestration (env.hip)
