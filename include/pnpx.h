@@ -81,6 +81,12 @@ int pnpx_ctx_reserve(pnpx_ctx* ctx, int B, int H, int W);
  *      itself and the up-sampling kernel is not launched.  It needs two 8-channel chunks of the first source (C0 >= 16); an entry without
  *      them, and every call in which the K-split claims the entry, stay as they are.  The result is bit-identical to the two-launch form
  *      (same floats for positions and weights, same rounding sequence), so 0 = the up-sampling kernel + the two-source instance, same bits.
+ *  "fp32_winof4_c32" (layer mask numbered like fp32_winof4_layers; only bits 1, 2 and 25 are accepted; default: see
+ *      profiles/winof4_c32.md): bit i = the full-resolution 32 -> 32 layer i (layer 2 with its fused max-pool) runs on the 32-cout instance
+ *      of the F(4x4,3x3) kernel (a workgroup owns 32 couts x a region of 16 x 64 px) in forward passes, inference and training alike, when
+ *      its fp32_wino8_layers bit is set, "fp32_winograd" is 1 and its geometry allows: a single source, cout % 32 == 0 and cout % 64 != 0,
+ *      >= 16 input channels in multiples of 8, H % 16 == 0, W % 64 == 0.  The decoder entry 24, the last layer 26 (out-conv epilogue) and
+ *      the backward pass keep the F(2x2) kernel.  0 = F(2x2) on these layers (bit-identical to the library before the option existed).
  *  "fp32_chains" (default 2): in conv_mode 0 the denoiser forward runs as n independent launch chains over contiguous slices of the batch
  *      (caller's stream + side streams, joined before the entry returns; bit-identical per image): 2 measured best (-3.6 % at 48 x 256^2,
  *      -7 % at B = 24); 1 = only the bottom level's three launches fork two chains; 0 = one chain.  The VJP's adjoint chain forks exactly
@@ -671,6 +677,9 @@ int pnpx_ct_pg_backward(pnpx_ctx* ctx, int n_view, float opnorm, const float* si
  * position (2 stage + row, 2 pair + column), channel 8 chunk + 2 group + k-step). */
 void pnpx_winof4_matrices(double* g18, double* bt36, double* at24);
 int pnpx_winof4_pack(const float* w, int cout, int cin, float* dst);
+/* ... and the packer of the kernel's 32-cout instance (cout % 32 == 0): [cout/32][cin/8][stage 3][row 2][column pair 3][cout block 2]
+ * [channel group 4][cout 16][k-step 2][column 2], positions and channels numbered as above. */
+int pnpx_winof4_c32_pack(const float* w, int cout, int cin, float* dst);
 
 /* Single-layer probe of the fp32 3x3 convolution kernels of conv_mode 0 (csrc/conv_probe.hip), for tests: one layer's HOST weights are
  * packed by the packers pnpx_unet_load uses and ONE kernel of the chosen kind runs on DEVICE tensors the caller laid out in the denoiser's
@@ -683,7 +692,7 @@ int pnpx_winof4_pack(const float* w, int cout, int cin, float* dst);
  *     WINOF4 is single-source (C1 = 0), WINOF4_2SRC the same kernel's two-source instance (C1 > 0, in1 at full resolution; takes
  *     pool_out); WINOF4_UPS is reserved (its plan is 0 for every geometry and the probe returns PNPX_ERR_SHAPE) and stays so: the
  *     instance that up-samples in1 (LOW-resolution [B][C1][H/2 + 2][W/2 + 8], like WINO8_UPS) is kind WINOF4_FUSE_UP = 11, and 10 is
- *     unknown.
+ *     unknown.  WINOF4_C32 = 12 is the F(4x4,3x3) kernel's 32-cout instance: single-source, takes pool_out, W % 64 == 0.
  *   adjoint kinds: w is the FORWARD layer's [C0][cout][3][3]; in0 = the gradient of its output (C0 channels), out = the gradient of its
  *     input (cout channels, a multiple of 32) = conv_transpose(in0, w), times (mask > 0 ? 1 : slope) when mask (out's geometry) is given;
  *     no bias.
@@ -702,7 +711,8 @@ enum pnpx_probe_kind {
   PNPX_PROBE_WINOF4_2SRC = 8,   /* the F(4x4,3x3) kernel's two-source instance: in1 at full resolution, C1 > 0 */
   PNPX_PROBE_WINOF4_UPS = 9,    /* reserved before an F(4x4,3x3) instance that up-samples in1 existed: still refuses every geometry */
   /* 10 is no kind */
-  PNPX_PROBE_WINOF4_FUSE_UP = 11   /* the F(4x4,3x3) kernel's up-sampling instance: in1 at H/2 x W/2, C1 > 0, C0 >= 16; no pool_out */
+  PNPX_PROBE_WINOF4_FUSE_UP = 11,  /* the F(4x4,3x3) kernel's up-sampling instance: in1 at H/2 x W/2, C1 > 0, C0 >= 16; no pool_out */
+  PNPX_PROBE_WINOF4_C32 = 12       /* the F(4x4,3x3) kernel's 32-cout instance: cout % 32 == 0 and % 64 != 0, C1 = 0, W % 64 == 0 */
 };
 int pnpx_conv3x3_probe(pnpx_ctx* ctx, int kind, const float* w_host, const float* bias_host, int cout, const float* in0, int C0,
                        const float* in1, int C1, float* out, const float* res, const float* mask, float slope, float* pool_out,
@@ -720,6 +730,12 @@ int pnpx_upsample2x_probe(pnpx_ctx* ctx, const float* src, float* dst, int plane
  * Returns kernel + 16 x K-split pieces + 256 x fused, kernel 0 = direct, 1 = 4-wave F(2x2), 2 = 8-wave F(2x2), 3 = F(4x4); fused = the
  * instance that up-samples the second source itself runs (else the separate up-sampling kernel runs first); -1 = a non-positive size. */
 int pnpx_conv_f32_entry_plan(int opts, int ksplit, int ksplit_rule, int C0, int C1, int cout, int H, int W, int B_call);
+/* ... and which kernel a plain forward layer gets (conv_f32_forward; C1 >= 0) or, with bit 7, the network's last 3x3 layer (conv_f32_last).
+ * opts: bit 0 "fp32_winograd", bit 1 the layer's "fp32_wino8_layers" bit, bit 2 its "fp32_winof4_layers" bit, bit 3 its "fp32_winof4_c32"
+ * bit, bit 4 its F(2x2) weights are packed, bit 5 its F(4x4) weights, bit 6 its F(4x4) weights in the 32-cout instance's layout, bit 7
+ * the layer is the last one.  Same return value, kernel 4 = the F(4x4) kernel's 32-cout instance; fused = the layer's fused epilogue
+ * (2x2 max-pool; last layer: out-conv) is available. */
+int pnpx_conv_f32_forward_plan(int opts, int ksplit, int ksplit_rule, int C0, int C1, int cout, int H, int W, int B_call);
 
 #ifdef __cplusplus
 }

@@ -153,6 +153,8 @@ _SIGNATURES = {
     "pnpx_conv3x3_probe_plan": (C.c_int, [C.c_int] * 7),
     "pnpx_upsample2x_probe": (C.c_int, [c_void_p, _P, _P, C.c_int, C.c_int, C.c_int, c_void_p]),
     "pnpx_conv_f32_entry_plan": (C.c_int, [C.c_int] * 9),
+    "pnpx_conv_f32_forward_plan": (C.c_int, [C.c_int] * 9),
+    "pnpx_winof4_c32_pack": (C.c_int, [c_void_p, C.c_int, C.c_int, c_void_p]),
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 

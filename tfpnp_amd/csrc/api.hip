@@ -408,6 +408,7 @@ const PlainOption PLAIN_OPTIONS[] = {
     {"fp32_winof4_entries", &pnpx_ctx::opt_fp32_winof4_entries, 0, (1 << 27) - 1},      // bits 15, 18, 21: that decoder entry on it
     {"fp32_winof4_fuse_up", &pnpx_ctx::opt_fp32_winof4_fuse_up, 0, (1 << 27) - 1},      // bits 15, 18, 21: ... up-sampling its second source itself
 };
+constexpr int WINOF4_C32_BITS = (1 << 1) | (1 << 2) | (1 << 25);      // the layers the 32-cout F(4x4,3x3) weights are packed for
 const PlainOption* plain_option(const char* key) {
   for (const PlainOption& o : PLAIN_OPTIONS)
     if (key && !std::strcmp(key, o.name)) return &o;
@@ -423,6 +424,10 @@ int pnpx_ctx_set_option(pnpx_ctx* ctx, const char* key, int value) {
       ctx->*(o->field) = value;
       return PNPX_OK;
     }
+  }
+  if (is("fp32_winof4_c32") && value >= 0 && (value & ~WINOF4_C32_BITS) == 0) {   // bits 1, 2, 25: that layer on the 32-cout F(4x4,3x3) instance
+    ctx->opt_fp32_winof4_c32 = value;
+    return PNPX_OK;
   }
   if (is("drunet_shift") && value >= 0 && value <= 8 && (value & 3) == 0) {   // DRUNet passes run on inputs scaled by 2^-value
     ctx->drunet.shift = value;                                                 // (raised by 4 whenever the range guard trips)
@@ -461,6 +466,7 @@ int pnpx_ctx_get_option(pnpx_ctx* ctx, const char* key, int* value) {
     return PNPX_ERR_ARG;
   }
   if (const PlainOption* o = plain_option(key)) *value = ctx->*(o->field);
+  else if (is("fp32_winof4_c32")) *value = ctx->opt_fp32_winof4_c32;
   else if (is("drunet_shift")) *value = ctx->drunet.shift;
   else if (is("policy_s2_hs")) *value = 1;
   else if (is("range_guard")) *value = ctx->opt_range_guard;
@@ -618,6 +624,21 @@ int pnpx_unet_load(pnpx_ctx* ctx, const float* params_host, size_t n_params) {
       wsrc += (size_t)L[i].cin * L[i].cout * 9 + L[i].cout;
     }
   }
+  // ... and in the 32-cout instance's layout for the full-resolution 32 -> 32 layers (1, 2, 25: 36 * 32 * 32 floats each)
+  size_t u4c32off[27];
+  {
+    const float* wsrc = params_host;
+    for (int i = 0; i < 27; ++i) {
+      u4c32off[i] = 0;
+      if (((WINOF4_C32_BITS >> i) & 1) && conv3x3_winof4_c32_packs(L[i].cout, L[i].cin)) {
+        align();
+        u4c32off[i] = host.size();
+        host.resize(host.size() + conv3x3_winof4_floats(L[i].cout, L[i].cin));
+        pack_conv_weights_winof4_c32(wsrc, L[i].cout, L[i].cin, host.data() + u4c32off[i]);
+      }
+      wsrc += (size_t)L[i].cin * L[i].cout * 9 + L[i].cout;
+    }
+  }
   size_t thoff[27], tuoff[27];      // tuoff: the same adjoint layers as Winograd weights of the fp32 family (conv3x3_wino8.hip, r5)
   float thscale[27];
   {
@@ -680,6 +701,7 @@ int pnpx_unet_load(pnpx_ctx* ctx, const float* params_host, size_t n_params) {
     ctx->conv_wino_u[i] = uoff[i] ? d + uoff[i] : nullptr;
     ctx->conv_wino_u_bwd[i] = tuoff[i] ? d + tuoff[i] : nullptr;
     ctx->conv_winof4_u[i] = u4off[i] ? d + u4off[i] : nullptr;
+    ctx->conv_winof4_c32_u[i] = u4c32off[i] ? d + u4c32off[i] : nullptr;
     ctx->conv_hs[i].w = reinterpret_cast<char*>(d + hoff[i]);
     ctx->conv_bwd[i].w = d + toff[i];
     ctx->conv_bwd[i].b = nullptr;

@@ -269,6 +269,13 @@ struct pnpx_ctx {
   // second source itself runs it and the up-sampling launch is skipped; same bits in the result.  Default: entry 21 alone, the one whose
   // up-sampling launch costs more than the interpolation in the kernel does (profiles/winof4_fuse_up.md)
   int opt_fp32_winof4_fuse_up = 1 << 21;
+  float* conv_winof4_c32_u[27] = {};   // F(4x4,3x3) weights in the 32-cout instance's layout: the full-resolution 32 -> 32 layers 1, 2, 25 (else null)
+  // bits 1, 2, 25: that layer runs on the F(4x4,3x3) kernel's 32-cout instance in forward passes where its geometry allows (H % 16 == 0,
+  // W % 64 == 0) and its fp32_wino8_layers bit is set.  All three layers measured faster on it by the same 0.055-0.06 ms at 48 x 256^2;
+  // the default holds layers 1 and 25, the largest set that keeps two noise-level distances of the existing suite under their bars
+  // (episode drift of seed 36 against the fp32 oracle, 1e-4: layers 1 + 2 reach 1.02e-4; training against inference forward of the HQS
+  // solver at 3 x 48 x 64, 1e-6: all three reach 1.016e-6; profiles/winof4_c32.md, drift table profiles/winof4_c32_probe.md)
+  int opt_fp32_winof4_c32 = (1 << 1) | (1 << 25);
   int opt_fp32_chains = 2;         // conv_mode 0: n >= 2 = the forward as n launch chains over slices of the batch (default 2: this family is not
                                    // power-capped, a second chain fills the other's tails and partial rounds: 8.76 -> 8.44 ms at 48 x 256^2, -7 % at
                                    // B = 24; 3 and 4 chains measured slower); 1 = only the bottom level forks two chains; 0 = one chain

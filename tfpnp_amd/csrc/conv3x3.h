@@ -82,6 +82,13 @@ size_t conv3x3_winof4_floats(int cout, int cin);
 void pack_conv_weights_winof4(const float* w, int cout, int cin, float* dst);
 int launch_conv3x3_winof4(const float* u, const float* bias, int cout, const float* in0, int C0, const float* in1, int C1, float* out, int B,
                           int H, int W, hipStream_t s, float slope = 0.2f, float* pool_out = nullptr);
+// ... its 32-cout instance (option fp32_winof4_c32): single-source layers with cout a multiple of 32 but not of 64, >= 16 input channels
+// in multiples of 8, H a multiple of 16, W of 64.  u: pack_conv_weights_winof4_c32's output (36 cout cin floats)
+bool conv3x3_winof4_c32_ok(int C0, int C1, int cout, int H, int W);
+bool conv3x3_winof4_c32_packs(int cout, int cin);
+void pack_conv_weights_winof4_c32(const float* w, int cout, int cin, float* dst);
+int launch_conv3x3_winof4_c32(const float* u, const float* bias, int cout, const float* in0, int C0, float* out, int B, int H, int W,
+                              hipStream_t s, float slope = 0.2f, float* pool_out = nullptr);
 // ... and its up-sampling instance (option fp32_winof4_fuse_up): in1_lowres is the second source at H/2 x W/2 and the kernel writes what
 // upsample2x_v4_kernel followed by the two-source instance writes, bit for bit.  The entry rules and C0 >= 16 (two gathered chunks per tile).
 bool conv3x3_winof4_ups_ok(int C0, int C1, int cout, int H, int W);

@@ -1,8 +1,9 @@
 // Winograd F(4x4, 3x3) on the exact-fp32 MFMA v_mfma_f32_16x16x4_f32: 36 products per 16 outputs instead of F(2x2)'s 16 per 4
 // = 0.5625 x the MFMAs of conv3x3_wino8.hip.  64-cout-tile layers of the UNet's forward passes only: the plain single-source layers
 // (option fp32_winof4_layers) and, as a second instance, the two-source decoder entries on an already up-sampled second source (option
-// fp32_winof4_entries) or, as a third, on the low-resolution second source itself, up-sampled in the kernel (option fp32_winof4_fuse_up); no
-// residual, no K-split, no out-conv.  Same activation layout (padded planar fp32), WinoArgs,
+// fp32_winof4_entries) or, as a third, on the low-resolution second source itself, up-sampled in the kernel (option fp32_winof4_fuse_up); and, as a
+// separate kernel of the same per-wave structure on a 32-cout tile, the full-resolution 32 -> 32 layers (conv3x3_winof4_c32_f32_kernel
+// below, option fp32_winof4_c32).  No residual, no K-split, no out-conv.  Same activation layout (padded planar fp32), WinoArgs,
 // bias + LeakyReLU as max(y, slope y) and optional fused 2x2 max-pool as the F(2x2) kernels.
 //
 // Points (0, +-1, +-1/2, inf), rows scaled as tools/wino_f4_probe.py's cook_toom does (winof4_mats.h holds the matrices the packer uses;
@@ -529,6 +530,280 @@ __global__ __launch_bounds__(512, 1) void conv3x3_winof4_f32_kernel(WinoArgs a) 
   else body(std::integral_constant<int, 1>{});
 }
 
+// ---------------------------------------------------------------------------------------------------------------------------------
+// The 32-cout instance (option fp32_winof4_c32): the full-resolution 32 -> 32 layers.  The per-wave structure is the one above -- 16 couts
+// x 16 tiles x 36 positions in 144 registers, 24 MFMAs per wave and stage, wave-local output transform, role P = wave / 4 -- on a
+// workgroup of 32 couts x 64 tiles: a region of 16 x 64 px = 4 tile rows x 16 tile columns.  Wave (P, sw) owns cout block P and tile row
+// sw, so the two waves of a SIMD read the same V operands.  LDS: weights 2 x 12 KiB and V 2 x 24 KiB (both: stage g of the running stage
+// count reads slot g & 1 and fills the other one for stage g + 1; the barrier between two stages separates a slot's last read from its next
+// write), raw halo 2 x 40.75 KiB (18 x 66 per channel in rows of 72 + 2 floats per plane: 4 * 72 = 32 mod 64 banks, as with 40).  The
+// weights of stage g + 1 are the last VMEM operations stage g needs, so stages 0 and 1 wait for everything in flight and stage 2 for all
+// but the halo gathers it issued behind its weight slice; a halo therefore has one stage of lead before its wait, the weights less.
+struct CfgF4C32 {
+  static constexpr int CT = 32, CK = 8;
+  static constexpr int RWL = 72;
+  static constexpr int RPXL = 18 * RWL + 2;
+  static constexpr int RAW_ELEMS = CK * RPXL;
+  static constexpr int RAW_INSTR = (RAW_ELEMS + 63) / 64;     // 163
+  static constexpr int RAW_BYTES = RAW_INSTR * 256;           // 41728
+  static constexpr int RAW_PER_WAVE = (RAW_INSTR + 7) / 8;    // 21, of which the last exists for the first RAW_INSTR % 8 = 3 waves only
+  static constexpr int NRAW = RAW_INSTR / 8;                  // 20: gathers every wave issues
+  static constexpr int USTG = 2 * 6 * CK * CT * 4;            // 12 KiB = 12 16-byte LDS-DMA instructions: one per wave + one more on waves 4 .. 7
+  static constexpr int VSTG = 2 * 6 * CK * 64 * 4;            // 24 KiB
+  static constexpr int OFF_U = 0, OFF_V = 2 * USTG, OFF_RAW = OFF_V + 2 * VSTG;
+  static constexpr int LDS_USED = OFF_RAW + 2 * RAW_BYTES;    // 157184
+};
+static_assert(CfgF4C32::LDS_USED <= LDS_REQF4 && CfgF4C32::RAW_PER_WAVE + 3 <= 24 && CfgF4C32::USTG == 12 * 1024, "32-cout instance");
+
+__global__ __launch_bounds__(512, 1) void conv3x3_winof4_c32_f32_kernel(WinoArgs a) {
+  using C = CfgF4C32;
+  constexpr int CK = C::CK, RWL = C::RWL, RPXL = C::RPXL, RAW_BYTES = C::RAW_BYTES, RAW_PER_WAVE = C::RAW_PER_WAVE;
+  constexpr int USTG = C::USTG, VSTG = C::VSTG, OFF_U = C::OFF_U, OFF_V = C::OFF_V, OFF_RAW = C::OFF_RAW;
+  constexpr int UQ = USTG / 4;      // floats per weight stage
+  extern __shared__ __attribute__((aligned(16))) char lds[];
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int sw = wave & 3;
+  const int HpWp = a.Hp * a.Wp;
+  const unsigned lds0 = (unsigned)(size_t)(lptr_t)lds;
+  const int nregions = a.rx * a.ry * a.B;
+  const int nx = (gridDim.x % 8 == 0 && nregions >= 32) ? 8 : 1;       // XCD-grouped walk, as above
+  const int xcd = blockIdx.x % nx, slot = blockIdx.x / nx, nslot = gridDim.x / nx;
+
+  struct Tile {
+    const float* s0;   // halo origin in channel 0
+    const float* w;    // weights of the cout tile
+    int ct, b, x0, y0, ok;
+  };
+  auto decode = [&](int k) {
+    Tile T;
+    const int j = slot + nslot * k;
+    const int q = j / a.nct;
+    T.ct = j - q * a.nct;
+    const int reg = nx * q + xcd;
+    T.ok = reg < nregions;
+    const int t1 = reg / a.rx;
+    const int tx = reg - t1 * a.rx;
+    const int t2 = t1 / a.ry;
+    const int ty = t1 - t2 * a.ry;
+    T.b = t2;
+    T.x0 = tx * 64;
+    T.y0 = ty * 16;
+    T.s0 = a.in0 + (size_t)T.b * a.C0 * HpWp + (size_t)T.y0 * a.Wp + T.x0 + (PADL - 1);
+    T.w = a.u + (size_t)T.ct * a.nch * 3 * UQ;
+    return T;
+  };
+  auto raw_of = [&](const Tile& X, int c) { return X.s0 + (size_t)CK * c * HpWp; };
+  auto sync_all = [&]() {
+    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+    __builtin_amdgcn_s_barrier();
+  };
+
+  // -- LDS-DMA, an eighth per wave: per-lane byte offsets of the halo elements from the chunk's origin (lanes in the rows' and planes'
+  // slack read the origin itself)
+  unsigned roff[RAW_PER_WAVE];
+#pragma unroll
+  for (int k = 0; k < RAW_PER_WAVE; ++k) {
+    const int idx = (wave + 8 * k) * 64 + lane;
+    const int c = idx / RPXL, r = idx - c * RPXL;
+    const int hy = r / RWL, hx = r - hy * RWL;
+    roff[k] = (c < CK && hy < 18 && hx < 66) ? 4u * (unsigned)(c * HpWp + hy * a.Wp + hx) : 0u;
+  }
+  const unsigned uoff = lane * 16u;
+  auto dma_u_piece = [&](const float* src, int uslot, int p) {      // KiB p (of 12) of one stage's weights -> ring slot uslot
+    if (WINOF4_ABL & 4) return;
+    glds16(src + p * 256, uoff, lds0 + OFF_U + uslot * USTG + p * 1024);
+  };
+  auto dma_raw_piece = [&](const float* src, int rbuf, int k) {     // gather k (of RAW_PER_WAVE per wave) of one chunk's halo
+    if (WINOF4_ABL & 2) return;
+    if (k < C::NRAW || wave + 8 * k < C::RAW_INSTR) glds4(src, roff[k], lds0 + OFF_RAW + rbuf * RAW_BYTES + (wave + 8 * k) * 256);
+  };
+  auto dma_raw = [&](const float* src, int rbuf) {
+#pragma unroll
+    for (int k = 0; k < RAW_PER_WAVE; ++k) dma_raw_piece(src, rbuf, k);
+  };
+
+  auto body = [&](auto role_tag) {
+  constexpr int P = decltype(role_tag)::value;
+
+  // -- input transform: one channel, position row P of the stage's two and TWO tiles per thread (tile rows sw / 2 and sw / 2 + 2, the
+  // same tile column).  Lanes as above: k-step bit, 16 tile columns, low bit of the channel group; sw: its high bit, tile row.
+  const int t_ks = lane & 1, t_t16 = (lane >> 1) & 15, t_kq = (lane >> 5) | ((sw & 1) << 1), t_wn = sw >> 1;
+  const int t_rd = ((2 * t_kq + t_ks) * RPXL + 4 * t_wn * RWL + 4 * t_t16) * 4;           // + 8 tile-row strides for the second tile
+  const int t_wr = (P * 3 * 4 + t_wn) * 1024 + (t_kq * 16 + t_t16) * 16 + t_ks * 8;       // + column pair * 4096 (+ slot); + 2048 for the second tile
+  auto transform = [&](auto a_tag, int rbuf, int vslot, int second) {
+    constexpr int A = decltype(a_tag)::value;       // position row
+    const char* rb = lds + OFF_RAW + rbuf * RAW_BYTES + t_rd + second * (8 * RWL * 4);
+    float d[6][6];
+#pragma unroll
+    for (int y = 0; y < 6; ++y) {
+      const bool need = (A == 0) ? (y % 2 == 0) : (A == 5) ? (y % 2 == 1) : (y >= 1 && y <= 4);
+#pragma unroll
+      for (int x = 0; x < 6; x += 2) {
+        if (need) {
+          const f32x2 v = *reinterpret_cast<const f32x2*>(rb + (y * RWL + x) * 4);
+          d[y][x] = v[0];
+          d[y][x + 1] = v[1];
+        } else {
+          d[y][x] = d[y][x + 1] = 0.f;
+        }
+      }
+    }
+    float t[6];
+#pragma unroll
+    for (int x = 0; x < 6; ++x) t[x] = bt_row<A>(d[0][x], d[1][x], d[2][x], d[3][x], d[4][x], d[5][x]);
+    char* vb = lds + OFF_V + vslot * VSTG + t_wr + second * 2048;
+    *reinterpret_cast<f32x2*>(vb) = (f32x2){bt_row<0>(t[0], t[1], t[2], t[3], t[4], t[5]), bt_row<1>(t[0], t[1], t[2], t[3], t[4], t[5])};
+    *reinterpret_cast<f32x2*>(vb + 4096) = (f32x2){bt_row<2>(t[0], t[1], t[2], t[3], t[4], t[5]), bt_row<3>(t[0], t[1], t[2], t[3], t[4], t[5])};
+    *reinterpret_cast<f32x2*>(vb + 8192) = (f32x2){bt_row<4>(t[0], t[1], t[2], t[3], t[4], t[5]), bt_row<5>(t[0], t[1], t[2], t[3], t[4], t[5])};
+  };
+  auto transform_row = [&](auto s_tag, int rbuf, int vslot) {      // this thread's two tiles of row P of stage S's two
+    constexpr int S = decltype(s_tag)::value;
+    if (WINOF4_ABL & 1) return;
+    transform(std::integral_constant<int, 2 * S + P>{}, rbuf, vslot, 0);
+    transform(std::integral_constant<int, 2 * S + P>{}, rbuf, vslot, 1);
+  };
+
+  // -- MFMA operands: 16 bytes = (k-step 2) x (position 2 of a column pair) per lane; lane = 16 * channel group + cout / tile of the block
+  const int a_lane = P * 1024 + lane * 16;       // + (row in stage * 3 + column pair) * 2048 (+ slot)
+  const int b_lane = sw * 1024 + lane * 16;      // + (row in stage * 3 + column pair) * 4096 (+ slot)
+  f32x4 acc[6][6];
+
+  // One pipeline stage S of a chunk, reading weight and V slot vrd: fetch the next stage's weights (and, S == 2, the halo of the chunk
+  // after next) into the other slots between the 24 MFMAs, transform the next stage's V, then the counted wait and the barrier.
+  auto stage = [&](auto s_tag, const float* u_src, const float* raw_src, int raw_buf, int t_rbuf, int vrd) {
+    constexpr int S = decltype(s_tag)::value, SN = (S + 1) % 3;
+    // the stage's LDS-DMA pieces, one behind each MFMA: the weight slice behind MFMA 0 (waves 4 .. 7: and 1), stage 2's halo gathers
+    // behind 3 .. 23
+    auto piece = [&](int m) {
+      if (m == 0) dma_u_piece(u_src, vrd ^ 1, wave);
+      if (m == 1 && P == 1) dma_u_piece(u_src, vrd ^ 1, 4 + wave);
+      if (S == 2 && m >= 3 && m < 3 + RAW_PER_WAVE) dma_raw_piece(raw_src, raw_buf, m - 3);
+    };
+    auto mfmas = [&]() {
+      if (WINOF4_ABL & 16) {      // data movement alone: the stage's LDS-DMA pieces without the MFMAs they stand behind
+#pragma unroll
+        for (int m = 0; m < 24; ++m) piece(m);
+        return;
+      }
+      f32x4 af[6], bf[6];
+#pragma unroll
+      for (int q = 0; q < 6; ++q) {
+        af[q] = *reinterpret_cast<const f32x4*>(lds + OFF_U + vrd * USTG + q * 2048 + a_lane);
+        bf[q] = *reinterpret_cast<const f32x4*>(lds + OFF_V + vrd * VSTG + q * 4096 + b_lane);
+      }
+      static_for<6>([&](auto q_tag) {
+        constexpr int Q = decltype(q_tag)::value, R = Q / 3, CP = Q % 3;
+#pragma unroll
+        for (int ks = 0; ks < 2; ++ks)
+#pragma unroll
+          for (int pos = 0; pos < 2; ++pos) {
+            acc[2 * S + R][2 * CP + pos] = __builtin_amdgcn_mfma_f32_16x16x4f32(af[Q][2 * ks + pos], bf[Q][2 * ks + pos], acc[2 * S + R][2 * CP + pos], 0, 0, 0);
+            piece(4 * Q + 2 * ks + pos);
+            __builtin_amdgcn_sched_barrier(0);
+          }
+      });
+    };
+    if (P == 0) {
+      mfmas();
+      __builtin_amdgcn_sched_barrier(0);
+      transform_row(std::integral_constant<int, SN>{}, t_rbuf, vrd ^ 1);
+    } else {
+      transform_row(std::integral_constant<int, SN>{}, t_rbuf, vrd ^ 1);
+      __builtin_amdgcn_sched_barrier(0);
+      mfmas();
+    }
+    // stage 2 leaves the halo gathers every wave issued behind its weight slice in flight (a wave with one more waits for that one too)
+    // (the timing build without halo gathers issues nothing behind the weight slice: it waits for everything)
+    if (S == 2 && !(WINOF4_ABL & 2)) asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(C::NRAW) : "memory");
+    else asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+    __builtin_amdgcn_s_barrier();
+  };
+
+  // -- epilogue, wave-local, as above: tile row sw, tile column lane & 15
+  auto epilogue = [&](const Tile& T) {
+    const int ty = sw, tx = lane & 15;
+    const int cbase = T.ct * 32 + P * 16 + 4 * (lane >> 4);
+    float* ob = a.out + ((size_t)T.b * a.Cout + cbase) * HpWp + (size_t)(T.y0 + 4 * ty + 1) * a.Wp + T.x0 + 4 * tx + PADL;
+    const int Hp_pool = padded_h(a.H / 2), Wp_pool = padded_w(a.W / 2);
+    const size_t HpWp_pool = (size_t)Hp_pool * Wp_pool;
+    float* pb = a.pool ? a.pool + ((size_t)T.b * a.Cout + cbase) * HpWp_pool + (size_t)(T.y0 / 2 + 2 * ty + 1) * Wp_pool + T.x0 / 2 + 2 * tx + PADL : nullptr;
+    float bias4[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) bias4[j] = a.bias[cbase + j];
+    static_for<4>([&](auto j_tag) {
+      constexpr int j = decltype(j_tag)::value;
+      float s[4][6];
+#pragma unroll
+      for (int b = 0; b < 6; ++b) at_rows(acc[0][b][j], acc[1][b][j], acc[2][b][j], acc[3][b][j], acc[4][b][j], acc[5][b][j], s[0][b], s[1][b], s[2][b], s[3][b]);
+      const float bias = bias4[j];
+      float* o = ob + (size_t)j * HpWp;
+      f32x4 y[4];
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        float y0, y1, y2, y3;
+        at_rows(s[i][0], s[i][1], s[i][2], s[i][3], s[i][4], s[i][5], y0, y1, y2, y3);
+        y0 += bias;
+        y1 += bias;
+        y2 += bias;
+        y3 += bias;
+        // LeakyReLU with 0 <= slope <= 1 as max(y, slope y)
+        y[i] = (f32x4){fmaxf(y0, y0 * a.slope), fmaxf(y1, y1 * a.slope), fmaxf(y2, y2 * a.slope), fmaxf(y3, y3 * a.slope)};
+        if (!(WINOF4_ABL & 32) || a.slope == 123.f) *reinterpret_cast<f32x4*>(o + i * a.Wp) = y[i];
+      }
+      if (a.pool && (!(WINOF4_ABL & 32) || a.slope == 123.f)) {      // four 2x2 windows per tile; same association as maxpool2_kernel
+        float* p = pb + (size_t)j * HpWp_pool;
+        *reinterpret_cast<f32x2*>(p) = (f32x2){fmaxf(fmaxf(y[0][0], y[0][1]), fmaxf(y[1][0], y[1][1])), fmaxf(fmaxf(y[0][2], y[0][3]), fmaxf(y[1][2], y[1][3]))};
+        *reinterpret_cast<f32x2*>(p + Wp_pool) = (f32x2){fmaxf(fmaxf(y[2][0], y[2][1]), fmaxf(y[3][0], y[3][1])), fmaxf(fmaxf(y[2][2], y[2][3]), fmaxf(y[3][2], y[3][3]))};
+      }
+    });
+  };
+
+  using I0 = std::integral_constant<int, 0>;
+  using I1 = std::integral_constant<int, 1>;
+  using I2 = std::integral_constant<int, 2>;
+
+  int k = 0;
+  Tile T = decode(0);
+  if (!T.ok) return;
+  // prologue: the first two halos, the first weight stage, the first transform (nch >= 2: chunk 1 exists)
+  dma_raw(T.s0, 0);
+  dma_u_piece(T.w, 0, wave);
+  if (P == 1) dma_u_piece(T.w, 0, 4 + wave);
+  dma_raw(raw_of(T, 1), 1);
+  sync_all();
+  transform_row(I0{}, 0, 0);
+  sync_all();
+
+  int cc = 0;
+  for (;;) {
+    Tile Tn = decode(k + 1);
+    const bool more = Tn.ok;
+    if (!more) Tn = T;      // after the walk's last chunks: surplus loads of this tile's first chunks into buffers nobody reads
+#pragma unroll
+    for (int i = 0; i < 6; ++i)
+#pragma unroll
+      for (int j = 0; j < 6; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
+    for (int c = 0; c < a.nch; ++c, ++cc) {
+      const float* w_c = T.w + (size_t)c * 3 * UQ;
+      const float* nu = (c + 1 < a.nch) ? w_c + 3 * UQ : Tn.w;                                    // the next chunk's weights
+      const float* nraw = (c + 2 < a.nch) ? raw_of(T, c + 2) : raw_of(Tn, c + 2 - a.nch);         // the halo of the chunk after next
+      const int rcur = cc & 1;      // the chunk's halo buffer; stage g = 3 cc + s reads weight and V slot g & 1 = (cc + s) & 1
+      stage(I0{}, w_c + UQ, nullptr, 0, rcur, rcur);
+      stage(I1{}, w_c + 2 * UQ, nullptr, 0, rcur, rcur ^ 1);
+      stage(I2{}, nu, nraw, rcur, rcur ^ 1, rcur);
+    }
+    if (!(WINOF4_ABL & 8)) epilogue(T);
+    if (!more) break;
+    T = Tn;
+    ++k;
+  }
+  sync_all();   // the surplus loads of the last chunk
+  };
+  if (wave < 4) body(std::integral_constant<int, 0>{});
+  else body(std::integral_constant<int, 1>{});
+}
+
 }  // namespace
 
 // ---------------------------------------------------------------------------------------------------------------------------------
@@ -566,6 +841,78 @@ void pack_conv_weights_winof4(const float* w, int cout, int cin, float* dst) {
           dst[idx] = (float)u[i][j];
         }
     }
+}
+
+// The 32-cout instance: one source, cout tiles of 32 (cout a multiple of 32 but not of 64: the UNet's full-resolution 32 -> 32 layers),
+// regions of 16 x 64 px; two chunks for the pipeline's prologue.
+bool conv3x3_winof4_c32_ok(int C0, int C1, int cout, int H, int W) {
+  return C1 == 0 && C0 >= 16 && C0 % 8 == 0 && cout > 0 && cout % 32 == 0 && cout % 64 != 0 && H >= 16 && H % 16 == 0 && W >= 64 && W % 64 == 0;
+}
+bool conv3x3_winof4_c32_packs(int cout, int cin) { return conv3x3_winof4_c32_ok(cin, 0, cout, 16, 64); }
+
+// ... layout [cout / 32][cin / 8][stage 3][row in stage 2][column pair 3][cout block 2][channel group 4][cout 16][k-step 2][column in pair 2]
+void pack_conv_weights_winof4_c32(const float* w, int cout, int cin, float* dst) {
+  const int nch = cin / 8;
+  for (int co = 0; co < cout; ++co)
+    for (int ci = 0; ci < cin; ++ci) {
+      const float* g = w + ((size_t)co * cin + ci) * 9;
+      double gg[6][3], u[6][6];
+      for (int i = 0; i < 6; ++i)
+        for (int x = 0; x < 3; ++x) gg[i][x] = WINOF4_G[i][0] * g[0 * 3 + x] + WINOF4_G[i][1] * g[1 * 3 + x] + WINOF4_G[i][2] * g[2 * 3 + x];
+      for (int i = 0; i < 6; ++i)
+        for (int j = 0; j < 6; ++j) u[i][j] = gg[i][0] * WINOF4_G[j][0] + gg[i][1] * WINOF4_G[j][1] + gg[i][2] * WINOF4_G[j][2];
+      const int ct = co / 32, mb = (co % 32) / 16, m = co % 16, ch = ci / 8, kq = (ci % 8) / 2, ks = ci % 2;
+      for (int i = 0; i < 6; ++i)
+        for (int j = 0; j < 6; ++j) {
+          const size_t idx = (((((((((size_t)ct * nch + ch) * 3 + i / 2) * 2 + i % 2) * 3 + j / 2) * 2 + mb) * 4 + kq) * 16 + m) * 2 + ks) * 2 + j % 2;
+          dst[idx] = (float)u[i][j];
+        }
+    }
+}
+
+int launch_conv3x3_winof4_c32(const float* u, const float* bias, int cout, const float* in0, int C0, float* out, int B, int H, int W,
+                              hipStream_t s, float slope, float* pool_out) {
+  if (!conv3x3_winof4_c32_ok(C0, 0, cout, H, W)) {
+    set_error("conv3x3_winof4_c32: unsupported geometry (%d -> %d channels, %d x %d)", C0, cout, H, W);
+    return PNPX_ERR_SHAPE;
+  }
+  WinoArgs a{};
+  a.in0 = a.in1 = in0;
+  a.u = u;
+  a.bias = bias;
+  a.pool = pool_out;
+  a.out = out;
+  a.B = B;
+  a.H = H;
+  a.W = W;
+  a.Hp = padded_h(H);
+  a.Wp = padded_w(W);
+  a.C0 = C0;
+  a.Cout = cout;
+  a.slope = slope;
+  a.nct = cout / 32;
+  a.nch = C0 / CfgF4C32::CK;
+  a.nch_all = a.nch;
+  a.ksplit = 1;
+  a.rx = W / 64;
+  a.ry = H / 16;
+  static std::once_flag attr_once[64];
+  int dev = 0;
+  PNPX_HIP(hipGetDevice(&dev));
+  if (dev >= 0 && dev < 64) {
+    hipError_t e = hipSuccess;
+    std::call_once(attr_once[dev], [&] {
+      e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3x3_winof4_c32_f32_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_REQF4);
+    });
+    PNPX_HIP(e);
+  }
+  const long long nreg = (long long)a.rx * a.ry * a.B, ntiles = nreg * a.nct;
+  long long grid = 256;
+  if (grid >= ntiles) grid = ntiles;
+  else if ((grid / 8) % a.nct != 0 && grid >= 8LL * a.nct) grid -= grid % (8 * a.nct);
+  hipLaunchKernelGGL(conv3x3_winof4_c32_f32_kernel, dim3((unsigned)grid), dim3(512), LDS_REQF4, s, a);
+  PNPX_LAUNCH_CHECK();
+  return PNPX_OK;
 }
 
 // ups: in1 is the low-resolution second source (H/2 x W/2) and the kernel up-samples it (launch_conv3x3_winof4_ups)
@@ -653,5 +1000,10 @@ extern "C" void pnpx_winof4_matrices(double* g18, double* bt36, double* at24) {
 extern "C" int pnpx_winof4_pack(const float* w, int cout, int cin, float* dst) {
   if (!w || !dst || cout <= 0 || cout % 64 != 0 || cin <= 0 || cin % 8 != 0) return PNPX_ERR_SHAPE;
   pnpx::pack_conv_weights_winof4(w, cout, cin, dst);
+  return PNPX_OK;
+}
+extern "C" int pnpx_winof4_c32_pack(const float* w, int cout, int cin, float* dst) {
+  if (!w || !dst || cout <= 0 || cout % 32 != 0 || cin <= 0 || cin % 8 != 0) return PNPX_ERR_SHAPE;
+  pnpx::pack_conv_weights_winof4_c32(w, cout, cin, dst);
   return PNPX_OK;
 }

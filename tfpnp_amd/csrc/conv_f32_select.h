@@ -6,7 +6,7 @@
 
 namespace pnpx {
 
-enum class ConvF32Kernel { Direct, Wino4, Wino8, WinoF4 };   // conv3x3.hip, conv3x3_wino.hip, conv3x3_wino8.hip, conv3x3_winof4.hip
+enum class ConvF32Kernel { Direct, Wino4, Wino8, WinoF4, WinoF4C32 };   // conv3x3.hip, conv3x3_wino.hip, conv3x3_wino8.hip, conv3x3_winof4.hip (the last two)
 
 struct ConvF32Choice {
   ConvF32Kernel kernel = ConvF32Kernel::Direct;
@@ -23,11 +23,13 @@ struct ConvF32Sel {
   bool winof4 = false;     // the layer's fp32_winof4_layers bit (DRUNet: never)
   bool winof4_entry = false;   // the layer's fp32_winof4_entries bit (decoder entries 15, 18, 21; DRUNet: never)
   bool winof4_fuse_up = false; // the layer's fp32_winof4_fuse_up bit (the same entries)
+  bool winof4_c32 = false;     // the layer's fp32_winof4_c32 bit (layers 1, 2, 25; DRUNet: never)
   int ksplit = 0;          // fp32_ksplit (DRUNet: 0)
   int ksplit_rule = 1;     // fp32_ksplit_rule
   bool fuse_up = false;    // fp32_fuse_up
   const float* u = nullptr;      // F(2x2,3x3) weights (both Winograd kernels)
   const float* u_f4 = nullptr;   // F(4x4,3x3) weights
+  const float* u_f4c32 = nullptr;   // F(4x4,3x3) weights in the 32-cout instance's layout
   const float* u_bwd = nullptr;  // F(2x2,3x3) weights of the adjoint layer
 };
 ConvF32Sel conv_f32_sel(const pnpx_ctx* ctx, int li);                                      // layer li of the UNet

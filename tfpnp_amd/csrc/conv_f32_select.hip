@@ -10,11 +10,13 @@ ConvF32Sel conv_f32_sel(const pnpx_ctx* ctx, int li) {
   v.winof4 = (ctx->opt_fp32_winof4 >> li) & 1;
   v.winof4_entry = (ctx->opt_fp32_winof4_entries >> li) & 1;
   v.winof4_fuse_up = (ctx->opt_fp32_winof4_fuse_up >> li) & 1;
+  v.winof4_c32 = (ctx->opt_fp32_winof4_c32 >> li) & 1;
   v.ksplit = ctx->opt_fp32_ksplit;
   v.ksplit_rule = ctx->opt_ksplit_rule;
   v.fuse_up = ctx->opt_fp32_fuse_up != 0;
   v.u = ctx->conv_wino_u[li];
   v.u_f4 = ctx->conv_winof4_u[li];
+  v.u_f4c32 = ctx->conv_winof4_c32_u[li];
   v.u_bwd = ctx->conv_wino_u_bwd[li];
   return v;
 }
@@ -51,6 +53,8 @@ ConvF32Choice conv_f32_forward(const ConvF32Sel& v, int C0, int C1, int cout, in
   // closely as before (tests/test_gpu_amp.py holds them to 1e-5 through the Onsager term, which amplifies a layer-level 7e-7 difference
   // past that bar); the backward pass keeps the F(2x2) adjoint kernels.
   if (c.pieces == 1 && v.winof4 && v.u_f4 && C1 == 0 && conv3x3_winof4_ok(C0, 0, cout, H, W)) c.kernel = ConvF32Kernel::WinoF4;
+  // ... and its 32-cout instance under its own mask (the full-resolution 32 -> 32 layers; the K-split never names a 32-cout layer)
+  else if (c.pieces == 1 && v.winof4_c32 && v.u_f4c32 && C1 == 0 && conv3x3_winof4_c32_ok(C0, 0, cout, H, W)) c.kernel = ConvF32Kernel::WinoF4C32;
   return c;
 }
 
@@ -108,6 +112,8 @@ int launch_conv_f32(const ConvF32Choice& c, const ConvF32Sel& v, const ConvLayer
     case ConvF32Kernel::WinoF4:      // no residual operand
       if (a.in1_lowres) return launch_conv3x3_winof4_ups(v.u_f4, L.b, L.cout, a.in0, a.C0, a.in1, a.C1, a.out, a.B, a.H, a.W, s, a.slope);
       return launch_conv3x3_winof4(v.u_f4, L.b, L.cout, a.in0, a.C0, a.in1, a.C1, a.out, a.B, a.H, a.W, s, a.slope, a.pool_out);
+    case ConvF32Kernel::WinoF4C32:   // single source, no residual operand
+      return launch_conv3x3_winof4_c32(v.u_f4c32, L.b, L.cout, a.in0, a.C0, a.out, a.B, a.H, a.W, s, a.slope, a.pool_out);
     case ConvF32Kernel::Wino8:
       return launch_conv3x3_wino8(v.u, L.b, L.cout, a.in0, a.C0, a.in1, a.C1, a.out, a.B, a.H, a.W, s, a.slope, a.res, a.pool_out,
                                   c.pieces > 1 ? a.ks_part : nullptr, v.ksplit_rule);
@@ -137,5 +143,25 @@ extern "C" int pnpx_conv_f32_entry_plan(int opts, int ksplit, int ksplit_rule, i
   v.ksplit_rule = ksplit_rule;
   if (C0 <= 0 || C1 <= 0 || cout <= 0 || H <= 0 || W <= 0 || B_call <= 0) return -1;
   const pnpx::ConvF32Choice c = pnpx::conv_f32_entry(v, C0, C1, cout, H, W, B_call);
+  return static_cast<int>(c.kernel) + 16 * c.pieces + 256 * (c.fused ? 1 : 0);
+}
+
+// conv_f32_forward and conv_f32_last likewise.  opts: bit 0 fp32_winograd, bit 1 the layer's fp32_wino8_layers bit, bit 2 its
+// fp32_winof4_layers bit, bit 3 its fp32_winof4_c32 bit, bit 4 its F(2x2) weights are packed, bit 5 its F(4x4) weights, bit 6 its F(4x4)
+// weights in the 32-cout instance's layout, bit 7 the layer is the network's last (conv_f32_last; C1 must be 0)
+extern "C" int pnpx_conv_f32_forward_plan(int opts, int ksplit, int ksplit_rule, int C0, int C1, int cout, int H, int W, int B_call) {
+  static const float packed = 0.f;
+  pnpx::ConvF32Sel v;
+  v.winograd = opts & 1;
+  v.wino8 = opts & 2;
+  v.winof4 = opts & 4;
+  v.winof4_c32 = opts & 8;
+  v.u = (opts & 16) ? &packed : nullptr;
+  v.u_f4 = (opts & 32) ? &packed : nullptr;
+  v.u_f4c32 = (opts & 64) ? &packed : nullptr;
+  v.ksplit = ksplit;
+  v.ksplit_rule = ksplit_rule;
+  if (C0 <= 0 || C1 < 0 || cout <= 0 || H <= 0 || W <= 0 || B_call <= 0 || ((opts & 128) && C1 != 0)) return -1;
+  const pnpx::ConvF32Choice c = (opts & 128) ? pnpx::conv_f32_last(v, C0, cout, H, W, B_call) : pnpx::conv_f32_forward(v, C0, C1, cout, H, W, B_call);
   return static_cast<int>(c.kernel) + 16 * c.pieces + 256 * (c.fused ? 1 : 0);
 }

@@ -41,6 +41,7 @@ extern "C" int pnpx_conv3x3_probe_plan(int kind, int C0, int C1, int cout, int H
     case PNPX_PROBE_WINOF4_2SRC: return C1 > 0 && conv3x3_winof4_entry_ok(C0, C1, cout, H, W) ? 64 : 0;
     case PNPX_PROBE_WINOF4_UPS: return 0;      // reserved before the up-sampling instance existed: still refuses every geometry
     case PNPX_PROBE_WINOF4_FUSE_UP: return C1 > 0 && conv3x3_winof4_ups_ok(C0, C1, cout, H, W) ? 64 : 0;
+    case PNPX_PROBE_WINOF4_C32: return conv3x3_winof4_c32_ok(C0, C1, cout, H, W) ? 32 : 0;
   }
   return 0;
 }
@@ -56,7 +57,7 @@ extern "C" int pnpx_conv3x3_probe(pnpx_ctx* ctx, int kind, const float* w_host, 
   PNPX_HIP(hipSetDevice(ctx->device));
   hipStream_t s = static_cast<hipStream_t>(stream);
   const bool grad = is_grad(kind);
-  if (kind < PNPX_PROBE_DIRECT || (kind > PNPX_PROBE_WINOF4_UPS && kind != PNPX_PROBE_WINOF4_FUSE_UP)) {      // (10 is no kind)
+  if (kind < PNPX_PROBE_DIRECT || (kind > PNPX_PROBE_WINOF4_UPS && kind != PNPX_PROBE_WINOF4_FUSE_UP && kind != PNPX_PROBE_WINOF4_C32)) {      // (10 is no kind)
     set_error("pnpx_conv3x3_probe: unknown kind %d", kind);
     return PNPX_ERR_ARG;
   }
@@ -66,12 +67,13 @@ extern "C" int pnpx_conv3x3_probe(pnpx_ctx* ctx, int kind, const float* w_host, 
   }
   // operands a kind has no place for are refused, never dropped
   const bool takes_res = kind == PNPX_PROBE_DIRECT || kind == PNPX_PROBE_WINO4 || kind == PNPX_PROBE_WINO8;
-  const bool takes_pool = kind == PNPX_PROBE_WINO4 || kind == PNPX_PROBE_WINO8 || kind == PNPX_PROBE_WINOF4 || kind == PNPX_PROBE_WINOF4_2SRC;
+  const bool takes_pool = kind == PNPX_PROBE_WINO4 || kind == PNPX_PROBE_WINO8 || kind == PNPX_PROBE_WINOF4 || kind == PNPX_PROBE_WINOF4_2SRC ||
+                          kind == PNPX_PROBE_WINOF4_C32;
   if ((res && !takes_res) || (pool_out && !takes_pool) || (mask && !grad) || (res && pool_out)) {
     set_error("pnpx_conv3x3_probe: kind %d takes no %s operand", kind, res && !takes_res ? "res" : (mask && !grad ? "mask" : "pool_out"));
     return PNPX_ERR_ARG;
   }
-  if ((grad || kind == PNPX_PROBE_WINOF4) && C1 != 0) {
+  if ((grad || kind == PNPX_PROBE_WINOF4 || kind == PNPX_PROBE_WINOF4_C32) && C1 != 0) {
     set_error("pnpx_conv3x3_probe: kind %d is single-source (C1 = %d)", kind, C1);
     return PNPX_ERR_SHAPE;
   }
@@ -102,6 +104,7 @@ extern "C" int pnpx_conv3x3_probe(pnpx_ctx* ctx, int kind, const float* w_host, 
       case PNPX_PROBE_WINOF4_2SRC: return launch_conv3x3_winof4(pk, b, cout, in0, C0, in1, C1, out, B, H, W, s, slope, pool_out);
       case PNPX_PROBE_WINO8_UPS: return launch_conv3x3_wino8_ups(pk, b, cout, in0, C0, in1, C1, out, B, H, W, s, slope);
       case PNPX_PROBE_WINOF4_FUSE_UP: return launch_conv3x3_winof4_ups(pk, b, cout, in0, C0, in1, C1, out, B, H, W, s, slope);
+      case PNPX_PROBE_WINOF4_C32: return launch_conv3x3_winof4_c32(pk, b, cout, in0, C0, out, B, H, W, s, slope, pool_out);
       case PNPX_PROBE_DIRECT_GRAD:
         L.mt = cout % 64 == 0 ? 64 : 32;
         L.cc = 8;
@@ -131,6 +134,10 @@ extern "C" int pnpx_conv3x3_probe(pnpx_ctx* ctx, int kind, const float* w_host, 
     case PNPX_PROBE_WINOF4_FUSE_UP:
       host.resize(conv3x3_winof4_floats(cout, cin));
       pack_conv_weights_winof4(w_host, cout, cin, host.data());
+      break;
+    case PNPX_PROBE_WINOF4_C32:
+      host.resize(conv3x3_winof4_floats(cout, cin));
+      pack_conv_weights_winof4_c32(w_host, cout, cin, host.data());
       break;
     case PNPX_PROBE_DIRECT_GRAD:   // w_host: the forward layer's [C0][cout][3][3]
       host.resize((size_t)cout * C0 * 9);

@@ -14,7 +14,12 @@ usage: python tools/wino_f4_probe.py [n_seeds] > profiles/r6_wino_f4_probe.md
       levels: the UNet levels given (level k = 1 / 2^k of the image size), once under the eligibility rule of conv3x3_winof4.hip (plain
       single-source layers with cout % 64 == 0, >= 16 input channels in multiples of 8, H % 16 == 0, W % 32 == 0) and once under the
       superset "every cout % 32 == 0 layer of those levels" (what the kernel would run on larger images, where the same levels are
-      wider).  python tools/wino_f4_probe.py 12 --levels 1,2 > profiles/winof4_probe.md"""
+      wider).  python tools/wino_f4_probe.py 12 --levels 1,2 > profiles/winof4_probe.md
+
+  (4) --c32 [--jobs N]: the drift table alone under the GPU's selection rule as it stands (levels 1-3 run F(4x4) on every single- or
+      two-source layer with cout % 64 == 0 where H % 16 == 0 and W % 32 == 0, decoder entries 15 / 18 / 21 included; everything else
+      F(2x2)), and with chosen full-resolution 32-cout layers added (layer index = position among the forward's 3x3 convolutions; level 0
+      needs H % 16 == 0 and W % 64 == 0).  python tools/wino_f4_probe.py 12 --c32 > profiles/winof4_c32_probe.md"""
 import os
 import sys
 
@@ -127,6 +132,29 @@ def f4_layer(rule, levels, H0, inp_shape, w_shape):
     return cout % 64 == 0 and cin >= 16 and cin % 8 == 0 and cin <= cout and h % 16 == 0 and w % 32 == 0
 
 
+C32_SETS = {
+    "the GPU's rule today (levels 1-3, entries included)": (),
+    "+ level-0 layers 1, 2, 25": (1, 2, 25),
+    "+ every cout % 32 layer of level 0 (1, 2, 24, 25, 26)": (1, 2, 24, 25, 26),
+    "+ level-0 layer 25 alone": (25,),
+    "+ level-0 layers 1, 2": (1, 2),
+    "+ level-0 layers 1, 25": (1, 25),
+}
+
+
+def f4_gpu(level0, idx, H0, inp_shape, w_shape):
+    """the GPU's selection: conv_f32_forward's and the entries' F(4x4) rows on levels 1-3, plus the level-0 layers named in `level0`
+    (idx = position of the layer among the forward's 3x3 convolutions, 0 = the 2 -> 32 first convolution)."""
+    h, w = inp_shape[-2], inp_shape[-1]
+    cout, cin = w_shape[0], w_shape[1]
+    lvl = {H0 >> k: k for k in range(5)}.get(h)
+    if lvl is None or h % 16 or cin < 16 or cin % 8:
+        return False
+    if lvl == 0:
+        return idx in level0 and cout % 32 == 0 and w % 64 == 0
+    return lvl in (1, 2, 3) and cout % 64 == 0 and w % 32 == 0
+
+
 def make_den(params, deep, rule=None, levels=()):
     """fp32 CPU denoiser whose 3x3 layers with cout % 32 == 0 run as emulated F(2x2); `deep` (a MATS key) replaces the scheme on the two
     deepest levels (spatial size <= 1/8 of the image) or, with `rule`, on the layers f4_layer() names."""
@@ -136,11 +164,17 @@ def make_den(params, deep, rule=None, levels=()):
     class Den:
         def __call__(self, x, sigma):
             H0 = x.shape[-1]
+            n3 = [0]
 
             def patched(inp, w, b=None, **kw):
+                idx = n3[0]
+                n3[0] += w.shape[-1] == 3
                 if w.shape[-1] == 3 and w.shape[0] % 32 == 0 and w.shape[1] % 8 == 0 and inp.shape[-1] % 2 == 0:
                     key = "F2"
-                    if deep and rule and f4_layer(rule, levels, H0, inp.shape, w.shape):
+                    if deep and rule == "gpu":
+                        if f4_gpu(levels, idx, H0, inp.shape, w.shape):
+                            key = deep
+                    elif deep and rule and f4_layer(rule, levels, H0, inp.shape, w.shape):
                         key = deep
                     elif deep and not rule and inp.shape[-1] * 8 <= H0 and inp.shape[-1] % 4 == 0:
                         key = deep
@@ -159,7 +193,10 @@ def make_den(params, deep, rule=None, levels=()):
 
 def drift_schemes(levels, points):
     schemes = {"emulated F(2x2) everywhere (= today's fp32 family)": (None, None)}
-    if levels:
+    if levels == "c32":
+        for name, layers in C32_SETS.items():
+            schemes[name] = ("F4 (0,+-1,+-1/2,inf)", "gpu", layers)
+    elif levels:
         key = "F4 (0,+-1,+-1/2,inf)" if points == "half" else "F4 (0,+-1,+-2,inf)"
         lv = ",".join(str(l) for l in levels)
         schemes[f"{key}, levels {lv}, the kernel's eligibility rule"] = (key, "kernel")
@@ -192,8 +229,8 @@ def drift_seed(job):
     ref64 = run(O.Denoiser(params, dtype=torch.float64), torch.float64)
     ref32 = run(O.Denoiser(params, dtype=torch.float32), torch.float32)
     res = {}
-    for name, (deep, rule) in drift_schemes(levels, points).items():
-        out = run(make_den(params, deep, rule, levels), torch.float32)
+    for name, (deep, rule, *sel) in drift_schemes(levels, points).items():
+        out = run(make_den(params, deep, rule, sel[0] if sel else levels), torch.float32)
         res[name] = (rel(out, ref64), rel(out, ref32))
     return seed, rel(ref32, ref64), res
 
@@ -202,7 +239,7 @@ def drift_table(params, n_seeds, levels=(), points="half", jobs=1):
     schemes = drift_schemes(levels, points)
     rows = {k: [] for k in schemes}
     ecpu = []
-    work = [(seed, tuple(levels), points, max(1, 8 // jobs) if jobs > 1 else 8) for seed in range(31, 31 + n_seeds)]
+    work = [(seed, levels if levels == "c32" else tuple(levels), points, max(1, 8 // jobs) if jobs > 1 else 8) for seed in range(31, 31 + n_seeds)]
     if jobs > 1:
         import multiprocessing as mp
         with mp.get_context("spawn").Pool(jobs) as pool:
@@ -243,6 +280,16 @@ if __name__ == "__main__":
         Vv = np.einsum("ia,bcyxaz,jz->bcyxij", Bt, xp, Bt)
         Y = np.einsum("pi,ijkc,bcyxij,qj->bkyxpq", At, U, Vv, At).transpose(0, 1, 2, 4, 3, 5).reshape(1, 4, 8, 8) + bb.view(1, -1, 1, 1).numpy()
         assert rel(torch.from_numpy(Y), F.conv2d(xx, ww, bb, padding=1)) < 1e-12, k
+    if "--c32" in sys.argv:
+        threads = max(1, 8 // jobs) if jobs > 1 else 8
+        print(f"# Numerics probe -- Winograd F(4x4,3x3) on full-resolution 32-cout layers beside the GPU's level 1-3 rule (CPU emulation, `tools/wino_f4_probe.py {n_seeds} --c32 --jobs {jobs}`)\n")
+        print(f"{threads} torch thread(s) per seed.  The episode is chaotic: the figures of a scheme move by about 1e-5 with the host's thread count "
+              "and CPU type, and differ from `winof4_probe.md`'s rows of the same scheme for that reason.\n")
+        print(f"30-iteration CS-MRI ADMM episode (B = 2, 64 x 64, {n_seeds} seeds), relative L2 of the reconstructed image.  Bars of "
+              "tests/test_gpu_modes.py::test_csmri_episode_drift_not_worse_than_fp32: 1e-4 against the fp32 oracle, 8e-5 against fp64.  "
+              "At 64 x 64 level 1 (32 x 32) is the only deep level the GPU's rule admits (level 2 is 16 wide); level 0 is 64 x 64.")
+        drift_table(params, n_seeds, "c32", "half", jobs)
+        sys.exit(0)
     if levels:
         lv = ",".join(str(l) for l in levels)
         print(f"# Numerics probe -- Winograd F(4x4,3x3) on UNet levels {lv} of the fp32 family (CPU emulation, `tools/wino_f4_probe.py {n_seeds} --levels {lv} --points {points}`)\n")
