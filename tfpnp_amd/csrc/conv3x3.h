@@ -72,7 +72,9 @@ int launch_conv3x3_wino8_outc(const float* u, const float* bias, const float* in
                               const float* x_img, float* img, float* img_pre, int B, int H, int W, hipStream_t s);
 // Winograd F(4x4, 3x3) on v_mfma_f32_16x16x4_f32 (conv3x3_winof4.hip; option fp32_winof4_layers): plain single-source layers with cout a
 // multiple of 64, >= 16 input channels in multiples of 8, H a multiple of 16, W of 32.  u: pack_conv_weights_winof4's output
-// (conv3x3_winof4_floats(cout, cin) = 36 cout cin floats, 2.25 x the F(2x2) weights).
+// (conv3x3_winof4_floats(cout, cin) = 36 cout cin floats, 2.25 x the F(2x2) weights).  The four instances below are two kernels; what
+// the kernels share (geometry, work decode, halo gather, input transform, a stage's MFMAs, epilogue) and the one packer and one launch
+// path behind these entry points stand once each in conv3x3_winof4.hip.
 bool conv3x3_winof4_ok(int C0, int C1, int cout, int H, int W);
 // ... and its two-source instance (the UNet's decoder entries on an up-sampled second source; option fp32_winof4_entries): the same rules
 // on cout, H and W, both sources whole 8-channel chunks and at least one chunk each.  C1 = 0 launches the single-source instance.

@@ -3,8 +3,10 @@
 // (option fp32_winof4_layers) and, as a second instance, the two-source decoder entries on an already up-sampled second source (option
 // fp32_winof4_entries) or, as a third, on the low-resolution second source itself, up-sampled in the kernel (option fp32_winof4_fuse_up); and, as a
 // separate kernel of the same per-wave structure on a 32-cout tile, the full-resolution 32 -> 32 layers (conv3x3_winof4_c32_f32_kernel
-// below, option fp32_winof4_c32).  No residual, no K-split, no out-conv.  Same activation layout (padded planar fp32), WinoArgs,
-// bias + LeakyReLU as max(y, slope y) and optional fused 2x2 max-pool as the F(2x2) kernels.
+// below, option fp32_winof4_c32).  What the two kernels share stands once in front of them -- geometry (GeoF4), work decode, halo gather,
+// input transform, a stage's MFMA block, accumulator clear, epilogue -- and each kernel keeps its own stage pipeline.  No residual, no
+// K-split, no out-conv.  Same activation layout (padded planar fp32), WinoArgs, bias + LeakyReLU as max(y, slope y) and optional fused
+// 2x2 max-pool as the F(2x2) kernels.
 //
 // Points (0, +-1, +-1/2, inf), rows scaled as tools/wino_f4_probe.py's cook_toom does (winof4_mats.h holds the matrices the packer uses;
 // tests/test_winof4_pack.py checks them against a direct convolution).
@@ -40,20 +42,26 @@ namespace {
 
 using namespace wino;
 
-struct CfgF4 {
-  static constexpr int CT = 64, CK = 8;
-  static constexpr int RWL = 40;                          // LDS row stride of the halo (34 used): tile rows land 32 banks apart
+// Geometry of an instance: a workgroup owns CT couts x a region of 16 x RW px = RW tiles of 4 x 4 (4 tile rows x RW / 4 tile columns)
+// and keeps rings of NS weight stages and NS V stages in front of two raw halo buffers.  (64, 32, 3) / (32, 64, 2) in the comments.
+template <int CT_, int RW_, int NS>
+struct GeoF4 {
+  static constexpr int CT = CT_, RW = RW_, CK = 8;
+  static constexpr int RWL = RW + 8;                      // LDS row stride of the halo (RW + 2 used): tile rows land 32 banks apart (4 * RWL = 32 mod 64)
   static constexpr int RPXL = 18 * RWL + 2;               // LDS plane stride: odd channels land on the bank pairs the even ones leave free
   static constexpr int RAW_ELEMS = CK * RPXL;
-  static constexpr int RAW_INSTR = (RAW_ELEMS + 63) / 64; // dword gathers of 64 lanes: 91
-  static constexpr int RAW_BYTES = RAW_INSTR * 256;
-  static constexpr int RAW_PER_WAVE = (RAW_INSTR + 7) / 8;   // 12, of which the last exists for the first RAW_INSTR % 8 waves only
-  static constexpr int NRAW = RAW_INSTR / 8;                 // 11: gathers every wave issues
-  static constexpr int USTG = 2 * 6 * CK * CT * 4;        // bytes of one stage of weights (two position rows): 24 KiB
+  static constexpr int RAW_INSTR = (RAW_ELEMS + 63) / 64; // dword gathers of 64 lanes: 91 / 163
+  static constexpr int RAW_BYTES = RAW_INSTR * 256;       // 23296 / 41728
+  static constexpr int RAW_PER_WAVE = (RAW_INSTR + 7) / 8;   // 12 / 21, of which the last exists for the first RAW_INSTR % 8 waves only
+  static constexpr int NRAW = RAW_INSTR / 8;                 // 11 / 20: gathers every wave issues
+  static constexpr int USTG = 2 * 6 * CK * CT * 4;        // bytes of one stage of weights (two position rows): 24 / 12 KiB
+  static constexpr int VSTG = 2 * 6 * CK * RW * 4;        // bytes of one stage of V: 12 / 24 KiB
+  static constexpr int UCP = USTG / 6, VCP = VSTG / 6;    // ... of one column pair of a position row: 16 bytes per lane and 16-cout / 16-tile block
+  static constexpr int OFF_U = 0, OFF_V = NS * USTG, OFF_RAW = OFF_V + NS * VSTG;
+  static constexpr int LDS_USED = OFF_RAW + 2 * RAW_BYTES;   // 157184 / 157184
+};
+struct CfgF4 : GeoF4<64, 32, 3> {
   static constexpr int NUW = USTG / 8192;                 // 16-byte LDS-DMA instructions per wave and stage: 3
-  static constexpr int VSTG = 2 * 6 * CK * 32 * 4;        // bytes of one stage of V: 12 KiB
-  static constexpr int OFF_U = 0, OFF_V = 3 * USTG, OFF_RAW = OFF_V + 3 * VSTG;
-  static constexpr int LDS_USED = OFF_RAW + 2 * RAW_BYTES;   // 157184
   // UPS instance: a V ring of TWO slots (below) makes room for two staging windows of the low-resolution second source -- 11 rows x 20
   // columns per channel, [channel quad 2][row][column][channel 4] so that a halo pixel's tap is one 16-byte read per quad -- and the
   // per-tile interpolation tables (18 halo rows + 34 halo columns, 16 bytes each)
@@ -93,6 +101,175 @@ __device__ __forceinline__ void at_rows(float m0, float m1, float m2, float m3, 
   o3 = fmaf(0.125f, m34, m12) + m5;
 }
 
+// ---------------------------------------------------------------------------------------------------------------------------------
+// The pieces both kernels run, written once.  What differs between the instances reaches them as a geometry (C), as addresses or as
+// the caller's own callable; the stage schedules, the weight DMA and the up-sampling stay with the kernels.
+
+// -- work decode: the XCD-grouped walk over (region, cout tile) as conv3x3_wino8.hip (siblings share the halo in L2)
+struct Walk {
+  int nregions, nx, xcd, slot, nslot;
+};
+__device__ __forceinline__ Walk make_walk(const WinoArgs& a) {
+  Walk wk;
+  wk.nregions = a.rx * a.ry * a.B;
+  wk.nx = (gridDim.x % 8 == 0 && wk.nregions >= 32) ? 8 : 1;
+  wk.xcd = blockIdx.x % wk.nx;
+  wk.slot = blockIdx.x / wk.nx;
+  wk.nslot = gridDim.x / wk.nx;
+  return wk;
+}
+struct Tile {
+  const float* s0;   // halo origin in channel 0
+  const float* w;    // weights of the cout tile
+  int ct, b, x0, y0, ok;
+};
+template <class C>
+__device__ __forceinline__ Tile decode_tile(const WinoArgs& a, const Walk& wk, int HpWp, int k) {      // work item k of this workgroup
+  Tile T;
+  const int j = wk.slot + wk.nslot * k;
+  const int q = j / a.nct;
+  T.ct = j - q * a.nct;
+  const int reg = wk.nx * q + wk.xcd;
+  T.ok = reg < wk.nregions;
+  const int t1 = reg / a.rx;
+  const int tx = reg - t1 * a.rx;
+  const int t2 = t1 / a.ry;
+  const int ty = t1 - t2 * a.ry;
+  T.b = t2;
+  T.x0 = tx * C::RW;
+  T.y0 = ty * 16;
+  T.s0 = a.in0 + (size_t)T.b * a.C0 * HpWp + (size_t)T.y0 * a.Wp + T.x0 + (PADL - 1);
+  T.w = a.u + (size_t)T.ct * a.nch * 3 * (C::USTG / 4);
+  return T;
+}
+
+__device__ __forceinline__ void sync_all() {
+  asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+  __builtin_amdgcn_s_barrier();
+}
+
+// -- halo gather by dword LDS-DMA, an eighth per wave: per-lane byte offsets of the halo elements from the chunk's origin (lanes in the
+// rows' and planes' slack read the origin itself); raw0 = LDS address of halo buffer 0
+template <class C>
+struct HaloGather {
+  unsigned roff[C::RAW_PER_WAVE];
+  unsigned raw0;
+  int wave;
+  __device__ __forceinline__ HaloGather(const WinoArgs& a, int HpWp, unsigned raw0_, int wave_, int lane) : raw0(raw0_), wave(wave_) {
+#pragma unroll
+    for (int k = 0; k < C::RAW_PER_WAVE; ++k) {
+      const int idx = (wave + 8 * k) * 64 + lane;
+      const int c = idx / C::RPXL, r = idx - c * C::RPXL;
+      const int hy = r / C::RWL, hx = r - hy * C::RWL;
+      roff[k] = (c < C::CK && hy < 18 && hx < C::RW + 2) ? 4u * (unsigned)(c * HpWp + hy * a.Wp + hx) : 0u;
+    }
+  }
+  __device__ __forceinline__ void piece(const float* src, int rbuf, int k) const {      // gather k (of RAW_PER_WAVE per wave) of one chunk's halo
+    if (WINOF4_ABL & 2) return;
+    if (k < C::NRAW || wave + 8 * k < C::RAW_INSTR) glds4(src, roff[k], raw0 + rbuf * C::RAW_BYTES + (wave + 8 * k) * 256);
+  }
+  __device__ __forceinline__ void all(const float* src, int rbuf) const {
+#pragma unroll
+    for (int k = 0; k < C::RAW_PER_WAVE; ++k) piece(src, rbuf, k);
+  }
+};
+
+// -- input transform of one tile and one channel: position row A of B^T d B from the tile's 6 x 6 halo window at rb (rows RWL floats
+// apart) to vb, the three column pairs VCP bytes apart
+template <int A, int RWL, int VCP>
+__device__ __forceinline__ void transform_tile(const char* rb, char* vb) {
+  float d[6][6];
+#pragma unroll
+  for (int y = 0; y < 6; ++y) {
+    const bool need = (A == 0) ? (y % 2 == 0) : (A == 5) ? (y % 2 == 1) : (y >= 1 && y <= 4);
+#pragma unroll
+    for (int x = 0; x < 6; x += 2) {
+      if (need) {
+        const f32x2 v = *reinterpret_cast<const f32x2*>(rb + (y * RWL + x) * 4);
+        d[y][x] = v[0];
+        d[y][x + 1] = v[1];
+      } else {
+        d[y][x] = d[y][x + 1] = 0.f;
+      }
+    }
+  }
+  float t[6];
+#pragma unroll
+  for (int x = 0; x < 6; ++x) t[x] = bt_row<A>(d[0][x], d[1][x], d[2][x], d[3][x], d[4][x], d[5][x]);
+  *reinterpret_cast<f32x2*>(vb) = (f32x2){bt_row<0>(t[0], t[1], t[2], t[3], t[4], t[5]), bt_row<1>(t[0], t[1], t[2], t[3], t[4], t[5])};
+  *reinterpret_cast<f32x2*>(vb + VCP) = (f32x2){bt_row<2>(t[0], t[1], t[2], t[3], t[4], t[5]), bt_row<3>(t[0], t[1], t[2], t[3], t[4], t[5])};
+  *reinterpret_cast<f32x2*>(vb + 2 * VCP) = (f32x2){bt_row<4>(t[0], t[1], t[2], t[3], t[4], t[5]), bt_row<5>(t[0], t[1], t[2], t[3], t[4], t[5])};
+}
+
+// -- the 24 MFMAs of stage S (position rows 2 S and 2 S + 1): operands as 16-byte LDS reads = (k-step 2) x (position 2 of a column
+// pair) per lane at ua / vb, (row in stage * 3 + column pair) UCP / VCP bytes apart.  piece(m) is the caller's LDS-DMA schedule: one
+// call behind MFMA m, so that its issue cost runs under the MFMAs.
+template <int S, int UCP, int VCP, class Piece>
+__device__ __forceinline__ void mfma_stage(f32x4 (&acc)[6][6], const char* ua, const char* vb, Piece&& piece) {
+  f32x4 af[6], bf[6];
+#pragma unroll
+  for (int q = 0; q < 6; ++q) {
+    af[q] = *reinterpret_cast<const f32x4*>(ua + q * UCP);
+    bf[q] = *reinterpret_cast<const f32x4*>(vb + q * VCP);
+  }
+  static_for<6>([&](auto q_tag) {
+    constexpr int Q = decltype(q_tag)::value, R = Q / 3, CP = Q % 3;
+#pragma unroll
+    for (int ks = 0; ks < 2; ++ks)
+#pragma unroll
+      for (int pos = 0; pos < 2; ++pos) {
+        acc[2 * S + R][2 * CP + pos] = __builtin_amdgcn_mfma_f32_16x16x4f32(af[Q][2 * ks + pos], bf[Q][2 * ks + pos], acc[2 * S + R][2 * CP + pos], 0, 0, 0);
+        piece(4 * Q + 2 * ks + pos);
+        __builtin_amdgcn_sched_barrier(0);
+      }
+  });
+}
+
+__device__ __forceinline__ void clear_acc(f32x4 (&acc)[6][6]) {
+#pragma unroll
+  for (int i = 0; i < 6; ++i)
+#pragma unroll
+    for (int j = 0; j < 6; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
+}
+
+// -- epilogue, wave-local: Y = A^T M A per accumulator register (= cout cbase + register) of the lane's tile (ty, tx) of region T,
+// bias + activation, one 16-byte store per tile row, optional fused 2x2 max-pool
+__device__ __forceinline__ void epilogue_tile(const WinoArgs& a, const f32x4 (&acc)[6][6], int HpWp, const Tile& T, int ty, int tx, int cbase) {
+  float* ob = a.out + ((size_t)T.b * a.Cout + cbase) * HpWp + (size_t)(T.y0 + 4 * ty + 1) * a.Wp + T.x0 + 4 * tx + PADL;
+  const int Hp_pool = padded_h(a.H / 2), Wp_pool = padded_w(a.W / 2);
+  const size_t HpWp_pool = (size_t)Hp_pool * Wp_pool;
+  float* pb = a.pool ? a.pool + ((size_t)T.b * a.Cout + cbase) * HpWp_pool + (size_t)(T.y0 / 2 + 2 * ty + 1) * Wp_pool + T.x0 / 2 + 2 * tx + PADL : nullptr;
+  float bias4[4];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) bias4[j] = a.bias[cbase + j];
+  static_for<4>([&](auto j_tag) {
+    constexpr int j = decltype(j_tag)::value;
+    float s[4][6];
+#pragma unroll
+    for (int b = 0; b < 6; ++b) at_rows(acc[0][b][j], acc[1][b][j], acc[2][b][j], acc[3][b][j], acc[4][b][j], acc[5][b][j], s[0][b], s[1][b], s[2][b], s[3][b]);
+    const float bias = bias4[j];
+    float* o = ob + (size_t)j * HpWp;
+    f32x4 y[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      float y0, y1, y2, y3;
+      at_rows(s[i][0], s[i][1], s[i][2], s[i][3], s[i][4], s[i][5], y0, y1, y2, y3);
+      y0 += bias;
+      y1 += bias;
+      y2 += bias;
+      y3 += bias;
+      // LeakyReLU with 0 <= slope <= 1 as max(y, slope y)
+      y[i] = (f32x4){fmaxf(y0, y0 * a.slope), fmaxf(y1, y1 * a.slope), fmaxf(y2, y2 * a.slope), fmaxf(y3, y3 * a.slope)};
+      if (!(WINOF4_ABL & 32) || a.slope == 123.f) *reinterpret_cast<f32x4*>(o + i * a.Wp) = y[i];
+    }
+    if (a.pool && (!(WINOF4_ABL & 32) || a.slope == 123.f)) {      // four 2x2 windows per tile; same association as maxpool2_kernel
+      float* p = pb + (size_t)j * HpWp_pool;
+      *reinterpret_cast<f32x2*>(p) = (f32x2){fmaxf(fmaxf(y[0][0], y[0][1]), fmaxf(y[1][0], y[1][1])), fmaxf(fmaxf(y[0][2], y[0][3]), fmaxf(y[1][2], y[1][3]))};
+      *reinterpret_cast<f32x2*>(p + Wp_pool) = (f32x2){fmaxf(fmaxf(y[2][0], y[2][1]), fmaxf(y[3][0], y[3][1])), fmaxf(fmaxf(y[2][2], y[2][3]), fmaxf(y[3][2], y[3][3]))};
+    }
+  });
+}
+
 // TWO: the channel chunks C0 / 8 .. of a tile come from in1 (C1 channels, same geometry as in0); the weights are packed over C0 + C1 and
 // a.nch counts both sources' chunks.  A chunk lies in one source (C0 % 8 == 0), so only its halo origin differs.
 //
@@ -118,15 +295,10 @@ __global__ __launch_bounds__(512, 1) void conv3x3_winof4_f32_kernel(WinoArgs a) 
   const int sw = wave & 3;
   const int HpWp = a.Hp * a.Wp;
   const unsigned lds0 = (unsigned)(size_t)(lptr_t)lds;
-  const int nregions = a.rx * a.ry * a.B;
-  const int nx = (gridDim.x % 8 == 0 && nregions >= 32) ? 8 : 1;       // XCD-grouped walk as conv3x3_wino8.hip (siblings share the halo in L2)
-  const int xcd = blockIdx.x % nx, slot = blockIdx.x / nx, nslot = gridDim.x / nx;
+  const Walk wk = make_walk(a);
 
-  struct Tile {
-    const float* s0;   // halo origin in channel 0
-    const float* s1;   // ... of the second source (TWO)
-    const float* w;    // weights of the cout tile
-    int ct, b, x0, y0, ok, pad_;
+  struct Tile2 : Tile {
+    const float* s1;   // halo origin of the second source (TWO)
     int rs, cs;        // UPS: padded row / column of the low-resolution tensor at which the tile's staging window starts (s1 points there)
   };
   struct UpsStage {      // UPS: what differs from chunk to chunk in a pipeline stage
@@ -139,21 +311,8 @@ __global__ __launch_bounds__(512, 1) void conv3x3_winof4_f32_kernel(WinoArgs a) 
   // UPS: geometry of the low-resolution source
   const int h_lo = a.ups_h, w_lo = a.ups_w, hp_lo = padded_h(a.ups_h), wp_lo = padded_w(a.ups_w), hpwp_lo = hp_lo * wp_lo;
   auto decode = [&](int k) {
-    Tile T;
-    const int j = slot + nslot * k;
-    const int q = j / a.nct;
-    T.ct = j - q * a.nct;
-    const int reg = nx * q + xcd;
-    T.ok = reg < nregions;
-    T.pad_ = 0;
-    const int t1 = reg / a.rx;
-    const int tx = reg - t1 * a.rx;
-    const int t2 = t1 / a.ry;
-    const int ty = t1 - t2 * a.ry;
-    T.b = t2;
-    T.x0 = tx * 32;
-    T.y0 = ty * 16;
-    T.s0 = a.in0 + (size_t)T.b * a.C0 * HpWp + (size_t)T.y0 * a.Wp + T.x0 + (PADL - 1);
+    Tile2 T;
+    static_cast<Tile&>(T) = decode_tile<C>(a, wk, HpWp, k);
     if constexpr (UPS) {
       // The window starts at the first tap of the first halo row / column inside the image (the taps' indices grow with the halo index:
       // 18 rows span at most 10 source rows + the second tap, 34 columns at most 18 + 1), pulled back so that its SR rows and SC columns
@@ -166,46 +325,24 @@ __global__ __launch_bounds__(512, 1) void conv3x3_winof4_f32_kernel(WinoArgs a) 
       T.rs = T.cs = 0;
       T.s1 = TWO ? a.in1 + (size_t)T.b * a.C1 * HpWp + (size_t)T.y0 * a.Wp + T.x0 + (PADL - 1) : nullptr;
     }
-    T.w = a.u + (size_t)T.ct * a.nch * 3 * UQ;
     return T;
   };
   const int nch0 = a.C0 / CK;      // chunks of the first source
-  auto raw_of = [&](const Tile& X, int c) {
+  auto raw_of = [&](const Tile2& X, int c) {
     if (TWO && !UPS && c >= nch0) return X.s1 + (size_t)CK * (c - nch0) * HpWp;
     return X.s0 + (size_t)CK * c * HpWp;
   };
-  auto st_of = [&](const Tile& X, int c) { return X.s1 + (size_t)CK * (c - nch0) * hpwp_lo; };      // UPS: window origin of second-source chunk c
+  auto st_of = [&](const Tile2& X, int c) { return X.s1 + (size_t)CK * (c - nch0) * hpwp_lo; };      // UPS: window origin of second-source chunk c
 
-  auto sync_all = [&]() {
-    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-  };
-
-  // -- LDS-DMA, an eighth per wave: per-lane byte offsets of the halo elements from the chunk's origin
-  unsigned roff[RAW_PER_WAVE];
-#pragma unroll
-  for (int k = 0; k < RAW_PER_WAVE; ++k) {
-    const int idx = (wave + 8 * k) * 64 + lane;
-    const int c = idx / RPXL, r = idx - c * RPXL;
-    const int hy = r / RWL, hx = r - hy * RWL;
-    roff[k] = (c < CK && hy < 18 && hx < 34) ? 4u * (unsigned)(c * HpWp + hy * a.Wp + hx) : 0u;
-  }
+  const HaloGather<C> halo(a, HpWp, lds0 + OFF_RAW, wave, lane);
   const unsigned uoff = lane * 16u;
   auto dma_u_piece = [&](const float* src, int uslot, int k) {     // piece k (of NUW per wave) of one stage's weights -> ring slot uslot
     if (WINOF4_ABL & 4) return;
     glds16(src + wave * 256 + k * 2048, uoff, lds0 + OFF_U + uslot * USTG + (wave + 8 * k) * 1024);
   };
-  auto dma_raw_piece = [&](const float* src, int rbuf, int k) {     // gather k (of RAW_PER_WAVE per wave) of one chunk's halo
-    if (WINOF4_ABL & 2) return;
-    if (k < C::NRAW || wave + 8 * k < C::RAW_INSTR) glds4(src, roff[k], lds0 + OFF_RAW + rbuf * RAW_BYTES + (wave + 8 * k) * 256);
-  };
   auto dma_u = [&](const float* src, int uslot) {
 #pragma unroll
     for (int k = 0; k < NUW; ++k) dma_u_piece(src, uslot, k);
-  };
-  auto dma_raw = [&](const float* src, int rbuf) {
-#pragma unroll
-    for (int k = 0; k < RAW_PER_WAVE; ++k) dma_raw_piece(src, rbuf, k);
   };
 
   // -- UPS: the staging window of a second-source chunk, an eighth per wave: per-lane byte offsets from the window's origin in the
@@ -229,7 +366,7 @@ __global__ __launch_bounds__(512, 1) void conv3x3_winof4_f32_kernel(WinoArgs a) 
   // its weight h, the second tap's weight l, byte offset of the second tap); h = -1 marks a row / column outside the image (the
   // convolution's zero padding).  The floats are upsample2x_v4_kernel's, operation by operation (its disassembly: no contraction here):
   // f = s * index, i0 = (int) f, l = f - i0, h = 1 - l, second tap i0 + (i0 < n - 1).
-  auto write_tables = [&](const Tile& X) {
+  auto write_tables = [&](const Tile2& X) {
     if (tid < 18 + 34) {
       const bool row = tid < 18;
       const int g = (row ? X.y0 : X.x0) - 1 + (row ? tid : tid - 18);      // image coordinate of the halo row / column
@@ -296,36 +433,10 @@ __global__ __launch_bounds__(512, 1) void conv3x3_winof4_f32_kernel(WinoArgs a) 
   const int t_tile = t_wn * 16 + t_t16;
   const int t_rd = ((2 * t_kq + t_ks) * RPXL + 4 * (t_tile >> 3) * RWL + 4 * (t_tile & 7)) * 4;
   const int t_wr = (P * 3 * 2 + t_wn) * 1024 + (t_kq * 16 + t_t16) * 16 + t_ks * 8;       // + column pair * 2048 (+ slot)
-  auto transform = [&](auto a_tag, int rbuf, int vslot) {
-    constexpr int A = decltype(a_tag)::value;       // position row
-    const char* rb = lds + OFF_RAW + rbuf * RAW_BYTES + t_rd;
-    float d[6][6];
-#pragma unroll
-    for (int y = 0; y < 6; ++y) {
-      const bool need = (A == 0) ? (y % 2 == 0) : (A == 5) ? (y % 2 == 1) : (y >= 1 && y <= 4);
-#pragma unroll
-      for (int x = 0; x < 6; x += 2) {
-        if (need) {
-          const f32x2 v = *reinterpret_cast<const f32x2*>(rb + (y * RWL + x) * 4);
-          d[y][x] = v[0];
-          d[y][x + 1] = v[1];
-        } else {
-          d[y][x] = d[y][x + 1] = 0.f;
-        }
-      }
-    }
-    float t[6];
-#pragma unroll
-    for (int x = 0; x < 6; ++x) t[x] = bt_row<A>(d[0][x], d[1][x], d[2][x], d[3][x], d[4][x], d[5][x]);
-    char* vb = lds + OFF_V + vslot * VSTG + t_wr;
-    *reinterpret_cast<f32x2*>(vb) = (f32x2){bt_row<0>(t[0], t[1], t[2], t[3], t[4], t[5]), bt_row<1>(t[0], t[1], t[2], t[3], t[4], t[5])};
-    *reinterpret_cast<f32x2*>(vb + 2048) = (f32x2){bt_row<2>(t[0], t[1], t[2], t[3], t[4], t[5]), bt_row<3>(t[0], t[1], t[2], t[3], t[4], t[5])};
-    *reinterpret_cast<f32x2*>(vb + 4096) = (f32x2){bt_row<4>(t[0], t[1], t[2], t[3], t[4], t[5]), bt_row<5>(t[0], t[1], t[2], t[3], t[4], t[5])};
-  };
   auto transform_row = [&](auto s_tag, int rbuf, int vslot_ups = 0) {      // this thread's row of stage S's two, into V slot S (UPS: vslot_ups)
     constexpr int S = decltype(s_tag)::value;
     if (WINOF4_ABL & 1) return;
-    transform(std::integral_constant<int, 2 * S + P>{}, rbuf, UPS ? vslot_ups : S);
+    transform_tile<2 * S + P, RWL, C::VCP>(lds + OFF_RAW + rbuf * RAW_BYTES + t_rd, lds + OFF_V + (UPS ? vslot_ups : S) * VSTG + t_wr);
   };
 
   // -- MFMA operands: 16 bytes = (k-step 2) x (position 2 of a column pair) per lane; lane = 16 * channel group + cout / tile of the block
@@ -352,33 +463,14 @@ __global__ __launch_bounds__(512, 1) void conv3x3_winof4_f32_kernel(WinoArgs a) 
     // chunk three ahead behind 16 .. 19
     auto piece = [&](int m) {
       if (m < NUW) dma_u_piece(u_src, (S + 2) % 3, m);
-      if (S == 2 && m >= 4 && m < 4 + RAW_PER_WAVE && (!UPS || x.raw)) dma_raw_piece(raw_src, raw_buf, m - 4);
+      if (S == 2 && m >= 4 && m < 4 + RAW_PER_WAVE && (!UPS || x.raw)) halo.piece(raw_src, raw_buf, m - 4);
       if constexpr (UPS) {
         if (S == 2 && m >= 16 && m < 16 + ST_PER_WAVE && x.st) dma_st_piece(x.st_src, x.st_buf, m - 16);
       }
     };
     auto mfmas = [&]() {
-      if (WINOF4_ABL & 16) return;
-      f32x4 af[6], bf[6];
-#pragma unroll
-      for (int q = 0; q < 6; ++q) {
-        af[q] = *reinterpret_cast<const f32x4*>(lds + OFF_U + S * USTG + q * 4096 + a_lane);
-        bf[q] = *reinterpret_cast<const f32x4*>(lds + OFF_V + (UPS ? x.vrd : S) * VSTG + q * 2048 + b_lane);
-      }
-      static_for<6>([&](auto q_tag) {
-        constexpr int Q = decltype(q_tag)::value, R = Q / 3, CP = Q % 3;
-#pragma unroll
-        for (int ks = 0; ks < 2; ++ks)
-#pragma unroll
-          for (int pos = 0; pos < 2; ++pos)
-          {
-            acc[2 * S + R][2 * CP + pos] = __builtin_amdgcn_mfma_f32_16x16x4f32(af[Q][2 * ks + pos], bf[Q][2 * ks + pos], acc[2 * S + R][2 * CP + pos], 0, 0, 0);
-            if (!(WINOF4_ABL & 16)) {
-              piece(4 * Q + 2 * ks + pos);
-              __builtin_amdgcn_sched_barrier(0);
-            }
-          }
-      });
+      if (WINOF4_ABL & 16) return;      // (and none of the stage's pieces)
+      mfma_stage<S, C::UCP, C::VCP>(acc, lds + OFF_U + S * USTG + a_lane, lds + OFF_V + (UPS ? x.vrd : S) * VSTG + b_lane, piece);
     };
     if (P == 0) {
       mfmas();
@@ -403,43 +495,10 @@ __global__ __launch_bounds__(512, 1) void conv3x3_winof4_f32_kernel(WinoArgs a) 
     __builtin_amdgcn_s_barrier();
   };
 
-  // -- epilogue, wave-local: Y = A^T M A per accumulator register (= cout), bias + activation, one 16-byte store per tile row
+  // -- epilogue: the lane's tile of the wave's 16 and its four couts
   auto epilogue = [&](const Tile& T) {
-    const int tile = wn * 16 + (lane & 15), ty = tile >> 3, tx = tile & 7;
-    const int cbase = T.ct * 64 + mb * 16 + 4 * (lane >> 4);
-    float* ob = a.out + ((size_t)T.b * a.Cout + cbase) * HpWp + (size_t)(T.y0 + 4 * ty + 1) * a.Wp + T.x0 + 4 * tx + PADL;
-    const int Hp_pool = padded_h(a.H / 2), Wp_pool = padded_w(a.W / 2);
-    const size_t HpWp_pool = (size_t)Hp_pool * Wp_pool;
-    float* pb = a.pool ? a.pool + ((size_t)T.b * a.Cout + cbase) * HpWp_pool + (size_t)(T.y0 / 2 + 2 * ty + 1) * Wp_pool + T.x0 / 2 + 2 * tx + PADL : nullptr;
-    float bias4[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) bias4[j] = a.bias[cbase + j];
-    static_for<4>([&](auto j_tag) {
-      constexpr int j = decltype(j_tag)::value;
-      float s[4][6];
-#pragma unroll
-      for (int b = 0; b < 6; ++b) at_rows(acc[0][b][j], acc[1][b][j], acc[2][b][j], acc[3][b][j], acc[4][b][j], acc[5][b][j], s[0][b], s[1][b], s[2][b], s[3][b]);
-      const float bias = bias4[j];
-      float* o = ob + (size_t)j * HpWp;
-      f32x4 y[4];
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        float y0, y1, y2, y3;
-        at_rows(s[i][0], s[i][1], s[i][2], s[i][3], s[i][4], s[i][5], y0, y1, y2, y3);
-        y0 += bias;
-        y1 += bias;
-        y2 += bias;
-        y3 += bias;
-        // LeakyReLU with 0 <= slope <= 1 as max(y, slope y)
-        y[i] = (f32x4){fmaxf(y0, y0 * a.slope), fmaxf(y1, y1 * a.slope), fmaxf(y2, y2 * a.slope), fmaxf(y3, y3 * a.slope)};
-        if (!(WINOF4_ABL & 32) || a.slope == 123.f) *reinterpret_cast<f32x4*>(o + i * a.Wp) = y[i];
-      }
-      if (a.pool && (!(WINOF4_ABL & 32) || a.slope == 123.f)) {      // four 2x2 windows per tile; same association as maxpool2_kernel
-        float* p = pb + (size_t)j * HpWp_pool;
-        *reinterpret_cast<f32x2*>(p) = (f32x2){fmaxf(fmaxf(y[0][0], y[0][1]), fmaxf(y[1][0], y[1][1])), fmaxf(fmaxf(y[0][2], y[0][3]), fmaxf(y[1][2], y[1][3]))};
-        *reinterpret_cast<f32x2*>(p + Wp_pool) = (f32x2){fmaxf(fmaxf(y[2][0], y[2][1]), fmaxf(y[3][0], y[3][1])), fmaxf(fmaxf(y[2][2], y[2][3]), fmaxf(y[3][2], y[3][3]))};
-      }
-    });
+    const int tile = wn * 16 + (lane & 15);
+    epilogue_tile(a, acc, HpWp, T, tile >> 3, tile & 7, T.ct * 64 + mb * 16 + 4 * (lane >> 4));
   };
 
   using I0 = std::integral_constant<int, 0>;
@@ -450,13 +509,13 @@ __global__ __launch_bounds__(512, 1) void conv3x3_winof4_f32_kernel(WinoArgs a) 
   using WaitU = std::integral_constant<int, NUW>;
 
   int k = 0;
-  Tile T = decode(0);
+  Tile2 T = decode(0);
   if (!T.ok) return;
   // prologue: the first two halos and weight stages, the first transform
-  dma_raw(T.s0, 0);
+  halo.all(T.s0, 0);
   dma_u(T.w, 0);
   dma_u(T.w + UQ, 1);
-  dma_raw(raw_of(T, 1), 1);      // (nch >= 2: chunk 1 exists; chunk 0 lies in the first source)
+  halo.all(raw_of(T, 1), 1);      // (nch >= 2: chunk 1 exists; chunk 0 lies in the first source)
   if constexpr (UPS) {           // (UPS: nch0 >= 2, chunks 0 and 1 are gathered; chunk 2 is staged here when it is the second source's first)
     if (nch0 == 2) {
 #pragma unroll
@@ -470,16 +529,13 @@ __global__ __launch_bounds__(512, 1) void conv3x3_winof4_f32_kernel(WinoArgs a) 
   int cc = 0;
   int wait_prev = NUW;      // UPS: what the last stage 2 left in flight (nothing before the first chunk)
   for (;;) {
-    Tile Tn = decode(k + 1);
+    Tile2 Tn = decode(k + 1);
     const bool more = Tn.ok;
     if (!more) Tn = T;      // after the walk's last chunks: surplus loads of this tile's first chunks into buffers nobody reads
     // UPS: the tile's tables.  Their last readers were the previous tile's last interpolation steps, two barriers back; their first
     // reader is stage 2 of chunk nch0 - 2, two barriers ahead.
     if constexpr (UPS) write_tables(T);
-#pragma unroll
-    for (int i = 0; i < 6; ++i)
-#pragma unroll
-      for (int j = 0; j < 6; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
+    clear_acc(acc);
     for (int c = 0; c < a.nch; ++c, ++cc) {
       const float* w_c = T.w + (size_t)c * 3 * UQ;
       const float* nu = (c + 1 < a.nch) ? w_c + 3 * UQ : Tn.w;                                    // the next chunk's weights
@@ -531,28 +587,14 @@ __global__ __launch_bounds__(512, 1) void conv3x3_winof4_f32_kernel(WinoArgs a) 
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------------
-// The 32-cout instance (option fp32_winof4_c32): the full-resolution 32 -> 32 layers.  The per-wave structure is the one above -- 16 couts
-// x 16 tiles x 36 positions in 144 registers, 24 MFMAs per wave and stage, wave-local output transform, role P = wave / 4 -- on a
-// workgroup of 32 couts x 64 tiles: a region of 16 x 64 px = 4 tile rows x 16 tile columns.  Wave (P, sw) owns cout block P and tile row
-// sw, so the two waves of a SIMD read the same V operands.  LDS: weights 2 x 12 KiB and V 2 x 24 KiB (both: stage g of the running stage
-// count reads slot g & 1 and fills the other one for stage g + 1; the barrier between two stages separates a slot's last read from its next
-// write), raw halo 2 x 40.75 KiB (18 x 66 per channel in rows of 72 + 2 floats per plane: 4 * 72 = 32 mod 64 banks, as with 40).  The
+// The 32-cout instance (option fp32_winof4_c32): the full-resolution 32 -> 32 layers.  What differs from the kernel above: a workgroup
+// owns 32 couts x 64 tiles, a region of 16 x 64 px = 4 tile rows x 16 tile columns; wave (P, sw) owns cout block P and tile row sw, so the
+// two waves of a SIMD read the same V operands, and a thread transforms two tiles per stage.  LDS: weights 2 x 12 KiB and V 2 x 24 KiB
+// (both: stage g of the running stage count reads slot g & 1 and fills the other one for stage g + 1; the barrier between two stages
+// separates a slot's last read from its next write), raw halo 2 x 40.75 KiB (18 x 66 per channel in rows of 72 + 2 floats per plane).  The
 // weights of stage g + 1 are the last VMEM operations stage g needs, so stages 0 and 1 wait for everything in flight and stage 2 for all
 // but the halo gathers it issued behind its weight slice; a halo therefore has one stage of lead before its wait, the weights less.
-struct CfgF4C32 {
-  static constexpr int CT = 32, CK = 8;
-  static constexpr int RWL = 72;
-  static constexpr int RPXL = 18 * RWL + 2;
-  static constexpr int RAW_ELEMS = CK * RPXL;
-  static constexpr int RAW_INSTR = (RAW_ELEMS + 63) / 64;     // 163
-  static constexpr int RAW_BYTES = RAW_INSTR * 256;           // 41728
-  static constexpr int RAW_PER_WAVE = (RAW_INSTR + 7) / 8;    // 21, of which the last exists for the first RAW_INSTR % 8 = 3 waves only
-  static constexpr int NRAW = RAW_INSTR / 8;                  // 20: gathers every wave issues
-  static constexpr int USTG = 2 * 6 * CK * CT * 4;            // 12 KiB = 12 16-byte LDS-DMA instructions: one per wave + one more on waves 4 .. 7
-  static constexpr int VSTG = 2 * 6 * CK * 64 * 4;            // 24 KiB
-  static constexpr int OFF_U = 0, OFF_V = 2 * USTG, OFF_RAW = OFF_V + 2 * VSTG;
-  static constexpr int LDS_USED = OFF_RAW + 2 * RAW_BYTES;    // 157184
-};
+using CfgF4C32 = GeoF4<32, 64, 2>;      // USTG = 12 16-byte LDS-DMA instructions: one per wave + one more on waves 4 .. 7
 static_assert(CfgF4C32::LDS_USED <= LDS_REQF4 && CfgF4C32::RAW_PER_WAVE + 3 <= 24 && CfgF4C32::USTG == 12 * 1024, "32-cout instance");
 
 __global__ __launch_bounds__(512, 1) void conv3x3_winof4_c32_f32_kernel(WinoArgs a) {
@@ -566,61 +608,15 @@ __global__ __launch_bounds__(512, 1) void conv3x3_winof4_c32_f32_kernel(WinoArgs
   const int sw = wave & 3;
   const int HpWp = a.Hp * a.Wp;
   const unsigned lds0 = (unsigned)(size_t)(lptr_t)lds;
-  const int nregions = a.rx * a.ry * a.B;
-  const int nx = (gridDim.x % 8 == 0 && nregions >= 32) ? 8 : 1;       // XCD-grouped walk, as above
-  const int xcd = blockIdx.x % nx, slot = blockIdx.x / nx, nslot = gridDim.x / nx;
-
-  struct Tile {
-    const float* s0;   // halo origin in channel 0
-    const float* w;    // weights of the cout tile
-    int ct, b, x0, y0, ok;
-  };
-  auto decode = [&](int k) {
-    Tile T;
-    const int j = slot + nslot * k;
-    const int q = j / a.nct;
-    T.ct = j - q * a.nct;
-    const int reg = nx * q + xcd;
-    T.ok = reg < nregions;
-    const int t1 = reg / a.rx;
-    const int tx = reg - t1 * a.rx;
-    const int t2 = t1 / a.ry;
-    const int ty = t1 - t2 * a.ry;
-    T.b = t2;
-    T.x0 = tx * 64;
-    T.y0 = ty * 16;
-    T.s0 = a.in0 + (size_t)T.b * a.C0 * HpWp + (size_t)T.y0 * a.Wp + T.x0 + (PADL - 1);
-    T.w = a.u + (size_t)T.ct * a.nch * 3 * UQ;
-    return T;
-  };
+  const Walk wk = make_walk(a);
+  auto decode = [&](int k) { return decode_tile<C>(a, wk, HpWp, k); };
   auto raw_of = [&](const Tile& X, int c) { return X.s0 + (size_t)CK * c * HpWp; };
-  auto sync_all = [&]() {
-    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-  };
 
-  // -- LDS-DMA, an eighth per wave: per-lane byte offsets of the halo elements from the chunk's origin (lanes in the rows' and planes'
-  // slack read the origin itself)
-  unsigned roff[RAW_PER_WAVE];
-#pragma unroll
-  for (int k = 0; k < RAW_PER_WAVE; ++k) {
-    const int idx = (wave + 8 * k) * 64 + lane;
-    const int c = idx / RPXL, r = idx - c * RPXL;
-    const int hy = r / RWL, hx = r - hy * RWL;
-    roff[k] = (c < CK && hy < 18 && hx < 66) ? 4u * (unsigned)(c * HpWp + hy * a.Wp + hx) : 0u;
-  }
+  const HaloGather<C> halo(a, HpWp, lds0 + OFF_RAW, wave, lane);
   const unsigned uoff = lane * 16u;
   auto dma_u_piece = [&](const float* src, int uslot, int p) {      // KiB p (of 12) of one stage's weights -> ring slot uslot
     if (WINOF4_ABL & 4) return;
     glds16(src + p * 256, uoff, lds0 + OFF_U + uslot * USTG + p * 1024);
-  };
-  auto dma_raw_piece = [&](const float* src, int rbuf, int k) {     // gather k (of RAW_PER_WAVE per wave) of one chunk's halo
-    if (WINOF4_ABL & 2) return;
-    if (k < C::NRAW || wave + 8 * k < C::RAW_INSTR) glds4(src, roff[k], lds0 + OFF_RAW + rbuf * RAW_BYTES + (wave + 8 * k) * 256);
-  };
-  auto dma_raw = [&](const float* src, int rbuf) {
-#pragma unroll
-    for (int k = 0; k < RAW_PER_WAVE; ++k) dma_raw_piece(src, rbuf, k);
   };
 
   auto body = [&](auto role_tag) {
@@ -631,37 +627,13 @@ __global__ __launch_bounds__(512, 1) void conv3x3_winof4_c32_f32_kernel(WinoArgs
   const int t_ks = lane & 1, t_t16 = (lane >> 1) & 15, t_kq = (lane >> 5) | ((sw & 1) << 1), t_wn = sw >> 1;
   const int t_rd = ((2 * t_kq + t_ks) * RPXL + 4 * t_wn * RWL + 4 * t_t16) * 4;           // + 8 tile-row strides for the second tile
   const int t_wr = (P * 3 * 4 + t_wn) * 1024 + (t_kq * 16 + t_t16) * 16 + t_ks * 8;       // + column pair * 4096 (+ slot); + 2048 for the second tile
-  auto transform = [&](auto a_tag, int rbuf, int vslot, int second) {
-    constexpr int A = decltype(a_tag)::value;       // position row
-    const char* rb = lds + OFF_RAW + rbuf * RAW_BYTES + t_rd + second * (8 * RWL * 4);
-    float d[6][6];
-#pragma unroll
-    for (int y = 0; y < 6; ++y) {
-      const bool need = (A == 0) ? (y % 2 == 0) : (A == 5) ? (y % 2 == 1) : (y >= 1 && y <= 4);
-#pragma unroll
-      for (int x = 0; x < 6; x += 2) {
-        if (need) {
-          const f32x2 v = *reinterpret_cast<const f32x2*>(rb + (y * RWL + x) * 4);
-          d[y][x] = v[0];
-          d[y][x + 1] = v[1];
-        } else {
-          d[y][x] = d[y][x + 1] = 0.f;
-        }
-      }
-    }
-    float t[6];
-#pragma unroll
-    for (int x = 0; x < 6; ++x) t[x] = bt_row<A>(d[0][x], d[1][x], d[2][x], d[3][x], d[4][x], d[5][x]);
-    char* vb = lds + OFF_V + vslot * VSTG + t_wr + second * 2048;
-    *reinterpret_cast<f32x2*>(vb) = (f32x2){bt_row<0>(t[0], t[1], t[2], t[3], t[4], t[5]), bt_row<1>(t[0], t[1], t[2], t[3], t[4], t[5])};
-    *reinterpret_cast<f32x2*>(vb + 4096) = (f32x2){bt_row<2>(t[0], t[1], t[2], t[3], t[4], t[5]), bt_row<3>(t[0], t[1], t[2], t[3], t[4], t[5])};
-    *reinterpret_cast<f32x2*>(vb + 8192) = (f32x2){bt_row<4>(t[0], t[1], t[2], t[3], t[4], t[5]), bt_row<5>(t[0], t[1], t[2], t[3], t[4], t[5])};
-  };
   auto transform_row = [&](auto s_tag, int rbuf, int vslot) {      // this thread's two tiles of row P of stage S's two
     constexpr int S = decltype(s_tag)::value;
     if (WINOF4_ABL & 1) return;
-    transform(std::integral_constant<int, 2 * S + P>{}, rbuf, vslot, 0);
-    transform(std::integral_constant<int, 2 * S + P>{}, rbuf, vslot, 1);
+    const char* rb = lds + OFF_RAW + rbuf * RAW_BYTES + t_rd;
+    char* vb = lds + OFF_V + vslot * VSTG + t_wr;
+    transform_tile<2 * S + P, RWL, C::VCP>(rb, vb);
+    transform_tile<2 * S + P, RWL, C::VCP>(rb + 8 * RWL * 4, vb + 2048);
   };
 
   // -- MFMA operands: 16 bytes = (k-step 2) x (position 2 of a column pair) per lane; lane = 16 * channel group + cout / tile of the block
@@ -678,7 +650,7 @@ __global__ __launch_bounds__(512, 1) void conv3x3_winof4_c32_f32_kernel(WinoArgs
     auto piece = [&](int m) {
       if (m == 0) dma_u_piece(u_src, vrd ^ 1, wave);
       if (m == 1 && P == 1) dma_u_piece(u_src, vrd ^ 1, 4 + wave);
-      if (S == 2 && m >= 3 && m < 3 + RAW_PER_WAVE) dma_raw_piece(raw_src, raw_buf, m - 3);
+      if (S == 2 && m >= 3 && m < 3 + RAW_PER_WAVE) halo.piece(raw_src, raw_buf, m - 3);
     };
     auto mfmas = [&]() {
       if (WINOF4_ABL & 16) {      // data movement alone: the stage's LDS-DMA pieces without the MFMAs they stand behind
@@ -686,23 +658,7 @@ __global__ __launch_bounds__(512, 1) void conv3x3_winof4_c32_f32_kernel(WinoArgs
         for (int m = 0; m < 24; ++m) piece(m);
         return;
       }
-      f32x4 af[6], bf[6];
-#pragma unroll
-      for (int q = 0; q < 6; ++q) {
-        af[q] = *reinterpret_cast<const f32x4*>(lds + OFF_U + vrd * USTG + q * 2048 + a_lane);
-        bf[q] = *reinterpret_cast<const f32x4*>(lds + OFF_V + vrd * VSTG + q * 4096 + b_lane);
-      }
-      static_for<6>([&](auto q_tag) {
-        constexpr int Q = decltype(q_tag)::value, R = Q / 3, CP = Q % 3;
-#pragma unroll
-        for (int ks = 0; ks < 2; ++ks)
-#pragma unroll
-          for (int pos = 0; pos < 2; ++pos) {
-            acc[2 * S + R][2 * CP + pos] = __builtin_amdgcn_mfma_f32_16x16x4f32(af[Q][2 * ks + pos], bf[Q][2 * ks + pos], acc[2 * S + R][2 * CP + pos], 0, 0, 0);
-            piece(4 * Q + 2 * ks + pos);
-            __builtin_amdgcn_sched_barrier(0);
-          }
-      });
+      mfma_stage<S, C::UCP, C::VCP>(acc, lds + OFF_U + vrd * USTG + a_lane, lds + OFF_V + vrd * VSTG + b_lane, piece);
     };
     if (P == 0) {
       mfmas();
@@ -720,44 +676,8 @@ __global__ __launch_bounds__(512, 1) void conv3x3_winof4_c32_f32_kernel(WinoArgs
     __builtin_amdgcn_s_barrier();
   };
 
-  // -- epilogue, wave-local, as above: tile row sw, tile column lane & 15
-  auto epilogue = [&](const Tile& T) {
-    const int ty = sw, tx = lane & 15;
-    const int cbase = T.ct * 32 + P * 16 + 4 * (lane >> 4);
-    float* ob = a.out + ((size_t)T.b * a.Cout + cbase) * HpWp + (size_t)(T.y0 + 4 * ty + 1) * a.Wp + T.x0 + 4 * tx + PADL;
-    const int Hp_pool = padded_h(a.H / 2), Wp_pool = padded_w(a.W / 2);
-    const size_t HpWp_pool = (size_t)Hp_pool * Wp_pool;
-    float* pb = a.pool ? a.pool + ((size_t)T.b * a.Cout + cbase) * HpWp_pool + (size_t)(T.y0 / 2 + 2 * ty + 1) * Wp_pool + T.x0 / 2 + 2 * tx + PADL : nullptr;
-    float bias4[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) bias4[j] = a.bias[cbase + j];
-    static_for<4>([&](auto j_tag) {
-      constexpr int j = decltype(j_tag)::value;
-      float s[4][6];
-#pragma unroll
-      for (int b = 0; b < 6; ++b) at_rows(acc[0][b][j], acc[1][b][j], acc[2][b][j], acc[3][b][j], acc[4][b][j], acc[5][b][j], s[0][b], s[1][b], s[2][b], s[3][b]);
-      const float bias = bias4[j];
-      float* o = ob + (size_t)j * HpWp;
-      f32x4 y[4];
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        float y0, y1, y2, y3;
-        at_rows(s[i][0], s[i][1], s[i][2], s[i][3], s[i][4], s[i][5], y0, y1, y2, y3);
-        y0 += bias;
-        y1 += bias;
-        y2 += bias;
-        y3 += bias;
-        // LeakyReLU with 0 <= slope <= 1 as max(y, slope y)
-        y[i] = (f32x4){fmaxf(y0, y0 * a.slope), fmaxf(y1, y1 * a.slope), fmaxf(y2, y2 * a.slope), fmaxf(y3, y3 * a.slope)};
-        if (!(WINOF4_ABL & 32) || a.slope == 123.f) *reinterpret_cast<f32x4*>(o + i * a.Wp) = y[i];
-      }
-      if (a.pool && (!(WINOF4_ABL & 32) || a.slope == 123.f)) {      // four 2x2 windows per tile; same association as maxpool2_kernel
-        float* p = pb + (size_t)j * HpWp_pool;
-        *reinterpret_cast<f32x2*>(p) = (f32x2){fmaxf(fmaxf(y[0][0], y[0][1]), fmaxf(y[1][0], y[1][1])), fmaxf(fmaxf(y[0][2], y[0][3]), fmaxf(y[1][2], y[1][3]))};
-        *reinterpret_cast<f32x2*>(p + Wp_pool) = (f32x2){fmaxf(fmaxf(y[2][0], y[2][1]), fmaxf(y[3][0], y[3][1])), fmaxf(fmaxf(y[2][2], y[2][3]), fmaxf(y[3][2], y[3][3]))};
-      }
-    });
-  };
+  // -- epilogue: tile row sw, tile column lane & 15
+  auto epilogue = [&](const Tile& T) { epilogue_tile(a, acc, HpWp, T, sw, lane & 15, T.ct * 32 + P * 16 + 4 * (lane >> 4)); };
 
   using I0 = std::integral_constant<int, 0>;
   using I1 = std::integral_constant<int, 1>;
@@ -767,10 +687,10 @@ __global__ __launch_bounds__(512, 1) void conv3x3_winof4_c32_f32_kernel(WinoArgs
   Tile T = decode(0);
   if (!T.ok) return;
   // prologue: the first two halos, the first weight stage, the first transform (nch >= 2: chunk 1 exists)
-  dma_raw(T.s0, 0);
+  halo.all(T.s0, 0);
   dma_u_piece(T.w, 0, wave);
   if (P == 1) dma_u_piece(T.w, 0, 4 + wave);
-  dma_raw(raw_of(T, 1), 1);
+  halo.all(raw_of(T, 1), 1);
   sync_all();
   transform_row(I0{}, 0, 0);
   sync_all();
@@ -780,10 +700,7 @@ __global__ __launch_bounds__(512, 1) void conv3x3_winof4_c32_f32_kernel(WinoArgs
     Tile Tn = decode(k + 1);
     const bool more = Tn.ok;
     if (!more) Tn = T;      // after the walk's last chunks: surplus loads of this tile's first chunks into buffers nobody reads
-#pragma unroll
-    for (int i = 0; i < 6; ++i)
-#pragma unroll
-      for (int j = 0; j < 6; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
+    clear_acc(acc);
     for (int c = 0; c < a.nch; ++c, ++cc) {
       const float* w_c = T.w + (size_t)c * 3 * UQ;
       const float* nu = (c + 1 < a.nch) ? w_c + 3 * UQ : Tn.w;                                    // the next chunk's weights
@@ -822,10 +739,10 @@ bool conv3x3_winof4_ups_ok(int C0, int C1, int cout, int H, int W) { return conv
 bool conv3x3_winof4_packs(int cout, int cin) { return conv3x3_winof4_ok(cin, 0, cout, 16, 32); }
 size_t conv3x3_winof4_floats(int cout, int cin) { return (size_t)36 * cout * cin; }
 
-// U = G g G^T in double, rounded once; layout [cout / 64][cin / 8][stage 3][row in stage 2][column pair 3][cout block 4][channel group 4]
+// U = G g G^T in double, rounded once; layout [cout / CT][cin / 8][stage 3][row in stage 2][column pair 3][cout block CT / 16][channel group 4]
 // [cout 16][k-step 2][column in pair 2]: position (2 * stage + row, 2 * pair + column), channel 8 * chunk + 2 * group + k-step
-void pack_conv_weights_winof4(const float* w, int cout, int cin, float* dst) {
-  const int nch = cin / 8;
+static void pack_winof4(const float* w, int cout, int cin, float* dst, int CT) {
+  const int nch = cin / 8, nmb = CT / 16;
   for (int co = 0; co < cout; ++co)
     for (int ci = 0; ci < cin; ++ci) {
       const float* g = w + ((size_t)co * cin + ci) * 9;
@@ -834,14 +751,15 @@ void pack_conv_weights_winof4(const float* w, int cout, int cin, float* dst) {
         for (int x = 0; x < 3; ++x) gg[i][x] = WINOF4_G[i][0] * g[0 * 3 + x] + WINOF4_G[i][1] * g[1 * 3 + x] + WINOF4_G[i][2] * g[2 * 3 + x];
       for (int i = 0; i < 6; ++i)
         for (int j = 0; j < 6; ++j) u[i][j] = gg[i][0] * WINOF4_G[j][0] + gg[i][1] * WINOF4_G[j][1] + gg[i][2] * WINOF4_G[j][2];
-      const int ct = co / 64, mb = (co % 64) / 16, m = co % 16, ch = ci / 8, kq = (ci % 8) / 2, ks = ci % 2;
+      const int ct = co / CT, mb = (co % CT) / 16, m = co % 16, ch = ci / 8, kq = (ci % 8) / 2, ks = ci % 2;
       for (int i = 0; i < 6; ++i)
         for (int j = 0; j < 6; ++j) {
-          const size_t idx = (((((((((size_t)ct * nch + ch) * 3 + i / 2) * 2 + i % 2) * 3 + j / 2) * 4 + mb) * 4 + kq) * 16 + m) * 2 + ks) * 2 + j % 2;
+          const size_t idx = (((((((((size_t)ct * nch + ch) * 3 + i / 2) * 2 + i % 2) * 3 + j / 2) * nmb + mb) * 4 + kq) * 16 + m) * 2 + ks) * 2 + j % 2;
           dst[idx] = (float)u[i][j];
         }
     }
 }
+void pack_conv_weights_winof4(const float* w, int cout, int cin, float* dst) { pack_winof4(w, cout, cin, dst, CfgF4::CT); }
 
 // The 32-cout instance: one source, cout tiles of 32 (cout a multiple of 32 but not of 64: the UNet's full-resolution 32 -> 32 layers),
 // regions of 16 x 64 px; two chunks for the pipeline's prologue.
@@ -849,83 +767,25 @@ bool conv3x3_winof4_c32_ok(int C0, int C1, int cout, int H, int W) {
   return C1 == 0 && C0 >= 16 && C0 % 8 == 0 && cout > 0 && cout % 32 == 0 && cout % 64 != 0 && H >= 16 && H % 16 == 0 && W >= 64 && W % 64 == 0;
 }
 bool conv3x3_winof4_c32_packs(int cout, int cin) { return conv3x3_winof4_c32_ok(cin, 0, cout, 16, 64); }
+void pack_conv_weights_winof4_c32(const float* w, int cout, int cin, float* dst) { pack_winof4(w, cout, cin, dst, CfgF4C32::CT); }
 
-// ... layout [cout / 32][cin / 8][stage 3][row in stage 2][column pair 3][cout block 2][channel group 4][cout 16][k-step 2][column in pair 2]
-void pack_conv_weights_winof4_c32(const float* w, int cout, int cin, float* dst) {
-  const int nch = cin / 8;
-  for (int co = 0; co < cout; ++co)
-    for (int ci = 0; ci < cin; ++ci) {
-      const float* g = w + ((size_t)co * cin + ci) * 9;
-      double gg[6][3], u[6][6];
-      for (int i = 0; i < 6; ++i)
-        for (int x = 0; x < 3; ++x) gg[i][x] = WINOF4_G[i][0] * g[0 * 3 + x] + WINOF4_G[i][1] * g[1 * 3 + x] + WINOF4_G[i][2] * g[2 * 3 + x];
-      for (int i = 0; i < 6; ++i)
-        for (int j = 0; j < 6; ++j) u[i][j] = gg[i][0] * WINOF4_G[j][0] + gg[i][1] * WINOF4_G[j][1] + gg[i][2] * WINOF4_G[j][2];
-      const int ct = co / 32, mb = (co % 32) / 16, m = co % 16, ch = ci / 8, kq = (ci % 8) / 2, ks = ci % 2;
-      for (int i = 0; i < 6; ++i)
-        for (int j = 0; j < 6; ++j) {
-          const size_t idx = (((((((((size_t)ct * nch + ch) * 3 + i / 2) * 2 + i % 2) * 3 + j / 2) * 2 + mb) * 4 + kq) * 16 + m) * 2 + ks) * 2 + j % 2;
-          dst[idx] = (float)u[i][j];
-        }
-    }
-}
-
-int launch_conv3x3_winof4_c32(const float* u, const float* bias, int cout, const float* in0, int C0, float* out, int B, int H, int W,
-                              hipStream_t s, float slope, float* pool_out) {
-  if (!conv3x3_winof4_c32_ok(C0, 0, cout, H, W)) {
-    set_error("conv3x3_winof4_c32: unsupported geometry (%d -> %d channels, %d x %d)", C0, cout, H, W);
-    return PNPX_ERR_SHAPE;
-  }
-  WinoArgs a{};
-  a.in0 = a.in1 = in0;
-  a.u = u;
-  a.bias = bias;
-  a.pool = pool_out;
-  a.out = out;
-  a.B = B;
-  a.H = H;
-  a.W = W;
-  a.Hp = padded_h(H);
-  a.Wp = padded_w(W);
-  a.C0 = C0;
-  a.Cout = cout;
-  a.slope = slope;
-  a.nct = cout / 32;
-  a.nch = C0 / CfgF4C32::CK;
-  a.nch_all = a.nch;
-  a.ksplit = 1;
-  a.rx = W / 64;
-  a.ry = H / 16;
-  static std::once_flag attr_once[64];
-  int dev = 0;
-  PNPX_HIP(hipGetDevice(&dev));
-  if (dev >= 0 && dev < 64) {
-    hipError_t e = hipSuccess;
-    std::call_once(attr_once[dev], [&] {
-      e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3x3_winof4_c32_f32_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_REQF4);
-    });
-    PNPX_HIP(e);
-  }
-  const long long nreg = (long long)a.rx * a.ry * a.B, ntiles = nreg * a.nct;
-  long long grid = 256;
-  if (grid >= ntiles) grid = ntiles;
-  else if ((grid / 8) % a.nct != 0 && grid >= 8LL * a.nct) grid -= grid % (8 * a.nct);
-  hipLaunchKernelGGL(conv3x3_winof4_c32_f32_kernel, dim3((unsigned)grid), dim3(512), LDS_REQF4, s, a);
-  PNPX_LAUNCH_CHECK();
-  return PNPX_OK;
-}
-
-// ups: in1 is the low-resolution second source (H/2 x W/2) and the kernel up-samples it (launch_conv3x3_winof4_ups)
-static int launch_winof4(const float* u, const float* bias, int cout, const float* in0, int C0, const float* in1, int C1, float* out, int B,
-                         int H, int W, hipStream_t s, float slope, float* pool_out, bool ups) {
-  const bool two = C1 != 0;
-  if (!(ups ? conv3x3_winof4_ups_ok(C0, C1, cout, H, W) : two ? conv3x3_winof4_entry_ok(C0, C1, cout, H, W) : conv3x3_winof4_ok(C0, 0, cout, H, W))) {
-    set_error("conv3x3_winof4: unsupported geometry (%d + %d -> %d channels, %d x %d)", C0, C1, cout, H, W);
+// One launch path for the four instances.  ups: in1 is the low-resolution second source (H/2 x W/2) and the kernel up-samples it
+// (launch_conv3x3_winof4_ups); c32: the 32-cout kernel (one source).
+enum class F4Inst { PLAIN, ENTRY, UPS, C32 };
+static int launch_winof4(F4Inst inst, const float* u, const float* bias, int cout, const float* in0, int C0, const float* in1, int C1, float* out,
+                         int B, int H, int W, hipStream_t s, float slope, float* pool_out) {
+  const bool c32 = inst == F4Inst::C32, ups = inst == F4Inst::UPS;
+  const bool ok = c32 ? conv3x3_winof4_c32_ok(C0, C1, cout, H, W)
+                  : ups ? conv3x3_winof4_ups_ok(C0, C1, cout, H, W)
+                        : inst == F4Inst::ENTRY ? conv3x3_winof4_entry_ok(C0, C1, cout, H, W) : conv3x3_winof4_ok(C0, C1, cout, H, W);
+  if (!ok) {
+    if (c32) set_error("conv3x3_winof4_c32: unsupported geometry (%d -> %d channels, %d x %d)", C0, cout, H, W);
+    else set_error("conv3x3_winof4: unsupported geometry (%d + %d -> %d channels, %d x %d)", C0, C1, cout, H, W);
     return PNPX_ERR_SHAPE;
   }
   WinoArgs a{};
   a.in0 = in0;
-  a.in1 = two ? in1 : in0;
+  a.in1 = C1 != 0 ? in1 : in0;
   a.u = u;
   a.bias = bias;
   a.pool = pool_out;
@@ -939,11 +799,11 @@ static int launch_winof4(const float* u, const float* bias, int cout, const floa
   a.C1 = C1;
   a.Cout = cout;
   a.slope = slope;
-  a.nct = cout / 64;
+  a.nct = cout / (c32 ? CfgF4C32::CT : CfgF4::CT);
   a.nch = (C0 + C1) / CfgF4::CK;
   a.nch_all = a.nch;
   a.ksplit = 1;
-  a.rx = W / 32;
+  a.rx = W / (c32 ? CfgF4C32::RW : CfgF4::RW);
   a.ry = H / 16;
   if (ups) {
     a.ups_h = H / 2;
@@ -952,17 +812,17 @@ static int launch_winof4(const float* u, const float* bias, int cout, const floa
     a.ups_sy = (float)(H / 2 - 1) / (float)(H - 1);
     a.ups_sx = (float)(W / 2 - 1) / (float)(W - 1);
   }
+  using Kernel = void (*)(WinoArgs);
+  static const Kernel kernels[4] = {conv3x3_winof4_f32_kernel<false>, conv3x3_winof4_f32_kernel<true>, conv3x3_winof4_f32_kernel<true, true>,
+                                    conv3x3_winof4_c32_f32_kernel};      // in F4Inst's order
   static std::once_flag attr_once[64];
   int dev = 0;
   PNPX_HIP(hipGetDevice(&dev));
   if (dev >= 0 && dev < 64) {
     hipError_t e = hipSuccess;
     std::call_once(attr_once[dev], [&] {
-      e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3x3_winof4_f32_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_REQF4);
-      if (e == hipSuccess)
-        e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3x3_winof4_f32_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_REQF4);
-      if (e == hipSuccess)
-        e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3x3_winof4_f32_kernel<true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_REQF4);
+      for (int i = 0; i < 4 && e == hipSuccess; ++i)
+        e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernels[i]), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_REQF4);
     });
     PNPX_HIP(e);
   }
@@ -970,20 +830,22 @@ static int launch_winof4(const float* u, const float* bias, int cout, const floa
   long long grid = 256;
   if (grid >= ntiles) grid = ntiles;
   else if ((grid / 8) % a.nct != 0 && grid >= 8LL * a.nct) grid -= grid % (8 * a.nct);
-  if (ups) hipLaunchKernelGGL((conv3x3_winof4_f32_kernel<true, true>), dim3((unsigned)grid), dim3(512), LDS_REQF4, s, a);
-  else if (two) hipLaunchKernelGGL(conv3x3_winof4_f32_kernel<true>, dim3((unsigned)grid), dim3(512), LDS_REQF4, s, a);
-  else hipLaunchKernelGGL(conv3x3_winof4_f32_kernel<false>, dim3((unsigned)grid), dim3(512), LDS_REQF4, s, a);
+  hipLaunchKernelGGL(kernels[(int)inst], dim3((unsigned)grid), dim3(512), LDS_REQF4, s, a);
   PNPX_LAUNCH_CHECK();
   return PNPX_OK;
 }
 
 int launch_conv3x3_winof4(const float* u, const float* bias, int cout, const float* in0, int C0, const float* in1, int C1, float* out, int B,
                           int H, int W, hipStream_t s, float slope, float* pool_out) {
-  return launch_winof4(u, bias, cout, in0, C0, in1, C1, out, B, H, W, s, slope, pool_out, false);
+  return launch_winof4(C1 != 0 ? F4Inst::ENTRY : F4Inst::PLAIN, u, bias, cout, in0, C0, in1, C1, out, B, H, W, s, slope, pool_out);
 }
 int launch_conv3x3_winof4_ups(const float* u, const float* bias, int cout, const float* in0, int C0, const float* in1_lowres, int C1,
                               float* out, int B, int H, int W, hipStream_t s, float slope) {
-  return launch_winof4(u, bias, cout, in0, C0, in1_lowres, C1, out, B, H, W, s, slope, nullptr, true);
+  return launch_winof4(F4Inst::UPS, u, bias, cout, in0, C0, in1_lowres, C1, out, B, H, W, s, slope, nullptr);
+}
+int launch_conv3x3_winof4_c32(const float* u, const float* bias, int cout, const float* in0, int C0, float* out, int B, int H, int W,
+                              hipStream_t s, float slope, float* pool_out) {
+  return launch_winof4(F4Inst::C32, u, bias, cout, in0, C0, nullptr, 0, out, B, H, W, s, slope, pool_out);
 }
 
 }  // namespace pnpx
