@@ -722,6 +722,43 @@ int pnpx_conv3x3_probe_plan(int kind, int C0, int C1, int cout, int H, int W, in
  * src [planes][h + 2][w + 8] -> the interior of dst [planes][2h + 2][2w + 8] (its border cells are not written).  Asynchronous on `stream`. */
 int pnpx_upsample2x_probe(pnpx_ctx* ctx, const float* src, float* dst, int planes, int h, int w, void* stream);
 
+/* Single-layer probe of the half-split convolution launcher (csrc/conv_hs_probe.hip), for tests: one layer's HOST weights are packed by
+ * the library's own pack_conv_weights_hs / pack_conv_weights_hs_taps for the tile conv_hs_mt gives, uploaded with the alignment and slack
+ * of pnpx_unet_load / pack_layer, and ONE launch_conv_hs call runs on DEVICE tensors the caller laid out.  The call waits for its launch
+ * and frees what it allocated.  Nothing in the library calls it; it adds no option and reads no state of the context but its device.
+ *   HS8 tensors: [B][C/8][H + 2][W + 2] records of 32 bytes = hi[8] f16 | lo[8] f16 with hi = f16(16 v), lo = f16(16 v - hi), zero border.
+ *   w [cout][cin][9] with cin <= 8 (G0 + G1) < cin + 16 (K is zero-padded to a multiple of 16); bias [cout] (null = zeros: the gradient
+ *   epilogues read none).  in0 carries in0_groups >= G0 groups per image (0 = G0) of which the layer reads the first G0; in1 carries G1
+ *   groups, at (ups_h, ups_w) = (H/2, W/2) when those are set.  out / res / dmask: cout/8 groups (res: res_groups when set, critic_epi 2
+ *   only); pool_out [B][cout/8][H/2 + 2][W/2 + 2].  outc_w [32], outc_b [1], first_w [32][2][9], first_b [32] are HOST arrays; x_in,
+ *   out_img, out_pre, first_x [B][H][W] and first_sigma [B * first_sigma_stride] are fp32 DEVICE arrays.
+ *   Every other field is the ConvHsFuse field of the same name (csrc/conv_hs.h); want_range_flag hands the kernel a cleared range-guard
+ *   word whose value after the launch comes back in *range_flag_out.
+ * An operand the selected path has no place for (pool_out where no pool is fused, res beside dmask, x_in without outc_w, in1 with G1 = 0,
+ * ...) is refused with PNPX_ERR_ARG, never dropped; what launch_conv_hs itself refuses returns its status and message, nothing launched.
+ * pnpx_conv_hs_probe_plan (host only, no context, dereferences no pointer of the descriptor: non-null = operand present) reports what
+ * that call would launch at (B, H, W), as launch_conv_hs / launch_hs_cfg themselves decide it:
+ *   out[0..7] = the conv_hs_kernel instance MT, NBW, MBW, NW, EPI, UPS, WREG, TAPS; out[8] = cout tile of the weight packing; out[9] =
+ *   grid size; out[10] = tiles; out[11] = plain_walk.  Returns 1, or 0 (out zeroed) when the probe or the launcher refuses. */
+typedef struct pnpx_conv_hs_probe_desc {
+  const float *w, *bias, *outc_w, *outc_b, *first_w, *first_b;                 /* host */
+  const void *in0, *in1, *res, *dmask;                                         /* device, HS8 */
+  void *out, *pool_out;                                                        /* device, HS8 */
+  const float *x_in, *first_x, *first_sigma;                                   /* device, fp32 */
+  float *out_img, *out_pre;                                                    /* device, fp32 */
+  int cin, cout, G0, G1, B, H, W;
+  float slope;
+  int taps, in0_groups, wreg, share, ups_h, ups_w, critic_epi;
+  float alpha;
+  int res_groups, first_sigma_stride;
+  float first_slope;
+  int want_range_flag;
+  unsigned* range_flag_out;                                                    /* host, may be null */
+} pnpx_conv_hs_probe_desc;
+enum { PNPX_CONV_HS_PLAN_INTS = 12 };
+int pnpx_conv_hs_probe(pnpx_ctx* ctx, const pnpx_conv_hs_probe_desc* desc, void* stream);
+int pnpx_conv_hs_probe_plan(const pnpx_conv_hs_probe_desc* desc, int B, int H, int W, int* out);
+
 /* Host-only, for tests: which kernel a UNet decoder entry of conv_mode 0 gets (csrc/conv_f32_select.hip, conv_f32_entry) for a set of
  * options, a geometry (second source C1 > 0 at H/2 x W/2, output H x W) and the batch of the whole call.
  * opts: bit 0 "fp32_winograd", bit 1 the layer's "fp32_wino8_layers" bit, bit 2 its "fp32_winof4_layers" bit, bit 3 its

@@ -26,6 +26,17 @@ class PnpxError(RuntimeError):
 PNPX_ERR_RANGE = 6      # include/pnpx.h: half-split range guard tripped (pnpx_ctx_status)
 
 
+class ConvHsProbeDesc(C.Structure):
+    """include/pnpx.h: pnpx_conv_hs_probe_desc (field for field)."""
+    _fields_ = ([(n, c_void_p) for n in ("w", "bias", "outc_w", "outc_b", "first_w", "first_b", "in0", "in1", "res", "dmask", "out", "pool_out",
+                                         "x_in", "first_x", "first_sigma", "out_img", "out_pre")] +
+                [(n, C.c_int) for n in ("cin", "cout", "G0", "G1", "B", "H", "W")] + [("slope", C.c_float)] +
+                [(n, C.c_int) for n in ("taps", "in0_groups", "wreg", "share", "ups_h", "ups_w", "critic_epi")] + [("alpha", C.c_float)] +
+                [("res_groups", C.c_int), ("first_sigma_stride", C.c_int), ("first_slope", C.c_float), ("want_range_flag", C.c_int),
+                 ("range_flag_out", C.POINTER(C.c_uint))])
+PNPX_CONV_HS_PLAN_INTS = 12
+
+
 # name -> (restype, argtypes); mirrors include/pnpx.h one to one
 _P = c_void_p  # device pointers travel as integers
 _SIGNATURES = {
@@ -155,6 +166,8 @@ _SIGNATURES = {
     "pnpx_conv_f32_entry_plan": (C.c_int, [C.c_int] * 9),
     "pnpx_conv_f32_forward_plan": (C.c_int, [C.c_int] * 9),
     "pnpx_winof4_c32_pack": (C.c_int, [c_void_p, C.c_int, C.c_int, c_void_p]),
+    "pnpx_conv_hs_probe": (C.c_int, [c_void_p, c_void_p, c_void_p]),
+    "pnpx_conv_hs_probe_plan": (C.c_int, [c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int)]),
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 

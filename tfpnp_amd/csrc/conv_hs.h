@@ -140,4 +140,20 @@ bool conv_hs_can_pool(int H, int W);
 int launch_conv_hs(const ConvLayerHs& L, const char* in0, int G0, const char* in1, int G1, char* out, int B, int H,
                    int W, const ConvHsFuse& fuse, hipStream_t s);
 
+// Host-side record of what launch_conv_hs decided (conv_hs_probe.hip, for tests): while a sink is installed on the calling thread,
+// launch_hs_cfg writes the instance, the packing's tile and the grid it is about to launch into it; with plan_only it then returns
+// before it touches the device (no attribute call, no launch).  No sink (every caller but the probe): one null test per launch.
+struct HsPlan {
+  int mt = 0, nbw = 0, mbw = 0, nw = 0, epi = 0, ups = 0, wreg = 0, taps = 0;   // the conv_hs_kernel instance
+  int w_mt = 0;              // cout tile of the weight packing (64 under a 32-cout instance: half tiles)
+  int grid = 0, plain_walk = 0;
+  long long ntiles = 0;
+};
+struct HsPlanSink {
+  HsPlan plan;
+  bool plan_only = false;
+  bool filled = false;
+};
+HsPlanSink*& hs_plan_sink();   // this thread's sink (null by default)
+
 }  // namespace pnpx

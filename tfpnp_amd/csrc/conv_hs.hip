@@ -31,6 +31,11 @@ namespace pnpx {
 
 bool conv_hs_can_pool(int H, int W) { return W >= 32 && (W % 2) == 0 && (H % 2) == 0; }
 
+HsPlanSink*& hs_plan_sink() {
+  static thread_local HsPlanSink* sink = nullptr;
+  return sink;
+}
+
 #ifdef PNPX_TUNING
 // Tuning builds only (libpnpx_tune.so, `make tuning`): PNPX_HS_<MT>_<W>="nbw,nw" overrides the launch table.
 static bool tuning_override(int mt, int W, HsChoice* c) {

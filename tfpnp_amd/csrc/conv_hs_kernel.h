@@ -556,7 +556,10 @@ __global__ __launch_bounds__((NW + HS_UPS_WAVES * UPS) * 64,
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
               const float t = __builtin_fmaf(acc[m][n][q * 4 + j], c16, bias[q * 4 + j]) + ((float)rh[j] + (float)rl[j]);
-              v[n][q * 4 + j] = __builtin_fmaxf(t, a16);
+              // (fmaxf returns its other operand for a NaN: select it back, so that a NaN is stored -- and raises the range flag -- as
+              // under every other epilogue, instead of leaving the layer as the threshold)
+              const float mx = __builtin_fmaxf(t, a16);
+              v[n][q * 4 + j] = (t != t) ? t : mx;
             }
           }
         }
@@ -976,7 +979,9 @@ static int launch_hs_cfg(const ConvHsArgs& a0, int B, hipStream_t s) {
   using G = HsGeom<MT, NBW, MBW, NW, WREG, TAPS>;
   constexpr int LDS_REQ = UPS ? G::LDS_USED + 3 * HsUpsGeom<MBW, NW * NBW>::BYTES : G::LDS_BYTES;   // UPS: window pool behind the used part
   static_assert(G::LDS_USED + UPS * 3 * HsUpsGeom<MBW, NW * NBW>::BYTES <= 160 * 1024, "no LDS room for the low-resolution windows");
-  PNPX_TRY(ensure_dyn_lds(reinterpret_cast<const void*>(&conv_hs_kernel<MT, NBW, MBW, NW, EPI, UPS, WREG, TAPS>), LDS_REQ));
+  HsPlanSink* const sink = hs_plan_sink();   // conv_hs_probe.hip only: record the decision; plan_only: touch no device
+  if (!(sink && sink->plan_only))
+    PNPX_TRY(ensure_dyn_lds(reinterpret_cast<const void*>(&conv_hs_kernel<MT, NBW, MBW, NW, EPI, UPS, WREG, TAPS>), LDS_REQ));
   ConvHsArgs a = a0;
   a.tilesX = (a.W + G::TW - 1) / G::TW;
   a.tilesY = (a.H + G::TH - 1) / G::TH;
@@ -1016,6 +1021,13 @@ static int launch_hs_cfg(const ConvHsArgs& a0, int B, hipStream_t s) {
     if (grid >= 8) grid -= grid % 8;          // whole XCD groups (the kernel falls back to a plain walk otherwise)
     const bool grouped = (long long)a.tilesX * a.tilesY * a.B >= 32;
     if (grouped && a.nct > 1 && (grid / 8) % a.nct != 0 && grid >= 8 * a.nct) grid -= grid % (8 * a.nct);
+  }
+  if (sink) {
+    HsPlan& p = sink->plan;
+    p.mt = MT, p.nbw = NBW, p.mbw = MBW, p.nw = NW, p.epi = EPI, p.ups = UPS, p.wreg = WREG, p.taps = TAPS;
+    p.w_mt = a.w_mt, p.grid = (int)grid, p.plain_walk = a.plain_walk, p.ntiles = ntiles;
+    sink->filled = true;
+    if (sink->plan_only) return PNPX_OK;
   }
 #ifdef PNPX_TUNING   // PNPX_HS_WGT=<file>: per-workgroup start / end stamps of every launch (tools/wg_spread.py)
   static unsigned long long* wbuf = nullptr;
