@@ -759,6 +759,51 @@ enum { PNPX_CONV_HS_PLAN_INTS = 12 };
 int pnpx_conv_hs_probe(pnpx_ctx* ctx, const pnpx_conv_hs_probe_desc* desc, void* stream);
 int pnpx_conv_hs_probe_plan(const pnpx_conv_hs_probe_desc* desc, int B, int H, int W, int* out);
 
+/* Probe of the launches between the UNet VJP's adjoint convolutions (csrc/vjp_glue_probe.hip; kernels and launchers: csrc/unet_bwd.hip,
+ * csrc/grad_common.h), for tests: ONE call of the launcher pnpx_unet_denoise_backward itself uses, on DEVICE tensors the caller laid out,
+ * and a wait for it.  Nothing in the library calls it; it adds no option and reads no state of the context but its device.
+ *   family 0: padded planar fp32 [B][C][H + 2][W + 8] (see pnpx_conv3x3_probe); family 1: HS8 records [B][C/8][H + 2][W + 2] (see
+ *   pnpx_conv_hs_probe; C, Ccat and c_off multiples of 8).  Plain images are fp32 [B][H][W].  Outputs: interiors only, borders untouched.
+ *   OUTC_BWD (C = 32): g = g_out [B][H][W], pre [B][H][W], w [32] (device), act = the saved activation, sc (family 1) ->
+ *     out = w[c] g 1[0 <= pre <= 1] LeakyReLU'(act) (family 1: g_out times sc[0] first), out_res [B][H][W] = the masked g.
+ *   UPSAMPLE_BWD: the adjoint of the bilinear x2 (align_corners) up-sampling of an H x W source into channels [c_off, c_off + C) of a
+ *     concat gradient g [B][Ccat][Ht][Wt], 2H <= Ht <= 2H + 1, 2W <= Wt <= 2W + 1; out [B][C][H][W] = the adjoint times
+ *     LeakyReLU'(act).  family 0 forms: 1 = one thread per source pixel, 2 = LDS window of 16 x 16 source pixels, 3 = of 16 x 64; auto
+ *     takes 3 at W >= 64, else 2, and 1 when B * C > 65535 (forms 2 and 3 put a plane on gridDim.z and refuse that).  family 1 has one
+ *     form; B * C/8 > 65535 runs as consecutive launches over whole images of at most 65535 / (C/8) images each (the VJP does the same),
+ *     so no geometry of the denoiser is refused and no launch exceeds the grid limit.
+ *   SKIP_POOL_MERGE: out [B][C][H][W] = (g [B][Ccat][H][W] channels [0, C) + the 2 x 2 max-pool routing of g_pool [B][C][H/2][W/2], null =
+ *     none, to the first maximum of act in scan order) LeakyReLU'(act).  family 0 forms: 1 = one thread per pixel, 2 = one per 2 x 2
+ *     block (even H and W only: auto takes it there).
+ *   INPUT_GRAD: g = the gradient of the first convolution's input [B][C][H][W] (family 1: C = 32), g_res [B][H][W], sc (family 1) ->
+ *     out [B][H][W] = g[:, 0] + g_res, part [B][64] = the partial sums of g[:, 1] over 64 pixel ranges, gsigma [B] = their sums
+ *     (family 1: all times sc[1]).
+ *   GRAD_SCALE (family 1): g = B * H * W floats -> bits = the bit pattern of max |g|, out = float2 {1 / m, m}, m = the power of two
+ *     above max |g| ({0, 0} for all zeros, {1, 1} when a value is infinite; a NaN is dropped by the maximum, so it leaves the scale of
+ *     the other values; a denormal maximum: m = 2^-126).
+ * LeakyReLU' is 1 where act > 0, else 0.2 (so 0.2 at +0 and -0).  An operand the op has no place for, or a missing one, is refused with
+ * PNPX_ERR_ARG; a size or a form the op cannot run with PNPX_ERR_SHAPE; nothing is launched then.
+ * pnpx_vjp_glue_probe_plan (host only, no context, reads the sizes only): 0 when refused, else the form the call runs (form = 0: the
+ * one the VJP dispatches) + 256 x (launches of the kernel - 1). */
+enum pnpx_vjp_glue_op {
+  PNPX_VJP_OUTC_BWD = 0,
+  PNPX_VJP_UPSAMPLE_BWD = 1,
+  PNPX_VJP_SKIP_POOL_MERGE = 2,
+  PNPX_VJP_INPUT_GRAD = 3,
+  PNPX_VJP_GRAD_SCALE = 4
+};
+typedef struct pnpx_vjp_glue_probe_desc {
+  int op, family, form;
+  int B, C, H, W, Ccat, c_off, Ht, Wt;
+  const void *g, *act, *g_pool;          /* device: incoming gradient, saved activation, pooled gradient */
+  const float *pre, *w, *g_res, *sc;     /* device, fp32 */
+  void* out;                             /* device */
+  float *out_res, *part, *gsigma;        /* device, fp32 */
+  unsigned* bits;                        /* device */
+} pnpx_vjp_glue_probe_desc;
+int pnpx_vjp_glue_probe(pnpx_ctx* ctx, const pnpx_vjp_glue_probe_desc* desc, void* stream);
+int pnpx_vjp_glue_probe_plan(const pnpx_vjp_glue_probe_desc* desc);
+
 /* Host-only, for tests: which kernel a UNet decoder entry of conv_mode 0 gets (csrc/conv_f32_select.hip, conv_f32_entry) for a set of
  * options, a geometry (second source C1 > 0 at H/2 x W/2, output H x W) and the batch of the whole call.
  * opts: bit 0 "fp32_winograd", bit 1 the layer's "fp32_wino8_layers" bit, bit 2 its "fp32_winof4_layers" bit, bit 3 its

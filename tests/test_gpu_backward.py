@@ -135,6 +135,46 @@ def test_denoiser_vjp_is_linear_and_batch_independent(den):
     assert torch.equal(den(g(x), g(s)), ref)
 
 
+def test_denoiser_vjp_at_65536_upsampling_planes(den):
+    """The one-thread-per-pixel fallback of the fp32 up-sampling adjoint (more than 65535 planes for gridDim.z) on the public path.  The
+    adjoint from the 1 x 1 bottom level of a 16 x 16 call has 512 planes per image, and the fp32 family decides PER LAUNCH CHAIN: under
+    the default options (fp32_chains = 2) a B = 128 call is two chains of 64 images, 32768 planes, and stays on the LDS-window form.  So
+    the fp32 family runs B = 128 as one chain (fp32_chains = 1, restored afterwards: 65536 planes) and B = 256 under the default options
+    (two chains of 128 images: 65536 planes each).  The half-split family runs B = 128 (8192 groups, one launch).  The first, a middle
+    and the last image of each call against the same images of B = 2 calls, under the batch-independence bars of the test above."""
+    from tests import vjp_glue_cases as VG
+    from tfpnp_amd import ops
+    ctx = den.context(dev())
+    fp32 = ctx.get_option("conv_mode") == 0
+    chains = ctx.get_option("fp32_chains")
+
+    def forms(B, n):      # per chain: the form of the bottom level's adjoint, asked of the library with the batch the chain is handed
+        C, h, w, Cc, co, Ht, Wt = VG.vjp_levels(16, 16)[3]
+        return [VG.plan(VG.UPSAMPLE_BWD, 0, B=b, C=C, H=h, W=w, Ccat=Cc, c_off=co, Ht=Ht, Wt=Wt)[0] for b in VG.fp32_chain_batches(B, n)]
+
+    def leg(B, seed):
+        x, s = denoiser_inputs(B, 16, 16, seed)
+        g1 = np.random.RandomState(seed).standard_normal((B, 1, 16, 16)).astype(np.float32)
+        a, sa = ops.unet_denoise_backward(ctx, g(x), g(s), g(g1))
+        assert bool(torch.isfinite(a).all()) and bool(torch.isfinite(sa).all())
+        for pair in ([0, B // 2], [B // 2, B - 1]):
+            two, stwo = ops.unet_denoise_backward(ctx, g(x[pair]), g(s[pair]), g(g1[pair]))
+            for j, i in enumerate(pair):
+                assert rel(two[j:j + 1], a[i:i + 1]) < 2e-6 and rel(stwo[j:j + 1], sa[i:i + 1]) < 1e-4, (B, i)
+
+    if not fp32:
+        leg(128, 67)
+        return
+    assert chains == 2 and forms(128, chains) == [VG.UPS_LDS16] * 2            # the default options do not reach the fallback at B = 128
+    assert forms(128, 1) == [VG.UPS_PLAIN] and forms(256, chains) == [VG.UPS_PLAIN] * 2
+    ctx.set_option("fp32_chains", 1)
+    try:
+        leg(128, 67)
+    finally:
+        ctx.set_option("fp32_chains", chains)
+    leg(256, 68)
+
+
 def _check(names, got, want64, want32, floor=2e-2):   # floor: see test_denoiser_vjp_vs_oracle_autograd
     for n, a, b64, b32 in zip(names, got, want64, want32):
         e, y = rel(a, b64), rel(b32, b64)

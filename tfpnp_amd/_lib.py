@@ -37,6 +37,12 @@ class ConvHsProbeDesc(C.Structure):
 PNPX_CONV_HS_PLAN_INTS = 12
 
 
+class VjpGlueProbeDesc(C.Structure):
+    """include/pnpx.h: pnpx_vjp_glue_probe_desc (field for field)."""
+    _fields_ = ([(n, C.c_int) for n in ("op", "family", "form", "B", "C", "H", "W", "Ccat", "c_off", "Ht", "Wt")] +
+                [(n, c_void_p) for n in ("g", "act", "g_pool", "pre", "w", "g_res", "sc", "out", "out_res", "part", "gsigma", "bits")])
+
+
 # name -> (restype, argtypes); mirrors include/pnpx.h one to one
 _P = c_void_p  # device pointers travel as integers
 _SIGNATURES = {
@@ -168,6 +174,8 @@ _SIGNATURES = {
     "pnpx_winof4_c32_pack": (C.c_int, [c_void_p, C.c_int, C.c_int, c_void_p]),
     "pnpx_conv_hs_probe": (C.c_int, [c_void_p, c_void_p, c_void_p]),
     "pnpx_conv_hs_probe_plan": (C.c_int, [c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int)]),
+    "pnpx_vjp_glue_probe": (C.c_int, [c_void_p, c_void_p, c_void_p]),
+    "pnpx_vjp_glue_probe_plan": (C.c_int, [c_void_p]),
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 

@@ -81,7 +81,7 @@ __global__ __launch_bounds__(256) void upsample_bwd_kernel(const float* __restri
   const int H = 2 * h, W = 2 * w;
   const int Hp = padded_h(Ht), Wp = padded_w(Wt), hp = padded_h(h), wp = padded_w(w);
   const float* g = gcat + (b * Ccat + c_off + c) * (size_t)Hp * Wp;
-  // candidate destination rows/cols: those whose floor(s*dst) is ys-1 or ys  (s ~ 0.5 => at most 5 candidates)
+  // candidate destination rows/cols: those whose floor(s*dst) is ys-1 or ys  (s ~ 0.5: the window 2*ys-3 .. 2*ys+3 holds them, 7 candidates)
   const int ylo = max(0, 2 * ys - 3), yhi = min(H - 1, 2 * ys + 3);
   const int xlo = max(0, 2 * xs - 3), xhi = min(W - 1, 2 * xs + 3);
   float acc = 0.f;
@@ -298,6 +298,14 @@ __global__ __launch_bounds__(256) void input_grad_kernel(const float* __restrict
 // (conv_hs.hip, LeakyReLU' from the saved activation's sign in its epilogue).  f16 has a narrow exponent range, so the
 // whole backward pass runs on grad_out / m with m = the power of two >= max|grad_out| and the two results are
 // multiplied by m at the end (exact: power-of-two scaling commutes with every linear step).  One thread per record.
+// The last product before hs_pack goes through rounded_f32 in all three kernels: left to the compiler it was fused into hs_pack's
+// conversions twice, differently -- the stored hi = f16(fp32(a * b)), but lo = f16(a * b - f16(a * b)) from the UNROUNDED product
+// (v_fma_mixlo_f16; __fmul_rn does not stop that fold) -- so where fp32(a * b) fell on an f16 tie the record was one hi-ulp (2^-11
+// relative) off, about one element in 8192 (found by tests/test_gpu_vjp_glue.py::test_upsample_adjoint, half-split cases).
+__device__ __forceinline__ float rounded_f32(float x) {
+  asm("" : "+v"(x));      // the fp32 value itself, in a register: nothing upstream can be fused into what is computed from it
+  return x;
+}
 __global__ __launch_bounds__(256) void outc_bwd_hs_kernel(const float* __restrict__ g_out, const float* __restrict__ pre,
                                                           const float* __restrict__ w, const HsRec* __restrict__ feat,
                                                           HsRec* __restrict__ g_feat, float* __restrict__ g_res,
@@ -317,7 +325,7 @@ __global__ __launch_bounds__(256) void outc_bwd_hs_kernel(const float* __restric
   float f[8], o[8];
   hs_unpack(feat[r], f);
 #pragma unroll
-  for (int k = 0; k < 8; ++k) o[k] = w[g * 8 + k] * gn * dlrelu(f[k]) * HS_ASCALE;
+  for (int k = 0; k < 8; ++k) o[k] = rounded_f32(w[g * 8 + k] * gn * dlrelu(f[k]) * HS_ASCALE);
   g_feat[r] = hs_pack(o);
 }
 
@@ -402,7 +410,7 @@ __global__ __launch_bounds__(256) void upsample_bwd_hs_kernel(const HsRec* __res
   float a[8];
   hs_unpack(src_act[r], a);
 #pragma unroll
-  for (int k = 0; k < 8; ++k) acc[k] *= dlrelu(a[k]);
+  for (int k = 0; k < 8; ++k) acc[k] = rounded_f32(acc[k] * dlrelu(a[k]));
   g_src[r] = hs_pack(acc);
 }
 
@@ -451,7 +459,7 @@ __global__ __launch_bounds__(256) void skip_pool_merge_hs_kernel(const HsRec* __
     }
   }
 #pragma unroll
-  for (int k = 0; k < 8; ++k) gv[k] *= dlrelu(a[k]);
+  for (int k = 0; k < 8; ++k) gv[k] = rounded_f32(gv[k] * dlrelu(a[k]));
   g_x[r] = hs_pack(gv);
 }
 
@@ -489,6 +497,115 @@ GradPlan make_grad_plan(int mode, int capB, int H, int W) {
 }
 
 }  // namespace
+
+// ------------------------------------------------------------------------------------ launchers (declared in grad_common.h)
+int launch_outc_bwd_f32(const float* g_out, const float* pre, const float* w, const float* feat, float* g_feat, float* g_res, int B, int H,
+                        int W, hipStream_t s) {
+  const size_t npix = (size_t)B * H * W;
+  hipLaunchKernelGGL(outc_bwd_kernel, g1(npix), dim3(256), 0, s, g_out, pre, w, SavedAct{feat, 0}, g_feat, g_res, H, W, npix);
+  PNPX_LAUNCH_CHECK();
+  return PNPX_OK;
+}
+
+int launch_outc_bwd_hs(const float* g_out, const float* pre, const float* w, const HsRec* feat, HsRec* g_feat, float* g_res, const float2* sc,
+                       int B, int H, int W, hipStream_t s) {
+  const size_t n = (size_t)B * H * W * 4;      // one thread per record: 4 groups of 8 channels per pixel
+  hipLaunchKernelGGL(outc_bwd_hs_kernel, g1(n), dim3(256), 0, s, g_out, pre, w, feat, g_feat, g_res, sc, H, W, n);
+  PNPX_LAUNCH_CHECK();
+  return PNPX_OK;
+}
+
+int launch_upsample_bwd_f32(int form, const float* gcat, int Ccat, int c_off, const float* src_act, float* g_src, int B, int C, int h, int w,
+                            int Ht, int Wt, hipStream_t s) {
+  if (form == VG_AUTO) form = upsample_bwd_form_f32((size_t)B, C, w);
+  if (!upsample_bwd_form_runs(form, (size_t)B, C)) {
+    set_error("up-sampling adjoint: form %d cannot run %d x %d planes (the LDS-window forms take at most %zu)", form, B, C, VG_GRID_Z_MAX);
+    return PNPX_ERR_SHAPE;
+  }
+  const float sy = upsample2x_scale(h), sx = upsample2x_scale(w);
+  if (form == VG_UPS_LDS64) {        // r6: LDS-window forms (bit-identical; fp32 planar activations)
+    hipLaunchKernelGGL(upsample_bwd_lds_kernel<64>, dim3((w + 63) / 64, (h + UBF_T - 1) / UBF_T, (unsigned)(B * C)), dim3(256), 0, s, gcat, Ccat,
+                       c_off, src_act, g_src, C, h, w, Ht, Wt, sy, sx);
+  } else if (form == VG_UPS_LDS16) {
+    hipLaunchKernelGGL(upsample_bwd_lds_kernel<16>, dim3((w + 15) / 16, (h + UBF_T - 1) / UBF_T, (unsigned)(B * C)), dim3(256), 0, s, gcat, Ccat,
+                       c_off, src_act, g_src, C, h, w, Ht, Wt, sy, sx);
+  } else {
+    const size_t n = (size_t)B * C * h * w;
+    hipLaunchKernelGGL(upsample_bwd_kernel, g1(n), dim3(256), 0, s, gcat, Ccat, c_off, SavedAct{src_act, 0}, g_src, C, h, w, Ht, Wt, sy, sx, n);
+  }
+  PNPX_LAUNCH_CHECK();
+  return PNPX_OK;
+}
+
+int launch_upsample_bwd_hs(const HsRec* gcat, int Gcat, int g_off, const HsRec* src_act, HsRec* g_src, int B, int Gs, int h, int w, int Ht,
+                           int Wt, hipStream_t s) {
+  const int per = upsample_bwd_hs_images_per_launch(Gs);
+  if (per <= 0) {
+    set_error("up-sampling adjoint (half-split): %d channel groups per image exceed the %zu planes of one launch", Gs, VG_GRID_Z_MAX);
+    return PNPX_ERR_SHAPE;
+  }
+  const float sy = upsample2x_scale(h), sx = upsample2x_scale(w);
+  // B * Gs above gridDim.z's limit: consecutive launches over whole images (the kernel numbers images from its own pointers)
+  for (int b0 = 0; b0 < B; b0 += per) {
+    const int nb = B - b0 < per ? B - b0 : per;
+    hipLaunchKernelGGL(upsample_bwd_hs_kernel, dim3((w + UB_T - 1) / UB_T, (h + UB_T - 1) / UB_T, (unsigned)(nb * Gs)), dim3(256), 0, s,
+                       gcat + (size_t)b0 * Gcat * (Ht + 2) * (Wt + 2), Gcat, g_off, src_act + (size_t)b0 * Gs * (h + 2) * (w + 2),
+                       g_src + (size_t)b0 * Gs * (h + 2) * (w + 2), Gs, h, w, Ht, Wt, sy, sx);
+    PNPX_LAUNCH_CHECK();
+  }
+  return PNPX_OK;
+}
+
+int launch_skip_pool_merge_f32(int form, const float* gcat, int Ccat, const float* g_pool, const float* xact, float* g_x, int B, int C, int H,
+                               int W, hipStream_t s) {
+  if (form == VG_AUTO) form = skip_pool_merge_form_f32(H, W);
+  if (!skip_pool_merge_form_runs(form, H, W)) {
+    set_error("skip / pool merge: form %d cannot run %d x %d (the 2 x 2-block form needs even sizes)", form, H, W);
+    return PNPX_ERR_SHAPE;
+  }
+  const size_t n = (size_t)B * C * H * W;
+  if (form == VG_SPM_BLOCK)          // r6: one thread per max-pool window (bit-identical)
+    hipLaunchKernelGGL(skip_pool_merge_f32_kernel, g1(n / 4), dim3(256), 0, s, gcat, Ccat, g_pool, xact, g_x, C, H, W, n / 4);
+  else
+    hipLaunchKernelGGL(skip_pool_merge_kernel, g1(n), dim3(256), 0, s, gcat, Ccat, g_pool, SavedAct{xact, 0}, g_x, C, H, W, n);
+  PNPX_LAUNCH_CHECK();
+  return PNPX_OK;
+}
+
+int launch_skip_pool_merge_hs(const HsRec* gcat, int Gcat, const HsRec* g_pool, const HsRec* xact, HsRec* g_x, int B, int G, int H, int W,
+                              hipStream_t s) {
+  const size_t n = (size_t)B * G * H * W;
+  hipLaunchKernelGGL(skip_pool_merge_hs_kernel, g1(n), dim3(256), 0, s, gcat, Gcat, g_pool, xact, g_x, G, H, W, n);
+  PNPX_LAUNCH_CHECK();
+  return PNPX_OK;
+}
+
+int launch_input_grad_f32(const float* g_in0, int Cg, const float* g_res, float* gx, float* part, float* gsigma, int B, int H, int W,
+                          hipStream_t s) {
+  hipLaunchKernelGGL(input_grad_kernel, dim3(SIG_CHUNKS, B), dim3(256), 0, s, g_in0, Cg, g_res, gx, part, H, W);
+  PNPX_LAUNCH_CHECK();
+  hipLaunchKernelGGL(sigma_grad_final_kernel, dim3((B + 63) / 64), dim3(64), 0, s, part, gsigma, B);
+  PNPX_LAUNCH_CHECK();
+  return PNPX_OK;
+}
+
+int launch_input_grad_hs(const HsRec* g_in0, const float* g_res, float* gx, float* part, const float2* sc, float* gsigma, int B, int H, int W,
+                         hipStream_t s) {
+  hipLaunchKernelGGL(input_grad_hs_kernel, dim3(SIG_CHUNKS, B), dim3(256), 0, s, g_in0, g_res, gx, part, sc, H, W);
+  PNPX_LAUNCH_CHECK();
+  hipLaunchKernelGGL(sigma_grad_final_kernel, dim3((B + 63) / 64), dim3(64), 0, s, part, gsigma, B);
+  PNPX_LAUNCH_CHECK();
+  return PNPX_OK;
+}
+
+int launch_grad_scale(const float* g, size_t n, unsigned* bits, float2* sc, hipStream_t s) {
+  PNPX_HIP(hipMemsetAsync(bits, 0, sizeof(unsigned), s));
+  hipLaunchKernelGGL(absmax_kernel, dim3(512), dim3(256), 0, s, g, n, bits);
+  PNPX_LAUNCH_CHECK();
+  hipLaunchKernelGGL(grad_scale_kernel, dim3(1), dim3(1), 0, s, bits, sc);
+  PNPX_LAUNCH_CHECK();
+  return PNPX_OK;
+}
 
 int unet_denoise_backward(pnpx_ctx* ctx, const float* x, const float* sigma, int sigma_stride, const float* grad_out,
                           float* grad_x, float* grad_sigma, int B, int H, int W, hipStream_t s, UNetArena* cached,
@@ -571,19 +688,15 @@ int unet_denoise_backward(pnpx_ctx* ctx, const float* x, const float* sigma, int
 
   if (hs) {
     // ---- half-split backward: HS8 gradients, f16x3 MFMA adjoint convolutions
-    PNPX_HIP(hipMemsetAsync(gmax_bits, 0, sizeof(unsigned), s));
-    hipLaunchKernelGGL(absmax_kernel, dim3(512), dim3(256), 0, s, grad_out, npix, gmax_bits);
-    hipLaunchKernelGGL(grad_scale_kernel, dim3(1), dim3(1), 0, s, gmax_bits, gscale);
+    PNPX_TRY(launch_grad_scale(grad_out, npix, gmax_bits, gscale, s));
     // the adjoint chain over images lo .. lo + B - 1 on stream s: the whole batch, or one of two launch chains (r5: like the forward's,
     // unet.hip launch_chains; the launch table plans for the chain beside it: ConvHsFuse::share).  The gradient scale above is the whole
     // batch's, so per-image results do not depend on the slicing.
     auto run_hs = [&](int lo, int B, hipStream_t s, int share) -> int {
-    const size_t npix = (size_t)B * H * W, px0 = (size_t)lo * H * W;
+    const size_t px0 = (size_t)lo * H * W;
     auto grec = [&](const Act& d) { return reinterpret_cast<HsRec*>(GA + d.off + (size_t)lo * act_bytes_per_image(CONV_HS, d.C, d.H, d.W)); };
     auto frec = [&](const Act& d) { return reinterpret_cast<const HsRec*>(FA + d.off + (size_t)lo * act_bytes_per_image(CONV_HS, d.C, d.H, d.W)); };
-    hipLaunchKernelGGL(outc_bwd_hs_kernel, g1(npix * 4), dim3(256), 0, s, grad_out + px0, pre + px0, ctx->outc_w, frec(F.y[0]),
-                       grec(G.y[0]), g_res + px0, gscale, H, W, npix * 4);
-    PNPX_LAUNCH_CHECK();
+    PNPX_TRY(launch_outc_bwd_hs(grad_out + px0, pre + px0, ctx->outc_w, frec(F.y[0]), grec(G.y[0]), g_res + px0, gscale, B, H, W, s));
     auto convH = [&](int li, const Act& gin, const Act& gout, const Act* saved) -> int {
       const ConvLayerHsDev& D = ctx->conv_hs_bwd[li];
       const ConvLayerHs Lh = hs_layer(D, ctx->zero_bias);
@@ -607,31 +720,19 @@ int unet_denoise_backward(pnpx_ctx* ctx, const float* x, const float* sigma, int
       PNPX_TRY(convH(li, G.a[l], G.cat[l], nullptr));
       const Act& below_f = (l == 3) ? F.x[4] : F.y[l + 1];
       const Act& below_g = (l == 3) ? G.x[4] : G.y[l + 1];
-      const int h = below_f.H, w = below_f.W, Gs = below_f.C / 8;
-      const float sy = (2 * h > 1) ? (float)(h - 1) / (float)(2 * h - 1) : 0.f;
-      const float sx = (2 * w > 1) ? (float)(w - 1) / (float)(2 * w - 1) : 0.f;
-      hipLaunchKernelGGL(upsample_bwd_hs_kernel, dim3((w + UB_T - 1) / UB_T, (h + UB_T - 1) / UB_T, (unsigned)(B * Gs)), dim3(256),
-                         0, s, grec(G.cat[l]), G.cat[l].C / 8, F.x[l].C / 8, frec(below_f), grec(below_g), Gs, h, w,
-                         G.cat[l].H, G.cat[l].W, sy, sx);
-      PNPX_LAUNCH_CHECK();
+      PNPX_TRY(launch_upsample_bwd_hs(grec(G.cat[l]), G.cat[l].C / 8, F.x[l].C / 8, frec(below_f), grec(below_g), B, below_f.C / 8, below_f.H,
+                                      below_f.W, G.cat[l].H, G.cat[l].W, s));
     }
     for (int l = 4; l >= 0; --l) {
       if (l < 4) {
-        const size_t n = (size_t)B * (F.x[l].C / 8) * F.x[l].H * F.x[l].W;
-        hipLaunchKernelGGL(skip_pool_merge_hs_kernel, g1(n), dim3(256), 0, s, grec(G.cat[l]), G.cat[l].C / 8,
-                           grec(G.p[l + 1]), frec(F.x[l]), grec(G.x[l]), F.x[l].C / 8, F.x[l].H, F.x[l].W, n);
-        PNPX_LAUNCH_CHECK();
+        PNPX_TRY(launch_skip_pool_merge_hs(grec(G.cat[l]), G.cat[l].C / 8, grec(G.p[l + 1]), frec(F.x[l]), grec(G.x[l]), B, F.x[l].C / 8,
+                                           F.x[l].H, F.x[l].W, s));
       }
       PNPX_TRY(convH(3 * l + 2, G.x[l], G.b[l], &F.b[l]));
       PNPX_TRY(convH(3 * l + 1, G.b[l], G.a[l], &F.a[l]));
       PNPX_TRY(convH(3 * l, G.a[l], l == 0 ? G.in0 : G.p[l], nullptr));
     }
-    hipLaunchKernelGGL(input_grad_hs_kernel, dim3(SIG_CHUNKS, B), dim3(256), 0, s, grec(G.in0), g_res + px0, grad_x + px0,
-                       part + (size_t)lo * SIG_CHUNKS, gscale, H, W);
-    PNPX_LAUNCH_CHECK();
-    hipLaunchKernelGGL(sigma_grad_final_kernel, dim3((B + 63) / 64), dim3(64), 0, s, part + (size_t)lo * SIG_CHUNKS, grad_sigma + lo, B);
-    PNPX_LAUNCH_CHECK();
-    return PNPX_OK;
+    return launch_input_grad_hs(grec(G.in0), g_res + px0, grad_x + px0, part + (size_t)lo * SIG_CHUNKS, gscale, grad_sigma + lo, B, H, W, s);
     };
     const int chains = launch_chains(ctx, B, H, W);
     if (chains <= 1) return run_hs(0, B, s, 1);
@@ -641,7 +742,7 @@ int unet_denoise_backward(pnpx_ctx* ctx, const float* x, const float* sigma, int
   // 3..6 over images lo .. lo + B - 1 on stream s: the whole batch, or one of two launch chains (r5, option fp32_chains; the fp32 family is
   // not power-capped, a second chain fills the first one's tails and partial rounds; per-image results do not depend on the slicing)
   auto run = [&](int lo, int B, hipStream_t s) -> int {
-  const size_t npix = (size_t)B * H * W, px0 = (size_t)lo * H * W;
+  const size_t px0 = (size_t)lo * H * W;
   const float* const grad_out_s = grad_out + px0;
   const float* const pre_s = pre + px0;
   float* const g_res_s = g_res + px0;
@@ -649,11 +750,9 @@ int unet_denoise_backward(pnpx_ctx* ctx, const float* x, const float* sigma, int
   float* const part_s = part + (size_t)lo * SIG_CHUNKS;
   float* const grad_sigma_s = grad_sigma ? grad_sigma + lo : nullptr;
   auto gp = [&](const Act& d) { return reinterpret_cast<float*>(GA + d.off + (size_t)lo * act_bytes_per_image(fmode, d.C, d.H, d.W)); };
-  auto sa = [&](const Act& d) { return SavedAct{FA + d.off + (size_t)lo * act_bytes_per_image(fmode, d.C, d.H, d.W), 0}; };
+  auto sa = [&](const Act& d) { return reinterpret_cast<const float*>(FA + d.off + (size_t)lo * act_bytes_per_image(fmode, d.C, d.H, d.W)); };
   // 3. tail: clamp + residual + 1x1 out-conv -> gradient wrt the pre-activation of the last conv (y[0])
-  hipLaunchKernelGGL(outc_bwd_kernel, g1(npix), dim3(256), 0, s, grad_out_s, pre_s, ctx->outc_w, sa(F.y[0]), gp(G.y[0]),
-                     g_res_s, H, W, npix);
-  PNPX_LAUNCH_CHECK();
+  PNPX_TRY(launch_outc_bwd_f32(grad_out_s, pre_s, ctx->outc_w, sa(F.y[0]), gp(G.y[0]), g_res_s, B, H, W, s));
 
   auto convT = [&](int li, const Act& gin, const Act& gout, const Act* saved) -> int {
     const float* dm = saved ? reinterpret_cast<const float*>(FA + saved->off + (size_t)lo * act_bytes_per_image(fmode, saved->C, saved->H, saved->W)) : nullptr;
@@ -673,47 +772,21 @@ int unet_denoise_backward(pnpx_ctx* ctx, const float* x, const float* sigma, int
     // up part -> through the bilinear upsample -> pre-activation gradient of the tensor below
     const Act& below_f = (l == 3) ? F.x[4] : F.y[l + 1];
     const Act& below_g = (l == 3) ? G.x[4] : G.y[l + 1];
-    const int h = below_f.H, w = below_f.W, Cb = below_f.C;
-    const float sy = (2 * h > 1) ? (float)(h - 1) / (float)(2 * h - 1) : 0.f;
-    const float sx = (2 * w > 1) ? (float)(w - 1) / (float)(2 * w - 1) : 0.f;
-    const size_t n = (size_t)B * Cb * h * w;
-    if (!hs && (size_t)B * Cb <= 65535) {      // r6: LDS-window form (bit-identical; fp32 planar activations)
-      if (w >= 64)
-        hipLaunchKernelGGL(upsample_bwd_lds_kernel<64>, dim3((w + 63) / 64, (h + UBF_T - 1) / UBF_T, (unsigned)(B * Cb)), dim3(256), 0, s, gp(G.cat[l]),
-                           G.cat[l].C, F.x[l].C, static_cast<const float*>(sa(below_f).p), gp(below_g), Cb, h, w, G.cat[l].H, G.cat[l].W, sy, sx);
-      else
-        hipLaunchKernelGGL(upsample_bwd_lds_kernel<16>, dim3((w + 15) / 16, (h + UBF_T - 1) / UBF_T, (unsigned)(B * Cb)), dim3(256), 0, s, gp(G.cat[l]),
-                           G.cat[l].C, F.x[l].C, static_cast<const float*>(sa(below_f).p), gp(below_g), Cb, h, w, G.cat[l].H, G.cat[l].W, sy, sx);
-    } else {
-      hipLaunchKernelGGL(upsample_bwd_kernel, g1(n), dim3(256), 0, s, gp(G.cat[l]), G.cat[l].C, F.x[l].C, sa(below_f),
-                         gp(below_g), Cb, h, w, G.cat[l].H, G.cat[l].W, sy, sx, n);
-    }
-    PNPX_LAUNCH_CHECK();
+    PNPX_TRY(launch_upsample_bwd_f32(VG_AUTO, gp(G.cat[l]), G.cat[l].C, F.x[l].C, sa(below_f), gp(below_g), B, below_f.C, below_f.H, below_f.W,
+                                     G.cat[l].H, G.cat[l].W, s));
   }
   // 5. encoder blocks, bottom (level 4) to top
   for (int l = 4; l >= 0; --l) {
     if (l < 4) {   // gradient reaching x[l]: skip part of the decoder concat + max-pool routing from level l+1
-      const size_t n = (size_t)B * F.x[l].C * F.x[l].H * F.x[l].W;
-      if (F.x[l].H % 2 == 0 && F.x[l].W % 2 == 0) {      // r6: one thread per max-pool window (bit-identical)
-        hipLaunchKernelGGL(skip_pool_merge_f32_kernel, g1(n / 4), dim3(256), 0, s, gp(G.cat[l]), G.cat[l].C, gp(G.p[l + 1]),
-                           static_cast<const float*>(sa(F.x[l]).p), gp(G.x[l]), F.x[l].C, F.x[l].H, F.x[l].W, n / 4);
-      } else {
-        hipLaunchKernelGGL(skip_pool_merge_kernel, g1(n), dim3(256), 0, s, gp(G.cat[l]), G.cat[l].C, gp(G.p[l + 1]),
-                           sa(F.x[l]), gp(G.x[l]), F.x[l].C, F.x[l].H, F.x[l].W, n);
-      }
-      PNPX_LAUNCH_CHECK();
+      PNPX_TRY(launch_skip_pool_merge_f32(VG_AUTO, gp(G.cat[l]), G.cat[l].C, gp(G.p[l + 1]), sa(F.x[l]), gp(G.x[l]), B, F.x[l].C, F.x[l].H,
+                                          F.x[l].W, s));
     }
     PNPX_TRY(convT(3 * l + 2, G.x[l], G.b[l], &F.b[l]));
     PNPX_TRY(convT(3 * l + 1, G.b[l], G.a[l], &F.a[l]));
     PNPX_TRY(convT(3 * l, G.a[l], l == 0 ? G.in0 : G.p[l], nullptr));
   }
   // 6. input gradients
-  hipLaunchKernelGGL(input_grad_kernel, dim3(SIG_CHUNKS, B), dim3(256), 0, s, gp(G.in0), G.in0.C, g_res_s, grad_x_s, part_s, H,
-                     W);
-  PNPX_LAUNCH_CHECK();
-  hipLaunchKernelGGL(sigma_grad_final_kernel, dim3((B + 63) / 64), dim3(64), 0, s, part_s, grad_sigma_s, B);
-  PNPX_LAUNCH_CHECK();
-  return PNPX_OK;
+  return launch_input_grad_f32(gp(G.in0), G.in0.C, g_res_s, grad_x_s, part_s, grad_sigma_s, B, H, W, s);
   };
   // the adjoint chain always forks exactly TWO launch chains when fp32_chains >= 2 (measured best, profiles/r5_wino8.md; the forward
   // honours larger n): documented in include/pnpx.h
