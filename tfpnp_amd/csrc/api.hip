@@ -500,8 +500,8 @@ int pnpx_ctx_status(pnpx_ctx* ctx) {
 size_t pnpx_ctx_bytes(const pnpx_ctx* ctx) {
   if (!ctx) return 0;
   size_t n = ctx->weights.bytes + ctx->arena.buf.bytes + ctx->arena_grad.buf.bytes + ctx->scratch.bytes +
-             ctx->drunet.weights.bytes + ctx->drunet.arena.bytes + ctx->drunet.arena_grad.bytes + ctx->drunet.f32_weights.bytes +
-             ctx->drunet.f32_arena.bytes + ctx->drunet.f32_weights_bwd.bytes + ctx->drunet.f32_arena_grad.bytes +
+             ctx->drunet.weights.bytes + ctx->drunet.arena.buf.bytes + ctx->drunet.arena_grad.buf.bytes + ctx->drunet.f32.weights.bytes +
+             ctx->drunet.f32_arena.buf.bytes + ctx->drunet.f32_bwd.weights.bytes + ctx->drunet.f32_arena_grad.buf.bytes +
              ctx->policy.weights.bytes + ctx->policy.arena.bytes + ctx->policy.live.master.bytes + ctx->policy.pack_ws.ws.bytes + ctx->policy.raw.weights.bytes + ctx->policy.raw_ws.ws.bytes +
              ctx->policy.train_ws.bytes + ctx->policy.bn_buf.bytes + ctx->policy.optim.state.bytes + ctx->critic.weights.bytes + ctx->critic.arena.bytes +
              ctx->critic.live.master.bytes + ctx->critic.pack_ws.ws.bytes + ctx->critic.optim.state.bytes;

@@ -171,7 +171,18 @@ int launch_chains(const pnpx_ctx* ctx, int B, int H, int W);
 // a launch-chain fan-out failed half way: drain the side streams before the error is returned, so that nothing queued on them
 // is still writing the shared arena / output buffers when the caller (or the next call) re-uses them
 void join_side_streams_after_failure(pnpx_ctx* ctx);
-// DRUNet denoiser (drunet.hip): packed weights per MFMA launch in state_dict order + its own activation arena
+// DRUNet denoiser (drunet.hip): packed weights per MFMA launch in state_dict order + its own activation arenas
+struct DruArena {   // one arena and the layout it holds (drunet_net.h: dru_arena_reserve)
+  DeviceBuf buf;
+  int capB = 0, capH = 0, capW = 0;
+  bool keeps = false;   // the layout has room for every ResBlock's middle activation (forward arenas, for the VJP)
+};
+struct DruF32Pack {   // fp32 packings of every layer (drunet_f32.hip), made on first use
+  bool ready = false;
+  std::vector<ConvLayer> layers;       // direct fp32 MFMA kernel
+  std::vector<const float*> wino;      // Winograd weights of the 3x3 ResBlock layers (else null)
+  DeviceBuf weights;
+};
 struct DruNet {
   bool loaded = false;
   int nb = 0;
@@ -191,23 +202,12 @@ struct DruNet {
   // launch whose channels 0 / 1 are the image / noise-map gradients; the tail's adjoint runs on the vector ALU)
   std::vector<ConvLayerHsDev> layers_bwd;
   const float* tail_bwd_w = nullptr;   // [64][2][3][3]: conv_first_hs_kernel weights of the tail's adjoint (1 -> 64 channels)
-  DeviceBuf weights, arena, arena_grad;
+  DeviceBuf weights;
+  DruArena arena, arena_grad;          // half-split family: activations (+ keep planes), gradients
   // conv_mode 0 (drunet_f32.hip): fp32 packings of the same layers, made on first use from the host copy of the parameters
   std::vector<float> params_host;
-  bool f32_ready = false;
-  std::vector<ConvLayer> f32_layers;       // direct fp32 MFMA kernel
-  std::vector<const float*> f32_wino;      // Winograd weights of the 3x3 ResBlock layers (else null)
-  DeviceBuf f32_weights, f32_arena;
-  int f32_capB = 0, f32_capH = 0, f32_capW = 0;
-  bool f32_arena_keeps = false;            // ... with room for every ResBlock's middle activation (the fp32 VJP, r5)
-  bool f32_bwd_ready = false;              // adjoint packings of the fp32 family (made on the first fp32 VJP)
-  std::vector<ConvLayer> f32_layers_bwd;
-  std::vector<const float*> f32_wino_bwd;
-  DeviceBuf f32_weights_bwd, f32_arena_grad;
-  int f32_gcapB = 0, f32_gcapH = 0, f32_gcapW = 0;
-  int capB = 0, capH = 0, capW = 0;
-  bool arena_keeps = false;            // the arena has room for every ResBlock's middle activation (backward pass)
-  int gcapB = 0, gcapH = 0, gcapW = 0;
+  DruF32Pack f32, f32_bwd;             // forward layers; their adjoints (made on the first fp32 VJP)
+  DruArena f32_arena, f32_arena_grad;
 };
 
 }  // namespace pnpx
@@ -421,9 +421,10 @@ int drunet_denoise(pnpx_ctx* ctx, const float* x, const float* sigma, int sigma_
 int drunet_denoise_backward(pnpx_ctx* ctx, const float* x, const float* sigma, int sigma_stride, const float* grad_out,
                             float* grad_x, float* grad_sigma, int B, int H, int W, hipStream_t s);
 void drunet_free(pnpx_ctx* ctx);
+// the fp32 family's pieces (drunet_f32.hip), reached through the two functions above in conv_mode 0: the forward, and the adjoint chain after it
 int drunet_denoise_f32(pnpx_ctx* ctx, const float* x, const float* sigma, int sigma_stride, float* out, float* out_pre, int B, int H,
                        int W, hipStream_t s, bool keep_mids = false);
-int drunet_denoise_backward_f32(pnpx_ctx* ctx, const float* x, const float* sigma, int sigma_stride, const float* grad_out, float* grad_x,
+int drunet_denoise_backward_f32(pnpx_ctx* ctx, const float* grad_out, const float* pre, float* g_pre, float* part, float* grad_x,
                                 float* grad_sigma, int B, int H, int W, hipStream_t s);
 void drunet_f32_free(pnpx_ctx* ctx);
 

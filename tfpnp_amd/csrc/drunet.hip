@@ -15,12 +15,15 @@
 //     (1x1 convolutions are sparse-tap launches, conv_hs_taps.hip: only the centre tap is stored, copied and multiplied);
 //   * head (K = 18) on the vector ALU straight from the fp32 image (conv_first_hs_kernel, as the UNet's first layer);
 //   * tail (64 -> 1) as a 32-cout launch with the fused "1x1 + residual + clamp" epilogue (EPI_OUTC) selecting channel 0.
-#include <cstring>
+//
+// The network itself -- layer table, weight tensors, topology walks, arena reservation -- is written once for both kernel
+// families in drunet_net.h; this file is the half-split family: its launches, its weight packing and its arena plan.
 #include <vector>
 
 #include "common.h"
 #include "conv_first.h"
 #include "conv_hs.h"
+#include "drunet_net.h"
 #include "grad_common.h"
 #include "hs_rec.h"
 #include "hs_relayout.h"
@@ -28,8 +31,6 @@
 namespace pnpx {
 
 namespace {
-
-constexpr int DRU_NC[4] = {64, 128, 256, 512};
 
 // out = a + b on interior records (fp32 add of the recombined halves, re-split)
 __global__ __launch_bounds__(256) void dru_add_kernel(const HsRec* __restrict__ a, const HsRec* __restrict__ b,
@@ -51,42 +52,11 @@ __global__ __launch_bounds__(256) void dru_add_kernel(const HsRec* __restrict__ 
 
 inline dim3 g1(size_t n) { return dim3((unsigned)((n + 255) / 256)); }
 
-struct LayerDesc {
-  int kind;   // 0 head, 1 res conv a (ReLU), 2 res conv b (+res), 3 strided 2x2, 4 transposed 2x2, 5 tail
-  int cin, cout;
-};
-// state_dict order (KAIR UNetRes): head; down1..3 = nb x (res.0, res.2) + strided conv; body; up3..1 = convT + nb x (..); tail
-std::vector<LayerDesc> dru_layers(int nb) {
-  std::vector<LayerDesc> L;
-  L.push_back({0, 2, DRU_NC[0]});
-  auto res = [&](int c) {
-    for (int i = 0; i < nb; ++i) {
-      L.push_back({1, c, c});
-      L.push_back({2, c, c});
-    }
-  };
-  for (int l = 0; l < 3; ++l) {
-    res(DRU_NC[l]);
-    L.push_back({3, DRU_NC[l], DRU_NC[l + 1]});
-  }
-  res(DRU_NC[3]);
-  for (int l = 2; l >= 0; --l) {
-    L.push_back({4, DRU_NC[l + 1], DRU_NC[l]});
-    res(DRU_NC[l]);
-  }
-  L.push_back({5, DRU_NC[0], 1});
-  return L;
-}
-size_t layer_params(const LayerDesc& d) {
-  const int k = (d.kind == 3 || d.kind == 4) ? 4 : 9;
-  return (size_t)d.cin * d.cout * k;
-}
-
 }  // namespace
 
 size_t drunet_num_params(int nb) {
   size_t n = 0;
-  for (const LayerDesc& d : dru_layers(nb)) n += layer_params(d);
+  for (const DruLayer& d : dru_layers(nb)) n += layer_params(d);
   return n;
 }
 
@@ -94,8 +64,8 @@ void drunet_free(pnpx_ctx* ctx) {
   DruNet& N = ctx->drunet;
   (void)hipDeviceSynchronize();
   if (N.weights.p) (void)hipFree(N.weights.p);
-  if (N.arena.p) (void)hipFree(N.arena.p);
-  if (N.arena_grad.p) (void)hipFree(N.arena_grad.p);
+  dru_arena_free(N.arena);
+  dru_arena_free(N.arena_grad);
   drunet_f32_free(ctx);
   N = DruNet();
 }
@@ -105,98 +75,56 @@ int drunet_load(pnpx_ctx* ctx, const float* params, size_t n, int nb) {
     set_error("pnpx_drunet_load: expected %zu parameters for nb=%d (1..8), got %zu", nb >= 1 && nb <= 8 ? drunet_num_params(nb) : (size_t)0, nb, n);
     return PNPX_ERR_ARG;
   }
-  const std::vector<LayerDesc> L = dru_layers(nb);
+  const std::vector<DruLayer> L = dru_layers(nb);
   std::vector<float> host;   // blob: packed HS weights per MFMA layer, head weights (native), zero bias, e0, 0
   auto align = [&]() { host.resize((host.size() + 255) & ~(size_t)255, 0.f); };
-  std::vector<size_t> off(L.size(), 0);
+  std::vector<size_t> off(L.size(), 0), offb(L.size(), 0);
   std::vector<ConvLayerHsDev> dev(L.size()), devb(L.size());
-  std::vector<size_t> offb(L.size(), 0);
   std::vector<int> taps(L.size(), 0x1FF);
-  std::vector<float> wt;
-  size_t tailb_off = 0;
-  // adjoint of a layer given as w[cout][cin][9]: wt[ci][co][tap] = w[co][ci][8 - tap], packed like a forward layer with
-  // cin / cout swapped (output channels padded to a multiple of 32 with zero rows)
-  auto pack_adjoint = [&](size_t i, const float* w, int cout, int cin, int tapmask) {
-    const int cout_b = (cin + 31) / 32 * 32, cin_b = cout, cin_pad_b = (cin_b + 15) / 16 * 16;
-    wt.assign((size_t)cout_b * cin_b * 9, 0.f);
-    for (int co = 0; co < cout; ++co)
-      for (int ci = 0; ci < cin; ++ci)
-        for (int t = 0; t < 9; ++t) wt[((size_t)ci * cin_b + co) * 9 + t] = w[((size_t)co * cin + ci) * 9 + (8 - t)];
+  std::vector<float> w3, wa;
+  size_t head_off = 0, tailb_off = 0;
+  // appends w[cout][cin][9] to the blob as one MFMA layer (the taps of tapmask only)
+  auto pack = [&](const float* w, int cout, int cin, int tapmask, size_t* off_o, ConvLayerHsDev* D) {
+    const int mt = conv_hs_mt(cout), cin_pad = (cin + 15) / 16 * 16;
     int ntap = 0;
     for (int t = 0; t < 9; ++t) ntap += (tapmask >> t) & 1;
-    const int mt = conv_hs_mt(cout_b);
     align();
-    offb[i] = host.size();
-    const size_t n16 = (size_t)cout_b * cin_pad_b * ntap * 2;
+    *off_o = host.size();
+    const size_t n16 = (size_t)cout * cin_pad * ntap * 2;
     host.resize(host.size() + (n16 + 1) / 2, 0.f);
-    const float scale = pack_conv_weights_hs_taps(wt.data(), cout_b, cin_b, mt, tapmask, reinterpret_cast<uint16_t*>(host.data() + offb[i]));
-    devb[i].cin = cin_b;
-    devb[i].cout = cout_b;
-    devb[i].cin_pad = cin_pad_b;
-    devb[i].mt = mt;
-    devb[i].inv_scale = 1.0f / (scale * HS_ASCALE);
+    const float scale = pack_conv_weights_hs_taps(w, cout, cin, mt, tapmask, reinterpret_cast<uint16_t*>(host.data() + *off_o));
+    D->cin = cin;
+    D->cout = cout;
+    D->cin_pad = cin_pad;
+    D->mt = mt;
+    D->inv_scale = 1.0f / (scale * HS_ASCALE);
   };
   const float* src = params;
-  std::vector<float> w3;
-  size_t head_off = 0;
   for (size_t i = 0; i < L.size(); ++i) {
-    const LayerDesc& d = L[i];
+    const DruLayer& d = L[i];
     const float* w = src;
     src += layer_params(d);
-    if (d.kind == 0) {   // head: native [64][2][3][3] for the VALU kernel; its adjoint (64 -> 2, padded to 32) on the MFMA kernel
+    int cin, cout;
+    dru_layer_w3(d, w, &cin, &cout, w3);
+    const int tapmask = dru_is_1x1(d) ? 0x010 : 0x1FF;   // 1x1 layers store / multiply the centre tap only
+    if (d.kind == 0) {   // head: native [64][2][3][3] for the VALU kernel
       align();
       head_off = host.size();
       host.insert(host.end(), w, w + layer_params(d));
-      pack_adjoint(i, w, d.cout, d.cin, 0x1FF);
-      continue;
+    } else {
+      pack(w3.data(), cout, cin, tapmask, &off[i], &dev[i]);
+      taps[i] = tapmask;
     }
-    int cin = d.cin, cout = d.cout;
-    const float* wp = w;
-    if (d.kind == 3) {          // Conv2d k2 s2 [cout][cin][2][2] -> 1x1 over the space-to-depth input (phase-major channels)
-      cin = 4 * d.cin;
-      w3.assign((size_t)cout * cin * 9, 0.f);
-      for (int co = 0; co < cout; ++co)
-        for (int ci = 0; ci < d.cin; ++ci)
-          for (int ph = 0; ph < 4; ++ph) w3[((size_t)co * cin + ph * d.cin + ci) * 9 + 4] = w[((size_t)co * d.cin + ci) * 4 + ph];
-      wp = w3.data();
-    } else if (d.kind == 4) {   // ConvTranspose2d k2 s2 [cin][cout][2][2] -> 1x1 to 4*cout phase-major channels
-      cout = 4 * d.cout;
-      w3.assign((size_t)cout * cin * 9, 0.f);
-      for (int ci = 0; ci < cin; ++ci)
-        for (int co = 0; co < d.cout; ++co)
-          for (int ph = 0; ph < 4; ++ph) w3[((size_t)(ph * d.cout + co) * cin + ci) * 9 + 4] = w[((size_t)ci * d.cout + co) * 4 + ph];
-      wp = w3.data();
-    } else if (d.kind == 5) {   // tail [1][64][3][3] -> 32 couts, rows 1..31 zero
-      cout = 32;
-      w3.assign((size_t)cout * cin * 9, 0.f);
-      std::memcpy(w3.data(), w, sizeof(float) * (size_t)cin * 9);
-      wp = w3.data();
-    }
-    const int mt = conv_hs_mt(cout);
-    const int cin_pad = (cin + 15) / 16 * 16;
-    const int tapmask = (d.kind == 3 || d.kind == 4) ? 0x010 : 0x1FF;   // 1x1 layers store / multiply the centre tap only
-    int ntap = 0;
-    for (int t = 0; t < 9; ++t) ntap += (tapmask >> t) & 1;
-    align();
-    off[i] = host.size();
-    const size_t n16 = (size_t)cout * cin_pad * ntap * 2;
-    host.resize(host.size() + (n16 + 1) / 2, 0.f);
-    const float scale = pack_conv_weights_hs_taps(wp, cout, cin, mt, tapmask, reinterpret_cast<uint16_t*>(host.data() + off[i]));
-    taps[i] = tapmask;
-    if (d.kind == 5) {          // tail adjoint (1 -> 64 channels) on the vector ALU: conv_first weights [64][2][9], noise-map half zero
+    if (d.kind == 5) {   // tail adjoint (1 -> 64 channels) on the vector ALU: conv_first weights [64][2][9], noise-map half zero
       align();
       tailb_off = host.size();
       host.resize(host.size() + 64 * 18, 0.f);
       for (int c = 0; c < 64; ++c)
         for (int t = 0; t < 9; ++t) host[tailb_off + (size_t)c * 18 + t] = w[(size_t)c * 9 + (8 - t)];
-    } else {
-      pack_adjoint(i, wp, cout, cin, tapmask);
+    } else {             // adjoint on the MFMA kernel, packed like a forward layer (the head's: 64 -> 2, padded to 32)
+      const int rows = dru_adjoint_w3(w3, cin, cout, wa);
+      pack(wa.data(), rows, cout, tapmask, &offb[i], &devb[i]);
     }
-    dev[i].cin = cin;
-    dev[i].cout = cout;
-    dev[i].cin_pad = cin_pad;
-    dev[i].mt = mt;
-    dev[i].inv_scale = 1.0f / (scale * HS_ASCALE);
   }
   align();
   const size_t zoff = host.size();
@@ -243,13 +171,9 @@ int drunet_load(pnpx_ctx* ctx, const float* params, size_t n, int nb) {
 
 namespace {
 
-struct DruPlan {
-  // per level l: S (skip / level input), P, Q (ResBlock outputs, alternating), M (ResBlock middle; skip sums), U (decoder
-  // level input, l <= 2), DT (space-to-depth input of the strided conv / output of the transposed conv, l >= 1: 2*C_l ch)
-  size_t S[4], P[4], Q[4], M[4], U[4], DT[4];
-  size_t MK[4][16];   // backward pass only: one M per ResBlock (level l: encoder blocks 0..nb-1, decoder blocks nb..2nb-1)
+struct DruPlan : DruOffsets {   // byte offsets
   size_t IN0;         // gradient arena only: 32-channel output of the head's adjoint
-  size_t zimg;     // [B][H][W] fp32 zeros (residual operand of the fused tail epilogue)
+  size_t zimg;        // [B][H][W] fp32 zeros (residual operand of the fused tail epilogue)
   size_t total;
 };
 size_t rec_bytes(int C, int h, int w) { return (size_t)(C / 8) * (h + 2) * (w + 2) * 32; }
@@ -277,77 +201,47 @@ DruPlan dru_plan(int capB, int H, int W, int nb_keep = 0, bool grad = false) {
   return P;
 }
 
-}  // namespace
+// The re-layouts and the skip sum, as both walks launch them on B images at H x W (level 0) on stream s.
+struct HsGlue {
+  int B, H, W;
+  hipStream_t s;
+  int s2d(int l, const char* in, char* out) const {
+    const int h = H >> l, w = W >> l, G = DRU_NC[l] / 8;
+    const size_t n = (size_t)B * 4 * G * (h / 2) * (w / 2) * 2;
+    hipLaunchKernelGGL(hs_s2d_kernel, g1(n), dim3(256), 0, s, reinterpret_cast<const uint4*>(in), reinterpret_cast<uint4*>(out), G, h, w, n);
+    PNPX_LAUNCH_CHECK();
+    return PNPX_OK;
+  }
+  int d2s(int l, const char* in, char* out) const {
+    const int h = H >> (l + 1), w = W >> (l + 1), G = DRU_NC[l] / 8;
+    const size_t n = (size_t)B * G * (2 * h) * (2 * w) * 2;
+    hipLaunchKernelGGL(hs_d2s_kernel, g1(n), dim3(256), 0, s, reinterpret_cast<const uint4*>(in), reinterpret_cast<uint4*>(out), G, h, w, n);
+    PNPX_LAUNCH_CHECK();
+    return PNPX_OK;
+  }
+  int add(int l, const char* a, const char* b, char* o) const {
+    const int h = H >> l, w = W >> l;
+    const size_t n = (size_t)B * (DRU_NC[l] / 8) * h * w;
+    hipLaunchKernelGGL(dru_add_kernel, g1(n), dim3(256), 0, s, reinterpret_cast<const HsRec*>(a), reinterpret_cast<const HsRec*>(b),
+                       reinterpret_cast<HsRec*>(o), h, w, n);
+    PNPX_LAUNCH_CHECK();
+    return PNPX_OK;
+  }
+};
 
-int drunet_denoise(pnpx_ctx* ctx, const float* x, const float* sigma, int sigma_stride, float* out, float* out_pre,
-                   int B, int H, int W, hipStream_t s, bool keep_mids) {
-  DruNet& N = ctx->drunet;
-  if (!N.loaded) {
-    set_error("DRUNet denoiser called before pnpx_drunet_load");
-    return PNPX_ERR_NO_WEIGHTS;
-  }
-  if (ctx->conv_mode != CONV_HS) {
-    return drunet_denoise_f32(ctx, x, sigma, sigma_stride, out, out_pre, B, H, W, s, keep_mids);   // fp32 arithmetic throughout (drunet_f32.hip)
-  }
-  if (B <= 0 || H < 8 || W < 8 || (H & 7) || (W & 7)) {
-    set_error("DRUNet: need B > 0 and H, W positive multiples of 8 (three 2x2 strided convolutions; got B=%d H=%d W=%d)", B, H, W);
-    return PNPX_ERR_SHAPE;
-  }
-  if (B > N.capB || H != N.capH || W != N.capW || (keep_mids && !N.arena_keeps)) {     // (re)lay the arena out: zero borders are written here, once
-    const int nb_img = (H == N.capH && W == N.capW && N.capB > B) ? N.capB : B;
-    const bool keeps = keep_mids || (N.arena_keeps && H == N.capH && W == N.capW);
-    const DruPlan Pl = dru_plan(nb_img, H, W, keeps ? N.nb : 0);
-    PNPX_HIP(hipDeviceSynchronize());
-    if (N.arena.bytes < Pl.total) {
-      if (N.arena.p) PNPX_HIP(hipFree(N.arena.p));
-      N.arena = DeviceBuf();
-      N.capB = N.capH = N.capW = 0;
-      void* p = nullptr;
-      hipError_t e = hipMalloc(&p, Pl.total);
-      if (e != hipSuccess) {
-        set_error("DRUNet arena allocation of %zu bytes failed: %s", Pl.total, hipGetErrorString(e));
-        return PNPX_ERR_ALLOC;
-      }
-      N.arena.p = p;
-      N.arena.bytes = Pl.total;
-    }
-    PNPX_HIP(hipMemset(N.arena.p, 0, N.arena.bytes));
-    N.capB = nb_img;
-    N.capH = H;
-    N.capW = W;
-    N.arena_keeps = keeps;
-  }
-  const DruPlan Pl = dru_plan(N.capB, H, W, N.arena_keeps ? N.nb : 0);
-  const int sh = N.shift;      // this pass runs on inputs scaled by 2^-sh (see DruNet::shift)
-  char* const A0 = static_cast<char*>(N.arena.p);
-  unsigned* const range_flag = ctx->opt_range_guard ? ctx->range_flag_dev : nullptr;
-  const std::vector<LayerDesc> L = dru_layers(N.nb);
-
-  const int chains = keep_mids ? 1 : launch_chains(ctx, B, H, W);      // (the launch table plans for the chains side by side: f.share)
-  // The forward over images b0 .. b0 + B - 1 of the arena on stream s (x / sigma / out already point at the first of them): every
-  // tensor is [image][group][h + 2][w + 2] records, so a slice of the batch is a contiguous piece of each -- independent launch
-  // chains over slices run side by side on side streams exactly as for the UNet (unet.hip: launch_chains; bit-identical per image).
-  auto run = [&](int b0, int B, const float* x, const float* sigma, float* out, float* out_pre, hipStream_t s) -> int {
-  struct Shifted {   // arena offsets of this slice
-    size_t S[4], P[4], Q[4], M[4], U[4], DT[4], MK[4][16], zimg;
-  } Sl{};
-  for (int l = 0; l < 4; ++l) {
-    const size_t per = rec_bytes(DRU_NC[l], H >> l, W >> l) * (size_t)b0;
-    Sl.S[l] = Pl.S[l] + per;
-    Sl.P[l] = Pl.P[l] + per;
-    Sl.Q[l] = Pl.Q[l] + per;
-    Sl.M[l] = Pl.M[l] + per;
-    Sl.U[l] = Pl.U[l] + per;
-    Sl.DT[l] = Pl.DT[l] + rec_bytes(2 * DRU_NC[l], H >> l, W >> l) * (size_t)b0;
-    for (int j = 0; j < 16; ++j) Sl.MK[l][j] = Pl.MK[l][j] + per;
-  }
-  Sl.zimg = Pl.zimg + sizeof(float) * (size_t)H * W * b0;
-  char* const A = A0;
-  const Shifted& Pl = Sl;      // the body below addresses the slice through the same names
-  size_t li = 0;
+// The forward's launches over one slice of the batch (x / sigma / out / out_pre / zimg point at its first image).
+struct HsForward : HsGlue {
+  const DruNet& N;
+  const float *x, *sigma;
+  int sigma_stride;
+  float *out, *out_pre;
+  const float* zimg;
+  char* unwritten;   // the tail launch's record output operand: not written (EPI_OUTC stores the images)
+  unsigned* range_flag;
+  int chains;        // launch chains running side by side: the launch table plans for all of them (f.share)
 
   // one MFMA convolution launch: layer li, `in` (cin channels) -> `outp`
-  auto conv = [&](const char* in, char* outp, int lvl_h, int lvl_w, float slope, const char* res, bool tail) -> int {
+  int conv(size_t li, const char* in, char* outp, int h, int w, float slope, const char* res, bool tail = false) const {
     const ConvLayerHsDev& D = N.layers[li];
     const ConvLayerHs Lh = hs_layer(D, N.zero);
     ConvHsFuse f;
@@ -358,83 +252,61 @@ int drunet_denoise(pnpx_ctx* ctx, const float* x, const float* sigma, int sigma_
     f.taps = N.taps[li];
     f.share = chains;
     if (tail) {
-      f.outc_w = N.e0 + 32 * (sh / 4);   // selects channel 0 and multiplies the 2^-sh of the head back
-      f.outc_b = N.e0 + 5 * 32;          // a zero
-      f.x_in = reinterpret_cast<const float*>(A + Pl.zimg);
+      f.outc_w = N.e0 + 32 * (N.shift / 4);   // selects channel 0 and multiplies the 2^-shift of the head back
+      f.outc_b = N.e0 + 5 * 32;               // a zero
+      f.x_in = zimg;
       f.out_img = out;
       f.out_pre = out_pre;
     }
-    ++li;
-    return launch_conv_hs(Lh, in, D.cin_pad / 8, nullptr, 0, outp, B, lvl_h, lvl_w, f, s);
-  };
-  auto resblocks = [&](int l, int dec, char* cur, char** result) -> int {
-    const int h = H >> l, w = W >> l;
-    char* pq[2] = {A + Pl.P[l], A + Pl.Q[l]};
-    int k = 0;
-    for (int i = 0; i < N.nb; ++i) {
-      char* mid = keep_mids ? A + Pl.MK[l][dec * N.nb + i] : A + Pl.M[l];
-      PNPX_TRY(conv(cur, mid, h, w, 0.f, nullptr, false));       // conv + ReLU
-      char* dst = pq[k];
-      if (dst == cur) dst = pq[k ^= 1];
-      PNPX_TRY(conv(mid, dst, h, w, 1.f, cur, false));            // conv + x
-      cur = dst;
-      k ^= 1;
-    }
-    *result = cur;
+    return launch_conv_hs(Lh, in, D.cin_pad / 8, nullptr, 0, outp, B, h, w, f, s);
+  }
+  // head: cat[x, sigma] -> 64 channels, linear (VALU, exact fp32 FMA chains); this pass runs on inputs scaled by 2^-shift (DruNet::shift)
+  int head(char* s0) const {
+    hipLaunchKernelGGL(conv_first_hs_kernel, dim3((H * W + 255) / 256, DRU_NC[0] / 8, B), dim3(256), 0, s, x, sigma, sigma_stride,
+                       N.head_w, N.zero, reinterpret_cast<HsRec*>(s0), H, W, 1.0f, std::ldexp(HS_ASCALE, -N.shift));
+    PNPX_LAUNCH_CHECK();
     return PNPX_OK;
-  };
+  }
+  int tail(size_t li, const char* m0) const { return conv(li, m0, unwritten, H, W, 1.f, nullptr, true); }
+};
 
-  // head: cat[x, sigma] -> 64 channels, linear (VALU, exact fp32 FMA chains)
-  hipLaunchKernelGGL(conv_first_hs_kernel, dim3((H * W + 255) / 256, DRU_NC[0] / 8, B), dim3(256), 0, s, x, sigma,
-                     sigma_stride, N.head_w, N.zero, reinterpret_cast<HsRec*>(A + Pl.S[0]), H, W, 1.0f, std::ldexp(HS_ASCALE, -sh));
-  PNPX_LAUNCH_CHECK();
-  li = 1;
-  char* cur = A + Pl.S[0];
-  for (int l = 0; l < 3; ++l) {
-    PNPX_TRY(resblocks(l, 0, cur, &cur));
-    const int h = H >> l, w = W >> l, G = DRU_NC[l] / 8;
-    const size_t n = (size_t)B * 4 * G * (h / 2) * (w / 2) * 2;
-    hipLaunchKernelGGL(hs_s2d_kernel, g1(n), dim3(256), 0, s, reinterpret_cast<const uint4*>(cur),
-                       reinterpret_cast<uint4*>(A + Pl.DT[l + 1]), G, h, w, n);
-    PNPX_LAUNCH_CHECK();
-    PNPX_TRY(conv(A + Pl.DT[l + 1], A + Pl.S[l + 1], h / 2, w / 2, 1.f, nullptr, false));
-    cur = A + Pl.S[l + 1];
-  }
-  PNPX_TRY(resblocks(3, 0, cur, &cur));
-  for (int l = 2; l >= 0; --l) {
-    const int h = H >> (l + 1), w = W >> (l + 1), Gin = DRU_NC[l + 1] / 8, Gout = DRU_NC[l] / 8;
-    const size_t na = (size_t)B * Gin * h * w;
-    hipLaunchKernelGGL(dru_add_kernel, g1(na), dim3(256), 0, s, reinterpret_cast<const HsRec*>(cur),
-                       reinterpret_cast<const HsRec*>(A + Pl.S[l + 1]), reinterpret_cast<HsRec*>(A + Pl.M[l + 1]), h, w, na);
-    PNPX_LAUNCH_CHECK();
-    PNPX_TRY(conv(A + Pl.M[l + 1], A + Pl.DT[l + 1], h, w, 1.f, nullptr, false));
-    const size_t nd = (size_t)B * Gout * (2 * h) * (2 * w) * 2;
-    hipLaunchKernelGGL(hs_d2s_kernel, g1(nd), dim3(256), 0, s, reinterpret_cast<const uint4*>(A + Pl.DT[l + 1]),
-                       reinterpret_cast<uint4*>(A + Pl.U[l]), Gout, h, w, nd);
-    PNPX_LAUNCH_CHECK();
-    PNPX_TRY(resblocks(l, 1, A + Pl.U[l], &cur));
-  }
-  {
-    const size_t na = (size_t)B * (DRU_NC[0] / 8) * H * W;
-    hipLaunchKernelGGL(dru_add_kernel, g1(na), dim3(256), 0, s, reinterpret_cast<const HsRec*>(cur),
-                       reinterpret_cast<const HsRec*>(A + Pl.S[0]), reinterpret_cast<HsRec*>(A + Pl.M[0]), H, W, na);
-    PNPX_LAUNCH_CHECK();
-  }
-  PNPX_TRY(conv(A + Pl.M[0], A + Pl.P[0], H, W, 1.f, nullptr, true));   // tail -> out / out_pre (P[0] is not written)
-  if (li != L.size()) {
-    set_error("DRUNet: internal layer walk mismatch (%zu of %zu)", li, L.size());
-    return PNPX_ERR_ARG;
-  }
-  return PNPX_OK;
-  };
+}  // namespace
 
+int drunet_denoise(pnpx_ctx* ctx, const float* x, const float* sigma, int sigma_stride, float* out, float* out_pre,
+                   int B, int H, int W, hipStream_t s, bool keep_mids) {
+  DruNet& N = ctx->drunet;
+  if (!N.loaded) {
+    set_error("DRUNet denoiser called before pnpx_drunet_load");
+    return PNPX_ERR_NO_WEIGHTS;
+  }
+  if (B <= 0 || H < 8 || W < 8 || (H & 7) || (W & 7)) {
+    set_error("DRUNet: need B > 0 and H, W positive multiples of 8 (three 2x2 strided convolutions; got B=%d H=%d W=%d)", B, H, W);
+    return PNPX_ERR_SHAPE;
+  }
+  if (ctx->conv_mode != CONV_HS) {
+    return drunet_denoise_f32(ctx, x, sigma, sigma_stride, out, out_pre, B, H, W, s, keep_mids);   // fp32 arithmetic throughout (drunet_f32.hip)
+  }
+  PNPX_TRY(dru_arena_reserve(N.arena, B, H, W, keep_mids, KEEPS_STAY, "arena",
+                             [&](int images, bool keeps) { return dru_plan(images, H, W, keeps ? N.nb : 0).total; }));
+  const DruPlan Pl = dru_plan(N.arena.capB, H, W, N.arena.keeps ? N.nb : 0);
+  char* const A = static_cast<char*>(N.arena.buf.p);
+  unsigned* const range_flag = ctx->opt_range_guard ? ctx->range_flag_dev : nullptr;
+  const int chains = keep_mids ? 1 : launch_chains(ctx, B, H, W);
+  // The forward over images b0 .. b0 + nB - 1 of the arena on stream st (x / sigma / out already point at the first of them): every
+  // tensor is [image][group][h + 2][w + 2] records, so a slice of the batch is a contiguous piece of each -- independent launch
+  // chains over slices run side by side on side streams exactly as for the UNet (unet.hip: launch_chains; bit-identical per image).
+  auto run = [&](int b0, int nB, const float* x, const float* sigma, float* out, float* out_pre, hipStream_t st) -> int {
+    const DruOffsets o = dru_slice(Pl, b0, [&](int C, int l) { return rec_bytes(C, H >> l, W >> l); });
+    const float* zimg = reinterpret_cast<const float*>(A + Pl.zimg) + (size_t)H * W * b0;
+    const HsForward f{{nB, H, W, st}, N, x, sigma, sigma_stride, out, out_pre, zimg, A + o.P[0], range_flag, chains};
+    return dru_forward_walk(f, A, o, N.nb, H, W, keep_mids);
+  };
   if (chains <= 1) return run(0, B, x, sigma, out, out_pre, s);
   const size_t px = (size_t)H * W;
   return fan_out_chains(ctx, chains, B, s, [&](int lo, int hi, hipStream_t st) -> int {
     return run(lo, hi - lo, x + lo * px, sigma + (size_t)lo * sigma_stride, out + lo * px, out_pre ? out_pre + lo * px : nullptr, st);
   });
 }
-
 
 // ------------------------------------------------------------------------------------------------ VJP
 namespace {
@@ -448,20 +320,58 @@ __global__ __launch_bounds__(256) void dru_tail_mask_kernel(const float* __restr
   g_pre[i] = (p >= 0.f && p <= 1.f) ? g_out[i] * sc->x : 0.f;
 }
 
+// The VJP's launches (dataflow: drunet_net.h dru_backward_walk) on the forward kernels with the adjoint layers (layers_bwd).
+// Gradients are HS8 tensors scaled to max |grad_out| <= 1 (unet_bwd.hip): gscale = {1/m, m}.
+struct HsBackward : HsGlue {
+  const DruNet& N;
+  const float *grad_out, *pre;
+  float *g_pre, *part, *grad_x, *grad_sigma;
+  float2* gscale;
+  unsigned *gmax_bits, *range_flag;
+  char* in0;           // 32-channel output of the head's adjoint
+  const float* zimg;   // zeros: the DRUNet has no input residual
+
+  int conv(int li, const char* in, char* outp, int h, int w, const char* dmask, const char* res) const {
+    const ConvLayerHsDev& D = N.layers_bwd[li];
+    const ConvLayerHs Lh = hs_layer(D, N.zero);
+    ConvHsFuse f;
+    f.slope = dmask ? 0.f : 1.f;
+    f.dmask = dmask;
+    f.res = res;
+    f.range_flag = range_flag;
+    f.wreg = 0;
+    f.taps = N.taps[li];
+    return launch_conv_hs(Lh, in, D.cin_pad / 8, nullptr, 0, outp, B, h, w, f, s);
+  }
+  int seed(char* s0) const {
+    const size_t npix = (size_t)B * H * W;
+    PNPX_HIP(hipMemsetAsync(gmax_bits, 0, sizeof(unsigned), s));
+    hipLaunchKernelGGL(absmax_kernel, dim3(512), dim3(256), 0, s, grad_out, npix, gmax_bits);
+    hipLaunchKernelGGL(grad_scale_kernel, dim3(1), dim3(1), 0, s, gmax_bits, gscale);
+    hipLaunchKernelGGL(dru_tail_mask_kernel, g1(npix), dim3(256), 0, s, grad_out, pre, gscale, g_pre, npix);
+    PNPX_LAUNCH_CHECK();
+    hipLaunchKernelGGL(conv_first_hs_kernel, dim3((H * W + 255) / 256, DRU_NC[0] / 8, B), dim3(256), 0, s, g_pre, N.zero, 0,
+                       N.tail_bwd_w, N.zero, reinterpret_cast<HsRec*>(s0), H, W, 1.0f, HS_ASCALE);
+    PNPX_LAUNCH_CHECK();
+    return PNPX_OK;
+  }
+  // head: 64 -> (image, noise map) gradients; no residual path (g_res = zeros)
+  int input_grad(const char* m0) const {
+    PNPX_TRY(conv(0, m0, in0, H, W, nullptr, nullptr));
+    hipLaunchKernelGGL(input_grad_hs_kernel, dim3(SIG_CHUNKS, B), dim3(256), 0, s, reinterpret_cast<const HsRec*>(in0), zimg, grad_x,
+                       part, gscale, H, W);
+    PNPX_LAUNCH_CHECK();
+    hipLaunchKernelGGL(sigma_grad_final_kernel, dim3((B + 63) / 64), dim3(64), 0, s, part, grad_sigma, B);
+    PNPX_LAUNCH_CHECK();
+    return PNPX_OK;
+  }
+};
+
 }  // namespace
 
-// Back-propagation through  out = clamp(tail(m0), 0, 1)  down to (x, sigma); see the dataflow at the top of this file.
-// Every step is the adjoint of a forward step on the SAME kernels: a 3x3 convolution's adjoint is the convolution with the
-// transposed, tap-flipped weights (layers_bwd); a ResBlock  out = B(relu(A(in))) + in  back-propagates as
-//     g_mid = B^T g_out * 1[mid > 0]   (EPI_DMASK, the saved ReLU output as mask, slope 0)
-//     g_in  = A^T g_mid + g_out        (EPI_RES, linear)
-// the strided 2x2 convolution (s2d + 1x1) as 1x1^T + d2s, the transposed 2x2 convolution (1x1 + d2s) as s2d + 1x1^T; skip
-// sums pass their gradient to both operands.  Gradients are HS8 tensors scaled to max |grad_out| <= 1 (unet_bwd.hip).
 int drunet_denoise_backward(pnpx_ctx* ctx, const float* x, const float* sigma, int sigma_stride, const float* grad_out,
                             float* grad_x, float* grad_sigma, int B, int H, int W, hipStream_t s) {
   DruNet& N = ctx->drunet;
-  if (ctx->conv_mode != CONV_HS)      // fp32 arithmetic throughout (drunet_f32.hip, r5)
-    return drunet_denoise_backward_f32(ctx, x, sigma, sigma_stride, grad_out, grad_x, grad_sigma, B, H, W, s);
   const size_t npix = (size_t)B * H * W;
   void* sp;
   PNPX_TRY(ctx_scratch(ctx, (3 * npix + (size_t)B * SIG_CHUNKS) * sizeof(float) + 8192, &sp));
@@ -472,126 +382,20 @@ int drunet_denoise_backward(pnpx_ctx* ctx, const float* x, const float* sigma, i
   float2* gscale = reinterpret_cast<float2*>(part + (((size_t)B * SIG_CHUNKS + 63) & ~(size_t)63));   // {1/m, m}
   unsigned* gmax_bits = reinterpret_cast<unsigned*>(gscale + 1);
 
-  // 1. forward, keeping the ReLU output of every ResBlock
+  // forward of the context's family, keeping the ReLU output of every ResBlock
   PNPX_TRY(drunet_denoise(ctx, x, sigma, sigma_stride, out_tmp, pre, B, H, W, s, true));
-  const DruPlan F = dru_plan(N.capB, H, W, N.nb);
-  char* const FA = static_cast<char*>(N.arena.p);
-
-  // 2. gradient arena (zero borders: gradients are convolution inputs of the adjoint convolutions)
-  if (B > N.gcapB || H != N.gcapH || W != N.gcapW) {
-    const int nb_img = (H == N.gcapH && W == N.gcapW && N.gcapB > B) ? N.gcapB : B;
-    const DruPlan Gp = dru_plan(nb_img, H, W, 0, true);
-    PNPX_HIP(hipDeviceSynchronize());
-    if (N.arena_grad.bytes < Gp.total) {
-      if (N.arena_grad.p) PNPX_HIP(hipFree(N.arena_grad.p));
-      N.arena_grad = DeviceBuf();
-      N.gcapB = N.gcapH = N.gcapW = 0;
-      void* p = nullptr;
-      hipError_t e = hipMalloc(&p, Gp.total);
-      if (e != hipSuccess) {
-        set_error("DRUNet gradient arena allocation of %zu bytes failed: %s", Gp.total, hipGetErrorString(e));
-        return PNPX_ERR_ALLOC;
-      }
-      N.arena_grad.p = p;
-      N.arena_grad.bytes = Gp.total;
-    }
-    PNPX_HIP(hipMemset(N.arena_grad.p, 0, N.arena_grad.bytes));
-    N.gcapB = nb_img;
-    N.gcapH = H;
-    N.gcapW = W;
-  }
-  const DruPlan G = dru_plan(N.gcapB, H, W, 0, true);
-  char* const GA = static_cast<char*>(N.arena_grad.p);
-  unsigned* const range_flag = ctx->opt_range_guard ? ctx->range_flag_dev : nullptr;
-  const int nb = N.nb;
-
-  // layer indices (state_dict order, dru_layers)
-  auto idx_down = [&](int l) { return 1 + l * (2 * nb + 1); };            // first conv of the encoder ResBlocks of level l
-  auto idx_strided = [&](int l) { return idx_down(l) + 2 * nb; };         // level l -> l + 1
-  const int idx_body = 1 + 3 * (2 * nb + 1);
-  auto idx_convT = [&](int l) { return idx_body + 2 * nb + (2 - l) * (2 * nb + 1); };   // level l + 1 -> l
-  auto idx_up = [&](int l) { return idx_convT(l) + 1; };
-
-  auto conv = [&](int li, const char* in, char* outp, int h, int w, float slope, const char* dmask, const char* res) -> int {
-    const ConvLayerHsDev& D = N.layers_bwd[li];
-    const ConvLayerHs Lh = hs_layer(D, N.zero);
-    ConvHsFuse f;
-    f.slope = slope;
-    f.dmask = dmask;
-    f.res = res;
-    f.range_flag = range_flag;
-    f.wreg = 0;
-    f.taps = N.taps[li];
-    return launch_conv_hs(Lh, in, D.cin_pad / 8, nullptr, 0, outp, B, h, w, f, s);
-  };
-  // adjoint of the nb ResBlocks of (level l, encoder / decoder side) applied to the gradient in `cur`; result pointer returned
-  auto resblocks_bwd = [&](int l, int dec, int idx0, char* cur, char** result) -> int {
-    const int h = H >> l, w = W >> l;
-    char* pq[2] = {GA + G.P[l], GA + G.Q[l]};
-    int k = 0;
-    for (int i = nb - 1; i >= 0; --i) {
-      const char* mid = FA + F.MK[l][dec * nb + i];
-      PNPX_TRY(conv(idx0 + 2 * i + 1, cur, GA + G.M[l], h, w, 0.f, mid, nullptr));     // B^T g_out * relu'(mid)
-      char* dst = pq[k];
-      if (dst == cur) dst = pq[k ^= 1];
-      PNPX_TRY(conv(idx0 + 2 * i, GA + G.M[l], dst, h, w, 1.f, nullptr, cur));         // A^T g_mid + g_out
-      cur = dst;
-      k ^= 1;
-    }
-    *result = cur;
-    return PNPX_OK;
-  };
-  auto add = [&](const char* a, const char* b, char* o, int l) -> int {
-    const int h = H >> l, w = W >> l;
-    const size_t n = (size_t)B * (DRU_NC[l] / 8) * h * w;
-    hipLaunchKernelGGL(dru_add_kernel, g1(n), dim3(256), 0, s, reinterpret_cast<const HsRec*>(a), reinterpret_cast<const HsRec*>(b),
-                       reinterpret_cast<HsRec*>(o), h, w, n);
-    PNPX_LAUNCH_CHECK();
-    return PNPX_OK;
-  };
-
-  // 3. clamp + tail
-  PNPX_HIP(hipMemsetAsync(gmax_bits, 0, sizeof(unsigned), s));
-  hipLaunchKernelGGL(absmax_kernel, dim3(512), dim3(256), 0, s, grad_out, npix, gmax_bits);
-  hipLaunchKernelGGL(grad_scale_kernel, dim3(1), dim3(1), 0, s, gmax_bits, gscale);
-  hipLaunchKernelGGL(dru_tail_mask_kernel, g1(npix), dim3(256), 0, s, grad_out, pre, gscale, g_pre, npix);
-  PNPX_LAUNCH_CHECK();
-  hipLaunchKernelGGL(conv_first_hs_kernel, dim3((H * W + 255) / 256, DRU_NC[0] / 8, B), dim3(256), 0, s, g_pre, N.zero, 0,
-                     N.tail_bwd_w, N.zero, reinterpret_cast<HsRec*>(GA + G.S[0]), H, W, 1.0f, HS_ASCALE);
-  PNPX_LAUNCH_CHECK();
-  // 4. decoder, level 0 up to level 2: G.S[l] = gradient of m_l = c_l + S[l] (kept: it is also the skip's gradient)
-  char* cur = GA + G.S[0];
-  for (int l = 0; l <= 2; ++l) {
-    PNPX_TRY(resblocks_bwd(l, 1, idx_up(l), cur, &cur));                       // -> gradient of U[l]
-    const int h = H >> l, w = W >> l, Gl = DRU_NC[l] / 8;
-    const size_t n = (size_t)B * 4 * Gl * (h / 2) * (w / 2) * 2;
-    hipLaunchKernelGGL(hs_s2d_kernel, g1(n), dim3(256), 0, s, reinterpret_cast<const uint4*>(cur),
-                       reinterpret_cast<uint4*>(GA + G.DT[l + 1]), Gl, h, w, n);   // adjoint of depth-to-space
-    PNPX_LAUNCH_CHECK();
-    PNPX_TRY(conv(idx_convT(l), GA + G.DT[l + 1], GA + G.S[l + 1], h / 2, w / 2, 1.f, nullptr, nullptr));
-    cur = GA + G.S[l + 1];
-  }
-  // 5. body and encoder, level 3 down to level 0: G.M[l] = total gradient of S[l]
-  PNPX_TRY(resblocks_bwd(3, 0, idx_body, cur, &cur));
-  PNPX_TRY(add(cur, GA + G.S[3], GA + G.M[3], 3));
-  for (int l = 2; l >= 0; --l) {
-    const int h = H >> (l + 1), w = W >> (l + 1), Gl = DRU_NC[l] / 8;
-    PNPX_TRY(conv(idx_strided(l), GA + G.M[l + 1], GA + G.DT[l + 1], h, w, 1.f, nullptr, nullptr));
-    const size_t n = (size_t)B * Gl * (2 * h) * (2 * w) * 2;
-    hipLaunchKernelGGL(hs_d2s_kernel, g1(n), dim3(256), 0, s, reinterpret_cast<const uint4*>(GA + G.DT[l + 1]),
-                       reinterpret_cast<uint4*>(GA + G.U[l]), Gl, h, w, n);        // adjoint of space-to-depth
-    PNPX_LAUNCH_CHECK();
-    PNPX_TRY(resblocks_bwd(l, 0, idx_down(l), GA + G.U[l], &cur));
-    PNPX_TRY(add(cur, GA + G.S[l], GA + G.M[l], l));
-  }
-  // 6. head: 64 -> (image, noise map) gradients; no residual path (g_res = zeros)
-  PNPX_TRY(conv(0, GA + G.M[0], GA + G.IN0, H, W, 1.f, nullptr, nullptr));
-  hipLaunchKernelGGL(input_grad_hs_kernel, dim3(SIG_CHUNKS, B), dim3(256), 0, s, reinterpret_cast<const HsRec*>(GA + G.IN0),
-                     reinterpret_cast<const float*>(FA + F.zimg), grad_x, part, gscale, H, W);
-  PNPX_LAUNCH_CHECK();
-  hipLaunchKernelGGL(sigma_grad_final_kernel, dim3((B + 63) / 64), dim3(64), 0, s, part, grad_sigma, B);
-  PNPX_LAUNCH_CHECK();
-  return PNPX_OK;
+  if (ctx->conv_mode != CONV_HS)      // fp32 arithmetic throughout (drunet_f32.hip, r5)
+    return drunet_denoise_backward_f32(ctx, grad_out, pre, g_pre, part, grad_x, grad_sigma, B, H, W, s);
+  const DruPlan F = dru_plan(N.arena.capB, H, W, N.nb);
+  char* const FA = static_cast<char*>(N.arena.buf.p);
+  // gradient arena (zero borders: gradients are convolution inputs of the adjoint convolutions)
+  PNPX_TRY(dru_arena_reserve(N.arena_grad, B, H, W, false, KEEPS_STAY, "gradient arena",
+                             [&](int images, bool) { return dru_plan(images, H, W, 0, true).total; }));
+  const DruPlan G = dru_plan(N.arena_grad.capB, H, W, 0, true);
+  char* const GA = static_cast<char*>(N.arena_grad.buf.p);
+  const HsBackward f{{B, H, W, s}, N, grad_out, pre, g_pre, part, grad_x, grad_sigma, gscale, gmax_bits,
+                     ctx->opt_range_guard ? ctx->range_flag_dev : nullptr, GA + G.IN0, reinterpret_cast<const float*>(FA + F.zimg)};
+  return dru_backward_walk(f, GA, G, FA, F, N.nb, H, W);
 }
 
 }  // namespace pnpx
