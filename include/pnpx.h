@@ -420,6 +420,28 @@ int pnpx_critic_optim_state(pnpx_ctx* ctx, float* exp_avg_dst, float* exp_avg_sq
 /* Forgets the moments and t (the state before the first step).  Synchronises the device. */
 int pnpx_critic_optim_reset(pnpx_ctx* ctx);
 
+/* ---- MDDPG policy loss (tfpnp/trainer/mddpg/trainer.py:174, :179-197) and its backward (:202), ONE launch ------------------
+ * Inputs on the device: p_stop [B][2] (the actor's softmax output), idx_stop [B] int64 (0 = continue; anything else counts as 1 =
+ * stop), v_cur = critic(eval_ob), v_next_target = critic_target(eval_ob2), v_next = critic(eval_ob2), reward (as PnPEnv.forward
+ * returns it: loop_penalty is subtracted here), [B] floats each.  Per row, eps = FLT_EPSILON:
+ *   r = reward - loop_penalty;  g = discount * (1 - idx_stop);  logp = log(max(p_stop[idx_stop], eps));
+ *   ent = -(xlogy(p0, p0) + xlogy(p1, p1));  Qt = g * v_next_target + r;  adv = Qt - v_cur (a constant of the backward pass);
+ *   policy_loss = -(1 / B) * sum(logp * adv + (g * v_next + r) + lambda_e * ent)
+ * Outputs: q_target, log_prob, entropy [B]; scalars [2] = {policy_loss, mean(entropy)}; the gradients of policy_loss:
+ *   grad_v_next [B] = -g / B (exactly zero where idx_stop is 1), grad_reward [B] = -1 / B,
+ *   grad_p_stop [B][2] = lambda_e * (log p_j + 1) / B at both entries, plus -adv / (B * p) at the taken entry where p >= eps
+ *   (clamp_min's backward: nothing where p < eps).
+ * Rows are fp32 in torch's order of operations without contraction (q_target has the bytes of the torch expression); the two sums
+ * are taken in double in a fixed order by one workgroup, without atomics: two calls give the same bytes, whatever the alignment
+ * of the pointers.  At p_j == 0 exactly the forward outputs are finite (xlogy(0, 0) = 0) and torch's gradient is NaN; this call
+ * writes the formula's value there: -inf for lambda_e > 0, NaN for lambda_e == 0, +inf for lambda_e < 0.
+ * PNPX_ERR_ARG with nothing written: B <= 0, a null pointer, a scalar that is not finite.  Keeps no state: ctx only names the
+ * device.  Capturable into a graph. */
+int pnpx_mddpg_policy_loss(pnpx_ctx* ctx, const float* p_stop, const int64_t* idx_stop, const float* v_cur, const float* v_next_target,
+                           const float* v_next, const float* reward, float discount, float loop_penalty, float lambda_e, int B,
+                           float* q_target, float* log_prob, float* entropy, float* scalars, float* grad_p_stop, float* grad_v_next,
+                           float* grad_reward, void* stream);
+
 /* ---- transforms (tfpnp/utils/transforms.py) ------------------------------------------------------ */
 /* fft2 / ifft2 (transforms.py:68-103): centered (ifftshift -> FFT -> fftshift), orthonormal, over the
  * last two image dims of [n_img, H, W, 2].  centered=0 gives the plain torch.fft(x, 2, normalized=True)

@@ -91,6 +91,7 @@ _SIGNATURES = {
     "pnpx_critic_adam_step": (C.c_int, [c_void_p, _P, C.c_size_t] + [C.c_float] * 5 + [_P, c_void_p]),
     "pnpx_critic_optim_state": (C.c_int, [c_void_p, _P, _P, C.c_size_t, C.POINTER(C.c_longlong), c_void_p]),
     "pnpx_critic_optim_reset": (C.c_int, [c_void_p]),
+    "pnpx_mddpg_policy_loss": (C.c_int, [c_void_p] + [_P] * 6 + [C.c_float] * 3 + [C.c_int] + [_P] * 7 + [c_void_p]),
     "pnpx_unet_profile": (C.c_int, [c_void_p, _P, _P, _P, C.c_int, C.c_int, C.c_int, c_void_p, C.c_int,
                                     c_float_p, C.POINTER(C.c_double), C.POINTER(C.c_char_p), C.POINTER(C.c_int)]),
     "pnpx_fft2": (C.c_int, [c_void_p, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_void_p]),

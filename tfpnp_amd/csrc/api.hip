@@ -368,6 +368,16 @@ int pnpx_critic_optim_reset(pnpx_ctx* ctx) {
   return critic_optim_reset(ctx);
 }
 
+int pnpx_mddpg_policy_loss(pnpx_ctx* ctx, const float* p_stop, const int64_t* idx_stop, const float* v_cur, const float* v_next_target,
+                           const float* v_next, const float* reward, float discount, float loop_penalty, float lambda_e, int B,
+                           float* q_target, float* log_prob, float* entropy, float* scalars, float* grad_p_stop, float* grad_v_next,
+                           float* grad_reward, void* stream) {
+  LOCK_CTX(ctx);
+  return mddpg_policy_loss(p_stop, reinterpret_cast<const long long*>(idx_stop), v_cur, v_next_target, v_next, reward, discount,
+                           loop_penalty, lambda_e, B, q_target, log_prob, entropy, scalars, grad_p_stop, grad_v_next, grad_reward,
+                           static_cast<hipStream_t>(stream));
+}
+
 int pnpx_ctx_reserve(pnpx_ctx* ctx, int B, int H, int W) {
   LOCK_CTX(ctx);
   if (B <= 0 || H < 16 || W < 16) {

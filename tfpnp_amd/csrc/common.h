@@ -484,6 +484,11 @@ int critic_optim_state(pnpx_ctx* ctx, float* exp_avg_dst, float* exp_avg_sq_dst,
 int critic_optim_reset(pnpx_ctx* ctx);
 void critic_free(pnpx_ctx* ctx);
 
+// MDDPG policy loss and its gradients, one launch (mddpg_loss.hip); checks its own arguments, keeps no state
+int mddpg_policy_loss(const float* p_stop, const long long* idx_stop, const float* v_cur, const float* v_next_target, const float* v_next,
+                      const float* reward, float discount, float loop_penalty, float lambda_e, int B, float* q_target, float* log_prob,
+                      float* entropy, float* scalars, float* grad_p_stop, float* grad_v_next, float* grad_reward, hipStream_t s);
+
 // FFT building blocks (fft.hip)
 int fft2(pnpx_ctx* ctx, const float* in, float* out, int n_img, int H, int W, bool inverse, bool centered,
          hipStream_t s);

@@ -2,8 +2,8 @@
 return values as tfpnp/env/base.py:43-242, so rollout and evaluation loops written against the reference
 (eval/evaluator.py, the rollout half of trainer/mddpg/trainer.py) drive it unchanged.  Scope: inference / evaluation
 episodes and the differentiable one-step model `forward` (gradients wrt actions through the native VJPs,
-tfpnp_amd/autograd.py).  A trainable actor / critic and the MDDPG trainer are NOT part of this package; the replay memory that
-keeps the observations of `step` on the device is utils/rpm.py.
+tfpnp_amd/autograd.py).  The trainer that drives both is trainer/mddpg/trainer.py::MDDPGTrainer (native actor and critic
+updates, policy loss in one launch); the replay memory that keeps the observations of `step` on the device is utils/rpm.py.
 
 One `step` (base.py:157-191), orchestrated on the device (csrc/env.hip):
   live-row gather of solver state + aux inputs (ONE launch)  ->  native solver loop  ->  write-back of state and output

@@ -736,6 +736,46 @@ def psnr(output, gt, ctx=None):
     return out
 
 
+def mddpg_policy_loss(ctx, p_stop, idx_stop, v_cur, v_next_target, v_next, reward, discount, loop_penalty, lambda_e):
+    """trainer/mddpg/trainer.py:174, :179-197 and the backward of policy_loss in ONE launch (pnpx_mddpg_policy_loss).
+    p_stop [B, 2] fp32; idx_stop [B] int64: 0 = continue, 1 = stop -- the values are not checked (that would be a device read),
+    and any other non-zero value counts as 1, as include/pnpx.h says; v_cur, v_next_target, v_next, reward: B fp32 values each ([B] or [B, 1]),
+    reward as PnPEnv.forward returns it (loop_penalty is subtracted inside).  ctx None: the default context of p_stop's device.
+    -> (q_target [B], log_prob [B], entropy [B], scalars [2] = (policy_loss, mean entropy), grad_p_stop [B, 2], grad_v_next [B],
+    grad_reward [B]): the last three are the gradients of policy_loss.  Wrong lengths, CPU tensors, a wrong dtype and scalars
+    that are not finite raise PnpxError."""
+    named = (("p_stop", p_stop), ("idx_stop", idx_stop), ("v_cur", v_cur), ("v_next_target", v_next_target), ("v_next", v_next),
+             ("reward", reward))
+    for name, t in named:                      # shapes and types first (they need no device), then where the tensors live
+        if not isinstance(t, torch.Tensor):
+            raise PnpxError(f"mddpg_policy_loss: {name}: expected a torch.Tensor, got {type(t).__name__}")
+        want = torch.int64 if name == "idx_stop" else torch.float32
+        if t.dtype != want:
+            raise PnpxError(f"mddpg_policy_loss: {name}: expected {want}, got {t.dtype}")
+    if p_stop.dim() != 2 or p_stop.shape[1] != 2 or p_stop.shape[0] == 0:
+        raise PnpxError(f"mddpg_policy_loss: p_stop must be [B, 2] with B > 0, got {tuple(p_stop.shape)}")
+    B = p_stop.shape[0]
+    for name, t in named[1:]:
+        if t.numel() != B:
+            raise PnpxError(f"mddpg_policy_loss: {name} has {t.numel()} values, p_stop has {B} rows")
+    scal = [float(discount), float(loop_penalty), float(lambda_e)]
+    if not all(np.isfinite(scal)):
+        raise PnpxError(f"mddpg_policy_loss: discount, loop_penalty and lambda_e must be finite, got {scal}")
+    for name, t in named:
+        if t.device.type != "cuda":
+            raise PnpxError(f"mddpg_policy_loss: {name} is on {t.device}; tfpnp_amd has no CPU path")
+        if t.device != p_stop.device:
+            raise PnpxError(f"mddpg_policy_loss: {name} is on {t.device}, p_stop on {p_stop.device}")
+    p_stop, *rows = (t.detach().contiguous() for _, t in named)
+    new = lambda *shape: torch.empty(shape, device=p_stop.device, dtype=torch.float32)
+    outs = (new(B), new(B), new(B), new(2), new(B, 2), new(B), new(B))
+    ctx = ctx or default_context(p_stop.device)
+    with torch.cuda.device(p_stop.device):
+        check(_lib.lib().pnpx_mddpg_policy_loss(ctx.handle, _p(p_stop), *(_p(t) for t in rows), *scal, B,
+                                                *(_p(t) for t in outs), _stream(p_stop)))
+    return outs
+
+
 # ------------------------------------------------------------------------------------------------- solver loops
 def _vars(variables, nvar, complex_):
     v = _f32(variables, "variables")

@@ -31,7 +31,8 @@ clip_grad_norm_ + torch.optim.Adam.step() on the context's own vector followed b
 running statistics are frozen ranges of that vector -- the optimiser neither reads their gradient slots nor moves them -- and
 Adam's moments never leave the context (`optim_state`, `reset_optim_`).  `head(p_stop, det, idx_stop, train)` is the O(B) part of
 `forward`, shared with trainer/mddpg/actor_step.py::actor_update, the actor's half of trainer.py::_update (:171, :201-204).
-Still out of scope: policy_loss itself (environment, critic, advantage: the caller's closure), the MDDPG trainer loop, the
+policy_loss itself (environment, critic, advantage) is one native launch (torch.ops.pnpx.mddpg_policy_loss) inside the closure of
+trainer/mddpg/trainer.py::MDDPGTrainer._update, which is also the trainer loop.  Still out of scope: the
 actor's input gradient, weight decay / amsgrad / other optimisers, loading Adam's moments from a checkpoint, statistics
 synchronised across devices (dist.py), num_batches_tracked (momentum is a number, so torch never reads it), graph capture.
 """

@@ -3,7 +3,7 @@
 Every operator is a thin shim over one C-ABI entry of libpnpx.so (include/pnpx.h, bound in tfpnp_amd/ops.py): schema
 + a ROCm ("cuda") implementation + a fake-tensor (meta) implementation, so the ops trace under FakeTensorMode /
 torch.compile / torch.export, and autograd formulas for the ops the training path differentiates (denoiser VJP, the
-unitary FFTs, the Radon pair, PSNR).  There is no CPU implementation: dispatching a CPU tensor raises
+unitary FFTs, the Radon pair, PSNR, the critic's value, the MDDPG policy loss).  There is no CPU implementation: dispatching a CPU tensor raises
 NotImplementedError from the dispatcher itself.
 
 A native context (packed denoiser weights + workspaces) cannot travel through an operator schema, so ops take an
@@ -638,6 +638,41 @@ def _pack_bwd(ctx, g):
 policy_ob_pack_diff.register_autograd(_pack_bwd, setup_context=_pack_setup)
 
 
+# ------------------------------------------------------------------------------------------------- MDDPG policy loss
+@_lib_def("pnpx::mddpg_policy_loss", mutates_args=(), device_types="cuda")
+def mddpg_policy_loss(p_stop: Tensor, idx_stop: Tensor, v_cur: Tensor, v_next_target: Tensor, v_next: Tensor, reward: Tensor,
+                      discount: float, loop_penalty: float, lambda_e: float) -> Tuple[Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor]:
+    """trainer/mddpg/trainer.py:174, :179-197 in one launch -> (scalars [2] = (policy_loss, mean entropy), q_target [B],
+    log_prob [B], entropy [B], grad_p_stop [B,2], grad_v_next [B], grad_reward [B]).  Differentiable through scalars[0] only, with
+    respect to p_stop, v_next and reward (the advantage is detached, :186): its backward scales the three gradient outputs, which
+    the same launch wrote.  The mean-entropy slot is a diagnostic (:214) and carries no gradient."""
+    q, logp, ent, scalars, gp, gv, gr = ops.mddpg_policy_loss(None, p_stop, idx_stop, v_cur, v_next_target, v_next, reward,
+                                                              discount, loop_penalty, lambda_e)
+    return scalars, q, logp, ent, gp, gv, gr
+
+
+@mddpg_policy_loss.register_fake
+def _(p_stop, idx_stop, v_cur, v_next_target, v_next, reward, discount, loop_penalty, lambda_e):
+    B = p_stop.shape[0]
+    e = lambda *shape: torch.empty(shape, dtype=torch.float32, device=p_stop.device)
+    return e(2), e(B), e(B), e(B), e(B, 2), e(B), e(B)
+
+
+def _mddpg_loss_setup(ctx, inputs, output):
+    ctx.save_for_backward(*output[4:])
+    ctx.shapes = (inputs[4].shape, inputs[5].shape)
+    ctx.mark_non_differentiable(*output[1:])
+
+
+def _mddpg_loss_bwd(ctx, g, *_unused):
+    gp, gv, gr = ctx.saved_tensors
+    s = g[0]                                   # d / d policy_loss; the mean-entropy slot g[1] is not differentiated
+    return (s * gp, None, None, None, (s * gv).view(ctx.shapes[0]), (s * gr).view(ctx.shapes[1]), None, None, None)
+
+
+mddpg_policy_loss.register_autograd(_mddpg_loss_bwd, setup_context=_mddpg_loss_setup)
+
+
 def call(name, *args):
     """torch.ops.pnpx.<name>(*args) with the package's error contract: tensors that are not on a ROCm device raise
     PnpxError (there is no CPU kernel to dispatch to) instead of the dispatcher's NotImplementedError."""
@@ -653,4 +688,5 @@ ALL_OPS = ("unet_denoise", "unet_denoise_preclamp", "unet_denoise_backward", "un
            "cdp_backward", "spi_inverse", "psnr", "radon_forward", "radon_backprojection", "csmri_admm", "csmri_admm_train",
            "csmri_admm_backward", "csmri_hqs", "csmri_amp",
            "csmri_pg", "csmri_apg", "csmri_redadmm", "pr_iadmm", "spi_admm", "ct_iadmm", "ct_pg", "pr_pg",
-           "critic_value", "critic_backward", "critic_param_grad", "critic_value_loss_grad", "policy_ob_pack_diff", "policy_ob_unpack")
+           "critic_value", "critic_backward", "critic_param_grad", "critic_value_loss_grad", "policy_ob_pack_diff", "policy_ob_unpack",
+           "mddpg_policy_loss")

@@ -20,8 +20,9 @@ backward() from ONE forward (pnpx_critic_value_loss_grad), and `adam_step_(grad,
 torch.optim.Adam.step() on the context's own parameter vector followed by the re-pack (pnpx_critic_adam_step): the
 parameters and Adam's moments never leave the native context, no torch optimiser is involved (`optim_state`,
 `reset_optim_`; trainer/mddpg/critic_step.py::critic_update is the critic's half of trainer.py::_update).
-Out of scope: the actor's loss, weight decay / amsgrad / other optimisers, checkpointing the moments
-(the reference's save_model does not save them either), a graph-capturable step, the MDDPG trainer loop, depths other
+policy_loss (one launch, csrc/mddpg_loss.hip) and the MDDPG trainer loop that joins the two updates are trainer.py::MDDPGTrainer.
+Out of scope: weight decay / amsgrad / other optimisers, checkpointing the moments
+(the reference's save_model does not save them either), a graph-capturable step, depths other
 than 18.  (The native actor has the same live weights and the same optimiser step: policy/network.py, trainer/mddpg/actor_step.py; the replay memory is utils/rpm.py.)
 """
 import torch
