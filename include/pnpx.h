@@ -702,6 +702,20 @@ int pnpx_winof4_pack(const float* w, int cout, int cin, float* dst);
 /* ... and the packer of the kernel's 32-cout instance (cout % 32 == 0): [cout/32][cin/8][stage 3][row 2][column pair 3][cout block 2]
  * [channel group 4][cout 16][k-step 2][column 2], positions and channels numbered as above. */
 int pnpx_winof4_c32_pack(const float* w, int cout, int cin, float* dst);
+/* ... and the plan by which an instance (0 plain, 1 two-source entry, 2 up-sampling entry, 3 32-cout) fetches one 8-channel chunk's halo
+ * into LDS at image size H x W, from the tables the kernels themselves use.  Host only.  info[PNPX_WINOF4_HALO_INFO]: 0 the instance
+ * gathers 16-byte units, 1 cout tile, 2 region width RW, 3 LDS row stride (floats), 4 LDS plane stride (floats), 5 first padded column of the
+ * fetched window, counted from x0 for a region whose first pixel is image column x0 (the chunk's origin is channel 0, padded row y0,
+ * padded column x0 + info[5]; image column x lies at padded column x + 4), 6 LDS column of halo column 0, 7 gather instructions per chunk, 8 of which 16-byte ones
+ * (the first), 9 most gathers a wave issues, 10 fewest (what the waits count), 11 bytes of a halo buffer, 12 LDS offset of halo buffer
+ * 0, 13 LDS bytes used, 14 weight LDS-DMA instructions every wave issues per stage, 15 staging gathers every wave issues (instance 2),
+ * 16 .. 19 the vmcnt immediates: weight slice alone, + halo gathers, + staging gathers, + both (-1: the instance has none such; the
+ * 32-cout instance: 0 and the halo gathers alone).  Per (instruction i, lane l), at [64 i + l]: src = byte offset of the lane's source
+ * from the chunk's origin, dst = byte offset in the halo buffer, width = bytes moved, wave = issuing wave, real = 0 for a dummy lane (it
+ * reads the origin and lands where nothing reads).  read[(c * 18 + hy) * (RW + 2) + hx] = byte offset in the halo buffer from which the
+ * input transform reads halo element (channel c, row hy, column hx).  The arrays may all be NULL (info alone). */
+#define PNPX_WINOF4_HALO_INFO 20
+int pnpx_winof4_halo_plan(int inst, int H, int W, int* info, long long* src, int* dst, int* width, int* wave, int* real, int* read);
 
 /* Single-layer probe of the fp32 3x3 convolution kernels of conv_mode 0 (csrc/conv_probe.hip), for tests: one layer's HOST weights are
  * packed by the packers pnpx_unet_load uses and ONE kernel of the chosen kind runs on DEVICE tensors the caller laid out in the denoiser's

@@ -173,6 +173,7 @@ _SIGNATURES = {
     "pnpx_conv_f32_entry_plan": (C.c_int, [C.c_int] * 9),
     "pnpx_conv_f32_forward_plan": (C.c_int, [C.c_int] * 9),
     "pnpx_winof4_c32_pack": (C.c_int, [c_void_p, C.c_int, C.c_int, c_void_p]),
+    "pnpx_winof4_halo_plan": (C.c_int, [C.c_int] * 3 + [c_void_p] * 7),
     "pnpx_conv_hs_probe": (C.c_int, [c_void_p, c_void_p, c_void_p]),
     "pnpx_conv_hs_probe_plan": (C.c_int, [c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int)]),
     "pnpx_vjp_glue_probe": (C.c_int, [c_void_p, c_void_p, c_void_p]),

@@ -23,9 +23,20 @@
 // Pipeline.  8-channel chunks, two position rows per stage = 3 stages per chunk, 24 MFMAs per wave and stage (12 positions x 2 k-steps),
 // operands as 16-byte LDS reads (two positions x two k-steps each).  LDS: weights 3 x 24 KiB (ring, stage s of every chunk = slot s, fetched
 // two stages ahead by 16-byte LDS-DMA), V 3 x 12 KiB (stage s = slot s, written one stage ahead by the input transform), raw halo
-// 2 x 22.75 KiB (18 x 34 per channel in rows of 40 + 2 floats per plane: the transform's 8-byte reads are then conflict-free; dword
-// LDS-DMA gathers, fetched three stages ahead).  One counted vmcnt wait and one barrier per stage.  The accumulators and the stage
+// 2 x 23 KiB, fetched three stages ahead by LDS-DMA.  One counted vmcnt wait and one barrier per stage.  The accumulators and the stage
 // schedule are the compiler's (MFMA builtins; at two waves per SIMD every value lives in the 256 architectural VGPRs, there are no AGPRs).
+//
+// Halo.  An LDS-DMA piece costs its issue slot whatever its width, so the halo of a chunk is fetched as 16-byte row gathers of the
+// ALIGNED super-window: padded columns x0 .. x0 + RW + 7 (x0 a multiple of the region width, Wp and Hp Wp multiples of 4: every unit is
+// 16-byte aligned at both ends and stays inside the padded plane) of rows y0 .. y0 + 17, 10 / 18 units per row, planes 18 rows + 16
+// floats apart (= 32 mod 64 banks: the transform's 16-byte reads are conflict-free).  A chunk's LDS image is one linear run: 22 / 40
+// whole 16-byte instructions (64 units = 1 KiB) and 4 dword instructions for the rest = 26 / 44 per chunk where the dword form (18 x 34
+// / 18 x 66 per channel in rows of 40 / 72, + 2 floats per plane, the halo columns alone) needs 91 / 163; halo column hx sits at LDS
+// column hx + 3, and the transform reads a tile's six columns as 8 + 16 + 8 bytes (12 LDS cycles a row against the dword form's 6: the
+// one cost the form adds).  GeoF4 holds both forms and the plan (which lane moves what where) as host-visible functions
+// (pnpx_winof4_halo_plan; tests/test_winof4_halo_host.py); the plain, two-source and 32-cout instances carry the 16-byte form, the
+// up-sampling instance the dword form (WINOF4_H16 below).  What remains for these kernels: the weight ring (one stage of lead in the
+// 32-cout kernel, weights re-fetched per region) and, for F(2x2), the 32-cout tile's LDS budget.
 #include <cmath>
 #include <mutex>
 #include <utility>
@@ -44,24 +55,63 @@ using namespace wino;
 
 // Geometry of an instance: a workgroup owns CT couts x a region of 16 x RW px = RW tiles of 4 x 4 (4 tile rows x RW / 4 tile columns)
 // and keeps rings of NS weight stages and NS V stages in front of two raw halo buffers.  (64, 32, 3) / (32, 64, 2) in the comments.
-template <int CT_, int RW_, int NS>
+template <int CT_, int RW_, int NS, bool H16_>
 struct GeoF4 {
   static constexpr int CT = CT_, RW = RW_, CK = 8;
-  static constexpr int RWL = RW + 8;                      // LDS row stride of the halo (RW + 2 used): tile rows land 32 banks apart (4 * RWL = 32 mod 64)
-  static constexpr int RPXL = 18 * RWL + 2;               // LDS plane stride: odd channels land on the bank pairs the even ones leave free
-  static constexpr int RAW_ELEMS = CK * RPXL;
-  static constexpr int RAW_INSTR = (RAW_ELEMS + 63) / 64; // dword gathers of 64 lanes: 91 / 163
-  static constexpr int RAW_BYTES = RAW_INSTR * 256;       // 23296 / 41728
-  static constexpr int RAW_PER_WAVE = (RAW_INSTR + 7) / 8;   // 12 / 21, of which the last exists for the first RAW_INSTR % 8 waves only
-  static constexpr int NRAW = RAW_INSTR / 8;                 // 11 / 20: gathers every wave issues
+  static constexpr bool H16 = H16_;                       // the halo as 16-byte row gathers of the aligned super-window (below), else as dword gathers
+  static constexpr int RWL = RW + 8;                      // LDS row stride of the halo: tile rows land 32 banks apart (4 * RWL = 32 mod 64)
+  // The fetched window.  Dword gathers: padded columns x0 + 3 .. of a region at x0 = the RW + 2 halo columns themselves.  16-byte gathers:
+  // padded columns x0 .. x0 + RWL - 1, whole rows of RWL / 4 aligned units (x0 is a multiple of RW, Wp and Hp Wp of 4; the window ends at
+  // Wp - 1 in the last region); halo column hx then sits at LDS column hx + 3.
+  static constexpr int ORG = H16 ? 0 : PADL - 1;          // padded column of the window's column 0, from x0
+  static constexpr int HCOL = PADL - 1 - ORG;             // LDS column of halo column 0
+  // LDS plane stride.  Dword form: + 2, odd channels land on the bank pairs the even ones leave free (8-byte reads).  16-byte form: = 32
+  // mod 64, the transform's 16-byte reads of a lane group (8 tiles x an even and an odd channel) then cover all 64 banks once.
+  static constexpr int RPXL = 18 * RWL + (H16 ? 16 : 2);
+  static constexpr int RAW_ELEMS = H16 ? (CK - 1) * RPXL + 18 * RWL : CK * RPXL;      // floats the gathers cover (16-byte form: not the last plane's slack)
+  static constexpr int N16 = H16 ? RAW_ELEMS / 256 : 0;                               // whole 16-byte gathers (64 units = 1 KiB): 22 / 40
+  static constexpr int N4 = (RAW_ELEMS - 256 * N16 + 63) / 64;                        // dword gathers of the rest: 4 / 4 (dword form: 91 / 163)
+  static constexpr int RAW_INSTR = N16 + N4;                 // 26 / 44 (dword form: 91 / 163); instruction i is wave i % 8's gather i / 8
+  static constexpr int RAW_BYTES = N16 * 1024 + N4 * 256;    // 23552 / 41984 (23296 / 41728): a chunk's image is one linear run
+  static constexpr int RAW_PER_WAVE = (RAW_INSTR + 7) / 8;   // 4 / 6 (12 / 21), of which the last exists for the first RAW_INSTR % 8 waves only
+  static constexpr int NRAW = RAW_INSTR / 8;                 // 3 / 5 (11 / 20): gathers every wave issues = what the counted waits assume
   static constexpr int USTG = 2 * 6 * CK * CT * 4;        // bytes of one stage of weights (two position rows): 24 / 12 KiB
   static constexpr int VSTG = 2 * 6 * CK * RW * 4;        // bytes of one stage of V: 12 / 24 KiB
   static constexpr int UCP = USTG / 6, VCP = VSTG / 6;    // ... of one column pair of a position row: 16 bytes per lane and 16-cout / 16-tile block
   static constexpr int OFF_U = 0, OFF_V = NS * USTG, OFF_RAW = OFF_V + NS * VSTG;
-  static constexpr int LDS_USED = OFF_RAW + 2 * RAW_BYTES;   // 157184 / 157184
+  static constexpr int LDS_USED = OFF_RAW + 2 * RAW_BYTES;   // 157696 / 157696
+  static_assert(RPXL % 4 == 0 || !H16, "16-byte units must not straddle planes");
+  static_assert(RAW_PER_WAVE <= NRAW + 1 && NRAW >= 1, "the waits count NRAW gathers per wave; a wave issues at most one more");
+
+  // -- the halo plan, shared by the kernels and the host (pnpx_winof4_halo_plan).  Instruction i writes a linear run of 64 lanes x
+  // width(i) bytes at dst(i) of the halo buffer; lane's piece starts at float first(i, lane) of the buffer's image.
+  static constexpr __host__ __device__ int width(int i) { return i < N16 ? 16 : 4; }
+  static constexpr __host__ __device__ int dst(int i) { return i < N16 ? i * 1024 : N16 * 1024 + (i - N16) * 256; }
+  static constexpr __host__ __device__ int first(int i, int lane) { return dst(i) / 4 + lane * (width(i) / 4); }
+  // byte offset of lane's source from the chunk's origin (channel 0, padded row y0, padded column x0 + ORG); lanes in the rows' and
+  // planes' slack or behind the last plane are dummies: they read the origin itself and land where nothing reads
+  static __host__ __device__ unsigned src(int i, int lane, int HpWp, int Wp, bool* real = nullptr) {
+    const int f = first(i, lane);
+    const int c = f / RPXL, r = f - c * RPXL;
+    const int hy = r / RWL, col = r - hy * RWL;
+    const bool ok = c < CK && hy < 18 && (H16 || col < RW + 2);
+    if (real) *real = ok;
+    return ok ? 4u * (unsigned)(c * HpWp + hy * Wp + col) : 0u;
+  }
+  // byte offset in the halo buffer of halo element (channel c of the chunk, row hy, column hx): where the transform reads it
+  static constexpr __host__ __device__ int at(int c, int hy, int hx) { return (c * RPXL + hy * RWL + hx + HCOL) * 4; }
 };
-struct CfgF4 : GeoF4<64, 32, 3> {
-  static constexpr int NUW = USTG / 8192;                 // 16-byte LDS-DMA instructions per wave and stage: 3
+// Which instances carry the 16-byte gathers: a compile-time property of the instance, no run-time option.  The plain, the two-source
+// and the 32-cout instance do; the up-sampling instance (bit 2) gathers only its first source's chunks, did not gain and keeps the
+// dword form (profiles/winof4_halo16.md has the per-layer rows).  -DWINOF4_H16=mask: timing A/B builds.
+#ifndef WINOF4_H16
+#define WINOF4_H16 11
+#endif
+constexpr bool H16_PLAIN = WINOF4_H16 & 1, H16_ENTRY = WINOF4_H16 & 2, H16_UPS = WINOF4_H16 & 4, H16_C32 = WINOF4_H16 & 8;
+template <bool H16>
+struct CfgF4T : GeoF4<64, 32, 3, H16> {
+  using G = GeoF4<64, 32, 3, H16>;
+  static constexpr int NUW = G::USTG / 8192;              // 16-byte LDS-DMA instructions per wave and stage: 3
   // UPS instance: a V ring of TWO slots (below) makes room for two staging windows of the low-resolution second source -- 11 rows x 20
   // columns per channel, [channel quad 2][row][column][channel 4] so that a halo pixel's tap is one 16-byte read per quad -- and the
   // per-tile interpolation tables (18 halo rows + 34 halo columns, 16 bytes each)
@@ -71,8 +121,12 @@ struct CfgF4 : GeoF4<64, 32, 3> {
   static constexpr int ST_STRIDE = ST_INSTR * 256;           // 7168
   static constexpr int ST_PER_WAVE = (ST_INSTR + 7) / 8;     // 4, of which the last exists for the first ST_INSTR % 8 waves only
   static constexpr int NST = ST_INSTR / 8;                   // 3: gathers every wave issues
-  static constexpr int OFF_RAW_UPS = OFF_V + 2 * VSTG, OFF_ST = OFF_RAW_UPS + 2 * RAW_BYTES, OFF_TAB = OFF_ST + 2 * ST_STRIDE;
-  static constexpr int LDS_USED_UPS = OFF_TAB + (18 + 34) * 16;   // 160064
+  static constexpr int OFF_RAW_UPS = G::OFF_V + 2 * G::VSTG, OFF_ST = OFF_RAW_UPS + 2 * G::RAW_BYTES, OFF_TAB = OFF_ST + 2 * ST_STRIDE;
+  static constexpr int LDS_USED_UPS = OFF_TAB + (18 + 34) * 16;   // 160576 (dword form: 160064)
+  // VMEM operations a stage may leave in flight, per wave and the smallest any wave issues: its own weight slice and, around stage 2,
+  // the halo gathers / (UPS) staging gathers issued behind it.  vmcnt counts loads and LDS-DMA alike, in issue order.
+  static constexpr int WAIT_U = NUW, WAIT_HALO = NUW + G::NRAW, WAIT_ST = NUW + NST, WAIT_HALO_ST = NUW + G::NRAW + NST;
+  static_assert(WAIT_HALO_ST <= 63, "vmcnt is six bits");
 };
 constexpr int LDS_REQF4 = 160 * 1024;
 // -DWINOF4_ABL=bits (timing only, results wrong; tools/build_variant.sh): 1 no input transform, 2 no halo gathers, 4 no weight DMA,
@@ -80,7 +134,12 @@ constexpr int LDS_REQF4 = 160 * 1024;
 #ifndef WINOF4_ABL
 #define WINOF4_ABL 0
 #endif
-static_assert(CfgF4::LDS_USED <= LDS_REQF4 && CfgF4::LDS_USED_UPS <= LDS_REQF4, "LDS budget");
+// -DWINOF4_HSTEP=n (timing A/B of placements): 16-byte halo gather k of a wave stands n MFMAs behind gather k - 1; 0 = the shipped placement
+#ifndef WINOF4_HSTEP
+#define WINOF4_HSTEP 0
+#endif
+static_assert(CfgF4T<false>::LDS_USED <= LDS_REQF4 && CfgF4T<false>::LDS_USED_UPS <= LDS_REQF4 && CfgF4T<true>::LDS_USED <= LDS_REQF4 &&
+              CfgF4T<true>::LDS_USED_UPS <= LDS_REQF4, "LDS budget");
 
 // row A of B^T applied to six values (points 0, +-1, +-1/2, inf; winof4_mats.h WINOF4_BT)
 template <int A>
@@ -138,7 +197,7 @@ __device__ __forceinline__ Tile decode_tile(const WinoArgs& a, const Walk& wk, i
   T.b = t2;
   T.x0 = tx * C::RW;
   T.y0 = ty * 16;
-  T.s0 = a.in0 + (size_t)T.b * a.C0 * HpWp + (size_t)T.y0 * a.Wp + T.x0 + (PADL - 1);
+  T.s0 = a.in0 + (size_t)T.b * a.C0 * HpWp + (size_t)T.y0 * a.Wp + T.x0 + C::ORG;
   T.w = a.u + (size_t)T.ct * a.nch * 3 * (C::USTG / 4);
   return T;
 }
@@ -148,8 +207,8 @@ __device__ __forceinline__ void sync_all() {
   __builtin_amdgcn_s_barrier();
 }
 
-// -- halo gather by dword LDS-DMA, an eighth per wave: per-lane byte offsets of the halo elements from the chunk's origin (lanes in the
-// rows' and planes' slack read the origin itself); raw0 = LDS address of halo buffer 0
+// -- halo gather by LDS-DMA, an eighth per wave, after the geometry's plan (C::src / C::dst / C::width): instruction wave + 8 k is the
+// wave's gather k, 16 bytes per lane while whole ones last and dwords for the rest; raw0 = LDS address of halo buffer 0
 template <class C>
 struct HaloGather {
   unsigned roff[C::RAW_PER_WAVE];
@@ -157,16 +216,15 @@ struct HaloGather {
   int wave;
   __device__ __forceinline__ HaloGather(const WinoArgs& a, int HpWp, unsigned raw0_, int wave_, int lane) : raw0(raw0_), wave(wave_) {
 #pragma unroll
-    for (int k = 0; k < C::RAW_PER_WAVE; ++k) {
-      const int idx = (wave + 8 * k) * 64 + lane;
-      const int c = idx / C::RPXL, r = idx - c * C::RPXL;
-      const int hy = r / C::RWL, hx = r - hy * C::RWL;
-      roff[k] = (c < C::CK && hy < 18 && hx < C::RW + 2) ? 4u * (unsigned)(c * HpWp + hy * a.Wp + hx) : 0u;
-    }
+    for (int k = 0; k < C::RAW_PER_WAVE; ++k) roff[k] = C::src(wave + 8 * k, lane, HpWp, a.Wp);
   }
   __device__ __forceinline__ void piece(const float* src, int rbuf, int k) const {      // gather k (of RAW_PER_WAVE per wave) of one chunk's halo
     if (WINOF4_ABL & 2) return;
-    if (k < C::NRAW || wave + 8 * k < C::RAW_INSTR) glds4(src, roff[k], raw0 + rbuf * C::RAW_BYTES + (wave + 8 * k) * 256);
+    const int i = wave + 8 * k;
+    if (k >= C::NRAW && i >= C::RAW_INSTR) return;
+    const unsigned to = raw0 + rbuf * C::RAW_BYTES + C::dst(i);
+    if (8 * k + 7 < C::N16 || (8 * k < C::N16 && i < C::N16)) glds16(src, roff[k], to);      // (the wave's index is uniform: a scalar branch)
+    else glds4(src, roff[k], to);
   }
   __device__ __forceinline__ void all(const float* src, int rbuf) const {
 #pragma unroll
@@ -174,22 +232,36 @@ struct HaloGather {
   }
 };
 
-// -- input transform of one tile and one channel: position row A of B^T d B from the tile's 6 x 6 halo window at rb (rows RWL floats
-// apart) to vb, the three column pairs VCP bytes apart
-template <int A, int RWL, int VCP>
+// -- input transform of one tile and one channel: position row A of B^T d B from the tile's 6 x 6 halo window at rb = C::at(channel,
+// 4 tile row, 4 tile column) (rows RWL floats apart) to vb, the three column pairs VCP bytes apart.  Dword-gathered halo: the window's
+// row starts 8-byte aligned, three 8-byte reads.  16-byte-gathered halo: it starts at LDS column 3 mod 4, so 8 bytes (second half used)
+// + an aligned 16 + 8 (first half used); two 4-byte reads instead of the 8-byte ones would run four-way into banks (a / 4) mod 32.
+template <int A, class C>
 __device__ __forceinline__ void transform_tile(const char* rb, char* vb) {
+  constexpr int RWL = C::RWL, VCP = C::VCP;
   float d[6][6];
 #pragma unroll
   for (int y = 0; y < 6; ++y) {
     const bool need = (A == 0) ? (y % 2 == 0) : (A == 5) ? (y % 2 == 1) : (y >= 1 && y <= 4);
+    if (!need) {
 #pragma unroll
-    for (int x = 0; x < 6; x += 2) {
-      if (need) {
+      for (int x = 0; x < 6; ++x) d[y][x] = 0.f;
+    } else if constexpr (C::H16) {
+      const f32x2 l = *reinterpret_cast<const f32x2*>(rb + (y * RWL - 1) * 4);
+      const f32x4 m = *reinterpret_cast<const f32x4*>(rb + (y * RWL + 1) * 4);
+      const f32x2 r = *reinterpret_cast<const f32x2*>(rb + (y * RWL + 5) * 4);
+      d[y][0] = l[1];
+      d[y][1] = m[0];
+      d[y][2] = m[1];
+      d[y][3] = m[2];
+      d[y][4] = m[3];
+      d[y][5] = r[0];
+    } else {
+#pragma unroll
+      for (int x = 0; x < 6; x += 2) {
         const f32x2 v = *reinterpret_cast<const f32x2*>(rb + (y * RWL + x) * 4);
         d[y][x] = v[0];
         d[y][x + 1] = v[1];
-      } else {
-        d[y][x] = d[y][x + 1] = 0.f;
       }
     }
   }
@@ -281,14 +353,18 @@ __device__ __forceinline__ void epilogue_tile(const WinoArgs& a, const f32x4 (&a
 // 4-7 of them) and stage 1 (pixels 512 .. 611, two channels per thread) of the chunk before -- every wave the same amount.  From the
 // halo buffer on nothing differs.  The V ring has two slots here (stage g reads slot g & 1 and writes the other one; the barrier between
 // two stages separates a slot's last read from its next write), which is where the staging windows' LDS comes from.
-template <bool TWO, bool UPS = false>
+template <bool TWO, bool UPS = false, bool H16 = false>
 __global__ __launch_bounds__(512, 1) void conv3x3_winof4_f32_kernel(WinoArgs a) {
   static_assert(TWO || !UPS, "the up-sampled source is the second one");
-  using C = CfgF4;
-  constexpr int CK = C::CK, RWL = C::RWL, RPXL = C::RPXL, RAW_BYTES = C::RAW_BYTES, RAW_PER_WAVE = C::RAW_PER_WAVE;
+  using C = CfgF4T<H16>;
+  constexpr int CK = C::CK, RPXL = C::RPXL, RAW_BYTES = C::RAW_BYTES, RAW_PER_WAVE = C::RAW_PER_WAVE;
   constexpr int USTG = C::USTG, NUW = C::NUW, VSTG = C::VSTG, OFF_U = C::OFF_U, OFF_V = C::OFF_V, OFF_RAW = UPS ? C::OFF_RAW_UPS : C::OFF_RAW;
   constexpr int SC = C::SC, QPLANE = C::QPLANE, ST_STRIDE = C::ST_STRIDE, ST_PER_WAVE = C::ST_PER_WAVE, OFF_ST = C::OFF_ST, OFF_TAB = C::OFF_TAB;
   constexpr int UQ = USTG / 4;      // floats per weight stage
+  // stage 2's halo gathers stand behind MFMAs 4, 4 + HSTEP, ..: the few 16-byte ones spread (UPS: short of the staging pieces at 16),
+  // the dword ones one behind each MFMA as they always did
+  constexpr int HSTEP = !H16 ? 1 : WINOF4_HSTEP > 0 ? WINOF4_HSTEP : UPS ? 3 : 4;
+  static_assert(4 + HSTEP * (RAW_PER_WAVE - 1) < (UPS && H16 ? 16 : 24), "halo pieces behind the stage's MFMAs");
   extern __shared__ __attribute__((aligned(16))) char lds[];
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -323,7 +399,7 @@ __global__ __launch_bounds__(512, 1) void conv3x3_winof4_f32_kernel(WinoArgs a) 
       T.s1 = a.in1 + (size_t)T.b * a.C1 * hpwp_lo + (size_t)T.rs * wp_lo + T.cs;
     } else {
       T.rs = T.cs = 0;
-      T.s1 = TWO ? a.in1 + (size_t)T.b * a.C1 * HpWp + (size_t)T.y0 * a.Wp + T.x0 + (PADL - 1) : nullptr;
+      T.s1 = TWO ? a.in1 + (size_t)T.b * a.C1 * HpWp + (size_t)T.y0 * a.Wp + T.x0 + C::ORG : nullptr;
     }
     return T;
   };
@@ -400,7 +476,7 @@ __global__ __launch_bounds__(512, 1) void conv3x3_winof4_f32_kernel(WinoArgs a) 
     const f32x4 ct = *reinterpret_cast<const f32x4*>(lds + OFF_TAB + (18 + hxi) * 16);
     const bool inside = rt[1] >= 0.f && ct[1] >= 0.f;
     const int r0 = __float_as_int(rt[0]), r1 = __float_as_int(rt[3]), c0 = __float_as_int(ct[0]), c1 = __float_as_int(ct[3]);
-    char* ob = lds + OFF_RAW + rbuf * RAW_BYTES + (hyi * RWL + hxi) * 4;
+    char* ob = lds + OFF_RAW + rbuf * RAW_BYTES + C::at(0, hyi, hxi);
     if (STEP < 2) {
       const char* sb = lds + OFF_ST + sbuf * ST_STRIDE + STEP * QPLANE;
       const f32x4 v00 = *reinterpret_cast<const f32x4*>(sb + r0 + c0), v01 = *reinterpret_cast<const f32x4*>(sb + r0 + c1);
@@ -431,12 +507,12 @@ __global__ __launch_bounds__(512, 1) void conv3x3_winof4_f32_kernel(WinoArgs a) 
   // tile block.  Channel = 2 * group + k-step bit (the MFMA's k index is the group).
   const int t_ks = lane & 1, t_t16 = (lane >> 1) & 15, t_kq = (lane >> 5) | ((sw & 1) << 1), t_wn = sw >> 1;
   const int t_tile = t_wn * 16 + t_t16;
-  const int t_rd = ((2 * t_kq + t_ks) * RPXL + 4 * (t_tile >> 3) * RWL + 4 * (t_tile & 7)) * 4;
+  const int t_rd = C::at(2 * t_kq + t_ks, 4 * (t_tile >> 3), 4 * (t_tile & 7));
   const int t_wr = (P * 3 * 2 + t_wn) * 1024 + (t_kq * 16 + t_t16) * 16 + t_ks * 8;       // + column pair * 2048 (+ slot)
   auto transform_row = [&](auto s_tag, int rbuf, int vslot_ups = 0) {      // this thread's row of stage S's two, into V slot S (UPS: vslot_ups)
     constexpr int S = decltype(s_tag)::value;
     if (WINOF4_ABL & 1) return;
-    transform_tile<2 * S + P, RWL, C::VCP>(lds + OFF_RAW + rbuf * RAW_BYTES + t_rd, lds + OFF_V + (UPS ? vslot_ups : S) * VSTG + t_wr);
+    transform_tile<2 * S + P, C>(lds + OFF_RAW + rbuf * RAW_BYTES + t_rd, lds + OFF_V + (UPS ? vslot_ups : S) * VSTG + t_wr);
   };
 
   // -- MFMA operands: 16 bytes = (k-step 2) x (position 2 of a column pair) per lane; lane = 16 * channel group + cout / tile of the block
@@ -459,11 +535,11 @@ __global__ __launch_bounds__(512, 1) void conv3x3_winof4_f32_kernel(WinoArgs a) 
       }
     };
     // the stage's LDS-DMA pieces, one behind each MFMA (their issue cost then runs under the MFMAs): the weight slice behind MFMAs
-    // 0 .. 2, stage 2's halo gathers behind 4 .. 15 (UPS: when the chunk after next is gathered) and, UPS, the staging window of the
-    // chunk three ahead behind 16 .. 19
+    // 0 .. 2, stage 2's halo gathers behind 4, 4 + HSTEP .. (UPS: when the chunk after next is gathered) and, UPS, the staging window
+    // of the chunk three ahead behind 16 .. 19
     auto piece = [&](int m) {
       if (m < NUW) dma_u_piece(u_src, (S + 2) % 3, m);
-      if (S == 2 && m >= 4 && m < 4 + RAW_PER_WAVE && (!UPS || x.raw)) halo.piece(raw_src, raw_buf, m - 4);
+      if (S == 2 && m >= 4 && (m - 4) % HSTEP == 0 && (m - 4) / HSTEP < RAW_PER_WAVE && (!UPS || x.raw)) halo.piece(raw_src, raw_buf, (m - 4) / HSTEP);
       if constexpr (UPS) {
         if (S == 2 && m >= 16 && m < 16 + ST_PER_WAVE && x.st) dma_st_piece(x.st_src, x.st_buf, m - 16);
       }
@@ -484,11 +560,12 @@ __global__ __launch_bounds__(512, 1) void conv3x3_winof4_f32_kernel(WinoArgs a) 
     if constexpr (UPS && S != 1) {
       // The operations behind the weight slice the next stage needs: this stage's slice (stage 0: and, before it, what stage 2 issued
       // behind its own) + NRAW halo gathers when the chunk after next was gathered + NST staging gathers when the chunk three ahead was
-      // staged = 3 + {0, 11} + {0, 3}.  The count is per wave and the smallest any wave issues, so no wave waits for too little.
-      if (x.wait_n == NUW + C::NRAW + C::NST) asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(NUW + C::NRAW + C::NST) : "memory");
-      else if (x.wait_n == NUW + C::NRAW) asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(NUW + C::NRAW) : "memory");
-      else if (x.wait_n == NUW + C::NST) asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(NUW + C::NST) : "memory");
-      else asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(NUW) : "memory");
+      // staged = 3 + {0, NRAW} + {0, 3} (C::WAIT_*).  The count is per wave and the smallest any wave issues, so no wave waits for too
+      // little.  Two of the four may coincide (NRAW = NST with the 16-byte gathers): each branch waits for the value it compares with.
+      if (x.wait_n == C::WAIT_HALO_ST) asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(C::WAIT_HALO_ST) : "memory");
+      else if (x.wait_n == C::WAIT_HALO) asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(C::WAIT_HALO) : "memory");
+      else if (x.wait_n == C::WAIT_ST) asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(C::WAIT_ST) : "memory");
+      else asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(C::WAIT_U) : "memory");
     } else {
       asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(WAITN) : "memory");
     }
@@ -505,8 +582,8 @@ __global__ __launch_bounds__(512, 1) void conv3x3_winof4_f32_kernel(WinoArgs a) 
   using I1 = std::integral_constant<int, 1>;
   using I2 = std::integral_constant<int, 2>;
   // VMEM operations a stage may leave in flight: its own weight slice (and, around stage 2, the halo gathers issued behind it)
-  using WaitHalo = std::integral_constant<int, NUW + C::NRAW>;
-  using WaitU = std::integral_constant<int, NUW>;
+  using WaitHalo = std::integral_constant<int, C::WAIT_HALO>;
+  using WaitU = std::integral_constant<int, C::WAIT_U>;
 
   int k = 0;
   Tile2 T = decode(0);
@@ -550,7 +627,7 @@ __global__ __launch_bounds__(512, 1) void conv3x3_winof4_f32_kernel(WinoArgs a) 
         const bool up1 = c + 1 < a.nch && c + 1 >= nch0, up2 = c + 2 < a.nch && c + 2 >= nch0;
         const bool up3 = c + 3 < a.nch ? c + 3 >= nch0 : c + 3 - a.nch >= nch0;
         const float* nst = c + 3 < a.nch ? st_of(T, c + 3) : st_of(Tn, c + 3 - a.nch);
-        const int wait_cur = NUW + (up2 ? 0 : C::NRAW) + (up3 ? C::NST : 0);
+        const int wait_cur = up2 ? (up3 ? C::WAIT_ST : C::WAIT_U) : (up3 ? C::WAIT_HALO_ST : C::WAIT_HALO);
         UpsStage x{};
         x.ip = up1;
         x.ip_sbuf = x.ip_rbuf = rcur ^ 1;
@@ -591,15 +668,19 @@ __global__ __launch_bounds__(512, 1) void conv3x3_winof4_f32_kernel(WinoArgs a) 
 // owns 32 couts x 64 tiles, a region of 16 x 64 px = 4 tile rows x 16 tile columns; wave (P, sw) owns cout block P and tile row sw, so the
 // two waves of a SIMD read the same V operands, and a thread transforms two tiles per stage.  LDS: weights 2 x 12 KiB and V 2 x 24 KiB
 // (both: stage g of the running stage count reads slot g & 1 and fills the other one for stage g + 1; the barrier between two stages
-// separates a slot's last read from its next write), raw halo 2 x 40.75 KiB (18 x 66 per channel in rows of 72 + 2 floats per plane).  The
+// separates a slot's last read from its next write), raw halo 2 x 41 KiB (the aligned super-window of 18 rows x 72 columns per channel).  The
 // weights of stage g + 1 are the last VMEM operations stage g needs, so stages 0 and 1 wait for everything in flight and stage 2 for all
 // but the halo gathers it issued behind its weight slice; a halo therefore has one stage of lead before its wait, the weights less.
-using CfgF4C32 = GeoF4<32, 64, 2>;      // USTG = 12 16-byte LDS-DMA instructions: one per wave + one more on waves 4 .. 7
-static_assert(CfgF4C32::LDS_USED <= LDS_REQF4 && CfgF4C32::RAW_PER_WAVE + 3 <= 24 && CfgF4C32::USTG == 12 * 1024, "32-cout instance");
+struct CfgF4C32 : GeoF4<32, 64, 2, H16_C32> {      // USTG = 12 16-byte LDS-DMA instructions: one per wave + one more on waves 4 .. 7
+  static constexpr int HSTEP = !H16 ? 1 : WINOF4_HSTEP > 0 ? WINOF4_HSTEP : 3;      // stage 2's halo gathers behind MFMAs 3, 3 + HSTEP, ..
+  static constexpr int WAIT_S2 = NRAW;      // what stage 2 may leave in flight: the halo gathers every wave issued behind its weight slice
+};
+static_assert(CfgF4C32::LDS_USED <= LDS_REQF4 && 3 + CfgF4C32::HSTEP * (CfgF4C32::RAW_PER_WAVE - 1) < 24 && CfgF4C32::USTG == 12 * 1024 &&
+              CfgF4C32::WAIT_S2 <= 63, "32-cout instance");
 
 __global__ __launch_bounds__(512, 1) void conv3x3_winof4_c32_f32_kernel(WinoArgs a) {
   using C = CfgF4C32;
-  constexpr int CK = C::CK, RWL = C::RWL, RPXL = C::RPXL, RAW_BYTES = C::RAW_BYTES, RAW_PER_WAVE = C::RAW_PER_WAVE;
+  constexpr int CK = C::CK, RWL = C::RWL, RAW_BYTES = C::RAW_BYTES, RAW_PER_WAVE = C::RAW_PER_WAVE;
   constexpr int USTG = C::USTG, VSTG = C::VSTG, OFF_U = C::OFF_U, OFF_V = C::OFF_V, OFF_RAW = C::OFF_RAW;
   constexpr int UQ = USTG / 4;      // floats per weight stage
   extern __shared__ __attribute__((aligned(16))) char lds[];
@@ -625,15 +706,15 @@ __global__ __launch_bounds__(512, 1) void conv3x3_winof4_c32_f32_kernel(WinoArgs
   // -- input transform: one channel, position row P of the stage's two and TWO tiles per thread (tile rows sw / 2 and sw / 2 + 2, the
   // same tile column).  Lanes as above: k-step bit, 16 tile columns, low bit of the channel group; sw: its high bit, tile row.
   const int t_ks = lane & 1, t_t16 = (lane >> 1) & 15, t_kq = (lane >> 5) | ((sw & 1) << 1), t_wn = sw >> 1;
-  const int t_rd = ((2 * t_kq + t_ks) * RPXL + 4 * t_wn * RWL + 4 * t_t16) * 4;           // + 8 tile-row strides for the second tile
+  const int t_rd = C::at(2 * t_kq + t_ks, 4 * t_wn, 4 * t_t16);                           // + 8 tile-row strides for the second tile
   const int t_wr = (P * 3 * 4 + t_wn) * 1024 + (t_kq * 16 + t_t16) * 16 + t_ks * 8;       // + column pair * 4096 (+ slot); + 2048 for the second tile
   auto transform_row = [&](auto s_tag, int rbuf, int vslot) {      // this thread's two tiles of row P of stage S's two
     constexpr int S = decltype(s_tag)::value;
     if (WINOF4_ABL & 1) return;
     const char* rb = lds + OFF_RAW + rbuf * RAW_BYTES + t_rd;
     char* vb = lds + OFF_V + vslot * VSTG + t_wr;
-    transform_tile<2 * S + P, RWL, C::VCP>(rb, vb);
-    transform_tile<2 * S + P, RWL, C::VCP>(rb + 8 * RWL * 4, vb + 2048);
+    transform_tile<2 * S + P, C>(rb, vb);
+    transform_tile<2 * S + P, C>(rb + 8 * RWL * 4, vb + 2048);
   };
 
   // -- MFMA operands: 16 bytes = (k-step 2) x (position 2 of a column pair) per lane; lane = 16 * channel group + cout / tile of the block
@@ -646,11 +727,11 @@ __global__ __launch_bounds__(512, 1) void conv3x3_winof4_c32_f32_kernel(WinoArgs
   auto stage = [&](auto s_tag, const float* u_src, const float* raw_src, int raw_buf, int t_rbuf, int vrd) {
     constexpr int S = decltype(s_tag)::value, SN = (S + 1) % 3;
     // the stage's LDS-DMA pieces, one behind each MFMA: the weight slice behind MFMA 0 (waves 4 .. 7: and 1), stage 2's halo gathers
-    // behind 3 .. 23
+    // behind 3, 3 + HSTEP, ..
     auto piece = [&](int m) {
       if (m == 0) dma_u_piece(u_src, vrd ^ 1, wave);
       if (m == 1 && P == 1) dma_u_piece(u_src, vrd ^ 1, 4 + wave);
-      if (S == 2 && m >= 3 && m < 3 + RAW_PER_WAVE) halo.piece(raw_src, raw_buf, m - 3);
+      if (S == 2 && m >= 3 && (m - 3) % C::HSTEP == 0 && (m - 3) / C::HSTEP < RAW_PER_WAVE) halo.piece(raw_src, raw_buf, (m - 3) / C::HSTEP);
     };
     auto mfmas = [&]() {
       if (WINOF4_ABL & 16) {      // data movement alone: the stage's LDS-DMA pieces without the MFMAs they stand behind
@@ -671,7 +752,7 @@ __global__ __launch_bounds__(512, 1) void conv3x3_winof4_c32_f32_kernel(WinoArgs
     }
     // stage 2 leaves the halo gathers every wave issued behind its weight slice in flight (a wave with one more waits for that one too)
     // (the timing build without halo gathers issues nothing behind the weight slice: it waits for everything)
-    if (S == 2 && !(WINOF4_ABL & 2)) asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(C::NRAW) : "memory");
+    if (S == 2 && !(WINOF4_ABL & 2)) asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(C::WAIT_S2) : "memory");
     else asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
   };
@@ -759,7 +840,7 @@ static void pack_winof4(const float* w, int cout, int cin, float* dst, int CT) {
         }
     }
 }
-void pack_conv_weights_winof4(const float* w, int cout, int cin, float* dst) { pack_winof4(w, cout, cin, dst, CfgF4::CT); }
+void pack_conv_weights_winof4(const float* w, int cout, int cin, float* dst) { pack_winof4(w, cout, cin, dst, CfgF4T<false>::CT); }
 
 // The 32-cout instance: one source, cout tiles of 32 (cout a multiple of 32 but not of 64: the UNet's full-resolution 32 -> 32 layers),
 // regions of 16 x 64 px; two chunks for the pipeline's prologue.
@@ -799,11 +880,11 @@ static int launch_winof4(F4Inst inst, const float* u, const float* bias, int cou
   a.C1 = C1;
   a.Cout = cout;
   a.slope = slope;
-  a.nct = cout / (c32 ? CfgF4C32::CT : CfgF4::CT);
-  a.nch = (C0 + C1) / CfgF4::CK;
+  a.nct = cout / (c32 ? CfgF4C32::CT : CfgF4T<false>::CT);
+  a.nch = (C0 + C1) / CfgF4C32::CK;
   a.nch_all = a.nch;
   a.ksplit = 1;
-  a.rx = W / (c32 ? CfgF4C32::RW : CfgF4::RW);
+  a.rx = W / (c32 ? CfgF4C32::RW : CfgF4T<false>::RW);
   a.ry = H / 16;
   if (ups) {
     a.ups_h = H / 2;
@@ -813,8 +894,15 @@ static int launch_winof4(F4Inst inst, const float* u, const float* bias, int cou
     a.ups_sx = (float)(W / 2 - 1) / (float)(W - 1);
   }
   using Kernel = void (*)(WinoArgs);
-  static const Kernel kernels[4] = {conv3x3_winof4_f32_kernel<false>, conv3x3_winof4_f32_kernel<true>, conv3x3_winof4_f32_kernel<true, true>,
-                                    conv3x3_winof4_c32_f32_kernel};      // in F4Inst's order
+  static const Kernel kernels[4] = {conv3x3_winof4_f32_kernel<false, false, H16_PLAIN>, conv3x3_winof4_f32_kernel<true, false, H16_ENTRY>,
+                                    conv3x3_winof4_f32_kernel<true, true, H16_UPS>, conv3x3_winof4_c32_f32_kernel};      // in F4Inst's order
+  // the 16-byte halo gathers read whole aligned units: plane and row strides are multiples of 16 bytes (Wp = W + 8, W % 32 == 0), the
+  // tensors' bases must be too
+  const bool h16[4] = {H16_PLAIN, H16_ENTRY, H16_UPS, H16_C32};
+  if (h16[(int)inst] && ((reinterpret_cast<uintptr_t>(in0) & 15) || (inst == F4Inst::ENTRY && (reinterpret_cast<uintptr_t>(in1) & 15)))) {
+    set_error("conv3x3_winof4: the input tensors must be 16-byte aligned");
+    return PNPX_ERR_SHAPE;
+  }
   static std::once_flag attr_once[64];
   int dev = 0;
   PNPX_HIP(hipGetDevice(&dev));
@@ -848,7 +936,52 @@ int launch_conv3x3_winof4_c32(const float* u, const float* bias, int cout, const
   return launch_winof4(F4Inst::C32, u, bias, cout, in0, C0, nullptr, 0, out, B, H, W, s, slope, pool_out);
 }
 
+// The halo plan of an instance as the kernels run it (include/pnpx.h has the layout): every table entry comes from the geometry's own
+// functions and constants, the ones HaloGather, transform_tile and the stages' waits use.
+template <class C>
+static void halo_plan_of(int H, int W, int off_raw, int lds_used, const int (&waits)[4], int nuw, int nst, int* info, long long* src, int* dst,
+                         int* width, int* wave, int* real, int* read) {
+  const int Hp = padded_h(H), Wp = padded_w(W), HpWp = Hp * Wp;
+  const int v[PNPX_WINOF4_HALO_INFO] = {C::H16, C::CT, C::RW, C::RWL, C::RPXL, C::ORG, C::HCOL, C::RAW_INSTR, C::N16, C::RAW_PER_WAVE, C::NRAW,
+                                        C::RAW_BYTES, off_raw, lds_used, nuw, nst, waits[0], waits[1], waits[2], waits[3]};
+  for (int i = 0; i < PNPX_WINOF4_HALO_INFO; ++i) info[i] = v[i];
+  for (int i = 0; i < C::RAW_INSTR && src; ++i)
+    for (int lane = 0; lane < 64; ++lane) {
+      bool ok = false;
+      src[i * 64 + lane] = (long long)C::src(i, lane, HpWp, Wp, &ok);
+      dst[i * 64 + lane] = C::dst(i) + lane * C::width(i);
+      width[i * 64 + lane] = C::width(i);
+      wave[i * 64 + lane] = i % 8;
+      real[i * 64 + lane] = ok;
+    }
+  for (int c = 0; c < C::CK && read; ++c)
+    for (int hy = 0; hy < 18; ++hy)
+      for (int hx = 0; hx < C::RW + 2; ++hx) read[(c * 18 + hy) * (C::RW + 2) + hx] = C::at(c, hy, hx);
+}
+
 }  // namespace pnpx
+
+extern "C" int pnpx_winof4_halo_plan(int inst, int H, int W, int* info, long long* src, int* dst, int* width, int* wave, int* real, int* read) {
+  using namespace pnpx;
+  if (!info || inst < 0 || inst > 3 || H < 16 || H % 16 != 0 || W < (inst == 3 ? 64 : 32) || W % (inst == 3 ? 64 : 32) != 0) return PNPX_ERR_SHAPE;
+  if (src && !(dst && width && wave && real)) return PNPX_ERR_SHAPE;
+  auto cfg64 = [&](auto h16_tag, bool ups) {
+    using C = CfgF4T<decltype(h16_tag)::value>;
+    const int w_plain[4] = {C::WAIT_U, C::WAIT_HALO, -1, -1}, w_ups[4] = {C::WAIT_U, C::WAIT_HALO, C::WAIT_ST, C::WAIT_HALO_ST};
+    halo_plan_of<C>(H, W, ups ? C::OFF_RAW_UPS : C::OFF_RAW, ups ? C::LDS_USED_UPS : C::LDS_USED, ups ? w_ups : w_plain, C::NUW, ups ? C::NST : 0, info,
+                    src, dst, width, wave, real, read);
+  };
+  const bool h16 = inst == 0 ? H16_PLAIN : inst == 1 ? H16_ENTRY : H16_UPS;
+  if (inst == 3) {
+    const int w_c32[4] = {0, CfgF4C32::WAIT_S2, -1, -1};      // stages 0 and 1 wait for everything
+    halo_plan_of<CfgF4C32>(H, W, CfgF4C32::OFF_RAW, CfgF4C32::LDS_USED, w_c32, 1, 0, info, src, dst, width, wave, real, read);
+  } else if (h16) {
+    cfg64(std::true_type{}, inst == 2);
+  } else {
+    cfg64(std::false_type{}, inst == 2);
+  }
+  return PNPX_OK;
+}
 
 // the matrices the packer uses and the packer itself, for tests/test_winof4_pack.py (host only)
 extern "C" void pnpx_winof4_matrices(double* g18, double* bt36, double* at24) {
