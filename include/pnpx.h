@@ -840,6 +840,63 @@ typedef struct pnpx_vjp_glue_probe_desc {
 int pnpx_vjp_glue_probe(pnpx_ctx* ctx, const pnpx_vjp_glue_probe_desc* desc, void* stream);
 int pnpx_vjp_glue_probe_plan(const pnpx_vjp_glue_probe_desc* desc);
 
+/* Probe of the launches between the convolutions of the two denoisers' FORWARD passes and of the DRUNet VJP's own glue
+ * (csrc/fwd_glue_probe.hip; launchers: csrc/fwd_glue.h; kernels: csrc/unet.hip, csrc/conv_first.h, csrc/drunet_f32.hip, csrc/drunet.hip,
+ * csrc/hs_relayout.h), for tests: ONE call of the launcher the network walks themselves use, on DEVICE tensors the caller laid out, and a
+ * wait for it.  Nothing in the library calls it; it adds no option and reads no state of the context but its device.
+ *   family 0: padded planar fp32 [B][C][H + 2][W + 8] (see pnpx_conv3x3_probe); family 1: HS8 records [B][C/8][H + 2][W + 2] (see
+ *   pnpx_conv_hs_probe; C a multiple of 8).  Plain images are fp32 [B][H][W].  Outputs: interiors only, borders untouched.  w and bias
+ *   are HOST arrays (copied to the device for the call); every other pointer is a device pointer.
+ *   PREP_INPUT (C = 0): x [B][H][W], sigma [1 + (B - 1) sigma_stride] -> out, 2 channels (family 1: 16, i.e. two groups; the second is
+ *     not written): channel 0 = x, channel 1 = sigma[b sigma_stride] inside the image; the border is not written.
+ *   CONV_FIRST (C = cout, 32 or 64): x, sigma, sigma_stride as above, w [cout][2][9], bias [cout], slope -> out [B][cout][H][W] =
+ *     act(bias + sum_t w[c][0][t] x[t] + w[c][1][t] sigma 1[t inside the image]), act(v) = max(v, slope v); family 1 writes the records of
+ *     HS_ASCALE 2^-k times that (0 <= k <= 24).  family 0 needs W % 4 == 0.
+ *   MAXPOOL2: src [B][C][H][W] -> out [B][C][H/2][W/2], floor semantics (H, W >= 2).
+ *   UPSAMPLE2X: bilinear x2 (align_corners) of src [B][C][H][W] into the 2H x 2W corner of out [B][C][Ht][Wt], 2H <= Ht <= 2H + 1,
+ *     2W <= Wt <= 2W + 1; the extra row / column is not written.  family 0 forms: 1 = one thread per output pixel, 2 = four outputs along
+ *     x per thread (2W % 4 == 0 and B C <= 65535 planes only: the forward takes it there).  family 1 forms: 1 = 32 x 16 output tiles,
+ *     2 = 64 x 16 (the forward takes 2 above 32 output columns); B C/8 > 65535 runs as consecutive launches over whole images of at most
+ *     65535 / (C/8) images each, so no launch exceeds the grid limit.
+ *   OUTC_RESIDUAL (C = 32): src = feat, x [B][H][W], w [32], bias [1] -> out_pre (may be null) = x + (sum_c w[c] feat[c] + bias),
+ *     out = clamp(out_pre, 0, 1), both [B][H][W].
+ *   S2D: src [B][C][H][W] (H, W even) -> out [B][4C][H/2][W/2], channel (2 dy + dx) C + c = src[c][2y + dy][2x + dx] (family 1: the same
+ *     over groups of 8 channels: group (2 dy + dx) C/8 + g; record copies).  D2S: src [B][4C][H][W] -> out [B][C][2H][2W], its inverse.
+ *   ADD: out = src + src2, [B][C][H][W].
+ *   TAIL_OUT (family 0, C = 32): out_pre (may be null) = channel 0 of src, out = clamp(that, 0, 1), both [B][H][W].
+ *   TAIL_MASK (C = 0): out = x 1[0 <= pre <= 1], all [B][H][W] (family 1: x times sc[0] first, sc a device float2).
+ *   DRU_INPUT_GRAD (family 0, C >= 2): src = the gradient of the first convolution's input -> out [B][H][W] = src[:, 0], part [B][64] =
+ *     the partial sums of src[:, 1] over 64 pixel ranges, gsigma [B] = their sums.
+ * A field the op has no place for must be 0 / null: an operand the op has no place for, or a missing one, is refused with PNPX_ERR_ARG; a
+ * size or a form the op cannot run with PNPX_ERR_SHAPE; nothing is launched then.
+ * pnpx_fwd_glue_probe_plan (host only, no context, reads the sizes only): 0 when refused, else the form the call runs (form = 0: the one
+ * the forward dispatches; 1 for the ops with one form) + 256 x (launches of the kernel - 1). */
+enum pnpx_fwd_glue_op {
+  PNPX_FWD_PREP_INPUT = 0,
+  PNPX_FWD_CONV_FIRST = 1,
+  PNPX_FWD_MAXPOOL2 = 2,
+  PNPX_FWD_UPSAMPLE2X = 3,
+  PNPX_FWD_OUTC_RESIDUAL = 4,
+  PNPX_FWD_S2D = 5,
+  PNPX_FWD_D2S = 6,
+  PNPX_FWD_ADD = 7,
+  PNPX_FWD_TAIL_OUT = 8,
+  PNPX_FWD_TAIL_MASK = 9,
+  PNPX_FWD_DRU_INPUT_GRAD = 10
+};
+typedef struct pnpx_fwd_glue_probe_desc {
+  int op, family, form;
+  int B, C, H, W, Ht, Wt, sigma_stride, k;
+  float slope;
+  const void *src, *src2;                /* device: padded tensors */
+  const float *x, *sigma, *pre, *sc;     /* device, fp32 */
+  const float *w, *bias;                 /* host */
+  void* out;                             /* device */
+  float *out_pre, *part, *gsigma;        /* device, fp32 */
+} pnpx_fwd_glue_probe_desc;
+int pnpx_fwd_glue_probe(pnpx_ctx* ctx, const pnpx_fwd_glue_probe_desc* desc, void* stream);
+int pnpx_fwd_glue_probe_plan(const pnpx_fwd_glue_probe_desc* desc);
+
 /* Host-only, for tests: which kernel a UNet decoder entry of conv_mode 0 gets (csrc/conv_f32_select.hip, conv_f32_entry) for a set of
  * options, a geometry (second source C1 > 0 at H/2 x W/2, output H x W) and the batch of the whole call.
  * opts: bit 0 "fp32_winograd", bit 1 the layer's "fp32_wino8_layers" bit, bit 2 its "fp32_winof4_layers" bit, bit 3 its

@@ -544,6 +544,41 @@ def test_fp32_ksplit_is_deterministic_and_batch_independent(unet_params):
         ctx.set_option("fp32_chains", 2)
 
 
+@pytest.fixture(scope="module")
+def oden(unet_params):
+    from oracle import pnp_oracle as O
+    return O.Denoiser(unet_params)
+
+
+@pytest.mark.parametrize("option", ["fuse_first", "fuse_pool", "fuse_outc"])
+@pytest.mark.parametrize("mode", [1, 0], ids=["hs_f16x3", "f32_mfma"])
+def test_unfused_glue_branches_match_the_oracle(unet_params, oden, mode, option):
+    """Each fusion option off, one at a time, through the real walk: fuse_first = 0 runs the input preparation (half-split:
+    prep_input_hs_kernel, which no default forward launches) and layer 0 as an MFMA convolution; fuse_pool = 0 the separate pooling
+    kernel at every level; fuse_outc = 0 the separate out-conv + residual + clamp kernel.  Against the CPU oracle at the parity
+    tests' bar (tests/test_gpu_parity.py: 1e-4 relative L2); the single launches are held to their own references in
+    tests/test_gpu_fwd_glue.py."""
+    from tfpnp_amd.pnp import UNetDenoiser2D
+    B, H, W = 2, 32, 48
+    x, s = denoiser_inputs(B, H, W, 31)
+    want = oden(torch.from_numpy(x), torch.from_numpy(s))
+    xd, sd = torch.from_numpy(x).to(dev()), torch.from_numpy(s).to(dev())
+    den = UNetDenoiser2D(state_dict=unet_params, conv_mode=mode)
+    ctx = den.context(dev())
+    saved = ctx.get_option(option)
+    assert saved != 0, "the option is on by default"
+    try:
+        fused = den(xd, sd).clone()
+        ctx.set_option(option, 0)
+        unfused = den(xd, sd).clone()
+    finally:
+        ctx.set_option(option, saved)
+    e_fused, e_unfused = rel(fused.cpu(), want), rel(unfused.cpu(), want)
+    print(f"\nmode {mode} {option}=0: rel-L2 vs oracle {e_unfused:.3e} (fused: {e_fused:.3e})")
+    assert e_unfused < 1e-4 and e_fused < 1e-4
+    assert torch.equal(den(xd, sd), fused), "the option was not restored"
+
+
 @pytest.mark.parametrize("mode", [1, 0])
 def test_solver_call_replays_from_a_hip_graph(unet_params, mode):
     """A solver call launches on the caller's stream (+ side streams forked and joined by events for the launch chains) and, once its

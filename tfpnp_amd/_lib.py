@@ -43,6 +43,12 @@ class VjpGlueProbeDesc(C.Structure):
                 [(n, c_void_p) for n in ("g", "act", "g_pool", "pre", "w", "g_res", "sc", "out", "out_res", "part", "gsigma", "bits")])
 
 
+class FwdGlueProbeDesc(C.Structure):
+    """include/pnpx.h: pnpx_fwd_glue_probe_desc (field for field)."""
+    _fields_ = ([(n, C.c_int) for n in ("op", "family", "form", "B", "C", "H", "W", "Ht", "Wt", "sigma_stride", "k")] + [("slope", C.c_float)] +
+                [(n, c_void_p) for n in ("src", "src2", "x", "sigma", "pre", "sc", "w", "bias", "out", "out_pre", "part", "gsigma")])
+
+
 # name -> (restype, argtypes); mirrors include/pnpx.h one to one
 _P = c_void_p  # device pointers travel as integers
 _SIGNATURES = {
@@ -178,6 +184,8 @@ _SIGNATURES = {
     "pnpx_conv_hs_probe_plan": (C.c_int, [c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int)]),
     "pnpx_vjp_glue_probe": (C.c_int, [c_void_p, c_void_p, c_void_p]),
     "pnpx_vjp_glue_probe_plan": (C.c_int, [c_void_p]),
+    "pnpx_fwd_glue_probe": (C.c_int, [c_void_p, c_void_p, c_void_p]),
+    "pnpx_fwd_glue_probe_plan": (C.c_int, [c_void_p]),
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 

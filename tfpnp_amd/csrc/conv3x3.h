@@ -96,8 +96,7 @@ int launch_conv3x3_winof4_c32(const float* u, const float* bias, int cout, const
 bool conv3x3_winof4_ups_ok(int C0, int C1, int cout, int H, int W);
 int launch_conv3x3_winof4_ups(const float* u, const float* bias, int cout, const float* in0, int C0, const float* in1_lowres, int C1,
                               float* out, int B, int H, int W, hipStream_t s, float slope = 0.2f);
-// the fp32 family's bilinear x2 (align_corners) up-sampling launch (unet.hip): bc planes of h x w into planes of Ht x Wt >= 2h x 2w
-void launch_upsample2x_f32(const float* src, float* dst, size_t bc, int h, int w, int Ht, int Wt, hipStream_t s);
+// (the fp32 family's bilinear x2 up-sampling launch: fwd_glue.h, launch_upsample2x_f32)
 // w[cout][cin][3][3] -> packed weights of the adjoint convolution: wt[ci][co][tap] = w[co][ci][8 - tap], with the
 // adjoint's output channels (= cin) zero-padded to cout_pad.
 void pack_conv_weights_transposed(const float* w, int cout, int cin, int cout_pad, int mt, int cc, float* dst);

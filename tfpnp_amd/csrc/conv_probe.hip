@@ -3,6 +3,7 @@
 // library calls it; it adds no option and reads no state of the context beyond its device.
 #include "common.h"
 #include "conv3x3.h"
+#include "fwd_glue.h"
 
 using namespace pnpx;
 
@@ -186,7 +187,5 @@ extern "C" int pnpx_upsample2x_probe(pnpx_ctx* ctx, const float* src, float* dst
   }
   std::lock_guard<std::mutex> lk(ctx->mu);
   PNPX_HIP(hipSetDevice(ctx->device));
-  launch_upsample2x_f32(src, dst, (size_t)planes, h, w, 2 * h, 2 * w, static_cast<hipStream_t>(stream));
-  PNPX_LAUNCH_CHECK();
-  return PNPX_OK;
+  return launch_upsample2x_f32(FG_AUTO, src, dst, (size_t)planes, h, w, 2 * h, 2 * w, static_cast<hipStream_t>(stream));
 }

@@ -21,9 +21,9 @@
 #include <vector>
 
 #include "common.h"
-#include "conv_first.h"
 #include "conv_hs.h"
 #include "drunet_net.h"
+#include "fwd_glue.h"
 #include "grad_common.h"
 #include "hs_rec.h"
 #include "hs_relayout.h"
@@ -205,27 +205,12 @@ DruPlan dru_plan(int capB, int H, int W, int nb_keep = 0, bool grad = false) {
 struct HsGlue {
   int B, H, W;
   hipStream_t s;
-  int s2d(int l, const char* in, char* out) const {
-    const int h = H >> l, w = W >> l, G = DRU_NC[l] / 8;
-    const size_t n = (size_t)B * 4 * G * (h / 2) * (w / 2) * 2;
-    hipLaunchKernelGGL(hs_s2d_kernel, g1(n), dim3(256), 0, s, reinterpret_cast<const uint4*>(in), reinterpret_cast<uint4*>(out), G, h, w, n);
-    PNPX_LAUNCH_CHECK();
-    return PNPX_OK;
-  }
-  int d2s(int l, const char* in, char* out) const {
-    const int h = H >> (l + 1), w = W >> (l + 1), G = DRU_NC[l] / 8;
-    const size_t n = (size_t)B * G * (2 * h) * (2 * w) * 2;
-    hipLaunchKernelGGL(hs_d2s_kernel, g1(n), dim3(256), 0, s, reinterpret_cast<const uint4*>(in), reinterpret_cast<uint4*>(out), G, h, w, n);
-    PNPX_LAUNCH_CHECK();
-    return PNPX_OK;
-  }
+  static const HsRec* rec(const char* p) { return reinterpret_cast<const HsRec*>(p); }
+  static HsRec* rec(char* p) { return reinterpret_cast<HsRec*>(p); }
+  int s2d(int l, const char* in, char* out) const { return launch_s2d_hs(rec(in), rec(out), B, DRU_NC[l] / 8, H >> l, W >> l, s); }
+  int d2s(int l, const char* in, char* out) const { return launch_d2s_hs(rec(in), rec(out), B, DRU_NC[l] / 8, H >> (l + 1), W >> (l + 1), s); }
   int add(int l, const char* a, const char* b, char* o) const {
-    const int h = H >> l, w = W >> l;
-    const size_t n = (size_t)B * (DRU_NC[l] / 8) * h * w;
-    hipLaunchKernelGGL(dru_add_kernel, g1(n), dim3(256), 0, s, reinterpret_cast<const HsRec*>(a), reinterpret_cast<const HsRec*>(b),
-                       reinterpret_cast<HsRec*>(o), h, w, n);
-    PNPX_LAUNCH_CHECK();
-    return PNPX_OK;
+    return launch_add_hs(rec(a), rec(b), rec(o), (size_t)B * (DRU_NC[l] / 8), H >> l, W >> l, s);
   }
 };
 
@@ -262,10 +247,7 @@ struct HsForward : HsGlue {
   }
   // head: cat[x, sigma] -> 64 channels, linear (VALU, exact fp32 FMA chains); this pass runs on inputs scaled by 2^-shift (DruNet::shift)
   int head(char* s0) const {
-    hipLaunchKernelGGL(conv_first_hs_kernel, dim3((H * W + 255) / 256, DRU_NC[0] / 8, B), dim3(256), 0, s, x, sigma, sigma_stride,
-                       N.head_w, N.zero, reinterpret_cast<HsRec*>(s0), H, W, 1.0f, std::ldexp(HS_ASCALE, -N.shift));
-    PNPX_LAUNCH_CHECK();
-    return PNPX_OK;
+    return launch_conv_first_hs(x, sigma, sigma_stride, N.head_w, N.zero, rec(s0), DRU_NC[0], B, H, W, 1.0f, std::ldexp(HS_ASCALE, -N.shift), s);
   }
   int tail(size_t li, const char* m0) const { return conv(li, m0, unwritten, H, W, 1.f, nullptr, true); }
 };
@@ -348,12 +330,8 @@ struct HsBackward : HsGlue {
     PNPX_HIP(hipMemsetAsync(gmax_bits, 0, sizeof(unsigned), s));
     hipLaunchKernelGGL(absmax_kernel, dim3(512), dim3(256), 0, s, grad_out, npix, gmax_bits);
     hipLaunchKernelGGL(grad_scale_kernel, dim3(1), dim3(1), 0, s, gmax_bits, gscale);
-    hipLaunchKernelGGL(dru_tail_mask_kernel, g1(npix), dim3(256), 0, s, grad_out, pre, gscale, g_pre, npix);
-    PNPX_LAUNCH_CHECK();
-    hipLaunchKernelGGL(conv_first_hs_kernel, dim3((H * W + 255) / 256, DRU_NC[0] / 8, B), dim3(256), 0, s, g_pre, N.zero, 0,
-                       N.tail_bwd_w, N.zero, reinterpret_cast<HsRec*>(s0), H, W, 1.0f, HS_ASCALE);
-    PNPX_LAUNCH_CHECK();
-    return PNPX_OK;
+    PNPX_TRY(launch_tail_mask_hs(grad_out, pre, gscale, g_pre, npix, s));
+    return launch_conv_first_hs(g_pre, N.zero, 0, N.tail_bwd_w, N.zero, rec(s0), DRU_NC[0], B, H, W, 1.0f, HS_ASCALE, s);
   }
   // head: 64 -> (image, noise map) gradients; no residual path (g_res = zeros)
   int input_grad(const char* m0) const {
@@ -368,6 +346,31 @@ struct HsBackward : HsGlue {
 };
 
 }  // namespace
+
+// ---- the launchers of the kernels above and of hs_relayout.h (fwd_glue.h): the walks and, for tests, pnpx_fwd_glue_probe go through them
+int launch_s2d_hs(const HsRec* in, HsRec* out, int B, int G, int h, int w, hipStream_t s) {
+  const size_t n = (size_t)B * 4 * G * (h / 2) * (w / 2) * 2;
+  hipLaunchKernelGGL(hs_s2d_kernel, g1(n), dim3(256), 0, s, reinterpret_cast<const uint4*>(in), reinterpret_cast<uint4*>(out), G, h, w, n);
+  PNPX_LAUNCH_CHECK();
+  return PNPX_OK;
+}
+int launch_d2s_hs(const HsRec* in, HsRec* out, int B, int G, int h, int w, hipStream_t s) {
+  const size_t n = (size_t)B * G * (2 * h) * (2 * w) * 2;
+  hipLaunchKernelGGL(hs_d2s_kernel, g1(n), dim3(256), 0, s, reinterpret_cast<const uint4*>(in), reinterpret_cast<uint4*>(out), G, h, w, n);
+  PNPX_LAUNCH_CHECK();
+  return PNPX_OK;
+}
+int launch_add_hs(const HsRec* a, const HsRec* b, HsRec* o, size_t planes, int h, int w, hipStream_t s) {
+  const size_t n = planes * h * w;
+  hipLaunchKernelGGL(dru_add_kernel, g1(n), dim3(256), 0, s, a, b, o, h, w, n);
+  PNPX_LAUNCH_CHECK();
+  return PNPX_OK;
+}
+int launch_tail_mask_hs(const float* g_out, const float* pre, const float2* sc, float* g_pre, size_t n, hipStream_t s) {
+  hipLaunchKernelGGL(dru_tail_mask_kernel, g1(n), dim3(256), 0, s, g_out, pre, sc, g_pre, n);
+  PNPX_LAUNCH_CHECK();
+  return PNPX_OK;
+}
 
 int drunet_denoise_backward(pnpx_ctx* ctx, const float* x, const float* sigma, int sigma_stride, const float* grad_out,
                             float* grad_x, float* grad_sigma, int B, int H, int W, hipStream_t s) {

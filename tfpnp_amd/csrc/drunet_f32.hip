@@ -22,8 +22,8 @@
 
 #include "common.h"
 #include "conv_f32_select.h"
-#include "conv_first.h"
 #include "drunet_net.h"
+#include "fwd_glue.h"
 #include "grad_common.h"
 
 namespace pnpx {
@@ -32,17 +32,7 @@ namespace {
 
 inline dim3 g1(size_t n) { return dim3((unsigned)((n + 255) / 256)); }
 
-// [x | sigma] -> padded 2-channel tensor (sigma inside the image, zero border: what zero-padding the concatenated map gives)
-__global__ void f32_prep_kernel(const float* __restrict__ x, const float* __restrict__ sigma, int sigma_stride, float* __restrict__ dst,
-                                int H, int W, int Hp, int Wp) {
-  const int b = blockIdx.z, y = blockIdx.y;
-  const int xx = blockIdx.x * blockDim.x + threadIdx.x;
-  if (xx >= W) return;
-  float* d = dst + (size_t)b * 2 * Hp * Wp + (size_t)(y + 1) * Wp + xx + PADL;
-  d[0] = x[((size_t)b * H + y) * W + xx];
-  d[(size_t)Hp * Wp] = sigma[(size_t)b * sigma_stride];
-}
-
+// ([x | sigma] -> padded 2-channel tensor: unet.hip's prep_input_kernel, launch_prep_input_f32)
 // space-to-depth: in [B][C][h][w] -> out [B][4C][h/2][w/2], channel (2 dy + dx) * C + c = in[c][2y + dy][2x + dx]
 __global__ __launch_bounds__(256) void f32_s2d_kernel(const float* __restrict__ in, float* __restrict__ out, int C, int h, int w, size_t n) {
   const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;   // over out interior: B * 4C * (h/2) * (w/2)
@@ -210,27 +200,9 @@ int prepare_weights(pnpx_ctx* ctx, bool adjoint) {
 struct F32Glue {
   int B, H, W;
   hipStream_t s;
-  int s2d(int l, const float* in, float* out) const {
-    const int h = H >> l, w = W >> l;
-    const size_t n = (size_t)B * 4 * DRU_NC[l] * (h / 2) * (w / 2);
-    hipLaunchKernelGGL(f32_s2d_kernel, g1(n), dim3(256), 0, s, in, out, DRU_NC[l], h, w, n);
-    PNPX_LAUNCH_CHECK();
-    return PNPX_OK;
-  }
-  int d2s(int l, const float* in, float* out) const {
-    const int h = H >> (l + 1), w = W >> (l + 1);
-    const size_t n = (size_t)B * DRU_NC[l] * (2 * h) * (2 * w);
-    hipLaunchKernelGGL(f32_d2s_kernel, g1(n), dim3(256), 0, s, in, out, DRU_NC[l], h, w, n);
-    PNPX_LAUNCH_CHECK();
-    return PNPX_OK;
-  }
-  int add(int l, const float* a, const float* b, float* o) const {
-    const int h = H >> l, w = W >> l;
-    const size_t n = (size_t)B * DRU_NC[l] * h * w;
-    hipLaunchKernelGGL(f32_add_kernel, g1(n), dim3(256), 0, s, a, b, o, h, w, n);
-    PNPX_LAUNCH_CHECK();
-    return PNPX_OK;
-  }
+  int s2d(int l, const float* in, float* out) const { return launch_s2d_f32(in, out, B, DRU_NC[l], H >> l, W >> l, s); }
+  int d2s(int l, const float* in, float* out) const { return launch_d2s_f32(in, out, B, DRU_NC[l], H >> (l + 1), W >> (l + 1), s); }
+  int add(int l, const float* a, const float* b, float* o) const { return launch_add_f32(a, b, o, (size_t)B * DRU_NC[l], H >> l, W >> l, s); }
 };
 
 struct F32Forward : F32Glue {
@@ -251,17 +223,13 @@ struct F32Forward : F32Glue {
     return launch_conv_f32(conv_f32_forward(v, Lc.cin, 0, Lc.cout, h, w, B), v, Lc, a, s);
   }
   int head(float* s0) const {
-    hipLaunchKernelGGL(f32_prep_kernel, dim3((W + 63) / 64, H, B), dim3(64), 0, s, x, sigma, sigma_stride, in2, H, W, padded_h(H),
-                       padded_w(W));
-    PNPX_LAUNCH_CHECK();
+    PNPX_TRY(launch_prep_input_f32(x, sigma, sigma_stride, in2, B, H, W, s));
     return conv(0, in2, s0, H, W, 1.f, nullptr);
   }
   // linear, 32 couts (channel 0 real)
   int tail(size_t li, const float* m0) const {
     PNPX_TRY(conv(li, m0, t32, H, W, 1.f, nullptr));
-    hipLaunchKernelGGL(f32_out_kernel, dim3((W + 63) / 64, H, B), dim3(64), 0, s, t32, out, out_pre, H, W);
-    PNPX_LAUNCH_CHECK();
-    return PNPX_OK;
+    return launch_tail_out_f32(t32, out, out_pre, B, H, W, s);
   }
 };
 
@@ -324,26 +292,54 @@ struct F32Backward : F32Glue {
   }
   // clamp + tail (64 <- 1 channel: vector ALU, the [64][2][9] table of the half-split context; its second input channel is zero)
   int seed(float* s0) const {
-    const size_t npix = (size_t)B * H * W;
-    hipLaunchKernelGGL(f32_tail_mask_kernel, g1(npix), dim3(256), 0, s, grad_out, pre, g_pre, npix);
-    PNPX_LAUNCH_CHECK();
-    hipLaunchKernelGGL(conv_first_f32_kernel, dim3((H * (W / 4) + 255) / 256, DRU_NC[0] / 8, B), dim3(256), 0, s, g_pre, ctx->drunet.zero, 0,
-                       ctx->drunet.tail_bwd_w, ctx->drunet.zero, s0, H, W, 1.0f);
-    PNPX_LAUNCH_CHECK();
-    return PNPX_OK;
+    PNPX_TRY(launch_tail_mask_f32(grad_out, pre, g_pre, (size_t)B * H * W, s));
+    return launch_conv_first_f32(g_pre, ctx->drunet.zero, 0, ctx->drunet.tail_bwd_w, ctx->drunet.zero, s0, DRU_NC[0], B, H, W, 1.0f, s);
   }
   // head: 64 -> (image, noise map) gradients
   int input_grad(const float* m0) const {
     PNPX_TRY(conv(0, m0, t32, H, W, nullptr, nullptr));
-    hipLaunchKernelGGL(f32_input_grad_kernel, dim3(SIG_CHUNKS, B), dim3(256), 0, s, t32, 32, grad_x, part, H, W);
-    PNPX_LAUNCH_CHECK();
-    hipLaunchKernelGGL(sigma_grad_final_kernel, dim3((B + 63) / 64), dim3(64), 0, s, part, grad_sigma, B);
-    PNPX_LAUNCH_CHECK();
-    return PNPX_OK;
+    return launch_dru_input_grad_f32(t32, 32, grad_x, part, grad_sigma, B, H, W, s);
   }
 };
 
 }  // namespace
+
+// ---- the launchers of the kernels above (fwd_glue.h): the walks and, for tests, pnpx_fwd_glue_probe go through them
+int launch_s2d_f32(const float* in, float* out, int B, int C, int h, int w, hipStream_t s) {
+  const size_t n = (size_t)B * 4 * C * (h / 2) * (w / 2);
+  hipLaunchKernelGGL(f32_s2d_kernel, g1(n), dim3(256), 0, s, in, out, C, h, w, n);
+  PNPX_LAUNCH_CHECK();
+  return PNPX_OK;
+}
+int launch_d2s_f32(const float* in, float* out, int B, int C, int h, int w, hipStream_t s) {
+  const size_t n = (size_t)B * C * (2 * h) * (2 * w);
+  hipLaunchKernelGGL(f32_d2s_kernel, g1(n), dim3(256), 0, s, in, out, C, h, w, n);
+  PNPX_LAUNCH_CHECK();
+  return PNPX_OK;
+}
+int launch_add_f32(const float* a, const float* b, float* o, size_t planes, int h, int w, hipStream_t s) {
+  const size_t n = planes * h * w;
+  hipLaunchKernelGGL(f32_add_kernel, g1(n), dim3(256), 0, s, a, b, o, h, w, n);
+  PNPX_LAUNCH_CHECK();
+  return PNPX_OK;
+}
+int launch_tail_out_f32(const float* t32, float* out, float* out_pre, int B, int H, int W, hipStream_t s) {
+  hipLaunchKernelGGL(f32_out_kernel, dim3((W + 63) / 64, H, B), dim3(64), 0, s, t32, out, out_pre, H, W);
+  PNPX_LAUNCH_CHECK();
+  return PNPX_OK;
+}
+int launch_tail_mask_f32(const float* g_out, const float* pre, float* g_pre, size_t n, hipStream_t s) {
+  hipLaunchKernelGGL(f32_tail_mask_kernel, g1(n), dim3(256), 0, s, g_out, pre, g_pre, n);
+  PNPX_LAUNCH_CHECK();
+  return PNPX_OK;
+}
+int launch_dru_input_grad_f32(const float* g_in0, int Cg, float* gx, float* part, float* gsigma, int B, int H, int W, hipStream_t s) {
+  hipLaunchKernelGGL(f32_input_grad_kernel, dim3(SIG_CHUNKS, B), dim3(256), 0, s, g_in0, Cg, gx, part, H, W);
+  PNPX_LAUNCH_CHECK();
+  hipLaunchKernelGGL(sigma_grad_final_kernel, dim3((B + 63) / 64), dim3(64), 0, s, part, gsigma, B);
+  PNPX_LAUNCH_CHECK();
+  return PNPX_OK;
+}
 
 void drunet_f32_free(pnpx_ctx* ctx) {
   DruNet& N = ctx->drunet;

@@ -13,6 +13,7 @@
 #include "conv_f32_select.h"
 #include "conv_hs.h"
 #include "conv_first.h"
+#include "fwd_glue.h"
 #include "hs_rec.h"
 #include "unet_plan.h"
 
@@ -79,7 +80,9 @@ __global__ __launch_bounds__(256) void upsample2x_kernel(const float* __restrict
 
 // The same up-sampling, four outputs along x per thread (one 16-byte store; fp32 family, r4).  The four outputs' sources lie in a
 // window of 4 consecutive input pixels per row (scale < 1/2: x0 advances by at most 2 over three steps, x1 <= x0 + 1), loaded once
-// -- 8 loads per 4 outputs instead of 16 -- and picked by position.  Same expression per element as the scalar kernel.
+// -- 8 loads per 4 outputs instead of 16 -- and picked by position.  Same expression per element as the scalar kernel; as compiled the
+// weights differ, though: here l = fp32(s * index) - i0 stays a product and a subtraction, the scalar kernel's is fused into one fma
+// (up to 2^-24 per unit of the index apart; tests/fwd_glue_cases.py: ups_contracted holds each form to its own table).
 // Blocks of (x quads <= 64) x (256 / that many rows), grid.z = B * C.  Used when the output width is a multiple of 4.
 // (The pooling kernel stays scalar: four outputs per thread read 32-byte-strided 16-byte pieces and measured 0.129 vs 0.096 ms.)
 constexpr int UPS_ROWS = 4;   // output rows per thread of upsample2x_v4_kernel (the x-dependent terms are computed once per thread)
@@ -435,19 +438,110 @@ inline dim3 g1d(size_t n) { return dim3((unsigned)((n + 255) / 256)); }
 
 }  // namespace
 
-// The fp32 family's up-sampling launch: bc planes of h x w into the 2h x 2w corner of planes of Ht x Wt (unet_forward_f32 and, for tests,
-// pnpx_upsample2x_probe).  The caller checks the launch.
-void launch_upsample2x_f32(const float* src, float* dst, size_t bc, int h, int w, int Ht, int Wt, hipStream_t s) {
+// ---- the launchers of the kernels above (fwd_glue.h): the forward walks below and, for tests, pnpx_fwd_glue_probe go through them
+int launch_prep_input_f32(const float* x, const float* sigma, int sigma_stride, float* dst, int B, int H, int W, hipStream_t s) {
+  hipLaunchKernelGGL(prep_input_kernel, dim3((W + 63) / 64, H, B), dim3(64), 0, s, x, sigma, sigma_stride, dst, H, W, padded_h(H), padded_w(W));
+  PNPX_LAUNCH_CHECK();
+  return PNPX_OK;
+}
+int launch_prep_input_hs(const float* x, const float* sigma, int sigma_stride, HsRec* dst, int B, int H, int W, hipStream_t s) {
+  const size_t npix = (size_t)B * H * W;
+  hipLaunchKernelGGL(prep_input_hs_kernel, g1d(npix), dim3(256), 0, s, x, sigma, sigma_stride, dst, H, W, npix);
+  PNPX_LAUNCH_CHECK();
+  return PNPX_OK;
+}
+int launch_conv_first_f32(const float* x, const float* sigma, int sigma_stride, const float* w, const float* bias, float* dst, int cout, int B,
+                          int H, int W, float slope, hipStream_t s) {
+  if (!conv_first_runs_f32(W) || cout % 8) {
+    set_error("the fp32 first convolution stores 4 pixels along x and 8 channels per thread (W = %d, cout = %d)", W, cout);
+    return PNPX_ERR_SHAPE;
+  }
+  hipLaunchKernelGGL(conv_first_f32_kernel, dim3((H * (W / 4) + 255) / 256, cout / 8, B), dim3(256), 0, s, x, sigma, sigma_stride, w, bias, dst,
+                     H, W, slope);
+  PNPX_LAUNCH_CHECK();
+  return PNPX_OK;
+}
+int launch_conv_first_hs(const float* x, const float* sigma, int sigma_stride, const float* w, const float* bias, HsRec* dst, int cout, int B,
+                         int H, int W, float slope, float oscale, hipStream_t s) {
+  if (cout % 8) {
+    set_error("the half-split first convolution writes records of 8 channels (cout = %d)", cout);
+    return PNPX_ERR_SHAPE;
+  }
+  hipLaunchKernelGGL(conv_first_hs_kernel, dim3((H * W + 255) / 256, cout / 8, B), dim3(256), 0, s, x, sigma, sigma_stride, w, bias, dst, H, W,
+                     slope, oscale);
+  PNPX_LAUNCH_CHECK();
+  return PNPX_OK;
+}
+int launch_maxpool2_f32(const float* src, float* dst, size_t planes, int H, int W, hipStream_t s) {
+  const size_t n_pool = planes * (H / 2) * (W / 2);
+  hipLaunchKernelGGL(maxpool2_kernel, g1d(n_pool), dim3(256), 0, s, src, dst, n_pool, H, W);
+  PNPX_LAUNCH_CHECK();
+  return PNPX_OK;
+}
+int launch_maxpool2_hs(const HsRec* src, HsRec* dst, size_t planes, int H, int W, hipStream_t s) {
+  const size_t n_pool = planes * (H / 2) * (W / 2);
+  hipLaunchKernelGGL(maxpool2_hs_kernel, g1d(n_pool), dim3(256), 0, s, src, dst, n_pool, H, W);
+  PNPX_LAUNCH_CHECK();
+  return PNPX_OK;
+}
+// The fp32 family's up-sampling launch: planes of h x w into the 2h x 2w corner of planes of Ht x Wt.
+int launch_upsample2x_f32(int form, const float* src, float* dst, size_t planes, int h, int w, int Ht, int Wt, hipStream_t s) {
+  if (!form) form = upsample2x_form_f32(planes, w);
+  if (!upsample2x_form_runs_f32(form, planes, w)) {
+    set_error("fp32 up-sampling: form %d cannot run %zu planes of width %d", form, planes, w);
+    return PNPX_ERR_SHAPE;
+  }
   const float sy = (2 * h > 1) ? (float)(h - 1) / (float)(2 * h - 1) : 0.f;
   const float sx = (2 * w > 1) ? (float)(w - 1) / (float)(2 * w - 1) : 0.f;
-  if ((2 * w) % 4 == 0 && bc <= 65535) {
+  if (form == FG_UPS_V4) {
     const int quads = w / 2, bx = quads >= 64 ? 64 : quads, by = 256 / bx;
-    hipLaunchKernelGGL(upsample2x_v4_kernel, dim3((quads + bx - 1) / bx, (2 * h + by * UPS_ROWS - 1) / (by * UPS_ROWS), (unsigned)bc), dim3(bx, by), 0, s,
+    hipLaunchKernelGGL(upsample2x_v4_kernel, dim3((quads + bx - 1) / bx, (2 * h + by * UPS_ROWS - 1) / (by * UPS_ROWS), (unsigned)planes), dim3(bx, by), 0, s,
                        src, dst, h, w, Ht, Wt, sy, sx);
   } else {
-    const size_t n_up = bc * (2 * h) * (2 * w);
+    const size_t n_up = planes * (2 * h) * (2 * w);
     hipLaunchKernelGGL(upsample2x_kernel, g1d(n_up), dim3(256), 0, s, src, dst, n_up, h, w, Ht, Wt, sy, sx);
   }
+  PNPX_LAUNCH_CHECK();
+  return PNPX_OK;
+}
+// The half-split family's: nb images of G groups.  More than FG_GRID_Z_MAX (image, group) planes run as consecutive launches over whole
+// images (at or below the limit: one launch, as before).
+int launch_upsample2x_hs(int form, const HsRec* src, HsRec* dst, int nb, int G, int h, int w, int Ht, int Wt, hipStream_t s) {
+  if (!form) form = upsample2x_form_hs(w);
+  const int per = upsample2x_hs_images_per_launch(G);
+  if (!upsample2x_form_runs_hs(form) || per <= 0) {
+    set_error("half-split up-sampling: unknown form %d, or %d groups of one image exceed the planes of one launch", form, G);
+    return PNPX_ERR_SHAPE;
+  }
+  const float sy = (2 * h > 1) ? (float)(h - 1) / (float)(2 * h - 1) : 0.f;
+  const float sx = (2 * w > 1) ? (float)(w - 1) / (float)(2 * w - 1) : 0.f;
+  const int Wo = 2 * w, Ho = 2 * h;
+  const size_t src_image = (size_t)G * (h + 2) * (w + 2), dst_image = (size_t)G * (Ht + 2) * (Wt + 2);   // records
+  for (int b0 = 0; b0 < nb; b0 += per) {
+    const unsigned nbg = (unsigned)((nb - b0 < per ? nb - b0 : per) * G);
+    const HsRec* sp = src + b0 * src_image;
+    HsRec* dp = dst + b0 * dst_image;
+    if (form == FG_UPS_HS64) {   // 64 x 16 output tiles
+      hipLaunchKernelGGL((upsample2x_hs_kernel<64, 4>), dim3((Wo + 63) / 64, (Ho + 15) / 16, nbg), dim3(256), 0, s, sp, dp, h, w, Ht, Wt, sy, sx);
+    } else {                     // 32 x 16
+      hipLaunchKernelGGL((upsample2x_hs_kernel<32, 2>), dim3((Wo + 31) / 32, (Ho + 15) / 16, nbg), dim3(256), 0, s, sp, dp, h, w, Ht, Wt, sy, sx);
+    }
+    PNPX_LAUNCH_CHECK();
+  }
+  return PNPX_OK;
+}
+int launch_outc_residual_f32(const float* feat, const float* x, const float* w, const float* bias, float* out, float* out_pre, int B, int H,
+                             int W, hipStream_t s) {
+  hipLaunchKernelGGL(outc_residual_kernel, dim3((W + 63) / 64, H, B), dim3(64), 0, s, feat, x, w, bias, out, out_pre, H, W);
+  PNPX_LAUNCH_CHECK();
+  return PNPX_OK;
+}
+int launch_outc_residual_hs(const HsRec* feat, const float* x, const float* w, const float* bias, float* out, float* out_pre, int B, int H,
+                            int W, hipStream_t s) {
+  const size_t npix = (size_t)B * H * W;
+  hipLaunchKernelGGL(outc_residual_hs_kernel, g1d(npix), dim3(256), 0, s, feat, x, w, bias, out, out_pre, H, W, npix);
+  PNPX_LAUNCH_CHECK();
+  return PNPX_OK;
 }
 
 // Half-split forward pass.  Levels 0 and 1 (the memory-bound, shallow-K layers) can be processed in sub-batches so
@@ -480,11 +574,9 @@ static int unet_forward_hs(pnpx_ctx* ctx, UNetArena& ar, const UNetPlan& P, cons
   };
   auto pool_fused = [&](int l) { return !no_pool_fuse && l < 4 && conv_hs_can_pool(P.x[l].H, P.x[l].W); };
 
-  const size_t npix = (size_t)B * H * W;
   const bool first_fused = ctx->opt_fuse_first != 0;   // the VALU first convolution replaces prep_input + conv 0
   if (!first_fused) {
-    hipLaunchKernelGGL(prep_input_hs_kernel, g1d(npix), dim3(256), 0, s, x, sigma, sigma_stride, rat(P.in0, 0), H, W, npix);
-    PNPX_LAUNCH_CHECK();
+    PNPX_TRY(launch_prep_input_hs(x, sigma, sigma_stride, rat(P.in0, 0), B, H, W, s));
     PNPX_TRY(rec.mark("prep_input", 0));
   }
 
@@ -529,10 +621,8 @@ static int unet_forward_hs(pnpx_ctx* ctx, UNetArena& ar, const UNetPlan& P, cons
     }
     if (folded) {
     } else if (li == 0 && first_fused) {
-      hipLaunchKernelGGL(conv_first_hs_kernel, dim3((H * W + 255) / 256, 4, nb), dim3(256), 0, s, x + (size_t)b0 * H * W,
-                         sigma + (size_t)b0 * sigma_stride, sigma_stride, ctx->conv0_w, ctx->conv[0].b, rat(ta, b0), H, W,
-                         0.2f, HS_ASCALE);
-      PNPX_LAUNCH_CHECK();
+      PNPX_TRY(launch_conv_first_hs(x + (size_t)b0 * H * W, sigma + (size_t)b0 * sigma_stride, sigma_stride, ctx->conv0_w, ctx->conv[0].b,
+                                    rat(ta, b0), 32, nb, H, W, 0.2f, HS_ASCALE, s));
       PNPX_TRY(rec.mark("conv3x3", 2.0 * 9.0 * 2 * 32 * (double)H * W * nb));
     } else
     PNPX_TRY(conv(li, i0, i1, ta, b0, nb, first_fuse));
@@ -549,10 +639,7 @@ static int unet_forward_hs(pnpx_ctx* ctx, UNetArena& ar, const UNetPlan& P, cons
       const int nb = (B - b0 < sb) ? (B - b0) : sb;
       if (l > 0 && !pool_fused(l - 1)) {
         const Act& src = P.x[l - 1];
-        const size_t n_pool = (size_t)nb * (src.C / 8) * (src.H / 2) * (src.W / 2);
-        hipLaunchKernelGGL(maxpool2_hs_kernel, g1d(n_pool), dim3(256), 0, s, rat(src, b0), rat(P.p[l], b0), n_pool, src.H,
-                           src.W);
-        PNPX_LAUNCH_CHECK();
+        PNPX_TRY(launch_maxpool2_hs(rat(src, b0), rat(P.p[l], b0), (size_t)nb * (src.C / 8), src.H, src.W, s));
         PNPX_TRY(rec.mark("maxpool2", 0));
       }
       ConvHsFuse f;
@@ -564,8 +651,6 @@ static int unet_forward_hs(pnpx_ctx* ctx, UNetArena& ar, const UNetPlan& P, cons
   const Act* below = &P.x[4];
   for (int l = 3; l >= 0; --l) {
     const int h = below->H, w = below->W;
-    const float sy = (2 * h > 1) ? (float)(h - 1) / (float)(2 * h - 1) : 0.f;
-    const float sx = (2 * w > 1) ? (float)(w - 1) / (float)(2 * w - 1) : 0.f;
     const int sb = sub_of(l);
     for (int b0 = 0; b0 < B; b0 += sb) {
       const int nb = (B - b0 < sb) ? (B - b0) : sb;
@@ -587,16 +672,7 @@ static int unet_forward_hs(pnpx_ctx* ctx, UNetArena& ar, const UNetPlan& P, cons
         f_first.ups_h = h;
         f_first.ups_w = w;
       } else {
-        const unsigned nbg = (unsigned)(nb * (below->C / 8));
-        const int Wo = 2 * w, Ho = 2 * h;
-        if (Wo > 32) {   // 64 x 16 output tiles
-          hipLaunchKernelGGL((upsample2x_hs_kernel<64, 4>), dim3((Wo + 63) / 64, (Ho + 15) / 16, nbg), dim3(256), 0, s,
-                             rat(*below, b0), rat(P.u[l], b0), h, w, P.u[l].H, P.u[l].W, sy, sx);
-        } else {         // 32 x 16
-          hipLaunchKernelGGL((upsample2x_hs_kernel<32, 2>), dim3((Wo + 31) / 32, (Ho + 15) / 16, nbg), dim3(256), 0, s,
-                             rat(*below, b0), rat(P.u[l], b0), h, w, P.u[l].H, P.u[l].W, sy, sx);
-        }
-        PNPX_LAUNCH_CHECK();
+        PNPX_TRY(launch_upsample2x_hs(FG_AUTO, rat(*below, b0), rat(P.u[l], b0), nb, below->C / 8, h, w, P.u[l].H, P.u[l].W, s));
         PNPX_TRY(rec.mark("upsample2x", 0));
       }
       if (l == 0 && !no_outc_fuse) {   // the network tail (1x1 conv + residual + clamp) rides on the last conv's epilogue
@@ -611,9 +687,7 @@ static int unet_forward_hs(pnpx_ctx* ctx, UNetArena& ar, const UNetPlan& P, cons
     below = &P.y[l];
   }
   if (no_outc_fuse) {
-    hipLaunchKernelGGL(outc_residual_hs_kernel, g1d(npix), dim3(256), 0, s, rat(P.y[0], 0), x, ctx->outc_w, ctx->outc_b,
-                       out, out_pre, H, W, npix);
-    PNPX_LAUNCH_CHECK();
+    PNPX_TRY(launch_outc_residual_hs(rat(P.y[0], 0), x, ctx->outc_w, ctx->outc_b, out, out_pre, B, H, W, s));
     PNPX_TRY(rec.mark("outc_residual_clamp", 2.0 * 32 * (double)H * W * B));
   }
   return PNPX_OK;
@@ -633,9 +707,7 @@ static int unet_forward_f32(pnpx_ctx* ctx, UNetArena& ar, const UNetPlan& P, con
   // layer's output, not its padded input tensor)
   const bool first_valu = ctx->opt_fuse_first && W % 4 == 0 && ctx->conv[0].cout == 32;
   if (!first_valu) {
-    hipLaunchKernelGGL(prep_input_kernel, dim3((W + 63) / 64, H, B), dim3(64), 0, s, x, sigma, sigma_stride, fptr(P.in0), H,
-                       W, padded_h(H), padded_w(W));
-    PNPX_LAUNCH_CHECK();
+    PNPX_TRY(launch_prep_input_f32(x, sigma, sigma_stride, fptr(P.in0), B, H, W, s));
     PNPX_TRY(rec.mark("prep_input", 0));
   }
   // pooled: the encoder's MaxPool2d(2) of this layer's output, written by the same launch when the Winograd kernel runs the layer
@@ -657,9 +729,7 @@ static int unet_forward_f32(pnpx_ctx* ctx, UNetArena& ar, const UNetPlan& P, con
     const Act& ta = i1 ? P.da[lvl] : P.a[lvl];
     const Act& tb = i1 ? P.db[lvl] : P.b[lvl];
     if (li == 0 && first_valu) {
-      hipLaunchKernelGGL(conv_first_f32_kernel, dim3((H * (W / 4) + 255) / 256, 4, B), dim3(256), 0, s, x, sigma, sigma_stride, ctx->conv0_w,
-                         ctx->conv[0].b, fptr(ta), H, W, 0.2f);
-      PNPX_LAUNCH_CHECK();
+      PNPX_TRY(launch_conv_first_f32(x, sigma, sigma_stride, ctx->conv0_w, ctx->conv[0].b, fptr(ta), 32, B, H, W, 0.2f, s));
       PNPX_TRY(rec.mark("conv3x3", 2.0 * 9.0 * 2 * 32 * (double)H * W * B));
     } else
     PNPX_TRY(conv(li, i0, i1, ta));
@@ -671,9 +741,7 @@ static int unet_forward_f32(pnpx_ctx* ctx, UNetArena& ar, const UNetPlan& P, con
   for (int l = 1; l < 5; ++l) {
     const Act& src = P.x[l - 1];
     if (!pooled) {
-      const size_t n_pool = (size_t)B * src.C * (src.H / 2) * (src.W / 2);
-      hipLaunchKernelGGL(maxpool2_kernel, g1d(n_pool), dim3(256), 0, s, fptr(src), fptr(P.p[l]), n_pool, src.H, src.W);
-      PNPX_LAUNCH_CHECK();
+      PNPX_TRY(launch_maxpool2_f32(fptr(src), fptr(P.p[l]), (size_t)B * src.C, src.H, src.W, s));
       PNPX_TRY(rec.mark("maxpool2", 0));
     }
     // r5: the bottom level's three launches as TWO launch chains over halves of the batch when their tile count sits between round
@@ -718,8 +786,7 @@ static int unet_forward_f32(pnpx_ctx* ctx, UNetArena& ar, const UNetPlan& P, con
     const ConvF32Choice c0 = even ? conv_f32_entry(v0, P.x[l].C, below->C, ctx->conv[li0].cout, 2 * h, 2 * w, B_call) : ConvF32Choice();
     const bool ups_fused = c0.fused;
     if (!ups_fused) {
-      launch_upsample2x_f32(fptr(*below), fptr(P.u[l]), (size_t)B * below->C, h, w, P.u[l].H, P.u[l].W, s);
-      PNPX_LAUNCH_CHECK();
+      PNPX_TRY(launch_upsample2x_f32(FG_AUTO, fptr(*below), fptr(P.u[l]), (size_t)B * below->C, h, w, P.u[l].H, P.u[l].W, s));
       PNPX_TRY(rec.mark("upsample2x", 0));
     }
     // first convolution of a decoder block: the fused instance reads the low-resolution tensor
@@ -749,9 +816,7 @@ static int unet_forward_f32(pnpx_ctx* ctx, UNetArena& ar, const UNetPlan& P, con
     PNPX_TRY(conv(li0 + 2, P.db[l], nullptr, P.y[l]));
     below = &P.y[l];
   }
-  hipLaunchKernelGGL(outc_residual_kernel, dim3((W + 63) / 64, H, B), dim3(64), 0, s, fptr(P.y[0]), x, ctx->outc_w,
-                     ctx->outc_b, out, out_pre, H, W);
-  PNPX_LAUNCH_CHECK();
+  PNPX_TRY(launch_outc_residual_f32(fptr(P.y[0]), x, ctx->outc_w, ctx->outc_b, out, out_pre, B, H, W, s));
   PNPX_TRY(rec.mark("outc_residual_clamp", 2.0 * 32 * (double)H * W * B));
   return PNPX_OK;
 }
