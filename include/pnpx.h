@@ -897,6 +897,71 @@ typedef struct pnpx_fwd_glue_probe_desc {
 int pnpx_fwd_glue_probe(pnpx_ctx* ctx, const pnpx_fwd_glue_probe_desc* desc, void* stream);
 int pnpx_fwd_glue_probe_plan(const pnpx_fwd_glue_probe_desc* desc);
 
+/* Probe of the TRAINING kernels of the two ResNet-18 networks (csrc/net_train_probe.hip; launchers: csrc/policy_grad.h, csrc/critic_grad.h;
+ * kernels: csrc/policy_bn.hip, csrc/policy_grad.hip, csrc/critic_grad.hip), for tests: ONE call of the launcher(s) the network walks
+ * themselves use, on DEVICE tensors the caller laid out, and a wait for it.  Nothing in the library calls it; it adds no option and reads
+ * no state of the context but its device.  HS8 tensors are records [B][G][h + 2][w + 2] (see pnpx_conv_hs_probe), values times 16; cout = 8 G.
+ * The probe allocates every scratch (K-split slab, partial sums, head rows, range bits) itself and fills it with NaN before the launch.
+ *   BN_STATS: z0, params [4 cout] (weight, bias, running_mean, running_var), momentum, update -> fout [4][cout] = mean, biased variance,
+ *     scale = weight / sqrt(var + 1e-5), shift = bias - mean scale, over the interior; update != 0 moves the running statistics in params
+ *     (variance times n / (n - 1)).
+ *   BN_APPLY: z0, st0 [3][cout] (mean, scale, beta) [, z1, st1] [, res] -> out and / or out2 = relu((z0 - mean) scale + beta [+ the same of
+ *     z1] [+ res]); out2 is the space-to-depth copy [B][4 G][h/2 + 2][w/2 + 2] (h, w even), group (2 (y & 1) + (x & 1)) G + g.
+ *   BN_BWD: g, act, z0, st0 [2][cout] (mean, var) [, z1, st1], params [4 cout per layer] [, slot (float2: s, 1 / s)] [, boost] -> grad
+ *     [4 cout per layer] (weight, bias, two rows of zeros), coef [3 cout per layer], out = dz0 [, out2 = dz1] [, dy_out] [, flag |= 1
+ *     where |dz| >= 4095].  dy = g [act > 0]; slot null: (1, 1); boost 0: 1 (the gradients are times 1 / (s boost)).
+ *   WGRAD_PLAIN (G = 0): g [B][Gg][..] (cout = K-split GEMM rows), x [B][Xg][..], gv [B], inv_w, kind 0 / 1 / 2 (3x3 stride 1; 3x3 stride 2
+ *     on the space-to-depth grid, K = 4 Cp, cin <= Cp; 1x1 shortcut, Cp = 0), cout, cin, K -> grad [cout][cin][9] ([cout][cin] for kind 2)
+ *     = inv_w sum_b gv[b] corr(g, x).
+ *   WGRAD_WN: the same with params = bias [cout] | weight_g [cout] | weight_v [cout][fan] and inv_b -> grad in the same layout.
+ *   CLIP_MASK: act, thr (in the records' units, 16 x the activation) -> out (every record written: hi = 16 where the stored value does not
+ *     exceed thr inside, zero border).
+ *   ALPHA_DOT: g, x (= W m), G [, res, m with resG, mG groups] -> dout [B].
+ *   FC_GRAD: act [B][64][h + 2][w + 2], gv, fin = fc.weight [512], thr (records' units) -> fout [512] = fc.weight's gradient, dout [512] =
+ *     the head threshold's share per channel.
+ *   ALPHA_FINISH: alpha_src (HOST int [21], each -1 or an index below 21), din [21][B], din2 [512], gv, inv_w -> grad [23]: [21] the head's
+ *     threshold, [22] fc.bias.
+ *   HEAD_GRAD: act = feat [B][64][..], params = the head tensors in parameter order (fc_softmax.0 weight [2][512], bias [2]; the first
+ *     deterministic Linear [n1][512], [n1], n1 = spi ? 64 : n_det; with spi the second [n_det][64], [n_det]), fin = gp [B][2],
+ *     fin2 = gd [B][n_det] -> fout = g_f [B][512], grad in the layout of params.
+ *   GRAD_SEED: fin = g_f [B][512], boost -> fout (float2 slot), out = ga [B][64][..], fout2 = gv [B].
+ * A field the op has no place for must be 0 / null (PNPX_ERR_ARG); a size the op cannot run: PNPX_ERR_SHAPE; nothing is launched then.
+ * pnpx_net_train_probe_plan (host only, no context, reads the sizes only): 0 when refused, else BN_STATS / BN_BWD: the pieces of 2048
+ * pixels; BN_APPLY: the workgroups; WGRAD_*: K-split pieces + 256 x chunks (of 32 pixels) per piece; HEAD_GRAD: the rows of the head
+ * tensors (one workgroup each); the others: 1. */
+enum pnpx_net_train_op {
+  PNPX_NT_BN_STATS = 0,
+  PNPX_NT_BN_APPLY = 1,
+  PNPX_NT_BN_BWD = 2,
+  PNPX_NT_WGRAD_PLAIN = 3,
+  PNPX_NT_WGRAD_WN = 4,
+  PNPX_NT_CLIP_MASK = 5,
+  PNPX_NT_ALPHA_DOT = 6,
+  PNPX_NT_FC_GRAD = 7,
+  PNPX_NT_ALPHA_FINISH = 8,
+  PNPX_NT_HEAD_GRAD = 9,
+  PNPX_NT_GRAD_SEED = 10
+};
+typedef struct pnpx_net_train_probe_desc {
+  int op;
+  int B, G, h, w;
+  int cout, K, cin, Cp, kind, Gg, Xg;    /* WGRAD_* */
+  int resG, mG;                          /* ALPHA_DOT */
+  int n_det, spi, update;
+  float momentum, thr, boost, inv_w, inv_b;
+  const void *z0, *z1, *g, *act, *res, *x, *m;          /* device, HS8 */
+  const float *st0, *st1, *gv, *slot, *fin, *fin2;      /* device, fp32 */
+  float* params;                                        /* device, fp32 (BN_STATS moves its running statistics) */
+  const double *din, *din2;                             /* device */
+  const int* alpha_src;                                 /* host */
+  void *out, *out2, *dy_out;                            /* device, HS8 */
+  float *grad, *coef, *fout, *fout2;                    /* device, fp32 */
+  double* dout;                                         /* device */
+  unsigned* flag;                                       /* device */
+} pnpx_net_train_probe_desc;
+int pnpx_net_train_probe(pnpx_ctx* ctx, const pnpx_net_train_probe_desc* desc, void* stream);
+int pnpx_net_train_probe_plan(const pnpx_net_train_probe_desc* desc);
+
 /* Host-only, for tests: which kernel a UNet decoder entry of conv_mode 0 gets (csrc/conv_f32_select.hip, conv_f32_entry) for a set of
  * options, a geometry (second source C1 > 0 at H/2 x W/2, output H x W) and the batch of the whole call.
  * opts: bit 0 "fp32_winograd", bit 1 the layer's "fp32_wino8_layers" bit, bit 2 its "fp32_winof4_layers" bit, bit 3 its

@@ -49,6 +49,14 @@ class FwdGlueProbeDesc(C.Structure):
                 [(n, c_void_p) for n in ("src", "src2", "x", "sigma", "pre", "sc", "w", "bias", "out", "out_pre", "part", "gsigma")])
 
 
+class NetTrainProbeDesc(C.Structure):
+    """include/pnpx.h: pnpx_net_train_probe_desc (field for field)."""
+    _fields_ = ([(n, C.c_int) for n in ("op", "B", "G", "h", "w", "cout", "K", "cin", "Cp", "kind", "Gg", "Xg", "resG", "mG", "n_det", "spi", "update")] +
+                [(n, C.c_float) for n in ("momentum", "thr", "boost", "inv_w", "inv_b")] +
+                [(n, c_void_p) for n in ("z0", "z1", "g", "act", "res", "x", "m", "st0", "st1", "gv", "slot", "fin", "fin2", "params", "din", "din2",
+                                         "alpha_src", "out", "out2", "dy_out", "grad", "coef", "fout", "fout2", "dout", "flag")])
+
+
 # name -> (restype, argtypes); mirrors include/pnpx.h one to one
 _P = c_void_p  # device pointers travel as integers
 _SIGNATURES = {
@@ -186,6 +194,8 @@ _SIGNATURES = {
     "pnpx_vjp_glue_probe_plan": (C.c_int, [c_void_p]),
     "pnpx_fwd_glue_probe": (C.c_int, [c_void_p, c_void_p, c_void_p]),
     "pnpx_fwd_glue_probe_plan": (C.c_int, [c_void_p]),
+    "pnpx_net_train_probe": (C.c_int, [c_void_p, c_void_p, c_void_p]),
+    "pnpx_net_train_probe_plan": (C.c_int, [c_void_p]),
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 

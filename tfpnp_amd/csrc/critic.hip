@@ -228,9 +228,7 @@ bool make_layout(int num_inputs, CriticLayout& L) {
       P.rows = adj ? K : c.cout;
       P.K = adj ? c.cout : K;
       P.mt = (P.rows % 64 == 0) ? 64 : 32;
-      const int mask = trunk_taps(li, adj != 0);
-      for (int t = 0; t < 9; ++t)
-        if ((mask >> t) & 1) P.tap[P.nt++] = t;
+      pack_desc_window(P, trunk_taps(li, adj != 0));
       P.kind = kind;
       P.cin = c.cin;
       P.Cp = Cp;

@@ -20,6 +20,8 @@ struct WgradJob {
 };
 // K-split: pieces the pixel axis of a layer is cut into -- a function of (cout, K, B, h, w) only
 int critic_wgrad_pieces(int cout, int K, int B, int h, int w);
+// chunks of 32 pixels each piece but the last takes (the last takes what is left)
+int critic_wgrad_chunks_per_piece(int cout, int K, int B, int h, int w);
 inline size_t critic_wgrad_piece_floats(int cout, int K, int nt) { return (size_t)cout * nt * K + cout; }
 int launch_critic_wgrad(const WgradJob& J, float* slab, hipStream_t s);
 

@@ -292,6 +292,12 @@ int critic_wgrad_pieces(int cout, int K, int B, int h, int w) {
   return (int)((nchunks + cpp - 1) / cpp);   // no empty piece
 }
 
+int critic_wgrad_chunks_per_piece(int cout, int K, int B, int h, int w) {
+  const long long nchunks = ((long long)B * h * w + WG_KC - 1) / WG_KC;
+  const int pieces = critic_wgrad_pieces(cout, K, B, h, w);
+  return (int)((nchunks + pieces - 1) / pieces);
+}
+
 int launch_critic_wgrad(const WgradJob& J, float* slab, hipStream_t s) {
   if (J.cout % 32 || J.K % 32 || J.nt < 1 || J.nt > 9 || J.K / 8 > J.Xg || J.cout / 8 > J.Gg || (long long)J.B * J.h * J.w >= (1LL << 31) - WG_KC) {
     set_error("critic weight gradient: unsupported geometry (%d x %d channels, %d taps, %d x %d x %d)", J.cout, J.K, J.nt, J.B, J.h, J.w);
@@ -313,7 +319,7 @@ int launch_critic_wgrad(const WgradJob& J, float* slab, hipStream_t s) {
   a.tilesM = J.cout / 32;
   a.nchunks = (int)(((long long)J.B * J.h * J.w + WG_KC - 1) / WG_KC);
   const int pieces = critic_wgrad_pieces(J.cout, J.K, J.B, J.h, J.w);
-  a.cpp = (a.nchunks + pieces - 1) / pieces;
+  a.cpp = critic_wgrad_chunks_per_piece(J.cout, J.K, J.B, J.h, J.w);
   a.stride = critic_wgrad_piece_floats(J.cout, J.K, J.nt);
   for (int i = 0; i < 9; ++i) a.tap[i] = i < J.nt ? J.tap[i] : 0;
   hipLaunchKernelGGL(critic_wgrad_kernel, dim3((unsigned)(a.tilesM * (J.K / 32)), (unsigned)pieces), dim3(256), 0, s, a);

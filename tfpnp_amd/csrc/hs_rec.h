@@ -22,6 +22,14 @@ __device__ __forceinline__ HsRec hs_pack(const float v[8]) {
   }
   return r;
 }
+// A product that is the LAST operation before hs_pack goes through this: left to the compiler it is fused into hs_pack's two conversions
+// separately (hi = f16(fp32(a * b)), lo = f16(a * b - f16(a * b)) from the unrounded product, v_fma_mixlo_f16), and where fp32(a * b)
+// falls on an f16 tie the record comes out one hi-ulp off (unet_bwd.hip, policy_grad.hip::pol_grad_seed_kernel).  A product with a power
+// of two is exact and needs none.
+__device__ __forceinline__ float rounded_f32(float x) {
+  asm("" : "+v"(x));      // the fp32 value itself, in a register: nothing upstream can be fused into what is computed from it
+  return x;
+}
 // global average pool: the sum of channel c of image b over the h x w interior of an HS8 tensor of G groups, times inv.
 // Fixed summation order (a result does not depend on the batch it arrives in).
 __device__ __forceinline__ float hs_pooled(const HsRec* __restrict__ feat, int b, int G, int c, int h, int w, float inv) {

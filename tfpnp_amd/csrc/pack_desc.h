@@ -16,6 +16,14 @@ struct PackDesc {     // one packing: [rows/mt][K/16][nt][hi,lo][kg][mt][8] f16 
   int adj;                 // the adjoint: rows / K transposed, taps mirrored
   int tap[9];
 };
+// The window of a packing: its taps are the set bits of `mask` in ascending order.
+inline void pack_desc_window(PackDesc& P, int mask) {
+  P.nt = 0;
+  for (int t = 0; t < 9; ++t)
+    if ((mask >> t) & 1) P.tap[P.nt++] = t;
+}
+// The window a FORWARD packing of each kind has: 3x3 stride 1; 3x3 stride 2 on the space-to-depth grid; the 1x1 shortcut
+inline int pack_kind_window(int kind) { return kind == 0 ? 0x1FF : kind == 1 ? 0x01B : 0x010; }
 struct CopyDesc {
   unsigned src, dst, n;
   unsigned space;          // source: 0 = the parameter vector; 1 = the folded BatchNorm shifts (actor only)

@@ -35,7 +35,7 @@ namespace {
 
 constexpr double BN_EPS = 1e-5;
 constexpr int NBN = TRUNK_LAYERS;    // one BatchNorm behind every convolution: the trunk's layer numbering (resnet18_hs.h)
-constexpr int BN_PIECE = 2048;       // pixels per partial sum: 256 threads x 8
+constexpr int BN_PIECE = BN_FWD_PIECE;   // pixels per partial sum: 256 threads x 8
 
 struct BnLayer {
   size_t bn;       // floats into the parameter vector: weight, bias, running_mean, running_var (cout each)
@@ -141,10 +141,6 @@ __global__ __launch_bounds__(64) void bn_finish_kernel(BnFinishArgs a) {
   }
 }
 
-struct BnSrc {
-  const HsRec* z;      // the layer's raw output, HS8 [B][G][h+2][w+2]; null: absent
-  const float *mean, *scale, *beta;   // at the layer's first channel
-};
 struct BnApplyArgs {
   BnSrc a, b;          // b: the second normalised summand (block 0: the shortcut)
   const HsRec* res;    // identity residual, HS8 [B][G][h+2][w+2], or null
@@ -209,7 +205,7 @@ struct TrainPlan {
   size_t part = 0;                        // doubles: the partial sums of the largest layer
   size_t total = 0;
 };
-inline size_t bn_pieces(long long npix) { return (size_t)((npix + BN_PIECE - 1) / BN_PIECE); }
+inline size_t bn_pieces(long long npix) { return bn_fwd_pieces(npix); }
 // every tensor is HS8.  keep: the gradient's plan
 TrainPlan make_train_plan(int capB, int cin_pad, int H, int W, bool keep = false) {
   TrainPlan P;
@@ -311,26 +307,22 @@ int train_forward_launches(pnpx_ctx* ctx, const TrainPlan& P, float* A, const fl
   // statistics of layer l's raw output at `z` (h x w)
   auto stats = [&](size_t z, int h, int w, int l) -> int {
     const BnLayer& L = BL[l];
-    const long long npix = (long long)B * h * w;
-    const int np = (int)bn_pieces(npix);
-    hipLaunchKernelGGL(bn_partial_kernel, dim3(np, L.cout / 8), dim3(256), 0, s, rec(z), L.cout / 8, h, w, npix, part);
-    PNPX_LAUNCH_CHECK();
-    BnFinishArgs a;
-    a.part = part;
-    a.cout = L.cout;
-    a.npieces = np;
-    a.n = npix;
-    a.params = params;
-    a.bn = L.bn;
-    a.mean = st_mean + L.chan0;
-    a.var = st_var + L.chan0;
-    a.scale = st_scale + L.chan0;
-    a.shift = st_shift + L.chan0;
-    a.momentum = momentum;
-    a.update = update_running ? 1 : 0;
-    hipLaunchKernelGGL(bn_finish_kernel, dim3((L.cout + 63) / 64), dim3(64), 0, s, a);
-    PNPX_LAUNCH_CHECK();
-    return PNPX_OK;
+    BnStatsJob J;
+    J.z = rec(z);
+    J.G = L.cout / 8;
+    J.B = B;
+    J.h = h;
+    J.w = w;
+    J.part = part;
+    J.params = params;
+    J.bn = L.bn;
+    J.mean = st_mean + L.chan0;
+    J.var = st_var + L.chan0;
+    J.scale = st_scale + L.chan0;
+    J.shift = st_shift + L.chan0;
+    J.momentum = momentum;
+    J.update = update_running ? 1 : 0;
+    return launch_bn_stats(J, s);
   };
   auto src = [&](size_t z, int l) {
     const BnLayer& L = BL[l];
@@ -338,19 +330,17 @@ int train_forward_launches(pnpx_ctx* ctx, const TrainPlan& P, float* A, const fl
   };
   // `sd`: the space-to-depth copy for a following stride-2 entry (offset; NONE = none); out / res: NONE = none
   auto apply = [&](BnSrc a0, BnSrc b0, size_t res, size_t out, size_t sd, int G, int h, int w) -> int {
-    BnApplyArgs a;
-    a.a = a0;
-    a.b = b0;
-    a.res = res == NONE ? nullptr : rec(res);
-    a.out = out == NONE ? nullptr : rec(out);
-    a.s2d_hs = sd == NONE ? nullptr : rec(sd);
-    a.G = G;
-    a.h = h;
-    a.w = w;
-    a.n = (size_t)B * G * h * w;
-    hipLaunchKernelGGL(bn_apply_kernel, g1(a.n), dim3(256), 0, s, a);
-    PNPX_LAUNCH_CHECK();
-    return PNPX_OK;
+    BnApplyJob J;
+    J.a = a0;
+    J.b = b0;
+    J.res = res == NONE ? nullptr : rec(res);
+    J.out = out == NONE ? nullptr : rec(out);
+    J.s2d_hs = sd == NONE ? nullptr : rec(sd);
+    J.G = G;
+    J.B = B;
+    J.h = h;
+    J.w = w;
+    return launch_bn_apply(J, s);
   };
   const BnSrc no_src{nullptr, nullptr, nullptr, nullptr};
 
@@ -389,6 +379,45 @@ int train_forward_launches(pnpx_ctx* ctx, const TrainPlan& P, float* A, const fl
 }
 
 }  // namespace
+
+int launch_bn_stats(const BnStatsJob& J, hipStream_t s) {
+  const long long npix = (long long)J.B * J.h * J.w;
+  const int np = (int)bn_pieces(npix), cout = J.G * 8;
+  hipLaunchKernelGGL(bn_partial_kernel, dim3(np, J.G), dim3(256), 0, s, J.z, J.G, J.h, J.w, npix, J.part);
+  PNPX_LAUNCH_CHECK();
+  BnFinishArgs a;
+  a.part = J.part;
+  a.cout = cout;
+  a.npieces = np;
+  a.n = npix;
+  a.params = J.params;
+  a.bn = J.bn;
+  a.mean = J.mean;
+  a.var = J.var;
+  a.scale = J.scale;
+  a.shift = J.shift;
+  a.momentum = J.momentum;
+  a.update = J.update ? 1 : 0;
+  hipLaunchKernelGGL(bn_finish_kernel, dim3((cout + 63) / 64), dim3(64), 0, s, a);
+  PNPX_LAUNCH_CHECK();
+  return PNPX_OK;
+}
+
+int launch_bn_apply(const BnApplyJob& J, hipStream_t s) {
+  BnApplyArgs a;
+  a.a = J.a;
+  a.b = J.b;
+  a.res = J.res;
+  a.out = J.out;
+  a.s2d_hs = J.s2d_hs;
+  a.G = J.G;
+  a.h = J.h;
+  a.w = J.w;
+  a.n = (size_t)J.B * J.G * J.h * J.w;
+  hipLaunchKernelGGL(bn_apply_kernel, g1(a.n), dim3(256), 0, s, a);
+  PNPX_LAUNCH_CHECK();
+  return PNPX_OK;
+}
 
 int policy_forward_train(pnpx_ctx* ctx, const float* ob, float* probs, float* det, int B, int H, int W, float momentum,
                          int update_running, hipStream_t s) {

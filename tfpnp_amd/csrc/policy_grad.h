@@ -37,6 +37,36 @@ int launch_pol_head_grad(const PolHeadGradJob& J, hipStream_t s);
 //   gv[b]           1 / (s * boost): the per-image factor of the weight-gradient GEMM, which so undoes the scale
 int launch_pol_grad_seed(const float* gf, unsigned* bits, float2* slot, HsRec* ga, float* gv, float boost, int B, int h, int w, hipStream_t s);
 
+// ------------------------------------------------------------------------------------------- BatchNorm forward (train mode)
+// Kernels: policy_bn.hip.  The train-mode walk and the test probe (net_train_probe.hip) both go through these two launchers.
+constexpr int BN_FWD_PIECE = 2048;   // pixels per partial sum: 256 threads x 8
+inline size_t bn_fwd_pieces(long long npix) { return (size_t)((npix + BN_FWD_PIECE - 1) / BN_FWD_PIECE); }
+struct BnStatsJob {
+  const HsRec* z = nullptr;         // the layer's raw convolution output, HS8 [B][G][h+2][w+2]
+  int G = 0, B = 0, h = 0, w = 0;
+  double* part = nullptr;           // [pieces][8 G][2]: sum, sum of squares
+  float* params = nullptr;          // the live parameter vector
+  size_t bn = 0;                    // floats into it: weight, bias, running_mean, running_var (8 G each)
+  float *mean = nullptr, *var = nullptr, *scale = nullptr, *shift = nullptr;   // out, at the layer's first channel
+  float momentum = 0.f;
+  int update = 0;                   // move the running statistics
+};
+// bn_partial_kernel, bn_finish_kernel
+int launch_bn_stats(const BnStatsJob& J, hipStream_t s);
+struct BnSrc {
+  const HsRec* z;      // the layer's raw output, HS8 [B][G][h+2][w+2]; null: absent
+  const float *mean, *scale, *beta;   // at the layer's first channel
+};
+struct BnApplyJob {
+  BnSrc a{nullptr, nullptr, nullptr, nullptr}, b{nullptr, nullptr, nullptr, nullptr};   // b: the second normalised summand (block 0: the shortcut)
+  const HsRec* res = nullptr;       // identity residual, HS8 [B][G][h+2][w+2], or null
+  HsRec* out = nullptr;             // HS8 [B][G][h+2][w+2] or null
+  HsRec* s2d_hs = nullptr;          // HS8 [B][4G][h/2+2][w/2+2] (phase-major groups, hs_relayout.h) or null
+  int G = 0, B = 0, h = 0, w = 0;
+};
+// bn_apply_kernel
+int launch_bn_apply(const BnApplyJob& J, hipStream_t s);
+
 // ------------------------------------------------------------------------------------------- BatchNorm backward
 constexpr int BN_BWD_PIECE = 2048;   // pixels per partial sum (the forward's BN_PIECE)
 inline size_t bn_bwd_pieces(long long npix) { return (size_t)((npix + BN_BWD_PIECE - 1) / BN_BWD_PIECE); }

@@ -153,7 +153,7 @@ __global__ __launch_bounds__(256) void pol_grad_seed_kernel(const float* __restr
   t /= h;   // t = b * 64 + group
   float v[8];
 #pragma unroll
-  for (int e = 0; e < 8; ++e) v[e] = (gf[t * 8 + e] * sc.x) * k16;
+  for (int e = 0; e < 8; ++e) v[e] = rounded_f32((gf[t * 8 + e] * sc.x) * k16);   // k16 is no power of two where h w is none
   ga[(t * (h + 2) + (y + 1)) * (size_t)(w + 2) + (x + 1)] = hs_pack(v);
 }
 

@@ -84,8 +84,7 @@ bool make_layout(int num_inputs, int n_det, int spi_head, PolicyLayout& L) {
     P.rows = F.cout;
     P.K = K;
     P.mt = 64;
-    for (int t = 0; t < 9; ++t)
-      if ((mask >> t) & 1) P.tap[P.nt++] = t;
+    pack_desc_window(P, mask);
     P.kind = kind;
     P.cin = cin;
     P.Cp = Cp;
@@ -278,10 +277,7 @@ bool make_adj_layout(const PolicyLayout& L, PolAdjLayout& A) {
     P.rows = F.K;
     P.K = F.rows;
     P.mt = 64;
-    P.nt = 0;
-    const int mask = trunk_taps(li, true);
-    for (int t = 0; t < 9; ++t)
-      if ((mask >> t) & 1) P.tap[P.nt++] = t;
+    pack_desc_window(P, trunk_taps(li, true));
     P.adj = 1;
     P.items = (unsigned)((size_t)P.rows * (P.K / 8) * P.nt);
     P.dst = (unsigned)cur.put((size_t)P.rows * P.K * P.nt);

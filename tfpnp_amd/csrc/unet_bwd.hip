@@ -302,10 +302,7 @@ __global__ __launch_bounds__(256) void input_grad_kernel(const float* __restrict
 // conversions twice, differently -- the stored hi = f16(fp32(a * b)), but lo = f16(a * b - f16(a * b)) from the UNROUNDED product
 // (v_fma_mixlo_f16; __fmul_rn does not stop that fold) -- so where fp32(a * b) fell on an f16 tie the record was one hi-ulp (2^-11
 // relative) off, about one element in 8192 (found by tests/test_gpu_vjp_glue.py::test_upsample_adjoint, half-split cases).
-__device__ __forceinline__ float rounded_f32(float x) {
-  asm("" : "+v"(x));      // the fp32 value itself, in a register: nothing upstream can be fused into what is computed from it
-  return x;
-}
+// (rounded_f32: hs_rec.h)
 __global__ __launch_bounds__(256) void outc_bwd_hs_kernel(const float* __restrict__ g_out, const float* __restrict__ pre,
                                                           const float* __restrict__ w, const HsRec* __restrict__ feat,
                                                           HsRec* __restrict__ g_feat, float* __restrict__ g_res,
