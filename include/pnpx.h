@@ -693,6 +693,54 @@ int pnpx_ct_pg_backward(pnpx_ctx* ctx, int n_view, float opnorm, const float* si
                         float* grad_sigma_d, float* grad_tau, float* work, int B, int R, int T,
                         unsigned long long ticket, void* stream);
 
+/* ---- CT, fan beam: flat detector, full circle (own discretisation: DESIGN.md section 7) ---------------------------------------
+ * Centred pixel units (x = column - (R/2 - 0.5), y = row - (R/2 - 0.5)), e_s(b) = (cos b, sin b), e_t(b) = (-sin b, cos b).  View v
+ * has beta_v = 2 pi v / n_view; the source sits at -source_distance e_t, bin j is centred at det_distance e_t + u_j e_s with
+ * u_j = (j - det_count/2 + 0.5) det_spacing; D = source_distance + det_distance.
+ *   forward (ray-driven): ray (v, j) is the parallel-beam ray of angle beta_v - gamma_j (tan gamma_j = u_j / D) and offset
+ *     source_distance sin gamma_j, sampled at the parallel projector's n = pnpx_radon_det_count(R) unit steps (bilinear, zero outside);
+ *   backprojection (pixel-driven): per pixel and view s = x cos b + y sin b, t = -x sin b + y cos b, U = source_distance + t,
+ *     u = s D / U, linear interpolation at bin u / det_spacing + det_count/2 - 0.5 (zero outside), times
+ *     w = sqrt(D^2 + u^2) / (U det_spacing), the reciprocal spacing of the fan's rays at the pixel: with it the pair is adjoint to
+ *     1e-5 on smooth images, as the parallel pair is.
+ * Refused, with a message and nothing launched: source_distance < n/2 + 1 (the source would stand inside the sampled span) and
+ * det_count < 2 (or > 2^20) with PNPX_ERR_SHAPE; det_spacing <= 0, det_distance < 0, a value that is not finite, n_view <= 0,
+ * R <= 0 and a struct that is NULL or not of kind PNPX_GEOM_FAN with PNPX_ERR_ARG. */
+enum { PNPX_GEOM_PARALLEL = 0, PNPX_GEOM_FAN = 1 };
+typedef struct pnpx_radon_geom {
+  int kind;      /* PNPX_GEOM_PARALLEL: the other fields are not read */
+  int n_view;
+  int det_count;
+  float source_distance, det_distance, det_spacing;
+} pnpx_radon_geom;
+/* The default bin count: the fan that just covers the sampled circle, ceil(2 D tan(asin((n/2) / source_distance)) / det_spacing).
+ * 0 with a message for a geometry the entries refuse.  Host only. */
+int pnpx_fan_det_count(int R, float source_distance, float det_distance, float det_spacing);
+/* img [B,1,R,R] <-> sino [B,1,n_view,det_count]. */
+int pnpx_fan_forward(pnpx_ctx* ctx, const float* img, float* sino, const pnpx_radon_geom* geom, int B, int R, void* stream);
+int pnpx_fan_backprojection(pnpx_ctx* ctx, const float* sino, float* img, const pnpx_radon_geom* geom, int B, int R,
+                            void* stream);
+/* Host only, for tests: the tables the kernels read -- view_cs [n_view][2] = (cos, sin) of beta_v rounded to fp32, bins [det_count][3]
+ * = (cos gamma_j, sin gamma_j, source_distance sin gamma_j) -- and *window = the bins per view and 32 x 32 tile that the LDS
+ * backprojection kernel stages (0: n_view windows exceed its 60 KiB and the per-pixel gather kernel runs; same bytes).  Any
+ * output may be NULL.  Refuses what the entries refuse; needs no device. */
+int pnpx_fan_tables(const pnpx_radon_geom* geom, int R, float* view_cs, float* bins, int* window);
+/* HQS for CT (HQSSolver_CT): state cat(x, z) [B,2,R,R], hyper-parameters (sigma_d, mu).  Per iteration x = D(z, sigma_d_i), then
+ * z <- z - (A^T(A z - y0) / opnorm^2 + mu_i (z - x)) / (1 + mu_i): the reference's inexact data step (tasks/ct/solver.py:46-49)
+ * without the dual, with the step 1 / (1 + mu).  geom NULL or of kind PNPX_GEOM_PARALLEL: the parallel pair, y0 [B,1,n_view,det];
+ * a fan geometry (its n_view must equal n_view): y0 [B,1,n_view,det_count].  opnorm as for pnpx_ct_iadmm, of the pair in use. */
+int pnpx_ct_hqs(pnpx_ctx* ctx, const float* vars_in, float* vars_out, const float* y0, const pnpx_radon_geom* geom, int n_view,
+                float opnorm, const float* sigma_d, const float* mu, int param_stride, int B, int R, int T, void* stream);
+/* Training path: `saved` = 3*T*B*R*R floats; grads wrt (cat(x, z), sigma_d, mu), hyper-parameter gradients [T][B];
+ * work = 5*B*R*R + 4 + 2*n_view floats, plus 4*det_count with a fan geometry. */
+int pnpx_ct_hqs_train(pnpx_ctx* ctx, const float* vars_in, float* vars_out, const float* y0, const pnpx_radon_geom* geom,
+                      int n_view, float opnorm, const float* sigma_d, const float* mu, int param_stride, int B, int R, int T,
+                      float* saved, unsigned long long* ticket, void* stream);
+int pnpx_ct_hqs_backward(pnpx_ctx* ctx, const pnpx_radon_geom* geom, int n_view, float opnorm, const float* sigma_d,
+                         const float* mu, int param_stride, const float* saved, const float* grad_vars_out, float* grad_vars_in,
+                         float* grad_sigma_d, float* grad_mu, float* work, int B, int R, int T, unsigned long long ticket,
+                         void* stream);
+
 /* Host-only helpers of the Winograd F(4x4,3x3) kernel (csrc/conv3x3_winof4.hip), for tests: the 1-D matrices the weight packer and the
  * kernel use (G 6x3, B^T 6x6, A^T 4x6, row-major doubles), and the packer itself (w [cout][cin][3][3], cout % 64 == 0, cin % 8 == 0 ->
  * dst 36 * cout * cin floats: [cout/64][cin/8][stage 3][row 2][column pair 3][cout block 4][channel group 4][cout 16][k-step 2][column 2],

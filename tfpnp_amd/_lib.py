@@ -57,6 +57,13 @@ class NetTrainProbeDesc(C.Structure):
                                          "alpha_src", "out", "out2", "dy_out", "grad", "coef", "fout", "fout2", "dout", "flag")])
 
 
+class RadonGeom(C.Structure):
+    """include/pnpx.h: pnpx_radon_geom (field for field)."""
+    _fields_ = [("kind", C.c_int), ("n_view", C.c_int), ("det_count", C.c_int), ("source_distance", C.c_float),
+                ("det_distance", C.c_float), ("det_spacing", C.c_float)]
+PNPX_GEOM_PARALLEL, PNPX_GEOM_FAN = 0, 1
+
+
 # name -> (restype, argtypes); mirrors include/pnpx.h one to one
 _P = c_void_p  # device pointers travel as integers
 _SIGNATURES = {
@@ -178,6 +185,15 @@ _SIGNATURES = {
                             [C.c_int] * 3 + [C.c_ulonglong, c_void_p]),
     "pnpx_ct_iadmm": (C.c_int, [c_void_p, _P, _P, _P, C.c_int, C.c_float, _P, _P, _P] + [C.c_int] * 4 + [c_void_p]),
     "pnpx_ct_pg": (C.c_int, [c_void_p, _P, _P, _P, C.c_int, C.c_float, _P, _P] + [C.c_int] * 4 + [c_void_p]),
+    "pnpx_fan_det_count": (C.c_int, [C.c_int, C.c_float, C.c_float, C.c_float]),
+    "pnpx_fan_forward": (C.c_int, [c_void_p, _P, _P, C.POINTER(RadonGeom), C.c_int, C.c_int, c_void_p]),
+    "pnpx_fan_backprojection": (C.c_int, [c_void_p, _P, _P, C.POINTER(RadonGeom), C.c_int, C.c_int, c_void_p]),
+    "pnpx_fan_tables": (C.c_int, [C.POINTER(RadonGeom), C.c_int, c_float_p, c_float_p, C.POINTER(C.c_int)]),
+    "pnpx_ct_hqs_train": (C.c_int, [c_void_p, _P, _P, _P, C.POINTER(RadonGeom), C.c_int, C.c_float, _P, _P] + [C.c_int] * 4 +
+                          [_P, C.POINTER(C.c_ulonglong), c_void_p]),
+    "pnpx_ct_hqs_backward": (C.c_int, [c_void_p, C.POINTER(RadonGeom), C.c_int, C.c_float, _P, _P, C.c_int, _P, _P, _P, _P, _P, _P] +
+                             [C.c_int] * 3 + [C.c_ulonglong, c_void_p]),
+    "pnpx_ct_hqs": (C.c_int, [c_void_p, _P, _P, _P, C.POINTER(RadonGeom), C.c_int, C.c_float, _P, _P] + [C.c_int] * 4 + [c_void_p]),
     "pnpx_winof4_matrices": (None, [c_void_p, c_void_p, c_void_p]),
     "pnpx_winof4_pack": (C.c_int, [c_void_p, C.c_int, C.c_int, c_void_p]),
     "pnpx_conv3x3_probe": (C.c_int, [c_void_p, C.c_int, c_void_p, c_void_p, C.c_int, _P, C.c_int, _P, C.c_int, _P, _P, _P, C.c_float, _P,

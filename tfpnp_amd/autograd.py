@@ -11,6 +11,7 @@ fused loops (tests/composed_solvers.py):
                            re-computed, transposed MFMA convolutions), dispatcher-registered ops (torch_ops.py)
   * fft2 / ifft2 / plain FFTs   native; the transforms are unitary, so the VJP is the inverse transform
   * radon forward / backprojection   native; each is the other's VJP (the unmatched pair torch_radon also uses)
+  * fan forward / backprojection     the fan-beam pair, the same way (the backprojection carries the ray-density weight)
 and ordinary PyTorch pointwise autograd for the O(N) glue (masks, blends, dual updates).
 """
 import torch
@@ -38,6 +39,17 @@ def radon_forward(img, n_view):
 
 def radon_backprojection(sino, R):
     return T.call("radon_backprojection", sino, int(R))              # VJP = forward projection
+
+
+def fan_forward(img, geom):
+    """geom: a resolved utils.transforms.FanBeam (n_view, det_count, source_distance, det_distance, det_spacing)."""
+    return T.call("fan_forward", img, int(geom.n_view), int(geom.det_count), float(geom.source_distance),
+                  float(geom.det_distance), float(geom.det_spacing))       # VJP = the weighted backprojection
+
+
+def fan_backprojection(sino, R, geom):
+    return T.call("fan_backprojection", sino, int(R), float(geom.source_distance), float(geom.det_distance),
+                  float(geom.det_spacing))                                 # VJP = forward projection
 
 
 # ---- complex helpers (pure layout / pointwise, autograd by PyTorch) -- tfpnp/utils/transforms.py:12-17,260-274

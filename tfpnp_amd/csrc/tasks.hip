@@ -758,6 +758,210 @@ static void launch_radon_backproject(const float* sino, float* img, const float2
                        det, B, scale);
   }
 }
+
+// =================================================================================== CT, fan beam (flat detector, full circle)
+// Geometry (centred pixel units): view angles beta_v = 2 pi v / V, source at -D_so e_t, bin j centred at
+// D_od e_t + u_j e_s, u_j = (j - det/2 + 0.5) du, D = D_so + D_od.  Ray (v, j) is the parallel ray of angle beta_v - gamma_j and offset
+// D_so sin gamma_j, sampled at the parallel projector's n = ceil(sqrt 2 R) unit steps centred on its closest point to the isocentre.
+// A geometry resolved and checked on the host:
+struct FanGeom {
+  int V, det, nstep, win;      // views, bins, unit steps per ray, bins of a tile's LDS window (fan_window)
+  float Dso, D, du;
+};
+// The parallel projector's data path (radon_pad_kernel's row-pair copies, one 16-byte gather per sample, eight lanes per ray and the
+// fixed xor butterfly, the loosely clipped k interval, images dealt to XCDs by b % 8, the fused `sub`), with a direction per RAY:
+// (cos, sin)(beta - gamma) and the offset come from the view table cs [V] = (cos beta, sin beta) and the bin table bins [det] =
+// (cos gamma, sin gamma, D_so sin gamma, 0), both built in double on the host (fan_tables); the products below are rounded one by
+// one (mulx / addx / subx: not contracted) in the order tests/fanbeam_ref.py repeats.  The transposed copy is chosen per ray, and the
+// step count (nstep) and the bin count (det) are different numbers.
+__global__ void radon_fan_forward_kernel(const float* __restrict__ imgP, const float* __restrict__ imgPT,
+                                         const float* __restrict__ sub, float* __restrict__ sino,
+                                         const float2* __restrict__ cs, const float4* __restrict__ bins, int R, int V, int det,
+                                         int nstep, int B) {
+  const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;
+  const int bpi = (int)(((size_t)V * det * RADON_LPR + blockDim.x - 1) / blockDim.x);      // workgroups per image
+  const int b = (slot / bpi) * 8 + xcd;
+  if (b >= B) return;
+  const size_t tid = (size_t)(slot % bpi) * blockDim.x + threadIdx.x;      // within the image
+  const size_t n_rays = (size_t)V * det;
+  const bool live = (tid / RADON_LPR) < n_rays;
+  const size_t ir = live ? tid / RADON_LPR : n_rays - 1;      // dead tail lanes shadow the image's last ray (shuffles stay uniform)
+  const size_t i = (size_t)b * n_rays + ir;
+  const int dk = (int)(tid % RADON_LPR);
+  const int j = (int)(ir % det);
+  const int v = (int)(ir / det);
+  const float2 vb = cs[v];
+  const float4 bn = bins[j];
+  const float c = addx(mulx(vb.x, bn.x), mulx(vb.y, bn.y));       // cos(beta - gamma)
+  const float sn = subx(mulx(vb.y, bn.x), mulx(vb.x, bn.y));      // sin(beta - gamma)
+  const float half = (float)nstep / 2.f - 0.5f, off = (float)R / 2.f - 0.5f;
+  const bool tr = fabsf(sn) > fabsf(c);
+  const int RP = R + 2 * RADON_PAD;
+  const float* im = (tr ? imgPT : imgP) + 2 * (size_t)b * RP * RP;      // this image's padded row-pair copy
+  const float sc = mulx(bn.z, c), ss = mulx(bn.z, sn);
+  // the contributing k interval, as in radon_forward_kernel; the bounds are clamped before the conversion, because a fan ray may
+  // be almost, not exactly, axis-parallel
+  int k0 = 0, k1 = nstep;
+  {
+    auto clip = [&](float base, float slope) {   // base + (k - half) * slope in [-1, R)
+      if (fabsf(slope) < 1e-6f) {
+        if (!(base >= -1.f && base < (float)R)) k1 = 0;
+        return;
+      }
+      const float rs = __builtin_amdgcn_rcpf(slope);
+      const float ka = (-1.f - base) * rs + half, kb = ((float)R - base) * rs + half;
+      const float lo = fmaxf(fminf(ka, kb), -4.f), hi = fminf(fmaxf(ka, kb), (float)nstep + 4.f);
+      k0 = max(k0, (int)floorf(lo) - 2);
+      k1 = min(k1, (int)ceilf(hi) + 3);
+    };
+    clip(sc + off, -sn);
+    clip(ss + off, c);
+  }
+  const float a1 = tr ? ss : sc, a2 = tr ? -c : sn;      // pa = (a1 - t a2) + off
+  const float b1 = tr ? sc : ss, b2 = tr ? sn : -c;      // pb = (b1 - t b2) + off
+  const float* imo = im + 2 * ((size_t)RADON_PAD * RP + RADON_PAD);
+  float acc = 0.f;
+  float t = subr((float)(k0 + dk), half);
+  for (int k = k0 + dk; k < k1; k += RADON_LPR) {
+    const float pa = addx(subx(a1, mulx(t, a2)), off), pb = addx(subx(b1, mulx(t, b2)), off);
+    t += (float)RADON_LPR;                       // exact: integers + 0.5
+    int a0, b0;
+    asm("v_cvt_flr_i32_f32 %0, %1" : "=v"(a0) : "v"(pa));
+    asm("v_cvt_flr_i32_f32 %0, %1" : "=v"(b0) : "v"(pb));
+    const float fa = subr(pa, floorf(pa)), fb = subr(pb, floorf(pb));
+    typedef float f32x4u __attribute__((ext_vector_type(4), aligned(8)));
+    const f32x4u r = *reinterpret_cast<const f32x4u*>(imo + 2 * (ptrdiff_t)(__mul24(b0, RP) + a0));
+    const float top = __builtin_fmaf(fa, r[2] - r[0], r[0]);
+    const float bot = __builtin_fmaf(fa, r[3] - r[1], r[1]);
+    acc += __builtin_fmaf(fb, bot - top, top);
+  }
+  acc = addr(acc, __shfl_xor(acc, 1, 64));
+  acc = addr(acc, __shfl_xor(acc, 2, 64));
+  acc = addr(acc, __shfl_xor(acc, 4, 64));
+  if (live && dk == 0) sino[i] = sub ? subr(acc, sub[i]) : acc;
+}
+static void launch_radon_fan_forward(const float* img, size_t istride, const float* sub, float* sino, const float2* cs,
+                                     const float4* bins, float* pad, int R, const FanGeom& G, int B, hipStream_t s) {
+  const int RP = R + 2 * RADON_PAD;
+  float* padT = pad + 2 * (size_t)B * RP * RP;
+  hipLaunchKernelGGL(radon_pad_kernel, dim3((RP + 31) / 32, (RP + 31) / 32, B), dim3(256), 0, s, img, istride, pad, padT, R);
+  const size_t bpi = ((size_t)G.V * G.det * RADON_LPR + 255) / 256;      // workgroups per image; images dealt to XCDs by b % 8
+  hipLaunchKernelGGL(radon_fan_forward_kernel, dim3((unsigned)(8 * (((size_t)B + 7) / 8) * bpi)), dim3(256), 0, s, pad, padT, sub, sino,
+                     cs, bins, R, G.V, G.det, G.nstep, B);
+}
+// One pixel (xs, ys) under one view t = (cos beta, sin beta): its detector position in bins and the weight of the view,
+// w = sqrt(D^2 + u^2) / (U du), the reciprocal spacing of the fan's rays at the pixel (what makes the pair near-adjoint: DESIGN.md).
+// Every operation is rounded on its own, in the order of tests/fanbeam_ref.py.  U = D_so + t >= 1 by the host's check of D_so.  The
+// position is clamped to [-2, det + 1]: outside (-1, det) both taps are outside the detector whatever the position, so the clamp
+// changes no result and bounds the LDS window.
+__device__ __forceinline__ void fan_pixel_view(float xs, float ys, float2 t, float Dso, float D, float du, float half, float hi,
+                                               float* pos, float* w) {
+  const float s = addx(mulx(xs, t.x), mulx(ys, t.y));
+  const float tt = subx(mulx(ys, t.x), mulx(xs, t.y));
+  const float U = addx(Dso, tt);
+  const float u = divr(mulx(s, D), U);
+  *pos = fminf(fmaxf(addx(divr(u, du), half), -2.f), hi);
+  *w = divr(__fsqrt_rn(addx(mulx(D, D), mulx(u, u))), mulx(U, du));
+}
+__device__ __forceinline__ float fan_view_term(float r0, float r1, float f, float w) {
+  return mulx(w, addx(mulx(r0, subx(1.f, f)), mulx(r1, f)));
+}
+// Pixel-driven fan backprojection, one thread per pixel: the fallback of the LDS kernel below, same bytes.
+__global__ void radon_fan_backproject_kernel(const float* __restrict__ sino, float* __restrict__ img,
+                                             const float2* __restrict__ cs, int R, int V, int det, int B, float Dso, float D,
+                                             float du, float scale) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= (size_t)B * R * R) return;
+  const int x = (int)(i % R), y = (int)((i / R) % R);
+  const int b = (int)(i / ((size_t)R * R));
+  const float off = (float)R / 2.f - 0.5f, half = (float)det / 2.f - 0.5f, hi = (float)det + 1.f;
+  const float xs = subx((float)x, off), ys = subx((float)y, off);
+  float acc = 0.f;
+  for (int v = 0; v < V; ++v) {
+    float pos, w;
+    fan_pixel_view(xs, ys, cs[v], Dso, D, du, half, hi, &pos, &w);
+    const float f0 = floorf(pos);
+    const int s0 = (int)f0;
+    const float* row = sino + ((size_t)b * V + v) * det;
+    const float r0 = (s0 >= 0 && s0 < det) ? row[s0] : 0.f;
+    const float r1 = (s0 + 1 >= 0 && s0 + 1 < det) ? row[s0 + 1] : 0.f;
+    acc = addx(acc, fan_view_term(r0, r1, subx(pos, f0), w));
+  }
+  img[i] = scale == 1.f ? acc : divr(acc, scale);
+}
+// The same with the sinogram staged in LDS, built like radon_backproject_lds_kernel: a workgroup = one 32 x 32 tile of one image.
+// The detector coordinate u = s D / U is a ratio of two affine functions of the pixel with a positive denominator, so over the
+// tile it takes its extremes at the tile's corners: the window of a view starts two bins below the smallest corner position.  Its
+// width `win` comes from the host (fan_window: the widest tile of this geometry; the parallel kernel's 64 bins are too few once the
+// source is close), and a tap index is clamped into the window, which is a no-op unless that bound were wrong.
+__global__ __launch_bounds__(256) void radon_fan_backproject_lds_kernel(const float* __restrict__ sino, float* __restrict__ img,
+                                                                        const float2* __restrict__ cs, int R, int V, int det,
+                                                                        int win, float Dso, float D, float du, float scale) {
+  extern __shared__ float rb_lds[];          // [V][win] taps, then [V] window origins (as int)
+  int* base = reinterpret_cast<int*>(rb_lds + (size_t)V * win);
+  const int b = blockIdx.z, x0 = blockIdx.x * RBP_T, y0 = blockIdx.y * RBP_T;
+  const float off = (float)R / 2.f - 0.5f, half = (float)det / 2.f - 0.5f, hi = (float)det + 1.f;
+  for (int v = threadIdx.x; v < V; v += 256) {
+    const float xa = subx((float)x0, off), xb = subx((float)min(x0 + RBP_T - 1, R - 1), off);
+    const float ya = subx((float)y0, off), yb = subx((float)min(y0 + RBP_T - 1, R - 1), off);
+    float p0, p1, p2, p3, w;
+    fan_pixel_view(xa, ya, cs[v], Dso, D, du, half, hi, &p0, &w);
+    fan_pixel_view(xb, ya, cs[v], Dso, D, du, half, hi, &p1, &w);
+    fan_pixel_view(xa, yb, cs[v], Dso, D, du, half, hi, &p2, &w);
+    fan_pixel_view(xb, yb, cs[v], Dso, D, du, half, hi, &p3, &w);
+    base[v] = (int)floorf(fminf(fminf(p0, p1), fminf(p2, p3))) - 2;      // two bins of slack against rounding
+  }
+  __syncthreads();
+  for (int e = threadIdx.x; e < V * win; e += 256) {
+    const int v = e / win, k = e - v * win;
+    const int sidx = base[v] + k;
+    rb_lds[e] = (sidx >= 0 && sidx < det) ? sino[((size_t)b * V + v) * det + sidx] : 0.f;
+  }
+  __syncthreads();
+  const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
+  const int x = x0 + tx;
+  const float xs = subx((float)min(x, R - 1), off);     // (pixels past the image edge compute inside the window, are not stored)
+  float ys[4], acc[4];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    ys[j] = subx((float)min(y0 + ty + 8 * j, R - 1), off);
+    acc[j] = 0.f;
+  }
+  for (int v = 0; v < V; ++v) {
+    const float2 t = cs[v];
+    const float* row = rb_lds + v * win;
+    const int bv = base[v];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      float pos, w;
+      fan_pixel_view(xs, ys[j], t, Dso, D, du, half, hi, &pos, &w);
+      const float f0 = floorf(pos);
+      const int k = min(max((int)f0 - bv, 0), win - 2);
+      acc[j] = addx(acc[j], fan_view_term(row[k], row[k + 1], subx(pos, f0), w));
+    }
+  }
+  if (x < R) {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int y = y0 + ty + 8 * j;
+      if (y < R) img[((size_t)b * R + y) * R + x] = scale == 1.f ? acc[j] : divr(acc[j], scale);
+    }
+  }
+}
+static bool fan_lds_fits(const FanGeom& G, int B) {      // the LDS budget of radon_backproject_lds_kernel
+  return (size_t)G.V * G.win * sizeof(float) + (size_t)G.V * sizeof(int) <= 60 * 1024 && B <= 65535;
+}
+static void launch_radon_fan_backproject(const float* sino, float* img, const float2* cs, int R, const FanGeom& G, int B,
+                                         float scale, hipStream_t s) {
+  if (fan_lds_fits(G, B)) {
+    const size_t lds = (size_t)G.V * G.win * sizeof(float) + (size_t)G.V * sizeof(int);
+    hipLaunchKernelGGL(radon_fan_backproject_lds_kernel, dim3((R + RBP_T - 1) / RBP_T, (R + RBP_T - 1) / RBP_T, B), dim3(256), lds, s,
+                       sino, img, cs, R, G.V, G.det, G.win, G.Dso, G.D, G.du, scale);
+  } else {   // V x window beyond the budget (close source, many views): the per-pixel gather kernel
+    hipLaunchKernelGGL(radon_fan_backproject_kernel, dim3((unsigned)(((size_t)B * R * R + 255) / 256)), dim3(256), 0, s, sino, img, cs, R,
+                       G.V, G.det, B, G.Dso, G.D, G.du, scale);
+  }
+}
 // z = z - tau*(g + mu*(z - (x+u))); u = u + x - z; d = z - u                tasks/ct/solver.py:46-49
 __global__ void ct_update_kernel(const float* __restrict__ g, const float* __restrict__ xr, const float* zin,
                                  const float* uin, float* xout, float* zout, float* uout, size_t istride,
@@ -789,6 +993,58 @@ __global__ void real_diff_slots_kernel(const float* __restrict__ a, const float*
   const size_t b = i / HW, r = i - b * HW;
   d[i] = subr(a[b * istride + r], c[b * istride + r]);
 }
+// ---- HQS for CT: x = D(z), then one inexact data step on z (the reference's iADMM data step, tasks/ct/solver.py:46-49, without
+// the dual; step 1 / (1 + mu), the reciprocal Lipschitz bound of the z-objective with A normalised)
+// d = the z plane of a state as a contiguous image batch (the first denoiser input; cotangent e = gz' of the backward)
+__global__ void ct_hqs_plane_kernel(const float* __restrict__ v, size_t istride, float* __restrict__ d, int HW, int B) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= (size_t)HW * B) return;
+  const size_t b = i / HW, r = i - b * HW;
+  d[i] = v[b * istride + r + HW];
+}
+// q = z - x;  G = g + mu q;  z' = z - G / (1 + mu);  d = z' (the next denoiser input).  Gs / qs (training forward): G and q kept.
+__global__ void ct_hqs_update_kernel(const float* __restrict__ g, const float* __restrict__ xr, const float* zin, float* xout,
+                                     float* zout, size_t istride, float* __restrict__ d, const float* __restrict__ mu, int stride,
+                                     int HW, int B, int write_x, float* __restrict__ Gs, float* __restrict__ qs) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= (size_t)HW * B) return;
+  const size_t b = i / HW, r = i - b * HW;
+  const float m = mu[b * stride];
+  const float z = zin[b * istride + r], xv = xr[i];
+  const float q = subr(z, xv);
+  const float G = addr(g[i], mulr(m, q));
+  const float zn = subr(z, divr(G, addr(1.f, m)));
+  zout[b * istride + r] = zn;
+  d[i] = zn;
+  if (write_x) xout[b * istride + r] = xv;
+  if (Gs) {
+    Gs[i] = G;
+    qs[i] = q;
+  }
+}
+// Backward of one HQS iteration after J = A^T A e / opnorm^2, e = gz', a = 1 / (1 + mu):
+//   gxr = gx' + a mu e (into the denoiser's VJP),  gz = e - a (J + mu e),  gx = 0 (the iteration does not read x),
+//   d/d mu = -a <e, q - a G>
+__global__ void ct_hqs_adjoint_kernel(const float* __restrict__ e, const float* __restrict__ J, float* g, size_t istride,
+                                      const float* __restrict__ Gs, const float* __restrict__ qs, const float* __restrict__ mu,
+                                      int stride, int HW, int B, float* __restrict__ gxr, float* __restrict__ c_mu) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= (size_t)HW * B) return;
+  const size_t b = i / HW, r = i - b * HW;
+  const float m = mu[b * stride], a = 1.f / (1.f + m);
+  float* gi = g + b * istride + r;
+  const float ev = e[i];
+  c_mu[i] = -a * (ev * (qs[i] - a * Gs[i]));
+  gxr[i] = gi[0] + a * m * ev;
+  gi[0] = 0.f;
+  gi[HW] = ev - a * (J[i] + m * ev);
+}
+__global__ void ct_hqs_adjoint_finish_kernel(const float* __restrict__ gd, float* g, size_t istride, int HW, int B) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= (size_t)HW * B) return;
+  const size_t b = i / HW, r = i - b * HW;
+  g[b * istride + r + HW] += gd[i];
+}
 
 int radon_table(int R, int V, std::vector<float2>* cs, int* det) {
   *det = (int)std::ceil(std::sqrt(2.0) * R);
@@ -800,6 +1056,93 @@ int radon_table(int R, int V, std::vector<float2>* cs, int* det) {
     (*cs)[v] = make_float2((float)std::cos((double)af), (float)std::sin((double)af));
   }
   return PNPX_OK;
+}
+
+void fan_tables(const FanGeom& G, std::vector<float2>* cs, std::vector<float4>* bins);
+int fan_window(const FanGeom& G, int R, const std::vector<float2>& cs);
+// Checks a fan geometry and resolves what the launches need; on a refusal nothing has been launched.
+int fan_resolve(const pnpx_radon_geom* g, int R, FanGeom* G) {
+  if (!g || g->kind != PNPX_GEOM_FAN) {
+    set_error("fan geometry: expected a pnpx_radon_geom of kind PNPX_GEOM_FAN");
+    return PNPX_ERR_ARG;
+  }
+  if (R <= 0 || g->n_view <= 0) {
+    set_error("fan geometry: R and n_view must be positive (R %d, n_view %d)", R, g->n_view);
+    return PNPX_ERR_ARG;
+  }
+  const int n = (int)std::ceil(std::sqrt(2.0) * R);
+  const double Dso = g->source_distance, Dod = g->det_distance, du = g->det_spacing;
+  if (!std::isfinite(Dso) || !std::isfinite(Dod) || !std::isfinite(du)) {
+    set_error("fan geometry: distances and spacing must be finite");
+    return PNPX_ERR_ARG;
+  }
+  if (!(Dso >= n / 2.0 + 1.0)) {
+    set_error("fan geometry: source_distance %g puts the source inside the sampled span (needs >= n/2 + 1 = %g at R = %d)", Dso,
+              n / 2.0 + 1.0, R);
+    return PNPX_ERR_SHAPE;
+  }
+  if (!(du > 0.0)) {
+    set_error("fan geometry: det_spacing must be positive, got %g", du);
+    return PNPX_ERR_ARG;
+  }
+  if (!(Dod >= 0.0)) {
+    set_error("fan geometry: det_distance must not be negative, got %g", Dod);
+    return PNPX_ERR_ARG;
+  }
+  if (g->det_count < 2 || g->det_count > (1 << 20)) {
+    set_error("fan geometry: det_count must be in [2, 2^20], got %d", g->det_count);
+    return PNPX_ERR_SHAPE;
+  }
+  G->V = g->n_view;
+  G->det = g->det_count;
+  G->nstep = n;
+  G->Dso = (float)Dso;
+  G->D = (float)(Dso + Dod);
+  G->du = (float)du;
+  std::vector<float2> cs;
+  std::vector<float4> bins;
+  fan_tables(*G, &cs, &bins);
+  G->win = fan_window(*G, R, cs);
+  return PNPX_OK;
+}
+// View table (cos, sin)(beta_v), beta_v = 2 pi v / V rounded to fp32 before cos / sin are taken in double (as radon_table does), and bin
+// table (cos gamma_j, sin gamma_j, D_so sin gamma_j, 0) with u_j = (j - det/2 + 0.5) du, L_j = sqrt(D^2 + u_j^2).  D, D_so and du are the
+// fp32 values the kernels receive.
+void fan_tables(const FanGeom& G, std::vector<float2>* cs, std::vector<float4>* bins) {
+  cs->resize(G.V);
+  for (int v = 0; v < G.V; ++v) {
+    const float af = (float)((2.0 * M_PI * (double)v) / (double)G.V);
+    (*cs)[v] = make_float2((float)std::cos((double)af), (float)std::sin((double)af));
+  }
+  bins->resize(G.det);
+  const double D = G.D, du = G.du;
+  for (int j = 0; j < G.det; ++j) {
+    const double u = ((double)j - G.det / 2.0 + 0.5) * du, L = std::sqrt(D * D + u * u);
+    (*bins)[j] = make_float4((float)(D / L), (float)(u / L), (float)((double)G.Dso * (u / L)), 0.f);
+  }
+}
+// Bins of the LDS window of radon_fan_backproject_lds_kernel: the widest span, over every 32 x 32 tile and view, between the tile's
+// corner positions (clamped as fan_pixel_view clamps them), plus the kernel's two bins below, the second tap above and slack for
+// the fp32 rounding of the kernel's own corner values; rounded up to a multiple of 4.
+int fan_window(const FanGeom& G, int R, const std::vector<float2>& cs) {
+  const double off = R / 2.0 - 0.5, half = G.det / 2.0 - 0.5, hi = G.det + 1.0;
+  int span = 0;
+  for (int y0 = 0; y0 < R; y0 += RBP_T)
+    for (int x0 = 0; x0 < R; x0 += RBP_T) {
+      const double xs[2] = {x0 - off, std::min(x0 + RBP_T - 1, R - 1) - off}, ys[2] = {y0 - off, std::min(y0 + RBP_T - 1, R - 1) - off};
+      for (int v = 0; v < G.V; ++v) {
+        double lo = 1e300, up = -1e300;
+        for (int k = 0; k < 4; ++k) {
+          const double x = xs[k & 1], y = ys[k >> 1];
+          const double s = x * cs[v].x + y * cs[v].y, U = (double)G.Dso + (y * cs[v].x - x * cs[v].y);
+          const double pos = std::min(std::max(s * (double)G.D / U / (double)G.du + half, -2.0), hi);
+          lo = std::min(lo, pos);
+          up = std::max(up, pos);
+        }
+        span = std::max(span, (int)std::floor(up) - (int)std::floor(lo));
+      }
+    }
+  return (span + 8 + 3) & ~3;
 }
 
 // scratch carve-up helper
@@ -1252,21 +1595,40 @@ struct CtScratch {
   const float2* cs;
   float *sino, *pad, *img[4];
   int det;
+  const float4* bins;      // fan beam: the bin table, and the resolved geometry
+  const FanGeom* fan;
 };
 // `cs_home`: where the (cos, sin) table lives.  NULL = in the scratch itself (forward loops: nothing else touches the scratch
 // while they run); the backward loops pass a place in their caller-provided work buffer, because the denoiser's VJP uses --
 // and may re-allocate -- the same scratch between two uses of the table, and re-carve the rest every iteration (upload = false).
+// `fan` (the HQS loops): a resolved fan geometry, which must outlive C; its bin table [det] float4 stands in front of the view table, so a
+// `cs_home` is 16-byte aligned and holds 4 * det + 2 * n_view floats then.
 static int ct_scratch(pnpx_ctx* ctx, int B, int R, int n_view, int extra, hipStream_t s, CtScratch* C,
-                      float2* cs_home = nullptr, bool upload = true) {
+                      float2* cs_home = nullptr, bool upload = true, const FanGeom* fan = nullptr) {
   const size_t n = (size_t)R * R * B;
-  const int det = pnpx_radon_det_count(R);
+  const int det = fan ? fan->det : pnpx_radon_det_count(R);
   void* p;
   PNPX_TRY(ctx_scratch(ctx, (extra * n + radon_pad_floats(B, R) + (size_t)B * n_view * det) * sizeof(float) +
-                                sizeof(float2) * n_view + 16384, &p));
+                                sizeof(float2) * n_view + (fan ? sizeof(float4) * det : 0) + 16384, &p));
   Carver cv{static_cast<char*>(p)};
   float2* table = cv.take<float2>(n_view);
-  if (cs_home) table = cs_home;
-  if (upload) {
+  float4* btab = fan ? cv.take<float4>(det) : nullptr;
+  if (cs_home && fan) {
+    btab = reinterpret_cast<float4*>(cs_home);
+    table = reinterpret_cast<float2*>(btab + det);
+  } else if (cs_home) {
+    table = cs_home;
+  }
+  C->bins = btab;
+  C->fan = fan;
+  if (upload && fan) {
+    std::vector<float2> cs;
+    std::vector<float4> bins;
+    fan_tables(*fan, &cs, &bins);
+    PNPX_HIP(hipMemcpyAsync(table, cs.data(), sizeof(float2) * n_view, hipMemcpyHostToDevice, s));
+    PNPX_HIP(hipMemcpyAsync(btab, bins.data(), sizeof(float4) * det, hipMemcpyHostToDevice, s));
+    PNPX_HIP(hipStreamSynchronize(s));      // the host tables are locals
+  } else if (upload) {
     std::vector<float2> cs;
     int det2;
     PNPX_TRY(radon_table(R, n_view, &cs, &det2));
@@ -1284,9 +1646,89 @@ static int ct_scratch(pnpx_ctx* ctx, int B, int R, int n_view, int extra, hipStr
 // out = A^T (A img - sub) / op2 for a contiguous image batch
 static int ct_normal_op(const CtScratch& C, const float* img, size_t istride, const float* sub, float* out, float op2, int R,
                         int n_view, int B, hipStream_t s) {
+  if (C.fan) {
+    launch_radon_fan_forward(img, istride, sub, C.sino, C.cs, C.bins, C.pad, R, *C.fan, B, s);
+    PNPX_LAUNCH_CHECK();
+    launch_radon_fan_backproject(C.sino, out, C.cs, R, *C.fan, B, op2, s);
+    PNPX_LAUNCH_CHECK();
+    return PNPX_OK;
+  }
   launch_radon_forward(img, istride, sub, C.sino, C.cs, C.pad, R, n_view, C.det, B, s);
   PNPX_LAUNCH_CHECK();
   launch_radon_backproject(C.sino, out, C.cs, R, n_view, C.det, B, op2, s);
+  PNPX_LAUNCH_CHECK();
+  return PNPX_OK;
+}
+
+// ---- fan-beam pair (geometry: include/pnpx.h)
+static int upload_fan(const FanGeom& G, hipStream_t s, Carver* cv, const float2** cs_dev, const float4** bins_dev) {
+  std::vector<float2> cs;
+  std::vector<float4> bins;
+  fan_tables(G, &cs, &bins);
+  float4* b = cv->take<float4>(G.det);
+  float2* c = cv->take<float2>(G.V);
+  // small synchronous uploads (the host tables are locals)
+  PNPX_HIP(hipMemcpyAsync(b, bins.data(), sizeof(float4) * G.det, hipMemcpyHostToDevice, s));
+  PNPX_HIP(hipMemcpyAsync(c, cs.data(), sizeof(float2) * G.V, hipMemcpyHostToDevice, s));
+  PNPX_HIP(hipStreamSynchronize(s));
+  *cs_dev = c;
+  *bins_dev = b;
+  return PNPX_OK;
+}
+int pnpx_fan_det_count(int R, float source_distance, float det_distance, float det_spacing) {
+  const double n = std::ceil(std::sqrt(2.0) * R), Dso = source_distance, D = Dso + (double)det_distance, du = det_spacing;
+  if (R <= 0 || !(Dso >= n / 2.0 + 1.0) || !(det_distance >= 0.f) || !(du > 0.0) || !std::isfinite(D / du)) {
+    set_error("pnpx_fan_det_count: bad geometry (R %d, source_distance %g, det_distance %g, det_spacing %g)", R, Dso,
+              (double)det_distance, du);
+    return 0;
+  }
+  return (int)std::ceil(2.0 * D * std::tan(std::asin((n / 2.0) / Dso)) / du);
+}
+
+int pnpx_fan_tables(const pnpx_radon_geom* geom, int R, float* view_cs, float* bins, int* window) {
+  FanGeom G;
+  PNPX_TRY(fan_resolve(geom, R, &G));
+  std::vector<float2> cs;
+  std::vector<float4> bt;
+  fan_tables(G, &cs, &bt);
+  for (int v = 0; v < G.V && view_cs; ++v) view_cs[2 * v] = cs[v].x, view_cs[2 * v + 1] = cs[v].y;
+  for (int j = 0; j < G.det && bins; ++j) bins[3 * j] = bt[j].x, bins[3 * j + 1] = bt[j].y, bins[3 * j + 2] = bt[j].z;
+  if (window) *window = fan_lds_fits(G, 1) ? G.win : 0;
+  return PNPX_OK;
+}
+
+int pnpx_fan_forward(pnpx_ctx* ctx, const float* img, float* sino, const pnpx_radon_geom* geom, int B, int R, void* stream) {
+  LOCK_CTX(ctx);
+  REQUIRE(img && sino && B > 0, "pnpx_fan_forward: bad argument");
+  FanGeom G;
+  PNPX_TRY(fan_resolve(geom, R, &G));
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  void* p;
+  PNPX_TRY(ctx_scratch(ctx, sizeof(float2) * G.V + sizeof(float4) * G.det + radon_pad_floats(B, R) * sizeof(float) + 16384, &p));
+  Carver cv{static_cast<char*>(p)};
+  const float2* cs;
+  const float4* bins;
+  PNPX_TRY(upload_fan(G, s, &cv, &cs, &bins));
+  float* pad = cv.take<float>(radon_pad_floats(B, R));
+  launch_radon_fan_forward(img, (size_t)R * R, nullptr, sino, cs, bins, pad, R, G, B, s);
+  PNPX_LAUNCH_CHECK();
+  return PNPX_OK;
+}
+
+int pnpx_fan_backprojection(pnpx_ctx* ctx, const float* sino, float* img, const pnpx_radon_geom* geom, int B, int R,
+                            void* stream) {
+  LOCK_CTX(ctx);
+  REQUIRE(img && sino && B > 0, "pnpx_fan_backprojection: bad argument");
+  FanGeom G;
+  PNPX_TRY(fan_resolve(geom, R, &G));
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  void* p;
+  PNPX_TRY(ctx_scratch(ctx, sizeof(float2) * G.V + sizeof(float4) * G.det + 16384, &p));
+  Carver cv{static_cast<char*>(p)};
+  const float2* cs;
+  const float4* bins;
+  PNPX_TRY(upload_fan(G, s, &cv, &cs, &bins));
+  launch_radon_fan_backproject(sino, img, cs, R, G, B, 1.f, s);
   PNPX_LAUNCH_CHECK();
   return PNPX_OK;
 }
@@ -1448,6 +1890,109 @@ int pnpx_ct_pg_backward(pnpx_ctx* ctx, int n_view, float opnorm, const float* si
                          param_stride, HW, B, grad_vars_in, c_tau);
       PNPX_LAUNCH_CHECK();
       hipLaunchKernelGGL(pr_item_sum_kernel, dim3(B), dim3(256), 0, s, c_tau, grad_tau + (size_t)i * B, HW);
+      PNPX_LAUNCH_CHECK();
+    }
+    return PNPX_OK;
+  });
+}
+
+// The geometry argument of the HQS trio: NULL or kind PNPX_GEOM_PARALLEL = the parallel pair with today's table; a fan geometry is
+// resolved into *G (its n_view must be the call's).  *fan = G or NULL.
+static int ct_hqs_geometry(const char* name, const pnpx_radon_geom* geom, int n_view, int R, FanGeom* G, const FanGeom** fan) {
+  *fan = nullptr;
+  if (!geom || geom->kind == PNPX_GEOM_PARALLEL) return PNPX_OK;
+  PNPX_TRY(fan_resolve(geom, R, G));
+  if (G->V != n_view) {
+    set_error("%s: the geometry has %d views, the call %d", name, G->V, n_view);
+    return PNPX_ERR_ARG;
+  }
+  *fan = G;
+  return PNPX_OK;
+}
+// where the backward loops keep the tables in `work`: behind k image-sized buffers, 16-byte aligned
+static size_t ct_table_offset(size_t k, size_t n) { return (k * n + 3) & ~(size_t)3; }
+
+// HQSSolver_CT.forward: state cat(x, z); per iteration x = D(z, sigma_d_i), z <- z - (A^T(A z - y0) / opnorm^2 + mu_i (z - x)) / (1 + mu_i).
+// `saved` != NULL (training path): per iteration the denoiser input z_i [T][n], G = g + mu (z - x) [T][n] and q = z - x [T][n]
+static int ct_hqs_forward(pnpx_ctx* ctx, const float* vars_in, float* vars_out, const float* y0, const pnpx_radon_geom* geom,
+                          int n_view, float opnorm, const float* sigma_d, const float* mu, int param_stride, int B, int R, int T,
+                          float* saved, unsigned long long* ticket_out, hipStream_t s) {
+  REQUIRE(vars_in && vars_out && y0 && sigma_d && mu && B > 0 && R > 0 && n_view > 0 && T >= 0 && param_stride >= T &&
+              opnorm > 0.f,
+          "pnpx_ct_hqs: bad argument");
+  FanGeom G;
+  const FanGeom* fan;
+  PNPX_TRY(ct_hqs_geometry("pnpx_ct_hqs", geom, n_view, R, &G, &fan));
+  const Prox px = prox_begin(ctx, sigma_d, param_stride, B, R, R, saved, ticket_out, s);
+  const auto [HW, is, n] = state_dims(B, R, R, 2);
+  if (T == 0) return copy_state(vars_out, vars_in, sizeof(float) * is * B, s);
+  CtScratch C;
+  PNPX_TRY(ct_scratch(ctx, B, R, n_view, 3, s, &C, nullptr, true, fan));
+  float *d = C.img[0], *xr = C.img[1], *g = C.img[2];
+  const float op2 = (float)((double)opnorm * (double)opnorm);
+  hipLaunchKernelGGL(ct_hqs_plane_kernel, g1(n), dim3(256), 0, s, vars_in, is, d, HW, B);
+  PNPX_LAUNCH_CHECK();
+  for (int i = 0; i < T; ++i) {
+    PNPX_TRY(prox_step(px, i, d, xr, saved ? saved + (size_t)i * n : nullptr));
+    const float* zi = ((i == 0) ? vars_in : vars_out) + HW;
+    PNPX_TRY(ct_normal_op(C, zi, is, y0, g, op2, R, n_view, B, s));
+    hipLaunchKernelGGL(ct_hqs_update_kernel, g1(n), dim3(256), 0, s, g, xr, zi, vars_out, vars_out + HW, is, d, mu + i,
+                       param_stride, HW, B, i == T - 1, saved ? saved + ((size_t)T + i) * n : nullptr,
+                       saved ? saved + (2 * (size_t)T + i) * n : nullptr);
+    PNPX_LAUNCH_CHECK();
+  }
+  return PNPX_OK;
+}
+
+int pnpx_ct_hqs(pnpx_ctx* ctx, const float* vars_in, float* vars_out, const float* y0, const pnpx_radon_geom* geom, int n_view,
+                float opnorm, const float* sigma_d, const float* mu, int param_stride, int B, int R, int T, void* stream) {
+  return solver_entry(ctx, stream, [&](hipStream_t s) {
+    return ct_hqs_forward(ctx, vars_in, vars_out, y0, geom, n_view, opnorm, sigma_d, mu, param_stride, B, R, T, nullptr, nullptr,
+                          s);
+  });
+}
+
+int pnpx_ct_hqs_train(pnpx_ctx* ctx, const float* vars_in, float* vars_out, const float* y0, const pnpx_radon_geom* geom,
+                      int n_view, float opnorm, const float* sigma_d, const float* mu, int param_stride, int B, int R, int T,
+                      float* saved, unsigned long long* ticket, void* stream) {
+  return solver_train_entry(ctx, "pnpx_ct_hqs_train", saved || T == 0, ticket, stream, [&](hipStream_t s) {
+    return ct_hqs_forward(ctx, vars_in, vars_out, y0, geom, n_view, opnorm, sigma_d, mu, param_stride, B, R, T, saved, ticket, s);
+  });
+}
+
+// VJP of the T-iteration CT HQS map wrt (cat(x, z), sigma_d, mu); the data step's adjoint is A^T A / opnorm^2 with the projector
+// pair standing in for each other's transpose, as in the iADMM backward.  work = 5*B*R*R + 4 + 2*n_view (+ 4*det_count, fan) floats.
+int pnpx_ct_hqs_backward(pnpx_ctx* ctx, const pnpx_radon_geom* geom, int n_view, float opnorm, const float* sigma_d,
+                         const float* mu, int param_stride, const float* saved, const float* grad_vars_out, float* grad_vars_in,
+                         float* grad_sigma_d, float* grad_mu, float* work, int B, int R, int T, unsigned long long ticket,
+                         void* stream) {
+  return solver_entry(ctx, stream, [&](hipStream_t s) -> int {
+    REQUIRE(sigma_d && mu && grad_vars_out && grad_vars_in && B > 0 && R > 0 && n_view > 0 && T >= 0 && param_stride >= T &&
+                opnorm > 0.f && (T == 0 || (saved && grad_sigma_d && grad_mu && work)),
+            "pnpx_ct_hqs_backward: bad argument");
+    FanGeom G;
+    const FanGeom* fan;
+    PNPX_TRY(ct_hqs_geometry("pnpx_ct_hqs_backward", geom, n_view, R, &G, &fan));
+    const auto [HW, is, n] = state_dims(B, R, R, 2);
+    PNPX_TRY(copy_state(grad_vars_in, grad_vars_out, sizeof(float) * is * B, s));
+    if (T == 0) return PNPX_OK;
+    CtScratch C;
+    float2* cs_home = reinterpret_cast<float2*>(work + ct_table_offset(5, n));   // the tables outlive the VJP calls in the work buffer
+    PNPX_TRY(ct_scratch(ctx, B, R, n_view, 0, s, &C, cs_home, true, fan));
+    const float op2 = (float)((double)opnorm * (double)opnorm);
+    float *e = work, *J = work + n, *gxr = work + 2 * n, *gd = work + 3 * n, *c_mu = work + 4 * n;
+    for (int i = T - 1; i >= 0; --i) {
+      PNPX_TRY(ct_scratch(ctx, B, R, n_view, 0, s, &C, cs_home, false, fan));   // re-carve: the VJP below shares (and may grow) the scratch
+      hipLaunchKernelGGL(ct_hqs_plane_kernel, g1(n), dim3(256), 0, s, grad_vars_in, is, e, HW, B);
+      PNPX_LAUNCH_CHECK();
+      PNPX_TRY(ct_normal_op(C, e, (size_t)HW, nullptr, J, op2, R, n_view, B, s));
+      hipLaunchKernelGGL(ct_hqs_adjoint_kernel, g1(n), dim3(256), 0, s, e, J, grad_vars_in, is, saved + ((size_t)T + i) * n,
+                         saved + (2 * (size_t)T + i) * n, mu + i, param_stride, HW, B, gxr, c_mu);
+      PNPX_LAUNCH_CHECK();
+      hipLaunchKernelGGL(pr_item_sum_kernel, dim3(B), dim3(256), 0, s, c_mu, grad_mu + (size_t)i * B, HW);
+      PNPX_LAUNCH_CHECK();
+      PNPX_TRY(prox_vjp(ctx, i, saved, sigma_d, param_stride, gxr, gd, grad_sigma_d, B, R, R, s, ticket));
+      hipLaunchKernelGGL(ct_hqs_adjoint_finish_kernel, g1(n), dim3(256), 0, s, gd, grad_vars_in, is, HW, B);
       PNPX_LAUNCH_CHECK();
     }
     return PNPX_OK;

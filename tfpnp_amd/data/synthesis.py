@@ -144,15 +144,18 @@ def spi_measure(gt, K, generator=None, counts=None):
     return {'x0': x0, 'output': x0.clone(), 'gt': gt, 'K': torch.full_like(gt, K / 10)}
 
 
-def ct_measure(gt, view, radon_generator=None, noise_model=None, generator=None):
+def ct_measure(gt, view, radon_generator=None, noise_model=None, generator=None, geometry=None):
     """gt [B,1,R,R], view = number of projection angles -> dict(y0 sinogram, ATy0, output, x0 = FBP, gt, view map,
-    sigma_n map)."""
+    sigma_n map).  geometry: None = parallel beam, or a transforms.FanBeam; there is no fan-beam FBP, so with a fan geometry
+    x0 is ATy0 (the normalised weighted backprojection of y0)."""
     radon_generator = radon_generator or transforms.RadonGenerator()
-    radon = radon_generator(gt.shape[-1], view, device=gt.device)
+    radon = (radon_generator(gt.shape[-1], view, device=gt.device) if geometry is None else
+             radon_generator(gt.shape[-1], view, device=gt.device, geometry=geometry))
     y0 = radon.forward(gt)
     sigma_n = 0.0
     if noise_model is not None:
         y0, sigma_n = noise_model(y0, generator=generator)
     ATy0 = radon.backprojection_norm(y0)
-    return {'y0': y0, 'ATy0': ATy0, 'output': ATy0.clone(), 'x0': radon.filter_backprojection(y0), 'gt': gt,
+    x0 = radon.filter_backprojection(y0) if geometry is None else ATy0.clone()
+    return {'y0': y0, 'ATy0': ATy0, 'output': ATy0.clone(), 'x0': x0, 'gt': gt,
             'view': torch.full_like(gt, view / 120), 'sigma_n': _item_map(sigma_n, gt)}

@@ -1112,6 +1112,96 @@ def ct_pg_backward(ctx, n_view, opnorm, sigma_d, tau, saved, grad_out, iter_num=
     return _solver_backward(_CT_PG, ctx, (n_view, opnorm), (sigma_d, tau), saved, grad_out, iter_num, ticket)
 
 
+# ------------------------------------------------------------------------------------------------- CT, fan beam
+def fan_geom(n_view, det_count, source_distance, det_distance, det_spacing):
+    """include/pnpx.h: a pnpx_radon_geom of kind PNPX_GEOM_FAN.  Nothing is checked here: the native entries refuse a bad one."""
+    return _lib.RadonGeom(_lib.PNPX_GEOM_FAN, int(n_view), int(det_count), float(source_distance), float(det_distance),
+                          float(det_spacing))
+
+
+def fan_det_count(R, source_distance, det_distance, det_spacing):
+    """pnpx_fan_det_count: the bin count of the fan that just covers the sampled circle (host only)."""
+    n = int(_lib.lib().pnpx_fan_det_count(int(R), float(source_distance), float(det_distance), float(det_spacing)))
+    if n <= 0:
+        raise PnpxError(_lib.lib().pnpx_last_error().decode("utf-8", "replace"))
+    return n
+
+
+def fan_tables(R, n_view, det_count, source_distance, det_distance, det_spacing):
+    """pnpx_fan_tables (host only) -> (view table [n_view, 2], bin table [det_count, 3], LDS window in bins or 0 = gather kernel)."""
+    g = fan_geom(n_view, det_count, source_distance, det_distance, det_spacing)
+    cs = np.zeros((max(int(n_view), 0), 2), np.float32)
+    bins = np.zeros((max(int(det_count), 0), 3), np.float32)
+    win = C.c_int(0)
+    check(_lib.lib().pnpx_fan_tables(g, int(R), cs.ctypes.data_as(_lib.c_float_p), bins.ctypes.data_as(_lib.c_float_p), C.byref(win)))
+    return cs, bins, int(win.value)
+
+
+def fan_forward(img, n_view, det_count, source_distance, det_distance, det_spacing, ctx=None):
+    """pnpx_fan_forward: [B,1,R,R] -> [B,1,n_view,det_count]."""
+    img = _f32(img, "img")
+    B, _, R, R2 = img.shape
+    if R != R2:
+        raise PnpxError("fan_forward: square images only")
+    g = fan_geom(n_view, det_count, source_distance, det_distance, det_spacing)
+    out = torch.empty((B, 1, max(int(n_view), 0), max(int(det_count), 0)), device=img.device, dtype=torch.float32)
+    ctx = ctx or default_context(img.device)
+    with torch.cuda.device(img.device):
+        check(_lib.lib().pnpx_fan_forward(ctx.handle, _p(img), _p(out), g, B, R, _stream(img)))
+    return out
+
+
+def fan_backprojection(sino, R, source_distance, det_distance, det_spacing, ctx=None):
+    """pnpx_fan_backprojection: [B,1,n_view,det_count] -> [B,1,R,R] (weighted: include/pnpx.h)."""
+    sino = _f32(sino, "sino")
+    B, _, V, det = sino.shape
+    g = fan_geom(V, det, source_distance, det_distance, det_spacing)
+    out = torch.empty((B, 1, int(R), int(R)), device=sino.device, dtype=torch.float32)
+    ctx = ctx or default_context(sino.device)
+    with torch.cuda.device(sino.device):
+        check(_lib.lib().pnpx_fan_backprojection(ctx.handle, _p(sino), _p(out), g, B, int(R), _stream(sino)))
+    return out
+
+
+def _aux_ct_hqs(L, v, args, backward):
+    """aux = ([y0,] n_view, opnorm, det_count, source_distance, det_distance, det_spacing); det_count 0 = parallel beam."""
+    B, R = v.shape[0], v.shape[2]
+    n_view, opnorm, det_count, dso, dod, du = args[-6:]
+    geom = fan_geom(n_view, det_count, dso, dod, du) if int(det_count) else None
+    lead = []
+    if not backward:            # the backward entry takes no sinogram
+        y0 = _f32(args[0], "y0")
+        want = (B, 1, int(n_view), int(det_count) if int(det_count) else radon_det_count(R))
+        if tuple(y0.shape) != want:
+            raise PnpxError(f"y0: sinogram of shape {tuple(y0.shape)} does not match (B, 1, n_view, det) = {want}")
+        lead = [y0]
+    return lead + [geom, int(n_view), float(opnorm)], (B, R), R * R, 1
+
+
+_CT_HQS = _Loop("ct_hqs", 2, False, _aux_ct_hqs, 2, lambda S: 3, 5,
+                lambda n_view, opnorm, det_count, *_: 4 + 2 * int(n_view) + 4 * int(det_count))
+
+
+def ct_hqs(ctx, variables, y0, n_view, opnorm, det_count, source_distance, det_distance, det_spacing, sigma_d, mu, iter_num=None):
+    """pnpx_ct_hqs: HQSSolver_CT.forward, state [B,2,R,R]; det_count 0 = the parallel pair (the distances are not read then)."""
+    return _solver_forward(_CT_HQS, ctx, variables, (y0, n_view, opnorm, det_count, source_distance, det_distance, det_spacing),
+                           (sigma_d, mu), iter_num, False)
+
+
+def ct_hqs_train(ctx, variables, y0, n_view, opnorm, det_count, source_distance, det_distance, det_spacing, sigma_d, mu,
+                 iter_num=None):
+    """pnpx_ct_hqs_train: HQSSolver_CT.forward for autograd -> (next state [B,2,R,R], saved [3*T*B*R*R], ticket)."""
+    return _solver_forward(_CT_HQS, ctx, variables, (y0, n_view, opnorm, det_count, source_distance, det_distance, det_spacing),
+                           (sigma_d, mu), iter_num, True)
+
+
+def ct_hqs_backward(ctx, n_view, opnorm, det_count, source_distance, det_distance, det_spacing, sigma_d, mu, saved, grad_out,
+                    iter_num=None, ticket=0):
+    """pnpx_ct_hqs_backward -> (grad variables [B,2,R,R], grad sigma_d, grad mu, each [B,T])."""
+    return _solver_backward(_CT_HQS, ctx, (n_view, opnorm, det_count, source_distance, det_distance, det_spacing), (sigma_d, mu),
+                            saved, grad_out, iter_num, ticket)
+
+
 # ------------------------------------------------------------------------------------- episode orchestration (env.hip)
 def _dense(t, name):
     if not isinstance(t, torch.Tensor) or t.device.type != "cuda":

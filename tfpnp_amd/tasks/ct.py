@@ -4,7 +4,7 @@ import torch
 from .. import autograd as A
 from .. import torch_ops as T
 from ..env.base import PnPEnv
-from ..pnp.solver.base import IADMMSolver, PGSolver
+from ..pnp.solver.base import HQSSolver, IADMMSolver, PGSolver
 from ..utils.transforms import RadonGenerator
 
 
@@ -53,7 +53,31 @@ class PGSolver_CT(CTMixin, PGSolver):
                           -1 if iter_num is None else iter_num, self._ctx(variables).cid)[0]
         return T.call("ct_pg", variables, y0, n_view, float(radon.opnorm), sigma_d, tau, -1 if iter_num is None else iter_num, self._ctx(variables).cid)
 
-_solver_map = {'iadmm': IADMMSolver_CT, 'pg': PGSolver_CT}
+
+class HQSSolver_CT(CTMixin, HQSSolver):
+    """HQS for CT: state cat(x, z) = (x0, x0), hyper-parameters (sigma_d, mu) -- ResNetActor_HQS drives it.  Per iteration
+    x = D(z, sigma_d_i), then z <- z - (A^T(A z - y0) / |A|^2 + mu_i (z - x)) / (1 + mu_i): the inexact data step of
+    tasks/ct/solver.py:46-49 without the dual.  geometry: None = the parallel pair, or a utils.transforms.FanBeam."""
+
+    def __init__(self, denoiser, geometry=None):
+        super().__init__(denoiser)
+        self.radon_generator = RadonGenerator()
+        self.geometry = geometry
+
+    def forward(self, inputs, parameters, iter_num=None):
+        variables, (y0, view) = inputs
+        sigma_d, mu = parameters
+        n_view = int(y0.shape[2])                        # see IADMMSolver_CT.forward
+        radon = self.radon_generator(variables.shape[-1], n_view, device=variables.device, geometry=self.geometry)
+        g = getattr(radon, "geometry", None)
+        geom = (g.det_count, g.source_distance, g.det_distance, g.det_spacing) if g is not None else (0, 0.0, 0.0, 0.0)
+        name = "ct_hqs_train" if A.needs_grad(variables, sigma_d, mu) else "ct_hqs"   # training: native forward + fused native VJP
+        out = T.call(name, variables, y0, n_view, float(radon.opnorm), *geom, sigma_d, mu, -1 if iter_num is None else iter_num,
+                     self._ctx(variables).cid)
+        return out[0] if name == "ct_hqs_train" else out
+
+
+_solver_map = {'iadmm': IADMMSolver_CT, 'pg': PGSolver_CT, 'hqs': HQSSolver_CT}
 
 
 def create_solver_ct(opt, denoiser):

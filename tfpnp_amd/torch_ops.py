@@ -311,6 +311,38 @@ radon_backprojection.register_autograd(
     setup_context=lambda ctx, inputs, output: setattr(ctx, "V", inputs[0].shape[2]))
 
 
+@_lib_def("pnpx::fan_forward", mutates_args=(), device_types="cuda")
+def fan_forward(img: Tensor, n_view: int, det_count: int, source_distance: float, det_distance: float, det_spacing: float) -> Tensor:
+    """Fan-beam projector (flat detector, full circle; include/pnpx.h): [B,1,R,R] -> [B,1,n_view,det_count]."""
+    return ops.fan_forward(img, n_view, det_count, source_distance, det_distance, det_spacing)
+
+
+@fan_forward.register_fake
+def _(img, n_view, det_count, source_distance, det_distance, det_spacing):
+    return torch.empty((img.shape[0], 1, n_view, det_count), dtype=img.dtype, device=img.device)
+
+
+@_lib_def("pnpx::fan_backprojection", mutates_args=(), device_types="cuda")
+def fan_backprojection(sino: Tensor, R: int, source_distance: float, det_distance: float, det_spacing: float) -> Tensor:
+    """The weighted pixel-driven fan backprojection: [B,1,n_view,det_count] -> [B,1,R,R]."""
+    return ops.fan_backprojection(sino, R, source_distance, det_distance, det_spacing)
+
+
+@fan_backprojection.register_fake
+def _(sino, R, source_distance, det_distance, det_spacing):
+    return torch.empty((sino.shape[0], 1, R, R), dtype=sino.dtype, device=sino.device)
+
+
+# each is the other's VJP, as for the parallel pair
+fan_forward.register_autograd(
+    lambda ctx, g: (torch.ops.pnpx.fan_backprojection(g.contiguous(), ctx.R, *ctx.geom), None, None, None, None, None),
+    setup_context=lambda ctx, inputs, output: (setattr(ctx, "R", inputs[0].shape[-1]), setattr(ctx, "geom", tuple(inputs[3:]))))
+fan_backprojection.register_autograd(
+    lambda ctx, g: (torch.ops.pnpx.fan_forward(g.contiguous(), ctx.V, ctx.det, *ctx.geom), None, None, None, None),
+    setup_context=lambda ctx, inputs, output: (setattr(ctx, "V", inputs[0].shape[2]), setattr(ctx, "det", inputs[0].shape[3]),
+                                               setattr(ctx, "geom", tuple(inputs[2:]))))
+
+
 # ------------------------------------------------------------------------------------------------- solver loops
 # ------------------------------------------------------------------------------------------------- solver training ops
 def _solver_train_ops(name, aux, hypers, train_fn, backward_fn, saved_per_pixel, bwd_takes_aux=True):
@@ -415,7 +447,10 @@ ct_iadmm_train, ct_iadmm_backward = _solver_train_ops(
 ct_pg_train, ct_pg_backward = _solver_train_ops(
     "ct_pg", [("y0", "Tensor"), ("n_view", "int"), ("opnorm", "float")], ("sigma_d", "tau"), ops.ct_pg_train, ops.ct_pg_backward, 2,
     bwd_takes_aux=False)
-
+_CT_GEOM_AUX = [("y0", "Tensor"), ("n_view", "int"), ("opnorm", "float"), ("det_count", "int"), ("source_distance", "float"),
+                ("det_distance", "float"), ("det_spacing", "float")]         # det_count 0 = parallel beam
+ct_hqs_train, ct_hqs_backward = _solver_train_ops(
+    "ct_hqs", _CT_GEOM_AUX, ("sigma_d", "mu"), ops.ct_hqs_train, ops.ct_hqs_backward, 3, bwd_takes_aux=False)
 
 
 def _same(variables, *a):
@@ -524,6 +559,17 @@ def ct_pg(variables: Tensor, y0: Tensor, n_view: int, opnorm: float, sigma_d: Te
 
 
 ct_pg.register_fake(_same)
+
+
+@_lib_def("pnpx::ct_hqs", mutates_args=(), device_types="cuda")
+def ct_hqs(variables: Tensor, y0: Tensor, n_view: int, opnorm: float, det_count: int, source_distance: float, det_distance: float,
+           det_spacing: float, sigma_d: Tensor, mu: Tensor, iter_num: int, ctx: int) -> Tensor:
+    """HQSSolver_CT.forward: state cat(x, z); det_count 0 = parallel beam, else the fan geometry of include/pnpx.h."""
+    return ops.ct_hqs(_ctx(ctx, variables), variables, y0, n_view, opnorm, det_count, source_distance, det_distance, det_spacing,
+                      sigma_d, mu, _it(iter_num))
+
+
+ct_hqs.register_fake(_same)
 
 # ------------------------------------------------------------------------------------------------- value network
 @_lib_def("pnpx::critic_value", mutates_args=(), device_types="cuda")
@@ -688,5 +734,6 @@ ALL_OPS = ("unet_denoise", "unet_denoise_preclamp", "unet_denoise_backward", "un
            "cdp_backward", "spi_inverse", "psnr", "radon_forward", "radon_backprojection", "csmri_admm", "csmri_admm_train",
            "csmri_admm_backward", "csmri_hqs", "csmri_amp",
            "csmri_pg", "csmri_apg", "csmri_redadmm", "pr_iadmm", "spi_admm", "ct_iadmm", "ct_pg", "pr_pg",
+           "fan_forward", "fan_backprojection", "ct_hqs", "ct_hqs_train", "ct_hqs_backward",
            "critic_value", "critic_backward", "critic_param_grad", "critic_value_loss_grad", "policy_ob_pack_diff", "policy_ob_unpack",
            "mddpg_policy_loss")

@@ -3,9 +3,12 @@
 Layout helpers (real2complex ...) are plain tensor views/stacks -- pure data movement, exactly as in the
 reference.  Everything that computes (fft2, ifft2, cdp_*, spi_inverse, Radon) is a libpnpx.so call.
 """
+import collections
+
 import numpy as np
 import torch
 
+from .. import ops
 from .. import torch_ops as T
 
 
@@ -140,14 +143,68 @@ def ramp_filter(size):
     return (2 * np.real(np.fft.fft(f))).astype(np.float32)
 
 
+FanGeometry = collections.namedtuple("FanGeometry", "n_view det_count source_distance det_distance det_spacing")
+
+
+class FanBeam:
+    """A fan-beam geometry (flat detector, full circle; include/pnpx.h and DESIGN.md section 7), in pixel units.  What is left None
+    takes its default when the geometry meets a resolution: det_distance = source_distance, det_spacing = D / source_distance
+    (unit ray spacing at the isocentre, D = source_distance + det_distance) and det_count = the fan that just covers the sampled
+    circle (pnpx_fan_det_count).  The values travel as float32, as the native entries take them."""
+
+    def __init__(self, source_distance, det_distance=None, det_count=None, det_spacing=None):
+        self.source_distance, self.det_distance, self.det_count, self.det_spacing = source_distance, det_distance, det_count, det_spacing
+
+    def key(self):
+        return (self.source_distance, self.det_distance, self.det_count, self.det_spacing)
+
+    def resolve(self, resolution, view):
+        f32 = lambda v: float(np.float32(v))
+        dso = f32(self.source_distance)
+        dod = dso if self.det_distance is None else f32(self.det_distance)
+        du = f32((dso + dod) / dso) if self.det_spacing is None else f32(self.det_spacing)
+        det = ops.fan_det_count(resolution, dso, dod, du) if self.det_count is None else int(self.det_count)
+        return FanGeometry(int(view), det, dso, dod, du)
+
+
+class FanBeam_norm(Radon_norm):
+    """Radon_norm's surface on a fan-beam pair: forward, the weighted backprojection, their normalised forms and the same seeded
+    ten-step power method for opnorm.  Fan-beam filtered backprojection is not provided."""
+
+    def __init__(self, resolution, view, geometry, opnorm=None, device=None, seed=0):
+        self.geometry = geometry.resolve(resolution, view)
+        super().__init__(resolution, view, opnorm=opnorm, device=device, seed=seed)
+
+    def forward(self, x):
+        g = self.geometry
+        return T.call("fan_forward", x, g.n_view, g.det_count, g.source_distance, g.det_distance, g.det_spacing)
+
+    def backprojection(self, sinogram):
+        g = self.geometry
+        return T.call("fan_backprojection", sinogram, int(self.resolution), g.source_distance, g.det_distance, g.det_spacing)
+
+    backward = backprojection
+
+    def filter_sinogram(self, sinogram, filter_name='ramp'):
+        raise NotImplementedError("fan-beam filtered backprojection is not provided")
+
+    def filter_backprojection(self, sinogram):
+        raise NotImplementedError("fan-beam filtered backprojection is not provided")
+
+
 class RadonGenerator:
-    """transforms.py:494-508: caches the operator norm per (resolution, view)."""
+    """transforms.py:494-508: caches the operator norm per (resolution, view), and per geometry when one is given (a FanBeam;
+    None = the reference's parallel beam)."""
 
     def __init__(self):
         self.opnorms = {}
 
-    def __call__(self, resolution, view, device=None):
-        key = (resolution, view)
-        radon = Radon_norm(resolution, view, opnorm=self.opnorms.get(key), device=device)
+    def __call__(self, resolution, view, device=None, geometry=None):
+        if geometry is None:
+            key = (resolution, view)
+            radon = Radon_norm(resolution, view, opnorm=self.opnorms.get(key), device=device)
+        else:
+            key = (resolution, view, geometry.key())
+            radon = FanBeam_norm(resolution, view, geometry, opnorm=self.opnorms.get(key), device=device)
         self.opnorms[key] = radon.opnorm
         return radon
