@@ -657,6 +657,30 @@ int pnpx_spi_admm_backward(pnpx_ctx* ctx, const float* x0, const float* Kmap, co
                            int param_stride, const float* saved, const float* grad_vars_out, float* grad_vars_in,
                            float* grad_sigma_d, float* grad_mu, float* work, int B, int H, int W, int T,
                            unsigned long long ticket, void* stream);
+/* PGSolver_SPI: proximal gradient on the SPI data term.  The reference has no counterpart (tasks/spi/solver.py stops at ADMM);
+ * the step is this package's own, on the likelihood behind spi_inverse (transforms.py:404-439, func) divided by K^2:
+ *   f(x) = (1 - x0) x - x0 log(1 - e^-x);   K = 10 Kmap[b,0,0,0];  x_lo = 0.5 / K^2;  x_c = max(x, x_lo);  q = -expm1(-x_c);
+ *   g = 1 - x0 / q  (= f');  c = x0 (1 - q) / q^2  (= f'');  h = g / max(c, 1);  z = clamp(x - tau h, 0, 1)
+ * (the gradient step where f'' < 1, the damped Newton step where f'' >= 1).
+ * pnpx_spi_pg_step is that one step alone, the counterpart of pnpx_spi_inverse: x, x0 [B,1,H,W]; Kmap [B,1,H,W] (only
+ * [b,0,0,0] is read); tau [B] -> out = z [B,1,H,W]. */
+int pnpx_spi_pg_step(pnpx_ctx* ctx, const float* x, const float* x0, const float* Kmap, const float* tau, float* out, int B,
+                     int H, int W, void* stream);
+/* PGSolver_SPI.forward: per iteration i, x <- D(z(x, tau_i), sigma_d_i).  vars [B,1,H,W] real; x0, Kmap as above; sigma_d, tau
+ * [B,T] (row stride param_stride >= T).  T = 0 copies the state. */
+int pnpx_spi_pg(pnpx_ctx* ctx, const float* vars_in, float* vars_out, const float* x0, const float* Kmap,
+                const float* sigma_d, const float* tau, int param_stride, int B, int H, int W, int T, void* stream);
+/* Training path of PGSolver_SPI.forward (same contract): `saved` = 2*T*B*H*W floats (x of every iteration, then the denoiser
+ * inputs); grads wrt (x, sigma_d, tau), each hyper-parameter gradient [T][B] as in pnpx_pr_pg_backward; work = 3*B*H*W floats.
+ * The VJP is that of the expression above with torch.clamp's rule (closed intervals pass); x0 and Kmap get no gradient; the tau
+ * term is summed per item in a fixed order (no atomics: two runs give equal bytes).  ticket as in pnpx_csmri_admm_train. */
+int pnpx_spi_pg_train(pnpx_ctx* ctx, const float* vars_in, float* vars_out, const float* x0, const float* Kmap,
+                      const float* sigma_d, const float* tau, int param_stride, int B, int H, int W, int T, float* saved,
+                      unsigned long long* ticket, void* stream);
+int pnpx_spi_pg_backward(pnpx_ctx* ctx, const float* x0, const float* Kmap, const float* sigma_d, const float* tau,
+                         int param_stride, const float* saved, const float* grad_vars_out, float* grad_vars_in,
+                         float* grad_sigma_d, float* grad_tau, float* work, int B, int H, int W, int T,
+                         unsigned long long ticket, void* stream);
 
 /* ---- CT: Radon pair standing in for torch_radon (tfpnp/utils/transforms.py:465-508) -------------- */
 /* Parallel beam, angles = linspace(0, 179/180*pi, n_view), det = ceil(sqrt(2)*R), unit spacing

@@ -172,6 +172,12 @@ _SIGNATURES = {
     "pnpx_spi_admm_backward": (C.c_int, [c_void_p, _P, _P, _P, _P, C.c_int, _P, _P, _P, _P, _P, _P] + [C.c_int] * 4 +
                                [C.c_ulonglong, c_void_p]),
     "pnpx_spi_admm": (C.c_int, [c_void_p, _P, _P, _P, _P, _P, _P] + [C.c_int] * 5 + [c_void_p]),
+    "pnpx_spi_pg_step": (C.c_int, [c_void_p, _P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, c_void_p]),
+    "pnpx_spi_pg_train": (C.c_int, [c_void_p, _P, _P, _P, _P, _P, _P] + [C.c_int] * 5 +
+                          [_P, C.POINTER(C.c_ulonglong), c_void_p]),
+    "pnpx_spi_pg_backward": (C.c_int, [c_void_p, _P, _P, _P, _P, C.c_int, _P, _P, _P, _P, _P, _P] + [C.c_int] * 4 +
+                             [C.c_ulonglong, c_void_p]),
+    "pnpx_spi_pg": (C.c_int, [c_void_p, _P, _P, _P, _P, _P, _P] + [C.c_int] * 5 + [c_void_p]),
     "pnpx_radon_det_count": (C.c_int, [C.c_int]),
     "pnpx_radon_forward": (C.c_int, [c_void_p, _P, _P, C.c_int, C.c_int, C.c_int, c_void_p]),
     "pnpx_radon_backprojection": (C.c_int, [c_void_p, _P, _P, C.c_int, C.c_int, C.c_int, c_void_p]),

@@ -388,6 +388,57 @@ __global__ void copy_real_slot_kernel(const float* __restrict__ src, float* __re
   dst[b * istride + r] = src[i];
 }
 
+// ---- PGSolver_SPI (pnpx_spi_pg_step, pnpx_spi_pg / _train / _backward): x' = D(clamp(x - tau h(x), 0, 1)).  The reference has no
+// counterpart (tasks/spi/solver.py stops at ADMM); the step is this package's own, on the likelihood behind spi_inverse divided
+// by K^2:  f(x) = (1 - x0) x - x0 log(1 - e^-x),  f' = 1 - x0 / q,  f'' = x0 (1 - q) / q^2,  q = 1 - e^-x.  f'' is unbounded as
+// x -> 0, so the step is scaled by the local curvature: h = f' / max(f'', 1) -- the gradient step where f'' < 1, the damped
+// Newton step where f'' >= 1 -- and x enters f through max(x, x_lo), x_lo = 0.5 / K^2 (half the quantum of x0), so that a pixel
+// the denoiser returned as 0 can leave 0.  One pixel of the step, every operation rounded on its own, in the order of
+// tests/spi_pg_ref.py; shared by the forward and the adjoint kernel (which re-derives pass / live / h / h' from the saved x).
+struct SpiPgPx {
+  float q, c, h, pre;   // q = 1 - e^-x_c, c = f''(x_c), h, pre = x - tau h (before the clamp)
+  bool live;            // x >= x_lo: x_c follows x
+};
+__device__ __forceinline__ SpiPgPx spi_pg_step_px(float x, float x0, float K, float tau) {
+  const float xlo = divr(0.5f, mulr(K, K));
+  const float xc = fmaxf(x, xlo);
+  const float q = -expm1f(-xc);
+  const float g = subr(1.f, divr(x0, q));
+  const float c = divr(mulr(x0, subr(1.f, q)), mulr(q, q));
+  const float h = divr(g, fmaxf(c, 1.f));
+  return SpiPgPx{q, c, h, subr(x, mulr(tau, h)), x >= xlo};
+}
+// d = clamp(x - tau h, 0, 1), the denoiser's input.  x comes with its own item stride (the state on the first iteration, the
+// denoiser's contiguous output afterwards; no per-iteration copy); `xsave` (training forward, or NULL) keeps x.
+__global__ void spi_pg_step_kernel(const float* xin, size_t xstride, const float* __restrict__ x0, const float* __restrict__ Kmap,
+                                   float* __restrict__ d, const float* __restrict__ tau, int stride, int HW, int B,
+                                   float* __restrict__ xsave) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= (size_t)HW * B) return;
+  const size_t b = i / HW, r = i - b * HW;
+  const float K = mulr(Kmap[b * HW], 10.f);
+  const float x = xin[b * xstride + r];
+  const SpiPgPx p = spi_pg_step_px(x, x0[i], K, tau[b * stride]);
+  d[i] = fminf(fmaxf(p.pre, 0.f), 1.f);
+  if (xsave) xsave[i] = x;
+}
+// Backward of one PG iteration after the denoiser's VJP gd, at the saved x (torch.clamp's rule: closed intervals pass):
+//   pass = 0 <= x - tau h <= 1;  h' = c where c < 1 (h = f'),  (2q - q^2 - x0) / (x0 (1 - q)) where c >= 1 (h = f' / f'');
+//   gx = pass ? gd (1 - tau h' live) : 0;  d/d tau = pass ? -gd h : 0 per pixel (pr_item_sum_kernel sums it per item)
+__global__ void spi_pg_adjoint_kernel(const float* __restrict__ gd, const float* __restrict__ xs, const float* __restrict__ x0,
+                                      const float* __restrict__ Kmap, const float* __restrict__ tau, int stride, int HW, int B,
+                                      float* __restrict__ gx, float* __restrict__ c_tau) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= (size_t)HW * B) return;
+  const size_t b = i / HW;
+  const float K = mulr(Kmap[b * HW], 10.f), t = tau[b * stride], a = x0[i], e = gd[i];
+  const SpiPgPx p = spi_pg_step_px(xs[i], a, K, t);
+  const bool pass = p.pre >= 0.f && p.pre <= 1.f;
+  const float hp = !p.live ? 0.f : (p.c < 1.f ? p.c : (2.f * p.q - p.q * p.q - a) / (a * (1.f - p.q)));
+  gx[i] = pass ? e * (1.f - t * hp) : 0.f;
+  c_tau[i] = pass ? -(e * p.h) : 0.f;
+}
+
 // ---- training paths of ADMMSolver_SPI / IADMMSolver_CT / PGSolver_CT (pnpx_{spi_admm,ct_iadmm,ct_pg}_train / _backward)
 // spi_step_kernel that also keeps zt = x + u (the argument of spi_inverse)
 __global__ void spi_step_save_kernel(const float* xin, size_t xstride, const float* uin, size_t istride, const float* __restrict__ x0,
@@ -1521,6 +1572,86 @@ int pnpx_spi_admm_backward(pnpx_ctx* ctx, const float* x0, const float* Kmap, co
                          mu + i, param_stride, HW, B, c_mu);
       PNPX_LAUNCH_CHECK();
       hipLaunchKernelGGL(pr_item_sum_kernel, dim3(B), dim3(256), 0, s, c_mu, grad_mu + (size_t)i * B, HW);
+      PNPX_LAUNCH_CHECK();
+    }
+    return PNPX_OK;
+  });
+}
+
+// One gradient step of PGSolver_SPI alone (no denoiser): out = clamp(x - tau h(x), 0, 1), the counterpart of pnpx_spi_inverse
+int pnpx_spi_pg_step(pnpx_ctx* ctx, const float* x, const float* x0, const float* Kmap, const float* tau, float* out, int B,
+                     int H, int W, void* stream) {
+  LOCK_CTX(ctx);
+  REQUIRE(x && x0 && Kmap && tau && out && B > 0 && H > 0 && W > 0, "pnpx_spi_pg_step: bad argument");
+  const int HW = H * W;
+  hipLaunchKernelGGL(spi_pg_step_kernel, g1((size_t)B * HW), dim3(256), 0, static_cast<hipStream_t>(stream), x, (size_t)HW, x0,
+                     Kmap, out, tau, 1, HW, B, static_cast<float*>(nullptr));
+  PNPX_LAUNCH_CHECK();
+  return PNPX_OK;
+}
+
+// PGSolver_SPI.forward; `saved` != NULL (training path): per iteration x [T][n] and the denoiser input [T][n]  (n = B*H*W)
+static int spi_pg_forward(pnpx_ctx* ctx, const float* vars_in, float* vars_out, const float* x0, const float* Kmap,
+                          const float* sigma_d, const float* tau, int param_stride, int B, int H, int W, int T, float* saved,
+                          unsigned long long* ticket_out, hipStream_t s) {
+  REQUIRE(vars_in && vars_out && x0 && Kmap && sigma_d && tau && B > 0 && H > 0 && W > 0 && T >= 0 && param_stride >= T,
+          "pnpx_spi_pg: bad argument");
+  const Prox px = prox_begin(ctx, sigma_d, param_stride, B, H, W, saved, ticket_out, s);
+  const auto [HW, is, n] = state_dims(B, H, W, 1);
+  if (T == 0) return copy_state(vars_out, vars_in, sizeof(float) * is * B, s);
+  void* p;
+  PNPX_TRY(ctx_scratch(ctx, 2 * n * sizeof(float) + 4096, &p));
+  Carver cv{static_cast<char*>(p)};
+  float* dscr = cv.take<float>(n);
+  float* xr = cv.take<float>(n);
+  for (int i = 0; i < T; ++i) {
+    // x of iteration i: the state on the first pass, the previous denoiser output later (both contiguous: one variable)
+    const float* xin = (i == 0) ? vars_in : xr;
+    float* d = saved ? saved + ((size_t)T + i) * n : dscr;   // the training path denoises straight out of `saved`
+    hipLaunchKernelGGL(spi_pg_step_kernel, g1(n), dim3(256), 0, s, xin, (size_t)HW, x0, Kmap, d, tau + i, param_stride, HW, B,
+                       saved ? saved + (size_t)i * n : static_cast<float*>(nullptr));
+    PNPX_LAUNCH_CHECK();
+    // the last denoiser output is the state: it is written where it belongs, the call copies nothing
+    PNPX_TRY(prox_step(px, i, d, i == T - 1 ? vars_out : xr));
+  }
+  return PNPX_OK;
+}
+
+int pnpx_spi_pg(pnpx_ctx* ctx, const float* vars_in, float* vars_out, const float* x0, const float* Kmap, const float* sigma_d,
+                const float* tau, int param_stride, int B, int H, int W, int T, void* stream) {
+  return solver_entry(ctx, stream, [&](hipStream_t s) {
+    return spi_pg_forward(ctx, vars_in, vars_out, x0, Kmap, sigma_d, tau, param_stride, B, H, W, T, nullptr, nullptr, s);
+  });
+}
+
+int pnpx_spi_pg_train(pnpx_ctx* ctx, const float* vars_in, float* vars_out, const float* x0, const float* Kmap,
+                      const float* sigma_d, const float* tau, int param_stride, int B, int H, int W, int T, float* saved,
+                      unsigned long long* ticket, void* stream) {
+  return solver_train_entry(ctx, "pnpx_spi_pg_train", saved || T == 0, ticket, stream, [&](hipStream_t s) {
+    return spi_pg_forward(ctx, vars_in, vars_out, x0, Kmap, sigma_d, tau, param_stride, B, H, W, T, saved, ticket, s);
+  });
+}
+
+// VJP of the T-iteration SPI PG map wrt (x, sigma_d, tau), iterations walked in reverse: gd = D^T gx' at the saved denoiser
+// input, then spi_pg_adjoint_kernel at the saved x and the per-item sum of its tau term.  work = 3*B*H*W floats.
+int pnpx_spi_pg_backward(pnpx_ctx* ctx, const float* x0, const float* Kmap, const float* sigma_d, const float* tau,
+                         int param_stride, const float* saved, const float* grad_vars_out, float* grad_vars_in,
+                         float* grad_sigma_d, float* grad_tau, float* work, int B, int H, int W, int T,
+                         unsigned long long ticket, void* stream) {
+  return solver_entry(ctx, stream, [&](hipStream_t s) -> int {
+    REQUIRE(x0 && Kmap && sigma_d && tau && grad_vars_out && grad_vars_in && B > 0 && H > 0 && W > 0 && T >= 0 &&
+                param_stride >= T && (T == 0 || (saved && grad_sigma_d && grad_tau && work)),
+            "pnpx_spi_pg_backward: bad argument");
+    const auto [HW, is, n] = state_dims(B, H, W, 1);
+    if (T == 0) return copy_state(grad_vars_in, grad_vars_out, sizeof(float) * is * B, s);
+    float *gx = work, *gd = work + n, *c_tau = work + 2 * n;
+    for (int i = T - 1; i >= 0; --i) {
+      PNPX_TRY(prox_vjp(ctx, i, saved + (size_t)T * n, sigma_d, param_stride, i == T - 1 ? grad_vars_out : gx, gd, grad_sigma_d,
+                        B, H, W, s, ticket));
+      hipLaunchKernelGGL(spi_pg_adjoint_kernel, g1(n), dim3(256), 0, s, gd, saved + (size_t)i * n, x0, Kmap, tau + i,
+                         param_stride, HW, B, i == 0 ? grad_vars_in : gx, c_tau);
+      PNPX_LAUNCH_CHECK();
+      hipLaunchKernelGGL(pr_item_sum_kernel, dim3(B), dim3(256), 0, s, c_tau, grad_tau + (size_t)i * B, HW);
       PNPX_LAUNCH_CHECK();
     }
     return PNPX_OK;

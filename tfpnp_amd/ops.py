@@ -720,6 +720,30 @@ def spi_inverse(ztilde, K1, K, mu, ctx=None):
     return out
 
 
+def spi_pg_step(x, x0, Kmap, tau, ctx=None):
+    """pnpx_spi_pg_step: one gradient step of PGSolver_SPI without the denoiser, clamp(x - tau h(x), 0, 1) (include/pnpx.h; the
+    reference has no counterpart).  x, x0 [B,1,H,W]; Kmap = K / 10 as the solver state carries it, [B,1,H,W] or one value per
+    item; tau one value per item."""
+    x = _f32(x, "x")
+    if x.dim() != 4 or x.shape[1] != 1:
+        raise PnpxError(f"spi_pg_step: x must be [B,1,H,W], got {tuple(x.shape)}")
+    B, _, H, W = x.shape
+    x0 = _f32(x0, "x0")
+    Kmap, tau = _f32(Kmap, "K"), _f32(tau, "tau")
+    if tuple(x0.shape) != tuple(x.shape) or Kmap.numel() not in (B, x.numel()) or tau.numel() != B:
+        raise PnpxError("spi_pg_step: x0 must be [B,1,H,W] like x, K [B,1,H,W] or one value per item, tau one value per item")
+    if Kmap.numel() != x.numel():                       # only [b,0,0,0] is read, at item stride H*W
+        Kmap = Kmap.reshape(B, 1).expand(B, H * W).contiguous()
+    tau = tau.reshape(B).contiguous()
+    out = torch.empty_like(x)
+    if B == 0:
+        return out
+    ctx = ctx or default_context(x.device)
+    with torch.cuda.device(x.device):
+        check(_lib.lib().pnpx_spi_pg_step(ctx.handle, _p(x), _p(x0), _p(Kmap), _p(tau), _p(out), B, H, W, _stream(x)))
+    return out
+
+
 def psnr(output, gt, ctx=None):
     output = _f32(output, "output")
     gt = _f32(gt, "gt")
@@ -880,7 +904,7 @@ def _aux_spi(L, v, args, backward):
     B, H, W = v.shape[0], v.shape[2], v.shape[3]
     x0, Kmap = _f32(args[0], "x0"), _f32(args[1], "K")
     if not backward and (x0.numel() != B * H * W or Kmap.numel() != B * H * W):
-        raise PnpxError("spi_admm: x0 and K must be [B,1,H,W]")
+        raise PnpxError(f"{L.name}: x0 and K must be [B,1,H,W]")
     return [x0, Kmap], (B, H, W), H * W, 1
 
 
@@ -892,6 +916,7 @@ _CSMRI_RED = _Loop("csmri_redadmm", 3, True, _aux_csmri, 3, lambda S: 7, 4)
 _PR_IADMM = _Loop("pr_iadmm", 3, True, _aux_pr, 3, lambda S: 2 * S + 5, 4, fwd_checks_iter=False)
 _PR_PG = _Loop("pr_pg", 1, True, _aux_pr, 2, lambda S: 2 * S + 2, 3)
 _SPI_ADMM = _Loop("spi_admm", 3, False, _aux_spi, 2, lambda S: 2, 3, fwd_checks_iter=False)
+_SPI_PG = _Loop("spi_pg", 1, False, _aux_spi, 2, lambda S: 2, 3)
 
 
 def csmri_admm(ctx, variables, y0, mask, sigma_d, mu, iter_num=None):
@@ -1030,6 +1055,21 @@ def spi_admm_train(ctx, variables, x0, Kmap, sigma_d, mu, iter_num=None):
 def spi_admm_backward(ctx, x0, Kmap, sigma_d, mu, saved, grad_out, iter_num=None, ticket=0):
     """pnpx_spi_admm_backward -> (grad variables [B,3,H,W], grad sigma_d, grad mu, each [B,T])."""
     return _solver_backward(_SPI_ADMM, ctx, (x0, Kmap), (sigma_d, mu), saved, grad_out, iter_num, ticket)
+
+
+def spi_pg(ctx, variables, x0, Kmap, sigma_d, tau, iter_num=None):
+    """pnpx_spi_pg: PGSolver_SPI.forward, x [B,1,H,W] -> next x (include/pnpx.h; the reference has no counterpart)."""
+    return _solver_forward(_SPI_PG, ctx, variables, (x0, Kmap), (sigma_d, tau), iter_num, False)
+
+
+def spi_pg_train(ctx, variables, x0, Kmap, sigma_d, tau, iter_num=None):
+    """pnpx_spi_pg_train: PGSolver_SPI.forward for autograd -> (next x [B,1,H,W], saved [2*T*B*H*W], ticket)."""
+    return _solver_forward(_SPI_PG, ctx, variables, (x0, Kmap), (sigma_d, tau), iter_num, True)
+
+
+def spi_pg_backward(ctx, x0, Kmap, sigma_d, tau, saved, grad_out, iter_num=None, ticket=0):
+    """pnpx_spi_pg_backward -> (grad x [B,1,H,W], grad sigma_d, grad tau, each [B,T])."""
+    return _solver_backward(_SPI_PG, ctx, (x0, Kmap), (sigma_d, tau), saved, grad_out, iter_num, ticket)
 
 
 # ------------------------------------------------------------------------------------------------- CT

@@ -251,6 +251,17 @@ def _(ztilde, K1, K, mu):
     return torch.empty_like(ztilde, memory_format=torch.contiguous_format)
 
 
+@_lib_def("pnpx::spi_pg_step", mutates_args=(), device_types="cuda")
+def spi_pg_step(x: Tensor, x0: Tensor, Kmap: Tensor, tau: Tensor) -> Tensor:
+    """One gradient step of PGSolver_SPI without the denoiser (include/pnpx.h; the reference has no counterpart).  Forward only."""
+    return ops.spi_pg_step(x, x0, Kmap, tau)
+
+
+@spi_pg_step.register_fake
+def _(x, x0, Kmap, tau):
+    return torch.empty_like(x, memory_format=torch.contiguous_format)
+
+
 @_lib_def("pnpx::psnr", mutates_args=(), device_types="cuda")
 def psnr(output: Tensor, gt: Tensor) -> Tensor:
     """torch_psnr (tfpnp/env/base.py:237-242): [B,...] x 2 -> [B,1]."""
@@ -441,6 +452,8 @@ pr_pg_train, pr_pg_backward = _solver_train_ops(
     lambda aux: 2 * aux[1].shape[1] + 2)        # S k-space images, the denoiser input and Re g per iteration
 spi_admm_train, spi_admm_backward = _solver_train_ops(
     "spi_admm", [("x0", "Tensor"), ("Kmap", "Tensor")], ("sigma_d", "mu"), ops.spi_admm_train, ops.spi_admm_backward, 2)
+spi_pg_train, spi_pg_backward = _solver_train_ops(
+    "spi_pg", [("x0", "Tensor"), ("Kmap", "Tensor")], ("sigma_d", "tau"), ops.spi_pg_train, ops.spi_pg_backward, 2)
 ct_iadmm_train, ct_iadmm_backward = _solver_train_ops(
     "ct_iadmm", [("y0", "Tensor"), ("n_view", "int"), ("opnorm", "float")], ("sigma_d", "mu", "tau"), ops.ct_iadmm_train,
     ops.ct_iadmm_backward, 3, bwd_takes_aux=False)
@@ -539,6 +552,15 @@ def spi_admm(variables: Tensor, x0: Tensor, Kmap: Tensor, sigma_d: Tensor, mu: T
 
 
 spi_admm.register_fake(_same)
+
+
+@_lib_def("pnpx::spi_pg", mutates_args=(), device_types="cuda")
+def spi_pg(variables: Tensor, x0: Tensor, Kmap: Tensor, sigma_d: Tensor, tau: Tensor, iter_num: int, ctx: int) -> Tensor:
+    """PGSolver_SPI.forward: proximal gradient on the SPI data term (include/pnpx.h; the reference has no counterpart)."""
+    return ops.spi_pg(_ctx(ctx, variables), variables, x0, Kmap, sigma_d, tau, _it(iter_num))
+
+
+spi_pg.register_fake(_same)
 
 
 @_lib_def("pnpx::ct_iadmm", mutates_args=(), device_types="cuda")
@@ -735,5 +757,6 @@ ALL_OPS = ("unet_denoise", "unet_denoise_preclamp", "unet_denoise_backward", "un
            "csmri_admm_backward", "csmri_hqs", "csmri_amp",
            "csmri_pg", "csmri_apg", "csmri_redadmm", "pr_iadmm", "spi_admm", "ct_iadmm", "ct_pg", "pr_pg",
            "fan_forward", "fan_backprojection", "ct_hqs", "ct_hqs_train", "ct_hqs_backward",
+           "spi_pg_step", "spi_pg", "spi_pg_train", "spi_pg_backward",
            "critic_value", "critic_backward", "critic_param_grad", "critic_value_loss_grad", "policy_ob_pack_diff", "policy_ob_unpack",
            "mddpg_policy_loss")

@@ -75,6 +75,12 @@ def spi_inverse(ztilde, K1, K, mu):
     return T.call("spi_inverse", ztilde, K1, K, mu)
 
 
+def spi_pg_step(x, x0, K, tau):
+    """One gradient step of PGSolver_SPI on the likelihood behind spi_inverse, without the denoiser (no counterpart in the
+    reference; include/pnpx.h pnpx_spi_pg_step).  x, x0 [B,1,H,W]; K = the K / 10 map of the solver state; tau per item."""
+    return T.call("spi_pg_step", x, x0, K, tau)
+
+
 # ------------------------------------------------------------------------------------------------ CT
 class Radon_norm:
     """Stands in for transforms.py:465-484 (a torch_radon.Radon subclass): parallel beam,
