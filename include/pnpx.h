@@ -765,6 +765,49 @@ int pnpx_ct_hqs_backward(pnpx_ctx* ctx, const pnpx_radon_geom* geom, int n_view,
                          float* grad_sigma_d, float* grad_mu, float* work, int B, int R, int T, unsigned long long ticket,
                          void* stream);
 
+/* ---- CT, filtered backprojection of a fan-beam sinogram (Kak & Slaney section 3.4.2, equispaced flat detector, full circle)
+ *   fbp(y)(x, y) = sum over views v of (D_so / U)^2 * lerp(q_v, pos),   U and pos as in the fan backprojection above,
+ *   q_v[j] = S * sum over m, ascending, of (y_v[m] c[m]) h[j - m],   c[m] = cos gamma_m = D / sqrt(D^2 + u_m^2),
+ *   h[0] = 1/4, h[odd n] = -1 / (pi n)^2, h[even n != 0] = 0 (the band-limited ramp's spatial kernel; even lags are skipped),
+ *   S = pi / (n_view dp), dp = det_spacing * source_distance / D the ray spacing at the isocentre: the view step 2 pi / n_view, the
+ *   factor 1/2 of a full circle and dp h / dp^2 of the sampled ramp in one constant, computed in double and applied last.
+ * pnpx_radon_filter is the row filter alone: sino_in, sino_out [B,1,n_view,det].  geom NULL or of kind PNPX_GEOM_PARALLEL: the parallel
+ * beam's filter, c = 1 and S = pi / n_view (Radon_norm.filter_sinogram without its FFTs), det given by the caller; a fan geometry:
+ * its n_view and det_count must be the call's, and what depends on an image (the source's distance from the sampled span) is not
+ * checked.  A pre-weighted row is staged in LDS: det must be in [2, 8192] (PNPX_ERR_SHAPE beyond), and sino_out == sino_in is refused
+ * (PNPX_ERR_ARG).  pnpx_fan_backprojection_w is pnpx_fan_backprojection with the view weight chosen: PNPX_FAN_W_ADJOINT (the same
+ * bytes) or PNPX_FAN_W_FBP, w = (D_so / U)^2.  pnpx_fan_fbp runs the two, with the filtered sinogram in the context's scratch.  The
+ * refusals are those of the fan entries above. */
+enum { PNPX_FAN_W_ADJOINT = 0, PNPX_FAN_W_FBP = 1 };
+int pnpx_radon_filter(pnpx_ctx* ctx, const float* sino_in, float* sino_out, const pnpx_radon_geom* geom, int B, int n_view, int det,
+                      void* stream);
+int pnpx_fan_backprojection_w(pnpx_ctx* ctx, const float* sino, float* img, const pnpx_radon_geom* geom, int weight, int B, int R,
+                              void* stream);
+int pnpx_fan_fbp(pnpx_ctx* ctx, const float* sino, float* img, const pnpx_radon_geom* geom, int B, int R, void* stream);
+/* pnpx_ct_iadmm / pnpx_ct_pg and their training pairs on a chosen geometry, as pnpx_ct_hqs takes it: geom NULL or of kind
+ * PNPX_GEOM_PARALLEL is the entry without _geom (same bytes); a fan geometry (its n_view must equal n_view) runs the fan pair,
+ * y0 [B,1,n_view,det_count], opnorm of that pair.  The backward work buffers grow with a fan geometry, whose tables stand 16-byte
+ * aligned behind the image buffers: iADMM 6*B*R*R + 2*n_view + 4 + 4*det_count floats, PG 3*B*R*R + 1 + 2*n_view + 3 + 4*det_count. */
+int pnpx_ct_iadmm_geom(pnpx_ctx* ctx, const float* vars_in, float* vars_out, const float* y0, const pnpx_radon_geom* geom,
+                       int n_view, float opnorm, const float* sigma_d, const float* mu, const float* tau, int param_stride, int B,
+                       int R, int T, void* stream);
+int pnpx_ct_iadmm_geom_train(pnpx_ctx* ctx, const float* vars_in, float* vars_out, const float* y0, const pnpx_radon_geom* geom,
+                             int n_view, float opnorm, const float* sigma_d, const float* mu, const float* tau, int param_stride,
+                             int B, int R, int T, float* saved, unsigned long long* ticket, void* stream);
+int pnpx_ct_iadmm_geom_backward(pnpx_ctx* ctx, const pnpx_radon_geom* geom, int n_view, float opnorm, const float* sigma_d,
+                                const float* mu, const float* tau, int param_stride, const float* saved, const float* grad_vars_out,
+                                float* grad_vars_in, float* grad_sigma_d, float* grad_mu, float* grad_tau, float* work, int B, int R,
+                                int T, unsigned long long ticket, void* stream);
+int pnpx_ct_pg_geom(pnpx_ctx* ctx, const float* vars_in, float* vars_out, const float* y0, const pnpx_radon_geom* geom, int n_view,
+                    float opnorm, const float* sigma_d, const float* tau, int param_stride, int B, int R, int T, void* stream);
+int pnpx_ct_pg_geom_train(pnpx_ctx* ctx, const float* vars_in, float* vars_out, const float* y0, const pnpx_radon_geom* geom,
+                          int n_view, float opnorm, const float* sigma_d, const float* tau, int param_stride, int B, int R, int T,
+                          float* saved, unsigned long long* ticket, void* stream);
+int pnpx_ct_pg_geom_backward(pnpx_ctx* ctx, const pnpx_radon_geom* geom, int n_view, float opnorm, const float* sigma_d,
+                             const float* tau, int param_stride, const float* saved, const float* grad_vars_out,
+                             float* grad_vars_in, float* grad_sigma_d, float* grad_tau, float* work, int B, int R, int T,
+                             unsigned long long ticket, void* stream);
+
 /* Host-only helpers of the Winograd F(4x4,3x3) kernel (csrc/conv3x3_winof4.hip), for tests: the 1-D matrices the weight packer and the
  * kernel use (G 6x3, B^T 6x6, A^T 4x6, row-major doubles), and the packer itself (w [cout][cin][3][3], cout % 64 == 0, cin % 8 == 0 ->
  * dst 36 * cout * cin floats: [cout/64][cin/8][stage 3][row 2][column pair 3][cout block 4][channel group 4][cout 16][k-step 2][column 2],

@@ -62,6 +62,7 @@ class RadonGeom(C.Structure):
     _fields_ = [("kind", C.c_int), ("n_view", C.c_int), ("det_count", C.c_int), ("source_distance", C.c_float),
                 ("det_distance", C.c_float), ("det_spacing", C.c_float)]
 PNPX_GEOM_PARALLEL, PNPX_GEOM_FAN = 0, 1
+PNPX_FAN_W_ADJOINT, PNPX_FAN_W_FBP = 0, 1
 
 
 # name -> (restype, argtypes); mirrors include/pnpx.h one to one
@@ -200,6 +201,20 @@ _SIGNATURES = {
     "pnpx_ct_hqs_backward": (C.c_int, [c_void_p, C.POINTER(RadonGeom), C.c_int, C.c_float, _P, _P, C.c_int, _P, _P, _P, _P, _P, _P] +
                              [C.c_int] * 3 + [C.c_ulonglong, c_void_p]),
     "pnpx_ct_hqs": (C.c_int, [c_void_p, _P, _P, _P, C.POINTER(RadonGeom), C.c_int, C.c_float, _P, _P] + [C.c_int] * 4 + [c_void_p]),
+    "pnpx_radon_filter": (C.c_int, [c_void_p, _P, _P, C.POINTER(RadonGeom), C.c_int, C.c_int, C.c_int, c_void_p]),
+    "pnpx_fan_backprojection_w": (C.c_int, [c_void_p, _P, _P, C.POINTER(RadonGeom), C.c_int, C.c_int, C.c_int, c_void_p]),
+    "pnpx_fan_fbp": (C.c_int, [c_void_p, _P, _P, C.POINTER(RadonGeom), C.c_int, C.c_int, c_void_p]),
+    "pnpx_ct_iadmm_geom": (C.c_int, [c_void_p, _P, _P, _P, C.POINTER(RadonGeom), C.c_int, C.c_float, _P, _P, _P] + [C.c_int] * 4 +
+                           [c_void_p]),
+    "pnpx_ct_iadmm_geom_train": (C.c_int, [c_void_p, _P, _P, _P, C.POINTER(RadonGeom), C.c_int, C.c_float, _P, _P, _P] + [C.c_int] * 4 +
+                                 [_P, C.POINTER(C.c_ulonglong), c_void_p]),
+    "pnpx_ct_iadmm_geom_backward": (C.c_int, [c_void_p, C.POINTER(RadonGeom), C.c_int, C.c_float, _P, _P, _P, C.c_int] + [_P] * 7 +
+                                    [C.c_int] * 3 + [C.c_ulonglong, c_void_p]),
+    "pnpx_ct_pg_geom": (C.c_int, [c_void_p, _P, _P, _P, C.POINTER(RadonGeom), C.c_int, C.c_float, _P, _P] + [C.c_int] * 4 + [c_void_p]),
+    "pnpx_ct_pg_geom_train": (C.c_int, [c_void_p, _P, _P, _P, C.POINTER(RadonGeom), C.c_int, C.c_float, _P, _P] + [C.c_int] * 4 +
+                              [_P, C.POINTER(C.c_ulonglong), c_void_p]),
+    "pnpx_ct_pg_geom_backward": (C.c_int, [c_void_p, C.POINTER(RadonGeom), C.c_int, C.c_float, _P, _P, C.c_int] + [_P] * 6 +
+                                 [C.c_int] * 3 + [C.c_ulonglong, c_void_p]),
     "pnpx_winof4_matrices": (None, [c_void_p, c_void_p, c_void_p]),
     "pnpx_winof4_pack": (C.c_int, [c_void_p, C.c_int, C.c_int, c_void_p]),
     "pnpx_conv3x3_probe": (C.c_int, [c_void_p, C.c_int, c_void_p, c_void_p, C.c_int, _P, C.c_int, _P, C.c_int, _P, _P, _P, C.c_float, _P,

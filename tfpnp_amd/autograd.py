@@ -52,6 +52,17 @@ def fan_backprojection(sino, R, geom):
                   float(geom.det_spacing))                                 # VJP = forward projection
 
 
+def fan_fbp(sino, R, geom):
+    """Fan-beam filtered backprojection: the start image of an episode is data, so there is no VJP (sino must not need one)."""
+    return T.call("fan_fbp", sino, int(R), float(geom.source_distance), float(geom.det_distance), float(geom.det_spacing))
+
+
+def radon_filter(sino, geom=None):
+    """The ramp filter of filtered backprojection; geom None = the parallel beam's.  No VJP, as fan_fbp."""
+    g = (0.0, 0.0, 0.0) if geom is None else (float(geom.source_distance), float(geom.det_distance), float(geom.det_spacing))
+    return T.call("radon_filter", sino, *g)
+
+
 # ---- complex helpers (pure layout / pointwise, autograd by PyTorch) -- tfpnp/utils/transforms.py:12-17,260-274
 def r2c(x):
     return torch.stack([x, torch.zeros_like(x)], dim=-1)

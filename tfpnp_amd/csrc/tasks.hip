@@ -2,6 +2,7 @@
 //   tasks/pr/solver.py:37-76, tasks/spi/solver.py:17-52, tasks/ct/solver.py:17-87,
 //   tfpnp/utils/transforms.py:282-320 (cdp), :404-439 (spi_inverse), :447-508 (Radon wrapper),
 //   tfpnp/env/base.py:237-242 (torch_psnr).
+#include <climits>
 #include <cmath>
 
 #include "common.h"
@@ -905,6 +906,9 @@ static void launch_radon_fan_forward(const float* img, size_t istride, const flo
 // Every operation is rounded on its own, in the order of tests/fanbeam_ref.py.  U = D_so + t >= 1 by the host's check of D_so.  The
 // position is clamped to [-2, det + 1]: outside (-1, det) both taps are outside the detector whatever the position, so the clamp
 // changes no result and bounds the LDS window.
+// WEIGHT (compile time, PNPX_FAN_W_*): the adjoint weight above, or the weight of filtered backprojection, w = (D_so / U)^2 (Kak &
+// Slaney section 3.4.2: the squared magnification of the pixel onto the detector through the isocentre); the position is the same.
+template <int WEIGHT>
 __device__ __forceinline__ void fan_pixel_view(float xs, float ys, float2 t, float Dso, float D, float du, float half, float hi,
                                                float* pos, float* w) {
   const float s = addx(mulx(xs, t.x), mulx(ys, t.y));
@@ -912,12 +916,18 @@ __device__ __forceinline__ void fan_pixel_view(float xs, float ys, float2 t, flo
   const float U = addx(Dso, tt);
   const float u = divr(mulx(s, D), U);
   *pos = fminf(fmaxf(addx(divr(u, du), half), -2.f), hi);
-  *w = divr(__fsqrt_rn(addx(mulx(D, D), mulx(u, u))), mulx(U, du));
+  if constexpr (WEIGHT == PNPX_FAN_W_FBP) {
+    const float m = divr(Dso, U);
+    *w = mulx(m, m);
+  } else {
+    *w = divr(__fsqrt_rn(addx(mulx(D, D), mulx(u, u))), mulx(U, du));
+  }
 }
 __device__ __forceinline__ float fan_view_term(float r0, float r1, float f, float w) {
   return mulx(w, addx(mulx(r0, subx(1.f, f)), mulx(r1, f)));
 }
 // Pixel-driven fan backprojection, one thread per pixel: the fallback of the LDS kernel below, same bytes.
+template <int WEIGHT>
 __global__ void radon_fan_backproject_kernel(const float* __restrict__ sino, float* __restrict__ img,
                                              const float2* __restrict__ cs, int R, int V, int det, int B, float Dso, float D,
                                              float du, float scale) {
@@ -930,7 +940,7 @@ __global__ void radon_fan_backproject_kernel(const float* __restrict__ sino, flo
   float acc = 0.f;
   for (int v = 0; v < V; ++v) {
     float pos, w;
-    fan_pixel_view(xs, ys, cs[v], Dso, D, du, half, hi, &pos, &w);
+    fan_pixel_view<WEIGHT>(xs, ys, cs[v], Dso, D, du, half, hi, &pos, &w);
     const float f0 = floorf(pos);
     const int s0 = (int)f0;
     const float* row = sino + ((size_t)b * V + v) * det;
@@ -945,6 +955,7 @@ __global__ void radon_fan_backproject_kernel(const float* __restrict__ sino, flo
 // tile it takes its extremes at the tile's corners: the window of a view starts two bins below the smallest corner position.  Its
 // width `win` comes from the host (fan_window: the widest tile of this geometry; the parallel kernel's 64 bins are too few once the
 // source is close), and a tap index is clamped into the window, which is a no-op unless that bound were wrong.
+template <int WEIGHT>
 __global__ __launch_bounds__(256) void radon_fan_backproject_lds_kernel(const float* __restrict__ sino, float* __restrict__ img,
                                                                         const float2* __restrict__ cs, int R, int V, int det,
                                                                         int win, float Dso, float D, float du, float scale) {
@@ -956,10 +967,10 @@ __global__ __launch_bounds__(256) void radon_fan_backproject_lds_kernel(const fl
     const float xa = subx((float)x0, off), xb = subx((float)min(x0 + RBP_T - 1, R - 1), off);
     const float ya = subx((float)y0, off), yb = subx((float)min(y0 + RBP_T - 1, R - 1), off);
     float p0, p1, p2, p3, w;
-    fan_pixel_view(xa, ya, cs[v], Dso, D, du, half, hi, &p0, &w);
-    fan_pixel_view(xb, ya, cs[v], Dso, D, du, half, hi, &p1, &w);
-    fan_pixel_view(xa, yb, cs[v], Dso, D, du, half, hi, &p2, &w);
-    fan_pixel_view(xb, yb, cs[v], Dso, D, du, half, hi, &p3, &w);
+    fan_pixel_view<WEIGHT>(xa, ya, cs[v], Dso, D, du, half, hi, &p0, &w);
+    fan_pixel_view<WEIGHT>(xb, ya, cs[v], Dso, D, du, half, hi, &p1, &w);
+    fan_pixel_view<WEIGHT>(xa, yb, cs[v], Dso, D, du, half, hi, &p2, &w);
+    fan_pixel_view<WEIGHT>(xb, yb, cs[v], Dso, D, du, half, hi, &p3, &w);
     base[v] = (int)floorf(fminf(fminf(p0, p1), fminf(p2, p3))) - 2;      // two bins of slack against rounding
   }
   __syncthreads();
@@ -985,7 +996,7 @@ __global__ __launch_bounds__(256) void radon_fan_backproject_lds_kernel(const fl
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       float pos, w;
-      fan_pixel_view(xs, ys[j], t, Dso, D, du, half, hi, &pos, &w);
+      fan_pixel_view<WEIGHT>(xs, ys[j], t, Dso, D, du, half, hi, &pos, &w);
       const float f0 = floorf(pos);
       const int k = min(max((int)f0 - bv, 0), win - 2);
       acc[j] = addx(acc[j], fan_view_term(row[k], row[k + 1], subx(pos, f0), w));
@@ -1002,16 +1013,74 @@ __global__ __launch_bounds__(256) void radon_fan_backproject_lds_kernel(const fl
 static bool fan_lds_fits(const FanGeom& G, int B) {      // the LDS budget of radon_backproject_lds_kernel
   return (size_t)G.V * G.win * sizeof(float) + (size_t)G.V * sizeof(int) <= 60 * 1024 && B <= 65535;
 }
-static void launch_radon_fan_backproject(const float* sino, float* img, const float2* cs, int R, const FanGeom& G, int B,
-                                         float scale, hipStream_t s) {
+template <int WEIGHT>
+static void launch_radon_fan_backproject_w(const float* sino, float* img, const float2* cs, int R, const FanGeom& G, int B,
+                                           float scale, hipStream_t s) {
   if (fan_lds_fits(G, B)) {
     const size_t lds = (size_t)G.V * G.win * sizeof(float) + (size_t)G.V * sizeof(int);
-    hipLaunchKernelGGL(radon_fan_backproject_lds_kernel, dim3((R + RBP_T - 1) / RBP_T, (R + RBP_T - 1) / RBP_T, B), dim3(256), lds, s,
-                       sino, img, cs, R, G.V, G.det, G.win, G.Dso, G.D, G.du, scale);
+    hipLaunchKernelGGL(radon_fan_backproject_lds_kernel<WEIGHT>, dim3((R + RBP_T - 1) / RBP_T, (R + RBP_T - 1) / RBP_T, B), dim3(256),
+                       lds, s, sino, img, cs, R, G.V, G.det, G.win, G.Dso, G.D, G.du, scale);
   } else {   // V x window beyond the budget (close source, many views): the per-pixel gather kernel
-    hipLaunchKernelGGL(radon_fan_backproject_kernel, dim3((unsigned)(((size_t)B * R * R + 255) / 256)), dim3(256), 0, s, sino, img, cs, R,
-                       G.V, G.det, B, G.Dso, G.D, G.du, scale);
+    hipLaunchKernelGGL(radon_fan_backproject_kernel<WEIGHT>, dim3((unsigned)(((size_t)B * R * R + 255) / 256)), dim3(256), 0, s, sino,
+                       img, cs, R, G.V, G.det, B, G.Dso, G.D, G.du, scale);
   }
+}
+// weight: PNPX_FAN_W_ADJOINT (the pair's backprojection, divided by `scale`) or PNPX_FAN_W_FBP (checked by the caller)
+static void launch_radon_fan_backproject(const float* sino, float* img, const float2* cs, int R, const FanGeom& G, int B,
+                                         float scale, hipStream_t s, int weight = PNPX_FAN_W_ADJOINT) {
+  if (weight == PNPX_FAN_W_FBP) launch_radon_fan_backproject_w<PNPX_FAN_W_FBP>(sino, img, cs, R, G, B, scale, s);
+  else launch_radon_fan_backproject_w<PNPX_FAN_W_ADJOINT>(sino, img, cs, R, G, B, scale, s);
+}
+// Ramp filter of filtered backprojection in the detector domain, one launch: per sinogram row r[m] = p[m] c[m] (c = cos gamma, the `.x`
+// column of the fan bin table; bins NULL: parallel beam, c = 1), then q[j] = S * sum over m ascending of r[m] h[j - m] with the
+// band-limited ramp's spatial kernel h[0] = 1/4, h[odd n] = -1 / (pi n)^2, h[even n != 0] = 0 (Kak & Slaney eq. 3.61; the kernel whose
+// DFT utils.transforms.ramp_filter is).  Only the centre and the odd lags are visited -- det^2 / 2 multiply-adds per row, no FFT, no
+// padding -- and every operation is rounded on its own in the order tests/fan_fbp_ref.py repeats; S (host, double, rounded once) is
+// the last multiply.  A workgroup stages `rpw` pre-weighted rows and the taps tap[i] = h[2 i + 1], i < det / 2, in LDS -- (rpw + 1/2)
+// det floats: 2.3 KiB at config #4's 389 bins, so LDS never limits the 8 workgroups (32 waves) a CU holds -- and its 256 threads
+// walk the rpw * det outputs.  Per multiply-add a lane reads one row element (a wave's lanes share two addresses, one per parity of
+// j: broadcasts) and one tap (lanes of equal parity read consecutive words): both free of bank conflicts.  The lanes of a wave
+// split the m range at different j, so a wave walks at most det / 2 + 32 steps of the two loops where a lane needs det / 2.
+constexpr int RADON_FILTER_MAX_DET = 8192;      // rpw = 1 above 128 bins: 1.5 * det floats <= 48 KiB of LDS
+__global__ __launch_bounds__(256) void radon_filter_kernel(const float* __restrict__ sin_, float* __restrict__ sout,
+                                                           const float4* __restrict__ bins, int det, int rows, int rpw, float S) {
+  extern __shared__ float rf_lds[];            // [rpw][det] pre-weighted rows, then [det / 2] taps
+  float* tap = rf_lds + rpw * det;
+  const size_t row0 = (size_t)blockIdx.x * rpw;
+  const int live = (int)min((size_t)rpw, (size_t)rows - row0);      // rows of this workgroup (the last one may hold fewer)
+  const float* src = sin_ + row0 * det;
+  for (int e = threadIdx.x; e < live * det; e += 256) {
+    const float p = src[e];
+    rf_lds[e] = bins ? mulx(p, bins[e % det].x) : p;
+  }
+  for (int i = threadIdx.x; i < det / 2; i += 256) {
+    const float pn = mulx(3.14159265358979323846f, (float)(2 * i + 1));
+    tap[i] = divr(-1.f, mulx(pn, pn));
+  }
+  __syncthreads();
+  for (int e = threadIdx.x; e < live * det; e += 256) {
+    const int r = e / det, j = e - r * det;
+    const float* row = rf_lds + r * det;
+    float acc = 0.f;
+    // (unrolled by four: the eight LDS reads of four steps are in flight together; the adds stay in order)
+#pragma unroll 4
+    for (int m = (j + 1) & 1; m < j; m += 2) acc = addx(acc, mulx(row[m], tap[(j - m) >> 1]));      // lags j - m = 1, 3, ... from the far end
+    acc = addx(acc, mulx(row[j], 0.25f));
+#pragma unroll 4
+    for (int m = j + 1; m < det; m += 2) acc = addx(acc, mulx(row[m], tap[(m - j) >> 1]));
+    sout[row0 * det + e] = mulx(acc, S);
+  }
+}
+// S of a fan geometry: pi / (V dp), dp = du D_so / D the ray spacing at the isocentre -- the 1/2 of the full circle's doubly measured
+// rays, the view step 2 pi / V and dp h / dp^2 of the sampled ramp; in double from the fp32 values the kernels get, rounded once.
+static float fan_filter_scale(const FanGeom& G) {
+  return (float)(M_PI / ((double)G.V * ((double)G.du * (double)G.Dso / (double)G.D)));
+}
+static void launch_radon_filter(const float* sin_, float* sout, const float4* bins, int det, size_t rows, float S, hipStream_t s) {
+  const int rpw = std::max(1, std::min(8, 256 / det));      // fill the 256 threads once where a row is short
+  const size_t lds = ((size_t)rpw * det + det / 2) * sizeof(float);
+  hipLaunchKernelGGL(radon_filter_kernel, dim3((unsigned)((rows + rpw - 1) / rpw)), dim3(256), lds, s, sin_, sout, bins, det, (int)rows,
+                     rpw, S);
 }
 // z = z - tau*(g + mu*(z - (x+u))); u = u + x - z; d = z - u                tasks/ct/solver.py:46-49
 __global__ void ct_update_kernel(const float* __restrict__ g, const float* __restrict__ xr, const float* zin,
@@ -1111,13 +1180,15 @@ int radon_table(int R, int V, std::vector<float2>* cs, int* det) {
 
 void fan_tables(const FanGeom& G, std::vector<float2>* cs, std::vector<float4>* bins);
 int fan_window(const FanGeom& G, int R, const std::vector<float2>& cs);
-// Checks a fan geometry and resolves what the launches need; on a refusal nothing has been launched.
-int fan_resolve(const pnpx_radon_geom* g, int R, FanGeom* G) {
+// Checks a fan geometry and resolves what the launches need; on a refusal nothing has been launched.  image = false (the ramp filter,
+// which works on the detector alone and is given no R): what depends on the image is neither checked nor resolved (nstep, win = 0),
+// and the source only has to stand off the isocentre.
+int fan_resolve(const pnpx_radon_geom* g, int R, FanGeom* G, bool image = true) {
   if (!g || g->kind != PNPX_GEOM_FAN) {
     set_error("fan geometry: expected a pnpx_radon_geom of kind PNPX_GEOM_FAN");
     return PNPX_ERR_ARG;
   }
-  if (R <= 0 || g->n_view <= 0) {
+  if ((image && R <= 0) || g->n_view <= 0) {
     set_error("fan geometry: R and n_view must be positive (R %d, n_view %d)", R, g->n_view);
     return PNPX_ERR_ARG;
   }
@@ -1127,7 +1198,11 @@ int fan_resolve(const pnpx_radon_geom* g, int R, FanGeom* G) {
     set_error("fan geometry: distances and spacing must be finite");
     return PNPX_ERR_ARG;
   }
-  if (!(Dso >= n / 2.0 + 1.0)) {
+  if (!image && !(Dso > 0.0)) {
+    set_error("fan geometry: source_distance must be positive, got %g", Dso);
+    return PNPX_ERR_ARG;
+  }
+  if (image && !(Dso >= n / 2.0 + 1.0)) {
     set_error("fan geometry: source_distance %g puts the source inside the sampled span (needs >= n/2 + 1 = %g at R = %d)", Dso,
               n / 2.0 + 1.0, R);
     return PNPX_ERR_SHAPE;
@@ -1146,10 +1221,12 @@ int fan_resolve(const pnpx_radon_geom* g, int R, FanGeom* G) {
   }
   G->V = g->n_view;
   G->det = g->det_count;
-  G->nstep = n;
+  G->nstep = image ? n : 0;
   G->Dso = (float)Dso;
   G->D = (float)(Dso + Dod);
   G->du = (float)du;
+  G->win = 0;
+  if (!image) return PNPX_OK;
   std::vector<float2> cs;
   std::vector<float4> bins;
   fan_tables(*G, &cs, &bins);
@@ -1846,37 +1923,130 @@ int pnpx_fan_forward(pnpx_ctx* ctx, const float* img, float* sino, const pnpx_ra
   return PNPX_OK;
 }
 
-int pnpx_fan_backprojection(pnpx_ctx* ctx, const float* sino, float* img, const pnpx_radon_geom* geom, int B, int R,
-                            void* stream) {
+// The fan backprojection under either weight; `filter`: the sinogram is ramp-filtered first, into the scratch (FBP).
+static int fan_backproject_entry(const char* name, pnpx_ctx* ctx, const float* sino, float* img, const pnpx_radon_geom* geom,
+                                 int weight, bool filter, int B, int R, void* stream) {
   LOCK_CTX(ctx);
-  REQUIRE(img && sino && B > 0, "pnpx_fan_backprojection: bad argument");
+  if (!(img && sino && B > 0)) {
+    set_error("%s: bad argument", name);
+    return PNPX_ERR_ARG;
+  }
+  if (weight != PNPX_FAN_W_ADJOINT && weight != PNPX_FAN_W_FBP) {
+    set_error("%s: weight must be PNPX_FAN_W_ADJOINT or PNPX_FAN_W_FBP, got %d", name, weight);
+    return PNPX_ERR_ARG;
+  }
   FanGeom G;
   PNPX_TRY(fan_resolve(geom, R, &G));
+  if (filter && G.det > RADON_FILTER_MAX_DET) {
+    set_error("%s: det_count %d exceeds the %d bins a filter row holds in LDS", name, G.det, RADON_FILTER_MAX_DET);
+    return PNPX_ERR_SHAPE;
+  }
   hipStream_t s = static_cast<hipStream_t>(stream);
+  const size_t rows = (size_t)B * G.V, fsino = filter ? rows * G.det : 0;
+  if (rows > (size_t)INT_MAX) {
+    set_error("%s: B * n_view = %zu rows exceed 2^31 - 1", name, rows);
+    return PNPX_ERR_SHAPE;
+  }
   void* p;
-  PNPX_TRY(ctx_scratch(ctx, sizeof(float2) * G.V + sizeof(float4) * G.det + 16384, &p));
+  PNPX_TRY(ctx_scratch(ctx, sizeof(float2) * G.V + sizeof(float4) * G.det + fsino * sizeof(float) + 16384, &p));
   Carver cv{static_cast<char*>(p)};
   const float2* cs;
   const float4* bins;
   PNPX_TRY(upload_fan(G, s, &cv, &cs, &bins));
-  launch_radon_fan_backproject(sino, img, cs, R, G, B, 1.f, s);
+  if (filter) {
+    float* q = cv.take<float>(fsino);
+    launch_radon_filter(sino, q, bins, G.det, rows, fan_filter_scale(G), s);
+    PNPX_LAUNCH_CHECK();
+    sino = q;
+  }
+  launch_radon_fan_backproject(sino, img, cs, R, G, B, 1.f, s, weight);
   PNPX_LAUNCH_CHECK();
   return PNPX_OK;
 }
 
+int pnpx_fan_backprojection(pnpx_ctx* ctx, const float* sino, float* img, const pnpx_radon_geom* geom, int B, int R,
+                            void* stream) {
+  return fan_backproject_entry("pnpx_fan_backprojection", ctx, sino, img, geom, PNPX_FAN_W_ADJOINT, false, B, R, stream);
+}
+
+int pnpx_fan_backprojection_w(pnpx_ctx* ctx, const float* sino, float* img, const pnpx_radon_geom* geom, int weight, int B, int R,
+                              void* stream) {
+  return fan_backproject_entry("pnpx_fan_backprojection_w", ctx, sino, img, geom, weight, false, B, R, stream);
+}
+
+int pnpx_fan_fbp(pnpx_ctx* ctx, const float* sino, float* img, const pnpx_radon_geom* geom, int B, int R, void* stream) {
+  return fan_backproject_entry("pnpx_fan_fbp", ctx, sino, img, geom, PNPX_FAN_W_FBP, true, B, R, stream);
+}
+
+int pnpx_radon_filter(pnpx_ctx* ctx, const float* sino_in, float* sino_out, const pnpx_radon_geom* geom, int B, int n_view, int det,
+                      void* stream) {
+  LOCK_CTX(ctx);
+  REQUIRE(sino_in && sino_out && B > 0 && n_view > 0, "pnpx_radon_filter: bad argument");
+  REQUIRE(sino_in != sino_out, "pnpx_radon_filter: sino_out must not be sino_in (every output reads the whole input row)");
+  const bool fan = geom && geom->kind != PNPX_GEOM_PARALLEL;
+  FanGeom G;
+  if (fan) {
+    PNPX_TRY(fan_resolve(geom, 0, &G, false));
+    if (G.V != n_view || G.det != det) {
+      set_error("pnpx_radon_filter: the geometry has %d views of %d bins, the call %d of %d", G.V, G.det, n_view, det);
+      return PNPX_ERR_ARG;
+    }
+  }
+  if (det < 2 || det > RADON_FILTER_MAX_DET) {
+    set_error("pnpx_radon_filter: det must be in [2, %d] (a row is staged in LDS), got %d", RADON_FILTER_MAX_DET, det);
+    return PNPX_ERR_SHAPE;
+  }
+  const size_t rows = (size_t)B * n_view;
+  if (rows > (size_t)INT_MAX) {
+    set_error("pnpx_radon_filter: B * n_view = %zu rows exceed 2^31 - 1", rows);
+    return PNPX_ERR_SHAPE;
+  }
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const float4* bins = nullptr;
+  if (fan) {
+    void* p;
+    PNPX_TRY(ctx_scratch(ctx, sizeof(float2) * G.V + sizeof(float4) * G.det + 16384, &p));
+    Carver cv{static_cast<char*>(p)};
+    const float2* cs;
+    PNPX_TRY(upload_fan(G, s, &cv, &cs, &bins));
+  }
+  launch_radon_filter(sino_in, sino_out, bins, det, rows, fan ? fan_filter_scale(G) : (float)(M_PI / (double)n_view), s);
+  PNPX_LAUNCH_CHECK();
+  return PNPX_OK;
+}
+
+// The geometry argument of the solver loops: NULL or kind PNPX_GEOM_PARALLEL = the parallel pair with today's table; a fan geometry is
+// resolved into *G (its n_view must be the call's).  *fan = G or NULL.
+static int ct_geometry(const char* name, const pnpx_radon_geom* geom, int n_view, int R, FanGeom* G, const FanGeom** fan) {
+  *fan = nullptr;
+  if (!geom || geom->kind == PNPX_GEOM_PARALLEL) return PNPX_OK;
+  PNPX_TRY(fan_resolve(geom, R, G));
+  if (G->V != n_view) {
+    set_error("%s: the geometry has %d views, the call %d", name, G->V, n_view);
+    return PNPX_ERR_ARG;
+  }
+  *fan = G;
+  return PNPX_OK;
+}
+// where the backward loops keep the tables in `work` with a fan geometry: behind k image-sized buffers, 16-byte aligned
+static size_t ct_table_offset(size_t k, size_t n) { return (k * n + 3) & ~(size_t)3; }
+
 // IADMMSolver_CT.forward; `saved` != NULL (training path): per iteration the denoiser input [T][n], G = g + mu (z - (x + u))
 // [T][n] and q2 = z - (x + u) [T][n]
-static int ct_iadmm_forward(pnpx_ctx* ctx, const float* vars_in, float* vars_out, const float* y0, int n_view, float opnorm,
-                            const float* sigma_d, const float* mu, const float* tau, int param_stride, int B, int R, int T,
-                            float* saved, unsigned long long* ticket_out, hipStream_t s) {
+static int ct_iadmm_forward(pnpx_ctx* ctx, const float* vars_in, float* vars_out, const float* y0, const pnpx_radon_geom* geom,
+                            int n_view, float opnorm, const float* sigma_d, const float* mu, const float* tau, int param_stride,
+                            int B, int R, int T, float* saved, unsigned long long* ticket_out, hipStream_t s) {
   REQUIRE(vars_in && vars_out && y0 && sigma_d && mu && tau && B > 0 && R > 0 && n_view > 0 && T >= 0 &&
               param_stride >= T && opnorm > 0.f,
           "pnpx_ct_iadmm: bad argument");
+  FanGeom G;
+  const FanGeom* fan;
+  PNPX_TRY(ct_geometry("pnpx_ct_iadmm", geom, n_view, R, &G, &fan));
   const Prox px = prox_begin(ctx, sigma_d, param_stride, B, R, R, saved, ticket_out, s);
   const auto [HW, is, n] = state_dims(B, R, R, 3);
   if (T == 0) return copy_state(vars_out, vars_in, sizeof(float) * is * B, s);
   CtScratch C;
-  PNPX_TRY(ct_scratch(ctx, B, R, n_view, 3, s, &C));
+  PNPX_TRY(ct_scratch(ctx, B, R, n_view, 3, s, &C, nullptr, true, fan));
   float *d = C.img[0], *xr = C.img[1], *g = C.img[2];
   const float op2 = (float)((double)opnorm * (double)opnorm);  // backprojection / opnorm**2   transforms.py:476-477
   hipLaunchKernelGGL(real_diff_slots_kernel, g1(n), dim3(256), 0, s, vars_in + HW, vars_in + 2 * HW, is, d, HW, B);
@@ -1899,44 +2069,61 @@ static int ct_iadmm_forward(pnpx_ctx* ctx, const float* vars_in, float* vars_out
   return PNPX_OK;
 }
 
+int pnpx_ct_iadmm_geom(pnpx_ctx* ctx, const float* vars_in, float* vars_out, const float* y0, const pnpx_radon_geom* geom,
+                       int n_view, float opnorm, const float* sigma_d, const float* mu, const float* tau, int param_stride, int B,
+                       int R, int T, void* stream) {
+  return solver_entry(ctx, stream, [&](hipStream_t s) {
+    return ct_iadmm_forward(ctx, vars_in, vars_out, y0, geom, n_view, opnorm, sigma_d, mu, tau, param_stride, B, R, T, nullptr,
+                            nullptr, s);
+  });
+}
+
 int pnpx_ct_iadmm(pnpx_ctx* ctx, const float* vars_in, float* vars_out, const float* y0, int n_view, float opnorm,
                   const float* sigma_d, const float* mu, const float* tau, int param_stride, int B, int R, int T,
                   void* stream) {
-  return solver_entry(ctx, stream, [&](hipStream_t s) {
-    return ct_iadmm_forward(ctx, vars_in, vars_out, y0, n_view, opnorm, sigma_d, mu, tau, param_stride, B, R, T, nullptr,
-                            nullptr, s);
+  return pnpx_ct_iadmm_geom(ctx, vars_in, vars_out, y0, nullptr, n_view, opnorm, sigma_d, mu, tau, param_stride, B, R, T, stream);
+}
+
+int pnpx_ct_iadmm_geom_train(pnpx_ctx* ctx, const float* vars_in, float* vars_out, const float* y0, const pnpx_radon_geom* geom,
+                             int n_view, float opnorm, const float* sigma_d, const float* mu, const float* tau, int param_stride,
+                             int B, int R, int T, float* saved, unsigned long long* ticket, void* stream) {
+  return solver_train_entry(ctx, "pnpx_ct_iadmm_train", saved || T == 0, ticket, stream, [&](hipStream_t s) {
+    return ct_iadmm_forward(ctx, vars_in, vars_out, y0, geom, n_view, opnorm, sigma_d, mu, tau, param_stride, B, R, T, saved,
+                            ticket, s);
   });
 }
 
 int pnpx_ct_iadmm_train(pnpx_ctx* ctx, const float* vars_in, float* vars_out, const float* y0, int n_view, float opnorm,
                         const float* sigma_d, const float* mu, const float* tau, int param_stride, int B, int R, int T,
                         float* saved, unsigned long long* ticket, void* stream) {
-  return solver_train_entry(ctx, "pnpx_ct_iadmm_train", saved || T == 0, ticket, stream, [&](hipStream_t s) {
-    return ct_iadmm_forward(ctx, vars_in, vars_out, y0, n_view, opnorm, sigma_d, mu, tau, param_stride, B, R, T, saved,
-                            ticket, s);
-  });
+  return pnpx_ct_iadmm_geom_train(ctx, vars_in, vars_out, y0, nullptr, n_view, opnorm, sigma_d, mu, tau, param_stride, B, R, T, saved,
+                                  ticket, stream);
 }
 
 // VJP of the T-iteration CT iADMM map wrt (cat(x, z, u), sigma_d, mu, tau); the data step's adjoint is A^T A / opnorm^2 with the
-// projector pair standing in for each other's transpose (as in the composed path and in torch_radon).  work = 6*B*R*R + 2*n_view floats.
-int pnpx_ct_iadmm_backward(pnpx_ctx* ctx, int n_view, float opnorm, const float* sigma_d, const float* mu, const float* tau,
-                           int param_stride, const float* saved, const float* grad_vars_out, float* grad_vars_in,
-                           float* grad_sigma_d, float* grad_mu, float* grad_tau, float* work, int B, int R, int T,
-                           unsigned long long ticket, void* stream) {
+// projector pair standing in for each other's transpose (as in the composed path and in torch_radon).  work = 6*B*R*R + 2*n_view floats;
+// with a fan geometry 4 + 4*det_count more (its tables stand 16-byte aligned behind the six buffers).
+int pnpx_ct_iadmm_geom_backward(pnpx_ctx* ctx, const pnpx_radon_geom* geom, int n_view, float opnorm, const float* sigma_d,
+                                const float* mu, const float* tau, int param_stride, const float* saved, const float* grad_vars_out,
+                                float* grad_vars_in, float* grad_sigma_d, float* grad_mu, float* grad_tau, float* work, int B, int R,
+                                int T, unsigned long long ticket, void* stream) {
   return solver_entry(ctx, stream, [&](hipStream_t s) -> int {
     REQUIRE(sigma_d && mu && tau && grad_vars_out && grad_vars_in && B > 0 && R > 0 && n_view > 0 && T >= 0 &&
                 param_stride >= T && opnorm > 0.f && (T == 0 || (saved && grad_sigma_d && grad_mu && grad_tau && work)),
             "pnpx_ct_iadmm_backward: bad argument");
+    FanGeom G;
+    const FanGeom* fan;
+    PNPX_TRY(ct_geometry("pnpx_ct_iadmm_backward", geom, n_view, R, &G, &fan));
     const auto [HW, is, n] = state_dims(B, R, R, 3);
     PNPX_TRY(copy_state(grad_vars_in, grad_vars_out, sizeof(float) * is * B, s));
     if (T == 0) return PNPX_OK;
     CtScratch C;
-    float2* cs_home = reinterpret_cast<float2*>(work + 6 * n);       // the table outlives the VJP calls in the work buffer
-    PNPX_TRY(ct_scratch(ctx, B, R, n_view, 0, s, &C, cs_home, true));
+    float2* cs_home = reinterpret_cast<float2*>(work + (fan ? ct_table_offset(6, n) : 6 * n));   // the tables outlive the VJP calls in the work buffer
+    PNPX_TRY(ct_scratch(ctx, B, R, n_view, 0, s, &C, cs_home, true, fan));
     const float op2 = (float)((double)opnorm * (double)opnorm);
     float *e = work, *J = work + n, *gxr = work + 2 * n, *gd = work + 3 * n, *c_tau = work + 4 * n, *c_mu = work + 5 * n;
     for (int i = T - 1; i >= 0; --i) {
-      PNPX_TRY(ct_scratch(ctx, B, R, n_view, 0, s, &C, cs_home, false));   // re-carve: the VJP below shares (and may grow) the scratch
+      PNPX_TRY(ct_scratch(ctx, B, R, n_view, 0, s, &C, cs_home, false, fan));   // re-carve: the VJP below shares (and may grow) the scratch
       hipLaunchKernelGGL(ct_cotangent_kernel, g1(n), dim3(256), 0, s, grad_vars_in, is, e, HW, B);
       PNPX_LAUNCH_CHECK();
       PNPX_TRY(ct_normal_op(C, e, (size_t)HW, nullptr, J, op2, R, n_view, B, s));
@@ -1954,18 +2141,29 @@ int pnpx_ct_iadmm_backward(pnpx_ctx* ctx, int n_view, float opnorm, const float*
   });
 }
 
+int pnpx_ct_iadmm_backward(pnpx_ctx* ctx, int n_view, float opnorm, const float* sigma_d, const float* mu, const float* tau,
+                           int param_stride, const float* saved, const float* grad_vars_out, float* grad_vars_in,
+                           float* grad_sigma_d, float* grad_mu, float* grad_tau, float* work, int B, int R, int T,
+                           unsigned long long ticket, void* stream) {
+  return pnpx_ct_iadmm_geom_backward(ctx, nullptr, n_view, opnorm, sigma_d, mu, tau, param_stride, saved, grad_vars_out, grad_vars_in,
+                                     grad_sigma_d, grad_mu, grad_tau, work, B, R, T, ticket, stream);
+}
+
 // PGSolver_CT.forward; `saved` != NULL (training path): per iteration the denoiser input [T][n] and g = A^T(A x - y0) / opnorm^2 [T][n]
-static int ct_pg_forward(pnpx_ctx* ctx, const float* vars_in, float* vars_out, const float* y0, int n_view, float opnorm,
-                         const float* sigma_d, const float* tau, int param_stride, int B, int R, int T, float* saved,
-                         unsigned long long* ticket_out, hipStream_t s) {
+static int ct_pg_forward(pnpx_ctx* ctx, const float* vars_in, float* vars_out, const float* y0, const pnpx_radon_geom* geom,
+                         int n_view, float opnorm, const float* sigma_d, const float* tau, int param_stride, int B, int R, int T,
+                         float* saved, unsigned long long* ticket_out, hipStream_t s) {
   REQUIRE(vars_in && vars_out && y0 && sigma_d && tau && B > 0 && R > 0 && n_view > 0 && T >= 0 &&
               param_stride >= T && opnorm > 0.f,
           "pnpx_ct_pg: bad argument");
+  FanGeom G;
+  const FanGeom* fan;
+  PNPX_TRY(ct_geometry("pnpx_ct_pg", geom, n_view, R, &G, &fan));
   const Prox px = prox_begin(ctx, sigma_d, param_stride, B, R, R, saved, ticket_out, s);
   const auto [HW, is, n] = state_dims(B, R, R, 1);
   if (T == 0) return copy_state(vars_out, vars_in, sizeof(float) * is * B, s);
   CtScratch C;
-  PNPX_TRY(ct_scratch(ctx, B, R, n_view, 2, s, &C));
+  PNPX_TRY(ct_scratch(ctx, B, R, n_view, 2, s, &C, nullptr, true, fan));
   const float op2 = (float)((double)opnorm * (double)opnorm);
   for (int i = 0; i < T; ++i) {
     const float* xi = (i == 0) ? vars_in : vars_out;
@@ -1979,43 +2177,59 @@ static int ct_pg_forward(pnpx_ctx* ctx, const float* vars_in, float* vars_out, c
   return PNPX_OK;
 }
 
+int pnpx_ct_pg_geom(pnpx_ctx* ctx, const float* vars_in, float* vars_out, const float* y0, const pnpx_radon_geom* geom, int n_view,
+                    float opnorm, const float* sigma_d, const float* tau, int param_stride, int B, int R, int T, void* stream) {
+  return solver_entry(ctx, stream, [&](hipStream_t s) {
+    return ct_pg_forward(ctx, vars_in, vars_out, y0, geom, n_view, opnorm, sigma_d, tau, param_stride, B, R, T, nullptr, nullptr, s);
+  });
+}
+
 int pnpx_ct_pg(pnpx_ctx* ctx, const float* vars_in, float* vars_out, const float* y0, int n_view, float opnorm,
                const float* sigma_d, const float* tau, int param_stride, int B, int R, int T, void* stream) {
-  return solver_entry(ctx, stream, [&](hipStream_t s) {
-    return ct_pg_forward(ctx, vars_in, vars_out, y0, n_view, opnorm, sigma_d, tau, param_stride, B, R, T, nullptr, nullptr, s);
+  return pnpx_ct_pg_geom(ctx, vars_in, vars_out, y0, nullptr, n_view, opnorm, sigma_d, tau, param_stride, B, R, T, stream);
+}
+
+int pnpx_ct_pg_geom_train(pnpx_ctx* ctx, const float* vars_in, float* vars_out, const float* y0, const pnpx_radon_geom* geom,
+                          int n_view, float opnorm, const float* sigma_d, const float* tau, int param_stride, int B, int R, int T,
+                          float* saved, unsigned long long* ticket, void* stream) {
+  return solver_train_entry(ctx, "pnpx_ct_pg_train", saved || T == 0, ticket, stream, [&](hipStream_t s) {
+    return ct_pg_forward(ctx, vars_in, vars_out, y0, geom, n_view, opnorm, sigma_d, tau, param_stride, B, R, T, saved, ticket, s);
   });
 }
 
 int pnpx_ct_pg_train(pnpx_ctx* ctx, const float* vars_in, float* vars_out, const float* y0, int n_view, float opnorm,
                      const float* sigma_d, const float* tau, int param_stride, int B, int R, int T, float* saved,
                      unsigned long long* ticket, void* stream) {
-  return solver_train_entry(ctx, "pnpx_ct_pg_train", saved || T == 0, ticket, stream, [&](hipStream_t s) {
-    return ct_pg_forward(ctx, vars_in, vars_out, y0, n_view, opnorm, sigma_d, tau, param_stride, B, R, T, saved, ticket, s);
-  });
+  return pnpx_ct_pg_geom_train(ctx, vars_in, vars_out, y0, nullptr, n_view, opnorm, sigma_d, tau, param_stride, B, R, T, saved, ticket,
+                               stream);
 }
 
 // VJP of the T-iteration CT PG map x' = D(x - tau g(x)) wrt (x, sigma_d, tau): gd = D^T gx';  d/d tau = -<gd, g_i>;
-// gx = gd - tau A^T A gd / opnorm^2.  work = 3*B*R*R + 2*n_view floats.
-int pnpx_ct_pg_backward(pnpx_ctx* ctx, int n_view, float opnorm, const float* sigma_d, const float* tau, int param_stride,
-                        const float* saved, const float* grad_vars_out, float* grad_vars_in, float* grad_sigma_d,
-                        float* grad_tau, float* work, int B, int R, int T, unsigned long long ticket, void* stream) {
+// gx = gd - tau A^T A gd / opnorm^2.  work = 3*B*R*R + 1 + 2*n_view floats; with a fan geometry 3 + 4*det_count more.
+int pnpx_ct_pg_geom_backward(pnpx_ctx* ctx, const pnpx_radon_geom* geom, int n_view, float opnorm, const float* sigma_d,
+                             const float* tau, int param_stride, const float* saved, const float* grad_vars_out,
+                             float* grad_vars_in, float* grad_sigma_d, float* grad_tau, float* work, int B, int R, int T,
+                             unsigned long long ticket, void* stream) {
   return solver_entry(ctx, stream, [&](hipStream_t s) -> int {
     REQUIRE(sigma_d && tau && grad_vars_out && grad_vars_in && B > 0 && R > 0 && n_view > 0 && T >= 0 &&
                 param_stride >= T && opnorm > 0.f && (T == 0 || (saved && grad_sigma_d && grad_tau && work)),
             "pnpx_ct_pg_backward: bad argument");
+    FanGeom G;
+    const FanGeom* fan;
+    PNPX_TRY(ct_geometry("pnpx_ct_pg_backward", geom, n_view, R, &G, &fan));
     const auto [HW, is, n] = state_dims(B, R, R, 1);
     PNPX_TRY(copy_state(grad_vars_in, grad_vars_out, sizeof(float) * is * B, s));
     if (T == 0) return PNPX_OK;
     CtScratch C;
     // (cos, sin) table behind the three n-float buffers, at an EVEN float offset: 3 * n is odd for odd B * R * R and a float2
-    // array needs 8-byte alignment (work holds 3 * n + 1 + 2 * n_view floats)
-    float2* cs_home = reinterpret_cast<float2*>(work + ((3 * n + 1) & ~(size_t)1));
-    PNPX_TRY(ct_scratch(ctx, B, R, n_view, 0, s, &C, cs_home, true));
+    // array needs 8-byte alignment (work holds 3 * n + 1 + 2 * n_view floats); a fan's float4 bin table in front of it, 16-byte
+    float2* cs_home = reinterpret_cast<float2*>(work + (fan ? ct_table_offset(3, n) : ((3 * n + 1) & ~(size_t)1)));
+    PNPX_TRY(ct_scratch(ctx, B, R, n_view, 0, s, &C, cs_home, true, fan));
     const float op2 = (float)((double)opnorm * (double)opnorm);
     float *gd = work, *J = work + n, *c_tau = work + 2 * n;
     for (int i = T - 1; i >= 0; --i) {
       PNPX_TRY(prox_vjp(ctx, i, saved, sigma_d, param_stride, grad_vars_in, gd, grad_sigma_d, B, R, R, s, ticket));
-      PNPX_TRY(ct_scratch(ctx, B, R, n_view, 0, s, &C, cs_home, false));   // re-carve after the VJP (shared, growable scratch)
+      PNPX_TRY(ct_scratch(ctx, B, R, n_view, 0, s, &C, cs_home, false, fan));   // re-carve after the VJP (shared, growable scratch)
       PNPX_TRY(ct_normal_op(C, gd, (size_t)HW, nullptr, J, op2, R, n_view, B, s));
       hipLaunchKernelGGL(ct_pg_adjoint_kernel, g1(n), dim3(256), 0, s, gd, J, saved + ((size_t)T + i) * n, tau + i,
                          param_stride, HW, B, grad_vars_in, c_tau);
@@ -2027,21 +2241,12 @@ int pnpx_ct_pg_backward(pnpx_ctx* ctx, int n_view, float opnorm, const float* si
   });
 }
 
-// The geometry argument of the HQS trio: NULL or kind PNPX_GEOM_PARALLEL = the parallel pair with today's table; a fan geometry is
-// resolved into *G (its n_view must be the call's).  *fan = G or NULL.
-static int ct_hqs_geometry(const char* name, const pnpx_radon_geom* geom, int n_view, int R, FanGeom* G, const FanGeom** fan) {
-  *fan = nullptr;
-  if (!geom || geom->kind == PNPX_GEOM_PARALLEL) return PNPX_OK;
-  PNPX_TRY(fan_resolve(geom, R, G));
-  if (G->V != n_view) {
-    set_error("%s: the geometry has %d views, the call %d", name, G->V, n_view);
-    return PNPX_ERR_ARG;
-  }
-  *fan = G;
-  return PNPX_OK;
+int pnpx_ct_pg_backward(pnpx_ctx* ctx, int n_view, float opnorm, const float* sigma_d, const float* tau, int param_stride,
+                        const float* saved, const float* grad_vars_out, float* grad_vars_in, float* grad_sigma_d,
+                        float* grad_tau, float* work, int B, int R, int T, unsigned long long ticket, void* stream) {
+  return pnpx_ct_pg_geom_backward(ctx, nullptr, n_view, opnorm, sigma_d, tau, param_stride, saved, grad_vars_out, grad_vars_in,
+                                  grad_sigma_d, grad_tau, work, B, R, T, ticket, stream);
 }
-// where the backward loops keep the tables in `work`: behind k image-sized buffers, 16-byte aligned
-static size_t ct_table_offset(size_t k, size_t n) { return (k * n + 3) & ~(size_t)3; }
 
 // HQSSolver_CT.forward: state cat(x, z); per iteration x = D(z, sigma_d_i), z <- z - (A^T(A z - y0) / opnorm^2 + mu_i (z - x)) / (1 + mu_i).
 // `saved` != NULL (training path): per iteration the denoiser input z_i [T][n], G = g + mu (z - x) [T][n] and q = z - x [T][n]
@@ -2053,7 +2258,7 @@ static int ct_hqs_forward(pnpx_ctx* ctx, const float* vars_in, float* vars_out, 
           "pnpx_ct_hqs: bad argument");
   FanGeom G;
   const FanGeom* fan;
-  PNPX_TRY(ct_hqs_geometry("pnpx_ct_hqs", geom, n_view, R, &G, &fan));
+  PNPX_TRY(ct_geometry("pnpx_ct_hqs", geom, n_view, R, &G, &fan));
   const Prox px = prox_begin(ctx, sigma_d, param_stride, B, R, R, saved, ticket_out, s);
   const auto [HW, is, n] = state_dims(B, R, R, 2);
   if (T == 0) return copy_state(vars_out, vars_in, sizeof(float) * is * B, s);
@@ -2103,7 +2308,7 @@ int pnpx_ct_hqs_backward(pnpx_ctx* ctx, const pnpx_radon_geom* geom, int n_view,
             "pnpx_ct_hqs_backward: bad argument");
     FanGeom G;
     const FanGeom* fan;
-    PNPX_TRY(ct_hqs_geometry("pnpx_ct_hqs_backward", geom, n_view, R, &G, &fan));
+    PNPX_TRY(ct_geometry("pnpx_ct_hqs_backward", geom, n_view, R, &G, &fan));
     const auto [HW, is, n] = state_dims(B, R, R, 2);
     PNPX_TRY(copy_state(grad_vars_in, grad_vars_out, sizeof(float) * is * B, s));
     if (T == 0) return PNPX_OK;

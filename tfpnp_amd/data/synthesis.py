@@ -144,10 +144,13 @@ def spi_measure(gt, K, generator=None, counts=None):
     return {'x0': x0, 'output': x0.clone(), 'gt': gt, 'K': torch.full_like(gt, K / 10)}
 
 
-def ct_measure(gt, view, radon_generator=None, noise_model=None, generator=None, geometry=None):
-    """gt [B,1,R,R], view = number of projection angles -> dict(y0 sinogram, ATy0, output, x0 = FBP, gt, view map,
-    sigma_n map).  geometry: None = parallel beam, or a transforms.FanBeam; there is no fan-beam FBP, so with a fan geometry
-    x0 is ATy0 (the normalised weighted backprojection of y0)."""
+def ct_measure(gt, view, radon_generator=None, noise_model=None, generator=None, geometry=None, x0_from=None):
+    """gt [B,1,R,R], view = number of projection angles -> dict(y0 sinogram, ATy0, output, x0, gt, view map, sigma_n map).
+    geometry: None = parallel beam, or a transforms.FanBeam.  x0_from: 'fbp' = the filtered backprojection of y0 (the reference's
+    start, transforms.py:479-481), 'aty0' = ATy0, the normalised weighted backprojection; None = 'fbp' for the parallel beam and
+    'aty0' for a fan."""
+    if x0_from not in (None, 'fbp', 'aty0'):
+        raise ValueError(f"ct_measure: x0_from must be None, 'fbp' or 'aty0', got {x0_from!r}")
     radon_generator = radon_generator or transforms.RadonGenerator()
     radon = (radon_generator(gt.shape[-1], view, device=gt.device) if geometry is None else
              radon_generator(gt.shape[-1], view, device=gt.device, geometry=geometry))
@@ -156,6 +159,11 @@ def ct_measure(gt, view, radon_generator=None, noise_model=None, generator=None,
     if noise_model is not None:
         y0, sigma_n = noise_model(y0, generator=generator)
     ATy0 = radon.backprojection_norm(y0)
-    x0 = radon.filter_backprojection(y0) if geometry is None else ATy0.clone()
+    if x0_from is None:
+        x0_from = 'fbp' if geometry is None else 'aty0'
+    if x0_from == 'aty0':
+        x0 = ATy0.clone()
+    else:
+        x0 = radon.filter_backprojection(y0) if geometry is None else radon.fbp(y0)
     return {'y0': y0, 'ATy0': ATy0, 'output': ATy0.clone(), 'x0': x0, 'gt': gt,
             'view': torch.full_like(gt, view / 120), 'sigma_n': _item_map(sigma_n, gt)}

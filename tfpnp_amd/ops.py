@@ -1191,15 +1191,51 @@ def fan_forward(img, n_view, det_count, source_distance, det_distance, det_spaci
     return out
 
 
-def fan_backprojection(sino, R, source_distance, det_distance, det_spacing, ctx=None):
-    """pnpx_fan_backprojection: [B,1,n_view,det_count] -> [B,1,R,R] (weighted: include/pnpx.h)."""
+_FAN_WEIGHTS = {"adjoint": _lib.PNPX_FAN_W_ADJOINT, "fbp": _lib.PNPX_FAN_W_FBP}
+
+
+def fan_backprojection(sino, R, source_distance, det_distance, det_spacing, ctx=None, weight=None):
+    """pnpx_fan_backprojection: [B,1,n_view,det_count] -> [B,1,R,R] (weighted: include/pnpx.h).  weight 'adjoint' or 'fbp':
+    pnpx_fan_backprojection_w with the pair's ray-density weight (the same bytes) or filtered backprojection's (D_so / U)^2."""
+    sino = _f32(sino, "sino")
+    B, _, V, det = sino.shape
+    g = fan_geom(V, det, source_distance, det_distance, det_spacing)
+    if weight is not None and weight not in _FAN_WEIGHTS:
+        raise PnpxError(f"fan_backprojection: weight must be one of {sorted(_FAN_WEIGHTS)}, got {weight!r}")
+    out = torch.empty((B, 1, int(R), int(R)), device=sino.device, dtype=torch.float32)
+    ctx = ctx or default_context(sino.device)
+    with torch.cuda.device(sino.device):
+        if weight is None:
+            check(_lib.lib().pnpx_fan_backprojection(ctx.handle, _p(sino), _p(out), g, B, int(R), _stream(sino)))
+        else:
+            check(_lib.lib().pnpx_fan_backprojection_w(ctx.handle, _p(sino), _p(out), g, _FAN_WEIGHTS[weight], B, int(R),
+                                                       _stream(sino)))
+    return out
+
+
+def radon_filter(sino, source_distance=None, det_distance=None, det_spacing=None, ctx=None):
+    """pnpx_radon_filter: the ramp filter of filtered backprojection along the detector axis, [B,1,n_view,det] -> the same shape
+    (a new tensor).  No distances: the parallel beam's filter (Radon_norm.filter_sinogram's result); with them the fan beam's, with
+    the cos gamma pre-weight and S = pi / (n_view dp) (include/pnpx.h)."""
+    sino = _f32(sino, "sino")
+    B, _, V, det = sino.shape
+    g = None if source_distance is None else fan_geom(V, det, source_distance, det_distance, det_spacing)
+    out = torch.empty_like(sino)
+    ctx = ctx or default_context(sino.device)
+    with torch.cuda.device(sino.device):
+        check(_lib.lib().pnpx_radon_filter(ctx.handle, _p(sino), _p(out), g, B, V, det, _stream(sino)))
+    return out
+
+
+def fan_fbp(sino, R, source_distance, det_distance, det_spacing, ctx=None):
+    """pnpx_fan_fbp: filtered backprojection of a fan-beam sinogram, [B,1,n_view,det_count] -> [B,1,R,R]."""
     sino = _f32(sino, "sino")
     B, _, V, det = sino.shape
     g = fan_geom(V, det, source_distance, det_distance, det_spacing)
     out = torch.empty((B, 1, int(R), int(R)), device=sino.device, dtype=torch.float32)
     ctx = ctx or default_context(sino.device)
     with torch.cuda.device(sino.device):
-        check(_lib.lib().pnpx_fan_backprojection(ctx.handle, _p(sino), _p(out), g, B, int(R), _stream(sino)))
+        check(_lib.lib().pnpx_fan_fbp(ctx.handle, _p(sino), _p(out), g, B, int(R), _stream(sino)))
     return out
 
 
@@ -1239,6 +1275,56 @@ def ct_hqs_backward(ctx, n_view, opnorm, det_count, source_distance, det_distanc
                     iter_num=None, ticket=0):
     """pnpx_ct_hqs_backward -> (grad variables [B,2,R,R], grad sigma_d, grad mu, each [B,T])."""
     return _solver_backward(_CT_HQS, ctx, (n_view, opnorm, det_count, source_distance, det_distance, det_spacing), (sigma_d, mu),
+                            saved, grad_out, iter_num, ticket)
+
+
+# iADMM and PG on a chosen geometry: the aux tuple of ct_hqs; the work tails of ct_iadmm / ct_pg, plus the aligned fan tables
+_CT_IADMM_GEOM = _Loop("ct_iadmm_geom", 3, False, _aux_ct_hqs, 3, lambda S: 3, 6,
+                       lambda n_view, opnorm, det_count, *_: 2 * int(n_view) + (4 + 4 * int(det_count) if int(det_count) else 0),
+                       fwd_checks_iter=False)
+_CT_PG_GEOM = _Loop("ct_pg_geom", 1, False, _aux_ct_hqs, 2, lambda S: 2, 3,
+                    lambda n_view, opnorm, det_count, *_: 1 + 2 * int(n_view) + (3 + 4 * int(det_count) if int(det_count) else 0),
+                    fwd_checks_iter=False)
+
+
+def ct_iadmm_geom(ctx, variables, y0, n_view, opnorm, det_count, source_distance, det_distance, det_spacing, sigma_d, mu, tau,
+                  iter_num=None):
+    """pnpx_ct_iadmm_geom: IADMMSolver_CT.forward on a chosen geometry; det_count 0 = the parallel pair, the bytes of ct_iadmm."""
+    return _solver_forward(_CT_IADMM_GEOM, ctx, variables, (y0, n_view, opnorm, det_count, source_distance, det_distance, det_spacing),
+                           (sigma_d, mu, tau), iter_num, False)
+
+
+def ct_iadmm_geom_train(ctx, variables, y0, n_view, opnorm, det_count, source_distance, det_distance, det_spacing, sigma_d, mu, tau,
+                        iter_num=None):
+    """pnpx_ct_iadmm_geom_train -> (next state [B,3,R,R], saved [3*T*B*R*R], ticket)."""
+    return _solver_forward(_CT_IADMM_GEOM, ctx, variables, (y0, n_view, opnorm, det_count, source_distance, det_distance, det_spacing),
+                           (sigma_d, mu, tau), iter_num, True)
+
+
+def ct_iadmm_geom_backward(ctx, n_view, opnorm, det_count, source_distance, det_distance, det_spacing, sigma_d, mu, tau, saved,
+                           grad_out, iter_num=None, ticket=0):
+    """pnpx_ct_iadmm_geom_backward -> (grad variables [B,3,R,R], grad sigma_d, grad mu, grad tau, each [B,T])."""
+    return _solver_backward(_CT_IADMM_GEOM, ctx, (n_view, opnorm, det_count, source_distance, det_distance, det_spacing),
+                            (sigma_d, mu, tau), saved, grad_out, iter_num, ticket)
+
+
+def ct_pg_geom(ctx, variables, y0, n_view, opnorm, det_count, source_distance, det_distance, det_spacing, sigma_d, tau, iter_num=None):
+    """pnpx_ct_pg_geom: PGSolver_CT.forward on a chosen geometry; det_count 0 = the parallel pair, the bytes of ct_pg."""
+    return _solver_forward(_CT_PG_GEOM, ctx, variables, (y0, n_view, opnorm, det_count, source_distance, det_distance, det_spacing),
+                           (sigma_d, tau), iter_num, False)
+
+
+def ct_pg_geom_train(ctx, variables, y0, n_view, opnorm, det_count, source_distance, det_distance, det_spacing, sigma_d, tau,
+                     iter_num=None):
+    """pnpx_ct_pg_geom_train -> (next x [B,1,R,R], saved [2*T*B*R*R], ticket)."""
+    return _solver_forward(_CT_PG_GEOM, ctx, variables, (y0, n_view, opnorm, det_count, source_distance, det_distance, det_spacing),
+                           (sigma_d, tau), iter_num, True)
+
+
+def ct_pg_geom_backward(ctx, n_view, opnorm, det_count, source_distance, det_distance, det_spacing, sigma_d, tau, saved, grad_out,
+                        iter_num=None, ticket=0):
+    """pnpx_ct_pg_geom_backward -> (grad x [B,1,R,R], grad sigma_d, grad tau, each [B,T])."""
+    return _solver_backward(_CT_PG_GEOM, ctx, (n_view, opnorm, det_count, source_distance, det_distance, det_spacing), (sigma_d, tau),
                             saved, grad_out, iter_num, ticket)
 
 

@@ -15,12 +15,20 @@ class CTMixin:
         return (state['y0'], state['view'])
 
 
-class IADMMSolver_CT(CTMixin, IADMMSolver):
-    """tasks/ct/solver.py:12-53"""
+def _geometry_args(radon):
+    """The geometry tail of the ct_*_geom / ct_hqs ops from a resolved projector pair."""
+    g = radon.geometry
+    return (g.det_count, g.source_distance, g.det_distance, g.det_spacing)
 
-    def __init__(self, denoiser):
+
+class IADMMSolver_CT(CTMixin, IADMMSolver):
+    """tasks/ct/solver.py:12-53.  geometry: None = the reference's parallel pair, or a utils.transforms.FanBeam (the reference's
+    solvers take none; the native loop is the same, on the fan pair)."""
+
+    def __init__(self, denoiser, geometry=None):
         super().__init__(denoiser)
         self.radon_generator = RadonGenerator()
+        self.geometry = geometry
 
     def forward(self, inputs, parameters, iter_num=None):
         variables, (y0, view) = inputs
@@ -29,29 +37,43 @@ class IADMMSolver_CT(CTMixin, IADMMSolver):
         # and the float32 round trip truncates many counts by one (50 -> 49, 100 -> 99), which torch_radon then rejects
         # with a shape error.  The sinogram itself carries the count, exactly and without a sync.
         n_view = int(y0.shape[2])
+        it = -1 if iter_num is None else iter_num
+        train = A.needs_grad(variables, sigma_d, mu, tau)      # training path: native forward + fused native VJP (tasks.hip)
+        if self.geometry is not None:
+            radon = self.radon_generator(variables.shape[-1], n_view, device=variables.device, geometry=self.geometry)
+            out = T.call("ct_iadmm_geom_train" if train else "ct_iadmm_geom", variables, y0, n_view, float(radon.opnorm),
+                         *_geometry_args(radon), sigma_d, mu, tau, it, self._ctx(variables).cid)
+            return out[0] if train else out
         radon = self.radon_generator(variables.shape[-1], n_view, device=variables.device)
-        if A.needs_grad(variables, sigma_d, mu, tau):      # training path: native forward + fused native VJP (tasks.hip)
-            return T.call("ct_iadmm_train", variables, y0, n_view, float(radon.opnorm), sigma_d, mu, tau,
-                          -1 if iter_num is None else iter_num, self._ctx(variables).cid)[0]
-        return T.call("ct_iadmm", variables, y0, n_view, float(radon.opnorm), sigma_d, mu, tau, -1 if iter_num is None else iter_num,
-                      self._ctx(variables).cid)
+        if train:
+            return T.call("ct_iadmm_train", variables, y0, n_view, float(radon.opnorm), sigma_d, mu, tau, it,
+                          self._ctx(variables).cid)[0]
+        return T.call("ct_iadmm", variables, y0, n_view, float(radon.opnorm), sigma_d, mu, tau, it, self._ctx(variables).cid)
+
 
 class PGSolver_CT(CTMixin, PGSolver):
-    """tasks/ct/solver.py:56-87"""
+    """tasks/ct/solver.py:56-87.  geometry: as for IADMMSolver_CT."""
 
-    def __init__(self, denoiser):
+    def __init__(self, denoiser, geometry=None):
         super().__init__(denoiser)
         self.radon_generator = RadonGenerator()
+        self.geometry = geometry
 
     def forward(self, inputs, parameters, iter_num=None):
         variables, (y0, view) = inputs
         sigma_d, tau = parameters
         n_view = int(y0.shape[2])                        # see IADMMSolver_CT.forward
+        it = -1 if iter_num is None else iter_num
+        train = A.needs_grad(variables, sigma_d, tau)      # training path: native forward + fused native VJP (tasks.hip)
+        if self.geometry is not None:
+            radon = self.radon_generator(variables.shape[-1], n_view, device=variables.device, geometry=self.geometry)
+            out = T.call("ct_pg_geom_train" if train else "ct_pg_geom", variables, y0, n_view, float(radon.opnorm),
+                         *_geometry_args(radon), sigma_d, tau, it, self._ctx(variables).cid)
+            return out[0] if train else out
         radon = self.radon_generator(variables.shape[-1], n_view, device=variables.device)
-        if A.needs_grad(variables, sigma_d, tau):          # training path: native forward + fused native VJP (tasks.hip)
-            return T.call("ct_pg_train", variables, y0, n_view, float(radon.opnorm), sigma_d, tau,
-                          -1 if iter_num is None else iter_num, self._ctx(variables).cid)[0]
-        return T.call("ct_pg", variables, y0, n_view, float(radon.opnorm), sigma_d, tau, -1 if iter_num is None else iter_num, self._ctx(variables).cid)
+        if train:
+            return T.call("ct_pg_train", variables, y0, n_view, float(radon.opnorm), sigma_d, tau, it, self._ctx(variables).cid)[0]
+        return T.call("ct_pg", variables, y0, n_view, float(radon.opnorm), sigma_d, tau, it, self._ctx(variables).cid)
 
 
 class HQSSolver_CT(CTMixin, HQSSolver):
@@ -83,7 +105,7 @@ _solver_map = {'iadmm': IADMMSolver_CT, 'pg': PGSolver_CT, 'hqs': HQSSolver_CT}
 def create_solver_ct(opt, denoiser):
     """tasks/ct/solver.py:95-103"""
     if opt.solver in _solver_map:
-        return _solver_map[opt.solver](denoiser)
+        return _solver_map[opt.solver](denoiser, getattr(opt, 'geometry', None))      # None, or a utils.transforms.FanBeam
     raise NotImplementedError
 
 

@@ -354,6 +354,29 @@ fan_backprojection.register_autograd(
                                                setattr(ctx, "geom", tuple(inputs[2:]))))
 
 
+# filtered backprojection: the start image of an episode is data, so neither op has an autograd formula
+@_lib_def("pnpx::radon_filter", mutates_args=(), device_types="cuda")
+def radon_filter(sino: Tensor, source_distance: float, det_distance: float, det_spacing: float) -> Tensor:
+    """The ramp filter along the detector axis (include/pnpx.h): source_distance 0 = the parallel beam's, else the fan beam's."""
+    return ops.radon_filter(sino, *((source_distance, det_distance, det_spacing) if source_distance else ()))
+
+
+@radon_filter.register_fake
+def _(sino, source_distance, det_distance, det_spacing):
+    return torch.empty_like(sino, memory_format=torch.contiguous_format)
+
+
+@_lib_def("pnpx::fan_fbp", mutates_args=(), device_types="cuda")
+def fan_fbp(sino: Tensor, R: int, source_distance: float, det_distance: float, det_spacing: float) -> Tensor:
+    """Fan-beam filtered backprojection: [B,1,n_view,det_count] -> [B,1,R,R]."""
+    return ops.fan_fbp(sino, R, source_distance, det_distance, det_spacing)
+
+
+@fan_fbp.register_fake
+def _(sino, R, source_distance, det_distance, det_spacing):
+    return torch.empty((sino.shape[0], 1, R, R), dtype=sino.dtype, device=sino.device)
+
+
 # ------------------------------------------------------------------------------------------------- solver loops
 # ------------------------------------------------------------------------------------------------- solver training ops
 def _solver_train_ops(name, aux, hypers, train_fn, backward_fn, saved_per_pixel, bwd_takes_aux=True):
@@ -464,6 +487,11 @@ _CT_GEOM_AUX = [("y0", "Tensor"), ("n_view", "int"), ("opnorm", "float"), ("det_
                 ("det_distance", "float"), ("det_spacing", "float")]         # det_count 0 = parallel beam
 ct_hqs_train, ct_hqs_backward = _solver_train_ops(
     "ct_hqs", _CT_GEOM_AUX, ("sigma_d", "mu"), ops.ct_hqs_train, ops.ct_hqs_backward, 3, bwd_takes_aux=False)
+ct_iadmm_geom_train, ct_iadmm_geom_backward = _solver_train_ops(
+    "ct_iadmm_geom", _CT_GEOM_AUX, ("sigma_d", "mu", "tau"), ops.ct_iadmm_geom_train, ops.ct_iadmm_geom_backward, 3,
+    bwd_takes_aux=False)
+ct_pg_geom_train, ct_pg_geom_backward = _solver_train_ops(
+    "ct_pg_geom", _CT_GEOM_AUX, ("sigma_d", "tau"), ops.ct_pg_geom_train, ops.ct_pg_geom_backward, 2, bwd_takes_aux=False)
 
 
 def _same(variables, *a):
@@ -592,6 +620,28 @@ def ct_hqs(variables: Tensor, y0: Tensor, n_view: int, opnorm: float, det_count:
 
 
 ct_hqs.register_fake(_same)
+
+
+@_lib_def("pnpx::ct_iadmm_geom", mutates_args=(), device_types="cuda")
+def ct_iadmm_geom(variables: Tensor, y0: Tensor, n_view: int, opnorm: float, det_count: int, source_distance: float,
+                  det_distance: float, det_spacing: float, sigma_d: Tensor, mu: Tensor, tau: Tensor, iter_num: int, ctx: int) -> Tensor:
+    """IADMMSolver_CT.forward on a chosen geometry: det_count 0 = parallel beam (ct_iadmm's bytes), else the fan geometry."""
+    return ops.ct_iadmm_geom(_ctx(ctx, variables), variables, y0, n_view, opnorm, det_count, source_distance, det_distance, det_spacing,
+                             sigma_d, mu, tau, _it(iter_num))
+
+
+ct_iadmm_geom.register_fake(_same)
+
+
+@_lib_def("pnpx::ct_pg_geom", mutates_args=(), device_types="cuda")
+def ct_pg_geom(variables: Tensor, y0: Tensor, n_view: int, opnorm: float, det_count: int, source_distance: float, det_distance: float,
+               det_spacing: float, sigma_d: Tensor, tau: Tensor, iter_num: int, ctx: int) -> Tensor:
+    """PGSolver_CT.forward on a chosen geometry: det_count 0 = parallel beam (ct_pg's bytes), else the fan geometry."""
+    return ops.ct_pg_geom(_ctx(ctx, variables), variables, y0, n_view, opnorm, det_count, source_distance, det_distance, det_spacing,
+                          sigma_d, tau, _it(iter_num))
+
+
+ct_pg_geom.register_fake(_same)
 
 # ------------------------------------------------------------------------------------------------- value network
 @_lib_def("pnpx::critic_value", mutates_args=(), device_types="cuda")
@@ -757,6 +807,8 @@ ALL_OPS = ("unet_denoise", "unet_denoise_preclamp", "unet_denoise_backward", "un
            "csmri_admm_backward", "csmri_hqs", "csmri_amp",
            "csmri_pg", "csmri_apg", "csmri_redadmm", "pr_iadmm", "spi_admm", "ct_iadmm", "ct_pg", "pr_pg",
            "fan_forward", "fan_backprojection", "ct_hqs", "ct_hqs_train", "ct_hqs_backward",
+           "radon_filter", "fan_fbp", "ct_iadmm_geom", "ct_iadmm_geom_train", "ct_iadmm_geom_backward", "ct_pg_geom",
+           "ct_pg_geom_train", "ct_pg_geom_backward",
            "spi_pg_step", "spi_pg", "spi_pg_train", "spi_pg_backward",
            "critic_value", "critic_backward", "critic_param_grad", "critic_value_loss_grad", "policy_ob_pack_diff", "policy_ob_unpack",
            "mddpg_policy_loss")

@@ -138,6 +138,8 @@ class Radon_norm:
         """transforms.py:479-481"""
         return self.backprojection(self.filter_sinogram(sinogram, filter_name='ramp'))
 
+    fbp = filter_backprojection      # one name for both geometries (FanBeam_norm.fbp)
+
 
 def ramp_filter(size):
     """Frequency response of the discrete ramp filter (Kak & Slaney eq. 61; the construction skimage / torch_radon
@@ -175,7 +177,9 @@ class FanBeam:
 
 class FanBeam_norm(Radon_norm):
     """Radon_norm's surface on a fan-beam pair: forward, the weighted backprojection, their normalised forms and the same seeded
-    ten-step power method for opnorm.  Fan-beam filtered backprojection is not provided."""
+    ten-step power method for opnorm.  Filtered backprojection is `fbp` (pnpx_fan_fbp: the cos gamma pre-weight, the ramp filter in
+    the detector domain and the (D_so / U)^2 backprojection; include/pnpx.h) and its filter alone `filter_fan`.  The parallel
+    beam's method names, filter_sinogram and filter_backprojection, keep raising here: they promise torch_radon's FFT filter."""
 
     def __init__(self, resolution, view, geometry, opnorm=None, device=None, seed=0):
         self.geometry = geometry.resolve(resolution, view)
@@ -191,10 +195,22 @@ class FanBeam_norm(Radon_norm):
 
     backward = backprojection
 
+    def filter_fan(self, sinogram):
+        """The pre-weighted, ramp-filtered and scaled sinogram that `fbp` backprojects."""
+        g = self.geometry
+        return T.call("radon_filter", sinogram, g.source_distance, g.det_distance, g.det_spacing)
+
+    def fbp(self, sinogram):
+        """Fan-beam filtered backprojection (Kak & Slaney section 3.4.2, full circle)."""
+        g = self.geometry
+        return T.call("fan_fbp", sinogram, int(self.resolution), g.source_distance, g.det_distance, g.det_spacing)
+
     def filter_sinogram(self, sinogram, filter_name='ramp'):
+        """Not the fan beam's filter: use filter_fan."""
         raise NotImplementedError("fan-beam filtered backprojection is not provided")
 
     def filter_backprojection(self, sinogram):
+        """Not the fan beam's reconstruction: use fbp."""
         raise NotImplementedError("fan-beam filtered backprojection is not provided")
 
 
